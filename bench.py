@@ -10,11 +10,15 @@ batch that is already resident in HBM.  Workload at N=1: BASELINE.json configs[1
 quadratic spline coupling, batch 16, 4096 target + 4096 context points).  For N > 1 every rank runs the same per-GPU batch on
 its own scenes (scenes are independent: no data-path collective; weak scaling); the global loss is one scalar all-reduce.
 
-Prints ONE JSON line on rank 0, with `roofline` (dominant kernel: a sample of its launches -- every n-th, about 32 per step --
-is bracketed by HIP events inside the library over the timed region; the other kernels are only bracketed in the last warmup step,
-which yields the `kernels` breakdown --
-bracketing every launch of the timed region costs 3 % of the throughput) and `cpu_baseline` (the pinned CPU oracle timed on the
-host cores on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps (in-library profiler off) and prints the headline
+line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...); `--dump-outputs DIR` also writes what the last timed
+step returned (`loss`, `log_prob`, `bpd` as float32 .npy).  `--full` adds what the headline does not need: `roofline` (dominant kernel:
+a sample of its launches -- every n-th, about 32 per step -- is bracketed by HIP events inside the library over the timed region; the
+other kernels are only bracketed in the last warmup step, which yields the `kernels` breakdown -- bracketing every launch of the timed
+region costs 3 % of the throughput), the `train` object (training step of the same workload) and `cpu_baseline` (the pinned CPU
+oracle timed on the host cores on a bounded sample of the same workload).
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 import argparse
 import contextlib
@@ -90,6 +94,22 @@ def init_rccl(dist, dev, **kw):
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_MAX_ELEMENTS = 1 << 24                               # --dump-outputs writes at most 64 MB of float32 in all
+
+
+def dump_outputs(d, **outputs):
+    """DIR/<name>.npy, float32, of each output.  One larger than its share of the 64 MB is written as a fixed sample: every n-th element of
+    the flattened array (the same elements on every run, so two builds compare element for element)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_MAX_ELEMENTS // len(outputs)
+    for name, t in outputs.items():
+        t = torch.as_tensor(t).detach().float()
+        if t.numel() > share:
+            t = t.reshape(-1)[::-(-t.numel() // share)]
+        np.save(os.path.join(d, name + ".npy"), t.cpu().numpy())
 
 
 def cpu_baseline(cfg, md, points, seed, sd=None):
@@ -333,12 +353,15 @@ def main():
                     help="time the TRAINING step instead (SURVEY.md 8f N1): forward + backward on the HIP training kernels, bucketed RCCL "
                          "gradient all-reduce overlapped with backward, clip_grad_norm_, Adam; embedder in train() mode.  Prints its own JSON line "
                          "(metric 'points/sec (training step ...)'); the default forward metric is BASELINE.json's")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the in-library HIP-event profile (`roofline`, `kernels`), the `train` object and the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, log_prob, bpd) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--train-steps", type=int, default=None,
-                    help="timed training steps of the `train` object that the default (forward) line carries: after the forward region, one warm-up + "
-                         "this many timed training steps of the same workload (0 = leave the object out).  Default: 2 on one GPU; 0 under "
-                         "torch.distributed.run with more than one rank -- the multi-rank RCCL gradient exchange has only ever run with one rank on "
-                         "hardware, and a crash there must not take the forward scaling line with it (`--train` or an explicit --train-steps measure it)")
+                    help="timed training steps of the `train` object that the forward line carries: after the forward region, one warm-up + "
+                         "this many timed training steps of the same workload (0 = leave the object out).  Default: 2 with --full, 0 without; "
+                         "with more than one rank the leg runs as a second, guarded phase in child processes")
     ap.add_argument("--sync-range-check", action="store_true",
                     help="diagnostic: the round-2 behaviour -- every forward call reads its fp16 range flag back (one stream synchronisation per call) "
                          "instead of the deferred check (fc_range_check_defer: K forwards queued back to back, flags read once at the end of the timed region)")
@@ -354,7 +377,8 @@ def main():
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.train_steps is None:
-        args.train_steps = 2                              # (with more than one rank the leg runs as a second, guarded phase in child processes: below)
+        args.train_steps = 2 if args.full else 0          # (with more than one rank the leg runs as a second, guarded phase in child processes: below)
+    profiling = args.full and not args.no_profile
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
@@ -424,7 +448,7 @@ def main():
     # bracketing all ~1000 launches of a step takes 3 % off the throughput being measured).
     warm_prof = []
     for i in range(args.warmup):
-        last = i == args.warmup - 1 and not args.no_profile
+        last = i == args.warmup - 1 and profiling
         if last:
             engine.profile_filter(None); engine.profile_reset(); engine.profile_enable(True)
         loss, lp, bpd = step()
@@ -442,7 +466,7 @@ def main():
     engine.profile_reset()
     engine.profile_filter(dominant)
     engine.profile_stride(stride)
-    engine.profile_enable(not args.no_profile)
+    engine.profile_enable(profiling)
     fb0 = fp16_fallbacks()
     if dist is not None:
         dist.barrier()
@@ -473,8 +497,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     mean_nats, bpd_f = float(-loss), float(bpd)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss=loss, log_prob=lp, bpd=bpd)
     sd = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # the weights the forward ran on (the training leg below updates them)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:      # the weights the forward ran on (the training leg below updates them)
         sd = ({k: v.detach().cpu().clone() for k, v in md["flow"].state_dict().items()},
               {k: v.detach().cpu().clone() for k, v in md["input_embedder"].state_dict().items()})
 
@@ -484,18 +510,6 @@ def main():
     elif rank == 0:
         total_pts = world * B * N * args.steps
         value = total_pts / dt
-        prof.sort(key=lambda p: -p["ms"])
-        dom = prof[0]                                       # live HIP-event timing of the dominant kernel over the timed region
-        breakdown, bsteps = (warm_prof, 1) if warm_prof else (prof, args.steps)      # all kernels: last warmup step
-        breakdown.sort(key=lambda p: -p["ms"])
-        tot_ms = sum(p["ms"] for p in breakdown) / bsteps * args.steps or 1.0
-        workload_key = f"{args.config} {B} x {N} + {M}" + (f" ({args.layers} layers)" if args.layers else "")
-        traffic, busy, why = pmc_tables(workload_key)
-        roof = roofline_of(dom, traffic, busy, why)
-        roof.update({"frac_note": "frac = algorithmic fp32-equivalent FLOPs (SURVEY.md 8d) / peak; frac_issued = MFMA FLOPs issued / the same peak (issue rate)",
-                     "launches_bracketed": f"every {stride}th launch of this kernel in the timed region" if stride > 1 else "all",
-                     "share_of_gpu_time": dom_warm["ms"] / sum(p["ms"] for p in warm_prof) if warm_prof else dom["ms"] / tot_ms,
-                     "flops_counted": "useful multiply-adds of the launches (padding excluded), HIP events on the launch stream"})
         alg = ALG_MFLOP_PER_POINT.get((args.config, N))
         out = {
             "metric": "nats/sec (forward log-prob) on 4096-pt coloured pairs", "value": value, "unit": "nats/sec",
@@ -509,13 +523,28 @@ def main():
             "range_check": "per call (stream synchronisation)" if args.sync_range_check else "deferred: flags of the K queued forwards read at the end of the timed region (fc_range_check_defer)",
             "job_algorithmic_tflops": None if alg is None or args.layers else alg * 1e6 * value / 1e12,
             "rccl": None if census is None else dict(census, backend="nccl (RCCL)", note="all_gather of every rank's device UUID / PCI address"),
-            "roofline": roof,
-            "kernels_source": "HIP events around every launch of the last warmup step" if warm_prof else "timed region",
-            # every kernel of a step with its own roofline entry (frac / frac_issued / traffic / matrix-pipe busy where a counter pass of this workload is committed)
-            "kernels": [dict(roofline_of(p, traffic, busy, why), ms_per_step=p["ms"] / bsteps, launches=p["launches"],
-                             tflops=(p["flops"] / (p["ms"] * 1e-3) / 1e12) if p["flops"] else None,
-                             gbs=(p["bytes"] / (p["ms"] * 1e-3) / 1e9) if p["bytes"] else None) for p in breakdown[:10]],
         }
+        if profiling:
+            prof.sort(key=lambda p: -p["ms"])
+            dom = prof[0]                                   # live HIP-event timing of the dominant kernel over the timed region
+            breakdown, bsteps = (warm_prof, 1) if warm_prof else (prof, args.steps)      # all kernels: last warmup step
+            breakdown.sort(key=lambda p: -p["ms"])
+            tot_ms = sum(p["ms"] for p in breakdown) / bsteps * args.steps or 1.0
+            workload_key = f"{args.config} {B} x {N} + {M}" + (f" ({args.layers} layers)" if args.layers else "")
+            traffic, busy, why = pmc_tables(workload_key)
+            roof = roofline_of(dom, traffic, busy, why)
+            roof.update({"frac_note": "frac = algorithmic fp32-equivalent FLOPs (SURVEY.md 8d) / peak; frac_issued = MFMA FLOPs issued / the same peak (issue rate)",
+                         "launches_bracketed": f"every {stride}th launch of this kernel in the timed region" if stride > 1 else "all",
+                         "share_of_gpu_time": dom_warm["ms"] / sum(p["ms"] for p in warm_prof) if warm_prof else dom["ms"] / tot_ms,
+                         "flops_counted": "useful multiply-adds of the launches (padding excluded), HIP events on the launch stream"})
+            out.update({
+                "roofline": roof,
+                "kernels_source": "HIP events around every launch of the last warmup step" if warm_prof else "timed region",
+                # every kernel of a step with its own roofline entry (frac / frac_issued / traffic / matrix-pipe busy where a counter pass of this workload is committed)
+                "kernels": [dict(roofline_of(p, traffic, busy, why), ms_per_step=p["ms"] / bsteps, launches=p["launches"],
+                                 tflops=(p["flops"] / (p["ms"] * 1e-3) / 1e12) if p["flops"] else None,
+                                 gbs=(p["bytes"] / (p["ms"] * 1e-3) / 1e9) if p["bytes"] else None) for p in breakdown[:10]],
+            })
 
     # `train` object: the training step of the same workload on the same clock (`bench.py --train` prints it as its own
     # line).  Every rank takes part; the forward numbers are complete before it starts and are printed even if the leg fails or hangs.
@@ -563,7 +592,7 @@ def main():
         if out is not None:
             out["train"] = train_obj
     if out is not None:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb, _ = cpu_baseline(cfg, md, args.cpu_points or N, 1000, sd)
             out["cpu_baseline"] = cb
             out["gpu_over_cpu"] = out["value"] / cb["value"]

@@ -6,7 +6,9 @@ import os
 import socket
 import sys
 
+import numpy as np
 import pytest
+import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
@@ -51,6 +53,19 @@ def test_kernel_peaks_by_symbol():
     assert (n, peak) == (1, 157.3)
     r = bench.roofline_of({"kernel": "void fc::attn16_kernel<64>(fc::Attn16Params)", "launches": 2, "ms": 1.0, "flops": 2.0e9, "bytes": 0.0}, {}, {}, "no pass")
     assert r["bound"] == "mfma" and abs(r["frac"] - r["achieved"] / 2500.0) < 1e-12 and abs(r["frac_issued"] - 3 * r["frac"]) < 1e-12 and r["traffic"] is None and r["traffic_note"] == "no pass"
+
+
+def test_dump_outputs_float32_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output, shapes kept; an output beyond its share of the budget becomes the same strided sample on
+    every call (here with a budget of 64 elements in place of 64 MB)."""
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMENTS", 64)
+    lp = torch.arange(2 * 50, dtype=torch.float32).reshape(2, 50)
+    bench.dump_outputs(str(tmp_path / "d"), loss=-lp.mean(), log_prob=lp, bpd=torch.tensor(1.5, dtype=torch.float64))
+    loss, got, bpd = (np.load(tmp_path / "d" / f"{n}.npy") for n in ("loss", "log_prob", "bpd"))
+    assert loss.dtype == got.dtype == bpd.dtype == np.float32 and loss.shape == bpd.shape == () and float(bpd) == 1.5
+    assert got.size <= 64 // 3 and np.array_equal(got, lp.reshape(-1)[::5].numpy())
+    bench.dump_outputs(str(tmp_path / "d"), log_prob=lp[:, :10])
+    assert np.array_equal(np.load(tmp_path / "d" / "log_prob.npy"), lp[:, :10].numpy())
 
 
 def _census_worker(rank, world, port, idents, q):

@@ -336,6 +336,15 @@ void launch_spline(const float* params, int ldp, float* xbuf, int ldx, int x2_co
 void launch_ldj_reduce(const float* part, int ntiles, size_t pitch, float* logprob, int rows, hipStream_t s);   // params[row, p*d2s + j] = parameter p of dim j
 void launch_expm_coupling(const float* params, int ldp, float* xbuf, int ldx, int x2_col0, int d2, const float* scal4, float* logprob,
                           int rows, int inverse, hipStream_t s);
+// ExponentialCoupling for 17 <= d2 <= 256 (expm_wide.hip): one workgroup per point, the action e^(+-W) x2 by Al-Mohy & Higham's truncated
+// Taylor method; ldj_mode 0 = none, 1 = ldj[row] = tr W, 2 = ldj[row] += tr W; y2 may alias x2, its columns [d2, ypad) are zeroed; *status
+// raised (outputs NaN) for a point
+// whose ||W - mu I||_1 needs more than kExpmWideMaxSteps Taylor steps; info (optional) [rows][4] = {||W - mu I||_1, s, m, products}
+constexpr int kExpmSmallMaxD2 = 16;       // d2 <= 16: the one-lane-per-point kernel of misc.hip (launch_expm_coupling)
+constexpr int kExpmWideMaxD2 = 256;
+constexpr int kExpmWideMaxSteps = 40;     // ||W - mu I||_1 <= 40 theta_55 = 534
+void launch_expm_wide(const float* params, int ldp, const float* x2, int ldx, const float* scal4, float* y2, int ldy, int ypad, float* ldj,
+                      int ldj_mode, int rows, int d2, int inverse, int* status, float* info, hipStream_t s);
 void launch_spline_flat(const float* x, const float* params, float* y, float* lad, int64_t n, int K, int inverse, hipStream_t s);
 void launch_knn(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm = nullptr);
 void launch_gather_max(const float* uv, int lduv, int c_out, const int32_t* idx, int k, float* out, int ldo, int out_col0,

@@ -80,6 +80,7 @@ struct Dims {
 
 struct fc_flow {
     int* fp16_flag = nullptr;   // device word raised by the split-fp16 GEMM loop on an activation >= 65504 (common.h: Fp16Guard)
+    int* expm_status = nullptr; // device word raised by the wide ExponentialCoupling kernel on a matrix beyond its bound (expm_wide.hip)
     fc_flow_config cfg;
     fc::Dims d;
     fc::DeviceArena arena;
@@ -470,8 +471,9 @@ static void build_flow(fc_flow& f, const WeightTable& wt) {
         h_pad = std::max(h_pad, max_hidden_pad(b.net));
         if (c.flow_type != FC_FLOW_AFFINE) ldp = b.net.out_layer.N_pad;
         if (c.flow_type == FC_FLOW_EXPONENTIAL) {
-            if (d.d2 > 16)       // the permanent cap of include/fcflow.h (enum fc_flow_type): refused at create, not at the first forward
-                throw Error(FC_ERR_UNSUPPORTED, "ExponentialCoupling: latent_dim - latent_dim/2 > 16 is not supported (the layer emits d2^2 numbers per point)");
+            if (d.d2 > kExpmWideMaxD2)   // the cap of include/fcflow.h (enum fc_flow_type): refused at create, not at the first forward
+                throw Error(FC_ERR_UNSUPPORTED, "ExponentialCoupling: latent_dim - latent_dim/2 > 256 is not supported (the matrix-exponential action "
+                                                "kernel holds at most a 256 x 256 matrix per point)");
             const std::string pt = p + ".transform";
             std::vector<float> sc = {wt.get(pt + ".scale", {1}).data[0], wt.get(pt + ".shift", {1}).data[0],
                                      wt.get(pt + ".rescale", {1}).data[0], wt.get(pt + ".reshift", {1}).data[0]};
@@ -526,6 +528,7 @@ struct FlowWs {
     float* lnss;           // [A_in / 64][P_pad] per-row sums of squares of the centred pre-MLP output (LayerNorm -> q fold)
     unsigned short* h16;   // fp16 limb image of the last hidden activation feeding the spline parameter GEMM (limb chain)
     int P, P_pad, Pc, Pc_pad, ldkv;
+    int spl_rows;          // rows of w.spl: P_pad, or the row chunk of the wide ExponentialCoupling (expm_chunk_rows)
 };
 // Log-det partial slots (rows of FlowWs::ldjp): one per 128-column tile of the fused spline epilogue, two (one per wave column)
 // per 128-column tile of a pair-packed epilogue (affine coupling, augmenter, CIF slice) on the 8-wave split-fp16 tile.  The
@@ -540,6 +543,17 @@ static int ldj_slot_count(const fc_flow& f) {
         if (b.has_cif) { pair(b.cif.dist.out_layer); pair(b.cif.aff.out_layer); }
     }
     return n;
+}
+
+// ExponentialCoupling with d2 > 16 emits d2^2 + d2 parameters per point (90.6 KB at d2 = 150): the out-layer GEMM and the expm kernel run
+// chunk by chunk over row blocks whose parameter panel stays within kExpmChunkBytes (2048 rows at d2 = 150), so the panel does not grow with
+// B x N and a chunk's panel can be read back from the 256 MiB Infinity Cache.
+constexpr size_t kExpmChunkBytes = 192ull << 20;
+static bool expm_wide(const fc_flow& f) { return f.cfg.flow_type == FC_FLOW_EXPONENTIAL && f.d.d2 > kExpmSmallMaxD2; }
+static int expm_chunk_rows(const fc_flow& f, int P_pad) {
+    const size_t per = (size_t)f.d.ldp * sizeof(float);
+    const int c = std::max(ROW_PAD, (int)(kExpmChunkBytes / per) / ROW_PAD * ROW_PAD);
+    return std::min(c, P_pad);
 }
 
 static FlowWs plan_ws(const fc_flow& f, int B, int N, int M, void* ws, size_t bytes, bool dry, size_t* need) {
@@ -558,7 +572,8 @@ static FlowWs plan_ws(const fc_flow& f, int B, int N, int M, void* ws, size_t by
     w.kv = c.floats((size_t)w.Pc_pad * std::max(w.ldkv, 32));
     w.xin = c.floats((size_t)w.P_pad * 32);
     w.rowscal = c.floats((size_t)w.P_pad);
-    w.spl = c.floats(d.ldp ? (size_t)w.P_pad * d.ldp : 1);
+    w.spl_rows = expm_wide(f) ? expm_chunk_rows(f, w.P_pad) : w.P_pad;
+    w.spl = c.floats(d.ldp ? (size_t)w.spl_rows * d.ldp : 1);
     w.cbuf = c.floats(d.nz > 0 ? (size_t)w.P_pad * d.nz_pad : 1);
     w.ldj_slots = ldj_slot_count(f);
     w.ldjp = c.floats(std::max<size_t>((size_t)w.ldj_slots * w.P_pad, 1));
@@ -572,6 +587,9 @@ static FlowWs plan_ws(const fc_flow& f, int B, int N, int M, void* ws, size_t by
 thread_local float* t_flow_trace = nullptr;
 thread_local size_t t_flow_trace_floats = 0;
 void flow_set_trace(float* buf, size_t floats) { t_flow_trace = buf; t_flow_trace_floats = floats; }
+thread_local float* t_expm_info = nullptr;      // fc_debug_expm_info: per-point statistics of the wide ExponentialCoupling kernel
+thread_local size_t t_expm_info_floats = 0;
+void flow_set_expm_info(float* buf, size_t floats) { t_expm_info = buf; t_expm_info_floats = floats; }
 
 int g_premlp_chain = 0;      // knob 19: limb chain through the pre-attention MLP into the LayerNorm -> q GEMM (K = 256: 8 k-tiles per
                              // output tile, the tile-boundary cost of the DMA loop outweighs its main loop: measured 1 % slower end to end)
@@ -708,6 +726,20 @@ static void run_coupling(fc_flow& f, const BlockPack& b, FlowWs& w, float* xc, c
         e.ldj_part = w.ldjp; e.ldj_pitch = (size_t)w.P_pad;
         if (chain) { e.A16 = w.h16; e.a16_scale = wide ? kOneAccActScale : 0.f; }
         launch_gemm(b.net.out_layer, &a, w.P_pad, e, EPI_SPLINE, s);       // log-dets accumulate in w.ldjp; flow_forward reduces them once
+    } else if (expm_wide(f)) {
+        // parameter panel in row chunks: out-layer GEMM of the chunk into w.spl, then the matrix-exponential action of its points
+        for (int r0 = 0; r0 < w.P; r0 += w.spl_rows) {
+            const int rows_alloc = std::min(w.spl_rows, w.P_pad - r0);
+            GemmEpi e{};
+            e.C = w.spl; e.ldc = d.ldp; e.rows_valid = std::min(rows_alloc, w.P - r0);
+            ASeg ac{a.ptr + (size_t)r0 * a.lda, a.lda};
+            launch_gemm(b.net.out_layer, &ac, rows_alloc, e, EPI_LINEAR, s);
+            float* x2 = xc + (size_t)r0 * d.ldx + d.d1_pad;
+            float* info = t_expm_info && trace_layer >= 0 && (size_t)(trace_layer + 1) * w.P * 4 <= t_expm_info_floats
+                              ? t_expm_info + ((size_t)trace_layer * w.P + r0) * 4 : nullptr;
+            launch_expm_wide(w.spl, d.ldp, x2, d.ldx, b.expm_scal, x2, d.ldx, d.d2, inverse ? nullptr : logprob + r0, inverse ? 0 : 2, e.rows_valid, d.d2,
+                             inverse, f.expm_status, info, s);
+        }
     } else {
         GemmEpi e{};
         e.C = w.spl; e.ldc = d.ldp; e.rows_valid = w.P;
@@ -791,6 +823,7 @@ static void flow_forward(fc_flow& f, const float* x, const float* ctx, const flo
     Prep pr = prepare(f, ctx, extra, B, N, M, ws, ws_bytes, s);
     FlowWs& w = pr.w;
     const int ldh = std::max(d.H_pad, 32);
+    if (f.expm_status) FC_HIP(hipMemsetAsync(f.expm_status, 0, sizeof(int), s));
     int eps_i = 0;
 
     launch_fill(logprob, 0.f, (size_t)w.P, s);
@@ -874,6 +907,7 @@ static void flow_inverse(fc_flow& f, const float* z, const float* ctx, const flo
         }
     Prep pr = prepare(f, ctx, extra, B, N, M, ws, ws_bytes, s);
     FlowWs& w = pr.w;
+    if (f.expm_status) FC_HIP(hipMemsetAsync(f.expm_status, 0, sizeof(int), s));
     float* xc = w.xa;
     float* xn = w.xb;
     launch_fill(xc, 0.f, (size_t)w.P_pad * d.ldx, s);
@@ -902,6 +936,17 @@ static void flow_inverse(fc_flow& f, const float* z, const float* ctx, const flo
     const int n1 = std::min(d.Din, d.d1);
     launch_pack_rows(xc, d.ldx, n1, x_out, d.Din, 0, n1, w.P, s);
     if (d.Din > n1) launch_pack_rows(xc + d.d1_pad, d.ldx, d.Din - n1, x_out, d.Din, n1, d.Din - n1, w.P, s);
+}
+
+// the wide ExponentialCoupling kernel's status word, read back after a pass (a synchronisation, paid by those flows only): a point whose
+// matrix exceeds the kernel's bound fails the call instead of returning a truncated series
+static void check_expm_status(const fc_flow& f, hipStream_t s) {
+    if (!f.expm_status) return;
+    int h = 0;
+    FC_HIP(hipMemcpyAsync(&h, f.expm_status, sizeof(int), hipMemcpyDeviceToHost, s));
+    FC_HIP(hipStreamSynchronize(s));
+    if (h) throw Error(FC_ERR_UNSUPPORTED, "ExponentialCoupling: a coupling matrix norm ||W - mu I||_1 exceeds the matrix-exponential kernel's bound "
+                                           "(40 Taylor steps, 534): the result would be a truncated series");
 }
 
 }  // namespace fc
@@ -936,6 +981,7 @@ int fc_flow_create(const fc_flow_config* cfg, const fc_tensor* tensors, int32_t 
     fc::WeightTable wt(tensors, n_tensors);
     fc::build_flow(*f, wt);
     f->fp16_flag = (int*)f->arena.alloc_floats(1);
+    if (fc::expm_wide(*f)) f->expm_status = (int*)f->arena.alloc_floats(1);
     FC_HIP(hipDeviceSynchronize());
     *out = f.release();
     FC_API_END
@@ -967,6 +1013,7 @@ int fc_flow_logprob_f32(fc_flow* flow, const float* x, const float* ctx, const f
     fc::run_fp16_guarded(flow->fp16_flag, (hipStream_t)stream, [=] {
         fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, z_out, B, N, M, workspace, workspace_bytes, (hipStream_t)stream);
     }, true);
+    fc::check_expm_status(*flow, (hipStream_t)stream);
     FC_API_END
 }
 
@@ -975,6 +1022,7 @@ int fc_flow_inverse_f32(fc_flow* flow, const float* z, const float* ctx, const f
     FC_API_BEGIN
     if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_flow_inverse_f32: null flow / workspace");
     fc::flow_inverse(*flow, z, ctx, extra, eps, n_eps, x_out, B, N, M, workspace, workspace_bytes, (hipStream_t)stream);
+    fc::check_expm_status(*flow, (hipStream_t)stream);
     FC_API_END
 }
 

@@ -17,7 +17,7 @@ struct TmpBuf {
 }  // namespace fc
 
 
-namespace fc { void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t); long gemm_fp16_fallbacks(); extern int g_train_wgrad16; extern int g_train_attn16; extern int g_gemm_dma; extern int g_spline_ablate; extern int g_gemm_dma_linear; extern int g_limb_chain_all; extern int g_gemm_prefetch3; extern int g_premlp_chain; extern int g_gemm_stamp; extern int g_gemm_small_tiles; extern int g_spline_prefetch; extern int g_mlp_rows; extern int g_knn_mfma; extern int g_premlp_lu; extern int g_spline_wide_dma; extern int g_spline_wide_colgroup; extern int g_linear_wide; extern int g_knn_warm; size_t gemm_read_stamps(unsigned long long*, size_t); void flow_set_trace(float*, size_t); }
+namespace fc { void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t); long gemm_fp16_fallbacks(); extern int g_train_wgrad16; extern int g_train_attn16; extern int g_gemm_dma; extern int g_spline_ablate; extern int g_gemm_dma_linear; extern int g_limb_chain_all; extern int g_gemm_prefetch3; extern int g_premlp_chain; extern int g_gemm_stamp; extern int g_gemm_small_tiles; extern int g_spline_prefetch; extern int g_mlp_rows; extern int g_knn_mfma; extern int g_premlp_lu; extern int g_spline_wide_dma; extern int g_spline_wide_colgroup; extern int g_linear_wide; extern int g_knn_warm; size_t gemm_read_stamps(unsigned long long*, size_t); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t); }
 namespace fc { extern int g_gemm_variant, g_gemm_colgroup, g_gemm_bigtile, g_attn_fp16, g_fused_spline, g_premlp_fused, g_limb_chain, g_lnq_fold; }
 
 extern "C" {
@@ -99,6 +99,13 @@ int32_t fc_range_check_pending(void) { return fc::guard_pending(); }
    [n_flow_layers][B * N][d2] (flow_engine.cpp flow_set_trace); NULL switches it off.  Test infrastructure, not part of fcflow.h. */
 int fc_debug_flow_trace(float* device_buf, int64_t capacity_floats) {
     fc::flow_set_trace(device_buf, device_buf && capacity_floats > 0 ? (size_t)capacity_floats : 0);
+    return FC_OK;
+}
+
+/* diagnostic: while set, the wide ExponentialCoupling kernel of a forward pass writes {||W - mu I||_1, s, m, products} of every point of
+ * layer l to device_buf[(l * rows + row) * 4 ...] (profiles: the norms and product counts a run saw) */
+int fc_debug_expm_info(float* device_buf, int64_t capacity_floats) {
+    fc::flow_set_expm_info(device_buf, device_buf && capacity_floats > 0 ? (size_t)capacity_floats : 0);
     return FC_OK;
 }
 
@@ -280,6 +287,24 @@ int fc_change_map_f32(float* lp10, int32_t N, float* lp00, int32_t N0, float* ou
     FC_HIP(hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
     FC_HIP(hipStreamSynchronize((hipStream_t)stream));
     *invalid = h;
+    FC_API_END
+}
+
+int fc_op_expm_action_f32(const float* params, int32_t ldp, const float* x2, int32_t ldx, const float* scal4, float* y2, int32_t ldy, float* ldj,
+                          float* info, int32_t rows, int32_t d2, int32_t inverse, void* stream) {
+    FC_API_BEGIN
+    if (!params || !x2 || !scal4 || !y2 || rows < 1 || d2 < 1 || ldx < d2 || ldy < d2) throw fc::Error(FC_ERR_INVALID, "fc_op_expm_action_f32: bad argument");
+    if (d2 <= fc::kExpmSmallMaxD2) throw fc::Error(FC_ERR_INVALID, "fc_op_expm_action_f32: d2 <= 16 runs on the one-lane-per-point kernel of the engine");
+    fc::TmpBuf tmp(sizeof(int));
+    int* status = (int*)tmp.p;
+    hipStream_t s = (hipStream_t)stream;
+    FC_HIP(hipMemsetAsync(status, 0, sizeof(int), s));
+    fc::launch_expm_wide(params, ldp, x2, ldx, scal4, y2, ldy, d2, ldj, ldj ? 1 : 0, rows, d2, inverse, status, info, s);
+    int h = 0;
+    FC_HIP(hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, s));
+    FC_HIP(hipStreamSynchronize(s));
+    if (h) throw fc::Error(FC_ERR_UNSUPPORTED, "ExponentialCoupling: a coupling matrix norm ||W - mu I||_1 exceeds the matrix-exponential kernel's bound "
+                                               "(40 Taylor steps, 534): the result would be a truncated series");
     FC_API_END
 }
 

@@ -675,9 +675,13 @@ int fc_train_normlp_bwd_f32(const float* v, int32_t ldv, const float* p, int32_t
 int fc_train_expm_fwd_f32(const float* x2, int32_t ldx, const float* o, int32_t ldo, const float* scal4, float* y2, int32_t ldy, float* ldj, int32_t rows,
                           int32_t d2, int32_t* status, void* stream) {
     FC_API_BEGIN
-    if (!x2 || !o || !scal4 || !y2 || !ldj || !status || rows < 1 || d2 < 1 || d2 > EX_D || ldx < d2 || ldo < d2 * d2 + d2 || ldy < round_up(d2, 32))
-        throw Error(FC_ERR_INVALID, "fc_train_expm_fwd_f32: bad argument (d2 <= 16)");
+    if (!x2 || !o || !scal4 || !y2 || !ldj || !status || rows < 1 || d2 < 1 || d2 > kExpmWideMaxD2 || ldx < d2 || ldo < d2 * d2 + d2 || ldy < round_up(d2, 32))
+        throw Error(FC_ERR_INVALID, "fc_train_expm_fwd_f32: bad argument (d2 <= 256)");
     hipStream_t s = (hipStream_t)stream;
+    if (d2 > EX_D) {      // the inference engine's matrix-exponential action kernel (expm_wide.hip); its bound raises the same status word
+        launch_expm_wide(o, ldo, x2, ldx, scal4, y2, ldy, round_up(d2, 32), ldj, 1, rows, d2, 0, (int*)status, nullptr, s);
+        return FC_OK;
+    }
     ProfScope ps("fc::expm_train_fwd_kernel", 0.0, 0.0, s);
     hipLaunchKernelGGL(expm_train_fwd_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, x2, ldx, o, ldo, scal4, y2, ldy, ldj, rows, d2, round_up(d2, 32), (int*)status);
     FC_HIP(hipGetLastError());

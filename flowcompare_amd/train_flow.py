@@ -13,7 +13,8 @@ What runs where
 
 Covered: AugmentAttentionPreconditioner or IdentityTransform; PreConditionApplier with the attention or the global-context
 pre-conditioner; CIFblock (augment / affine_cif / ActNorm / Slice around the coupling); RationalQuadraticSplineCoupling,
-AffineCoupling or ExponentialCoupling (latent_dim - latent_dim // 2 <= 16, as in the inference engine); ActNormBijectionCloud incl. its
+AffineCoupling or ExponentialCoupling (backward: latent_dim - latent_dim // 2 <= 16; forward, e.g. condition_flow or ActNorm's data init,
+up to 256 as in the inference engine); ActNormBijectionCloud incl. its
 first-batch init; LinearLU, random_permute, FullCombiner, ExponentialCombiner; extra context.
 """
 import math

@@ -726,9 +726,13 @@ def edge_bn_max(pq, bn, idx, rows, C, k):
     return EdgeBNMaxFn.apply(pq, bn.weight, bn.bias, idx, rows, C, k, bn)
 
 
+EXPM_TRAIN_BWD_MAX_D2 = 16       # fc_train_expm_bwd_f32 (one lane per point); the forward runs up to d2 = 256
+
+
 class ExpmCouplingFn(torch.autograd.Function):
     """ExponentialCoupling element (models/exponential_coupling.py:44-58): x2 panel, o panel [d2*d2 raw matrix | d2 shift], scal4 =
-    cat(scale, shift, rescale, reshift) -> (y2 panel, ldj).  d2 <= 16 (the layer emits d2^2 numbers per point)."""
+    cat(scale, shift, rescale, reshift) -> (y2 panel, ldj).  Forward d2 <= 256 (d2 > 16 on the inference engine's matrix-exponential action
+    kernel, csrc/expm_wide.hip), backward d2 <= 16 (the layer emits d2^2 numbers per point)."""
 
     @staticmethod
     def forward(ctx, x2, o, scal4, rows, d2):
@@ -743,6 +747,9 @@ class ExpmCouplingFn(torch.autograd.Function):
             engine._check(L.fc_train_expm_fwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(y2), y2.shape[1],
                                                   engine._ptr(ldj), rows, d2, engine._ptr(status), engine._stream()))
         if int(status.item()):
+            if d2 > EXPM_TRAIN_BWD_MAX_D2:
+                raise RuntimeError("ExponentialCoupling (training forward): a coupling matrix norm ||W - mu I||_1 exceeds the matrix-exponential "
+                                   "kernel's bound (40 Taylor steps, 534)")
             raise RuntimeError("ExponentialCoupling (training): a matrix norm exceeds 2^5; the backward keeps at most 64 squaring states")
         ctx.save_for_backward(x2, o, s4)
         ctx.meta = (rows, d2, scal4.dtype)
@@ -750,9 +757,11 @@ class ExpmCouplingFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy2, dldj):
+        rows, d2, sdtype = ctx.meta
+        if d2 > EXPM_TRAIN_BWD_MAX_D2:
+            raise RuntimeError(f"ExponentialCoupling training backward supports d2 <= {EXPM_TRAIN_BWD_MAX_D2} (this flow has d2 = {d2})")
         L = engine.lib()
         x2, o, s4 = ctx.saved_tensors
-        rows, d2, sdtype = ctx.meta
         dy2, dldj = dy2.contiguous(), dldj.contiguous()
         dx2 = _panel_out(x2.shape[0], x2.shape[1], rows, x2.device) if x2.shape[1] == _round_up(d2, 32) else torch.zeros_like(x2)
         do = _panel_out(o.shape[0], o.shape[1], rows, x2.device) if o.shape[1] == _round_up(d2 * d2 + d2, 32) else torch.zeros_like(o)

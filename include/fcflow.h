@@ -22,6 +22,7 @@
  *     (fc_train_sqnorm_f32, fc_train_adam_f32);
  * 5 = + the deferred range check (fc_range_check_defer / _resolve / _pending);
  * 6 = + fc_profile_stride (sampled bracketing of the in-library kernel timing), fc_train_linear_act_fwd_f32 / fc_train_linear_dgrad_act_f32 (activation and its backward in the GEMM epilogues).
+ * 8 = + fc_op_expm_action_f32; ExponentialCoupling up to d2 = 256 (inference, training forward).
  */
 #ifndef FCFLOW_H
 #define FCFLOW_H
@@ -33,7 +34,7 @@
 extern "C" {
 #endif
 
-#define FC_ABI_VERSION 7
+#define FC_ABI_VERSION 8
 
 enum fc_status {
     FC_OK = 0,
@@ -53,11 +54,13 @@ typedef struct fc_tensor {
     int64_t shape[4];
 } fc_tensor;
 
-/* FC_FLOW_EXPONENTIAL (models/exponential_coupling.py:44-58) -- PERMANENT CAP: latent_dim - latent_dim / 2 <= 16, inference and training alike
- * (fc_flow_create returns FC_ERR_UNSUPPORTED beyond it).  The layer's coupling net emits d2 * d2 + d2 numbers per point (a dense matrix per
- * point): at the reference's latent width of 300 that is 22 650 outputs and 90 KB of matrix per point and layer, which the reference itself
- * never runs (no shipped configuration selects this flow_type; its own smoke configurations use single-digit latents).  The per-point
- * matrix exponential therefore lives in one lane's registers (csrc/misc.hip expm_coupling_kernel) and is not tiled. */
+/* FC_FLOW_EXPONENTIAL (models/exponential_coupling.py:44-58): d2 = latent_dim - latent_dim / 2 <= 256 for inference (fc_flow_logprob_f32,
+ * fc_flow_inverse_f32; fc_flow_create returns FC_ERR_UNSUPPORTED beyond it).  The coupling net emits d2 * d2 + d2 numbers per point (a dense
+ * matrix per point; 22 650 at the reference's latent width 300).  d2 <= 16: one lane per point (csrc/misc.hip expm_coupling_kernel);
+ * 17 <= d2 <= 256: one workgroup per point holds the matrix in registers and applies its exponential to the vector (csrc/expm_wide.hip),
+ * on row chunks of the parameter panel.  A point whose ||W - mu I||_1 exceeds 534 (40 Taylor steps) makes the call fail with
+ * FC_ERR_UNSUPPORTED instead of returning a truncated series.  Training: forward (fc_train_expm_fwd_f32) up to d2 = 256, backward
+ * (fc_train_expm_bwd_f32) d2 <= 16. */
 enum fc_flow_type { FC_FLOW_AFFINE = 0, FC_FLOW_SPLINE = 1, FC_FLOW_EXPONENTIAL = 2 };
 enum fc_scale_fn { FC_SCALE_EXP = 0, FC_SCALE_SIGMOID = 1 };
 enum fc_act { FC_ACT_NONE = 0, FC_ACT_GELU = 1, FC_ACT_RELU = 2, FC_ACT_ELU = 3, FC_ACT_LRELU02 = 4 };
@@ -233,6 +236,14 @@ int fc_op_knn_f32(const float* f, int32_t* idx, int32_t B, int32_t M, int32_t C,
  * best from below, so the stream skips everything under that bound; the returned set is the exact top-k whatever idx_warm holds.  ABI v7. */
 int fc_op_knn_warm_f32(const float* f, const int32_t* idx_warm, int32_t* idx, int32_t B, int32_t M, int32_t C, int32_t k, void* stream);
 
+/* ExponentialCoupling element for 17 <= d2 <= 256 (models/exponential_coupling.py:44-75, the engine's wide kernel): per row, params =
+ * [d2*d2 raw matrix (row-major) | d2 shift b] of pitch ldp, scal4 = device (scale, shift, rescale, reshift),
+ * W = rescale tanh(scale raw + shift) + reshift + 1e-8; forward y2 = expm(W) x2 + b, inverse y2 = expm(-W)(x2 - b).  ldj (may be NULL)
+ * [rows] = tr W.  info (may be NULL) [rows][4] = {||W - mu I||_1 (mu = tr(+-W)/d2), Taylor steps s, degree m, matrix-vector products}.
+ * y2 may equal x2.  Returns FC_ERR_UNSUPPORTED when a row's norm exceeds the kernel's bound (40 Taylor steps); synchronises the stream. */
+int fc_op_expm_action_f32(const float* params, int32_t ldp, const float* x2, int32_t ldx, const float* scal4, float* y2, int32_t ldy, float* ldj,
+                          float* info, int32_t rows, int32_t d2, int32_t inverse, void* stream);
+
 /* Elementwise rational-quadratic spline with linear tails (models/spline_coupling.py:24-169).
  * x [n], params [n, 3K+1] laid out [K widths | K heights | K+1 derivatives] -> y [n], logabsdet [n]. */
 int fc_op_rqspline_f32(const float* x, const float* params, float* y, float* logabsdet,
@@ -321,8 +332,10 @@ int fc_train_normlp_fwd_f32(const float* v, int32_t ldv, const float* p, int32_t
 int fc_train_normlp_bwd_f32(const float* v, int32_t ldv, const float* p, int32_t ldp, const float* g, float* dv, int32_t lddv, float* dp, int32_t lddp,
                             int32_t rows, int32_t nz, float clamp, void* stream);
 /* ExponentialCoupling element (models/exponential_coupling.py:44-58): o = [d2*d2 raw matrix | d2 shift] per point, scal4 = device
- * (scale, shift, rescale, reshift); y2 = expm(rescale tanh(scale raw + shift) + reshift + 1e-8) x2 + b, ldj = trace.  d2 <= 16.
- * status (device int32): set when a matrix norm exceeds the 64 squarings the backward keeps states for.
+ * (scale, shift, rescale, reshift); y2 = expm(rescale tanh(scale raw + shift) + reshift + 1e-8) x2 + b, ldj = trace.  fwd: d2 <= 256
+ * (d2 > 16 on the wide kernel of fc_op_expm_action_f32), bwd: d2 <= 16.
+ * status (device int32): set when a matrix norm exceeds the 64 squarings the backward keeps states for (d2 <= 16), or the wide kernel's
+ * bound (d2 > 16, 40 Taylor steps).
  * bwd: dscal [rows, 4] = per-point parts of the four scalars' gradients (column sums = the gradients). */
 int fc_train_expm_fwd_f32(const float* x2, int32_t ldx, const float* o, int32_t ldo, const float* scal4, float* y2, int32_t ldy, float* ldj, int32_t rows,
                           int32_t d2, int32_t* status, void* stream);

@@ -185,16 +185,8 @@ struct GemmEpi {
 // the calling thread: the scope hands the kernels a device flag they raise on such a value, and the entry point that opened the
 // scope repeats its whole computation with the bf16-limb loop (unbounded range) when the flag came back set.  Outside a scope
 // launch_gemm always takes the bf16-limb loop.
-// Kernel variants that lost a same-box A/B are compiled only with -DFC_DEV_VARIANTS (`python -m flowcompare_amd.build --dev`):
-// the default library holds, per role, the shipped kernel, the bf16-limb range fallback and ONE fp32-input reference loop.  In a default build
-// fc_debug_set refuses the knob values that would select a developer variant.
-#ifdef FC_DEV_VARIANTS
-#define FC_DEV(...) __VA_ARGS__
-constexpr bool kDevVariants = true;
-#else
-#define FC_DEV(...)
-constexpr bool kDevVariants = false;
-#endif
+// The library holds, per role, the shipped kernel, the bf16-limb range fallback and ONE fp32-input reference loop; the variants that lost a
+// same-box A/B were removed (DESIGN.md section 6 keeps their measurements, git history their code).
 
 // One-time setup per (call site, device) -- hipFuncSetAttribute for > 64 KB of dynamic LDS, the CU count behind a persistent grid: a process
 // may drive several devices and pack from a pool of host threads, so a process-wide `static bool done` is not enough.

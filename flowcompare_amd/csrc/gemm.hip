@@ -3,12 +3,16 @@
 //   C[rows, N_pad] = epilogue( sum_seg A_seg[rows, k_seg] @ W[N_pad, K_pad]^T )
 //
 // Every Linear of the flow (coupling MLPs, q/kv projections, the folded ActNorm+LinearLU matrix, DGCNN / PAConv 1x1
-// convolutions) goes through gemm_f32_kernel; operands and results are fp32 in memory, the products run in one of three
+// convolutions) goes through gemm_f32_kernel; operands and results are fp32 in memory, the products run in one of the
 // main loops selected by the template parameter VAR:
 //   VAR 5  split-fp16, the default: each operand as two fp16 limbs (hi + lo'/2048, 2^-24 relative), 3 v_mfma_f32_32x32x16_f16
 //          per product block, main and cross-product fp32 accumulators; needs the caller's Fp16Guard scope (|x| < 65504);
 //   VAR 3  split-bf16: three bf16 limbs, 6 MFMAs per block, unbounded range -- the pass a guarded call is repeated with;
-//   VAR 0-2 fp32-input MFMA (v_mfma_f32_32x32x2_f32, an exact fmaf chain): the first build's loop, kept for A/B and tests.
+//   VAR 2  fp32-input MFMA (v_mfma_f32_32x32x2_f32, an exact fmaf chain): the first build's loop, kept for A/B and tests;
+//   VAR 9  split-fp16 with A as the limb image its producer wrote (limb-chained layers): both operands reach LDS by DMA;
+//   VAR 11 the fused spline layer (K = 8) as a persistent transposed LDS-DMA GEMM, splines evaluated from the accumulators.
+// (The numbers of the variants that lost an A/B and were removed -- 0, 1, 6, 7, 8, 10 -- are not reused: profiles and DESIGN.md
+// section 6 quote kernels by their template arguments.)
 // Epilogues (EPI): LINEAR (bias, rank-1 extra-context term, residual, activation), SPLINE (forward rational-quadratic spline
 // coupling on the tile the workgroup just produced), AFFINE / AUGMENT / SLICE (pair-packed [first 32 | second 32] columns).
 //
@@ -118,7 +122,7 @@ void gemm_f32_kernel(const GemmParams p) {
     int nvalid = (p.N_pad - wave_n0) / 32;                 // wave-uniform number of live 32-col tiles (for the stores only:
     nvalid = nvalid < 0 ? 0 : (nvalid > TN ? TN : nvalid); // W / bias are allocated zero-padded to the grid, the k-loop is branch free)
     const GemmEpi& e = p.e;
-    if constexpr (VAR == 8 || VAR == 9 || VAR == 10) {
+    if constexpr (VAR == 9) {
         if (p.stamps && threadIdx.x == 0) {
             p.stamps[(size_t)blockIdx.x * 16 + 7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
             p.stamps[(size_t)blockIdx.x * 16 + 8] = wall_clock64();
@@ -136,16 +140,7 @@ void gemm_f32_kernel(const GemmParams p) {
     constexpr int SPL_PER_THREAD = EPI == EPI_SPLINE ? (BM * 5 + NT - 1) / NT : 1;      // (K = 8: 5 dims per 128-column tile; K = 4 / 16 re-load below)
     float spl_x[SPL_PER_THREAD];
     float spl_ldj = 0.f;
-    if constexpr (EPI == EPI_SPLINE && VAR == 10) {
-        // transposed product (below): this lane evaluates dims 2 lh, 2 lh + 1 (and, lower half, dim 4) of ONE point
-        const int row = m0 + wave * 32 + li, dim0 = bn * 5;
-        const float* xr = e.xbuf + (size_t)row * e.ldx + e.x2_col0 + dim0;
-        const bool rv = row < e.rows_valid;
-        spl_x[0] = rv && dim0 + 2 * lh < e.d2 ? xr[2 * lh] : 0.f;
-        spl_x[1] = rv && dim0 + 2 * lh + 1 < e.d2 ? xr[2 * lh + 1] : 0.f;
-        spl_x[2] = rv && dim0 + 4 < e.d2 ? xr[4] : 0.f;
-        if (lh == 0) spl_ldj = e.ldj_part[(size_t)bn * e.ldj_pitch + row];
-    } else if constexpr (EPI == EPI_SPLINE) {
+    if constexpr (EPI == EPI_SPLINE) {
         const int per = 3 * e.spline_K + 1, DPT = BN / per, dim0 = bn * DPT;
 #pragma unroll
         for (int k = 0; k < SPL_PER_THREAD; ++k) {
@@ -156,16 +151,6 @@ void gemm_f32_kernel(const GemmParams p) {
         if (tid < BM) spl_ldj = e.ldj_part[(size_t)bn * e.ldj_pitch + m0 + tid];
     }
     floatx16 acc[TM][TN];
-    if constexpr (VAR == 10) {
-        // transposed product: the accumulator's ROW index (register r, lane half) walks the tile's columns, so the bias varies per register
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 b4 = *reinterpret_cast<const float4*>(p.bias + n0 + j * 32 + 8 * g + 4 * lh);      // (the launcher requires a bias)
-                acc[0][j][4 * g + 0] = b4.x; acc[0][j][4 * g + 1] = b4.y; acc[0][j][4 * g + 2] = b4.z; acc[0][j][4 * g + 3] = b4.w;
-            }
-    } else
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         float bv = 0.f;
@@ -230,43 +215,34 @@ void gemm_f32_kernel(const GemmParams p) {
         }
     }
 
-    if constexpr (VAR == 8 || VAR == 9 || VAR == 10) {
+    if constexpr (VAR == 9) {
         // ================= split-fp16 main loop on LDS-DMA: BOTH operands arrive as fp16 limb images =================
         // A is the image its producer's epilogue wrote (e.A16, [rows][K/16][hi 16 | lo' 16]), W the host-packed one (p.W2): the main
         // loop converts nothing, so global -> LDS is a byte copy and goes through `global_load_lds_dwordx4` (no staging VGPRs, no
-        // ds_write, whose VGPR -> LDS path was half busy in the register-staged loop).  256 x 128 tile on eight waves of 64 x 64 (128
-        // accumulator registers: main + cross-product sets), two waves per SIMD, one workgroup per CU; k tile 32 = two 64-byte
-        // (row, k16) blocks = 128 bytes per LDS row; three LDS stages of 48 KB; ONE raw s_barrier per k tile with a counted vmcnt
-        // wait, so the DMA of tile t+1 stays in flight across the barrier while tile t is multiplied and tile t+2 is issued.
+        // ds_write, whose VGPR -> LDS path was half busy in the register-staged loop).  128 x 128 tile on FOUR waves of 64 x 64 (128
+        // accumulator registers: main + cross-product sets); k tile 32 = two 64-byte (row, k16) blocks = 128 bytes per LDS row; TWO LDS
+        // stages of 32 KB, so that two workgroups fit a CU (2 x 64 KB of stages / 2 x 69 KB with the spline epilogue's parameter tile;
+        // 2 waves per SIMD): one workgroup's epilogue then overlaps the other's main loop; ONE raw s_barrier per k tile.
         //   LDS image: row r = 128 bytes = 8 chunks of 16 B; logical chunk c = 4*(k16 block) + 2*limb + (k half) sits at physical
         //   chunk c ^ ((r >> 1) & 7): with 128-byte rows two rows share a 256-byte bank row, and ds_read_b128's 16-lane groups
         //   ({0-3,12-15,20-27}, ...) then hit 16 distinct 16-byte slots.  The DMA writes LDS linearly (wave base + lane * 16), so the
         //   permutation is applied to the per-lane SOURCE address and again on the read (same involution on both sides).
-        // VAR 9: the same loop on a 128 x 128 tile with FOUR waves of 64 x 64 and TWO LDS stages of 32 KB, so that two workgroups fit a
-        // CU (2 x 64 KB of stages / 2 x 69 KB with the spline epilogue's parameter tile; 2 waves per SIMD): one workgroup's epilogue
-        // then overlaps the other's main loop, which the one-workgroup-per-CU 256-row tile cannot do.
-        // VAR 10 (fused spline layer): the VAR 9 tile with its four waves stacked along the rows (32 points x 128 columns each) and the
-        // MFMA operands SWAPPED -- weights as the A operand, points as B -- so the accumulator holds, per lane, 64 parameters of ONE
-        // point (the other 64 sit in lane ^ 32).  With the column order of spline.h that is every parameter of 2-3 transformed dims in
-        // registers with compile-time indices: the spline is evaluated straight from the accumulators, the tile never goes through LDS
-        // (no 66 KB parameter tile, no transposition, no epilogue barrier).
-        static_assert((BN == 128 && ((VAR == 8 && BM == 256 && WM == 4 && WN == 2) || (VAR == 9 && BM == 128 && WM == 2 && WN == 2) ||
-                                     (VAR == 10 && BM == 128 && WM == 4 && WN == 1 && EPI == EPI_SPLINE))) ||
-                          (VAR == 9 && BM == 64 && BN == 64 && WM == 2 && ((WN == 2 && EPI == EPI_LINEAR) || (WN == 1 && EPI == EPI_AFFINE))),
-                      "LDS-DMA loop: 256x128 on 4x2 waves (VAR 8), 128x128 on 2x2 waves (VAR 9) or on 4x1 waves, transposed (VAR 10); 64x64 on 2x2 "
-                      "waves (EPI_LINEAR) / 2x1 waves (EPI_AFFINE: a wave's 64 columns are one pair block) for launches too small to fill the chip with 128x128 tiles");
+        static_assert((BN == 128 && BM == 128 && WM == 2 && WN == 2) ||
+                          (BM == 64 && BN == 64 && WM == 2 && ((WN == 2 && EPI == EPI_LINEAR) || (WN == 1 && EPI == EPI_AFFINE))),
+                      "LDS-DMA loop: 128x128 on 2x2 waves; 64x64 on 2x2 waves (EPI_LINEAR) / 2x1 waves (EPI_AFFINE: a wave's 64 columns are one "
+                      "pair block) for launches too small to fill the chip with 128x128 tiles");
         // 64 x 64 tiles (launches too small to fill the chip: ONE workgroup's k loop is the launch's duration, and with 6 MFMAs per wave and
         // k step that loop is pure DMA latency): EIGHT stages of 16 KB, seven k steps in flight, so the whole K = 512 operand is on its way
         // after one latency instead of one latency per k step (C1: 19 -> ~10 us per hidden-layer launch).  Same MFMAs in the same order.
-        constexpr int NST8 = VAR == 8 ? 3 : (BM == 64 ? 8 : 2);
+        constexpr int NST8 = BM == 64 ? 8 : 2;
         constexpr int ROWB8 = 128, STAGE8 = (BM + BN) * ROWB8;        // launch_cfg reserves NST8 * STAGE8
-        constexpr int PPW = STAGE8 / 1024 / (NT / 64);                       // 1-KB DMA pieces per wave and stage: 6
+        constexpr int PPW = STAGE8 / 1024 / (NT / 64);                       // 1-KB DMA pieces per wave and stage: 8 on the 128 x 128 tile
         typedef __attribute__((address_space(3))) char lds_char;
         typedef const __attribute__((address_space(1))) char glb_char;
         char* smc = reinterpret_cast<char*>(smem);
         const int KT = p.KT;                                                // k32 tiles
         const size_t rowbytes = (size_t)KT * 128;
-        // piece pc = wave * PPW + i covers stage rows 8 pc .. 8 pc + 7 (rows 0..255: A, 256..383: W); lane l: row 8 pc + (l >> 3), physical chunk l & 7
+        // piece pc = wave * PPW + i covers stage rows 8 pc .. 8 pc + 7 (rows 0..BM-1: A, then W); lane l: row 8 pc + (l >> 3), physical chunk l & 7
         const char* gsrc[PPW];
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
@@ -305,15 +281,9 @@ void gemm_f32_kernel(const GemmParams p) {
                 }                                                                                                  \
                 _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                     \
                     _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                               \
-                        if constexpr (VAR == 10) {                                                                 \
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf8[j][0], af8[i][0], acc[i][j], 0, 0, 0);   \
-                            corr[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf8[j][1], af8[i][0], corr[i][j], 0, 0, 0); \
-                            corr[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf8[j][0], af8[i][1], corr[i][j], 0, 0, 0); \
-                        } else {                                                                                   \
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af8[i][0], bf8[j][0], acc[i][j], 0, 0, 0);     /* hi * hi */  \
                         corr[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af8[i][0], bf8[j][1], corr[i][j], 0, 0, 0);   /* hi * lo' */ \
                         corr[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af8[i][1], bf8[j][0], corr[i][j], 0, 0, 0);   /* lo' * hi */ \
-                        }                                                                                          \
                     }                                                                                              \
             }                                                                                                      \
         }
@@ -332,19 +302,6 @@ void gemm_f32_kernel(const GemmParams p) {
                 FC_MMA8_STAGE(st)
                 st = st == NST8 - 1 ? 0 : st + 1;
             }
-        } else if constexpr (NST8 == 3) {
-            FC_DMA8(0, 0)
-            FC_DMA8((1 < KT ? 1 : KT - 1), 1)
-            int st = 0;
-            for (int kt = 0; kt < KT; ++kt) {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");      // this wave's pieces of tile kt have landed (tile kt+1 may fly on)
-                __builtin_amdgcn_s_barrier();                                   // ... and everybody's; everybody is done reading tile kt-1
-                const int kn = kt + 2 < KT ? kt + 2 : KT - 1;                   // (tail: harmless re-loads into a stage nobody reads again)
-                const int sn = st >= 1 ? st - 1 : 2;                            // (kt + 2) % 3
-                FC_DMA8(kn, sn)
-                FC_MMA8_STAGE(st)
-                st = st == 2 ? 0 : st + 1;
-            }
         } else {
             // two stages: tile kt+1 is in flight while tile kt is multiplied (issued right behind the barrier that frees its stage)
             FC_DMA8(0, 0)
@@ -361,7 +318,7 @@ void gemm_f32_kernel(const GemmParams p) {
         }
 #undef FC_MMA8_STAGE
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // the tail's re-loads: nothing may land in LDS once the epilogue owns it
-        if constexpr (VAR != 10) __syncthreads();                           // (VAR 10's epilogue stays in registers: its waves finish independently)
+        __syncthreads();
         FC_STAMP(3)
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -386,8 +343,7 @@ void gemm_f32_kernel(const GemmParams p) {
         // (5.3x the fp32-input matrix rate), 4 bytes per LDS element instead of 6.  fp16 overflows at 65504: every staged |x| is
         // max-reduced and a launch that met one >= 65504 raises *p.ovf; the entry point then repeats the whole call with the
         // bf16 limbs (unbounded range).  Weights with such entries never get an fp16 image (PackedLinear.W2 == nullptr).
-        constexpr bool F16 = VAR >= 5;
-        constexpr bool ALIMB = VAR == 7;                           // A arrives as the fp16 limb image its producer wrote (e.A16): plain copy
+        constexpr bool F16 = VAR == 5;
         constexpr int KS = 16;                                      // k extent of one LDS stage (32 with one-deep prefetch measured 13 % slower)
         constexpr int KSUB = KS / 16, U = 32 / KS;
         constexpr int NL = F16 ? 2 : 3;                             // limbs
@@ -409,12 +365,9 @@ void gemm_f32_kernel(const GemmParams p) {
         float amax = 0.f;
         // two register sets: the tile loaded in iteration kt is only converted/stored in iteration kt+1, so a global load has a
         // whole iteration (the MFMAs of the other resident waves included) to land before anything waits for it
-        float4 ra3_0[A3], ra3_1[A3], ra3_2[A3];            // (set 2: VAR 6 only, dead otherwise)
-        constexpr int A4N = (BM * CH + NT - 1) / NT;                // 16-byte chunks of the A limb image per thread and stage
-        typedef unsigned int u32xa __attribute__((ext_vector_type(4 * A4N)));
-        u32xa ra4_0, ra4_1, ra4_2;
+        float4 ra3_0[A3], ra3_1[A3];
         typedef unsigned int u32xw __attribute__((ext_vector_type(4 * W3N)));      // whole-vector values: never an alloca, so never scratch
-        u32xw rw3_0, rw3_1, rw3_2;
+        u32xw rw3_0, rw3_1;
 #define FC_GLOAD3(S_, KT_)                                                                                           \
         {                                                                                                          \
             const float* Ap_ = p.A[0];                                                                             \
@@ -423,18 +376,8 @@ void gemm_f32_kernel(const GemmParams p) {
                 kk_ -= U * p.kt[0]; Ap_ = p.A[1]; lda_ = p.lda[1];                                                 \
                 if (kk_ >= U * p.kt[1]) { kk_ -= U * p.kt[1]; Ap_ = p.A[2]; lda_ = p.lda[2]; }                     \
             }                                                                                                      \
-            if constexpr (ALIMB) {                                                                                 \
-                _Pragma("unroll") for (int i = 0; i < A4N; ++i) {                                                  \
-                    int c_ = tid + NT * i;                                                                         \
-                    c_ = c_ < BM * CH ? c_ : BM * CH - 1;                                                          \
-                    const int slot_ = c_ / CH, part_ = c_ - slot_ * CH, row_ = FC_WROW(slot_);                     \
-                    const uint4 t_ = *reinterpret_cast<const uint4*>(e.A16 + ((size_t)(m0 + row_) * KT16 + (KT_)) * (NL * 16) + part_ * 8); \
-                    ra4_##S_[4 * i] = t_.x; ra4_##S_[4 * i + 1] = t_.y; ra4_##S_[4 * i + 2] = t_.z; ra4_##S_[4 * i + 3] = t_.w; \
-                }                                                                                                  \
-            } else {                                                                                               \
-                const float* a_ = Ap_ + (size_t)(m0 + lrow3) * lda_ + kk_ * KS + lc3;                              \
-                _Pragma("unroll") for (int i = 0; i < A3; ++i) ra3_##S_[i] = *reinterpret_cast<const float4*>(a_ + (size_t)(RPP3 * i) * lda_); \
-            }                                                                                                      \
+            const float* a_ = Ap_ + (size_t)(m0 + lrow3) * lda_ + kk_ * KS + lc3;                                  \
+            _Pragma("unroll") for (int i = 0; i < A3; ++i) ra3_##S_[i] = *reinterpret_cast<const float4*>(a_ + (size_t)(RPP3 * i) * lda_); \
             _Pragma("unroll") for (int i = 0; i < W3N; ++i) {                                                      \
                 int c_ = tid + NT * i;                                                                             \
                 c_ = c_ < BN * CH ? c_ : BN * CH - 1;     /* unconditional load (a guarded one sends the staging registers through scratch) */ \
@@ -446,16 +389,8 @@ void gemm_f32_kernel(const GemmParams p) {
         }
 #define FC_LSTORE3(S_, ST_)                                                                                          \
         {                                                                                                          \
-            if constexpr (ALIMB) {                                                                                 \
-                _Pragma("unroll") for (int i = 0; i < A4N; ++i) {                                                  \
-                    const int c_ = tid + NT * i, slot_ = c_ / CH, part_ = c_ - slot_ * CH, row_ = FC_WROW(slot_);  \
-                    if (BM * CH % NT == 0 || c_ < BM * CH)                                                         \
-                        *reinterpret_cast<uint4*>(smc + (ST_) * STAGE3 + row_ * ROWB + part_ * 16) =               \
-                            make_uint4(ra4_##S_[4 * i], ra4_##S_[4 * i + 1], ra4_##S_[4 * i + 2], ra4_##S_[4 * i + 3]); \
-                }                                                                                                  \
-            }                                                                                                      \
             char* sa_ = smc + (ST_) * STAGE3 + lrow3 * ROWB + (tid % TPR) * 8;                                      \
-            _Pragma("unroll") for (int i = 0; i < (ALIMB ? 0 : A3); ++i) {                                         \
+            _Pragma("unroll") for (int i = 0; i < A3; ++i) {                                                       \
                 const float x_[4] = {ra3_##S_[i].x, ra3_##S_[i].y, ra3_##S_[i].z, ra3_##S_[i].w};                  \
                 if constexpr (F16) {                                                                               \
                     amax = fmaxf(fmaxf(amax, fmaxf(fabsf(x_[0]), fabsf(x_[1]))), fmaxf(fabsf(x_[2]), fabsf(x_[3])));  \
@@ -527,40 +462,6 @@ void gemm_f32_kernel(const GemmParams p) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) corr[i][j][r] = 0.f;
         }
-        if constexpr (VAR == 6) {
-            // THREE register sets: a tile's global loads are issued three stages before its MFMAs (two in registers, one in LDS).  The
-            // Linear launches of the flow stream their A operand from HBM / Infinity Cache once (no column-tile reuse to speak of at
-            // N <= 512), 64 KB in flight per CU did not cover that latency (SQ_WAIT_ANY 43 % of the wave cycles at 25 % matrix-pipe busy).
-            // LDS stays double-buffered: stage (kt + 1) & 1 was last read in iteration kt - 1, one barrier back.
-            FC_GLOAD3(0, 0)
-            FC_GLOAD3(1, (1 < KT16 ? 1 : KT16 - 1))
-            FC_GLOAD3(2, (2 < KT16 ? 2 : KT16 - 1))
-            FC_LSTORE3(0, 0)
-            __syncthreads();
-            int par = 0;
-            for (int kt = 0; kt < KT16; kt += 3) {
-                const int k3 = kt + 3 < KT16 ? kt + 3 : KT16 - 1, k4 = kt + 4 < KT16 ? kt + 4 : KT16 - 1, k5 = kt + 5 < KT16 ? kt + 5 : KT16 - 1;
-                FC_GLOAD3(0, k3)
-                FC_MMA3(par)
-                FC_LSTORE3(1, (par ^ 1))
-                __syncthreads();
-                par ^= 1;
-                if (kt + 1 < KT16) {
-                    FC_GLOAD3(1, k4)
-                    FC_MMA3(par)
-                    FC_LSTORE3(2, (par ^ 1))
-                    __syncthreads();
-                    par ^= 1;
-                }
-                if (kt + 2 < KT16) {
-                    FC_GLOAD3(2, k5)
-                    FC_MMA3(par)
-                    FC_LSTORE3(0, (par ^ 1))
-                    __syncthreads();
-                    par ^= 1;
-                }
-            }
-        } else {
         // KT16 is even (K_pad is a multiple of 32).  Stage s of LDS holds tile kt (s = kt & 1); register set s holds tile kt+1 ... kt+2.
         FC_GLOAD3(0, 0)
         FC_LSTORE3(0, 0)
@@ -576,7 +477,6 @@ void gemm_f32_kernel(const GemmParams p) {
             FC_MMA3(1)
             FC_LSTORE3(0, 0)
             __syncthreads();
-        }
         }
         if constexpr (F16) {
 #pragma unroll
@@ -644,7 +544,7 @@ void gemm_f32_kernel(const GemmParams p) {
                 for (int i = 0; i < TM; ++i) af[nb][i] = *reinterpret_cast<const float4*>(sA + i * 32 * LDS_LD + 8 * (g + 1));
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bf[nb][j] = *reinterpret_cast<const float4*>(sB + j * 32 * LDS_LD + 8 * (g + 1));
-            } else if (VAR == 2) {
+            } else {
                 FC_LSTORE((kt + 1) & 1)                     // next tile's LDS image is written under the last group's MFMAs
             }
 #pragma unroll
@@ -658,7 +558,6 @@ void gemm_f32_kernel(const GemmParams p) {
                 }
             }
         }
-        if (VAR != 2) FC_LSTORE((kt + 1) & 1)
         __syncthreads();
     }
 #undef FC_GLOAD
@@ -669,7 +568,7 @@ void gemm_f32_kernel(const GemmParams p) {
     // ------------------------------------------------------------------ epilogues
     // C/D layout of the 32x32 MFMA: column = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5), r = 0..15
     if constexpr (EPI == EPI_LINEAR) {
-        if ((VAR == 8 || VAR == 9) && e.inverse == 2) return;        // (diagnostic knob 14 = 2: main loop only, results invalid)
+        if (VAR == 9 && e.inverse == 2) return;        // (diagnostic knob 14 = 2: main loop only, results invalid)
         if constexpr (RES_EARLY) {
             if (e.residual16 && nvalid > 0) {
 #pragma unroll
@@ -789,7 +688,7 @@ void gemm_f32_kernel(const GemmParams p) {
             default: by_fmt(std::integral_constant<int, FC_ACT_NONE>{}); break;
         }
         if (omax >= 65504.0f) atomicOr(p.ovf, 1);                 // (omax stays 0 without a limb-image output)
-        if constexpr (VAR == 8 || VAR == 9) {
+        if constexpr (VAR == 9) {
             FC_STAMP(6)
             if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 16 + 9] = wall_clock64();
         }
@@ -815,44 +714,6 @@ void gemm_f32_kernel(const GemmParams p) {
                     for (int r = 0; r < 16; ++r)
                         e.C[(size_t)(wave_m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * e.ldc + (wave_n0 - e.d2) + j * 32 + li] = acc[i][j][r];
         }
-    } else if constexpr (EPI == EPI_SPLINE && VAR == 10) {
-        // ---- fused rational-quadratic spline coupling evaluated from the accumulator registers (transposed product, K = 8).
-        //      Slot s = 16 j + r of this lane is tile column spline_slot_col(s, lh): slots 0..24 / 25..49 are dims 2 lh / 2 lh + 1,
-        //      slots 50.. of the lower half are parameters 0..13 of dim 4, slots 50..60 of the upper half its parameters 14..24.
-        if (e.inverse == 2) return;                                  // (diagnostic knob 14: main loop only)
-        auto P = [&](int s) -> float { return acc[0][s >> 4][s & 15]; };
-        float t4[11];
-#pragma unroll
-        for (int i = 0; i < 11; ++i) {
-            t4[i] = upper_to_lower(acc[0][3][2 + i]);                 // slot 50 + i
-        }
-        FC_STAMP(4)
-        const int row = m0 + wave * 32 + li, dim0 = bn * 5;
-        const bool rv = row < e.rows_valid;
-        const bool vA = rv && dim0 + 2 * lh < e.d2, vB = rv && dim0 + 2 * lh + 1 < e.d2, vC = rv && lh == 0 && dim0 + 4 < e.d2;
-        float yA, yB, yC, lA, lB, lC;
-        if (e.inverse == 1) {                                        // (diagnostic knob 14 = 1: no spline evaluation)
-            yA = spl_x[0] + P(0); lA = P(1); yB = spl_x[1] + P(25); lB = P(26); yC = spl_x[2] + P(50); lC = P(51);
-        } else {
-            rq_spline_fwd_regs<8>(spl_x[0], [&](int q) { return P(q); }, yA, lA);
-            rq_spline_fwd_regs<8>(spl_x[1], [&](int q) { return P(25 + q); }, yB, lB);
-            rq_spline_fwd_regs<8>(spl_x[2], [&](int q) { return q < 14 ? P(50 + q) : t4[q - 14]; }, yC, lC);
-        }
-        FC_STAMP(5)
-        float* xr = e.xbuf + (size_t)row * e.ldx + e.x2_col0 + dim0;
-        if (vA) xr[2 * lh] = yA;
-        if (vB) xr[2 * lh + 1] = yB;
-        if (vC) xr[4] = yC;
-        lA = vA ? lA : 0.f; lB = vB ? lB : 0.f; lC = vC ? lC : 0.f;
-        // log-dets of dims 2, 3 cross to the lower half; summed in dim order like the LDS-tile epilogues (bit-identical slot values)
-        const float l2 = upper_to_lower(lA), l3 = upper_to_lower(lB);
-        if (lh == 0) {
-            float sum = 0.f;
-            sum += lA; sum += lB; sum += l2; sum += l3; sum += lC;
-            e.ldj_part[(size_t)bn * e.ldj_pitch + row] = spl_ldj + sum;
-        }
-        FC_STAMP(6)
-        if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 16 + 9] = wall_clock64();
     } else if constexpr (EPI == EPI_SPLINE) {
         // ---- fused rational-quadratic spline coupling (forward).  The parameter layer's columns are laid out so that this
         //      128-column tile holds all 3K+1 parameters of DPT transformed dims (spline.h): the tile goes through LDS (the
@@ -876,7 +737,7 @@ void gemm_f32_kernel(const GemmParams p) {
                     tile[(wr * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * TP + tpos[j]] = acc[i][j][r];
         } else { asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[TM - 1][TN - 1][15])); }
         __syncthreads();
-        if constexpr (VAR == 8 || VAR == 9) FC_STAMP(4)
+        if constexpr (VAR == 9) FC_STAMP(4)
         if (e.inverse == 5) return;                                  // (diagnostic knob 14 = 5: main loop + parameter-tile write + barrier)
         const int K = e.spline_K, per = 3 * K + 1, DPT = BN / per;
         const int dim0 = bn * DPT;
@@ -909,14 +770,14 @@ void gemm_f32_kernel(const GemmParams p) {
                 part[dl * BM + row] = lad;
             }
         }
-        if constexpr (VAR == 8 || VAR == 9) FC_STAMP(5)
+        if constexpr (VAR == 9) FC_STAMP(5)
         __syncthreads();
         if (tid < BM) {
             float sum = 0.f;
             for (int dl = 0; dl < DPT; ++dl) sum += part[dl * BM + tid];
             e.ldj_part[(size_t)bn * e.ldj_pitch + m0 + tid] = spl_ldj + sum;      // this (tile, row) slot has one owner per launch: reproducible
         }
-        if constexpr (VAR == 8 || VAR == 9) {
+        if constexpr (VAR == 9) {
             FC_STAMP(6)
             if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 16 + 9] = wall_clock64();
         }
@@ -1016,10 +877,14 @@ void gemm_f32_kernel(const GemmParams p) {
 }
 
 // ===================================================================================================================================
-// VAR 11: the fused spline layer as a PERSISTENT transposed LDS-DMA GEMM (K = 8 bins).  Same tile, operands, MFMA order and register
-// epilogue as VAR 10 (bit-identical results); what changes is the tile boundary, which the in-kernel stamps (knob 20,
-// profiles/micro/spline_gemm_stamps.py) priced at 6.5 of a workgroup's 25.5 us per tile: 2.6 us from entry until the first k tile has
-// landed, 0.8 us between a workgroup's exit and its successor's entry, 3.1 us of epilogue during which the slot fetches nothing.
+// VAR 11: the fused spline layer as a PERSISTENT transposed LDS-DMA GEMM (K = 8 bins).  The tile is 128 x 128 on four waves stacked along
+// the rows (32 points x 128 columns each) with the MFMA operands SWAPPED -- weights as the A operand, points as B -- so the accumulator
+// holds, per lane, 64 parameters of ONE point (the other 64 sit in lane ^ 32).  With the column order of spline.h that is every parameter
+// of 2-3 transformed dims in registers with compile-time indices: the spline is evaluated straight from the accumulators, the tile never
+// goes through LDS (no 66 KB parameter tile, no transposition, no epilogue barrier).  Persistent because with one tile per workgroup the
+// tile boundary is expensive: the in-kernel stamps (knob 20, profiles/micro/spline_gemm_stamps.py) priced it at 6.5 of a workgroup's 25.5 us
+// per tile: 2.6 us from entry until the first k tile has landed, 0.8 us between a workgroup's exit and its successor's entry, 3.1 us of
+// epilogue during which the slot fetches nothing.
 //   * grid = 2 workgroups per CU, each walks tiles t = blockIdx.x, + gridDim.x, ... (the XCD-aware order of the one-tile-per-workgroup
 //     launch: gridDim.x is a multiple of 8, so a workgroup's tiles stay on its XCD's band);
 //   * ONE continuous DMA stream: behind the barrier of a tile's LAST k step the workgroup issues the NEXT tile's first k step into the
@@ -1137,7 +1002,7 @@ __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, floa
     // them at once, and a miss holds back the hits queued behind it in the CU's in-order return path (PMC: 92 % L2 hits, yet the texture
     // data unit waits on the cache a third of the time and a DMA issued a whole k step earlier still kept its wave waiting).  A tile
     // therefore starts its k loop at step rot(column tile) and wraps around: the sharers are spread over the panel's k range, each k
-    // step is missed by one of them and hit by the others.  fp32 accumulation order changes with it (not bit-identical to VAR 9 / 10).
+    // step is missed by one of them and hit by the others.  fp32 accumulation order changes with it (not bit-identical to VAR 9).
     const bool rotate = e.prefetch_dist != 0;
     auto rot_of = [&](int bm_, int bn_) -> int { return rotate ? (int)(((unsigned)(bn_ % 10) * 3u + (unsigned)(bm_ & 15) * 5u) % (unsigned)KT) : 0; };
     for (;;) {
@@ -1200,7 +1065,8 @@ __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, floa
             st ^= 1;
         }
         FC_PSTAMP(3)
-        // ---- epilogue in registers (see VAR 10 in gemm_f32_kernel): slot s = 16 j + r of this lane is tile column spline_slot_col(s, lh)
+        // ---- epilogue in registers: slot s = 16 j + r of this lane is tile column spline_slot_col(s, lh): slots 0..24 / 25..49 are dims
+        //      2 lh / 2 lh + 1, slots 50.. of the lower half are parameters 0..13 of dim 4, slots 50..60 of the upper half its parameters 14..24
         if (e.inverse != 2) {                                           // (diagnostic knob 14 = 2: main loop only)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -1254,8 +1120,8 @@ void gemm_f32_kernel<128, 128, 4, 1, EPI_SPLINE, 11>(const GemmParams p) {
 }
 
 // tuning knobs (fc_debug_set), defaults = shipped configuration.  Every alternative below is kept because a test pins it against the
-// shipped path (tests/test_gpu_flow.py::test_every_kernel_variant_agrees...) and DESIGN.md section 6 quotes its measurement.
-int g_gemm_variant = 5, g_gemm_colgroup = 10, g_gemm_bigtile = 3, g_limb_chain = 1, g_lnq_fold = 1, g_fused_spline = 1;
+// shipped path (tests/test_gpu_flow.py::test_every_kernel_variant_in_the_library_agrees...) and DESIGN.md section 6 quotes its measurement.
+int g_gemm_variant = 5, g_gemm_colgroup = 10, g_limb_chain = 1, g_lnq_fold = 1, g_fused_spline = 1;
 int g_gemm_stamp = 0;        // knob 20: the LDS-DMA fused-spline launches record in-kernel phase stamps (read back with gemm_read_stamps)
 static unsigned long long* g_stamp_buf = nullptr;
 static size_t g_stamp_cap = 0, g_stamp_n = 0;
@@ -1274,21 +1140,19 @@ size_t gemm_read_stamps(unsigned long long* host, size_t max_n) {
     if (n) FC_HIP(hipMemcpy(host, g_stamp_buf, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return n;
 }
-int g_spline_prefetch = 0;   // knob 21: persistent fused spline GEMM (VAR 11): 1 = a tile's k loop starts at a column-tile dependent step and wraps around (measured: no gain, other summation order); 0 = every tile starts at k = 0 (shipped, bit-identical to VAR 7-10)
-int g_gemm_dma = 5;          // knob 13: fused spline GEMM: 5 = 256 x 256 one-accumulator tile on 16x16x32 MFMAs (spline_wide.hip, shipped round 4; K = 8 bins, limb-chained input; other launches fall to 4), 4 = persistent transposed LDS-DMA loop, splines evaluated from the accumulator registers (VAR 11, shipped; K = 8 bins), 3 = the same, one tile per workgroup (VAR 10), 2 = LDS-DMA loop on the 128x128 four-wave tile with the LDS parameter tile (VAR 9), 1 = on the 256x128 tile (VAR 8), 0 = register-staged (VAR 7); bit-identical results
+int g_spline_prefetch = 0;   // knob 21: persistent fused spline GEMM (VAR 11): 1 = a tile's k loop starts at a column-tile dependent step and wraps around (measured: no gain, other summation order); 0 = every tile starts at k = 0 (shipped, bit-identical to VAR 9)
+int g_gemm_dma = 5;          // knob 13: fused spline GEMM: 5 = 256 x 256 one-accumulator tile on 16x16x32 MFMAs (spline_wide.hip, shipped round 4; K = 8 bins, limb-chained input; other launches fall to 4), 4 = persistent transposed LDS-DMA loop, splines evaluated from the accumulator registers (VAR 11; K = 8 bins), 2 = LDS-DMA loop on the 128x128 four-wave tile with the LDS parameter tile (VAR 9; 4 and 16 bins always); bit-identical results
 int g_spline_ablate = 0;     // knob 14: diagnostics, results invalid (1 = no spline evaluation, 2 = main loop only, 3 = no parameter-tile write, 4 = no x2 store, 5 = stop behind the tile write)
 int g_gemm_small_tiles = 1;  // knob 22: limb-chained Linear launches with at most 256 tiles of 128x128 run on 64x64 tiles
-int g_gemm_dma_linear = 2;   // knob 15: limb-image A in a Linear layer: 2 = LDS-DMA loop on the 128x128 four-wave tile (shipped), 1 = on the 256x128 tile, 0 = register-staged
 int g_limb_chain_all = 1;    // knob 16: every hidden activation of the coupling MLP exists only as a limb image (A16 / residual16 / C16)
-int g_gemm_prefetch3 = 0;    // knob 17: three register sets of prefetch in the Linear loop (VAR 6): bit-identical, measured 3.5 % slower
 
 static thread_local int* t_fp16_flag = nullptr;
 static std::atomic<long> g_fp16_fallbacks{0};
 
 bool gemm_fp16_enabled() { return g_gemm_variant == 5; }
-bool gemm_lnq_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_gemm_bigtile == 3 && g_lnq_fold; }
-bool gemm_limb_chain_all_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_gemm_bigtile == 3 && g_fused_spline && g_limb_chain && g_limb_chain_all; }
-bool gemm_limb_chain_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_gemm_bigtile == 3 && g_fused_spline && g_limb_chain; }
+bool gemm_lnq_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_lnq_fold; }
+bool gemm_limb_chain_all_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_fused_spline && g_limb_chain && g_limb_chain_all; }
+bool gemm_limb_chain_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_fused_spline && g_limb_chain; }
 bool gemm_split_enabled() { return (g_gemm_variant == 5 || g_gemm_variant == 3) && g_fused_spline; }
 int* gemm_fp16_flag() { return g_gemm_variant == 5 ? t_fp16_flag : nullptr; }
 long gemm_fp16_fallbacks() { return g_fp16_fallbacks.load(); }
@@ -1381,9 +1245,9 @@ int guard_resolve() {
 
 template <int BM, int BN, int WM, int WN, int EPI, int VAR = 2>
 static void launch_cfg(const GemmParams& p, hipStream_t s) {
-    constexpr size_t lds_main = VAR == 8 ? 3 * (size_t)(BM + BN) * 128 : VAR == 11 ? 2 * (size_t)(BM + BN) * 128 + 1024 : (VAR == 9 || VAR == 10) ? (BM == 64 ? 8 : 2) * (size_t)(BM + BN) * 128 : (VAR == 5 || VAR == 6 || VAR == 7) ? 2 * (size_t)(BM + BN) * 80 : VAR >= 3 ? 2 * (size_t)(BM + BN) * 112 : 2 * (size_t)(BM + BN) * LDS_LD * sizeof(float);
+    constexpr size_t lds_main = VAR == 11 ? 2 * (size_t)(BM + BN) * 128 + 1024 : VAR == 9 ? (BM == 64 ? 8 : 2) * (size_t)(BM + BN) * 128 : VAR == 5 ? 2 * (size_t)(BM + BN) * 80 : VAR == 3 ? 2 * (size_t)(BM + BN) * 112 : 2 * (size_t)(BM + BN) * LDS_LD * sizeof(float);
     static PerDeviceOnce attr_once;
-    constexpr size_t lds_epi = EPI == EPI_SPLINE && VAR != 10 && VAR != 11 ? ((size_t)BM * (BN + 1) + (size_t)BM * 9) * sizeof(float) : 0;   // tile + <= 9 dims of log-dets
+    constexpr size_t lds_epi = EPI == EPI_SPLINE && VAR != 11 ? ((size_t)BM * (BN + 1) + (size_t)BM * 9) * sizeof(float) : 0;   // tile + <= 9 dims of log-dets
     constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
     auto kern = gemm_f32_kernel<BM, BN, WM, WN, EPI, VAR>;
     attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
@@ -1393,7 +1257,7 @@ static void launch_cfg(const GemmParams& p, hipStream_t s) {
     if ((size_t)p.N_pad * p.K_pad * sizeof(float) > (size_t)(3u << 19) && q.nbm % 8 == 0 && q.nbn > g_gemm_colgroup && g_gemm_colgroup > 0)
         q.col_group = g_gemm_colgroup;
     q.stamps = nullptr;
-    if constexpr ((EPI == EPI_SPLINE || EPI == EPI_LINEAR) && (VAR == 8 || VAR == 9 || VAR == 10 || VAR == 11)) {
+    if constexpr ((EPI == EPI_SPLINE || EPI == EPI_LINEAR) && (VAR == 9 || VAR == 11)) {
         if (g_gemm_stamp == (EPI == EPI_SPLINE ? 1 : 2)) {                  // knob 20: 1 = the fused spline launches, 2 = the limb-chained Linear launches
             const size_t n = (size_t)q.nbm * q.nbn * 16;
             if (n > g_stamp_cap) {
@@ -1423,8 +1287,7 @@ static void launch_cfg(const GemmParams& p, hipStream_t s) {
     FC_HIP(hipGetLastError());
 }
 
-bool gemm_dev_variants() { return kDevVariants; }
-bool gemm_spline_wide_on() { return g_gemm_dma == 5 && g_gemm_variant == 5 && g_gemm_bigtile == 3 && g_fused_spline && g_limb_chain && g_spline_ablate != 3 && g_spline_ablate != 4 && g_spline_ablate != 5; }
+bool gemm_spline_wide_on() { return g_gemm_dma == 5 && g_gemm_variant == 5 && g_fused_spline && g_limb_chain && g_spline_ablate != 3 && g_spline_ablate != 4 && g_spline_ablate != 5; }
 
 static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_alloc, const GemmEpi& e_in, int epi_kind, hipStream_t s);
 void launch_gemm(const PackedLinear& L, const ASeg* segs, int rows_alloc, const GemmEpi& e_in, int epi_kind, hipStream_t s) {
@@ -1440,11 +1303,6 @@ void launch_gemm(const PackedLinear& L, const ASeg* segs, int rows_alloc, const 
 }
 static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_alloc, const GemmEpi& e_in, int epi_kind, hipStream_t s) {
     if (rows_alloc % ROW_PAD != 0) throw Error(FC_ERR_INVALID, "launch_gemm: rows must be padded to ROW_PAD");
-    const int v_bigtile = kDevVariants ? g_gemm_bigtile : 3;
-    const int v_dma_linear = kDevVariants ? g_gemm_dma_linear : 2;
-    const int v_dma = kDevVariants ? g_gemm_dma : (g_gemm_dma == 2 ? 2 : 4);      // (5, the shipped wide kernel, takes one-accumulator images only: spline_wide.hip)      // (2: the LDS-tile epilogue on the four-wave DMA tile -- in every build: it serves 4 and 16 bins)
-    const int v_variant = kDevVariants ? g_gemm_variant : (g_gemm_variant < 2 ? 2 : g_gemm_variant);
-    (void)v_bigtile; (void)v_dma_linear; (void)v_dma;
     if (L.K_pad % 32 != 0 || L.N_pad % 32 != 0 || L.nseg < 1 || L.nseg > 3) throw Error(FC_ERR_INVALID, "launch_gemm: bad packing");
     GemmParams p{};
     int kt = 0;
@@ -1465,17 +1323,15 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
                    (double)(L.k_true ? L.k_true : L.K_pad);
     p.W = L.W; p.W3 = L.W3; p.W2 = L.W2; p.ovf = t_fp16_flag; p.K_pad = L.K_pad; p.bias = L.bias; p.colvec = L.colvec; p.N_pad = L.N_pad;
     p.e = e;
-    const bool split = (v_variant == 3 || v_variant == 5) && L.W3 != nullptr;
-    const bool f16 = v_variant == 5 && L.W2 != nullptr && t_fp16_flag != nullptr;
+    const bool split = (g_gemm_variant == 3 || g_gemm_variant == 5) && L.W3 != nullptr;
+    const bool f16 = g_gemm_variant == 5 && L.W2 != nullptr && t_fp16_flag != nullptr;
     if (epi_kind == EPI_LINEAR) {
         if ((!e.C && !e.C16) || (e.C && e.ldc < L.N_pad)) throw Error(FC_ERR_INVALID, "launch_gemm: output pitch smaller than N_pad");
         if ((e.gradu || e.Cpre) && e.A16) throw Error(FC_ERR_INVALID, "launch_gemm: the training epilogues exist on the fp32-A loops only");
         if (e.gradu && (!e.C || e.C16 || e.Cpre || e.act != FC_ACT_NONE || e.ldgu < L.N_pad || (e.gact != FC_ACT_GELU && e.gact != FC_ACT_RELU && e.gact != FC_ACT_ELU)))
             throw Error(FC_ERR_INVALID, "launch_gemm: an activation-gradient epilogue goes with an fp32 C, no activation, and GELU / RELU / ELU");
         if (e.Cpre && (!e.C || e.C16)) throw Error(FC_ERR_INVALID, "launch_gemm: a pre-activation output goes with an fp32 C and no limb image");
-        if ((e.gradu || e.Cpre) && kDevVariants && (v_variant == 0 || v_variant == 1 || (v_variant == 5 && v_bigtile == 3 && g_gemm_prefetch3)))
-            throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: the training epilogues (Cpre / gradu) exist on VAR 2 / 3 / 5 only; this developer variant would ignore them");
-        if (e.C16 && !(f16 && v_bigtile == 3 && L.N_pad > 64 && L.N_pad % 16 == 0))
+        if (e.C16 && !(f16 && L.N_pad > 64 && L.N_pad % 16 == 0))
             throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: limb-image output exists on the eight-wave split-fp16 tile only");
         if (e.a16_scale != 0.f) {                                       // a one-accumulator activation image: the 256 x 256 Linear kernel (spline_wide.hip EPI 1) only
             if (!(f16 && linear_wide_eligible(L, e, rows_alloc))) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator activation image needs the wide Linear kernel (GELU layer, images in and out, N % 256 == 0)");
@@ -1486,17 +1342,15 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
         if (e.A16) {
             p.e.inverse = g_spline_ablate;
             // A arrives as the limb image of the producing layer (limb-chained MLP): the copy-only main loops
-            if (!(f16 && v_bigtile == 3 && L.nseg == 1 && L.N_pad > 64 && L.n_alloc >= round_up(L.N_pad, 128)))
+            if (!(f16 && L.nseg == 1 && L.N_pad > 64 && L.n_alloc >= round_up(L.N_pad, 128)))
                 throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: a limb-image A operand needs the split-fp16 loop, one segment and N > 64");
-            if (v_dma_linear == 2 && g_gemm_small_tiles && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 256 && L.N_pad % 64 == 0) {
+            if (g_gemm_small_tiles && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 256 && L.N_pad % 64 == 0) {
                 // fewer 128x128 tiles than workgroup slots (C1: 2 x 1024 points = 16 row tiles): four times as many 64x64 tiles, each a
                 // quarter of the MFMA work per k step -- the launch is bound by one workgroup's k loop, not by throughput
                 p.nbm = rows_alloc / 64;
                 launch_cfg<64, 64, 2, 2, EPI_LINEAR, 9>(p, s);
             }
-            else if (v_dma_linear == 2) { p.nbm = rows_alloc / 128; launch_cfg<128, 128, 2, 2, EPI_LINEAR, 9>(p, s); }
-            FC_DEV(else if (v_dma_linear && rows_alloc % 256 == 0) { p.nbm = rows_alloc / 256; launch_cfg<256, 128, 4, 2, EPI_LINEAR, 8>(p, s); }
-                   else { p.nbm = rows_alloc / 128; launch_cfg<128, 128, 4, 2, EPI_LINEAR, 7>(p, s); })
+            else { p.nbm = rows_alloc / 128; launch_cfg<128, 128, 2, 2, EPI_LINEAR, 9>(p, s); }
         } else if (L.N_pad <= 64 || (f16 && g_gemm_small_tiles && !e.C16 && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 128 && L.n_alloc >= round_up(L.N_pad, 64))) {
             // (64-wide layers; and fp32-A launches with at most 128 tiles of 128x128: twice as many 128x64 tiles)
             p.nbm = rows_alloc / 128;
@@ -1507,28 +1361,17 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
             // (with the split-bf16 loop two co-resident 128x128 workgroups beat the one-wave-per-SIMD 128x320 tile even at N = 320)
             // Default for the split-fp16 loop: 128x128 tile on EIGHT waves of 32x64 (64 accumulator registers per lane instead of
             // 128 -> 118 VGPRs -> 4 waves per SIMD instead of 2): +4 ... +19 % over four waves of 64x64 on every layer shape, and
-            // better than the 8-wave 256x128 tile on the wide layers.  knob 3: 3 = that (default), 0 = four 64x64 waves,
-            // 1 = 256x128 for N >= 1024, 2 = 256x128 everywhere
-            FC_DEV(const bool big = v_bigtile == 2 || (v_bigtile == 1 && L.N_pad >= 1024);
-                   if (f16 && big && rows_alloc % 256 == 0) { p.nbm = rows_alloc / 256; launch_cfg<256, 128, 4, 2, EPI_LINEAR, 5>(p, s); }
-                   else if (split && v_bigtile == 2 && rows_alloc % 256 == 0) { p.nbm = rows_alloc / 256; launch_cfg<256, 128, 4, 2, EPI_LINEAR, 3>(p, s); }
-                   else)
-            {
-                p.nbm = rows_alloc / 128;
-                FC_DEV(if (f16 && v_bigtile == 3 && g_gemm_prefetch3) launch_cfg<128, 128, 4, 2, EPI_LINEAR, 6>(p, s); else)
-                if (f16 && v_bigtile == 3) launch_cfg<128, 128, 4, 2, EPI_LINEAR, 5>(p, s);
-                FC_DEV(else if (f16) launch_cfg<128, 128, 2, 2, EPI_LINEAR, 5>(p, s);)
-                else if (split) launch_cfg<128, 128, 2, 2, EPI_LINEAR, 3>(p, s);
-                FC_DEV(else if (v_variant == 0) launch_cfg<128, 128, 2, 2, EPI_LINEAR, 0>(p, s);
-                       else if (v_variant == 1) launch_cfg<128, 128, 2, 2, EPI_LINEAR, 1>(p, s);)
-                else launch_cfg<128, 128, 2, 2, EPI_LINEAR, 2>(p, s);
-            }
+            // better than the 8-wave 256x128 tile on the wide layers
+            p.nbm = rows_alloc / 128;
+            if (f16) launch_cfg<128, 128, 4, 2, EPI_LINEAR, 5>(p, s);
+            else if (split) launch_cfg<128, 128, 2, 2, EPI_LINEAR, 3>(p, s);
+            else launch_cfg<128, 128, 2, 2, EPI_LINEAR, 2>(p, s);
         } else {
             p.nbm = rows_alloc / 128;
             if (split) launch_cfg<128, 320, 4, 1, EPI_LINEAR, 3>(p, s); else launch_cfg<128, 320, 4, 1, EPI_LINEAR>(p, s);
         }
     } else if (epi_kind == EPI_LNQ) {
-        if (!(f16 && v_bigtile == 3)) throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: the LayerNorm -> q fold runs on the eight-wave split-fp16 tile only");
+        if (!f16) throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: the LayerNorm -> q fold runs on the eight-wave split-fp16 tile only");
         if (!e.C || !e.ldj_part || e.d2 % 64 != 0 || L.N_pad != e.d2 + 64 || e.ldc < 64 || e.ldj_pitch < (size_t)rows_alloc || !L.bias)
             throw Error(FC_ERR_INVALID, "launch_gemm: bad LayerNorm -> q fold arguments");
         p.nbm = rows_alloc / 128;
@@ -1544,22 +1387,18 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
         if ((K != 4 && K != 8 && K != 16) || L.N_pad != spline_ncols(e.d2, K) || !e.xbuf || !e.ldj_part || e.ldj_pitch < (size_t)rows_alloc)
             throw Error(FC_ERR_INVALID, "launch_gemm: bad fused-spline arguments (layout of spline.h, per-tile log-det buffer)");
         p.nbm = rows_alloc / 128;
-        if (e.a16_scale != 0.f && !(f16 && e.A16 && v_bigtile == 3)) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator activation image outside the split-fp16 guard scope");
-        if (f16 && e.A16 && v_bigtile == 3) {
+        if (e.a16_scale != 0.f && !(f16 && e.A16)) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator activation image outside the split-fp16 guard scope");
+        if (f16 && e.A16) {
             if (L.nseg != 1) throw Error(FC_ERR_INVALID, "launch_gemm: a limb-image A operand must be the only segment");
             if (L.n_alloc < round_up(L.N_pad, 128)) throw Error(FC_ERR_INVALID, "launch_gemm: fused spline layer not padded to the 128-column tile grid");
             if (e.a16_scale != 0.f) {                                   // the one-accumulator image: only spline_wide.hip reads it
                 if (!(g_gemm_dma == 5 && spline_wide_eligible(L, K))) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator activation image needs the wide fused spline kernel (knob 13 = 5)");
                 launch_spline_wide(L, p.e, rows_alloc, s);
             }
-            else if (v_dma >= 4 && K == 8 && L.bias) launch_cfg<128, 128, 4, 1, EPI_SPLINE, 11>(p, s);
-            FC_DEV(else if (v_dma == 3 && K == 8 && L.bias) launch_cfg<128, 128, 4, 1, EPI_SPLINE, 10>(p, s);)
-            else if (v_dma >= 2) launch_cfg<128, 128, 2, 2, EPI_SPLINE, 9>(p, s);      // (4 and 16 bins: the LDS-tile epilogue on the four-wave DMA tile)
-            FC_DEV(else if (v_dma == 1 && rows_alloc % 256 == 0) { p.nbm = rows_alloc / 256; launch_cfg<256, 128, 4, 2, EPI_SPLINE, 8>(p, s); }
-                   else launch_cfg<128, 128, 4, 2, EPI_SPLINE, 7>(p, s);)
+            else if (g_gemm_dma != 2 && K == 8 && L.bias) launch_cfg<128, 128, 4, 1, EPI_SPLINE, 11>(p, s);      // (knob 13 = 4; 5 where the wide kernel does not apply)
+            else launch_cfg<128, 128, 2, 2, EPI_SPLINE, 9>(p, s);      // (4 and 16 bins, knob 13 = 2: the LDS-tile epilogue on the four-wave DMA tile)
         }
-        else if (f16 && v_bigtile == 3) launch_cfg<128, 128, 4, 2, EPI_SPLINE, 5>(p, s);
-        FC_DEV(else if (f16) launch_cfg<128, 128, 2, 2, EPI_SPLINE, 5>(p, s);)
+        else if (f16) launch_cfg<128, 128, 4, 2, EPI_SPLINE, 5>(p, s);
         else launch_cfg<128, 128, 2, 2, EPI_SPLINE, 3>(p, s);
     } else {
         if (!L.bias || L.N_pad % 64 != 0) throw Error(FC_ERR_INVALID, "launch_gemm: pair-packed epilogue needs bias and N_pad % 64 == 0");
@@ -1567,9 +1406,9 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
         // forward direction inside a guard scope: 128x128 tile on eight waves with the split-fp16 loop (a wave's 64 columns are one
         // [first 32 | second 32] pair block); log-dets go to the caller's slot buffer.  Otherwise (inverse, bf16-limb fallback
         // pass, fp32 variants): the 128x320 tile whose workgroup owns whole rows.
-        if (e.A16 && !(epi_kind == EPI_AFFINE && f16 && e.ldj_part && !e.inverse && v_bigtile == 3 && L.nseg == 1 && L.n_alloc >= round_up(L.N_pad, 128)))
+        if (e.A16 && !(epi_kind == EPI_AFFINE && f16 && e.ldj_part && !e.inverse && L.nseg == 1 && L.n_alloc >= round_up(L.N_pad, 128)))
             throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: a limb-image A operand in a pair-packed epilogue exists for the forward affine coupling only");
-        if (f16 && e.ldj_part && !e.inverse && v_bigtile == 3) {
+        if (f16 && e.ldj_part && !e.inverse) {
             if (e.ldj_pitch < (size_t)rows_alloc) throw Error(FC_ERR_INVALID, "launch_gemm: log-det slot pitch smaller than the row count");
             if (e.A16 && g_gemm_small_tiles && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 256) { p.nbm = rows_alloc / 64; launch_cfg<64, 64, 2, 1, EPI_AFFINE, 9>(p, s); }   // (small launch: 64x64 tiles, see EPI_LINEAR)
             else if (e.A16) launch_cfg<128, 128, 2, 2, EPI_AFFINE, 9>(p, s);       // limb-chained MLP: copy-only LDS-DMA loop (a wave's 64 columns = one pair block)

@@ -17,43 +17,38 @@ struct TmpBuf {
 }  // namespace fc
 
 
-namespace fc { void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t); long gemm_fp16_fallbacks(); extern int g_train_wgrad16; extern int g_train_attn16; extern int g_gemm_dma; extern int g_spline_ablate; extern int g_gemm_dma_linear; extern int g_limb_chain_all; extern int g_gemm_prefetch3; extern int g_premlp_chain; extern int g_gemm_stamp; extern int g_gemm_small_tiles; extern int g_spline_prefetch; extern int g_mlp_rows; extern int g_knn_mfma; extern int g_premlp_lu; extern int g_spline_wide_dma; extern int g_spline_wide_colgroup; extern int g_linear_wide; extern int g_knn_warm; size_t gemm_read_stamps(unsigned long long*, size_t); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t); }
-namespace fc { extern int g_gemm_variant, g_gemm_colgroup, g_gemm_bigtile, g_attn_fp16, g_fused_spline, g_premlp_fused, g_limb_chain, g_lnq_fold; }
+namespace fc { void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t); long gemm_fp16_fallbacks(); extern int g_train_wgrad16; extern int g_train_attn16; extern int g_gemm_dma; extern int g_spline_ablate; extern int g_limb_chain_all; extern int g_premlp_chain; extern int g_gemm_stamp; extern int g_gemm_small_tiles; extern int g_spline_prefetch; extern int g_mlp_rows; extern int g_knn_mfma; extern int g_premlp_lu; extern int g_spline_wide_colgroup; extern int g_linear_wide; extern int g_knn_warm; size_t gemm_read_stamps(unsigned long long*, size_t); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t); }
+namespace fc { extern int g_gemm_variant, g_gemm_colgroup, g_attn_fp16, g_fused_spline, g_premlp_fused, g_limb_chain, g_lnq_fold; }
 
 extern "C" {
 
-/* tuning knobs for profiles/kernel_bench.py (not part of the stable ABI surface in fcflow.h on purpose) */
+/* tuning knobs for profiles/kernel_bench.py (not part of the stable ABI surface in fcflow.h on purpose).  A value a knob no longer has (its
+   kernel variant lost an A/B and was removed: DESIGN.md section 6) is refused with FC_ERR_UNSUPPORTED and leaves the setting as it was. */
 int fc_debug_set(int32_t key, int32_t value) {
-    if (!fc::kDevVariants && ((key == 0 && (value == 0 || value == 1)) || (key == 3 && value != 3) || (key == 8 && value == 1) || (key == 13 && value != 5 && value != 4 && value != 2) ||
-                              (key == 15 && value != 2) || (key == 17 && value != 0) || (key == 27 && value != 0)))
-        return FC_ERR_UNSUPPORTED;       /* a developer variant: compiled only with -DFC_DEV_VARIANTS (python -m flowcompare_amd.build --dev) */
-    if (key == 0) fc::g_gemm_variant = value;
+    if ((key == 0 && value != 2 && value != 3 && value != 5) || (key == 8 && value != 0 && value != 2) || (key == 13 && value != 2 && value != 4 && value != 5))
+        return FC_ERR_UNSUPPORTED;
+    if (key == 0) fc::g_gemm_variant = value;             /* GEMM main loop: 5 = split-fp16 (default), 3 = split-bf16, 2 = fp32-input MFMA */
     else if (key == 2) fc::g_gemm_colgroup = value;
-    else if (key == 3) fc::g_gemm_bigtile = value;
     else if (key == 5) fc::g_attn_fp16 = value;
     else if (key == 7) fc::g_fused_spline = value;
-    else if (key == 8) fc::g_premlp_fused = value;
+    else if (key == 8) fc::g_premlp_fused = value;        /* pre-attention chain: 2 = the row-resident kernel (premlp.hip, default), 0 = separate launches */
     else if (key == 9) fc::g_limb_chain = value;
     else if (key == 10) fc::g_lnq_fold = value;
     else if (key == 11) fc::g_train_wgrad16 = value;
     else if (key == 12) fc::g_train_attn16 = value;
-    else if (key == 13) fc::g_gemm_dma = value;
-    else if (key == 15) fc::g_gemm_dma_linear = value;   /* limb-image A in EPI_LINEAR: 1 = LDS-DMA loop on the 256x128 tile (default), 0 = register-staged 128x128 */
-    else if (key == 16) fc::g_limb_chain_all = value;    /* 1 = the coupling MLP's hidden activations exist only as limb images (default 0) */
-    else if (key == 17) fc::g_gemm_prefetch3 = value;   /* Linear GEMM: three register sets of prefetch (VAR 6) instead of two (VAR 5) */
+    else if (key == 13) fc::g_gemm_dma = value;           /* fused spline GEMM: 5 = the wide kernel (spline_wide.hip, default), 4 = persistent LDS-DMA loop (VAR 11), 2 = LDS-tile epilogue (VAR 9) */
+    else if (key == 16) fc::g_limb_chain_all = value;    /* 1 = the coupling MLP's hidden activations exist only as limb images (default), 0 = also as fp32 */
     else if (key == 19) fc::g_premlp_chain = value;
     else if (key == 21) fc::g_spline_prefetch = value;
     else if (key == 22) fc::g_gemm_small_tiles = value;
     else if (key == 23) fc::g_mlp_rows = value;          /* 1 = row-resident coupling MLP chain (mlprows.hip, default), 0 = one GEMM launch per layer */
     else if (key == 26) fc::g_premlp_lu = value;         /* 1 = ActNorm + LU as a pre-layer of the row-resident pre-attention kernel (default), 0 = its own GEMM launch */
     else if (key == 24) fc::g_knn_mfma = value;          /* 1 = k-NN Gram tiles on the matrix cores (default), 0 = lane-per-candidate kernel */
-    else if (key == 27) fc::g_spline_wide_dma = value;   /* developer builds: DMA pieces per phase of the wide fused spline kernel (spline_wide.hip) */
     else if (key == 29) fc::g_linear_wide = value;       /* hidden layers of the coupling MLP on the 256 x 256 one-accumulator kernel: 0 = off (default: measured no faster than the chain), 1 = for scenes of >= 2048 target points, 2 = at any size */
     else if (key == 32) fc::g_knn_warm = value;         /* 1 = DGCNN levels 1-3 start their k-NN stream from the previous level's neighbour sets (default; exact either way), 0 = from -inf */
     else if (key == 31) fc::g_train_wide = value;       /* 1 = training Linear layers with >= 1024 outputs (the spline parameter layer) on the 256 x 256 one-accumulator loop (default), 0 = on the fp32-A 128 x 128 loop, 3 = 1 with non-temporal stores of a GB-sized output (measured slower) */
-    else if (key == 30) { if (value != 0) return FC_ERR_UNSUPPORTED; }      /* (was: attention as two staggered wave groups -- measured no faster, removed with the one-accumulator attention kernel) */
     else if (key == 28) fc::g_spline_wide_colgroup = value;   /* column-group size of its tile order (-1 = shipped) */
-    else if (key == 20) fc::g_gemm_stamp = value;        /* diagnostic: in-kernel phase stamps of the LDS-DMA fused-spline launches */
+    else if (key == 20) fc::g_gemm_stamp = value;        /* diagnostic: in-kernel phase stamps, 1 = fused spline launches, 2 = limb-chained Linear launches, 3 = row-resident pre-attention kernel, 4 = row-resident coupling MLP */
     else if (key == 14) fc::g_spline_ablate = value;     /* diagnostic: 1 = fused spline epilogue without the spline evaluation, 2 = main loop only (results invalid) */
     else return FC_ERR_INVALID;
     return FC_OK;
@@ -66,9 +61,6 @@ int fc_debug_one_acc_gemm_f32(const float* x, const float* W, const float* bias,
     fc::one_acc_gemm_debug(x, W, bias, wmax, out, rows, N, K, (hipStream_t)stream);
     FC_API_END
 }
-
-/* 1 when the library was built with the developer kernel variants (-DFC_DEV_VARIANTS) */
-int32_t fc_debug_dev_variants(void) { return fc::kDevVariants ? 1 : 0; }
 
 /* host-side view of the spline parameter layer's column layout (csrc/spline.h) for the CPU tests: column of (transformed dim j, parameter
    pp) and the dim-major position inside a tile that the LDS-tile epilogues store a column at; no device call */

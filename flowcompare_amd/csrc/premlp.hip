@@ -2,14 +2,9 @@
 // (models/cif_block.py:14-20: x1 -> pre_attention_mlp; models/perceiver.py:18-35: PreNorm; :104-106: to_q), one launch per layer
 // instead of six (in_layer, two hidden layers, out_layer, LayerNorm, q projection).
 //
-// A workgroup owns 64 point rows for the whole chain; the 64 x 256 activation tile never leaves the CU:
-//   * it lives in LDS as the fp16 limb image the next layer's MFMAs read ([row][k/16][hi 16 | lo' 16], split-fp16 operands of
-//     gemm.hip / DESIGN.md section 3), 65 KB;
-//   * each layer streams its weight limb image (PackedLinear.W2) through a double-buffered 32-k LDS stage (2 x 36 KB) with a
-//     two-deep register prefetch, 12 MFMAs per wave and barrier (8 waves: 2 row blocks x 4 column blocks of 32 x 64);
-//   * the epilogue (bias, residual kept in registers, exact-erf GELU, limb split) writes the tile back in place;
-//   * LayerNorm statistics are reduced across the 4 column waves through LDS, the normalised tile feeds the 256 -> 64 q
-//     projection (gamma / beta / softmax scale / log2 e folded into it at create), and only q [rows, 64] is written to HBM.
+// A workgroup owns 128 point rows for the whole chain and keeps their activations in registers as split-fp16 limbs (gemm.hip /
+// DESIGN.md section 3); only the weight limb images (PackedLinear.W2) stream through LDS, the normalised rows feed the 256 -> 64 q
+// projection (gamma / beta / softmax scale / log2 e folded into it at create), and only q [rows, 64] is written to HBM.
 // Removes per layer: 4 activation round trips through HBM (67 MB written + read each), the LayerNorm pass, 5 launches.
 // Shapes: hidden width = attention input width = 256 exactly, q width 64, input width a multiple of 32 up to 256
 // (the engine falls back to the separate kernels otherwise, and always on the bf16-limb range-fallback pass).
@@ -21,7 +16,6 @@
 
 namespace fc {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 typedef __attribute__((address_space(3))) char pm_lds_char;
@@ -48,212 +42,10 @@ struct PreMlpParams {
     float* xnext; int ldxn;
 };
 
-constexpr int PM_ROWS = 64, PM_H = 256, PM_NT = 512;
-constexpr int PM_APITCH = (PM_H / 16) * 64 + 16;           // 1040 B per activation row
-constexpr int PM_WPITCH = 144;                             // [hi 32 k | lo' 32 k] + 16 B pad per weight row and stage
-constexpr int PM_ACT_BYTES = PM_ROWS * PM_APITCH;          // 66560
-constexpr int PM_WSTAGE = PM_H * PM_WPITCH;                // 36864
-constexpr int PM_RED_OFF = PM_ACT_BYTES + 2 * PM_WSTAGE;   // [64 rows][4] floats for the LayerNorm reductions
-constexpr int PM_LDS = PM_RED_OFF + PM_ROWS * 4 * 4;
-
-// One dense layer on the resident tile: acc[j] (+ corr) = tile(64 x K) * W(NOUT x K)^T for this wave's 32 x (32*TNW) block.
-// NOUT = 256 (TNW = 2, all 8 waves) or 64 (TNW = 1, waves with wc < 2).
-// (Reading the weight fragments straight from the L2-resident limb image -- no LDS staging, no barrier inside a layer -- was
-//  measured 60 % slower: 8 waves x 4 KB of 16-byte-per-lane loads per k-tile exceed what the CU's vector L1 delivers.)
-template <int NOUT>
-__device__ __forceinline__ void pm_gemm(const PreMlpLayer& L, char* smc, int tid, int li, int lh, int wr, int wc, floatx16 (&accm)[2], floatx16 (&accc)[2]) {
-    constexpr int TNW = NOUT == 256 ? 2 : 1;
-    constexpr int CHUNKS = NOUT * 8;                        // 16-byte chunks per 32-k stage
-    constexpr int NCH = (CHUNKS + PM_NT - 1) / PM_NT;       // per thread (4 or 1)
-    typedef unsigned int u32xs __attribute__((ext_vector_type(4 * NCH)));
-    u32xs r0, r1;
-    const int KT16 = L.K_pad / 16, KS = L.K_pad / 32;
-    char* wst = smc + PM_ACT_BYTES;
-#define PM_GLOAD(R_, S_)                                                                                         \
-    _Pragma("unroll") for (int i = 0; i < NCH; ++i) {                                                             \
-        int c_ = tid + PM_NT * i;                                                                                 \
-        c_ = c_ < CHUNKS ? c_ : CHUNKS - 1;                                                                       \
-        const int row_ = c_ >> 3, part_ = c_ & 7, sub_ = part_ >> 2, q2_ = part_ & 3;                             \
-        const uint4 t_ = *reinterpret_cast<const uint4*>(L.W2 + ((size_t)row_ * KT16 + 2 * (S_) + sub_) * 32 + q2_ * 8); \
-        R_[4 * i] = t_.x; R_[4 * i + 1] = t_.y; R_[4 * i + 2] = t_.z; R_[4 * i + 3] = t_.w;                       \
-    }
-#define PM_LSTORE(R_, ST_)                                                                                        \
-    _Pragma("unroll") for (int i = 0; i < NCH; ++i) {                                                             \
-        const int c_ = tid + PM_NT * i, row_ = c_ >> 3, part_ = c_ & 7, sub_ = part_ >> 2, q2_ = part_ & 3;       \
-        if (CHUNKS % PM_NT == 0 || c_ < CHUNKS)                                                                   \
-            *reinterpret_cast<uint4*>(wst + (ST_) * PM_WSTAGE + row_ * PM_WPITCH + (q2_ >> 1) * 64 + sub_ * 32 + (q2_ & 1) * 16) = \
-                make_uint4(R_[4 * i], R_[4 * i + 1], R_[4 * i + 2], R_[4 * i + 3]);                               \
-    }
-#define PM_MMA(ST_, S_)                                                                                           \
-    if (NOUT == 256 || wc < 2) {                                                                                  \
-        _Pragma("unroll") for (int sub = 0; sub < 2; ++sub) {                                                     \
-            const char* pa = smc + (32 * wr + li) * PM_APITCH + (2 * (S_) + sub) * 64 + lh * 16;                  \
-            const f16x8 ah = *reinterpret_cast<const f16x8*>(pa), al = *reinterpret_cast<const f16x8*>(pa + 32); \
-            _Pragma("unroll") for (int j = 0; j < TNW; ++j) {                                                     \
-                const char* pb = wst + (ST_) * PM_WSTAGE + (32 * TNW * wc + 32 * j + li) * PM_WPITCH + sub * 32 + lh * 16; \
-                const f16x8 bh = *reinterpret_cast<const f16x8*>(pb), bl = *reinterpret_cast<const f16x8*>(pb + 64); \
-                accm[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, accm[j], 0, 0, 0);                       \
-                accc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, accc[j], 0, 0, 0);                       \
-                accc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, accc[j], 0, 0, 0);                       \
-            }                                                                                                     \
-        }                                                                                                         \
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { accm[j][r] = 0.f; accc[j][r] = 0.f; }
-    // stage s & 1 of LDS holds k-step s; one register set holds step s + 1, the other s + 2 (two-deep prefetch, as in gemm.hip)
-    PM_GLOAD(r0, 0)
-    PM_LSTORE(r0, 0)
-    if (KS > 1) { PM_GLOAD(r1, 1) }
-    __syncthreads();
-    for (int s = 0; s < KS; s += 2) {
-        const int s2 = s + 2 < KS ? s + 2 : KS - 1, s3 = s + 3 < KS ? s + 3 : KS - 1;
-        PM_GLOAD(r0, s2)
-        PM_MMA(0, s)
-        if (s + 1 < KS) {
-            PM_LSTORE(r1, 1)
-            __syncthreads();
-            PM_GLOAD(r1, s3)
-            PM_MMA(1, s + 1)
-        }
-        if (s + 2 < KS) { PM_LSTORE(r0, 0) }          // (an odd tail step has nothing left to store: stage 0 may still be read)
-        __syncthreads();
-    }
-#undef PM_GLOAD
-#undef PM_LSTORE
-#undef PM_MMA
-}
-
-// v (this lane's 2 x 16 block values: column 64 wc + 32 j + li, rows 32 wr + (r&3) + 8 (r>>2) + 4 lh) -> limb image in the tile.
-// Adjacent lanes (columns c, c+1) pair their halves so that every lane writes one 32-bit word per element.
-__device__ __forceinline__ void pm_store_tile(char* smc, const float (&v)[2][16], int li, int lh, int wr, int wc, float& amax) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = 64 * wc + 32 * j + li;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float x = v[j][r];
-            amax = fmaxf(amax, fabsf(x));
-            const _Float16 h = (_Float16)x;
-            const _Float16 l = (_Float16)((x - (float)h) * 2048.0f);
-            const unsigned hb = __builtin_bit_cast(unsigned short, h), lb = __builtin_bit_cast(unsigned short, l);
-            const unsigned mine = (li & 1) ? lb : hb, give = (li & 1) ? hb : lb;      // even lane keeps hi, odd lane keeps lo'
-            const unsigned got = __shfl_xor(give, 1, 64);                              // even: neighbour's hi; odd: neighbour's lo'
-            const unsigned word = (li & 1) ? (got | (mine << 16)) : (mine | (got << 16));
-            const int row = 32 * wr + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int c0 = col & ~1;                                                   // the pair's even column
-            *reinterpret_cast<unsigned*>(smc + row * PM_APITCH + (c0 >> 4) * 64 + ((li & 1) ? 32 : 0) + (c0 & 15) * 2) = word;
-        }
-    }
-}
-
-#ifdef FC_DEV_VARIANTS      // (the LDS-tile form lost its A/B against the row-resident kernel below: developer builds only)
-__global__ __launch_bounds__(PM_NT) __attribute__((amdgpu_waves_per_eu(2))) void premlp_kernel(const PreMlpParams p) {
-    extern __shared__ float smem[];
-    char* smc = reinterpret_cast<char*>(smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5, wr = wave >> 2, wc = wave & 3;
-    const int row0 = blockIdx.x * PM_ROWS;
-    float amax = 0.f;
-
-    // ---- input rows -> limb image (columns >= in.K_pad are never read by the in_layer)
-    {
-        const int c4n = p.in.K_pad / 4;
-        for (int t = tid; t < PM_ROWS * c4n; t += PM_NT) {
-            const int row = t / c4n, c = (t - row * c4n) * 4;
-            const float4 x = *reinterpret_cast<const float4*>(p.x + (size_t)(row0 + row) * p.ldx + c);
-            const float xs[4] = {x.x, x.y, x.z, x.w};
-            typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-            f16x4 h, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                amax = fmaxf(amax, fabsf(xs[e]));
-                h[e] = (_Float16)xs[e];
-                l[e] = (_Float16)((xs[e] - (float)h[e]) * 2048.0f);
-            }
-            char* dst = smc + row * PM_APITCH + (c >> 4) * 64 + (c & 15) * 2;
-            *reinterpret_cast<f16x4*>(dst) = h;
-            *reinterpret_cast<f16x4*>(dst + 32) = l;
-        }
-    }
-    __syncthreads();
-
-    floatx16 accm[2], accc[2];
-    float keep[2][16];                                     // h0: residual of the second hidden layer (models/nets.py:24-29)
-    float v[2][16];
-
-    // ---- in_layer, hidden layer 0 (keep = x; x = act(W x)), hidden layer 1 (x = act(keep + W x)), out_layer (no activation)
-#pragma unroll 1
-    for (int layer = 0; layer < 4; ++layer) {
-        const PreMlpLayer& L = layer == 0 ? p.in : layer == 1 ? p.mid0 : layer == 2 ? p.mid1 : p.out;
-        pm_gemm<256>(L, smc, tid, li, lh, wr, wc, accm, accc);      // ends with a barrier: every wave is done reading the tile
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float b = L.bias[64 * wc + 32 * j + li];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float t = accm[j][r] + accc[j][r] * (1.0f / 2048.0f) + b;
-                if (layer == 2) t += keep[j][r];
-                v[j][r] = layer == 3 ? t : act_apply(t, p.act);
-                if (layer == 0) keep[j][r] = v[j][r];
-            }
-        }
-        if (layer < 3) {
-            pm_store_tile(smc, v, li, lh, wr, wc, amax);
-            __syncthreads();
-        }
-    }
-
-    // ---- LayerNorm over the 256 columns of each row (biased variance, eps 1e-5; gamma / beta live in the q projection)
-    float* red = reinterpret_cast<float*>(smc + PM_RED_OFF);
-    float mean[16], rstd[16];
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float t = 0.f;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float d = pass == 0 ? v[j][r] : v[j][r] - mean[r];
-                t += pass == 0 ? d : d * d;
-            }
-            t = half_wave_sum(t);
-            if (li == 0) red[(32 * wr + (r & 3) + 8 * (r >> 2) + 4 * lh) * 4 + wc] = t;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float4 q4 = *reinterpret_cast<const float4*>(red + (32 * wr + (r & 3) + 8 * (r >> 2) + 4 * lh) * 4);
-            const float tot = (q4.x + q4.y) + (q4.z + q4.w);
-            if (pass == 0) mean[r] = tot * (1.0f / PM_H); else rstd[r] = 1.0f / sqrtf(tot * (1.0f / PM_H) + 1e-5f);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[j][r] = (v[j][r] - mean[r]) * rstd[r];
-    pm_store_tile(smc, v, li, lh, wr, wc, amax);
-    __syncthreads();
-
-    // ---- q projection 256 -> 64 (4 of the 8 waves multiply; all of them stage the weights)
-    pm_gemm<64>(p.q, smc, tid, li, lh, wr, wc, accm, accc);
-    if (wc < 2) {
-        const int col = 32 * wc + li;
-        const float b = p.q.bias ? p.q.bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = row0 + 32 * wr + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            p.qout[(size_t)row * p.ldq + col] = accm[0][r] + accc[0][r] * (1.0f / 2048.0f) + b;
-        }
-    }
-    if (amax >= 65504.0f) atomicOr(p.ovf, 1);
-}
-#endif      // FC_DEV_VARIANTS
+constexpr int PM_H = 256;                                  // hidden width = attention input width
 
 // =====================================================================================================================================
-// Row-resident variant (knob 8 = 2): the chain's activations never leave the REGISTERS.
+// The row-resident kernel (knob 8 = 2): the chain's activations never leave the REGISTERS.
 //   The product is transposed (weights as the MFMA's A operand, points as B) on the 16x16x32 shape: a wave owns 16 points, a point is
 //   spread over the four lanes n, n + 16, n + 32, n + 48 (lane row kg = lane >> 4 supplies in-features 32 s + 8 kg + 0..7 of k step s).
 //   Per lane: the layer's input as B-operand fragments (8 k steps x [hi | lo'] x 8 fp16 = 64 registers), the output being assembled in
@@ -264,7 +56,7 @@ __global__ __launch_bounds__(PM_NT) __attribute__((amdgpu_waves_per_eu(2))) void
 //   and is split into limbs in place.  LayerNorm is an in-lane sum plus two cross-row adds.
 //   Only the weights move: a chunk = 32 out-features x K as one LDS stage (32 KB at K = 256: a 1 KiB DMA piece is one weight row;
 //   16-byte chunks XOR-swizzled by (row & 15) on the source address and on the read), two stages, 48 MFMAs per wave and barrier.
-//   The 1.3 MB of weights are streamed once per 128 rows (the LDS-tile kernel above: per 64) and, with no activation tile in LDS, a
+//   The 1.3 MB of weights are streamed once per 128 rows (the LDS-tile kernel it replaced: per 64) and, with no activation tile in LDS, a
 //   stage is 4x as long per barrier.
 constexpr int PR_ROWS = 128, PR_NT = 512, PR_CH = 32;
 constexpr int PR_BUF = PR_CH * PM_H * 4;                    // 32 KB: one chunk of 32 weight rows at K = 256
@@ -290,9 +82,6 @@ __device__ __forceinline__ void pr_swap16(float& a, float& b) { asm volatile("s_
 // one 64-bit add per piece on precomputed lane offsets), and for the other lengths the division is a multiply + shift in 32 bits.
 template <int CPRH>
 __device__ __forceinline__ void pr_dma(const PreMlpLayer& L, int c, char* dst, int wave, int lane, int grp) {
-#ifdef FC_PREMLP_DMA_LATE
-    const int first = wave, step = 8;                        // experiment: every wave issues its share, BEHIND its chunk's reads and MFMAs (see chunk_mma)
-#else
     if ((wave >> 2) != grp) return;
     const int first = wave & 3, step = 4;
     if constexpr (CPRH == 64) {
@@ -314,7 +103,6 @@ __device__ __forceinline__ void pr_dma(const PreMlpLayer& L, int c, char* dst, i
         }
         return;
     }
-#endif
     const int cpr = L.K_pad >> 2;                            // 16-byte chunks per weight row (64 at K = 256, 40 at K = 160)
     const int sw = (cpr & 15) == 0 ? 15 : 7;
     const int npieces = cpr >> 1;                            // 32 rows * cpr chunks / 64 lanes
@@ -411,19 +199,6 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     PR_STAMP(1)
 
     int buf = 0;                                             // stage that holds (is receiving) the chunk about to be multiplied
-    // diagnostic build (-DFC_PREMLP_WAIT_STAMPS, profiles/micro/premlp_rows_stamps.py): cycles this wave waited for its DMA pieces / at the chunk
-    // barriers.  Not in the shipped build: the two counters cost the kernel its last registers (248 bytes of scratch per lane).
-#ifdef FC_PREMLP_WAIT_STAMPS
-    unsigned long long t_vm = 0, t_bar = 0, tw0 = 0, tw1 = 0;
-#define PR_WAIT_T0 tw0 = __builtin_amdgcn_s_memtime();
-#define PR_WAIT_T1 tw1 = __builtin_amdgcn_s_memtime();
-#define PR_WAIT_T2 { const unsigned long long tw2 = __builtin_amdgcn_s_memtime(); t_vm += tw1 - tw0; t_bar += tw2 - tw1; }
-#else
-#define PR_WAIT_T0
-#define PR_WAIT_T1
-#define PR_WAIT_T2
-#endif
-
     // MFMAs of one chunk: (am, ac) = W[32 c .. 32 c + 31][:] . act  (main / cross-product accumulators of the two 16-feature blocks)
     auto chunk_mma = [&](const PreMlpLayer& L, const PreMlpLayer* nextL, int nextc, auto fullk_tag, floatx4 (&am)[2], floatx4 (&ac)[2], auto&& after_dma) __attribute__((always_inline)) {
         constexpr int KSTAT = decltype(fullk_tag)::value;             // compile-time k steps (8 for the 256-wide layers): the k loop is ONE basic block; 0 = run time
@@ -431,17 +206,12 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
             for (int i = 0; i < 4; ++i) { am[mb][i] = 0.f; ac[mb][i] = 0.f; }
-        PR_WAIT_T0
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // own pieces of this chunk have landed
-        PR_WAIT_T1
         __builtin_amdgcn_s_barrier();                                   // ... everybody's; everybody is done reading the other stage
-        PR_WAIT_T2
-#ifndef FC_PREMLP_DMA_LATE
         if (nextL) {                                                    // (the next chunk is this layer's, or -- a layer's last chunk -- the first of a 256-wide layer: premlp_fusable)
             if (nextL == &L) pr_dma<KSTAT * 8>(L, nextc, smc + (buf ^ 1) * PRB, wave, lane, grp);
             else pr_dma<64>(*nextL, nextc, smc + (buf ^ 1) * PRB, wave, lane, grp);
         }
-#endif
         grp ^= 1;
         after_dma();                                                    // (loads that must not sit in front of the wait above: they get this chunk's time to land)
         if constexpr (KSTAT > 0) {
@@ -466,12 +236,6 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                     ac[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, al[s_], ac[mb], 0, 0, 0);
                 }
             }
-#ifdef FC_PREMLP_DMA_LATE
-            if (nextL) {                                                    // (the next chunk is this layer's, or -- a layer's last chunk -- the first of a 256-wide layer: premlp_fusable)
-            if (nextL == &L) pr_dma<KSTAT * 8>(L, nextc, smc + (buf ^ 1) * PRB, wave, lane, grp);
-            else pr_dma<64>(*nextL, nextc, smc + (buf ^ 1) * PRB, wave, lane, grp);
-        }
-#endif
             buf ^= 1;
             return;
         }
@@ -493,12 +257,6 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                 }
             }
         }
-#ifdef FC_PREMLP_DMA_LATE
-        if (nextL) {                                                    // (the next chunk is this layer's, or -- a layer's last chunk -- the first of a 256-wide layer: premlp_fusable)
-            if (nextL == &L) pr_dma<KSTAT * 8>(L, nextc, smc + (buf ^ 1) * PRB, wave, lane, grp);
-            else pr_dma<64>(*nextL, nextc, smc + (buf ^ 1) * PRB, wave, lane, grp);
-        }
-#endif
         buf ^= 1;
     };
     // accumulator order (block mb, register i = feature 16 mb + 4 kg + i) -> operand order: t[e] = out-feature 32 c + 8 kg + e (before bias)
@@ -599,15 +357,10 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { am[mb][i] = 0.f; ac[mb][i] = 0.f; }
-            PR_WAIT_T0
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // own pieces of this chunk have landed
-            PR_WAIT_T1
             __builtin_amdgcn_s_barrier();                                   // ... everybody's; everybody is done reading the other stage
-            PR_WAIT_T2
-#ifndef FC_PREMLP_DMA_LATE
             if (c + 1 < NLU) pr_dma<NLU * 8>(p.lu, c + 1, smc + (buf ^ 1) * PRB, wave, lane, grp);
             else pr_dma<KSIN * 8>(p.in, 0, smc + (buf ^ 1) * PRB, wave, lane, grp);
-#endif
             grp ^= 1;
             constexpr int cpr = NLU * 8;                                    // 16-byte chunks per weight row
             constexpr bool SW4 = (cpr & 15) == 0;
@@ -629,10 +382,6 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                     ac[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ul[s_], ac[mb], 0, 0, 0);
                 }
             }
-#ifdef FC_PREMLP_DMA_LATE
-            if (c + 1 < NLU) pr_dma<NLU * 8>(p.lu, c + 1, smc + (buf ^ 1) * PRB, wave, lane, grp);
-            else pr_dma<KSIN * 8>(p.in, 0, smc + (buf ^ 1) * PRB, wave, lane, grp);
-#endif
             buf ^= 1;
         };
         auto lu_finish = [&](const float (&t)[8], int c) __attribute__((always_inline)) {       // chunk c >= 0 (wave-uniform)
@@ -737,20 +486,11 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     if (amax >= 65504.0f) atomicOr(p.ovf, 1);
     PR_STAMP(7)
     if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 16 + 15] = wall_clock64();
-#ifdef FC_PREMLP_WAIT_STAMPS
-    if (p.stamps && (threadIdx.x == 0 || threadIdx.x == 256)) {      // (wave 0: issues the even chunks' pieces; wave 4: the odd ones')
-        p.stamps[(size_t)blockIdx.x * 16 + 8 + 2 * (threadIdx.x >> 8)] = t_vm;
-        p.stamps[(size_t)blockIdx.x * 16 + 9 + 2 * (threadIdx.x >> 8)] = t_bar;
-    }
-#endif
-#undef PR_WAIT_T0
-#undef PR_WAIT_T1
-#undef PR_WAIT_T2
 #undef PR_STAMP
 }
 
 int g_premlp_fused = 2;       // tuning knob (fc_debug_set 8): 2 = the row-resident kernel (activations in registers; shipped: 190 us against ~250 us for the
-                              // five launches it replaces, -1.4 ... -2 % per C2 step), 1 = the LDS-tile kernel (263 us: one 64-row workgroup per CU
+                              // five launches it replaces, -1.4 ... -2 % per C2 step; the removed LDS-tile kernel, value 1, took 263 us: one 64-row workgroup per CU
                               // re-streams every layer's weights from L2, 16 % MFMA busy), 0 = separate GEMM launches + the LayerNorm -> q fold
 
 static bool premlp_layer_ok(const PackedLinear& L, int n, int kmax) {
@@ -781,19 +521,15 @@ int g_premlp_lu = 1;          // knob 26: 1 = the previous layer's folded ActNor
 // true when `lu` (the previous flow layer's folded ActNorm + permuter, latent pitch ldx) can run as the pre-layer of this pre-conditioner's
 // row-resident kernel: square 320 x 320 in the latent's padded layout, the in_layer reading its first 160 columns, GELU (the instantiated case)
 bool premlp_lu_fusable(const PackedLinear& lu, const PackedLinear& in, int act, int ldx) {
-    return g_premlp_lu && (g_premlp_fused == 2 || !kDevVariants) && act == FC_ACT_GELU && lu.W2 != nullptr && lu.bias != nullptr && lu.nseg == 1 && lu.K_pad == 320 && lu.N_pad == 320 && ldx == 320 &&
+    return g_premlp_lu && act == FC_ACT_GELU && lu.W2 != nullptr && lu.bias != nullptr && lu.nseg == 1 && lu.K_pad == 320 && lu.N_pad == 320 && ldx == 320 &&
            lu.n_alloc >= 320 && in.K_pad == 160;
 }
 
 void launch_premlp(const float* x, int ldx, const PackedLinear& in, const std::vector<PackedLinear>& mid, const PackedLinear& out,
                    const PackedLinear& q, int act, float* qout, int ldq, int rows_alloc, int rows_valid, hipStream_t s, float* keep_ws, size_t keep_floats,
                    const PackedLinear* lu, const float* xprev) {
-    if (rows_alloc % PM_ROWS != 0 || ldx % 4 != 0 || ldx < in.K_pad || ((uintptr_t)x & 15))
+    if (rows_alloc % 64 != 0 || ldx % 4 != 0 || ldx < in.K_pad || ((uintptr_t)x & 15))
         throw Error(FC_ERR_INVALID, "premlp: rows must be padded to 64, input pitch to 4 floats");
-#ifdef FC_DEV_VARIANTS
-    static PerDeviceOnce attr_once;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(premlp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PM_LDS)); return 0; });
-#endif
     PreMlpParams p{};
     p.x = x; p.ldx = ldx;
     auto L = [](const PackedLinear& l) { return PreMlpLayer{l.W2, l.bias, l.K_pad}; };
@@ -802,7 +538,7 @@ void launch_premlp(const float* x, int ldx, const PackedLinear& in, const std::v
     p.stamps = g_gemm_stamp == 3 ? gemm_stamp_buffer((size_t)(rows_alloc / PR_ROWS) * 16) : nullptr;
     const double rv = rows_valid > 0 ? rows_valid : rows_alloc;
     double flops = 2.0 * rv * ((double)in.k_true * PM_H + 3.0 * PM_H * PM_H + (double)PM_H * (q.n_true ? q.n_true : 64));
-    if ((g_premlp_fused == 2 || !kDevVariants) && premlp_rows_ok(rows_alloc, ldq, qout, keep_ws, keep_floats)) {
+    if (premlp_rows_ok(rows_alloc, ldq, qout, keep_ws, keep_floats)) {
         if (lu) {
             // the previous layer's ActNorm + LU as a pre-layer: x (this layer's latent buffer) is WRITTEN here, xprev is read
             if (!premlp_lu_fusable(*lu, in, act, ldx) || !xprev || ((uintptr_t)xprev & 15))
@@ -837,13 +573,7 @@ void launch_premlp(const float* x, int ldx, const PackedLinear& in, const std::v
         return;
     }
     if (lu) throw Error(FC_ERR_INVALID, "launch_premlp: the ActNorm + LU pre-layer exists in the row-resident kernel only");
-#ifdef FC_DEV_VARIANTS
-    ProfScope ps("fc::premlp_kernel(fc::PreMlpParams)", flops, 0.0, s);
-    hipLaunchKernelGGL(premlp_kernel, dim3(rows_alloc / PM_ROWS), dim3(PM_NT), PM_LDS, s, p);
-    FC_HIP(hipGetLastError());
-#else
     throw Error(FC_ERR_UNSUPPORTED, "launch_premlp: the row-resident kernel's launch conditions do not hold (callers check premlp_rows_ok)");
-#endif
 }
 
 }  // namespace fc

@@ -99,7 +99,6 @@ __global__ __launch_bounds__(256) void spline_wide_image_kernel(const float* __r
     if (k == 0 && bias1) bias1[row] = live && bias ? bias[srow] * bscale : 0.f;
 }
 
-int g_spline_wide_dma = 0;   // developer knob 27 (--dev builds): DMA pieces per phase, 0 = {2,3,3,0} / {2,3,3,0} (shipped: -1.5 % against {1,3,3,1} / {2,3,3,0}, same box)
 int g_spline_wide_colgroup = -1;   // knob 28: column-group size of the tile order in 256-column tiles (-1 = shipped: 5)
 
 // rows of 16 lanes (a0,a1,a2,a3 | b0,b1,b2,b3):  swap32 -> a = (a0,a1,b0,b1), b = (a2,a3,b2,b3) ;  swap16 -> a = (a0,b0,a2,b2), b = (a1,b1,a3,b3)
@@ -656,16 +655,9 @@ void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
     p.ablate = g_spline_ablate;
     if (g_spline_wide_colgroup >= 0) p.col_group = (p.nbm % 8 == 0 && p.nbn > g_spline_wide_colgroup) ? g_spline_wide_colgroup : 0;
     static PerDeviceOnce slots_once;
-    void (*kern)(const SplineWideParams) = spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>;
-    FC_DEV(if (g_spline_wide_dma == 1) kern = spline_wide_kernel<0, 2, 2, 2, 2, 3, 3, 2, 0>;
-           else if (g_spline_wide_dma == 2) kern = spline_wide_kernel<0, 0, 3, 3, 2, 3, 3, 2, 0>;
-           else if (g_spline_wide_dma == 3) kern = spline_wide_kernel<0, 1, 3, 3, 1, 2, 3, 3, 0>;
-           else if (g_spline_wide_dma == 4) kern = spline_wide_kernel<0, 1, 2, 3, 2, 2, 3, 3, 0>;)
-    {
-        static PerDeviceOnce attr_once[5];
-        attr_once[g_spline_wide_dma >= 0 && g_spline_wide_dma < 5 ? g_spline_wide_dma : 0].run(
-            [&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });
-    }
+    auto kern = spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>;
+    static PerDeviceOnce attr_once;
+    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });
     const int slots = slots_once.run([](int dev) {
         int cus = 0;
         FC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));

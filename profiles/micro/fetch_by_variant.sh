@@ -1,6 +1,6 @@
 #!/bin/bash
 # HBM-side read bytes per launch of the fused spline GEMM for several knob settings (short 8-layer C2 runs):
-#   bash profiles/micro/fetch_by_variant.sh "13=2" "13=3" "13=4" "13=4 2=8"
+#   bash profiles/micro/fetch_by_variant.sh "13=2" "13=4" "13=4 2=8"
 root=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 for kv in "$@"; do

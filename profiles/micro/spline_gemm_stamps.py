@@ -1,6 +1,6 @@
 """In-kernel phase stamps of the fused spline GEMM (diagnostic knob 20) on the C2 workload: where a workgroup's time goes.
 
-    python profiles/micro/spline_gemm_stamps.py [knob13 ...]        (default: 2 3)
+    python profiles/micro/spline_gemm_stamps.py [knob13 ...]        (default: 2 4)
 
 Per variant: runs two C2 steps with module-init weights (kernel work does not depend on the values), reads the stamps of the last
 fused-spline launch and prints per-phase shader cycles (mean over workgroups), the clock, the launch span, and the idle time between
@@ -20,7 +20,7 @@ args = sys.argv[1:]
 which = 2 if args and args[0] == "linear" else 1            # "linear": the limb-chained 512 -> 512 Linear launches (VAR 9) instead
 if which == 2:
     args = args[1:]
-variants = [int(v) for v in args] or ([4] if which == 2 else [2, 3])
+variants = [int(v) for v in args] or ([4] if which == 2 else [2, 4])
 cfg = fa.named_config("c2_dgcnn_attn_spline", sample_size=4096)
 torch.manual_seed(0)
 md = fa.initialize_flow(cfg, device=DEV, mode="test")

@@ -1,6 +1,6 @@
 """Same-box A/B of the wide fused spline kernel (spline_wide.hip) under fc_debug_set settings: a short C2 stack (8 layers, 16 x 4096 points), the
 in-library HIP-event profiler on, average launch duration of the fused spline kernel per setting, interleaved rounds.
-    python profiles/micro/wide_ab.py "" "27=1" "27=2" "28=3" "13=4"
+    python profiles/micro/wide_ab.py "" "28=3" "13=4"
 """
 import os
 import sys
@@ -21,7 +21,7 @@ batch = (e0.to(DEV), e1.to(DEV), None)
 ep = [eps.to(DEV)]
 lib = engine.lib()
 specs = sys.argv[1:] or [""]
-defaults = {13: 5, 27: 0, 28: -1, 2: 10, 14: 0}
+defaults = {13: 5, 28: -1, 2: 10, 14: 0}
 res = {s: [] for s in specs}
 for rnd in range(3):
     for spec in specs:

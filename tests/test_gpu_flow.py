@@ -244,15 +244,13 @@ def test_deferred_range_check_queues_forwards_back_to_back_and_still_repeats_out
     assert torch.isfinite(lp).all() and err < PER_POINT_TOL and err2 < PER_POINT_TOL
 
 
-def test_every_kernel_variant_agrees_on_the_c2_layer_stack():
+def test_every_kernel_variant_in_the_library_agrees_on_the_c2_layer_stack():
     """The shipped fast paths (split-fp16 GEMM on eight-wave tiles, fused spline epilogue, split-fp16 attention, row-resident chains)
     against the paths that stay in the library beside them -- the per-layer launches small batches take, the unfused spline of the inverse
-    direction, the bf16-limb range fallback, the fp32-input reference loop -- and, in a developer build (python -m flowcompare_amd.build
-    --dev), against every variant that lost an A/B: same log-probs within the fp32 noise of a 4-layer flow at the real layer widths, and
-    bit-identical ones where the arithmetic is the same.  A default build refuses the developer knob values: those cases are skipped."""
+    direction, the bf16-limb range fallback, the fp32-input reference loop: same log-probs within the fp32 noise of a 4-layer flow at the
+    real layer widths, and bit-identical ones where the arithmetic is the same.  Every case runs: a refused knob value fails the test."""
     from flowcompare_amd import engine
     lib = engine.lib()
-    dev = bool(lib.fc_debug_dev_variants())
     cfg = fa.named_config("c2_dgcnn_attn_spline", n_flow_layers=4, sample_size=300)
     torch.manual_seed(7)
     md = fa.initialize_flow(cfg, device=DEV, mode="test")
@@ -261,15 +259,13 @@ def test_every_kernel_variant_agrees_on_the_c2_layer_stack():
     e0, e1 = torch.rand(B, M, 6, generator=g), torch.rand(B, N, 6, generator=g)
     eps = [torch.randn(B, N, 294, generator=g).to(DEV)]
     batch = (e0.to(DEV), e1.to(DEV), None)
-    defaults = {0: 5, 3: 3, 5: 1, 7: 1, 8: 2, 9: 1, 10: 1, 13: 5, 15: 2, 16: 1, 17: 0, 19: 0, 21: 0, 22: 1, 23: 1, 29: 0}
+    defaults = {0: 5, 5: 1, 7: 1, 8: 2, 9: 1, 10: 1, 13: 5, 16: 1, 19: 0, 21: 0, 22: 1, 23: 1, 29: 0}
 
     def run_with(knobs):
-        """log-probs under the given knob values, or None when this build refuses one of them (a developer variant)"""
+        """log-probs under the given knob values"""
         try:
             for k, v in knobs.items():
-                if lib.fc_debug_set(k, v) != 0:
-                    assert not dev, f"knob {k} = {v} refused by a developer build"
-                    return None
+                assert lib.fc_debug_set(k, v) == 0, f"knob {k} = {v} refused"
             return fa.inner_loop(batch, md, cfg, eps=eps)[1]
         finally:
             for k in knobs:
@@ -277,18 +273,12 @@ def test_every_kernel_variant_agrees_on_the_c2_layer_stack():
 
     try:
         _, ref, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-        n_run = 0
-        for name, knobs in (("unfused spline", {7: 0}), ("LDS-tile pre-attention chain kernel", {8: 1}), ("separate pre-attention GEMM launches + LayerNorm -> q fold", {8: 0}), ("separate LayerNorm + q projection", {8: 0, 10: 0}), ("no limb chain", {9: 0}), ("limb chain into the spline GEMM only", {16: 0}), ("limb-chained pre-attention MLP", {8: 0, 19: 1}), ("limb-chained hidden layers on the register-staged tile", {15: 0}), ("limb-chained hidden layers on the 256x128 DMA tile", {15: 1}), ("fp32-input attention", {5: 0}),
-                            ("four-wave tile", {3: 0}), ("256x128 tile", {3: 2}), ("bf16-limb GEMM", {0: 3}), ("fp32-input MFMA GEMM", {0: 2})):
+        for name, knobs in (("unfused spline", {7: 0}), ("separate pre-attention GEMM launches + LayerNorm -> q fold", {8: 0}), ("separate LayerNorm + q projection", {8: 0, 10: 0}), ("no limb chain", {9: 0}), ("limb chain into the spline GEMM only", {16: 0}), ("limb-chained pre-attention MLP", {8: 0, 19: 1}), ("fp32-input attention", {5: 0}),
+                            ("bf16-limb GEMM", {0: 3}), ("fp32-input MFMA GEMM", {0: 2})):
             lp = run_with(knobs)
-            if lp is None:
-                print(f"{name}: developer variant, not in this build")
-                continue
-            n_run += 1
             err = (lp - ref).abs().max().item()
             print(f"{name}: max |log-prob - default path| {err:.2e}")
             assert err < 5e-4, name
-        assert n_run >= 9
         # the row-resident coupling-MLP chain (the engine takes it where a launch fills the chip; this batch is 3 row tiles: forced) issues the
         # same MFMAs in the same k order as the per-layer launches and adds bias, residual, GELU and limb split alike: bit-identical
         lp = run_with({23: 2})
@@ -300,31 +290,25 @@ def test_every_kernel_variant_agrees_on_the_c2_layer_stack():
         print(f"hidden layers on the wide one-accumulator kernel: max |log-prob - default path| {err:.2e}")
         assert err < 5e-4
         lp = run_with({23: 2, 16: 0})
-        assert lp is not None and (lp - ref).abs().max().item() < 5e-4
+        assert (lp - ref).abs().max().item() < 5e-4
         # round 4: the shipped fused spline layer is the 256 x 256 one-accumulator kernel on 16x16x32 MFMAs (spline_wide.hip, knob 13 = 5): another
         # arithmetic (one fp32 accumulator, unscaled low limbs, k32 MFMAs) than the 128 x 128 loops beside it -- same log-probs within fp32 noise
         ref4 = run_with({13: 4})
         err = (ref4 - ref).abs().max().item()
         print(f"persistent 128x128 fused spline GEMM (knob 13 = 4): max |log-prob - default path| {err:.2e}")
         assert err < 5e-4
-        # every main loop of the 128 x 128 family issues the same MFMAs in the same k order and hands the same parameters to the same
-        # spline arithmetic: the register-staged loop (0), the LDS-DMA loops with the LDS parameter tile (1: 256x128, 2: 128x128), the
-        # transposed product evaluated from the accumulator registers with one tile per workgroup (3) and the persistent form
-        # (4) give bit-identical log-probs
-        for v in (0, 1, 2, 3):
-            lp = run_with({13: v})
-            if lp is None:
-                continue
-            print(f"knob 13 = {v}: max |diff| {(lp - ref4).abs().max().item():.3e}")
-            assert torch.equal(lp, ref4), f"fused spline GEMM variant (knob 13 = {v}) differs from the persistent 128x128 loop"
+        # both main loops of the 128 x 128 family issue the same MFMAs in the same k order and hand the same parameters to the same
+        # spline arithmetic: the LDS-DMA loop with the LDS parameter tile (2) and the persistent transposed product evaluated from the
+        # accumulator registers (4) give bit-identical log-probs
+        lp = run_with({13: 2})
+        print(f"knob 13 = 2: max |diff| {(lp - ref4).abs().max().item():.3e}")
+        assert torch.equal(lp, ref4), "fused spline GEMM variant (knob 13 = 2) differs from the persistent 128x128 loop"
         lp = run_with({13: 4, 21: 1})                             # rotated k order: another fp32 summation order, same sums
         err = (lp - ref4).abs().max().item()
         print(f"persistent fused spline GEMM with rotated k loops: max |log-prob - knob 13 = 4| {err:.2e}")
         assert err < 5e-4
         lp = run_with({22: 0})                                    # 128x128 tiles also for launches with few tiles (this test: 5 row tiles -> 64x64 tiles by default)
         assert torch.equal(lp, ref), "64x64 tiles for small launches changed the limb-chained GEMMs' results"
-        lp = run_with({17: 1})                                    # three register sets of prefetch instead of two: same MFMAs, same order
-        assert lp is None or torch.equal(lp, ref), "prefetch depth changed the Linear GEMM's results"
     finally:
         for k, v in defaults.items():
             lib.fc_debug_set(k, v)
@@ -336,7 +320,7 @@ def test_persistent_spline_gemm_walks_several_tiles_per_workgroup():
     order, 24 x 15 = 360 on the column-group order (row tiles a multiple of 8) -- a scene's log-probs must not depend on where its tiles fall
     (bit for bit the run of that scene alone, one tile per workgroup), and must agree with the 128 x 128 persistent loop (knob 13 = 4: two
     workgroups per CU, 18 x 30 = 540 / 24 x 30 = 720 tiles) within fp32 noise.  That loop in turn must come out exactly as the
-    one-tile-per-workgroup kernels of its family."""
+    one-tile-per-workgroup kernel of its family (knob 13 = 2: the LDS-DMA loop with the LDS parameter tile)."""
     from flowcompare_amd import engine
     lib = engine.lib()
     for B, N in ((3, 768), (3, 1000), (3, 1600), (3, 2048)):       # 2304 rows; 3000 rows + 72 padding rows; 4800 rows = 19 tiles of 256; 6144 = 24
@@ -362,11 +346,9 @@ def test_persistent_spline_gemm_walks_several_tiles_per_workgroup():
             err = (ref4 - ref).abs().max().item()
             print(f"{B} x {N}: wide kernel vs the 128 x 128 persistent loop: max |diff| {err:.2e}")
             assert err < 1e-3
-            for v in (3, 2):
-                if lib.fc_debug_set(13, v) != 0:                   # (3 = one tile per workgroup: a developer variant, refused by a default build)
-                    continue
-                _, lp, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-                assert torch.equal(lp, ref4), f"{B} x {N}: persistent fused spline GEMM differs from knob 13 = {v}"
+            assert lib.fc_debug_set(13, 2) == 0
+            _, lp, _ = fa.inner_loop(batch, md, cfg, eps=eps)
+            assert torch.equal(lp, ref4), f"{B} x {N}: persistent fused spline GEMM differs from knob 13 = 2"
         finally:
             lib.fc_debug_set(13, 5)
         assert torch.isfinite(ref).all()

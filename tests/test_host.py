@@ -78,6 +78,26 @@ def test_library_exports_every_declared_symbol():
     assert lib.fc_abi_version() == engine.ABI_VERSION
 
 
+def test_debug_knobs_accept_kept_values_and_refuse_removed_ones():
+    """fc_debug_set (csrc/ops_api.cpp, host code only) takes the shipped and kept values of the kernel-choice knobs; the values of the
+    variants that lost an A/B and were removed come back FC_ERR_UNSUPPORTED, the retired keys FC_ERR_INVALID."""
+    FC_ERR_INVALID, FC_ERR_UNSUPPORTED = 1, 6
+    lib = ctypes.CDLL(engine.LIB_PATH)
+    defaults = {0: 5, 8: 2, 13: 5}
+    try:
+        for key, kept, removed in ((0, (2, 3, 5), (0, 1, 4, 6, 7)), (8, (0, 2), (1,)), (13, (2, 4, 5), (0, 1, 3))):
+            for v in kept:
+                assert lib.fc_debug_set(key, v) == 0, (key, v)
+            for v in removed:
+                assert lib.fc_debug_set(key, v) == FC_ERR_UNSUPPORTED, (key, v)
+        for key in (3, 15, 17, 27, 30):
+            for v in (0, 1, 2, 3):
+                assert lib.fc_debug_set(key, v) == FC_ERR_INVALID, (key, v)
+    finally:
+        for key, v in defaults.items():
+            assert lib.fc_debug_set(key, v) == 0
+
+
 def test_no_cpu_fallback():
     """The product path must fail loudly without a HIP device; it must never route through PyTorch or the oracle."""
     fx = Fixture("e2e_tiny_affine")

@@ -321,6 +321,12 @@ void launch_attention_c16(const float* q, int ldq, const unsigned short* kv_c16,
                           int n_stride_rows, int M, int m_stride_rows, int dh_pad, hipStream_t s, const AttnLnq* lnq = nullptr);
 void launch_attention_op(const float* q, const float* k, const float* v, float* out, int B, int N, int M, int dh_pad, float scale,
                          void* limb_ws, hipStream_t s);
+// attention_weights.hip: out[b, p, :] = softmax row of query sel[b, p] (null sel: query p, P == N) over the M keys, dense [B][P][M].  K is the fp32
+// panel k, or -- kv_c16 non-null -- columns [c16_col0, c16_col0 + dh_pad) of a GEMM limb-image output with c16_n_pad columns per row in the
+// one-accumulator form (what launch_attention_c16 reads); lnq as for launch_attention_c16.  No range check on sel on the device.
+void launch_attention_weights(const float* q, int ldq, const float* k, int ldk, const unsigned short* kv_c16, int c16_n_pad, int c16_col0,
+                              float* out, const int32_t* sel, int P, int sel_per_scene, int B, int N, int n_stride_rows, int M, int m_stride_rows,
+                              int dh_pad, float qscale, const AttnLnq* lnq, hipStream_t s);
 void launch_base_density(const float* x, int ldx, int d1, int d1_pad, int d2, float* logprob, float log_const,
                          float* z_out, int D, int rows, hipStream_t s);
 void launch_spline(const float* params, int ldp, float* xbuf, int ldx, int x2_col0, int d2, int K, float* logprob, int rows, int inverse,

@@ -529,6 +529,7 @@ struct FlowWs {
     unsigned short* h16;   // fp16 limb image of the last hidden activation feeding the spline parameter GEMM (limb chain)
     int P, P_pad, Pc, Pc_pad, ldkv;
     int spl_rows;          // rows of w.spl: P_pad, or the row chunk of the wide ExponentialCoupling (expm_chunk_rows)
+    float* lp_scratch;     // [P_pad] log-prob accumulator of a pass whose caller wants none (fc_flow_attention_weights_f32 with logprob = NULL)
 };
 // Log-det partial slots (rows of FlowWs::ldjp): one per 128-column tile of the fused spline epilogue, two (one per wave column)
 // per 128-column tile of a pair-packed epilogue (affine coupling, augmenter, CIF slice) on the 8-wave split-fp16 tile.  The
@@ -580,6 +581,7 @@ static FlowWs plan_ws(const fc_flow& f, int B, int N, int M, void* ws, size_t by
     w.h16 = (unsigned short*)c.bytes((size_t)w.P_pad * std::max(d.H_pad, 32) * 4);
     w.lnss = c.floats(f.n_attn > 0 ? (size_t)(std::max(d.A_in, 64) / 64) * w.P_pad : 1);
     w.kv16 = c.bytes(f.n_attn > 0 ? std::max<size_t>(attention_limb_ws_bytes(w.Pc_pad, d.I_pad), 16) : 16);
+    w.lp_scratch = c.floats((size_t)w.P_pad);
     if (need) *need = c.off + 256;
     return w;
 }
@@ -625,10 +627,31 @@ static bool attention_takes_lu(const fc_flow& f, const PackedMLP& pre, const Att
            premlp_rows_ok(w.P_pad, d.I_pad, w.q, w.h[0], (size_t)w.P_pad * ldh) && premlp_lu_fusable(lu, pre.in_layer, act, d.ldx);
 }
 
+// Attention probe (fc_flow_attention_weights_f32): the softmax rows of the selected target points at the requested attentions, written by
+// attention_weights.hip next to the layer's attention launch.  Layer id -1 = the augmenter's attention, l >= 0 = flow layer l's pre-conditioner.
+// Owns its tables: a pass deferred by the range check may run again after the entry point has returned.
+struct AttnProbe {
+    std::vector<int> layers;
+    std::vector<float*> out;        // one [B][P][M] device buffer per entry of `layers`
+    const int32_t* sel = nullptr;   // device [P] or [B][P]; null = all N points
+    int P = 0, sel_per_scene = 0;
+};
+constexpr int kNoProbeLayer = -2;
+
 static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack& at, const ASeg& in, FlowWs& w, int act, int B, int N, int M,
-                          hipStream_t s, const PackedLinear* lu = nullptr, const float* xprev = nullptr) {
+                          hipStream_t s, const PackedLinear* lu = nullptr, const float* xprev = nullptr, const AttnProbe* probe = nullptr,
+                          int probe_layer = kNoProbeLayer) {
     const Dims& d = f.d;
     const int ldh = std::max(d.H_pad, 32);
+    // q is complete in w.q (with `lq`: up to rstd and the bias the consumer applies on load); K as the forward left it (prepare)
+    auto probe_here = [&](const AttnLnq* lq) {
+        if (!probe) return;
+        for (size_t i = 0; i < probe->layers.size(); ++i)
+            if (probe->layers[i] == probe_layer)
+                launch_attention_weights(w.q, d.I_pad, w.kv_limbs ? nullptr : w.kv + at.kv_col, w.ldkv,
+                                         w.kv_limbs ? reinterpret_cast<const unsigned short*>(w.kv) : nullptr, w.ldkv, at.kv_col, probe->out[i],
+                                         probe->sel, probe->P, probe->sel_per_scene, B, N, N, M, M, d.I_pad, 1.0f, lq, s);
+    };
     if (premlp_fusable(pre.in_layer, pre.mid, pre.out_layer, at.q) && in.lda >= pre.in_layer.K_pad &&
         premlp_rows_ok(w.P_pad, d.I_pad, w.q, w.h[0], (size_t)w.P_pad * ldh)) {
         // the whole chain x1 -> MLP -> LayerNorm -> q in one kernel: the activations stay in registers (premlp.hip); with `lu` the
@@ -651,10 +674,12 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
             if (w.kv_limbs) {
                 // the attention kernel applies rstd and the bias while it loads its queries
                 const AttnLnq lq{w.lnss, d.A_in / 64, (size_t)w.P_pad, 1.0f / (float)d.A_in, at.q_bias};
+                probe_here(&lq);
                 launch_attention_c16(w.q, d.I_pad, reinterpret_cast<const unsigned short*>(w.kv), w.ldkv, at.kv_col, w.a, d.I_pad, B, N, N, M, M,
                                      d.I_pad, s, &lq);
             } else {
                 launch_lnq_finalize(w.q, d.I_pad, w.lnss, d.A_in / 64, (size_t)w.P_pad, d.A_in, at.q_bias, w.P, s);
+                probe_here(nullptr);
                 launch_attention(w.q, d.I_pad, w.kv + at.kv_col, w.ldkv, w.kv + at.kv_col + d.I_pad, w.ldkv, w.a, d.I_pad, B, N, N, M, M, d.I_pad,
                                  w.kv16, s);
             }
@@ -672,13 +697,15 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
         ASeg aq{w.h[o], ldh};
         launch_gemm(at.q, &aq, w.P_pad, eq, EPI_LINEAR, s);
     }
+    probe_here(nullptr);
     if (w.kv_limbs) launch_attention_c16(w.q, d.I_pad, reinterpret_cast<const unsigned short*>(w.kv), w.ldkv, at.kv_col, w.a, d.I_pad, B, N, N, M, M, d.I_pad, s);
     else launch_attention(w.q, d.I_pad, w.kv + at.kv_col, w.ldkv, w.kv + at.kv_col + d.I_pad, w.ldkv, w.a, d.I_pad, B, N, N, M, M, d.I_pad, w.kv16, s);
 }
 
 // the conditioned coupling of one block (PreConditionApplier, models/transform.py:47-58), forward or inverse, in place on xc
 static void run_coupling(fc_flow& f, const BlockPack& b, FlowWs& w, float* xc, const float* rowscal, float* logprob, bool inverse, int B, int N,
-                         int M, hipStream_t s, const PackedLinear* lu = nullptr, const float* xprev = nullptr, int trace_layer = -1) {
+                         int M, hipStream_t s, const PackedLinear* lu = nullptr, const float* xprev = nullptr, int trace_layer = -1,
+                         const AttnProbe* probe = nullptr) {
     const Dims& d = f.d;
     const fc_flow_config& c = f.cfg;
     const int ldh = std::max(d.H_pad, 32);
@@ -686,7 +713,8 @@ static void run_coupling(fc_flow& f, const BlockPack& b, FlowWs& w, float* xc, c
     segs[0] = {xc, d.ldx};
     if (b.has_attn) {
         // CIFblock builds its pre_attention_mlp with GELU regardless of the configured nonlinearity (cif_block.py:61)
-        run_attention(f, b.pre, b.attn, segs[0], w, b.has_cif ? (int)FC_ACT_GELU : c.nonlinearity, B, N, M, s, lu, xprev);
+        run_attention(f, b.pre, b.attn, segs[0], w, b.has_cif ? (int)FC_ACT_GELU : c.nonlinearity, B, N, M, s, lu, xprev, probe,
+                      trace_layer >= 0 ? trace_layer : kNoProbeLayer);
         segs[1] = {w.a, d.I_pad};
     } else {
         if (lu) throw Error(FC_ERR_INVALID, "run_coupling: a pending ActNorm + LU pre-layer needs an attention pre-conditioner");
@@ -814,15 +842,16 @@ static Prep prepare(fc_flow& f, const float* ctx, const float* extra, int B, int
 static int expected_noise(const fc_flow& f) { return (f.has_augment ? 1 : 0) + (f.d.nz > 0 ? f.cfg.n_flow_layers : 0); }
 
 static void flow_forward(fc_flow& f, const float* x, const float* ctx, const float* extra, const float* const* eps, int n_eps,
-                         float* logprob, float* z_out, int B, int N, int M, void* ws, size_t ws_bytes, hipStream_t s) {
+                         float* logprob, float* z_out, int B, int N, int M, void* ws, size_t ws_bytes, hipStream_t s, const AttnProbe* probe = nullptr) {
     const Dims& d = f.d;
     const fc_flow_config& c = f.cfg;
-    if (!x || !logprob) throw Error(FC_ERR_INVALID, "null x / logprob");
+    if (!x || (!logprob && !probe)) throw Error(FC_ERR_INVALID, "null x / logprob");
     if (n_eps != expected_noise(f)) throw Error(FC_ERR_INVALID, "wrong number of noise tensors");
     for (int i = 0; i < n_eps; ++i) if (!eps || !eps[i]) throw Error(FC_ERR_INVALID, "null noise tensor");
     Prep pr = prepare(f, ctx, extra, B, N, M, ws, ws_bytes, s);
     FlowWs& w = pr.w;
     const int ldh = std::max(d.H_pad, 32);
+    if (!logprob) logprob = w.lp_scratch;          // (a probe call that wants no log-prob: the pass still accumulates one)
     if (f.expm_status) FC_HIP(hipMemsetAsync(f.expm_status, 0, sizeof(int), s));
     int eps_i = 0;
 
@@ -839,7 +868,7 @@ static void flow_forward(fc_flow& f, const float* x, const float* ctx, const flo
         launch_pack_rows(x, d.Din, n1, xc, d.ldx, 0, n1, w.P, s);
         if (d.Din > n1) launch_pack_rows(x + n1, d.Din, d.Din - n1, xc, d.ldx, d.d1_pad, d.Din - n1, w.P, s);
         ASeg in{w.xin, 32};
-        run_attention(f, f.aug_pre, f.aug_attn, in, w, c.nonlinearity, B, N, M, s);
+        run_attention(f, f.aug_pre, f.aug_attn, in, w, c.nonlinearity, B, N, M, s, nullptr, nullptr, probe, -1);
         ASeg segs[2] = {{w.xin, 32}, {w.a, d.I_pad}};
         const int cur = run_mlp_hidden(f, f.aug_net, segs, pr.rowscal, w, c.nonlinearity, s);
         GemmEpi e{};
@@ -867,7 +896,7 @@ static void flow_forward(fc_flow& f, const float* x, const float* ctx, const flo
         // `pend`: the previous layer's folded ActNorm + permuter, not launched yet -- it runs as the pre-layer of this layer's row-resident
         // pre-attention kernel, reading xc and writing xn, which becomes this layer's latent
         if (pend) std::swap(xc, xn);
-        run_coupling(f, b, w, xc, pr.rowscal, logprob, false, B, N, M, s, pend, pend ? xn : nullptr, l);
+        run_coupling(f, b, w, xc, pr.rowscal, logprob, false, B, N, M, s, pend, pend ? xn : nullptr, l, probe);
         pend = nullptr;
         if (b.has_lin) {
             const bool next_takes_it = l + 1 < c.n_flow_layers && f.blocks[l + 1].has_attn && !f.blocks[l + 1].has_cif &&
@@ -1012,6 +1041,43 @@ int fc_flow_logprob_f32(fc_flow* flow, const float* x, const float* ctx, const f
     const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
     fc::run_fp16_guarded(flow->fp16_flag, (hipStream_t)stream, [=] {
         fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, z_out, B, N, M, workspace, workspace_bytes, (hipStream_t)stream);
+    }, true);
+    fc::check_expm_status(*flow, (hipStream_t)stream);
+    FC_API_END
+}
+
+int fc_flow_attention_weights_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int32_t n_eps,
+                                  const int32_t* layers, int32_t n_layers, const int32_t* sel, int32_t P, int32_t sel_per_scene, float* const* out,
+                                  float* logprob, int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
+    FC_API_BEGIN
+    if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: null flow / workspace");
+    if (n_layers < 1 || !layers || !out) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: no layers requested (layers / out are null or n_layers < 1)");
+    if (!sel) P = N;
+    if (P < 1) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: P must be positive");
+    // every request is checked before anything is launched
+    fc::AttnProbe probe;
+    probe.sel = sel; probe.P = P; probe.sel_per_scene = sel ? (sel_per_scene != 0) : 0;
+    for (int i = 0; i < n_layers; ++i) {
+        const int l = layers[i];
+        if (!out[i]) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: null output buffer for request " + std::to_string(i));
+        if (l == -1) {
+            if (!flow->has_augment)
+                throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: layer -1 (the augmenter's attention) does not exist: this flow's first transform "
+                                                "is IdentityTransform (latent_dim == input_dim)");
+        } else if (l < 0 || l >= flow->cfg.n_flow_layers) {
+            throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: layer id " + std::to_string(l) + " is out of range: valid ids are -1 (augmenter) and 0 .. " +
+                                            std::to_string(flow->cfg.n_flow_layers - 1));
+        } else if (!flow->blocks[l].has_attn) {
+            throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: flow layer " + std::to_string(l) + " has no attention: a global-context flow hands the "
+                                            "embedding to its couplings directly (only layer -1, the augmenter, attends)");
+        }
+        probe.layers.push_back(l);
+        probe.out.push_back(out[i]);
+    }
+    // the guarded pass of fc_flow_logprob_f32; a pass repeated on the bf16 limbs rewrites the weight buffers too.  Deferred: it owns its arguments
+    const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
+    fc::run_fp16_guarded(flow->fp16_flag, (hipStream_t)stream, [=] {
+        fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, nullptr, B, N, M, workspace, workspace_bytes, (hipStream_t)stream, &probe);
     }, true);
     fc::check_expm_status(*flow, (hipStream_t)stream);
     FC_API_END

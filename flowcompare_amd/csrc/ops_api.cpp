@@ -215,6 +215,17 @@ int fc_op_attention_f32(const float* q, const float* k, const float* v, float* o
     FC_API_END
 }
 
+int fc_op_attention_weights_f32(const float* q, const float* k, float* out, const int32_t* sel, int32_t P, int32_t sel_per_scene,
+                                int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream) {
+    FC_API_BEGIN
+    if (!q || !k || !out) throw fc::Error(FC_ERR_INVALID, "fc_op_attention_weights_f32: null pointer");
+    if (D != 32 && D != 64 && D != 128) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_weights_f32: D must be 32, 64 or 128");
+    fc::launch_attention_weights(q, D, k, D, nullptr, 0, 0, out, sel, sel ? P : N, sel_per_scene, B, N, N, M, M, D, scale * 1.4426950408889634f,
+                                 nullptr, (hipStream_t)stream);
+    FC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    FC_API_END
+}
+
 int fc_op_knn_f32(const float* f, int32_t* idx, int32_t B, int32_t M, int32_t C, int32_t k, void* stream) {
     FC_API_BEGIN
     using namespace fc;

@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FCFLOW_LIB", os.path.join(_HERE, "libfcflow.so"))   # FCFLOW_LIB: A/B another build in profiles/kernel_bench.py
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 FLOW_TYPES = {"AffineCoupling": 0, "RationalQuadraticSplineCoupling": 1, "ExponentialCoupling": 2}
 SCALE_FNS = {"exp": 0, "sigmoid": 1}
@@ -22,12 +22,12 @@ EXPM = {"torch": 0, "original": 1}
 EXPORTS = [
     "fc_abi_version", "fc_last_error",
     "fc_flow_create", "fc_flow_destroy", "fc_flow_workspace_bytes", "fc_flow_noise_count", "fc_flow_noise_width",
-    "fc_flow_logprob_f32", "fc_flow_inverse_f32",
+    "fc_flow_logprob_f32", "fc_flow_inverse_f32", "fc_flow_attention_weights_f32",
     "fc_dgcnn_create", "fc_dgcnn_destroy", "fc_dgcnn_out_dim", "fc_dgcnn_workspace_bytes", "fc_dgcnn_embed_f32",
     "fc_paconv_create", "fc_paconv_destroy", "fc_paconv_out_dim", "fc_paconv_workspace_bytes", "fc_paconv_embed_f32", "fc_op_fps_f32",
     "fc_range_check_defer", "fc_range_check_resolve", "fc_range_check_pending",
     "fc_profile_enable", "fc_profile_reset", "fc_profile_filter", "fc_profile_stride", "fc_profile_report",
-    "fc_op_linear_f32", "fc_op_mlp_hidden_f32", "fc_op_attention_f32", "fc_op_knn_f32", "fc_op_knn_warm_f32", "fc_op_rqspline_f32", "fc_op_expm_action_f32",
+    "fc_op_linear_f32", "fc_op_mlp_hidden_f32", "fc_op_attention_f32", "fc_op_attention_weights_f32", "fc_op_knn_f32", "fc_op_knn_warm_f32", "fc_op_rqspline_f32", "fc_op_expm_action_f32",
     "fc_stage_fps_f32", "fc_stage_co_unit_sphere_f32", "fc_clamp_infs_f32", "fc_change_map_f32",
     "fc_train_linear_pack_bytes", "fc_train_linear_pack_f32", "fc_train_linear_fwd_f32", "fc_train_linear_act_fwd_f32", "fc_train_linear_dgrad_f32", "fc_train_linear_dgrad_act_f32",
     "fc_train_linear_wgrad_ws_bytes", "fc_train_linear_wgrad_f32", "fc_train_act_fwd_f32", "fc_train_act_bwd_f32",
@@ -192,6 +192,22 @@ def _keep_if_deferred(*tensors):
         _deferred_keep.extend(t for t in tensors if t is not None)
 
 
+def _points_table(points, B, N, device):
+    """Selection table of the attention-weight entry points -> (int32 device tensor or None, P, per-scene flag).  The kernel does not
+    range-check it, so everything is checked here: integer dtype, shape [P] or [B, P], values in [0, N)."""
+    if points is None:
+        return None, N, 0
+    t = points if torch.is_tensor(points) else torch.as_tensor(points)
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise RuntimeError(f"points must be an integer index tensor, got dtype {t.dtype}")
+    if t.dim() not in (1, 2) or t.numel() == 0 or (t.dim() == 2 and t.shape[0] != B):
+        raise RuntimeError(f"points must have shape [P] or [B, P] with B = {B} and P >= 1, got {tuple(t.shape)}")
+    lo, hi = int(t.min()), int(t.max())
+    if lo < 0 or hi >= N:
+        raise RuntimeError(f"points out of range: index {lo if lo < 0 else hi} is not in [0, {N}) (the target cloud has {N} points)")
+    return t.to(device=device, dtype=torch.int32).contiguous(), t.shape[-1], int(t.dim() == 2)
+
+
 class _Workspace:
     """Grow-only device scratch owned by a handle (the C ABI never allocates inside compute calls)."""
     def __init__(self):
@@ -279,6 +295,30 @@ class FlowHandle:
                                          B, N, M, _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
             _keep_if_deferred(x, ctx, extra, out, z, ws, *eps)
         return (out, z) if return_latent else out
+
+    def attention_weights(self, x, context, extra_context, eps, layers, points=None, return_log_prob=False):
+        """fc_flow_attention_weights_f32: the forward of log_prob that also writes the softmax rows of the selected target points at the
+        requested attentions.  layers: ints, -1 = the augmenter's attention, l >= 0 = flow layer l's pre-conditioner; points: None (all N
+        points) or an integer tensor [P] / [B, P].  Returns a list of [B, P, M] fp32 tensors in the order of `layers` (and the log-prob)."""
+        x, ctx, extra, eps, B, N, M = self._prep(x, context, extra_context, eps)
+        layers = [int(l) for l in layers]
+        if not layers:
+            raise RuntimeError("attention_weights: no layers requested")
+        L = lib()
+        with torch.cuda.device(self.device):
+            sel, P, per_scene = _points_table(points, B, N, self.device)
+            need = ctypes.c_size_t()
+            _check(L.fc_flow_workspace_bytes(self._h, B, N, M, ctypes.byref(need)))
+            ws = self._ws.get(need.value, self.device)
+            outs = [torch.empty(B, P, M, dtype=torch.float32, device=self.device) for _ in layers]
+            lp = torch.empty(B, N, dtype=torch.float32, device=self.device) if return_log_prob else None
+            eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
+            lay_arr = (ctypes.c_int32 * len(layers))(*layers)
+            out_arr = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+            _check(L.fc_flow_attention_weights_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), lay_arr, len(layers), _ptr(sel), P,
+                                                   per_scene, out_arr, _ptr(lp), B, N, M, _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
+            _keep_if_deferred(x, ctx, extra, sel, lp, ws, *eps, *outs)
+        return (outs, lp) if return_log_prob else outs
 
     def inverse(self, z, context, extra_context, eps):
         """Inverse pass of Flow.sample from a drawn latent z [B,n,latent_dim] -> x [B,n,input_dim]."""
@@ -480,6 +520,18 @@ def op_attention(q, k, v, scale):
     out = torch.empty_like(q)
     with torch.cuda.device(q.device):
         _check(lib().fc_op_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, N, M, D, ctypes.c_float(scale), _stream()))
+    return out
+
+
+def op_attention_weights(q, k, scale, points=None):
+    """Rows `points` (None = all) of softmax(q k^T * scale): q [B,N,D], k [B,M,D] -> [B,P,M] (fc_op_attention_weights_f32)."""
+    q, k = _dev_f32(q), _dev_f32(k)
+    B, N, D = q.shape
+    M = k.shape[1]
+    with torch.cuda.device(q.device):
+        sel, P, per_scene = _points_table(points, B, N, q.device)
+        out = torch.empty(B, P, M, dtype=torch.float32, device=q.device)
+        _check(lib().fc_op_attention_weights_f32(_ptr(q), _ptr(k), _ptr(out), _ptr(sel), P, per_scene, B, N, M, D, ctypes.c_float(scale), _stream()))
     return out
 
 

@@ -187,6 +187,26 @@ def inner_loop(batch, models_dict, config, eps=None):
     return loss, log_prob, bpd
 
 
+def attention_weights(batch, models_dict, config, layers=("aug",), points=None, eps=None, return_log_prob=False):
+    """The attention maps visualize_attention.py colours the context cloud with (there: forward hooks on AttentionMine,
+    models/perceiver.py:108-115), from the same pass as inner_loop: batch = (extract_0, extract_1, extra_context) is sliced, embedded and
+    expanded exactly as inner_loop does.  layers: "aug" (the augmenter's attention) or 0-based flow-layer indices -- the reference
+    script's three maps are layers=("aug", 50, 110); points: None (every target point) or integer indices [P] / [B, P] into extract_1.
+    Returns a list of [B, P, M] tensors in the order of `layers` (row p: the weights of target point points[p] over the M context
+    points, summing to 1), or (weights, log_prob) with return_log_prob.  The batch is taken as given: no scene sharding under
+    config['data_parallel'] (every rank computes the scenes it is handed).  A full map is 4 B N M bytes per layer."""
+    extract_0, extract_1, extra_context = batch
+    Din = config["input_dim"]
+    extract_0, extract_1 = extract_0[:, :, :Din], extract_1[:, :, :Din]
+    if extra_context is not None:
+        extra_context = extra_context[:, None, :].expand(-1, config["sample_size"], -1)
+    emb = models_dict["input_embedder"](extract_0)
+    if config["global"]:
+        emb = emb[:, None, :].expand(-1, extract_1.shape[1], -1)
+    return models_dict["flow"].attention_weights(extract_1, context=emb, extra_context=extra_context, layers=layers, points=points, eps=eps,
+                                                 return_log_prob=return_log_prob)
+
+
 def make_sample(n_points, extract_0, models_dict, config, sample_distrib=None, extra_context=None):
     """model_initialization.py:231-245."""
     extract_0 = extract_0[:, :, :config["input_dim"]]

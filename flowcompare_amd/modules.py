@@ -327,6 +327,33 @@ class Flow(nn.Module):
         from . import library_ops                          # the inference call as a torch.library op (torch.ops.flowcompare_amd.flow_log_prob)
         return torch.ops.flowcompare_amd.flow_log_prob(x, context, extra_context, list(eps), library_ops.register(self._engine()))
 
+    def attention_weights(self, x, context=None, extra_context=None, layers=("aug",), points=None, eps=None, return_log_prob=False):
+        """The cross-attention softmax rows the reference materialises as `attn_weights` (models/perceiver.py:108-115; one forward hook
+        per AttentionMine there): for every entry of `layers` -- "aug" = the augmenter's attention, an int l = flow layer l's
+        pre-conditioner (0-based) -- a tensor [B, P, M] whose row p holds the weights target point points[p] puts on the M context
+        points.  points: None (all N points, P = N) or integer indices [P] (shared by the scenes) / [B, P].  x, context, extra_context
+        and eps are those of log_prob (the same pass runs; eps is drawn when omitted and kept in last_eps); with return_log_prob the
+        pass's log-prob comes back too.  Eval mode only.  A full map is 4 B N M bytes per layer: large scenes want `points`."""
+        if self.training:
+            raise RuntimeError("Flow.attention_weights is eval-mode only (the training path has no attention probe): call .eval() first")
+        ids = []
+        n_layers = self._config["n_flow_layers"]
+        for l in layers:
+            if isinstance(l, str):
+                if l != "aug":
+                    raise RuntimeError(f"attention_weights: unknown layer {l!r}: entries are \"aug\" or a flow-layer index 0 .. {n_layers - 1}")
+                ids.append(-1)
+            else:
+                if isinstance(l, bool) or int(l) != l or not 0 <= int(l) < n_layers:
+                    raise RuntimeError(f"attention_weights: layer index {l!r} is out of range: entries are \"aug\" or a flow-layer index 0 .. {n_layers - 1}")
+                ids.append(int(l))
+        B, N = x.shape[0], x.shape[1]
+        if eps is None:
+            eps = [torch.randn(s, device=x.device, dtype=torch.float32) for s in self.noise_shapes(B, N)]
+        self.last_eps = eps
+        with torch.no_grad():
+            return self._engine().attention_weights(x, context, extra_context, list(eps), ids, points=points, return_log_prob=return_log_prob)
+
     def sample(self, num_samples, n_points, context=None, sample_distrib=None, extra_context=None, eps=None):
         dist = sample_distrib if sample_distrib is not None else self.sample_dist
         z = dist.sample(num_samples, n_points=n_points)

@@ -23,6 +23,7 @@
  * 5 = + the deferred range check (fc_range_check_defer / _resolve / _pending);
  * 6 = + fc_profile_stride (sampled bracketing of the in-library kernel timing), fc_train_linear_act_fwd_f32 / fc_train_linear_dgrad_act_f32 (activation and its backward in the GEMM epilogues).
  * 8 = + fc_op_expm_action_f32; ExponentialCoupling up to d2 = 256 (inference, training forward).
+ * 9 = + fc_flow_attention_weights_f32 / fc_op_attention_weights_f32: the cross-attention softmax rows of selected target points.
  */
 #ifndef FCFLOW_H
 #define FCFLOW_H
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define FC_ABI_VERSION 8
+#define FC_ABI_VERSION 9
 
 enum fc_status {
     FC_OK = 0,
@@ -129,6 +130,20 @@ int fc_flow_noise_width(const fc_flow* flow, int32_t i);
 int fc_flow_logprob_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra,
                         const float* const* eps, int32_t n_eps, float* logprob, float* z_out,
                         int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The forward of fc_flow_logprob_f32 that additionally writes, for each of n_layers requested attentions, the softmax rows
+ * of the selected target points: out[i] is a device buffer [B, P, M] fp32.  layer id -1 = the augmenter's attention
+ * (transform 0), 0 .. n_flow_layers-1 = the pre-conditioner of that flow layer.  sel: device int32 [P] (sel_per_scene = 0)
+ * or [B, P] (1), values in [0, N); NULL = all N points (P = N).  logprob may be NULL.  Same workspace as the forward.
+ * These are the rows the reference materialises as `attn_weights` (models/perceiver.py:108-115) and visualize_attention.py
+ * colours the context cloud with.  A full map is 4 * B * N * M bytes PER LAYER (1 GiB at 16 x 4096 x 4096): large scenes
+ * want a selection.  FC_ERR_INVALID before anything is launched for: a flow layer without attention (global-context flows
+ * hand the embedding to the couplings; their augmenter still attends, so -1 is valid there), -1 on a flow whose first
+ * transform is IdentityTransform, an id outside [-1, n_flow_layers).  sel is NOT range-checked on the device. */
+int fc_flow_attention_weights_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps,
+                                  int32_t n_eps, const int32_t* layers, int32_t n_layers, const int32_t* sel, int32_t P,
+                                  int32_t sel_per_scene, float* const* out, float* logprob, int32_t B, int32_t N, int32_t M,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* Inverse pass of Flow.sample (models/transform.py:79-84) from a caller-drawn latent z [B,N,latent_dim]
  * -> x_out [B,N,input_dim].  eps: one tensor per CIF block (Slice.inverse draws, models/slice.py:46-58). */
@@ -227,6 +242,11 @@ int fc_op_mlp_hidden_f32(const float* x0, int32_t k0, const float* x1, int32_t k
 /* out[B,N,D] = softmax(q k^T * scale) v  with q [B,N,D], k,v [B,M,D]  (models/perceiver.py:106-113). */
 int fc_op_attention_f32(const float* q, const float* k, const float* v, float* out,
                         int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream);
+
+/* out[B,P,M] = rows sel of softmax(q k^T * scale) with q [B,N,D], k [B,M,D], D in {32, 64, 128} (models/perceiver.py:108-111): the
+ * kernel of fc_flow_attention_weights_f32 alone.  sel: device int32 [P] (sel_per_scene = 0) or [B,P] (1); NULL = all rows (P = N). */
+int fc_op_attention_weights_f32(const float* q, const float* k, float* out, const int32_t* sel, int32_t P, int32_t sel_per_scene,
+                                int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream);
 
 /* k nearest neighbours in feature space, reference ranking -|xi|^2 + 2 xi.xj - |xj|^2 (self included)
  * (models/pytorch_gcn.py:13-20).  f [B,M,C] channels-last -> idx [B,M,k] int32 (unordered set). */

@@ -1,0 +1,278 @@
+// Staging of whole scene pairs: what the voxel loader does per item (dataloaders/ams_voxel_loader.py:291-307),
+// for every voxel centre of a scene at once.
+//   * box membership (utils.get_voxel, utils.py:135-142) of every cloud row in every box, counted and then selected into a CSR
+//     list in ASCENDING row order, without atomics: the same input gives the same bytes, and farthest point sampling, which
+//     starts at a voxel's first row and breaks ties to the lowest position, sees the rows in the reference's order;
+//   * farthest point sampling of every voxel's rows, voxels of different sizes in one launch, one workgroup per voxel, with the
+//     distance arithmetic of fps_nd_kernel (fps_dist.h).
+#include "common.h"
+#include "fps_dist.h"
+
+#include <algorithm>
+
+namespace fc {
+
+// ---------------------------------------------------------------- box membership
+// A wave owns kVoxChunk = 512 consecutive cloud rows (8 per lane, row = chunk * 512 + it * 64 + lane, held in registers), a workgroup
+// of 4 waves 2048 rows and a tile of kVoxTile boxes whose bounds sit in LDS.  Ascending row order inside a chunk is (it, lane): the
+// rank of a member is the popcount of the earlier ballots plus the popcount of the lower lanes of its own ballot.  The count pass
+// writes one int per (chunk, box) into table[chunk * K + box]; voxel_scan_kernel turns every box's column into an exclusive prefix
+// over the chunks (and its total into counts[box]); the select pass repeats the tests and writes row numbers at
+// offsets[box] + table[chunk * K + box] + rank.  No wave needs another wave's result inside a launch, so there is no barrier
+// after the tile load and nothing is appended atomically.
+constexpr int kVoxChunk = 512, kVoxWaves = 4, kVoxTile = 256, kVoxPerLane = kVoxChunk / 64;
+
+__device__ __forceinline__ unsigned lanes_below(unsigned long long mask, int lane) {
+    return (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+}
+
+// SELECT = false: table[chunk * K + k] = members of box k among the chunk's rows.
+// SELECT = true : rows[offsets[k] + table[chunk * K + k] + rank] = row number, for every member (table already scanned).
+template <bool SELECT>
+__global__ __launch_bounds__(64 * kVoxWaves) void voxel_member_kernel(const float* __restrict__ cloud, int ld, int P, const float* __restrict__ centers, int K,
+                                                                      float hx, float hy, float hz, int* __restrict__ table,
+                                                                      const int64_t* __restrict__ offsets, int32_t* __restrict__ rows, int64_t rows_cap) {
+    __shared__ float lo[3][kVoxTile], hi[3][kVoxTile];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k0 = blockIdx.y * kVoxTile;
+    // lo = c - d/2, hi = c + d/2 in fp32, one rounding each (d/2 is exact), as torch rounds `center - dimensions / 2`
+    for (int j = threadIdx.x; j < kVoxTile; j += 64 * kVoxWaves) {
+        const int k = k0 + j;
+        const float cx = k < K ? centers[3 * (size_t)k] : NAN, cy = k < K ? centers[3 * (size_t)k + 1] : NAN, cz = k < K ? centers[3 * (size_t)k + 2] : NAN;
+        lo[0][j] = cx - hx; lo[1][j] = cy - hy; lo[2][j] = cz - hz;
+        hi[0][j] = cx + hx; hi[1][j] = cy + hy; hi[2][j] = cz + hz;
+    }
+    __syncthreads();
+    const int chunk = blockIdx.x * kVoxWaves + wave;
+    const long row0 = (long)chunk * kVoxChunk;
+    if (row0 >= P) return;                                   // whole wave; after the only barrier
+    float x[kVoxPerLane], y[kVoxPerLane], z[kVoxPerLane];
+#pragma unroll
+    for (int it = 0; it < kVoxPerLane; ++it) {
+        const long r = row0 + it * 64 + lane;
+        const bool in = r < P;                               // rows beyond the cloud are NaN: in no box
+        x[it] = in ? cloud[(size_t)r * ld] : NAN;
+        y[it] = in ? cloud[(size_t)r * ld + 1] : NAN;
+        z[it] = in ? cloud[(size_t)r * ld + 2] : NAN;
+    }
+    const int kend = min(kVoxTile, K - k0);
+    for (int g = 0; g < kend; g += 64) {                     // 64 boxes at a time: lane j keeps box g + j's count / write base
+        const int kb = k0 + g + lane;
+        int mine = 0;
+        long long base = 0;
+        if (SELECT && g + lane < kend) base = (long long)offsets[kb] + table[(size_t)chunk * K + kb];
+        const int jend = min(64, kend - g);
+        for (int j = 0; j < jend; ++j) {
+            const int t = g + j;
+            const float lx = lo[0][t], ly = lo[1][t], lz = lo[2][t], ux = hi[0][t], uy = hi[1][t], uz = hi[2][t];
+            const long long wbase = SELECT ? __shfl(base, j, 64) : 0;
+            unsigned run = 0;
+#pragma unroll
+            for (int it = 0; it < kVoxPerLane; ++it) {
+                const bool in = x[it] >= lx && x[it] <= ux && y[it] >= ly && y[it] <= uy && z[it] >= lz && z[it] <= uz;
+                const unsigned long long b = __ballot(in);
+                if (SELECT && in) {
+                    const long long pos = wbase + run + lanes_below(b, lane);
+                    if (pos >= 0 && pos < rows_cap) rows[pos] = (int32_t)(row0 + it * 64 + lane);    // cap: offsets that do not belong to this table
+                }
+                run += (unsigned)__popcll(b);
+            }
+            if (!SELECT && lane == j) mine = (int)run;
+        }
+        if (!SELECT && g + lane < kend) table[(size_t)chunk * K + kb] = mine;
+    }
+}
+
+// One thread per box: exclusive prefix of its column over the chunks, total -> counts.  Consecutive threads read consecutive ints.
+__global__ __launch_bounds__(64) void voxel_scan_kernel(int* __restrict__ table, int n_chunks, int K, int32_t* __restrict__ counts) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= K) return;
+    int run = 0;
+    int c = 0;
+    for (; c + 8 <= n_chunks; c += 8) {                      // 8 independent loads in flight
+        int t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = table[(size_t)(c + u) * K + k];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { table[(size_t)(c + u) * K + k] = run; run += t[u]; }
+    }
+    for (; c < n_chunks; ++c) { const int t = table[(size_t)c * K + k]; table[(size_t)c * K + k] = run; run += t; }
+    counts[k] = run;
+}
+
+static int voxel_chunks(long P) { return (int)((P + kVoxChunk - 1) / kVoxChunk); }
+
+size_t voxel_ws_bytes(long P, int K) { return (size_t)std::max(voxel_chunks(std::max(P, 1L)), 1) * (size_t)std::max(K, 1) * sizeof(int); }
+
+static void check_voxel_args(const float* cloud, int ld, long P, const float* centers, int K, const void* ws, size_t ws_bytes) {
+    if (!cloud || !centers || !ws) throw Error(FC_ERR_INVALID, "voxel membership: null pointer");
+    if (ld < 3 || P < 1 || P > 0x7fffffffL - kVoxChunk || K < 1) throw Error(FC_ERR_INVALID, "voxel membership: bad shape");
+    if ((K + kVoxTile - 1) / kVoxTile > 65535) throw Error(FC_ERR_UNSUPPORTED, "voxel membership: more than 16 776 960 boxes");
+    if (ws_bytes < voxel_ws_bytes(P, K)) throw Error(FC_ERR_WORKSPACE, "voxel membership: workspace smaller than fc_stage_voxel_ws_bytes");
+}
+
+static dim3 voxel_grid(long P, int K) { return dim3((voxel_chunks(P) + kVoxWaves - 1) / kVoxWaves, (K + kVoxTile - 1) / kVoxTile); }
+
+// algorithmic bytes of one membership pass: the cloud's xyz once per box tile, one table entry per (chunk, box)
+static double voxel_pass_bytes(long P, int K) { return (double)((K + kVoxTile - 1) / kVoxTile) * P * 12.0 + 4.0 * voxel_chunks(P) * (double)K; }
+
+void launch_voxel_count(const float* cloud, int ld, long P, const float* centers, int K, float dx, float dy, float dz, int32_t* counts, void* ws,
+                        size_t ws_bytes, hipStream_t s) {
+    check_voxel_args(cloud, ld, P, centers, K, ws, ws_bytes);
+    if (!counts) throw Error(FC_ERR_INVALID, "voxel count: null pointer");
+    {
+        ProfScope ps("fc::voxel_member_kernel<false>", 0.0, voxel_pass_bytes(P, K), s);
+        hipLaunchKernelGGL(voxel_member_kernel<false>, voxel_grid(P, K), dim3(64 * kVoxWaves), 0, s, cloud, ld, (int)P, centers, K, dx * 0.5f, dy * 0.5f,
+                           dz * 0.5f, (int*)ws, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0);
+    }
+    ProfScope ps("fc::voxel_scan_kernel", 0.0, 8.0 * voxel_chunks(P) * (double)K, s);
+    hipLaunchKernelGGL(voxel_scan_kernel, dim3((K + 63) / 64), dim3(64), 0, s, (int*)ws, voxel_chunks(P), K, counts);
+    FC_HIP(hipGetLastError());
+}
+
+void launch_voxel_select(const float* cloud, int ld, long P, const float* centers, int K, float dx, float dy, float dz, const int64_t* offsets,
+                         int32_t* rows, int64_t rows_cap, const void* ws, size_t ws_bytes, hipStream_t s) {
+    check_voxel_args(cloud, ld, P, centers, K, ws, ws_bytes);
+    if (!offsets || rows_cap < 0 || (rows_cap > 0 && !rows)) throw Error(FC_ERR_INVALID, "voxel select: bad argument");
+    if (rows_cap == 0) return;
+    ProfScope ps("fc::voxel_member_kernel<true>", 0.0, voxel_pass_bytes(P, K) + 4.0 * rows_cap, s);
+    hipLaunchKernelGGL(voxel_member_kernel<true>, voxel_grid(P, K), dim3(64 * kVoxWaves), 0, s, cloud, ld, (int)P, centers, K, dx * 0.5f, dy * 0.5f,
+                       dz * 0.5f, (int*)const_cast<void*>(ws), offsets, rows, rows_cap);
+    FC_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- ragged farthest point sampling
+// One workgroup per listed voxel v: n = offsets[v + 1] - offsets[v] rows of the cloud, named by rows[offsets[v] ...] in ascending
+// order.  Same algorithm, reduction order and tie rule as fps_nd_kernel on the cropped voxel (first pick = position 0, running
+// distances min'ed in place, first maximum wins); positions are translated to cloud row numbers on output.
+//   PTS_LDS : the voxel's rows are gathered ONCE into LDS (n * C floats behind the n running distances) and every pass reads them
+//             there; the values are the cloud's own floats, so the selection cannot differ from reading them in place;
+//   otherwise the rows are read through the index list on every pass; the running distances live in LDS up to kFpsLdsDist rows
+//   and in dist_scratch[offsets[v] ...] beyond (as in fps_nd_kernel).
+constexpr int kFpsLdsDist = 24576;                           // fps_nd_kernel's limit
+constexpr int kFpsLdsFloats = 36864;                         // 144 KB of gfx950's 160 KB per workgroup
+
+template <bool PTS_LDS>
+__device__ __forceinline__ void fps_ragged_body(const float* __restrict__ cloud, int ld, int C, int P, const int32_t* __restrict__ vr, int n, int m,
+                                                int64_t* __restrict__ out, float* __restrict__ dist, float* __restrict__ pts, float* red_v, int* red_i,
+                                                int* s_last) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    auto cloud_row = [&](int k) { return cloud + (size_t)min(max(vr[k], 0), P - 1) * ld; };    // clamped: a bad list cannot read outside the cloud
+    for (int k = tid; k < n; k += 1024) {
+        dist[k] = INFINITY;
+        if (PTS_LDS) {
+            const float* r = cloud_row(k);
+            for (int c = 0; c < C; ++c) pts[(size_t)k * C + c] = r[c];
+        }
+    }
+    if (tid == 0) { out[0] = vr[0]; *s_last = 0; }
+    __syncthreads();
+    for (int j = 1; j < m; ++j) {
+        const int last = *s_last;
+        const float* lr = PTS_LDS ? pts + (size_t)last * C : cloud_row(last);
+        float ref[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) ref[c] = c < C ? lr[c] : 0.f;
+        float best = -1.f;
+        int besti = 0x7fffffff;
+        for (int k = tid; k < n; k += 1024) {
+            const float d2 = fminf(fps_row_dist2(PTS_LDS ? pts + (size_t)k * C : cloud_row(k), ref, C), dist[k]);
+            dist[k] = d2;
+            if (d2 > best) { best = d2; besti = k; }          // ascending k: keeps this thread's lowest position among equals
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float ov = __shfl_xor(best, off, 64);
+            const int oi = __shfl_xor(besti, off, 64);
+            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        }
+        if (lane == 0) { red_v[wave] = best; red_i[wave] = besti; }
+        __syncthreads();
+        if (wave == 0) {
+            float v = lane < 16 ? red_v[lane] : -2.f;
+            int i = lane < 16 ? red_i[lane] : 0x7fffffff;
+#pragma unroll
+            for (int off = 8; off >= 1; off >>= 1) {
+                const float ov = __shfl_xor(v, off, 64);
+                const int oi = __shfl_xor(i, off, 64);
+                if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+            }
+            if (lane == 0) { *s_last = i; out[j] = vr[i]; }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(1024) void fps_ragged_kernel(const float* __restrict__ cloud, int ld, int C, int P, const int64_t* __restrict__ offsets,
+                                                          const int32_t* __restrict__ rows, const int32_t* __restrict__ voxel_ids,
+                                                          int64_t* __restrict__ idx, int m, int lds_floats, float* __restrict__ dist_scratch) {
+    extern __shared__ float sm[];
+    __shared__ float red_v[16];
+    __shared__ int red_i[16];
+    __shared__ int s_last;
+    const int v = voxel_ids ? voxel_ids[blockIdx.x] : (int)blockIdx.x;
+    const int64_t off = offsets[v];
+    const int64_t n64 = offsets[v + 1] - off;
+    if (n64 < m || n64 > 0x7fffffff) return;                  // refused by the host beforehand; uniform over the workgroup
+    const int n = (int)n64;
+    const int32_t* vr = rows + off;
+    int64_t* out = idx + (size_t)blockIdx.x * m;
+    if ((int64_t)n * (C + 1) <= lds_floats)
+        fps_ragged_body<true>(cloud, ld, C, P, vr, n, m, out, sm, sm + n, red_v, red_i, &s_last);
+    else if (n <= min(lds_floats, kFpsLdsDist))
+        fps_ragged_body<false>(cloud, ld, C, P, vr, n, m, out, sm, nullptr, red_v, red_i, &s_last);
+    else if (dist_scratch)
+        fps_ragged_body<false>(cloud, ld, C, P, vr, n, m, out, dist_scratch + off, nullptr, red_v, red_i, &s_last);
+}
+
+void launch_fps_ragged(const float* cloud, int ld, int C, long P, const int64_t* offsets, const int32_t* rows, const int32_t* voxel_ids, int n_voxels,
+                       int max_rows, int m, int64_t* idx, float* dist_scratch, hipStream_t s) {
+    if (n_voxels <= 0 || m <= 0) return;
+    if (!cloud || !offsets || !rows || !idx) throw Error(FC_ERR_INVALID, "ragged fps: null pointer");
+    if (C < 1 || C > 8 || ld < C) throw Error(FC_ERR_UNSUPPORTED, "fps: 1..8 feature columns supported");
+    if (P < 1 || P > 0x7fffffffL) throw Error(FC_ERR_INVALID, "ragged fps: bad cloud size");
+    if (m > max_rows) throw Error(FC_ERR_INVALID, "fps: more samples than points");
+    if (max_rows > kFpsLdsDist && !dist_scratch)
+        throw Error(FC_ERR_WORKSPACE, "ragged fps: voxels above 24576 rows need a float scratch as long as the row list");
+    const long want = (long)max_rows * (C + 1);
+    const int lds_floats = want <= kFpsLdsFloats ? (int)want : kFpsLdsFloats;          // >= min(max_rows, 24576) either way
+    static bool attr_done = false;
+    if (!attr_done) {
+        FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fps_ragged_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kFpsLdsFloats * 4));
+        attr_done = true;
+    }
+    ProfScope ps("fc::fps_ragged_kernel", 0.0, 4.0 * n_voxels * ((double)max_rows * (C + 1) + 2.0 * m), s);
+    hipLaunchKernelGGL(fps_ragged_kernel, dim3(n_voxels), dim3(1024), (size_t)lds_floats * sizeof(float), s, cloud, ld, C, (int)P, offsets, rows, voxel_ids,
+                       idx, m, lds_floats, dist_scratch);
+    FC_HIP(hipGetLastError());
+}
+
+}  // namespace fc
+
+extern "C" {
+
+size_t fc_stage_voxel_ws_bytes(int64_t P, int32_t K) { return fc::voxel_ws_bytes((long)P, K); }
+
+int fc_stage_voxel_count_f32(const float* cloud, int32_t ld, int64_t P, const float* centers, int32_t K, float dx, float dy, float dz, int32_t* counts,
+                             void* ws, size_t ws_bytes, void* stream) {
+    FC_API_BEGIN
+    fc::launch_voxel_count(cloud, ld, (long)P, centers, K, dx, dy, dz, counts, ws, ws_bytes, (hipStream_t)stream);
+    FC_API_END
+}
+
+int fc_stage_voxel_select_f32(const float* cloud, int32_t ld, int64_t P, const float* centers, int32_t K, float dx, float dy, float dz,
+                              const int64_t* offsets, int32_t* rows, int64_t rows_capacity, const void* ws, size_t ws_bytes, void* stream) {
+    FC_API_BEGIN
+    fc::launch_voxel_select(cloud, ld, (long)P, centers, K, dx, dy, dz, offsets, rows, rows_capacity, ws, ws_bytes, (hipStream_t)stream);
+    FC_API_END
+}
+
+int fc_stage_fps_ragged_f32(const float* cloud, int32_t ld, int32_t C, int64_t P, const int64_t* offsets, const int32_t* rows, const int32_t* voxel_ids,
+                            int32_t n_voxels, int32_t max_rows, int32_t m, int64_t* idx, float* dist_scratch, void* stream) {
+    FC_API_BEGIN
+    if (n_voxels < 0 || m < 1) throw fc::Error(FC_ERR_INVALID, "fc_stage_fps_ragged_f32: bad argument");
+    fc::launch_fps_ragged(cloud, ld, C, (long)P, offsets, rows, voxel_ids, n_voxels, max_rows, m, idx, dist_scratch, (hipStream_t)stream);
+    FC_API_END
+}
+
+}  // extern "C"

@@ -4,6 +4,7 @@
 //   * change-map post-processing (test_flow.py:241-275): clamp_infs, per-scene mean/std threshold, min-max scaling.
 // Small streaming / reduction kernels: one workgroup per scene, LDS tree reductions in a fixed order (bit-reproducible).
 #include "common.h"
+#include "fps_dist.h"
 
 #include <cfloat>
 
@@ -34,11 +35,7 @@ __global__ __launch_bounds__(1024) void fps_nd_kernel(const float* __restrict__ 
         float best = -1.f;
         int besti = 0x7fffffff;
         for (int k = tid; k < n; k += 1024) {
-            float d = 0.f;
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-                if (c < C) { const float t = src[(size_t)k * ld + c] - ref[c]; d += t * t; }
-            const float d2 = fminf(d, dist[k]);
+            const float d2 = fminf(fps_row_dist2(src + (size_t)k * ld, ref, C), dist[k]);
             dist[k] = d2;
             if (d2 > best) { best = d2; besti = k; }          // ascending k: keeps this thread's lowest index among equals
         }

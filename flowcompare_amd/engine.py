@@ -29,6 +29,7 @@ EXPORTS = [
     "fc_profile_enable", "fc_profile_reset", "fc_profile_filter", "fc_profile_stride", "fc_profile_report",
     "fc_op_linear_f32", "fc_op_mlp_hidden_f32", "fc_op_attention_f32", "fc_op_attention_weights_f32", "fc_op_knn_f32", "fc_op_knn_warm_f32", "fc_op_rqspline_f32", "fc_op_expm_action_f32",
     "fc_stage_fps_f32", "fc_stage_co_unit_sphere_f32", "fc_clamp_infs_f32", "fc_change_map_f32",
+    "fc_stage_voxel_ws_bytes", "fc_stage_voxel_count_f32", "fc_stage_voxel_select_f32", "fc_stage_fps_ragged_f32",
     "fc_train_linear_pack_bytes", "fc_train_linear_pack_f32", "fc_train_linear_fwd_f32", "fc_train_linear_act_fwd_f32", "fc_train_linear_dgrad_f32", "fc_train_linear_dgrad_act_f32",
     "fc_train_linear_wgrad_ws_bytes", "fc_train_linear_wgrad_f32", "fc_train_act_fwd_f32", "fc_train_act_bwd_f32",
     "fc_train_attention_ws_bytes", "fc_train_attention_fwd_f32", "fc_train_attention_bwd_f32",
@@ -454,6 +455,47 @@ def stage_co_unit_sphere(p0, p1):
     with torch.cuda.device(p0.device):
         _check(lib().fc_stage_co_unit_sphere_f32(_ptr(p0), n0, _ptr(p1), p1.shape[1], ld, _ptr(o0), _ptr(o1), _ptr(inv), B, _stream()))
     return o0, o1, inv
+
+
+def _voxel_args(cloud, centers, dims):
+    if len(dims) != 3:
+        raise RuntimeError("voxel membership: box dimensions must be three numbers")
+    return (_ptr(cloud), cloud.shape[1], ctypes.c_int64(cloud.shape[0]), _ptr(centers), centers.shape[0],
+            ctypes.c_float(dims[0]), ctypes.c_float(dims[1]), ctypes.c_float(dims[2]))
+
+
+def stage_voxel_count(cloud, centers, dims):
+    """cloud [P, ld], centers [K, 3] (contiguous fp32 device tensors), dims = three floats -> (counts [K] int32, ws): members of every
+    get_voxel box (fc_stage_voxel_count_f32).  `ws` is what stage_voxel_select needs for the same cloud, centers and dims."""
+    P, K = cloud.shape[0], centers.shape[0]
+    counts = torch.empty(K, dtype=torch.int32, device=cloud.device)
+    lib().fc_stage_voxel_ws_bytes.restype = ctypes.c_size_t        # here, not in lib(): an FCFLOW_LIB built before these entries still loads
+    with torch.cuda.device(cloud.device):
+        ws = torch.empty(lib().fc_stage_voxel_ws_bytes(ctypes.c_int64(P), K), dtype=torch.uint8, device=cloud.device)
+        _check(lib().fc_stage_voxel_count_f32(*_voxel_args(cloud, centers, dims), _ptr(counts), _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
+    return counts, ws
+
+
+def stage_voxel_select(cloud, centers, dims, offsets, total, ws):
+    """rows [total] int32: every box's member rows, ascending, at offsets[k] (fc_stage_voxel_select_f32); offsets [K + 1] int64 on the
+    device = exclusive prefix of stage_voxel_count's counts, ws = that call's workspace."""
+    rows = torch.empty(total, dtype=torch.int32, device=cloud.device)
+    with torch.cuda.device(cloud.device):
+        _check(lib().fc_stage_voxel_select_f32(*_voxel_args(cloud, centers, dims), _ptr(offsets), _ptr(rows), ctypes.c_int64(total), _ptr(ws),
+                                               ctypes.c_size_t(ws.numel()), _stream()))
+    return rows
+
+
+def stage_fps_ragged(cloud, offsets, rows, m, max_rows, voxel_ids=None):
+    """idx [K', m] int64 cloud row numbers: the first m FPS picks of every listed voxel (fc_stage_fps_ragged_f32).  offsets [K + 1] int64,
+    rows int32, voxel_ids [K'] int32 or None (all K voxels); max_rows bounds the listed voxels' sizes."""
+    n_vox = offsets.numel() - 1 if voxel_ids is None else voxel_ids.numel()
+    idx = torch.empty(n_vox, m, dtype=torch.int64, device=cloud.device)
+    scratch = torch.empty(rows.numel(), dtype=torch.float32, device=cloud.device) if max_rows > 24576 else None
+    with torch.cuda.device(cloud.device):
+        _check(lib().fc_stage_fps_ragged_f32(_ptr(cloud), cloud.shape[1], cloud.shape[1], ctypes.c_int64(cloud.shape[0]), _ptr(offsets), _ptr(rows),
+                                             _ptr(voxel_ids), n_vox, int(max_rows), int(m), _ptr(idx), _ptr(scratch), _stream()))
+    return idx
 
 
 def clamp_infs(t):

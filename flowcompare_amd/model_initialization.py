@@ -207,6 +207,48 @@ def attention_weights(batch, models_dict, config, layers=("aug",), points=None, 
                                                  return_log_prob=return_log_prob)
 
 
+def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=None, multiple=5.4, hard_cutoff=None, voxels_per_batch=16,
+                 final_voxel_size=None, context_voxel_size=None):
+    """test_flow.py:151-166 for a whole scene, one direction: the change of cloud_1 [P1, C] given cloud_0 [P0, C] at the voxel centres
+    `centers` [K, 3].  Sample counts are config['sample_size'] / config['n_samples_context'] as the reference's loader takes them
+    (test_flow.py:141-143); the box sizes default to the config's 'final_voxel_size' / 'context_voxel_size'.  Evaluated are the centres
+    valid for BOTH stagings needed, (1 | 0) = context of cloud 0, target of cloud 1 and (0 | 0) = context and target of cloud 0, so that
+    row k of both log-prob tensors is the same voxel.  inner_loop runs on chunks of `voxels_per_batch` voxels; like the reference the
+    (0 | 0) batch takes the extra context of the (1 | 0) batch.  log_prob_to_change acts per chunk: its clamp_infs takes the minimum
+    over the tensor it is given, i.e. per chunk here exactly as per loader batch in the reference.  Returns (change [P1], the (1 | 0)
+    SceneStage with `voxel` / counts referring to `centers`): NaN where a point was not evaluated, the larger value where two voxels
+    share a sampled point.  The augmenter noise is drawn as inner_loop draws it: seed torch's device generator for a reproducible map."""
+    from . import change as change_ops
+    from . import staging
+    fin = config.get("final_voxel_size") if final_voxel_size is None else final_voxel_size
+    ctx = config.get("context_voxel_size") if context_voxel_size is None else context_voxel_size
+    if fin is None or ctx is None:
+        raise RuntimeError("scene_change: final_voxel_size / context_voxel_size are neither given nor in the config")
+    if config.get("using_extra_context") and ground_height is None:
+        raise RuntimeError("scene_change: this config uses the extra z-value context and needs ground_height")
+    N, M = config["sample_size"], config["n_samples_context"]
+    c0_ctx, c1_fin, c0_fin = (staging.voxel_counts(cloud_0, centers, ctx), staging.voxel_counts(cloud_1, centers, fin),
+                              staging.voxel_counts(cloud_0, centers, fin))
+    both = torch.nonzero((c0_ctx >= M) & (c1_fin >= N) & (c0_fin >= N)).flatten()
+    sel = centers[both].contiguous()
+    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height)
+    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height)
+    assert st10.voxel.numel() == st00.voxel.numel() == both.numel()
+    out = torch.full((cloud_1.shape[0],), float("nan"), dtype=torch.float32, device=cloud_1.device)
+    chunks = []
+    with torch.no_grad():
+        for a in range(0, both.numel(), voxels_per_batch):
+            sl = slice(a, a + voxels_per_batch)
+            extra = st10.extra_context[sl] if config.get("using_extra_context") else None
+            _, lp_1_0, _ = inner_loop((st10.extract_0[sl], st10.extract_1[sl], extra), models_dict, config)
+            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config)
+            chunks.append(change_ops.log_prob_to_change(lp_1_0, lp_0_0, multiple, hard_cutoff))
+    if chunks:
+        out.scatter_reduce_(0, st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1), "amax", include_self=False)
+    st10.voxel, st10.count_0, st10.count_1 = both, c0_ctx, c1_fin
+    return out, st10
+
+
 def make_sample(n_points, extract_0, models_dict, config, sample_distrib=None, extra_context=None):
     """model_initialization.py:231-245."""
     extract_0 = extract_0[:, :, :config["input_dim"]]

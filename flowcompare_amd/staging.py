@@ -56,3 +56,141 @@ def stage_pair(voxel_0_large, voxel_1_small, n_samples_context, n_samples):
         sel = fps(v, torch.zeros(v.shape[0], dtype=torch.long, device=v.device), ratio=k / v.shape[0], random_start=False)
         return v[sel][:k]
     return co_unit_sphere(sub(voxel_0_large, n_samples_context), sub(voxel_1_small, n_samples), return_inverse=True)
+
+
+# ---------------------------------------------------------------- whole scene pairs (csrc/scene_stage.hip)
+class SceneStage:
+    """What `stage_scene` returns: the staged voxel pairs of a scene, K' valid voxels out of K centres.
+    extract_0 [K', M, C], extract_1 [K', N, C], extra_context [K', 1] or None, inverse {'furthest_distance' [K'], 'mean' [K', 3]},
+    index_0 [K', M] / index_1 [K', N] (rows of cloud_0 / cloud_1), voxel [K'] (which centres), count_0 / count_1 [K] int32."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def batch(self):
+        """(extract_0, extract_1, extra_context): what inner_loop takes."""
+        return self.extract_0, self.extract_1, self.extra_context
+
+
+def _scene_input(name, *tensors):
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2):
+            raise RuntimeError(f"{name}: expects contiguous float32 [rows, columns] tensors on the GPU (flowcompare_amd has no CPU fallback)")
+
+
+def _cloud_and_centers(name, cloud, centers):
+    _scene_input(name, cloud, centers)
+    if not 3 <= cloud.shape[1] <= 8 or cloud.shape[0] < 1 or centers.shape[1] != 3 or centers.device != cloud.device:
+        raise RuntimeError(f"{name}: cloud must be [P >= 1, 3..8], centers [K, 3] on the same device; got {tuple(cloud.shape)}, {tuple(centers.shape)}")
+
+
+def _dims(size):
+    d = [float(v) for v in (size.tolist() if torch.is_tensor(size) else size)]
+    if len(d) != 3:
+        raise RuntimeError("voxel size must be three numbers")
+    return d
+
+
+def voxel_centers(start, end, size, device=None):
+    """Centre grid of utils.get_all_voxel_centers / utils.voxelize (utils.py:436-451): arange(start + size/2, end + size/2, size) per
+    axis in fp32, x fastest -> [K, 3]."""
+    start, end, size = (torch.as_tensor(v, dtype=torch.float32).cpu() for v in (start, end, size))
+    axes = [torch.arange(start[i] + size[i] / 2, end[i] + size[i] / 2, size[i]) for i in range(len(size))]
+    centers = torch.cartesian_prod(*axes[::-1]).reshape(-1, len(size)).flip(-1).contiguous()
+    return centers if device is None else centers.to(device)
+
+
+def _count(name, cloud, centers, size):
+    _cloud_and_centers(name, cloud, centers)
+    if centers.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int32, device=cloud.device), None
+    return engine.stage_voxel_count(cloud, centers, _dims(size))
+
+
+def voxel_counts(cloud, centers, size):
+    """Points of cloud [P, C] inside every box of `size` around centers [K, 3], utils.get_voxel's rule (utils.py:135-142: both bounds
+    inclusive, fp32) -> [K] int32."""
+    return _count("voxel_counts", cloud, centers, size)[0]
+
+
+def _rows(name, cloud, centers, size):
+    counts, ws = _count(name, cloud, centers, size)
+    offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=cloud.device)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total = int(offsets[-1])                                           # the one read-back: sizes `rows`
+    rows = engine.stage_voxel_select(cloud, centers, _dims(size), offsets, total, ws) if total else \
+        torch.zeros(0, dtype=torch.int32, device=cloud.device)
+    return counts, offsets, rows
+
+
+def voxel_rows(cloud, centers, size):
+    """CSR member lists of every box: (offsets [K + 1], rows [total]) int64; rows[offsets[k]:offsets[k + 1]] are the rows of `cloud`
+    inside box k in ascending order (= torch.nonzero of get_voxel's mask).  Same input, same bytes on every run."""
+    _, offsets, rows = _rows("voxel_rows", cloud, centers, size)
+    return offsets, rows.long()
+
+
+def _fps_ragged(cloud, offsets, rows32, m, voxel_ids=None):
+    n = offsets[1:] - offsets[:-1]
+    if voxel_ids is not None:
+        n = n[voxel_ids.long()]
+    if n.numel() == 0:
+        return torch.zeros(0, m, dtype=torch.int64, device=cloud.device)
+    lo, hi = (int(v) for v in torch.stack((n.min(), n.max())).tolist())
+    if m < 1 or lo < m:
+        raise RuntimeError(f"fps_ragged: {m} samples asked of a voxel with {lo} rows")
+    return engine.stage_fps_ragged(cloud, offsets, rows32, m, hi, None if voxel_ids is None else voxel_ids.to(torch.int32).contiguous())
+
+
+def fps_ragged(cloud, offsets, rows, m):
+    """Farthest point subsampling of every voxel of a CSR list (voxel_rows) in one launch -> [K, m] int64 rows of `cloud`: the first m
+    picks of `fps(cloud[rows of voxel k], random_start=False)`, index for index.  Raises if a voxel has fewer than m rows."""
+    _scene_input("fps_ragged", cloud)
+    if not (offsets.is_cuda and rows.is_cuda and offsets.dtype == torch.int64 and rows.dtype in (torch.int64, torch.int32)):
+        raise RuntimeError("fps_ragged: offsets (int64) and rows must be GPU tensors (flowcompare_amd has no CPU fallback)")
+    if not 1 <= cloud.shape[1] <= 8:
+        raise RuntimeError("fps_ragged: 1..8 feature columns supported")
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= cloud.shape[0] or int(offsets[-1]) != rows.numel()):
+        raise RuntimeError("fps_ragged: rows / offsets do not describe rows of this cloud")
+    return _fps_ragged(cloud, offsets.contiguous(), rows.to(torch.int32).contiguous(), int(m))
+
+
+def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size, n_samples, n_samples_context, ground_height=None):
+    """The loader's test-mode item (ams_voxel_loader.py:291-307, 338, 349-350) for every centre of a scene at once: target =
+    get_voxel(cloud_1, c, final) -> first n_samples FPS picks, context = get_voxel(cloud_0, c, context) -> first n_samples_context
+    picks, co_unit_sphere(context, target).  A voxel is valid when count_0 >= n_samples_context and count_1 >= n_samples (:240);
+    invalid voxels are skipped, never padded; staged voxels keep ascending centre order.  Returns a SceneStage; with no valid voxel
+    its tensors are empty and nothing is launched beyond the counts.  stage_scene(cloud_0, cloud_0, ...) is the "self" pair."""
+    _cloud_and_centers("stage_scene", cloud_0, centers)
+    _cloud_and_centers("stage_scene", cloud_1, centers)
+    if cloud_0.shape[1] != cloud_1.shape[1] or cloud_0.device != cloud_1.device:
+        raise RuntimeError("stage_scene: the two clouds must have the same columns and device")
+    M, N, C, dev = int(n_samples_context), int(n_samples), cloud_0.shape[1], cloud_0.device
+    if M < 1 or N < 1:
+        raise RuntimeError("stage_scene: sample counts must be positive")
+    count_0, ws_0 = _count("stage_scene", cloud_0, centers, context_voxel_size)
+    count_1, ws_1 = _count("stage_scene", cloud_1, centers, final_voxel_size)
+    voxel = torch.nonzero((count_0 >= M) & (count_1 >= N)).flatten()
+    K1 = voxel.numel()
+    if K1 == 0:
+        f, i = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
+        return SceneStage(extract_0=torch.zeros(0, M, C, **f), extract_1=torch.zeros(0, N, C, **f),
+                          extra_context=None if ground_height is None else torch.zeros(0, 1, **f),
+                          inverse={'furthest_distance': torch.zeros(0, **f), 'mean': torch.zeros(0, 3, **f)},
+                          index_0=torch.zeros(0, M, **i), index_1=torch.zeros(0, N, **i), voxel=voxel, count_0=count_0, count_1=count_1)
+
+    def picks(cloud, size, counts, ws, m):
+        offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=offsets[1:])
+        rows = engine.stage_voxel_select(cloud, centers, _dims(size), offsets, int(offsets[-1]), ws)
+        return _fps_ragged(cloud, offsets, rows, m, voxel)
+
+    index_0 = picks(cloud_0, context_voxel_size, count_0, ws_0, M)
+    index_1 = picks(cloud_1, final_voxel_size, count_1, ws_1, N)
+    e0 = cloud_0.index_select(0, index_0.reshape(-1)).reshape(K1, M, C)
+    e1 = cloud_1.index_select(0, index_1.reshape(-1)).reshape(K1, N, C)
+    o0, o1, inv = engine.stage_co_unit_sphere(e0, e1)
+    inverse = {'furthest_distance': inv[:, 0].contiguous(), 'mean': inv[:, 1:4].contiguous()}
+    extra = None if ground_height is None else (inverse['mean'][:, 2] - ground_height).unsqueeze(-1)
+    return SceneStage(extract_0=o0, extract_1=o1, extra_context=extra, inverse=inverse, index_0=index_0, index_1=index_1, voxel=voxel,
+                      count_0=count_0, count_1=count_1)

@@ -185,6 +185,29 @@ int fc_stage_fps_f32(const float* pts, int32_t ld, int32_t C, int64_t* idx, int3
  * inverse [B,4] = furthest_distance, mean x, y, z (the dict the reference returns with return_inverse=True). */
 int fc_stage_co_unit_sphere_f32(const float* p0, int32_t n0, const float* p1, int32_t n1, int32_t ld, float* out0, float* out1,
                                 float* inverse, int32_t B, void* stream);
+/* ---- staging of whole scene pairs (csrc/scene_stage.hip) ----------------------
+ * Added without a version step: FC_ABI_VERSION stays 9, nothing declared before changes, a caller built against the earlier
+ * v9 header runs unchanged.  Caller-owned device buffers, no allocation, no synchronisation; all three run on `stream`.
+ *
+ * Box membership of utils.get_voxel (utils.py:135-142): row p of cloud [P, ld] (xyz first) is in box k of centers [K, 3] when
+ * c - d/2 <= x <= c + d/2 on all three axes, both bounds inclusive and rounded to fp32 as torch rounds them; a NaN is in no
+ * box; boxes may overlap.  The count call fills counts [K] and leaves in ws (at least the ws_bytes function's size for P, K)
+ * the table the select call needs: select takes the SAME cloud, centers, dims and ws, offsets [K + 1] = exclusive prefix of
+ * counts, and writes every box's member row numbers in ASCENDING order to rows[offsets[k] .. offsets[k + 1]) (a position at or
+ * beyond rows_capacity is not written).  No atomics: the same input gives the same bytes on every run.  P < 2^31 - 512. */
+size_t fc_stage_voxel_ws_bytes(int64_t P, int32_t K);
+int fc_stage_voxel_count_f32(const float* cloud, int32_t ld, int64_t P, const float* centers, int32_t K, float dx, float dy, float dz,
+                             int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+int fc_stage_voxel_select_f32(const float* cloud, int32_t ld, int64_t P, const float* centers, int32_t K, float dx, float dy, float dz,
+                              const int64_t* offsets, int32_t* rows, int64_t rows_capacity, const void* ws, size_t ws_bytes, void* stream);
+/* Farthest point sampling of many voxels of different sizes in one launch: voxel v = voxel_ids[i] (or i when voxel_ids is NULL),
+ * i < n_voxels, owns the cloud rows rows[offsets[v] .. offsets[v + 1]); idx [n_voxels, m] int64 receives the first m picks of
+ * fc_stage_fps_f32 on those rows (all C = first C <= 8 columns, first pick = the voxel's first row, ties to the lowest position)
+ * as row numbers OF THE CLOUD.  max_rows >= every listed voxel's row count >= m; voxels above 24576 rows keep their running
+ * distances in dist_scratch (as many floats as `rows` has entries; may be NULL when max_rows <= 24576). */
+int fc_stage_fps_ragged_f32(const float* cloud, int32_t ld, int32_t C, int64_t P, const int64_t* offsets, const int32_t* rows,
+                            const int32_t* voxel_ids, int32_t n_voxels, int32_t max_rows, int32_t m, int64_t* idx, float* dist_scratch,
+                            void* stream);
 /* Change map (test_flow.py:241-275 log_prob_to_change + clamp_infs): lp10 [B,N], lp00 [B,N0] are clamped IN PLACE when they
  * hold infs (all infs of a tensor -> its smallest non-inf entry), out [B,N] = 1 - (lp10 - min)/(max - min) where
  * lp10 < mean(lp00) - multiple * std(lp00) (per scene, unbiased std) or, with use_cutoff, lp10 < hard_cutoff; 0 elsewhere.

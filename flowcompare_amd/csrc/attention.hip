@@ -218,7 +218,8 @@ struct Attn16Params {
 };
 
 // fp32 K / V columns of the projected context -> limb row images in the ONE-ACCUMULATOR form (common.h kOneAccActScale): x s = hi + lo with
-// lo = rn16(x s - hi) unscaled; raises *ovf when |x s| leaves fp16's range.
+// lo = rn16(x s - hi) unscaled; raises *ovf when |x s| leaves fp16's range.  With a null v16 only the K image is made (the folded engine's
+// context panel, which is the keys AND the values of every layer: launch_context_limbs).
 __global__ __launch_bounds__(256) void kv_limbs_kernel(const float* k, int ldk, const float* v, int ldv, unsigned short* k16, unsigned short* v16,
                                                        long rows, int DH, int* ovf) {
     const int c4 = DH / 4;
@@ -229,6 +230,7 @@ __global__ __launch_bounds__(256) void kv_limbs_kernel(const float* k, int ldk, 
         const int c = (int)(t - row * c4) * 4;
 #pragma unroll
         for (int which = 0; which < 2; ++which) {
+            if (which && !v16) break;
             const float4 x = *reinterpret_cast<const float4*>((which ? v + row * ldv : k + row * ldk) + c);
             const float xs[4] = {x.x, x.y, x.z, x.w};
             uint2 h, l;
@@ -244,12 +246,21 @@ __global__ __launch_bounds__(256) void kv_limbs_kernel(const float* k, int ldk, 
     if (!(amax * kOneAccActScale < 65504.0f)) atomicOr(ovf, 1);
 }
 
-template <int DH>
+// SH = 1 (the folded engine, flow_engine.cpp: K and V of every layer ARE the context panel, head dim 64): k16 is that one packed row image and
+// a tile is staged ONCE -- half the global loads and LDS stores per tile, 16 KB per stage instead of 37 -- into plain 256-byte rows whose
+// 16-byte chunks are XOR-swizzled, chunk ch of row r at 256 r + 16 (ch ^ swz(r)), swz(r) = ((r & 3) << 2) | ((r >> 2) & 3):
+//   * the S phase's ds_read_b128 (lane = row, 16 rows per lane group {0-3, 12-15, 20-27} ...) sees 16 distinct swz values = 16 distinct slots;
+//   * the PV phase's ds_read_b64_tr_b16 (per 32-lane half: 4 rows q x 4 chunks x 2 halves of a chunk) sees slots const ^ (q << 2 | 2-bit chunk):
+//     16 distinct slots x 2 = all 64 banks;
+//   * the staging ds_write_b128 (8 consecutive lanes = 8 consecutive chunks of one row) keeps 8 distinct slots under the XOR.
+// The XOR only touches address bits 4-7, so every read is (lane constant ^ compile-time constant) + immediate.
+template <int DH, int SH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn16_kernel(const Attn16Params p) {
+    static_assert(!SH || DH == 64, "the shared K / V tile is laid out for 256-byte rows");
     constexpr int KS = DH / 16, DT = DH / 32;
-    constexpr int KP = 4 * DH + 16, VP = 4 * DH + 64;          // LDS row pitches in bytes
-    constexpr int VOFF = 64 * KP;
-    constexpr int STAGE = 64 * (KP + VP);
+    constexpr int KP = SH ? 4 * DH : 4 * DH + 16, VP = SH ? 4 * DH : 4 * DH + 64;          // LDS row pitches in bytes
+    constexpr int VOFF = SH ? 0 : 64 * KP;
+    constexpr int STAGE = SH ? 64 * KP : 64 * (KP + VP);
     constexpr int CPR = DH / 4;                                // 16-byte chunks per image row
     constexpr int NCH = 64 * CPR / 256;                        // chunks per thread, tile and image
     extern __shared__ float smem[];
@@ -311,6 +322,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     u32xs rk, rv;
     const uint4* kb = reinterpret_cast<const uint4*>(p.k16) + (size_t)b * p.m_stride * p.kv_pitch;
     const uint4* vb = reinterpret_cast<const uint4*>(p.v16) + (size_t)b * p.m_stride * p.kv_pitch;
+    // shared tile: thread tid stores chunk tid & 15 of rows (tid >> 4) + 16 i, whose swizzle does not depend on i (16 i keeps r & 3, adds 4 i to r >> 2)
+    const int st_sh = (tid >> 4) * KP + 16 * ((tid & 15) ^ ((((tid >> 4) & 3) << 2) | ((tid >> 6) & 3)));
+#define FC_GLOAD_SH(T_)                                                                       \
+    _Pragma("unroll") for (int i = 0; i < NCH; ++i) {                                         \
+        int key_ = (T_) * 64 + (tid >> 4) + 16 * i;                                           \
+        key_ = key_ < p.M ? key_ : p.M - 1; /* clamped rows are masked to -inf below */       \
+        const uint4 a_ = kb[(size_t)key_ * CPR + (tid & 15)];                                 \
+        rk[4 * i] = a_.x; rk[4 * i + 1] = a_.y; rk[4 * i + 2] = a_.z; rk[4 * i + 3] = a_.w;     \
+    }
+#define FC_LSTORE_SH(ST_)                                                                     \
+    _Pragma("unroll") for (int i = 0; i < NCH; ++i)                                           \
+        *reinterpret_cast<uint4*>(smc + (ST_) * STAGE + 16 * i * KP + st_sh) =                \
+            make_uint4(rk[4 * i], rk[4 * i + 1], rk[4 * i + 2], rk[4 * i + 3]);
 #define FC_GLOAD(T_)                                                                          \
     _Pragma("unroll") for (int i = 0; i < NCH; ++i) {                                         \
         const int c_ = tid + 256 * i, kr_ = c_ / CPR, part_ = c_ - kr_ * CPR;                 \
@@ -336,15 +360,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     // transposed-read address of this lane inside a [4 keys][16 columns] block: lane 4q+p of a 16-lane group supplies row q,
     // columns 4p..4p+3; the group's 16 columns are 16*((lane>>4)&1) .. +15 of the 32-column block, its keys start at 4*lh
     const int tr_off = (4 * lh + ((lane & 15) >> 2)) * VP + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+    // shared tile: the lane parts of the swizzled addresses.  S phase: row li, chunk (2 ks | lh) + 8 limb, swz = ((li & 3) << 2) | ((li >> 2) & 3);
+    // PV phase: row 4 lh + q (+ 32 h2 + 16 s2 + 8 j), q = (lane & 15) >> 2, chunk (4 d + 8 limb) | (tr_off's 16-byte chunk), swz = (q << 2) | lh, ^ 2 j
+    const int kr_sh = li * KP + 16 * (lh ^ (((li & 3) << 2) | ((li >> 2) & 3)));
+    const int tr_sh = tr_off ^ (16 * ((((lane & 15) >> 2) << 2) | lh));
 
     const int ntiles = (p.M + 63) / 64;
-    FC_GLOAD(0)
-    FC_LSTORE(0)
+    if constexpr (SH) { FC_GLOAD_SH(0) FC_LSTORE_SH(0) } else { FC_GLOAD(0) FC_LSTORE(0) }
     __syncthreads();
 
     for (int t = 0; t < ntiles; ++t) {
         const int tn = t + 1 < ntiles ? t + 1 : t;          // the last iteration re-loads its own tile: branch-free loop
-        FC_GLOAD(tn)
+        if constexpr (SH) { FC_GLOAD_SH(tn) } else { FC_GLOAD(tn) }
         const char* sK = smc + (t & 1) * STAGE;
         const char* sV = sK + VOFF;
 
@@ -357,8 +384,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
             const char* kr = sK + (32 * h2 + li) * KP + 16 * lh;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const f16x8 kh = *reinterpret_cast<const f16x8*>(kr + 32 * ks);
-                const f16x8 kl = *reinterpret_cast<const f16x8*>(kr + 2 * DH + 32 * ks);
+                const f16x8 kh = *reinterpret_cast<const f16x8*>(SH ? sK + 32 * h2 * KP + (kr_sh ^ (32 * ks)) : kr + 32 * ks);
+                const f16x8 kl = *reinterpret_cast<const f16x8*>(SH ? sK + 32 * h2 * KP + (kr_sh ^ (32 * ks + 2 * DH)) : kr + 2 * DH + 32 * ks);
                 s[h2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], s[h2], 0, 0, 0);
                 s[h2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], s[h2], 0, 0, 0);
                 s[h2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], s[h2], 0, 0, 0);
@@ -422,9 +449,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
                 for (int d = 0; d < DT; ++d) {
                     // (assembled with one shufflevector + whole-vector bit_cast: element-wise extraction of the read's result made hipcc
                     //  emit v_perm/v_mov sequences that duplicated its first dword)
-#define FC_TR(OFF_) __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(vr + (OFF_)))
-                    const f16x8 vh = __builtin_bit_cast(f16x8, __builtin_shufflevector(FC_TR(64 * d), FC_TR(8 * VP + 64 * d), 0, 1, 2, 3, 4, 5, 6, 7));
-                    const f16x8 vl = __builtin_bit_cast(f16x8, __builtin_shufflevector(FC_TR(64 * d + 2 * DH), FC_TR(8 * VP + 64 * d + 2 * DH),
+                    // FC_TR(j, col): keys 8 j .. 8 j + 7 of this k-step, byte column col of a row (32 columns of block d at 64 d, the low limb at
+                    // + 2 DH).  Shared tile: the rows ride in the offset, the lane's swizzle in tr_sh, and 8 j more rows add 2 j to swz (^ 32 bytes)
+#define FC_TR(J_, COL_) __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)( \
+        SH ? sV + (32 * h2 + 16 * s2 + 8 * (J_)) * VP + (tr_sh ^ (COL_) ^ (32 * (J_))) : vr + 8 * (J_) * VP + (COL_)))
+                    const f16x8 vh = __builtin_bit_cast(f16x8, __builtin_shufflevector(FC_TR(0, 64 * d), FC_TR(1, 64 * d), 0, 1, 2, 3, 4, 5, 6, 7));
+                    const f16x8 vl = __builtin_bit_cast(f16x8, __builtin_shufflevector(FC_TR(0, 64 * d + 2 * DH), FC_TR(1, 64 * d + 2 * DH),
                                                                                       0, 1, 2, 3, 4, 5, 6, 7));
 #undef FC_TR
                     om[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh, om[d], 0, 0, 0);
@@ -433,11 +463,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
                 }
             }
         }
-        FC_LSTORE((t + 1) & 1)
+        if constexpr (SH) { FC_LSTORE_SH((t + 1) & 1) } else { FC_LSTORE((t + 1) & 1) }
         __syncthreads();
     }
 #undef FC_GLOAD
 #undef FC_LSTORE
+#undef FC_GLOAD_SH
+#undef FC_LSTORE_SH
 
     if (p.lse && lane < 32 && q0 + lane < p.N)                   // scores are in the log2 domain (qscale carries log2 e); l_run carries 2^12 and the reference m_run
         p.lse[(size_t)b * p.n_stride + q0 + lane] = (m_run - P_EXP + __builtin_amdgcn_logf(l_run)) * 0.6931471805599453f;
@@ -460,14 +492,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
 //  softmax is VALU issue time that two waves per SIMD need more of than of MFMA time under any interleaving.  The kernel was removed when
 //  this one went to a single accumulator; its measurements stay in DESIGN.md section 9 and profiles/r04q_*, r04r_attn_stamps.log.)
 
-template <int DH>
+template <int DH, int SH = 0>
 static void launch_attn16_dh(const Attn16Params& p, int B, hipStream_t s) {
-    constexpr size_t lds = 2 * 64 * (size_t)(8 * DH + 80);
+    constexpr size_t lds = SH ? 2 * 64 * (size_t)(4 * DH) : 2 * 64 * (size_t)(8 * DH + 80);
     static PerDeviceOnce attr_once;
-    auto kern = attn16_kernel<DH>;
+    auto kern = attn16_kernel<DH, SH>;
     attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
     char name[64];
-    snprintf(name, sizeof name, "void fc::attn16_kernel<%d>(fc::Attn16Params)", DH);
+    if (SH) snprintf(name, sizeof name, "void fc::attn16_kernel<%d, 1>(fc::Attn16Params)", DH);
+    else snprintf(name, sizeof name, "void fc::attn16_kernel<%d>(fc::Attn16Params)", DH);
     ProfScope ps(name, 4.0 * B * (double)p.N * (double)p.M * DH, 0.0, s);
     hipLaunchKernelGGL(kern, dim3((p.N + 127) / 128, B), dim3(256), lds, s, p);
     FC_HIP(hipGetLastError());
@@ -544,6 +577,30 @@ void launch_attention_c16(const float* q, int ldq, const unsigned short* kv_c16,
     const unsigned short* kp = kv_c16 + (size_t)(col0 / 16) * 32;
     const unsigned short* vp = kp + (size_t)(dh_pad / 16) * 32;
     launch_attention_scaled(q, ldq, nullptr, 4, nullptr, 4, out, ldo, B, N, n_stride_rows, M, m_stride_rows, dh_pad, 1.0f, nullptr, s, kp, vp, n_pad / 4, lnq);
+}
+
+// The folded engine (flow_engine.cpp, fc_debug_set 33): keys and values of every attention are the context panel itself.  Its limb image
+// [row][hi dh_pad | lo dh_pad] (kv_limbs_kernel's K image alone) is made once per forward ...
+void launch_context_limbs(const float* ctx, int ldc, unsigned short* img, long rows, int dh_pad, hipStream_t s) {
+    int* flag = gemm_fp16_flag();
+    if (!flag || dh_pad > 64 || dh_pad % 4 != 0 || ldc % 4 != 0 || ldc < dh_pad || (((uintptr_t)ctx | (uintptr_t)img) & 15))
+        throw Error(FC_ERR_INVALID, "context limb image: needs a guard scope, a head dim <= 64 within the row pitch and 16-byte aligned operands");
+    ProfScope ps("fc::kv_limbs_kernel", 0.0, (double)rows * dh_pad * 8.0, s);
+    const long n = rows * (dh_pad / 4);
+    hipLaunchKernelGGL(kv_limbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctx, ldc, nullptr, 0, img, nullptr, rows, dh_pad, flag);
+    FC_HIP(hipGetLastError());
+}
+// ... and every layer attends over it: at head dim 64 with ONE staged tile per 64 keys (attn16_kernel<64, 1>), at 32 with the two-image kernel
+// reading the same image twice
+void launch_attention_ctx16(const float* q, int ldq, const unsigned short* ctx16, float* out, int ldo, int B, int N, int n_stride_rows, int M,
+                            int m_stride_rows, int dh_pad, hipStream_t s, const AttnLnq* lnq, float qscale) {
+    if (B <= 0 || N <= 0 || M <= 0) throw Error(FC_ERR_INVALID, "attention: empty problem");
+    int* flag = gemm_fp16_flag();
+    if (!flag || !ctx16 || (dh_pad != 32 && dh_pad != 64) || (ldq % 4) != 0 || (((uintptr_t)q | (uintptr_t)ctx16) & 15))
+        throw Error(FC_ERR_INVALID, "attention: the context limb image needs a guard scope, head dim 32 or 64 and 16-byte aligned operands");
+    Attn16Params p{q, ldq, ctx16, ctx16, out, ldo, N, n_stride_rows, M, m_stride_rows, qscale, flag, lnq ? lnq->sumsq : nullptr,
+                   lnq ? lnq->slots : 0, lnq ? lnq->pitch : 0, lnq ? lnq->inv_width : 0.f, lnq ? lnq->bias : nullptr, dh_pad / 4, 0};
+    if (dh_pad == 32) launch_attn16_dh<32>(p, B, s); else launch_attn16_dh<64, 1>(p, B, s);
 }
 
 // training path (train_attention.hip): strided q / k / v (columns of wider panels), explicit softmax scale

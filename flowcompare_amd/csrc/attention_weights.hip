@@ -4,7 +4,8 @@
 // caller asks about, and reads the operands in the forms the forward leaves them in:
 //   K  KF 0: an fp32 panel (head dim 128, the range-fallback pass, fc_op_*);  KF 1: columns of the stacked K|V GEMM's one-accumulator limb image
 //      (GemmEpi::C16 with c16_scale = kOneAccActScale: [16 columns: hi 16 | lo 16] tiles, k 16 = hi + lo) -- joined back to fp32 while the tile
-//      is staged, which is exact: hi + lo spans at most 22 significant bits;
+//      is staged, which is exact: hi + lo spans at most 22 significant bits; with k16_rows the folded engine's context image instead, packed rows
+//      [key][hi DH | lo DH] of the same form (launch_context_limbs: the keys of EVERY layer, with q carrying the layer's Wk);
 //   q  final, or the un-normalised projection of the LayerNorm -> q fold, finished on load with rstd and the bias exactly as attn16_kernel does.
 // Arithmetic: fp32 operands on v_mfma_f32_32x32x2_f32, fp32 everywhere (DESIGN.md section 11b says why not the limb products).
 //
@@ -26,6 +27,7 @@ struct AttnWParams {
     const float* q; int ldq;
     const float* k; int ldk;             // KF 0
     const unsigned short* k16; int ld16; // KF 1: first half-word of this layer's K columns, half-words per image row
+    int k16_rows;                        // KF 1: 0 = [16 columns: hi 16 | lo 16] tiles of a GEMM limb image, 1 = packed rows [hi DH | lo DH]
     float* out;                          // [B][P][M]
     const int* sel; int sel_stride;      // null = query p; else sel[b * sel_stride + p]  (sel_stride 0: one table for all scenes)
     int P, N, n_stride, M, m_stride;
@@ -85,8 +87,8 @@ __global__ __launch_bounds__(256) void attn_weights_kernel(const AttnWParams p) 
                 const int row = i / G8, w8 = i - row * G8;
                 int key = t * 64 + row;
                 key = key < p.M ? key : p.M - 1;
-                const unsigned short* src = p.k16 + ((size_t)b * p.m_stride + key) * p.ld16 + (w8 >> 1) * 32 + (w8 & 1) * 8;
-                const uint4 hu = *reinterpret_cast<const uint4*>(src), lu = *reinterpret_cast<const uint4*>(src + 16);
+                const unsigned short* src = p.k16 + ((size_t)b * p.m_stride + key) * p.ld16 + (p.k16_rows ? 8 * w8 : (w8 >> 1) * 32 + (w8 & 1) * 8);
+                const uint4 hu = *reinterpret_cast<const uint4*>(src), lu = *reinterpret_cast<const uint4*>(src + (p.k16_rows ? DH : 16));
                 const unsigned hw[4] = {hu.x, hu.y, hu.z, hu.w}, lw[4] = {lu.x, lu.y, lu.z, lu.w};
                 float x[8];
 #pragma unroll
@@ -193,15 +195,25 @@ static void launch_attnw_dh(const AttnWParams& p, int B, hipStream_t s) {
 
 void launch_attention_weights(const float* q, int ldq, const float* k, int ldk, const unsigned short* kv_c16, int c16_n_pad, int c16_col0,
                               float* out, const int32_t* sel, int P, int sel_per_scene, int B, int N, int n_stride_rows, int M, int m_stride_rows,
-                              int dh_pad, float qscale, const AttnLnq* lnq, hipStream_t s) {
+                              int dh_pad, float qscale, const AttnLnq* lnq, hipStream_t s, const unsigned short* k_rows16) {
     if (B <= 0 || N <= 0 || M <= 0 || P <= 0) throw Error(FC_ERR_INVALID, "attention weights: empty problem");
-    if (!q || !out || (!k && !kv_c16)) throw Error(FC_ERR_INVALID, "attention weights: null pointer");
+    if (!q || !out || (!k && !kv_c16 && !k_rows16)) throw Error(FC_ERR_INVALID, "attention weights: null pointer");
     if (!sel && P != N) throw Error(FC_ERR_INVALID, "attention weights: without a selection table P must equal N");
     if (ldq % 4 != 0 || ((uintptr_t)q & 15)) throw Error(FC_ERR_INVALID, "attention weights: q must be 16-byte aligned with a pitch that is a multiple of 4 floats");
     AttnWParams p{};
     p.q = q; p.ldq = ldq; p.out = out; p.sel = sel; p.sel_stride = sel && sel_per_scene ? P : 0;
     p.P = P; p.N = N; p.n_stride = n_stride_rows; p.M = M; p.m_stride = m_stride_rows; p.qscale = qscale;
     if (lnq) { p.q_sumsq = lnq->sumsq; p.q_slots = lnq->slots; p.q_pitch = lnq->pitch; p.q_inv_width = lnq->inv_width; p.q_bias = lnq->bias; }
+    if (k_rows16) {
+        if (((uintptr_t)k_rows16 & 15)) throw Error(FC_ERR_INVALID, "attention weights: the context limb image must be 16-byte aligned");
+        p.k16 = k_rows16;
+        p.ld16 = 2 * dh_pad;
+        p.k16_rows = 1;
+        if (dh_pad == 32) launch_attnw_dh<32, 1>(p, B, s);
+        else if (dh_pad == 64) launch_attnw_dh<64, 1>(p, B, s);
+        else throw Error(FC_ERR_UNSUPPORTED, "attention weights: inner dim (padded) must be 32 or 64 with a limb-image K");
+        return;
+    }
     if (kv_c16) {
         if (c16_col0 % 16 != 0 || c16_n_pad % 16 != 0 || dh_pad > 64) throw Error(FC_ERR_INVALID, "attention weights: limb-image K needs 16-column tiles and head dim <= 64");
         p.k16 = kv_c16 + (size_t)(c16_col0 / 16) * 32;

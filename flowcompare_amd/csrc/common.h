@@ -319,14 +319,20 @@ bool attention_fp16_enabled();
 struct AttnLnq { const float* sumsq; int slots; size_t pitch; float inv_width; const float* bias; };
 void launch_attention_c16(const float* q, int ldq, const unsigned short* kv_c16, int n_pad, int col0, float* out, int ldo, int B, int N,
                           int n_stride_rows, int M, int m_stride_rows, int dh_pad, hipStream_t s, const AttnLnq* lnq = nullptr);
+// the folded engine's attention: keys = values = the context panel, as ONE limb row image [row][hi dh_pad | lo dh_pad] of x 16 (made once per
+// forward by launch_context_limbs from the fp32 panel; raises the scope's range flag like the K|V projection's epilogue does)
+void launch_context_limbs(const float* ctx, int ldc, unsigned short* img, long rows, int dh_pad, hipStream_t s);
+void launch_attention_ctx16(const float* q, int ldq, const unsigned short* ctx16, float* out, int ldo, int B, int N, int n_stride_rows, int M,
+                            int m_stride_rows, int dh_pad, hipStream_t s, const AttnLnq* lnq = nullptr, float qscale = 1.0f);
 void launch_attention_op(const float* q, const float* k, const float* v, float* out, int B, int N, int M, int dh_pad, float scale,
                          void* limb_ws, hipStream_t s);
 // attention_weights.hip: out[b, p, :] = softmax row of query sel[b, p] (null sel: query p, P == N) over the M keys, dense [B][P][M].  K is the fp32
 // panel k, or -- kv_c16 non-null -- columns [c16_col0, c16_col0 + dh_pad) of a GEMM limb-image output with c16_n_pad columns per row in the
-// one-accumulator form (what launch_attention_c16 reads); lnq as for launch_attention_c16.  No range check on sel on the device.
+// one-accumulator form (what launch_attention_c16 reads), or -- k_rows16 non-null -- the packed row image [key][hi dh_pad | lo dh_pad] of
+// launch_context_limbs; lnq as for launch_attention_c16.  No range check on sel on the device.
 void launch_attention_weights(const float* q, int ldq, const float* k, int ldk, const unsigned short* kv_c16, int c16_n_pad, int c16_col0,
                               float* out, const int32_t* sel, int P, int sel_per_scene, int B, int N, int n_stride_rows, int M, int m_stride_rows,
-                              int dh_pad, float qscale, const AttnLnq* lnq, hipStream_t s);
+                              int dh_pad, float qscale, const AttnLnq* lnq, hipStream_t s, const unsigned short* k_rows16 = nullptr);
 void launch_base_density(const float* x, int ldx, int d1, int d1_pad, int d2, float* logprob, float log_const,
                          float* z_out, int D, int rows, hipStream_t s);
 void launch_spline(const float* params, int ldp, float* xbuf, int ldx, int x2_col0, int d2, int K, float* logprob, int rows, int inverse,

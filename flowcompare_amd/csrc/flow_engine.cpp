@@ -5,6 +5,8 @@
 // initialize_flow assembles (model_initialization.py:136-160).  Weight folding done once at create (double precision):
 //   * attn.fn.lin (I -> attn_dim) is folded INTO the coupling / augmenter in_layer:  W_ctx (W_lin a + b_lin) = (W_ctx W_lin) a + W_ctx b_lin
 //   * LayerNorm gamma/beta, the softmax scale inner^-0.5 and log2(e) are folded into the q projection
+//   * to_kv away (kv_fold_gate below): q k^T = LN(h) (Wk^T Wq)^T ctx^T and lin(softmax v) = (softmax ctx) (Wlin Wv)^T + b, so Wk rides in the q
+//     projection, Wv in lin (and with it in the consumer's in_layer), and every attention's keys AND values are the context panel itself
 //   * ActNorm and the permuter (LinearLU: L U; FullCombiner: w; ExponentialCombiner: expm; Permuter: P) become ONE matrix
 //     z = W' x + b',  W' = P diag(e^-log_scale),  b' = -W' shift; their log-dets are data independent and summed into one constant
 //   * extra context (one scalar per scene) enters every in_layer as a rank-1 epilogue term instead of a concatenated column
@@ -34,9 +36,9 @@ struct AttnPack {
     PackedLinear lnq;
     float* q_bias = nullptr;
     bool has_lnq = false;
-    MatD lin_w;          // [attn_dim][I]  (folded into the consumer's in_layer)
+    MatD lin_w;          // [attn_dim][I]  (folded into the consumer's in_layer; with the K|V fold: Wlin Wv, [attn_dim][E])
     VecD lin_b;
-    int kv_col = 0;      // column of this layer's [K | V] block inside the kv buffer
+    int kv_col = 0;      // column of this layer's [K | V] block inside the kv buffer (unused with the K|V fold)
 };
 
 // CIFblock pieces (models/cif_block.py:49-112), all expressed in the NATURAL index order of x (D) and z2 (Dc - D): the two
@@ -88,18 +90,38 @@ struct fc_flow {
     fc::PackedMLP aug_pre, aug_net;
     fc::AttnPack aug_attn;
     std::vector<fc::BlockPack> blocks;
-    fc::PackedLinear kv_all;   // ctx -> [K|V] of every attention (augmenter first)
+    fc::PackedLinear kv_all;   // ctx -> [K|V] of every attention (augmenter first); not packed when kv_fold
+    bool kv_fold = false;      // to_kv folded into the q projections and the consumers' in_layers: keys = values = the context panel
     int n_attn = 0;
     double log_const = 0.0;
 };
 
 namespace fc {
 
+int g_kv_fold = 1;           // knob 33, read when a flow is created: 1 = fold to_kv away where the gate allows it (shipped), 0 = stacked K|V projection
+
+// The K|V fold keeps every weight shape only when the context embedding is as wide as the attention's inner dimension (every shipped
+// configuration: 64 = 64), and the algebra above has no place for a bias on to_q / to_kv (the reference has none, models/perceiver.py:89-95).
+// The attention kernels then read the context panel (pitch E_pad = E rounded up to 32) as I_pad-column keys and values, so the two padded
+// widths must agree as well: inner 65..96 pads to 128 (pad_inner) but its panel to 96, and keeps the projection.
 static int pad_inner(int I) {
     if (I <= 32) return 32;
     if (I <= 64) return 64;
     if (I <= 128) return 128;
     throw Error(FC_ERR_UNSUPPORTED, "attention inner dim (cross_heads*cross_dim_head) > 128 is not supported yet");
+}
+bool kv_fold_gate_dims(int E, int inner, bool q_bias, bool kv_bias) {
+    return E > 0 && E == inner && inner <= 128 && round_up(E, 32) == pad_inner(inner) && !q_bias && !kv_bias;
+}
+static bool kv_fold_gate(const fc_flow_config& c, const WeightTable& wt, const std::vector<std::string>& attn_prefixes) {
+    if (!g_kv_fold || attn_prefixes.empty()) return false;
+    for (const std::string& p : attn_prefixes) {
+        const HostTensor& wq = wt.get(p + ".fn.attention.to_q.weight");
+        if (wq.shape.size() != 2 || !kv_fold_gate_dims(c.input_embedding_dim, (int)wq.shape[0], wt.has(p + ".fn.attention.to_q.bias"),
+                                                       wt.has(p + ".fn.attention.to_kv.bias")))
+            return false;
+    }
+    return true;
 }
 
 // q' = c * Wq (gamma . n + beta),  c = inner^-0.5 * log2(e)   (models/perceiver.py:18-26, 96-110)
@@ -119,20 +141,40 @@ static void build_attn(fc_flow& f, const WeightTable& wt, const std::string& p, 
             bq[i] += c * wq.at(i, k) * beta[k];
             wq.at(i, k) *= c * gamma[k];
         }
-    out.q = pack_linear(f.arena, wq, bq, {}, map_prefix(I, d.I_pad), map_prefix(A_in, d.A_in_pad), {d.A_in_pad});
-    out.q_w = wq;
-    out.q_b = bq;
     const HostTensor& wkv_t = wt.get(p + ".fn.attention.to_kv.weight", {2 * I, d.E});
     MatD wkv = mat_from(wkv_t);                 // rows [0,I) = K, [I,2I) = V  (chunk(2, dim=-1))
-    MatD blk(2 * d.I_pad, d.E);
-    for (int i = 0; i < I; ++i)
-        for (int k = 0; k < d.E; ++k) { blk.at(i, k) = wkv.at(i, k); blk.at(d.I_pad + i, k) = wkv.at(I + i, k); }
-    out.kv_col = slot * 2 * d.I_pad;            // column block of this attention in the stacked K|V projection
-    kv_rows[slot] = blk;
     const HostTensor& wl = wt.get(p + ".fn.lin.weight");
     if (wl.shape.size() != 2 || wl.shape[1] != I) throw Error(FC_ERR_SHAPE, p + ".fn.lin.weight: expected [attn_dim, inner]");
     out.lin_w = mat_from(wl);
     out.lin_b = vec_from(wt.get(p + ".fn.lin.bias", {wl.shape[0]}));
+    if (f.kv_fold) {
+        // q . k = (Wq' n + bq') . (Wk ctx) = ctx . (Wk^T Wq' n + Wk^T bq'): the q projection now ends in the E (= I) context columns;
+        // Wlin (P Wv ctx) = (Wlin Wv) (P ctx): lin now starts from them.  Shapes unchanged (kv_fold_gate).
+        MatD wq2(d.E, A_in), lw2(out.lin_w.rows, d.E);
+        VecD bq2(d.E, 0.0);
+        for (int e = 0; e < d.E; ++e) {
+            for (int i = 0; i < I; ++i) {
+                const double wk = wkv.at(i, e);
+                bq2[e] += wk * bq[i];
+                for (int k = 0; k < A_in; ++k) wq2.at(e, k) += wk * wq.at(i, k);
+            }
+        }
+        for (int c2 = 0; c2 < out.lin_w.rows; ++c2)
+            for (int i = 0; i < I; ++i) {
+                const double wlv = out.lin_w.at(c2, i);
+                for (int e = 0; e < d.E; ++e) lw2.at(c2, e) += wlv * wkv.at(I + i, e);
+            }
+        wq = wq2; bq = bq2; out.lin_w = lw2;
+    } else {
+        MatD blk(2 * d.I_pad, d.E);
+        for (int i = 0; i < I; ++i)
+            for (int k = 0; k < d.E; ++k) { blk.at(i, k) = wkv.at(i, k); blk.at(d.I_pad + i, k) = wkv.at(I + i, k); }
+        out.kv_col = slot * 2 * d.I_pad;            // column block of this attention in the stacked K|V projection
+        kv_rows[slot] = blk;
+    }
+    out.q = pack_linear(f.arena, wq, bq, {}, map_prefix(I, d.I_pad), map_prefix(A_in, d.A_in_pad), {d.A_in_pad});
+    out.q_w = wq;
+    out.q_b = bq;
 }
 
 // LayerNorm -> q fold (see AttnPack::lnq).  h = W3 a + b3 has no activation, so its centred form h_c = h - mean(h) is linear in a:
@@ -416,6 +458,14 @@ static void build_flow(fc_flow& f, const WeightTable& wt) {
     f.has_augment = d.D > d.Din;
     const int aug_slots = f.has_augment ? 1 : 0;
     std::vector<MatD> kv_rows(aug_slots + (c.global_context ? 0 : c.n_flow_layers));
+    {
+        std::vector<std::string> ap;
+        if (f.has_augment) ap.push_back("transforms.0.attn");
+        if (!c.global_context)
+            for (int l = 0; l < c.n_flow_layers; ++l)
+                ap.push_back("transforms." + std::to_string(1 + l * (2 + (c.act_norm ? 1 : 0))) + (cif ? ".flow" : "") + ".pre_conditioner.attn");
+        f.kv_fold = kv_fold_gate(c, wt, ap);
+    }
     std::mutex dims_mu;                          // d.H_pad / d.ldp maxima are the only shared writes of the per-layer builders
 
     // ---- transform 0: AugmentAttentionPreconditioner (models/augmenter.py:7-22) or IdentityTransform
@@ -511,7 +561,7 @@ static void build_flow(fc_flow& f, const WeightTable& wt) {
     for (const BlockPack& b : f.blocks) f.log_const += b.cif.log_const + b.log_const;      // fixed order: reproducible
     // ---- one stacked K|V projection for every attention
     f.n_attn = (int)kv_rows.size();
-    if (f.n_attn) {
+    if (f.n_attn && !f.kv_fold) {
         MatD all(f.n_attn * 2 * d.I_pad, d.E);
         for (int a = 0; a < f.n_attn; ++a) std::copy(kv_rows[a].v.begin(), kv_rows[a].v.end(), all.v.begin() + (size_t)a * 2 * d.I_pad * d.E);
         f.kv_all = pack_linear(f.arena, all, {}, {}, map_prefix(all.rows, all.rows), map_prefix(d.E, d.E_pad), {d.E_pad});
@@ -521,7 +571,8 @@ static void build_flow(fc_flow& f, const WeightTable& wt) {
 // ---------------------------------------------------------------- workspace plan
 struct FlowWs {
     float *xa, *xb, *h[3], *q, *a, *ctxp, *kv, *xin, *rowscal, *spl, *cbuf;
-    void* kv16;      // K / V limb images of the layer in flight (split-fp16 attention)
+    void* kv16;      // K / V limb images of the layer in flight (split-fp16 attention); with the K|V fold: the context panel's one image
+    const unsigned short* ctx16;   // K|V fold, split-fp16 attention: kv16 holds the context limb image of this forward (prepare); else null
     float* ldjp;     // log-det partial slots of the fused spline / pair epilogues, [ldj_slots][P_pad] (ldj_slot_count)
     int ldj_slots;
     bool kv_limbs;         // w.kv holds the K|V projections as the GEMM's fp16 limb image (GemmEpi::C16) instead of fp32
@@ -562,7 +613,7 @@ static FlowWs plan_ws(const fc_flow& f, int B, int N, int M, void* ws, size_t by
     FlowWs w{};
     w.P = B * N; w.P_pad = round_up(w.P, ROW_PAD);
     w.Pc = B * M; w.Pc_pad = round_up(w.Pc, ROW_PAD);
-    w.ldkv = f.n_attn * 2 * d.I_pad;
+    w.ldkv = f.kv_fold ? 0 : f.n_attn * 2 * d.I_pad;      // (K|V fold: no projected K|V, no region for them)
     WsCarver c(ws, bytes, dry);
     w.xa = c.floats((size_t)w.P_pad * d.ldx);
     w.xb = c.floats((size_t)w.P_pad * d.ldx);
@@ -570,7 +621,7 @@ static FlowWs plan_ws(const fc_flow& f, int B, int N, int M, void* ws, size_t by
     w.q = c.floats((size_t)w.P_pad * std::max(d.I_pad, 32));
     w.a = c.floats((size_t)w.P_pad * std::max(d.I_pad, 32));
     w.ctxp = c.floats((size_t)w.Pc_pad * d.E_pad);
-    w.kv = c.floats((size_t)w.Pc_pad * std::max(w.ldkv, 32));
+    w.kv = f.kv_fold ? nullptr : c.floats((size_t)w.Pc_pad * std::max(w.ldkv, 32));
     w.xin = c.floats((size_t)w.P_pad * 32);
     w.rowscal = c.floats((size_t)w.P_pad);
     w.spl_rows = expm_wide(f) ? expm_chunk_rows(f, w.P_pad) : w.P_pad;
@@ -580,7 +631,7 @@ static FlowWs plan_ws(const fc_flow& f, int B, int N, int M, void* ws, size_t by
     w.ldjp = c.floats(std::max<size_t>((size_t)w.ldj_slots * w.P_pad, 1));
     w.h16 = (unsigned short*)c.bytes((size_t)w.P_pad * std::max(d.H_pad, 32) * 4);
     w.lnss = c.floats(f.n_attn > 0 ? (size_t)(std::max(d.A_in, 64) / 64) * w.P_pad : 1);
-    w.kv16 = c.bytes(f.n_attn > 0 ? std::max<size_t>(attention_limb_ws_bytes(w.Pc_pad, d.I_pad), 16) : 16);
+    w.kv16 = c.bytes(f.n_attn > 0 ? std::max<size_t>(attention_limb_ws_bytes(w.Pc_pad, d.I_pad) / (f.kv_fold ? 2 : 1), 16) : 16);
     w.lp_scratch = c.floats((size_t)w.P_pad);
     if (need) *need = c.off + 256;
     return w;
@@ -648,9 +699,20 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
         if (!probe) return;
         for (size_t i = 0; i < probe->layers.size(); ++i)
             if (probe->layers[i] == probe_layer)
-                launch_attention_weights(w.q, d.I_pad, w.kv_limbs ? nullptr : w.kv + at.kv_col, w.ldkv,
-                                         w.kv_limbs ? reinterpret_cast<const unsigned short*>(w.kv) : nullptr, w.ldkv, at.kv_col, probe->out[i],
-                                         probe->sel, probe->P, probe->sel_per_scene, B, N, N, M, M, d.I_pad, 1.0f, lq, s);
+                if (f.kv_fold)
+                    launch_attention_weights(w.q, d.I_pad, w.ctxp, d.E_pad, nullptr, 0, 0, probe->out[i], probe->sel, probe->P, probe->sel_per_scene, B, N, N,
+                                             M, M, d.I_pad, 1.0f, lq, s, w.ctx16);
+                else
+                    launch_attention_weights(w.q, d.I_pad, w.kv_limbs ? nullptr : w.kv + at.kv_col, w.ldkv,
+                                             w.kv_limbs ? reinterpret_cast<const unsigned short*>(w.kv) : nullptr, w.ldkv, at.kv_col, probe->out[i],
+                                             probe->sel, probe->P, probe->sel_per_scene, B, N, N, M, M, d.I_pad, 1.0f, lq, s);
+    };
+    // q complete in w.q (`lq` null) or up to rstd and the bias, which the limb-image kernels apply on load
+    auto attend = [&](const AttnLnq* lq) {
+        if (w.ctx16) launch_attention_ctx16(w.q, d.I_pad, w.ctx16, w.a, d.I_pad, B, N, N, M, M, d.I_pad, s, lq);
+        else if (f.kv_fold) launch_attention(w.q, d.I_pad, w.ctxp, d.E_pad, w.ctxp, d.E_pad, w.a, d.I_pad, B, N, N, M, M, d.I_pad, nullptr, s);
+        else if (w.kv_limbs) launch_attention_c16(w.q, d.I_pad, reinterpret_cast<const unsigned short*>(w.kv), w.ldkv, at.kv_col, w.a, d.I_pad, B, N, N, M, M, d.I_pad, s, lq);
+        else launch_attention(w.q, d.I_pad, w.kv + at.kv_col, w.ldkv, w.kv + at.kv_col + d.I_pad, w.ldkv, w.a, d.I_pad, B, N, N, M, M, d.I_pad, w.kv16, s);
     };
     if (premlp_fusable(pre.in_layer, pre.mid, pre.out_layer, at.q) && in.lda >= pre.in_layer.K_pad &&
         premlp_rows_ok(w.P_pad, d.I_pad, w.q, w.h[0], (size_t)w.P_pad * ldh)) {
@@ -671,17 +733,15 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
             if (chain) e.A16 = w.h16;
             ASeg a{chain ? w.h[0] : w.h[cur], ldh};
             launch_gemm(at.lnq, &a, w.P_pad, e, EPI_LNQ, s);
-            if (w.kv_limbs) {
+            if (w.kv_limbs || w.ctx16) {
                 // the attention kernel applies rstd and the bias while it loads its queries
                 const AttnLnq lq{w.lnss, d.A_in / 64, (size_t)w.P_pad, 1.0f / (float)d.A_in, at.q_bias};
                 probe_here(&lq);
-                launch_attention_c16(w.q, d.I_pad, reinterpret_cast<const unsigned short*>(w.kv), w.ldkv, at.kv_col, w.a, d.I_pad, B, N, N, M, M,
-                                     d.I_pad, s, &lq);
+                attend(&lq);
             } else {
                 launch_lnq_finalize(w.q, d.I_pad, w.lnss, d.A_in / 64, (size_t)w.P_pad, d.A_in, at.q_bias, w.P, s);
                 probe_here(nullptr);
-                launch_attention(w.q, d.I_pad, w.kv + at.kv_col, w.ldkv, w.kv + at.kv_col + d.I_pad, w.ldkv, w.a, d.I_pad, B, N, N, M, M, d.I_pad,
-                                 w.kv16, s);
+                attend(nullptr);
             }
             return;
         }
@@ -698,8 +758,7 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
         launch_gemm(at.q, &aq, w.P_pad, eq, EPI_LINEAR, s);
     }
     probe_here(nullptr);
-    if (w.kv_limbs) launch_attention_c16(w.q, d.I_pad, reinterpret_cast<const unsigned short*>(w.kv), w.ldkv, at.kv_col, w.a, d.I_pad, B, N, N, M, M, d.I_pad, s);
-    else launch_attention(w.q, d.I_pad, w.kv + at.kv_col, w.ldkv, w.kv + at.kv_col + d.I_pad, w.ldkv, w.a, d.I_pad, B, N, N, M, M, d.I_pad, w.kv16, s);
+    attend(nullptr);
 }
 
 // the conditioned coupling of one block (PreConditionApplier, models/transform.py:47-58), forward or inverse, in place on xc
@@ -820,7 +879,14 @@ static Prep prepare(fc_flow& f, const float* ctx, const float* extra, int B, int
     // depend on what ran in the workspace before (found in round 4: one scene of 200 context points behind a three-scene batch)
     if (w.Pc_pad > w.Pc) launch_fill(w.ctxp + (size_t)w.Pc * d.E_pad, 0.f, (size_t)(w.Pc_pad - w.Pc) * d.E_pad, s);
     if (d.X) { launch_repeat_extra(extra, d.X, w.rowscal, B, N, s); p.rowscal = w.rowscal; }
-    if (f.n_attn) {
+    if (f.n_attn && f.kv_fold) {
+        // keys = values = the context panel: one limb image per forward for the split-fp16 attention (range flag as the projection's epilogue
+        // raised it); the fp32-input attention (knob 5 = 0, the bf16-limb repeat of a pass) reads the panel itself
+        if (gemm_fp16_flag() && attention_fp16_enabled() && d.I_pad <= 64) {
+            launch_context_limbs(w.ctxp, d.E_pad, reinterpret_cast<unsigned short*>(w.kv16), w.Pc, d.I_pad, s);
+            w.ctx16 = reinterpret_cast<const unsigned short*>(w.kv16);
+        }
+    } else if (f.n_attn) {
         // inside a guard scope the stacked K|V projection writes its output straight as the limb image the split-fp16 attention
         // stages (same bytes, same buffer): no fp32 K/V, no per-layer conversion pass
         w.kv_limbs = gemm_limb_chain_ok() && attention_fp16_enabled() && d.I_pad <= 64 && f.kv_all.W2 != nullptr && w.ldkv % 128 == 0 && w.ldkv == f.kv_all.N_pad;

@@ -17,7 +17,7 @@ struct TmpBuf {
 }  // namespace fc
 
 
-namespace fc { void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t); long gemm_fp16_fallbacks(); extern int g_train_wgrad16; extern int g_train_attn16; extern int g_gemm_dma; extern int g_spline_ablate; extern int g_limb_chain_all; extern int g_premlp_chain; extern int g_gemm_stamp; extern int g_gemm_small_tiles; extern int g_spline_prefetch; extern int g_mlp_rows; extern int g_knn_mfma; extern int g_premlp_lu; extern int g_spline_wide_colgroup; extern int g_linear_wide; extern int g_knn_warm; size_t gemm_read_stamps(unsigned long long*, size_t); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t); }
+namespace fc { void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t); long gemm_fp16_fallbacks(); extern int g_train_wgrad16; extern int g_train_attn16; extern int g_gemm_dma; extern int g_spline_ablate; extern int g_limb_chain_all; extern int g_premlp_chain; extern int g_gemm_stamp; extern int g_gemm_small_tiles; extern int g_spline_prefetch; extern int g_mlp_rows; extern int g_knn_mfma; extern int g_premlp_lu; extern int g_spline_wide_colgroup; extern int g_linear_wide; extern int g_knn_warm; extern int g_kv_fold; bool kv_fold_gate_dims(int, int, bool, bool); size_t gemm_read_stamps(unsigned long long*, size_t); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t); }
 namespace fc { extern int g_gemm_variant, g_gemm_colgroup, g_attn_fp16, g_fused_spline, g_premlp_fused, g_limb_chain, g_lnq_fold; }
 
 extern "C" {
@@ -46,6 +46,7 @@ int fc_debug_set(int32_t key, int32_t value) {
     else if (key == 24) fc::g_knn_mfma = value;          /* 1 = k-NN Gram tiles on the matrix cores (default), 0 = lane-per-candidate kernel */
     else if (key == 29) fc::g_linear_wide = value;       /* hidden layers of the coupling MLP on the 256 x 256 one-accumulator kernel: 0 = off (default: measured no faster than the chain), 1 = for scenes of >= 2048 target points, 2 = at any size */
     else if (key == 32) fc::g_knn_warm = value;         /* 1 = DGCNN levels 1-3 start their k-NN stream from the previous level's neighbour sets (default; exact either way), 0 = from -inf */
+    else if (key == 33) fc::g_kv_fold = value;          /* read by fc_flow_create: 1 = to_kv folded into the q projections and the consumers' in_layers, keys = values = the context panel (default, where embedding dim == inner dim), 0 = the stacked K|V projection */
     else if (key == 31) fc::g_train_wide = value;       /* 1 = training Linear layers with >= 1024 outputs (the spline parameter layer) on the 256 x 256 one-accumulator loop (default), 0 = on the fp32-A 128 x 128 loop, 3 = 1 with non-temporal stores of a GB-sized output (measured slower) */
     else if (key == 28) fc::g_spline_wide_colgroup = value;   /* column-group size of its tile order (-1 = shipped) */
     else if (key == 20) fc::g_gemm_stamp = value;        /* diagnostic: in-kernel phase stamps, 1 = fused spline launches, 2 = limb-chained Linear launches, 3 = row-resident pre-attention kernel, 4 = row-resident coupling MLP */
@@ -66,6 +67,10 @@ int fc_debug_one_acc_gemm_f32(const float* x, const float* W, const float* bias,
    pp) and the dim-major position inside a tile that the LDS-tile epilogues store a column at; no device call */
 int32_t fc_debug_spline_col(int32_t j, int32_t pp, int32_t K) { return fc::spline_col(j, pp, K); }
 int32_t fc_debug_spline_tile_pos(int32_t c, int32_t K) { return fc::spline_tile_pos(c, K); }
+
+/* host-side view of the K|V fold's gate (flow_engine.cpp kv_fold_gate_dims) for the CPU tests: 1 when a flow whose attentions have this
+   embedding width, inner width and these biases gets to_kv folded away at fc_flow_create (with knob 33 at its default); no device call */
+int32_t fc_debug_kv_fold_gate(int32_t E, int32_t inner, int32_t q_bias, int32_t kv_bias) { return fc::kv_fold_gate_dims(E, inner, q_bias != 0, kv_bias != 0) ? 1 : 0; }
 
 /* diagnostic (knob 20): copies the phase stamps of the last stamped fused-spline launch (16 x u64 per workgroup) to host memory; returns the count */
 int64_t fc_debug_gemm_stamps(uint64_t* host, int64_t max_n) {
@@ -211,6 +216,27 @@ int fc_op_attention_f32(const float* q, const float* k, const float* v, float* o
     fc::TmpBuf limbs(fc::attention_limb_ws_bytes((long)B * M, D)), flag(sizeof(int));
     fc::run_fp16_guarded((int*)flag.p, (hipStream_t)stream,
                          [&] { fc::launch_attention_op(q, k, v, out, B, N, M, D, scale, limbs.p, (hipStream_t)stream); });
+    FC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    FC_API_END
+}
+
+/* out[B,N,D] = softmax(q c^T * scale) c with ONE tensor c [B,M,D] as keys and values, on the kernels of the folded flow engine (to_kv folded
+   away, flow_engine.cpp): one limb image of c, then attn16_kernel<64, 1> (D = 64: one staged tile per 64 keys) or attn16_kernel<32> on that
+   image twice.  For the tests; a value beyond the image's range is an error here (the engine repeats such a pass on its fp32 path). */
+int fc_debug_attention_ctx_f32(const float* q, const float* c, float* out, int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream) {
+    FC_API_BEGIN
+    if (!q || !c || !out) throw fc::Error(FC_ERR_INVALID, "fc_debug_attention_ctx_f32: null pointer");
+    if (D != 32 && D != 64) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_debug_attention_ctx_f32: D must be 32 or 64");
+    if (((uintptr_t)q | (uintptr_t)c | (uintptr_t)out) & 15) throw fc::Error(FC_ERR_INVALID, "fc_debug_attention_ctx_f32: operands must be 16-byte aligned");
+    fc::TmpBuf limbs(fc::attention_limb_ws_bytes((long)B * M, D) / 2), flag(sizeof(int));
+    fc::run_fp16_guarded((int*)flag.p, (hipStream_t)stream, [&] {
+        if (fc::gemm_fp16_flag() && fc::attention_fp16_enabled()) {
+            fc::launch_context_limbs(c, D, (unsigned short*)limbs.p, (long)B * M, D, (hipStream_t)stream);
+            fc::launch_attention_ctx16(q, D, (const unsigned short*)limbs.p, out, D, B, N, N, M, M, D, (hipStream_t)stream, nullptr, scale * 1.4426950408889634f);
+        } else {                                        // as in the engine: the repeat after a raised range flag (and knob 5 = 0) takes c itself, in fp32
+            fc::launch_attention_op(q, c, c, out, B, N, M, D, scale, nullptr, (hipStream_t)stream);
+        }
+    });
     FC_HIP(hipStreamSynchronize((hipStream_t)stream));
     FC_API_END
 }

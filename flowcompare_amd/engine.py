@@ -565,6 +565,16 @@ def op_attention(q, k, v, scale):
     return out
 
 
+def op_attention_ctx(q, c, scale):
+    """softmax(q c^T * scale) c with one tensor as keys and values, on the folded flow engine's kernels (fc_debug_attention_ctx_f32)."""
+    q, c = _dev_f32(q), _dev_f32(c)
+    B, N, D = q.shape
+    out = torch.empty_like(q)
+    with torch.cuda.device(q.device):
+        _check(lib().fc_debug_attention_ctx_f32(_ptr(q), _ptr(c), _ptr(out), B, N, c.shape[1], D, ctypes.c_float(scale), _stream()))
+    return out
+
+
 def op_attention_weights(q, k, scale, points=None):
     """Rows `points` (None = all) of softmax(q k^T * scale): q [B,N,D], k [B,M,D] -> [B,P,M] (fc_op_attention_weights_f32)."""
     q, k = _dev_f32(q), _dev_f32(k)

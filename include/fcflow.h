@@ -106,11 +106,19 @@ const char* fc_last_error(void);     /* thread-local, valid until the next faili
 /* ---- flow: Flow.log_prob / Flow.sample ------------------------------------------------------- */
 
 /* Builds the device-resident, kernel-packed flow from the checkpoint tensors `flow.state_dict()`
- * (replaces the module graph initialize_flow assembles, model_initialization.py:136-160). */
+ * (replaces the module graph initialize_flow assembles, model_initialization.py:136-160).
+ * Weights are folded here, in double precision.  Where input_embedding_dim equals the attention's inner
+ * dimension (cross_heads * cross_dim_head; every shipped configuration: 64; widths 65..96, which the kernels pad differently
+ * for the two, excepted) and to_q / to_kv carry no bias, that includes
+ * to_kv itself: Wk goes into the q projection, Wv into lin and the consumer's in_layer, and every attention of a forward attends
+ * over the context embedding directly -- no K|V projection runs and fc_flow_workspace_bytes plans no K|V buffer (3.9 GB at
+ * 16 x 4096 context points and 116 attentions).  Any other flow keeps the stacked K|V projection; results agree within the fp32
+ * noise of the log-prob either way. */
 int fc_flow_create(const fc_flow_config* cfg, const fc_tensor* tensors, int32_t n_tensors, fc_flow** out);
 void fc_flow_destroy(fc_flow* flow);
 
-/* Bytes of device workspace fc_flow_logprob_f32 / fc_flow_inverse_f32 need for (B, N, M). */
+/* Bytes of device workspace fc_flow_logprob_f32 / fc_flow_inverse_f32 need for (B, N, M).  Depends on how the flow was
+ * packed (see fc_flow_create): ask the handle that will run. */
 int fc_flow_workspace_bytes(const fc_flow* flow, int32_t B, int32_t N, int32_t M, size_t* bytes);
 
 /* Number of noise tensors one forward consumes and the feature width of tensor i ([B,N,width]):

@@ -110,6 +110,7 @@ struct PackedLinear {
                                    // [round_up(N_pad, 256)][K_pad/16][2][16]: w 2^w1_exp = hi + lo with lo UNSCALED, rows in that kernel's column order
     float* bias1 = nullptr;        // its bias in the same order, times kOneAccActScale 2^w1_exp
     int w1_exp = 0;
+    bool w1_folded = false;        // ... and folded to 22 parameters per dim on 112-column wave tiles (spline_wide.hip, knob 34)
     bool w1_permuted = false;      // W1 rows in the fused spline kernel's register-slot order (else natural order: a Linear layer of the coupling MLP)
     float wmax = 0.f;              // max |w| of the packed matrix (pack_linear)
     int N_pad = 0;             // columns written (multiple of 32)
@@ -278,7 +279,7 @@ void launch_mlp_rows(const PackedLinear& in, const std::vector<PackedLinear>& mi
 void launch_limb_decode(const unsigned short* img, float* out, int ldo, int rows, int width, hipStream_t s);   // row-major limb image -> fp32 (tests)
 // spline_wide.hip: the fused spline parameter layer on 256 x 256 tiles with one accumulator per output (K = 8 bins, limb-chained input)
 bool spline_wide_eligible(const PackedLinear& L, int K_bins);
-void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool permute = true);
+void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool permute = true, bool fold = false);
 void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);
 bool linear_wide_eligible(const PackedLinear& L, const GemmEpi& e, int rows_alloc);   // a GELU Linear layer with one-accumulator images in and out
 void launch_linear_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);

@@ -98,6 +98,8 @@ struct fc_flow {
 
 namespace fc {
 
+int g_spline_fold = 1;       // knob 34, read when a flow is created: 1 = the wide spline kernel's image holds the 22 informative parameters per dim on
+                             // 112-column wave tiles (shipped), 0 = all 25 on 128-column tiles
 int g_kv_fold = 1;           // knob 33, read when a flow is created: 1 = fold to_kv away where the gate allows it (shipped), 0 = stacked K|V projection
 
 // The K|V fold keeps every weight shape only when the context embedding is as wide as the attention's inner dimension (every shipped
@@ -363,11 +365,22 @@ static void build_out_layer(fc_flow& f, const WeightTable& wt, const std::string
     net.out_layer = pack_linear(f.arena, mat_from(w), b, {}, nmap, map_prefix(hl, round_up(hl, 32)), {round_up(hl, 32)});
     if (f.cfg.flow_type == FC_FLOW_SPLINE && f.cfg.num_bins_spline == 8) {
         // the one-accumulator image of the 256 x 256 fused spline kernel (spline_wide.hip): rows in that kernel's register-slot order, pre-scaled by
-        // the power of two that puts max |w| into [2^14, 2^15)
+        // the power of two that puts max |w| into [2^14, 2^15).
+        // Folded (knob 34): softmax is shift-invariant and the reference never reads derivative logit 8 (models/spline_coupling.py:24-66: F.pad, then
+        // both end entries overwritten), so only 22 of a dim's 25 parameters carry information: width and height rows i < 7 become W_i - W_7 with
+        // b_i - b_7, rows 7 / 15 / 24 of every dim leave the image.  The subtraction is made in double from the checkpoint's values (the image
+        // kernel, from the fp32 pack that holds them exactly); the scale is taken HERE over the same folded rows.  W / W2 / W3 / bias keep all 25.
+        const bool fold = g_spline_fold != 0;
         float wmax = 0.f;
-        const int64_t nel = w.numel();
-        for (int64_t i = 0; i < nel; ++i) wmax = std::max(wmax, std::fabs(w.data[i]));
-        spline_wide_attach(f.arena, net.out_layer, wmax, nullptr);
+        const int hk = (int)w.shape[1];
+        for (int r = 0; r < n; ++r) {
+            const int pp = r % 25;
+            if (fold && (pp == 7 || pp == 15 || pp == 24)) continue;
+            const float* wr = w.data + (size_t)r * hk;
+            const float* ws = fold && pp < 16 ? w.data + (size_t)(r - pp + (pp < 8 ? 7 : 15)) * hk : nullptr;
+            for (int k = 0; k < hk; ++k) wmax = std::max(wmax, std::fabs(ws ? (float)((double)wr[k] - (double)ws[k]) : wr[k]));
+        }
+        spline_wide_attach(f.arena, net.out_layer, wmax, nullptr, true, fold);
     }
 }
 

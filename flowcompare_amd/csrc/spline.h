@@ -216,6 +216,76 @@ __device__ __forceinline__ void rq_spline_fwd_regs(float x, const U& u, float& y
     lad = inside ? ll : 0.f;
 }
 
+// rq_spline_fwd_regs on parameters that arrive SCALED: logical parameter i = u(i) * os with os an exact power of two.  The
+// scale rides inside the softmax's existing fma (fma(u, L2E os, -max u L2E os) is bit for bit fma(u os, L2E, -max(u os) L2E)), the two
+// derivative logits are scaled after their selection: same operations and roundings as the unscaled routine on u os.
+template <int K, class U>
+__device__ __forceinline__ void rq_spline_fwd_regs_scaled(float x, const U& u, float os, float& y, float& lad) {
+    constexpr float B = 3.0f, MINW = 1e-3f, MINH = 1e-3f, MIND = 1e-3f, L2E = 1.4426950408889634f;
+    const bool inside = x >= -B && x <= B;
+    const float l2s = L2E * os;
+    float ew[K], eh[K], mw = u(0), mh = u(K);
+#pragma unroll
+    for (int i = 0; i < K; ++i) { ew[i] = u(i); eh[i] = u(K + i); mw = fmaxf(mw, ew[i]); mh = fmaxf(mh, eh[i]); }
+    float sw = 0.f, sh = 0.f;
+    const float ow = -mw * l2s, oh = -mh * l2s;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        ew[i] = __builtin_amdgcn_exp2f(fmaf(ew[i], l2s, ow)); sw += ew[i];
+        eh[i] = __builtin_amdgcn_exp2f(fmaf(eh[i], l2s, oh)); sh += eh[i];
+    }
+    const float fw = (1.0f - MINW * K) * __builtin_amdgcn_rcpf(sw), fh = (1.0f - MINH * K) * __builtin_amdgcn_rcpf(sh);
+    float c = 0.f, in_cw = -B, hi = INFINITY;
+    float ud0r = 0.f, ud1r = u(2 * K);
+    int bin = 0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        c += fmaf(fw, ew[i], MINW);
+        const float knot = i == K - 1 ? B : fmaf(2.0f * B, c, -B);
+        const bool ge = x >= (i == K - 1 ? knot + 1e-6f : knot);
+        bin += ge ? 1 : 0;
+        in_cw = ge ? knot : in_cw;
+        hi = ge ? hi : fminf(hi, knot);
+        ud0r = ge ? u(2 * K + i) : ud0r;
+        ud1r = ge ? u(2 * K + i + 1) : ud1r;
+    }
+    const float in_w = hi - in_cw;
+    float ch = 0.f, in_ch = -B, ch_hi = B;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        ch += fmaf(fh, eh[i], MINH);
+        const float knot = i == K - 1 ? B : fmaf(2.0f * B, ch, -B);
+        in_ch = (i + 1 == bin) ? knot : in_ch;
+        ch_hi = (i == bin) ? knot : ch_hi;
+    }
+    const float in_h = ch_hi - in_ch;
+    const float ud0 = bin == 0 ? -1e-3f : ud0r * os, ud1 = ud1r * os;      // bin 0: left pad log(exp(1 - min_derivative - 1))
+    const float d0 = MIND + (ud0 > 20.f ? ud0 : fast_log(1.0f + fast_exp(ud0)));
+    const float d1 = MIND + (ud1 > 20.f ? ud1 : fast_log(1.0f + fast_exp(ud1)));
+    const float rw = __builtin_amdgcn_rcpf(in_w);
+    const float delta = in_h * rw;
+    const float th = (x - in_cw) * rw;
+    const float tt = th * (1.0f - th);
+    const float num = in_h * (delta * th * th + d0 * tt);
+    const float den = delta + (d0 + d1 - 2.0f * delta) * tt;
+    const float yy = in_ch + fast_div(num, den);
+    const float omt = 1.0f - th;
+    const float dnum = delta * delta * (d1 * th * th + 2.0f * delta * tt + d0 * omt * omt);
+    const float ll = fast_log(dnum) - 2.0f * fast_log(den);
+    y = inside ? yy : x;
+    lad = inside ? ll : 0.f;
+}
+
+// The K = 8 spline on its 22 INFORMATIVE parameters [7 width logits | 7 height logits | derivative logits 0..7], scaled as above (the folded
+// image of spline_wide.hip).  softmax is shift-invariant, so the parameter layer was folded at pack time to emit w_i - w_7 and h_i - h_7:
+// logit 7 of either softmax is the literal 0 and still takes part in the maximum, the exponentials and the sum (today's operation sequence on
+// a constant input).  Derivative logit 8 is read by the reference for no bin; the bin search above selects it only where x >= 3 + 1e-6, whose
+// result is discarded, so a literal stands in for it as well.
+template <class U>
+__device__ __forceinline__ void rq_spline_fwd_regs_folded(float x, const U& u, float os, float& y, float& lad) {
+    rq_spline_fwd_regs_scaled<8>(x, [&](int i) { return i < 7 ? u(i) : i == 7 || i == 15 || i == 24 ? 0.f : i < 15 ? u(i - 1) : u(i - 2); }, os, y, lad);
+}
+
 template <int K>
 __device__ __forceinline__ void rq_dispatch(float x, const float* u, int us, bool inv, float& y, float& lad) {
     rq_spline_elem<K>(x, u, us, inv, y, lad);

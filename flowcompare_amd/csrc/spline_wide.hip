@@ -27,6 +27,10 @@
 // whole-wave evaluations (every lane busy: 16 points x 4 dims) and a fifth in which row kq takes dim 4 of point block kq after a 4 x 4
 // transpose of those seven registers across the rows (v_permlane16_swap + v_permlane32_swap, one swap per register).  64 points x 5 dims =
 // 5 full wave evaluations (VAR 11: 6 for the same points, one half empty).
+// Shipped form of the spline layer (knob 34 = 1, read at fc_flow_create): the image is FOLDED to the 22 parameters per dim that carry
+// information (softmax's shift invariance removes width / height logit 7, derivative logit 8 is read for no bin: spline_wide_src_col_folded,
+// spline.h rq_spline_fwd_regs_folded), 22 + a 6 + 6 + 6 + 4 share of dim 4 = 28 slots per lane row = SEVEN 16-parameter blocks: a 64 x 112 wave
+// tile, a 256 x 224 workgroup tile, 84 instead of 96 MFMAs per wave and k step in a kernel bound by the MFMAs it issues.
 #include "common.h"
 #include "activations.h"
 #include "spline.h"
@@ -79,24 +83,52 @@ __host__ __device__ inline int spline_wide_src_col(int c) {
     return i < cnt ? spline_col(4, base + i, 8) : -1;
 }
 
+// The FOLDED tile order (knob 34, shipped): 22 informative parameters per dim, [7 width | 7 height | 8 derivative] (spline.h
+// rq_spline_fwd_regs_folded), on a wave tile of 7 blocks of 16 = 112 columns.  Column c as above; slot s = 4 jb + r < 28 of row kq:
+//   s < 22: folded parameter s of the tile's dim kq;  s >= 22: folded parameter 6 kq + s - 22 of dim 4 (rows 0..2 carry 6, row 3 carries 4:
+//   its last two slots are spare)
+// returns the column of the same tile in spline.h's order that holds the parameter, or -1 for a spare slot; *sub receives the column that is
+// SUBTRACTED from it (width / height logit 7 of the same dim), or -1 for a derivative logit
+__host__ __device__ inline int spline_wide_src_col_folded(int c, int* sub) {
+    const int jb = c >> 4, kq = (c >> 2) & 3, r = c & 3, s = 4 * jb + r;
+    const int dim = s < 22 ? kq : 4, q = s < 22 ? s : 6 * kq + s - 22;
+    *sub = -1;
+    if (q >= 22) return -1;
+    if (q < 14) *sub = spline_col(dim, q < 7 ? 7 : 15, 8);
+    return spline_col(dim, q < 7 ? q : q < 14 ? q + 1 : q + 2, 8);
+}
+
 // ---------------------------------------------------------------- weight image + bias in the kernel's order (fc_flow_create)
 __global__ __launch_bounds__(256) void spline_wide_image_kernel(const float* __restrict__ W, const float* __restrict__ bias, int n_src, int K_pad, float wscale,
                                                                 float bscale, unsigned short* __restrict__ W1, float* __restrict__ bias1, size_t n, int permute) {
+    // permute: 0 natural row order, 1 the 128-column tile order, 2 the folded 112-column order.  The fold W_i - W_7 is taken in double from the
+    // fp32 matrix, which holds the checkpoint's values exactly: the bits of a double-precision fold of the checkpoint tensors rounded to fp32.
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
     const size_t row = t / K_pad;
     const int k = (int)(t - row * K_pad);
-    const int tile = (int)(row >> 7), c = (int)(row & 127);
-    const int sc = permute ? spline_wide_src_col(c) : c;
-    const int srow = tile * 128 + sc;
+    const int tw = permute == 2 ? 112 : 128;
+    const int tile = (int)(row / tw), c = (int)(row - (size_t)tile * tw);
+    int sub = -1;
+    const int sc = permute == 2 ? spline_wide_src_col_folded(c, &sub) : permute ? spline_wide_src_col(c) : c;
+    const int srow = tile * 128 + sc, subrow = tile * 128 + sub;
     const bool live = sc >= 0 && srow < n_src;
-    const float x = live ? W[(size_t)srow * K_pad + k] * wscale : 0.f;
+    float x = 0.f, bv = 0.f;
+    if (live) {
+        x = W[(size_t)srow * K_pad + k];
+        bv = bias ? bias[srow] : 0.f;
+        if (sub >= 0) {
+            x = (float)((double)x - (double)W[(size_t)subrow * K_pad + k]);
+            bv = bias ? (float)((double)bv - (double)bias[subrow]) : 0.f;
+        }
+        x *= wscale;
+    }
     const _Float16 h = (_Float16)x;
     const _Float16 l = (_Float16)(x - (float)h);
     const size_t blk = row * (K_pad / 16) + k / 16;
     W1[blk * 32 + (k & 15)] = __builtin_bit_cast(unsigned short, h);
     W1[blk * 32 + 16 + (k & 15)] = __builtin_bit_cast(unsigned short, l);
-    if (k == 0 && bias1) bias1[row] = live && bias ? bias[srow] * bscale : 0.f;
+    if (k == 0 && bias1) bias1[row] = bv * bscale;
 }
 
 int g_spline_wide_colgroup = -1;   // knob 28: column-group size of the tile order in 256-column tiles (-1 = shipped: 5)
@@ -111,66 +143,6 @@ __device__ __forceinline__ float sw_row_sum(float v) {
     float c = a + b, d = c;
     sw_swap32(c, d);
     return c + d;
-}
-
-// rq_spline_fwd_regs (spline.h) on parameters that arrive SCALED: logical parameter i = u(i) * os with os an exact power of two.  The
-// scale rides inside the softmax's existing fma (fma(u, L2E os, -max u L2E os) is bit for bit fma(u os, L2E, -max(u os) L2E)), the two
-// derivative logits are scaled after their selection: same operations and roundings as the unscaled routine on u os.
-template <int K, class U>
-__device__ __forceinline__ void rq_spline_fwd_regs_scaled(float x, const U& u, float os, float& y, float& lad) {
-    constexpr float B = 3.0f, MINW = 1e-3f, MINH = 1e-3f, MIND = 1e-3f, L2E = 1.4426950408889634f;
-    const bool inside = x >= -B && x <= B;
-    const float l2s = L2E * os;
-    float ew[K], eh[K], mw = u(0), mh = u(K);
-#pragma unroll
-    for (int i = 0; i < K; ++i) { ew[i] = u(i); eh[i] = u(K + i); mw = fmaxf(mw, ew[i]); mh = fmaxf(mh, eh[i]); }
-    float sw = 0.f, sh = 0.f;
-    const float ow = -mw * l2s, oh = -mh * l2s;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        ew[i] = __builtin_amdgcn_exp2f(fmaf(ew[i], l2s, ow)); sw += ew[i];
-        eh[i] = __builtin_amdgcn_exp2f(fmaf(eh[i], l2s, oh)); sh += eh[i];
-    }
-    const float fw = (1.0f - MINW * K) * __builtin_amdgcn_rcpf(sw), fh = (1.0f - MINH * K) * __builtin_amdgcn_rcpf(sh);
-    float c = 0.f, in_cw = -B, hi = INFINITY;
-    float ud0r = 0.f, ud1r = u(2 * K);
-    int bin = 0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        c += fmaf(fw, ew[i], MINW);
-        const float knot = i == K - 1 ? B : fmaf(2.0f * B, c, -B);
-        const bool ge = x >= (i == K - 1 ? knot + 1e-6f : knot);
-        bin += ge ? 1 : 0;
-        in_cw = ge ? knot : in_cw;
-        hi = ge ? hi : fminf(hi, knot);
-        ud0r = ge ? u(2 * K + i) : ud0r;
-        ud1r = ge ? u(2 * K + i + 1) : ud1r;
-    }
-    const float in_w = hi - in_cw;
-    float ch = 0.f, in_ch = -B, ch_hi = B;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        ch += fmaf(fh, eh[i], MINH);
-        const float knot = i == K - 1 ? B : fmaf(2.0f * B, ch, -B);
-        in_ch = (i + 1 == bin) ? knot : in_ch;
-        ch_hi = (i == bin) ? knot : ch_hi;
-    }
-    const float in_h = ch_hi - in_ch;
-    const float ud0 = bin == 0 ? -1e-3f : ud0r * os, ud1 = ud1r * os;      // bin 0: left pad log(exp(1 - min_derivative - 1))
-    const float d0 = MIND + (ud0 > 20.f ? ud0 : fast_log(1.0f + fast_exp(ud0)));
-    const float d1 = MIND + (ud1 > 20.f ? ud1 : fast_log(1.0f + fast_exp(ud1)));
-    const float rw = __builtin_amdgcn_rcpf(in_w);
-    const float delta = in_h * rw;
-    const float th = (x - in_cw) * rw;
-    const float tt = th * (1.0f - th);
-    const float num = in_h * (delta * th * th + d0 * tt);
-    const float den = delta + (d0 + d1 - 2.0f * delta) * tt;
-    const float yy = in_ch + fast_div(num, den);
-    const float omt = 1.0f - th;
-    const float dnum = delta * delta * (d1 * th * th + 2.0f * delta * tt + d0 * omt * omt);
-    const float ll = fast_log(dnum) - 2.0f * fast_log(den);
-    y = inside ? yy : x;
-    lad = inside ? ll : 0.f;
 }
 
 // eight fp32 values (k = 8 kq .. 8 kq + 7 of one point) -> the hi / lo operand fragments of the one-accumulator form, x s = hi + lo with s an
@@ -210,7 +182,10 @@ constexpr int SW_LDS = 4 * 32768 + 2 * 1024;      // two stages of (256 point ro
 template <int EPI, int P0, int P1, int P2, int P3, int Q0, int Q1, int Q2, int Q3>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
 void spline_wide_kernel(const SplineWideParams p) {
-    static_assert(P0 + P1 + P2 + P3 == 8 && Q0 + Q1 + Q2 == 8 && Q3 == 0, "eight pieces per wave and k step");
+    // NB: 16-parameter blocks of a wave tile = weight DMA pieces per fetching wave and k step.  8: the 64 x 128 wave tile (every EPI);
+    // 7: the folded spline image, a 64 x 112 wave tile (EPI 0 only): 84 instead of 96 MFMAs per wave and k step, 224 weight rows per stage
+    constexpr int NB = Q0 + Q1 + Q2;
+    static_assert(P0 + P1 + P2 + P3 == 8 && (NB == 8 || (NB == 7 && EPI == 0)) && Q3 == 0, "eight point pieces and NB weight pieces per wave and k step");
     extern __shared__ char smc[];
     typedef __attribute__((address_space(3))) char lds_char;
     typedef const __attribute__((address_space(1))) char glb_char;
@@ -244,28 +219,28 @@ void spline_wide_kernel(const SplineWideParams p) {
     };
     // LDS: [stage 0 points 32 KB | stage 1 points | stage 0 weights | stage 1 weights]; a row = 128 B = one k32 step of one point / weight row
     // = 8 chunks of 16 B, logical chunk c = 4 (k16 block) + 2 limb + (k half) at physical chunk c ^ ((row >> 1) & 7).
-    // DMA piece i of this wave: operand rows (wave & 3) * 64 + 8 i + (lane >> 3); the swizzle term depends on the parity of i only.
+    // DMA piece i of this wave: point rows (wave & 3) * 64 + 8 i + (lane >> 3), weight rows (wave & 3) * 8 NB + 8 i + (lane >> 3).
     unsigned poff[2];
 #pragma unroll
     for (int par = 0; par < 2; ++par) {
-        const int r = pw * 64 + par * 8 + (lane >> 3);
+        const int r = pw * (grp == 0 ? 64 : 8 * NB) + par * 8 + (lane >> 3);      // (8 NB is a multiple of 8: the swizzle term still depends on the parity of i only)
         const int cl = (lane & 7) ^ ((r >> 1) & 7);
         poff[par] = (unsigned)r * rowbytes + cl * 16;
     }
     auto src_of = [&](int bm, int bn) -> const char* {
         return grp == 0 ? (AF32 ? reinterpret_cast<const char*>(p.A32) : reinterpret_cast<const char*>(p.A16)) + (size_t)bm * 256 * rowbytes
-                        : reinterpret_cast<const char*>(p.W1) + (size_t)bn * 256 * rowbytes;
+                        : reinterpret_cast<const char*>(p.W1) + (size_t)bn * (32 * NB) * rowbytes;
     };
-    const int dst0 = grp * 65536 + pw * 8192;
+    const int dst0 = grp == 0 ? pw * 8192 : 65536 + pw * (1024 * NB);
 #define SW_DMA(SRC_, ST_, I0_, N_)                                                                                                      \
     {                                                                                                                                     \
         _Pragma("unroll") for (int i_ = (I0_); i_ < (I0_) + (N_); ++i_)                                                                 \
             __builtin_amdgcn_global_load_lds((glb_char*)((SRC_) + (size_t)(i_ >> 1) * 16 * rowbytes + poff[i_ & 1]),                      \
                                              (lds_char*)(smc + dst0 + (ST_) * 32768 + i_ * 1024), 16, 0, 0);                            \
     }
-    auto bias_dma = [&](int bn, int par) {                              // 256 floats: waves 0-3, 4 bytes per lane
+    auto bias_dma = [&](int bn, int par) {                              // 256 floats: waves 0-3, 4 bytes per lane (NB = 7: 224 in use; bias1 is padded by 32)
         if (grp == 0 && (EPI != 3 || p.bias1))
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) float*)(p.bias1 + bn * 256 + pw * 64 + lane),
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) float*)(p.bias1 + bn * (32 * NB) + pw * 64 + lane),
                                              (__attribute__((address_space(3))) float*)(biasbuf + par * 256 + pw * 64), 4, 0, 0);
     };
     // a k32 step is ONE k extent of the 16x16x32 MFMA: lane (l15, kq) supplies row l15 of a 16-row block, k quarter kq = chunks 0, 1, 4, 5 of
@@ -276,7 +251,7 @@ void spline_wide_kernel(const SplineWideParams p) {
     for (int q = 0; q < 2; ++q) {
         const int c = (((kq >> 1) * 4 + q * 2 + (kq & 1)) ^ xsw) * 16;
         abase[q] = (pw * 64 + l15) * 128 + c;
-        bbase[q] = 65536 + (grp * 128 + l15) * 128 + c;
+        bbase[q] = 65536 + (grp * 16 * NB + l15) * 128 + c;
     }
     // EPI 3: the point rows arrive as fp32 (a k32 step of a row = 32 floats = the same 128 bytes) and are turned into the limb image IN PLACE, one
     // k step ahead of their use: lane (l15, kq) reads the eight floats k = 8 kq .. 8 kq + 7 (chunks 2 kq, 2 kq + 1) and writes their hi / lo
@@ -332,7 +307,9 @@ void spline_wide_kernel(const SplineWideParams p) {
     int bm, bn;
     tile_of(t, bm, bn);
     const char* src = src_of(bm, bn);
-    SW_DMA(src, 0, 0, 8)
+    if constexpr (NB == 8) SW_DMA(src, 0, 0, 8)
+    else if (grp == 0) SW_DMA(src, 0, 0, 8)
+    else SW_DMA(src, 0, 0, NB)
     bias_dma(bn, 0);
     float spl_x[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, spl_ldj = 0.f;
     if constexpr (EPI == 0) load_x(bm, bn, spl_x, spl_ldj);
@@ -347,7 +324,7 @@ void spline_wide_kernel(const SplineWideParams p) {
     }
     if (grp == 1) __builtin_amdgcn_s_barrier();                         // the second group runs one segment behind the first
 
-    floatx4 acc[4][8];
+    floatx4 acc[4][NB];
     int par = 0;
     for (;;) {
         const int tn = t + G;
@@ -358,10 +335,10 @@ void spline_wide_kernel(const SplineWideParams p) {
         float nx[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, nldj = 0.f;
         {
             // accumulators start from the (pre-scaled) bias: register r of block jb is tile column 16 jb + 4 kq + r for every point block
-            const float* bb = biasbuf + par * 256 + grp * 128 + 4 * kq;
+            const float* bb = biasbuf + par * 256 + grp * 16 * NB + 4 * kq;
             const bool has_bias = EPI != 3 || p.bias1 != nullptr;
 #pragma unroll
-            for (int jb = 0; jb < 8; ++jb) {
+            for (int jb = 0; jb < NB; ++jb) {
                 const float4 b4 = has_bias ? *reinterpret_cast<const float4*>(bb + jb * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
                 for (int ib = 0; ib < 4; ++ib) { acc[ib][jb][0] = b4.x; acc[ib][jb][1] = b4.y; acc[ib][jb][2] = b4.z; acc[ib][jb][3] = b4.w; }
@@ -374,7 +351,7 @@ void spline_wide_kernel(const SplineWideParams p) {
                     _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                        \
                         xf[i][q] = *reinterpret_cast<const f16x8*>(smc + abase[q] + (ST_) * 32768 + i * 2048);                            \
             }                                                                                                                             \
-            _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                                                                             \
+            _Pragma("unroll") for (int jj = 0; jj < 2 && 2 * (F_) + jj < NB; ++jj)                                                       \
                 _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                            \
                     wf[jj][q] = *reinterpret_cast<const f16x8*>(smc + bbase[q] + (ST_) * 32768 + (2 * (F_) + jj) * 2048);                 \
             if (grp == 0) { if ((NP_) > 0) SW_DMA(dsrc, (ST_) ^ 1, I0P_, NP_) }                                                          \
@@ -392,7 +369,7 @@ void spline_wide_kernel(const SplineWideParams p) {
             __builtin_amdgcn_sched_barrier(0);                                                                                            \
             __builtin_amdgcn_s_setprio(1);                                                                                                \
             _Pragma("unroll") for (int pr = 0; pr < 3; ++pr)                                                                             \
-                _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                                                                         \
+                _Pragma("unroll") for (int jj = 0; jj < 2 && 2 * (F_) + jj < NB; ++jj)                                                   \
                     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                        \
                         acc[i][2 * (F_) + jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[jj][pr == 1 ? 1 : 0], xf[i][pr == 2 ? 1 : 0],  \
                                                                                        acc[i][2 * (F_) + jj], 0, 0, 0);                   \
@@ -549,9 +526,11 @@ void spline_wide_kernel(const SplineWideParams p) {
             const float os = p.out_scale;
             const int t128 = 2 * bn + grp, dim0 = t128 * 5;
             const int row0 = bm * 256 + pw * 64 + l15, rowq = row0 + 16 * kq;
-            // slots 25..31 (registers 1..3 of block 6, 0..3 of block 7): the parts of dim 4 -> row d gets the parts of point block d
+            // NB = 8: slots 25..31 (registers 1..3 of block 6, 0..3 of block 7), NB = 7: slots 22..27 (registers 2, 3 of block 5, 0..3 of block 6):
+            // the parts of dim 4 -> row d gets the parts of point block d
+            constexpr int S4 = NB == 8 ? 25 : 22;
 #pragma unroll
-            for (int s = 25; s < 32; ++s) {
+            for (int s = S4; s < 4 * NB; ++s) {
                 float x0 = acc[0][s >> 2][s & 3], x1 = acc[1][s >> 2][s & 3], x2 = acc[2][s >> 2][s & 3], x3 = acc[3][s >> 2][s & 3];
                 sw_swap16(x0, x1);
                 sw_swap16(x2, x3);
@@ -564,6 +543,15 @@ void spline_wide_kernel(const SplineWideParams p) {
 #pragma unroll
                 for (int ib = 0; ib < 4; ++ib) { yv[ib] = spl_x[ib] + acc[ib][0][0] * os; lv[ib] = acc[ib][0][1] * os; }
                 yv[4] = spl_x[4] + acc[0][6][1] * os; lv[4] = acc[1][6][1] * os;
+            } else if constexpr (NB == 7) {
+#pragma unroll
+                for (int ib = 0; ib < 4; ++ib)
+                    rq_spline_fwd_regs_folded(spl_x[ib], [&](int q) { return acc[ib][q >> 2][q & 3]; }, os, yv[ib], lv[ib]);
+                // dim 4: folded parameters 6 d .. 6 d + 5 from (transposed) block d, slots 22 + i
+                rq_spline_fwd_regs_folded(spl_x[4], [&](int q) {
+                    const int part = q / 6, s = 22 + q % 6;
+                    return acc[part][s >> 2][s & 3];
+                }, os, yv[4], lv[4]);
             } else {
 #pragma unroll
                 for (int ib = 0; ib < 4; ++ib)
@@ -590,7 +578,7 @@ void spline_wide_kernel(const SplineWideParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(acc[i][j]));
+                for (int j = 0; j < NB; ++j) asm volatile("" ::"v"(acc[i][j]));
         }
         if (grp == 1) {
             __builtin_amdgcn_sched_barrier(0);
@@ -617,8 +605,10 @@ bool spline_wide_eligible(const PackedLinear& L, int K_bins) {
 }
 
 // Attaches the kernel's weight image and bias to the packed spline parameter layer (K = 8 bins; W / bias hold spline.h's column order).
-// wmax = max |w| over the layer (host side, from the checkpoint tensor).
-void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool permute) {
+// wmax = max |w| over the rows the image holds (host side, from the checkpoint tensor; fold: over the FOLDED rows, up to twice the tensor's).
+// fold (with permute): the 22-parameter image on 112-column wave tiles (spline_wide_src_col_folded); W / W2 / W3 / bias stay as they are.
+void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool permute, bool fold) {
+    fold = fold && permute;
     if (!L.W || !L.bias || !L.W2 || L.nseg != 1 || L.K_pad % 64 != 0 || L.N_pad % (permute ? 128 : 256) != 0 || L.n_alloc < L.N_pad) return;
     if (!(wmax < 65504.0f)) return;
     int e = 0;
@@ -626,13 +616,14 @@ void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStre
         while (ldexpf(wmax, e) >= 32768.0f) --e;
         while (ldexpf(wmax, e) < 16384.0f && e < 100) ++e;
     }
-    const int rows = round_up(L.N_pad, 256);
+    const int rows = fold ? round_up(L.N_pad, 256) / 256 * 224 : round_up(L.N_pad, 256);      // workgroup tiles of 2 x 112 / 2 x 128 columns
     const size_t n = (size_t)rows * L.K_pad;
     L.W1 = (unsigned short*)arena.alloc_bytes(n * 2 * sizeof(unsigned short));
-    L.bias1 = arena.alloc_floats((size_t)rows);
+    L.bias1 = arena.alloc_floats((size_t)rows + (fold ? 32 : 0));      // (the kernel fetches 256 floats per workgroup tile)
     L.w1_exp = e;
     L.w1_permuted = permute;
-    spline_wide_image_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(L.W, L.bias, L.N_pad, L.K_pad, ldexpf(1.f, e), kOneAccActScale * ldexpf(1.f, e), L.W1, L.bias1, n, permute ? 1 : 0);
+    L.w1_folded = fold;
+    spline_wide_image_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(L.W, L.bias, L.N_pad, L.K_pad, ldexpf(1.f, e), kOneAccActScale * ldexpf(1.f, e), L.W1, L.bias1, n, fold ? 2 : permute ? 1 : 0);
     FC_HIP(hipGetLastError());
 }
 
@@ -655,9 +646,10 @@ void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
     p.ablate = g_spline_ablate;
     if (g_spline_wide_colgroup >= 0) p.col_group = (p.nbm % 8 == 0 && p.nbn > g_spline_wide_colgroup) ? g_spline_wide_colgroup : 0;
     static PerDeviceOnce slots_once;
-    auto kern = spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>;
-    static PerDeviceOnce attr_once;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });
+    // (the weight pieces of the folded form: 2 + 3 + 2 per k step)
+    auto kern = L.w1_folded ? spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 2, 0> : spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>;
+    static PerDeviceOnce attr_once[2];
+    attr_once[L.w1_folded ? 1 : 0].run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });
     const int slots = slots_once.run([](int dev) {
         int cus = 0;
         FC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -667,7 +659,8 @@ void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
     int grid = p.nbm * p.nbn;
     if (grid > slots) grid = slots;
     const double flops = 2.0 * (double)(e.rows_valid > 0 ? e.rows_valid : rows_alloc) * (double)(L.n_true ? L.n_true : L.N_pad) * (double)(L.k_true ? L.k_true : L.K_pad);
-    ProfScope ps("void fc::spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>(fc::SplineWideParams)", flops, 0.0, s);
+    ProfScope ps(L.w1_folded ? "void fc::spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 2, 0>(fc::SplineWideParams)"
+                             : "void fc::spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>(fc::SplineWideParams)", flops, 0.0, s);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SW_LDS, s, p);
     FC_HIP(hipGetLastError());
 }

@@ -672,10 +672,15 @@ class EdgeBNMaxFn(torch.autograd.Function):
             # torch.nn.BatchNorm train-mode side effect (parameter-sized vectors): running <- (1 - m) running + m batch, unbiased variance
             with torch.no_grad():
                 n = rows * k
-                m = bn.momentum if bn.momentum is not None else 0.1
-                bn.running_mean.mul_(1 - m).add_(stats[:C].to(bn.running_mean.dtype), alpha=m)
-                bn.running_var.mul_(1 - m).add_(stats[2 * C:].to(bn.running_var.dtype) * (n / max(n - 1, 1)), alpha=m)
                 bn.num_batches_tracked += 1
+                if bn.momentum is not None:
+                    m = bn.momentum
+                    bn.running_mean.mul_(1 - m).add_(stats[:C].to(bn.running_mean.dtype), alpha=m)
+                    bn.running_var.mul_(1 - m).add_(stats[2 * C:].to(bn.running_var.dtype) * (n / max(n - 1, 1)), alpha=m)
+                else:                                                 # momentum=None: cumulative average, factor 1 / num_batches_tracked
+                    m = 1.0 / bn.num_batches_tracked.to(bn.running_mean.dtype)
+                    bn.running_mean.mul_(1 - m).add_(stats[:C].to(bn.running_mean.dtype) * m)
+                    bn.running_var.mul_(1 - m).add_(stats[2 * C:].to(bn.running_var.dtype) * (n / max(n - 1, 1)) * m)
         order = offsets = None
         if has_q:
             # edges sorted by the row they point at (index plumbing): the backward then sums each row's incoming gradients in a fixed order

@@ -183,10 +183,15 @@ class BNActMaxFn(torch.autograd.Function):
         if bn.track_running_stats and bn.running_mean is not None:
             with torch.no_grad():
                 n = rows * k
-                mom = bn.momentum if bn.momentum is not None else 0.1
-                bn.running_mean.mul_(1 - mom).add_(stats[:c_real].to(bn.running_mean.dtype), alpha=mom)
-                bn.running_var.mul_(1 - mom).add_(stats[2 * C:2 * C + c_real].to(bn.running_var.dtype) * (n / max(n - 1, 1)), alpha=mom)
                 bn.num_batches_tracked += 1
+                if bn.momentum is not None:
+                    mom = bn.momentum
+                    bn.running_mean.mul_(1 - mom).add_(stats[:c_real].to(bn.running_mean.dtype), alpha=mom)
+                    bn.running_var.mul_(1 - mom).add_(stats[2 * C:2 * C + c_real].to(bn.running_var.dtype) * (n / max(n - 1, 1)), alpha=mom)
+                else:                                                 # momentum=None: cumulative average, factor 1 / num_batches_tracked
+                    mom = 1.0 / bn.num_batches_tracked.to(bn.running_mean.dtype)
+                    bn.running_mean.mul_(1 - mom).add_(stats[:c_real].to(bn.running_mean.dtype) * mom)
+                    bn.running_var.mul_(1 - mom).add_(stats[2 * C:2 * C + c_real].to(bn.running_var.dtype) * (n / max(n - 1, 1)) * mom)
         ctx.save_for_backward(P, g32, b32, stats, arg, idx)
         ctx.meta = (rows, C, k, slope, gamma.dtype)
         return out

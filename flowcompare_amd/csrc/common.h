@@ -348,6 +348,7 @@ void launch_expm_coupling(const float* params, int ldp, float* xbuf, int ldx, in
 constexpr int kExpmSmallMaxD2 = 16;       // d2 <= 16: the one-lane-per-point kernel of misc.hip (launch_expm_coupling)
 constexpr int kExpmWideMaxD2 = 256;
 constexpr int kExpmWideMaxSteps = 40;     // ||W - mu I||_1 <= 40 theta_55 = 534
+constexpr int kExpmWideBwdMaxD2 = 160;    // training backward (expm_wide.hip): the 256-lane layouts only; 161 .. 256 is refused
 void launch_expm_wide(const float* params, int ldp, const float* x2, int ldx, const float* scal4, float* y2, int ldy, int ypad, float* ldj,
                       int ldj_mode, int rows, int d2, int inverse, int* status, float* info, hipStream_t s);
 void launch_spline_flat(const float* x, const float* params, float* y, float* lad, int64_t n, int K, int inverse, hipStream_t s);

@@ -36,7 +36,7 @@ EXPORTS = [
     "fc_train_rqspline_fwd_f32", "fc_train_rqspline_bwd_f32", "fc_train_layernorm_fwd_f32", "fc_train_layernorm_bwd_f32",
     "fc_train_colsum_ws_bytes", "fc_train_colsum_f32",
     "fc_train_affine_fwd_f32", "fc_train_affine_bwd_f32", "fc_train_gauss_fwd_f32", "fc_train_gauss_bwd_f32", "fc_train_base_fwd_f32", "fc_train_base_bwd_f32",
-    "fc_train_normlp_fwd_f32", "fc_train_normlp_bwd_f32", "fc_train_expm_fwd_f32", "fc_train_expm_bwd_f32",
+    "fc_train_normlp_fwd_f32", "fc_train_normlp_bwd_f32", "fc_train_expm_fwd_f32", "fc_train_expm_bwd_f32", "fc_train_expm_wide_bwd_f32",
     "fc_train_edge_ws_bytes", "fc_train_edge_stats_f32", "fc_train_edge_fwd_f32", "fc_train_edge_bwd_prep_f32", "fc_train_edge_bwd_scatter_f32", "fc_train_edge_bwd_gather_f32", "fc_train_pool_fwd_f32", "fc_train_pool_bwd_f32",
     "fc_op_paconv_knn_f32", "fc_train_paconv_group_f32", "fc_train_softmax_fwd_f32", "fc_train_softmax_bwd_f32", "fc_train_assign_fwd_f32", "fc_train_assign_bwd_f32",
     "fc_train_centerdiff_fwd_f32", "fc_train_centerdiff_bwd_f32", "fc_train_rows_gather_bwd_f32", "fc_train_three_nn_f32", "fc_train_interp_fwd_f32",
@@ -82,6 +82,9 @@ def lib():
         L.fc_train_colsum_ws_bytes.restype = ctypes.c_size_t
         L.fc_train_edge_ws_bytes.restype = ctypes.c_size_t
         L.fc_train_sqnorm_ws_bytes.restype = ctypes.c_size_t
+        _P, _I = ctypes.c_void_p, ctypes.c_int32
+        L.fc_train_expm_wide_bwd_f32.restype = ctypes.c_int
+        L.fc_train_expm_wide_bwd_f32.argtypes = [_P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P]
         if L.fc_abi_version() != ABI_VERSION:
             raise RuntimeError("libfcflow.so ABI version mismatch: rebuild with `python -m flowcompare_amd.build --force`")
         _lib = L

@@ -214,7 +214,7 @@ def flow_log_prob(flow, x, context, extra_context=None, eps=None, act=None, chec
         if isinstance(cp, M.RationalQuadraticSplineCoupling):
             x2, ldj = T.rq_spline(x2, p, rows, d2, cp.num_bins)
         elif isinstance(cp, M.ExponentialCoupling):
-            x2, ldj = T.expm_coupling(x2, p, cp, rows, d2)
+            x2, ldj = T.expm_coupling(x2, p, cp, rows, d2, wide_backward=bool(cfg.get("expm_wide_backward")))
         else:
             x2, ldj = T.affine(x2, p, rows, d2, cp.scale_fn_type)
         return x2, logp + ldj

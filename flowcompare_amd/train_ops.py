@@ -732,15 +732,18 @@ def edge_bn_max(pq, bn, idx, rows, C, k):
 
 
 EXPM_TRAIN_BWD_MAX_D2 = 16       # fc_train_expm_bwd_f32 (one lane per point); the forward runs up to d2 = 256
+EXPM_TRAIN_WIDE_BWD_MAX_D2 = 160 # fc_train_expm_wide_bwd_f32 (one workgroup per point, csrc/expm_wide.hip), opt-in: config['expm_wide_backward']
+_EXPM_BOUND_MSG = "a coupling matrix norm ||W - mu I||_1 exceeds the matrix-exponential kernel's bound (40 Taylor steps, 534)"
 
 
 class ExpmCouplingFn(torch.autograd.Function):
     """ExponentialCoupling element (models/exponential_coupling.py:44-58): x2 panel, o panel [d2*d2 raw matrix | d2 shift], scal4 =
     cat(scale, shift, rescale, reshift) -> (y2 panel, ldj).  Forward d2 <= 256 (d2 > 16 on the inference engine's matrix-exponential action
-    kernel, csrc/expm_wide.hip), backward d2 <= 16 (the layer emits d2^2 numbers per point)."""
+    kernel, csrc/expm_wide.hip), backward d2 <= 16 (the layer emits d2^2 numbers per point), or 17 <= d2 <= 160 with `wide_backward`
+    (expm_wide_bwd_kernel in the same file; the o panel and its gradient are whole, 90.6 KB per point each at d2 = 150)."""
 
     @staticmethod
-    def forward(ctx, x2, o, scal4, rows, d2):
+    def forward(ctx, x2, o, scal4, rows, d2, wide_backward=False):
         L = engine.lib()
         _check_panel(x2, d2)
         _check_panel(o, d2 * d2 + d2)
@@ -753,18 +756,21 @@ class ExpmCouplingFn(torch.autograd.Function):
                                                   engine._ptr(ldj), rows, d2, engine._ptr(status), engine._stream()))
         if int(status.item()):
             if d2 > EXPM_TRAIN_BWD_MAX_D2:
-                raise RuntimeError("ExponentialCoupling (training forward): a coupling matrix norm ||W - mu I||_1 exceeds the matrix-exponential "
-                                   "kernel's bound (40 Taylor steps, 534)")
+                raise RuntimeError("ExponentialCoupling (training forward): " + _EXPM_BOUND_MSG)
             raise RuntimeError("ExponentialCoupling (training): a matrix norm exceeds 2^5; the backward keeps at most 64 squaring states")
         ctx.save_for_backward(x2, o, s4)
-        ctx.meta = (rows, d2, scal4.dtype)
+        ctx.meta = (rows, d2, scal4.dtype, bool(wide_backward))
         return y2, ldj
 
     @staticmethod
     def backward(ctx, dy2, dldj):
-        rows, d2, sdtype = ctx.meta
-        if d2 > EXPM_TRAIN_BWD_MAX_D2:
-            raise RuntimeError(f"ExponentialCoupling training backward supports d2 <= {EXPM_TRAIN_BWD_MAX_D2} (this flow has d2 = {d2})")
+        rows, d2, sdtype, wide = ctx.meta
+        if d2 > EXPM_TRAIN_BWD_MAX_D2 and not wide:
+            raise RuntimeError(f"ExponentialCoupling training backward supports d2 <= {EXPM_TRAIN_BWD_MAX_D2} (this flow has d2 = {d2}); "
+                               f"config['expm_wide_backward'] = True enables {EXPM_TRAIN_BWD_MAX_D2 + 1} <= d2 <= {EXPM_TRAIN_WIDE_BWD_MAX_D2}")
+        if d2 > EXPM_TRAIN_WIDE_BWD_MAX_D2:
+            raise RuntimeError(f"ExponentialCoupling training backward (expm_wide_backward) supports d2 <= {EXPM_TRAIN_WIDE_BWD_MAX_D2} "
+                               f"(this flow has d2 = {d2})")
         L = engine.lib()
         x2, o, s4 = ctx.saved_tensors
         dy2, dldj = dy2.contiguous(), dldj.contiguous()
@@ -772,16 +778,24 @@ class ExpmCouplingFn(torch.autograd.Function):
         do = _panel_out(o.shape[0], o.shape[1], rows, x2.device) if o.shape[1] == _round_up(d2 * d2 + d2, 32) else torch.zeros_like(o)
         dscal = torch.zeros(x2.shape[0], 4, dtype=torch.float32, device=x2.device)
         with _OnDevice(x2.device):
-            engine._check(L.fc_train_expm_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(dy2), dy2.shape[1],
-                                                  engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(do), do.shape[1], engine._ptr(dscal), rows,
-                                                  d2, engine._stream()))
+            if d2 > EXPM_TRAIN_BWD_MAX_D2:
+                status = torch.zeros(1, dtype=torch.int32, device=x2.device)
+                engine._check(L.fc_train_expm_wide_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(dy2),
+                                                           dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(do), do.shape[1],
+                                                           engine._ptr(dscal), rows, d2, engine._ptr(status), engine._stream()))
+                if int(status.item()):
+                    raise RuntimeError("ExponentialCoupling (training backward): " + _EXPM_BOUND_MSG)
+            else:
+                engine._check(L.fc_train_expm_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(dy2),
+                                                      dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(do), do.shape[1],
+                                                      engine._ptr(dscal), rows, d2, engine._stream()))
             ds4 = _colsum(dscal, 4, rows).to(sdtype)
-        return dx2, do, ds4, None, None
+        return dx2, do, ds4, None, None, None
 
 
-def expm_coupling(x2, o, cp, rows, d2):
+def expm_coupling(x2, o, cp, rows, d2, wide_backward=False):
     scal4 = torch.cat((cp.scale.reshape(1), cp.shift.reshape(1), cp.rescale.reshape(1), cp.reshift.reshape(1)))
-    return ExpmCouplingFn.apply(x2, o, scal4, rows, d2)
+    return ExpmCouplingFn.apply(x2, o, scal4, rows, d2, wide_backward)
 
 
 class PoolMaxMeanFn(torch.autograd.Function):

@@ -61,7 +61,10 @@ typedef struct fc_tensor {
  * 17 <= d2 <= 256: one workgroup per point holds the matrix in registers and applies its exponential to the vector (csrc/expm_wide.hip),
  * on row chunks of the parameter panel.  A point whose ||W - mu I||_1 exceeds 534 (40 Taylor steps) makes the call fail with
  * FC_ERR_UNSUPPORTED instead of returning a truncated series.  Training: forward (fc_train_expm_fwd_f32) up to d2 = 256, backward
- * (fc_train_expm_bwd_f32) d2 <= 16. */
+ * d2 <= 16 (fc_train_expm_bwd_f32) and 17 <= d2 <= 160 (fc_train_expm_wide_bwd_f32, csrc/expm_wide.hip; Python: config key
+ * 'expm_wide_backward').  A training backward for 161 <= d2 <= 256 is not built: the 1024-lane layout would hold the matrix and its
+ * gradient in 128 registers per lane at 4 waves per SIMD.  The training path materialises the whole parameter panel and its gradient:
+ * 90.6 KB per point and layer each at d2 = 150. */
 enum fc_flow_type { FC_FLOW_AFFINE = 0, FC_FLOW_SPLINE = 1, FC_FLOW_EXPONENTIAL = 2 };
 enum fc_scale_fn { FC_SCALE_EXP = 0, FC_SCALE_SIGMOID = 1 };
 enum fc_act { FC_ACT_NONE = 0, FC_ACT_GELU = 1, FC_ACT_RELU = 2, FC_ACT_ELU = 3, FC_ACT_LRELU02 = 4 };
@@ -384,7 +387,7 @@ int fc_train_normlp_bwd_f32(const float* v, int32_t ldv, const float* p, int32_t
                             int32_t rows, int32_t nz, float clamp, void* stream);
 /* ExponentialCoupling element (models/exponential_coupling.py:44-58): o = [d2*d2 raw matrix | d2 shift] per point, scal4 = device
  * (scale, shift, rescale, reshift); y2 = expm(rescale tanh(scale raw + shift) + reshift + 1e-8) x2 + b, ldj = trace.  fwd: d2 <= 256
- * (d2 > 16 on the wide kernel of fc_op_expm_action_f32), bwd: d2 <= 16.
+ * (d2 > 16 on the wide kernel of fc_op_expm_action_f32), bwd: d2 <= 16 (17 <= d2 <= 160: fc_train_expm_wide_bwd_f32 below).
  * status (device int32): set when a matrix norm exceeds the 64 squarings the backward keeps states for (d2 <= 16), or the wide kernel's
  * bound (d2 > 16, 40 Taylor steps).
  * bwd: dscal [rows, 4] = per-point parts of the four scalars' gradients (column sums = the gradients). */
@@ -392,6 +395,16 @@ int fc_train_expm_fwd_f32(const float* x2, int32_t ldx, const float* o, int32_t 
                           int32_t d2, int32_t* status, void* stream);
 int fc_train_expm_bwd_f32(const float* x2, int32_t ldx, const float* o, int32_t ldo, const float* scal4, const float* dy2, int32_t lddy, const float* dldj,
                           float* dx2, int32_t lddx, float* dout, int32_t lddo, float* dscal, int32_t rows, int32_t d2, void* stream);
+/* Backward of the same element for 17 <= d2 <= 160 (anything else: FC_ERR_INVALID).  Added without a version step: FC_ABI_VERSION stays 9,
+ * nothing declared before changes.  One workgroup per point replays the forward of fc_op_expm_action_f32 and runs exact reverse mode
+ * through its Taylor recurrence (the shift mu, the step count and every step's early exit held constant).  Arguments as
+ * fc_train_expm_bwd_f32; columns [d2, round_up(d2, 32)) of dx2 and [d2*d2 + d2, round_up(d2*d2 + d2, 32)) of dout are zeroed.  status
+ * (device int32): set, with NaN in that row of dx2, dout and dscal, for a point beyond the forward's bound (||W - mu I||_1 > 534 or a
+ * non-finite matrix).  No atomics: bit-reproducible, and a row's outputs do not depend on the other rows.  Does not allocate, does not
+ * synchronise. */
+int fc_train_expm_wide_bwd_f32(const float* x2, int32_t ldx, const float* o, int32_t ldo, const float* scal4, const float* dy2, int32_t lddy,
+                               const float* dldj, float* dx2, int32_t lddx, float* dout, int32_t lddo, float* dscal, int32_t rows, int32_t d2,
+                               int32_t* status, void* stream);
 int fc_train_base_fwd_f32(const float* x, int32_t ldx, float* out, int32_t rows, int32_t width, void* stream);
 int fc_train_base_bwd_f32(const float* x, int32_t ldx, const float* g, float* dx, int32_t lddx, int32_t rows, int32_t width, void* stream);
 size_t fc_train_colsum_ws_bytes(int32_t cols, int32_t rows);

@@ -1,0 +1,143 @@
+"""ExponentialCoupling training backward at 17 <= d2 <= 160 (csrc/expm_wide.hip), host side: the config key, the ABI entry, and the
+algebra pin -- a fp32 torch restatement of the recurrence the kernel differentiates (Al-Mohy & Higham's Taylor action with the shift mu,
+the step count s and every step's early exit K_st held constant) against fp64 autograd through torch.matrix_exp."""
+import os
+import re
+
+import pytest
+import torch
+
+from flowcompare_amd import engine
+from flowcompare_amd.config import DEFAULTS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCAL4 = (0.7, 0.1, 1.3, 0.02)          # (scale, shift, rescale, reshift); rescale grows where the target norm needs |W| beyond it
+MAX_STEPS, M_MAX, U = 40, 55, 2.0 ** -24
+
+
+def theta_table():
+    """theta_m (m = 0 .. 55) as the kernels hold it (csrc/expm_wide.hip)."""
+    src = open(os.path.join(ROOT, "flowcompare_amd", "csrc", "expm_wide.hip")).read()
+    body = re.search(r"c_expm_theta\[56\]\s*=\s*\{(.*?)\}", src, re.S).group(1)
+    th = [float(v.rstrip("f")) for v in re.findall(r"[0-9.]+(?:e[+-]?\d+)?f", body)]
+    assert len(th) == 56 and th[0] == 0.0
+    return torch.tensor(th, dtype=torch.float32)
+
+
+def make_w(d2, norm, rows, seed):
+    """rows random matrices [rows, d2, d2] (fp64) with ||W||_1 = norm (one value, or one per row) and a diagonal offset
+    (mu = tr W / d2 != 0)."""
+    g = torch.Generator().manual_seed(seed)
+    W = torch.randn(rows, d2, d2, generator=g, dtype=torch.float64)
+    W = W + 0.15 * d2 ** 0.5 * torch.eye(d2, dtype=torch.float64) * (1.0 + torch.rand(rows, 1, 1, generator=g, dtype=torch.float64))
+    return W * (torch.as_tensor(norm, dtype=torch.float64) / W.abs().sum(1).max(1).values)[:, None, None]
+
+
+def make_case(d2, norm, rows=5, seed=0):
+    """Inputs of the operator: raw panel values such that W = rs tanh(sc raw + sh) + rsh + 1e-8 has ||W||_1 = norm (tanh argument within
+    +-1.1), x2, dy2, b, dldj (fp32) and the four scalars."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    W = make_w(d2, norm, rows, seed)
+    sc, sh, rs, rsh = SCAL4
+    rs = max(rs, 1.25 * float((W - rsh).abs().max()))
+    raw = ((torch.atanh((W - rsh - 1e-8) / rs) - sh) / sc).float()
+    x2 = torch.randn(rows, d2, generator=g)
+    dy2 = torch.randn(rows, d2, generator=g)
+    b = torch.randn(rows, d2, generator=g)
+    dldj = torch.randn(rows, generator=g)
+    return raw, x2, b, dy2, dldj, torch.tensor([sc, sh, rs, rsh], dtype=torch.float32)
+
+
+def autograd_reference(raw, x2, b, dy2, dldj, scal4, dtype):
+    """y = expm(W(raw)) x + b, L = sum y dy + sum_rows dldj tr W through torch.matrix_exp in `dtype` on the CPU.  Returns the gradients and
+    sum |terms| of each of the four scalar gradients."""
+    raw, x2, b = (t.to(dtype).clone().requires_grad_(True) for t in (raw, x2, b))
+    s4 = scal4.to(dtype).clone().requires_grad_(True)
+    t = torch.tanh(s4[0] * raw + s4[1])
+    W = s4[2] * t + s4[3] + 1e-8
+    W.retain_grad()
+    y = torch.einsum("rij,rj->ri", torch.matrix_exp(W), x2) + b
+    L = (y * dy2.to(dtype)).sum() + (dldj.to(dtype) * torch.diagonal(W, dim1=1, dim2=2).sum(-1)).sum()
+    L.backward()
+    gw = W.grad
+    gt = gw * s4[2].detach() * (1 - t.detach() ** 2)
+    terms = torch.stack([(gt * raw.detach()).abs().sum(), gt.abs().sum(), (gw * t.detach()).abs().sum(), gw.abs().sum()])
+    return dict(dx2=x2.grad, draw=raw.grad, db=b.grad, dscal=s4.grad, terms=terms, y=y.detach())
+
+
+def recurrence_backward(W, x, dy, theta):
+    """The kernel's recurrence for one point in W's dtype: forward F_st = eta sum_{k<=K_st} t_k with t_k = A t_{k-1} / (s k), A = W - mu I,
+    then exact reverse mode with mu, eta, m, s, K_st constant.  Returns (y - b, dx, dA, s, m)."""
+    d2 = W.shape[0]
+    dt = W.dtype
+    mu = torch.diagonal(W).sum() / d2
+    A = W - mu * torch.eye(d2, dtype=dt)
+    nrm = float(A.abs().sum(0).max())
+    assert nrm <= MAX_STEPS * float(theta[M_MAX])
+    best, m, s = float("inf"), 1, 1
+    for mm in range(1, M_MAX + 1):
+        sm = max(1.0, float(torch.ceil(torch.tensor(nrm, dtype=torch.float32) / theta[mm])))
+        if mm * sm < best:
+            best, m, s = mm * sm, mm, int(sm)
+    eta = torch.exp(mu / s)
+    F, steps = x.clone(), []
+    bnorm = float(F.abs().max())
+    for _ in range(s):
+        terms, c1, fn, acc = [F], bnorm, bnorm, F.clone()
+        for k in range(1, m + 1):
+            t = (A @ terms[-1]) * torch.tensor(1.0 / (s * k), dtype=dt)
+            terms.append(t)
+            acc = acc + t
+            c2, fn = float(t.abs().max()), float(acc.abs().max())
+            if c1 + c2 <= U * fn:
+                break
+            c1 = c2
+        steps.append(terms)
+        F = acc * eta
+        bnorm = fn * float(eta)
+    lam, dA = dy.clone(), torch.zeros_like(A)
+    for terms in reversed(steps):
+        nu = eta * lam
+        mk = nu
+        for k in range(len(terms) - 1, 0, -1):
+            mkf = mk * torch.tensor(1.0 / (s * k), dtype=dt)
+            dA += torch.outer(mkf, terms[k - 1])
+            mk = nu + A.T @ mkf
+        lam = mk
+    return F, lam, dA, s, m
+
+
+def _rel(a, b):
+    return float((a.double() - b).abs().max() / b.abs().max())
+
+
+def test_config_key_defaults_to_off():
+    assert DEFAULTS["expm_wide_backward"] is False
+
+
+def test_header_declares_the_entry_and_engine_exports_it():
+    header = open(os.path.join(ROOT, "include", "fcflow.h")).read()
+    assert re.search(r"\bint\s+fc_train_expm_wide_bwd_f32\s*\(", header)
+    assert "fc_train_expm_wide_bwd_f32" in engine.EXPORTS
+    assert re.search(r"FC_ABI_VERSION\s+9\b", header) and engine.ABI_VERSION == 9
+
+
+@pytest.mark.parametrize("d2", [33, 150])
+@pytest.mark.parametrize("norm", [0.3, 32.0])
+def test_fp32_recurrence_matches_fp64_autograd(d2, norm):
+    """W used directly (no tanh): max |g - g64| / max |g64| <= 1e-6 for dx and dW (3e-8 .. 6.6e-7 on these cases, depending on the host
+    BLAS's summation order).  The GPU operator's gate is 2e-6."""
+    theta = theta_table()
+    W64 = make_w(d2, norm, 2, seed=d2)
+    g = torch.Generator().manual_seed(d2)
+    x, dy = torch.randn(2, d2, generator=g), torch.randn(2, d2, generator=g)
+    for r in range(2):
+        Wr = W64[r].float().double().requires_grad_(True)
+        xr = x[r].double().requires_grad_(True)
+        y64 = torch.matrix_exp(Wr) @ xr
+        (y64 * dy[r].double()).sum().backward()
+        y, dx, dA, s, m = recurrence_backward(W64[r].float(), x[r], dy[r], theta)
+        ey, ex, ew = _rel(y, y64.detach()), _rel(dx, xr.grad), _rel(dA, Wr.grad)
+        print(f"d2 {d2} ||W||_1 {norm}: s {s} m {m}; y {ey:.1e} dx {ex:.1e} dW {ew:.1e}")
+        assert ex <= 1e-6 and ew <= 1e-6
+        assert (s, norm) in ((1, 0.3), (3, 32.0))

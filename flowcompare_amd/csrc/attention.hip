@@ -1,11 +1,11 @@
 // Single-head cross attention of the flow's pre-conditioner, flash style.  Two kernels: attn16_kernel (split-fp16 operands on
 // the 16-bit matrix cores, the default for head dims <= 64 inside an Fp16Guard scope; further down) and attn_kernel (fp32-input
-// MFMA; head dim 128, the range-fallback pass, and the first build's kernel), described here:
+// MFMA; head dims 128 and 256, the range-fallback pass, and the first build's kernel), described here:
 //   out[b, i, :] = softmax_j( q[b,i,:] . k[b,j,:] ) v[b,j,:]        (models/perceiver.py:106-113)
 // q arrives PRE-SCALED by inner_dim^-0.5 * log2(e) (folded into the packed q projection), so the softmax
 // is exp2(S - max).  The [N, M] score matrix is never materialised (the reference materialises [B,N,M]).
 //
-// One workgroup = 128 queries of one scene (4 waves x 32 queries); K/V tiles of 64 keys are staged in LDS
+// One workgroup = 128 queries of one scene (4 waves x 32 queries); K/V tiles of 64 keys (32 at head dim 256) are staged in LDS
 // (register prefetch, double buffered) and shared by the 4 waves.
 //   S^T tile = K Q^T   (A = K rows from LDS via ds_read_b128, B = Q held in registers for the whole kernel);
 //     its C layout puts the query on the LANE and the 32 keys in the 16 registers x 2 half-waves, so the
@@ -36,8 +36,10 @@ struct AttnParams {
 template <int DH>
 __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
     constexpr int NG = DH / 8, DT = DH / 32, LD = DH + 4;
-    constexpr int F4R = DH / 4, RPP = 256 / F4R, PASSES = 64 / RPP;
-    constexpr int STAGE = 2 * 64 * LD;
+    // keys per staged tile: 64 up to head dim 128; 32 at 256, where two stages of 64 keys of K and V (266 KB) exceed a CU's 160 KiB of LDS
+    constexpr int KT = DH > 128 ? 32 : 64, NH2 = KT / 32;
+    constexpr int F4R = DH / 4, RPP = 256 / F4R, PASSES = KT / RPP;
+    constexpr int STAGE = 2 * KT * LD;
     extern __shared__ float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
     float* const sKst = smem + srow * LD + sc4;
 #define FC_GLOAD(T_)                                                                          \
     _Pragma("unroll") for (int i = 0; i < PASSES; ++i) {                                      \
-        int key_ = (T_) * 64 + srow + RPP * i;                                                \
+        int key_ = (T_) * KT + srow + RPP * i;                                                \
         key_ = key_ < p.M ? key_ : p.M - 1; /* clamped rows are masked to -inf below */       \
         rk[i] = *reinterpret_cast<const float4*>(kb + (size_t)key_ * p.ldk);                  \
         rv[i] = *reinterpret_cast<const float4*>(vb + (size_t)key_ * p.ldv);                  \
@@ -82,10 +84,10 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
 #define FC_LSTORE(ST_)                                                                        \
     _Pragma("unroll") for (int i = 0; i < PASSES; ++i) {                                      \
         *reinterpret_cast<float4*>(sKst + (ST_) * STAGE + RPP * i * LD) = rk[i];              \
-        *reinterpret_cast<float4*>(sKst + (ST_) * STAGE + 64 * LD + RPP * i * LD) = rv[i];    \
+        *reinterpret_cast<float4*>(sKst + (ST_) * STAGE + KT * LD + RPP * i * LD) = rv[i];    \
     }
 
-    const int ntiles = (p.M + 63) / 64;
+    const int ntiles = (p.M + KT - 1) / KT;
     FC_GLOAD(0)
     FC_LSTORE(0)
     __syncthreads();
@@ -94,12 +96,12 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
         const int tn = t + 1 < ntiles ? t + 1 : t;          // the last iteration re-loads its own tile: branch-free loop
         FC_GLOAD(tn)
         const float* sK = smem + (t & 1) * STAGE;
-        const float* sV = sK + 64 * LD;
+        const float* sV = sK + KT * LD;
 
-        // ---- S^T = K Q^T for the two 32-key halves of the tile
-        floatx16 s[2];
+        // ---- S^T = K Q^T for the 32-key blocks of the tile
+        floatx16 s[NH2];
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
+        for (int h2 = 0; h2 < NH2; ++h2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[h2][r] = 0.f;
             const float* kr = sK + (32 * h2 + li) * LD + 4 * lh;
@@ -113,19 +115,19 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
             }
         }
         // ---- mask the tail keys of the last tile
-        if (t * 64 + 64 > p.M) {
+        if (t * KT + KT > p.M) {
 #pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2)
+            for (int h2 = 0; h2 < NH2; ++h2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = t * 64 + 32 * h2 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int key = t * KT + 32 * h2 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     if (key >= p.M) s[h2][r] = -INFINITY;
                 }
         }
         // ---- online softmax (this lane's query = lane&31; the other half of its keys lives in lane^32)
         float mt = s[0][0];
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
+        for (int h2 = 0; h2 < NH2; ++h2)
 #pragma unroll
             for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[h2][r]);
         mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);          // 0 on the first tile (m_run = -inf)
         float lt = 0.f;
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
+        for (int h2 = 0; h2 < NH2; ++h2)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float pv = __builtin_amdgcn_exp2f(s[h2][r] - m_new);   // raw v_exp_f32: arguments are <= 0, results below 2^-126 may flush to 0
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
         }
         // ---- O += P V : A = P registers (query on the lane, key per step), B = V[key][d] from LDS
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
+        for (int h2 = 0; h2 < NH2; ++h2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float* vr = sV + (32 * h2 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LD + li;
@@ -508,7 +510,7 @@ static void launch_attn16_dh(const Attn16Params& p, int B, hipStream_t s) {
 
 template <int DH>
 static void launch_attn_dh(const AttnParams& p, int B, hipStream_t s) {
-    constexpr size_t lds = 2 * 2 * 64 * (size_t)(DH + 4) * sizeof(float);
+    constexpr size_t lds = 2 * 2 * (size_t)(DH > 128 ? 32 : 64) * (DH + 4) * sizeof(float);      // 135 KB at head dim 128, 133 KB at 256 (32-key tiles)
     static PerDeviceOnce attr_once;
     auto kern = attn_kernel<DH>;
     attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
@@ -559,7 +561,8 @@ static void launch_attention_scaled(const float* q, int ldq, const float* k, int
         case 32: launch_attn_dh<32>(p, B, s); break;
         case 64: launch_attn_dh<64>(p, B, s); break;
         case 128: launch_attn_dh<128>(p, B, s); break;
-        default: throw Error(FC_ERR_UNSUPPORTED, "attention: inner dim (padded) must be 32, 64 or 128");
+        case 256: launch_attn_dh<256>(p, B, s); break;
+        default: throw Error(FC_ERR_UNSUPPORTED, "attention: inner dim (padded) must be 32, 64, 128 or 256");
     }
 }
 

@@ -2,7 +2,7 @@
 //   w[b, p, j] = softmax_j( q[b, sel[b,p], :] . k[b, j, :] )      j < M          (models/perceiver.py:108-111, `attn_weights`)
 // The forward's kernels (attention.hip) stream the softmax and never form a row; this kernel is launched next to them, only at the layers a
 // caller asks about, and reads the operands in the forms the forward leaves them in:
-//   K  KF 0: an fp32 panel (head dim 128, the range-fallback pass, fc_op_*);  KF 1: columns of the stacked K|V GEMM's one-accumulator limb image
+//   K  KF 0: an fp32 panel (head dims 128 and 256, the range-fallback pass, fc_op_*);  KF 1: columns of the stacked K|V GEMM's one-accumulator limb image
 //      (GemmEpi::C16 with c16_scale = kOneAccActScale: [16 columns: hi 16 | lo 16] tiles, k 16 = hi + lo) -- joined back to fp32 while the tile
 //      is staged, which is exact: hi + lo spans at most 22 significant bits; with k16_rows the folded engine's context image instead, packed rows
 //      [key][hi DH | lo DH] of the same form (launch_context_limbs: the keys of EVERY layer, with q carrying the layer's Wk);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void attn_weights_kernel(const AttnWParams p) 
 
 template <int DH, int KF>
 static void launch_attnw_dh(const AttnWParams& p, int B, hipStream_t s) {
-    constexpr size_t lds = (64 * (size_t)(DH + 4) + 4 * 32 * 65) * sizeof(float);      // 67 KB at head dim 128
+    constexpr size_t lds = (64 * (size_t)(DH + 4) + 4 * 32 * 65) * sizeof(float);      // 67 KB at head dim 128, 100 KB at 256
     static PerDeviceOnce attr_once;
     auto kern = attn_weights_kernel<DH, KF>;
     attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
@@ -229,7 +229,8 @@ void launch_attention_weights(const float* q, int ldq, const float* k, int ldk, 
         case 32: launch_attnw_dh<32, 0>(p, B, s); break;
         case 64: launch_attnw_dh<64, 0>(p, B, s); break;
         case 128: launch_attnw_dh<128, 0>(p, B, s); break;
-        default: throw Error(FC_ERR_UNSUPPORTED, "attention weights: inner dim (padded) must be 32, 64 or 128");
+        case 256: launch_attnw_dh<256, 0>(p, B, s); break;
+        default: throw Error(FC_ERR_UNSUPPORTED, "attention weights: inner dim (padded) must be 32, 64, 128 or 256");
     }
 }
 

@@ -110,7 +110,8 @@ static int pad_inner(int I) {
     if (I <= 32) return 32;
     if (I <= 64) return 64;
     if (I <= 128) return 128;
-    throw Error(FC_ERR_UNSUPPORTED, "attention inner dim (cross_heads*cross_dim_head) > 128 is not supported yet");
+    if (I <= 256) return 256;
+    throw Error(FC_ERR_UNSUPPORTED, "attention inner dim (cross_heads*cross_dim_head) > 256 is not supported (the limit is 256)");
 }
 bool kv_fold_gate_dims(int E, int inner, bool q_bias, bool kv_bias) {
     return E > 0 && E == inner && inner <= 128 && round_up(E, 32) == pad_inner(inner) && !q_bias && !kv_bias;

@@ -213,7 +213,7 @@ int fc_op_attention_f32(const float* q, const float* k, const float* v, float* o
                         void* stream) {
     FC_API_BEGIN
     if (!q || !k || !v || !out) throw fc::Error(FC_ERR_INVALID, "fc_op_attention_f32: null pointer");
-    if (D != 32 && D != 64 && D != 128) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_f32: D must be 32, 64 or 128");
+    if (D != 32 && D != 64 && D != 128 && D != 256) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_f32: D must be 32, 64 or 128, or 256");
     fc::TmpBuf limbs(fc::attention_limb_ws_bytes((long)B * M, D)), flag(sizeof(int));
     fc::run_fp16_guarded((int*)flag.p, (hipStream_t)stream,
                          [&] { fc::launch_attention_op(q, k, v, out, B, N, M, D, scale, limbs.p, (hipStream_t)stream); });
@@ -246,7 +246,7 @@ int fc_op_attention_weights_f32(const float* q, const float* k, float* out, cons
                                 int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream) {
     FC_API_BEGIN
     if (!q || !k || !out) throw fc::Error(FC_ERR_INVALID, "fc_op_attention_weights_f32: null pointer");
-    if (D != 32 && D != 64 && D != 128) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_weights_f32: D must be 32, 64 or 128");
+    if (D != 32 && D != 64 && D != 128 && D != 256) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_weights_f32: D must be 32, 64 or 128, or 256");
     fc::launch_attention_weights(q, D, k, D, nullptr, 0, 0, out, sel, sel ? P : N, sel_per_scene, B, N, N, M, M, D, scale * 1.4426950408889634f,
                                  nullptr, (hipStream_t)stream);
     FC_HIP(hipStreamSynchronize((hipStream_t)stream));

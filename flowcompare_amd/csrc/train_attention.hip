@@ -40,8 +40,9 @@ __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >
 template <int DH>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdParams p) {
     constexpr int LD = DH + 1, HALF = DH / 2, NB = DH / 32;
-    __shared__ float sK[32 * LD];
-    __shared__ float sV[32 * LD];
+    extern __shared__ float bwd_smem[];                        // dynamic: 2 x 32 x (DH + 1) floats are 66 KB at head dim 256, above the static limit
+    float* const sK = bwd_smem;
+    float* const sV = bwd_smem + 32 * LD;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
     const int b = blockIdx.y;
     const int qrow = blockIdx.x * 128 + wave * 32 + li;
@@ -58,6 +59,24 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdParams p) {
         dsum += dOr[j] * (qok ? p.o[grow * p.ldo + 2 * j + h] : 0.f);
     }
     dsum += __shfl_xor(dsum, 32, 64);
+    if constexpr (DH >= 128) {
+        // D_i = dO_i . O_i again, as the diagonal of O dO^T on the matrix cores: the products and the summation order of the dP tiles below
+        // (A = a row's 2 kk + h, B = dOr[kk]).  dS = P (dP - D) is a difference of two sums of ~sqrt(DH) |dO| |v|; summed in two different
+        // orders their rounding errors do not cancel, which at these widths showed as dq ~ 4e-6 where a one-key softmax (O = v, dP = D) owes an
+        // exact zero.  One extra 32 x 32 tile per wave and launch.  (Head dims 32 and 64 keep the in-lane sum: their bits do not move.)
+        f32x16 dd;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dd[r] = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < HALF; ++kk)
+            dd = __builtin_amdgcn_mfma_f32_32x32x2f32(qok ? p.o[grow * p.ldo + 2 * kk + h] : 0.f, dOr[kk], dd, 0, 0, 0);
+        // row li of column li sits in register (li & 3) + 4 (li >> 3) of the half-wave (li >> 2) & 1
+        const int rsel = (li & 3) + 4 * (li >> 3);
+        float dg = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dg = r == rsel ? dd[r] : dg;
+        dsum = __shfl(dg, li + 32 * ((li >> 2) & 1), 64);
+    }
     const int ntiles = (p.M + 31) / 32;
     // cooperative staging: 32 x DH floats per tile, 256 threads
     auto stage = [&](const float* src, int ld, float* dst, int t) {
@@ -96,12 +115,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdParams p) {
     }
     const float lse = m + logf(l);
     if (qok && h == 0) { p.lse[grow] = lse; p.dvec[grow] = dsum; }
-    // ---- pass B: dQ
-    f32x16 dqa[NB];
+    // ---- pass B: dQ.  At head dim 256 the query rows (Q, dO: 256 registers), 8 accumulator blocks (128) and the two score tiles (32) leave
+    //      the compiler short of a lane's 512 registers (it spilled), so the head dimension is walked in two 128-wide halves of dQ, each
+    //      recomputing the score tiles: 352 registers, no scratch.  One half up to 128: the loop below runs once, as it always did.
+    constexpr int NHALF = DH > 128 ? 2 : 1, NBH = NB / NHALF;
+#pragma unroll 1
+    for (int hh = 0; hh < NHALF; ++hh) {
+    f32x16 dqa[NBH];
 #pragma unroll
-    for (int i = 0; i < NB; ++i)
+    for (int i = 0; i < NBH; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dqa[i][r] = 0.f;
+    const int c0 = hh * NBH * 32;
     for (int t = 0; t < ntiles; ++t) {
         __syncthreads();
         stage(kb, p.ldk, sK, t);
@@ -126,39 +151,46 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
 #pragma unroll
-            for (int i = 0; i < NB; ++i)
-                dqa[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(sK[acc_row(r, h) * LD + i * 32 + li], s[r], dqa[i], 0, 0, 0);
+            for (int i = 0; i < NBH; ++i)
+                dqa[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(sK[acc_row(r, h) * LD + c0 + i * 32 + li], s[r], dqa[i], 0, 0, 0);
     }
     if (qok)
 #pragma unroll
-        for (int i = 0; i < NB; ++i)
+        for (int i = 0; i < NBH; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) p.dq[grow * p.lddq + i * 32 + acc_row(r, h)] = dqa[i][r];
+            for (int r = 0; r < 16; ++r) p.dq[grow * p.lddq + c0 + i * 32 + acc_row(r, h)] = dqa[i][r];
+    }
 }
 
-template <int DH>
-__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdParams p) {
+// One sweep over the query tiles for this wave's 32 keys: DV accumulates dV^T += dO^T P, DK accumulates dK^T += Q^T dS.  Up to head dim 128 one
+// sweep does both.  At 256 the key rows (K, V: 2 x 128 registers) and both accumulator sets (2 x 128) are more than a lane's 512 registers, and
+// two 128-wide halves of both sets (256 + 128 + two score tiles = 416) still spilled.  So the kernel sweeps three times: dV first, which needs
+// P alone (K rows + its whole accumulator set + one score tile: 272 registers), then dK, which needs P and dP, in NHALF = 2 halves of 128
+// columns (K and V rows + 64 + two tiles: 352).  7 DH of MFMA contraction per tile pair against 4 DH in one sweep; every accumulator still
+// receives its products in the one-sweep order: same bytes, no atomics, no scratch.
+template <int DH, bool DV, bool DK, int NHALF>
+__device__ __forceinline__ void attn_bwd_dkv_sweep(const AttnBwdParams& p, float* sQ, float* sdO, float* sLse, float* sD, int b, bool kok, size_t gk) {
     constexpr int LD = DH + 1, HALF = DH / 2, NB = DH / 32;
-    __shared__ float sQ[32 * LD];
-    __shared__ float sdO[32 * LD];
-    __shared__ float sLse[32];
-    __shared__ float sD[32];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
-    const int b = blockIdx.y;
-    const int krow = blockIdx.x * 128 + wave * 32 + li;
-    const bool kok = krow < p.M;
-    const size_t gk = (size_t)b * p.M + (kok ? krow : 0);
-    float Kr[HALF], Vr[HALF];
+    const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, h = lane >> 5;
+    float Kr[HALF], Vr[DK ? HALF : 1];
 #pragma unroll
     for (int j = 0; j < HALF; ++j) {
         Kr[j] = kok ? p.k[gk * p.ldk + 2 * j + h] : 0.f;
-        Vr[j] = kok ? p.v[gk * p.ldv + 2 * j + h] : 0.f;
+        if constexpr (DK) Vr[j] = kok ? p.v[gk * p.ldv + 2 * j + h] : 0.f;
     }
-    f32x16 dka[NB], dva[NB];
+    constexpr int NBH = NB / NHALF;
+    static_assert(NHALF == 1 || !DV, "only the dK sweep walks the head dimension in halves");
+#pragma unroll 1
+    for (int hh = 0; hh < NHALF; ++hh) {
+    const int c0 = hh * NBH * 32;
+    f32x16 dka[DK ? NBH : 1], dva[DV ? NBH : 1];
 #pragma unroll
-    for (int i = 0; i < NB; ++i)
+    for (int i = 0; i < NBH; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { dka[i][r] = 0.f; dva[i][r] = 0.f; }
+        for (int r = 0; r < 16; ++r) {
+            if constexpr (DK) dka[i][r] = 0.f;
+            if constexpr (DV) dva[i][r] = 0.f;
+        }
     const int ntiles = (p.N + 31) / 32;
     const size_t q0 = (size_t)b * p.N;
     for (int t = 0; t < ntiles; ++t) {
@@ -181,31 +213,52 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdParams p) {
 #pragma unroll
         for (int kk = 0; kk < HALF; ++kk) {
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(sQ[li * LD + 2 * kk + h], Kr[kk], s, 0, 0, 0);       // S[query][key]
-            dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sdO[li * LD + 2 * kk + h], Vr[kk], dp, 0, 0, 0);    // dP[query][key]
+            if constexpr (DK) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sdO[li * LD + 2 * kk + h], Vr[kk], dp, 0, 0, 0);    // dP[query][key]
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int qi = acc_row(r, h);
             const float pr = kok ? expf(s[r] * p.scale - sLse[qi]) : 0.f;
-            dp[r] = pr * (dp[r] - sD[qi]) * p.scale;                    // dS[query][key]
+            if constexpr (DK) dp[r] = pr * (dp[r] - sD[qi]) * p.scale;  // dS[query][key]
             s[r] = pr;                                                  // P[query][key]
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r)
 #pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                dva[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(sdO[acc_row(r, h) * LD + i * 32 + li], s[r], dva[i], 0, 0, 0);    // dV^T[d][key]
-                dka[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(sQ[acc_row(r, h) * LD + i * 32 + li], dp[r], dka[i], 0, 0, 0);    // dK^T[d][key]
+            for (int i = 0; i < NBH; ++i) {
+                if constexpr (DV) dva[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(sdO[acc_row(r, h) * LD + c0 + i * 32 + li], s[r], dva[i], 0, 0, 0);    // dV^T[d][key]
+                if constexpr (DK) dka[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(sQ[acc_row(r, h) * LD + c0 + i * 32 + li], dp[r], dka[i], 0, 0, 0);    // dK^T[d][key]
             }
     }
     if (kok)
 #pragma unroll
-        for (int i = 0; i < NB; ++i)
+        for (int i = 0; i < NBH; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                p.dk[gk * p.lddk + i * 32 + acc_row(r, h)] = dka[i][r];
-                p.dv[gk * p.lddv + i * 32 + acc_row(r, h)] = dva[i][r];
+                if constexpr (DK) p.dk[gk * p.lddk + c0 + i * 32 + acc_row(r, h)] = dka[i][r];
+                if constexpr (DV) p.dv[gk * p.lddv + c0 + i * 32 + acc_row(r, h)] = dva[i][r];
             }
+    }
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdParams p) {
+    constexpr int LD = DH + 1;
+    extern __shared__ float bwd_smem[];
+    float* const sQ = bwd_smem;
+    float* const sdO = bwd_smem + 32 * LD;
+    float* const sLse = bwd_smem + 64 * LD;
+    float* const sD = sLse + 32;
+    const int b = blockIdx.y;
+    const int krow = blockIdx.x * 128 + (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
+    const bool kok = krow < p.M;
+    const size_t gk = (size_t)b * p.M + (kok ? krow : 0);
+    if constexpr (DH <= 128) {
+        attn_bwd_dkv_sweep<DH, true, true, 1>(p, sQ, sdO, sLse, sD, b, kok, gk);
+    } else {
+        attn_bwd_dkv_sweep<DH, true, false, 1>(p, sQ, sdO, sLse, sD, b, kok, gk);
+        attn_bwd_dkv_sweep<DH, false, true, 2>(p, sQ, sdO, sLse, sD, b, kok, gk);
+    }
 }
 
 // ================================================================ the same two kernels on the split-fp16 loop (head dim 64)
@@ -540,13 +593,24 @@ static void launch_attn_bwd16(const AttnBwdParams& p, int B, int* ovf, hipStream
 template <int DH>
 static void launch_attn_bwd(const AttnBwdParams& p, int B, hipStream_t s) {
     const double fl = 2.0 * B * (double)p.N * p.M * DH;
+    constexpr size_t lds = (2 * 32 * (size_t)(DH + 1) + 64) * sizeof(float);      // 16.6 KB at head dim 64, 66 KB at 256
+    auto kq = attn_bwd_dq_kernel<DH>;
+    auto kkv = attn_bwd_dkv_kernel<DH>;
+    if constexpr (lds > 65536) {
+        static PerDeviceOnce attr_once;
+        attr_once.run([&](int) {
+            FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kq), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kkv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            return 0;
+        });
+    }
     {
-        ProfScope ps("fc::attn_bwd_dq_kernel", 4.0 * fl, 0.0, s);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<DH>, dim3((p.N + 127) / 128, B), dim3(256), 0, s, p);
+        ProfScope ps(DH <= 64 ? "fc::attn_bwd_dq_kernel" : DH == 128 ? "fc::attn_bwd_dq_kernel<128>" : "fc::attn_bwd_dq_kernel<256>", 4.0 * fl, 0.0, s);
+        hipLaunchKernelGGL(kq, dim3((p.N + 127) / 128, B), dim3(256), lds, s, p);
         FC_HIP(hipGetLastError());
     }
-    ProfScope ps("fc::attn_bwd_dkv_kernel", 4.0 * fl, 0.0, s);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<DH>, dim3((p.M + 127) / 128, B), dim3(256), 0, s, p);
+    ProfScope ps(DH <= 64 ? "fc::attn_bwd_dkv_kernel" : DH == 128 ? "fc::attn_bwd_dkv_kernel<128>" : "fc::attn_bwd_dkv_kernel<256>", (DH > 128 ? 7.0 : 4.0) * fl, 0.0, s);
+    hipLaunchKernelGGL(kkv, dim3((p.M + 127) / 128, B), dim3(256), lds, s, p);
     FC_HIP(hipGetLastError());
 }
 
@@ -573,7 +637,7 @@ int fc_train_attention_fwd_f32(const float* q, int32_t ldq, const float* k, int3
                                int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* ws, size_t ws_bytes, float* stats, int32_t* stats_valid,
                                int32_t* ovf, void* stream) {
     FC_API_BEGIN
-    if (B < 1 || N < 1 || M < 1 || (D != 32 && D != 64)) throw Error(FC_ERR_UNSUPPORTED, "fc_train_attention_fwd_f32: head dim (padded) must be 32 or 64");
+    if (B < 1 || N < 1 || M < 1 || (D != 32 && D != 64 && D != 128 && D != 256)) throw Error(FC_ERR_UNSUPPORTED, "fc_train_attention_fwd_f32: head dim (padded) must be 32, 64, 128 or 256");
     check_mat(q, ldq, D, "q"); check_mat(k, ldk, D, "k"); check_mat(v, ldv, D, "v"); check_mat(out, ldo, D, "out");
     const bool f16 = ovf && ws && ws_bytes >= fc_train_attention_ws_bytes(B, N, M, D) && !((uintptr_t)ws & 15);
     Fp16FlagScope scope(f16 ? (int*)ovf : nullptr);
@@ -587,7 +651,7 @@ int fc_train_attention_bwd_f32(const float* q, int32_t ldq, const float* k, int3
                                const float* dout, int32_t lddo, float* dq, int32_t lddq, float* dk, int32_t lddk, float* dv, int32_t lddv,
                                float* stats, int32_t stats_valid, int32_t B, int32_t N, int32_t M, int32_t D, float scale, int32_t* ovf, void* stream) {
     FC_API_BEGIN
-    if (B < 1 || N < 1 || M < 1 || (D != 32 && D != 64)) throw Error(FC_ERR_UNSUPPORTED, "fc_train_attention_bwd_f32: head dim (padded) must be 32 or 64");
+    if (B < 1 || N < 1 || M < 1 || (D != 32 && D != 64 && D != 128 && D != 256)) throw Error(FC_ERR_UNSUPPORTED, "fc_train_attention_bwd_f32: head dim (padded) must be 32, 64, 128 or 256");
     check_mat(q, ldq, D, "q"); check_mat(k, ldk, D, "k"); check_mat(v, ldv, D, "v"); check_mat(out, ldo, D, "out"); check_mat(dout, lddo, D, "dout");
     check_mat(dq, lddq, D, "dq"); check_mat(dk, lddk, D, "dk"); check_mat(dv, lddv, D, "dv");
     if (!stats) throw Error(FC_ERR_INVALID, "fc_train_attention_bwd_f32: stats scratch [2 * B * N] is required");
@@ -595,7 +659,9 @@ int fc_train_attention_bwd_f32(const float* q, int32_t ldq, const float* k, int3
     p.have_lse = (stats_valid && D == 64 && ovf && g_train_attn16) ? 1 : 0;
     if (D == 64 && ovf && g_train_attn16) launch_attn_bwd16(p, B, (int*)ovf, (hipStream_t)stream);
     else if (D == 32) launch_attn_bwd<32>(p, B, (hipStream_t)stream);
-    else launch_attn_bwd<64>(p, B, (hipStream_t)stream);
+    else if (D == 64) launch_attn_bwd<64>(p, B, (hipStream_t)stream);
+    else if (D == 128) launch_attn_bwd<128>(p, B, (hipStream_t)stream);
+    else launch_attn_bwd<256>(p, B, (hipStream_t)stream);
     FC_API_END
 }
 

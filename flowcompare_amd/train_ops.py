@@ -370,16 +370,29 @@ def mlp_forward(mlp, x, act="GELU"):
 
 class AttentionFn(torch.autograd.Function):
     """out = softmax(q k^T scale) v per scene (models/perceiver.py:106-113) on panels q [B*N (padded), D], k / v [B*M (padded), D];
-    D = head dim padded to 32 or 64 with zero columns.  Backward recomputes the scores tile by tile (csrc/train_attention.hip)."""
+    D = head dim padded with zero columns to a multiple of 32 (to_panel), at most 256.  The kernels take D = 32, 64, 128 or 256: a panel of
+    another width (96, 160, 192, 224) is copied here into zero-padded panels of the next kernel width, and out / dq / dk / dv come back
+    at the caller's width -- zero columns change neither the scores nor any gradient (`scale` is explicit, never derived from D).
+    Backward recomputes the scores tile by tile (csrc/train_attention.hip); the forward's saved log-sum-exp is reused at D = 64 only."""
+
+    @staticmethod
+    def _kernel_width(D):
+        for w in (32, 64, 128, 256):
+            if D <= w:
+                return w
+        raise RuntimeError(f"AttentionFn: head dim {D} (padded) is above the limit 256")
 
     @staticmethod
     def forward(ctx, q, k, v, B, N, M, scale):
         L = engine.lib()
-        D = q.shape[1]
+        D0 = q.shape[1]
         for t, rows in ((q, B * N), (k, B * M), (v, B * M)):
-            _check_panel(t, D)
-            if t.shape[0] < rows or t.shape[1] != D:
+            _check_panel(t, D0)
+            if t.shape[0] < rows or t.shape[1] != D0:
                 raise RuntimeError("AttentionFn: panel smaller than B * points, or head dims differ")
+        D = AttentionFn._kernel_width(D0)
+        if D != D0:
+            q, k, v = (torch.nn.functional.pad(t, (0, D - D0)) for t in (q, k, v))
         dev = q.device
         out = _panel_out(q.shape[0], D, B * N, dev)
         with _OnDevice(dev):
@@ -391,15 +404,15 @@ class AttentionFn(torch.autograd.Function):
                                                        ctypes.c_float(scale), engine._ptr(ws), ctypes.c_size_t(nb), engine._ptr(stats),
                                                        ctypes.byref(valid), _flag_ptr(), engine._stream()))
         ctx.save_for_backward(q, k, v, out, stats)
-        ctx.meta = (B, N, M, D, scale, int(valid.value))
-        return out
+        ctx.meta = (B, N, M, D, scale, int(valid.value), D0)
+        return out if D == D0 else out[:, :D0].contiguous()
 
     @staticmethod
     def backward(ctx, dout):
         L = engine.lib()
         q, k, v, out, stats = ctx.saved_tensors
-        B, N, M, D, scale, stats_valid = ctx.meta
-        dout = dout.contiguous()
+        B, N, M, D, scale, stats_valid, D0 = ctx.meta
+        dout = dout.contiguous() if D == D0 else torch.nn.functional.pad(dout, (0, D - D0))
         dq = _panel_out(q.shape[0], D, B * N, q.device)
         dk, dv = _panel_out(k.shape[0], D, B * M, q.device), _panel_out(k.shape[0], D, B * M, q.device)
         with _OnDevice(q.device):
@@ -407,6 +420,8 @@ class AttentionFn(torch.autograd.Function):
                                                        engine._ptr(dout), D, engine._ptr(dq), D, engine._ptr(dk), D, engine._ptr(dv), D,
                                                        engine._ptr(stats), stats_valid if _Step.flag is not None else 0, B, N, M, D,
                                                        ctypes.c_float(scale), _flag_ptr(), engine._stream()))
+        if D != D0:
+            dq, dk, dv = (t[:, :D0].contiguous() for t in (dq, dk, dv))
         return dq, dk, dv, None, None, None, None
 
 

@@ -273,11 +273,12 @@ int fc_op_linear_f32(const float* x, const float* W, const float* bias, const fl
 int fc_op_mlp_hidden_f32(const float* x0, int32_t k0, const float* x1, int32_t k1, const float* rowscal, const fc_tensor* tensors,
                          int32_t n_tensors, float* out, int32_t rows, int32_t act, int32_t use_rows, void* stream);
 
-/* out[B,N,D] = softmax(q k^T * scale) v  with q [B,N,D], k,v [B,M,D]  (models/perceiver.py:106-113). */
+/* out[B,N,D] = softmax(q k^T * scale) v  with q [B,N,D], k,v [B,M,D], D in {32, 64, 128, 256}  (models/perceiver.py:106-113).
+ * D <= 64 runs the split-fp16 kernel, 128 and 256 the fp32-input MFMA kernel (256: 32-key tiles). */
 int fc_op_attention_f32(const float* q, const float* k, const float* v, float* out,
                         int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream);
 
-/* out[B,P,M] = rows sel of softmax(q k^T * scale) with q [B,N,D], k [B,M,D], D in {32, 64, 128} (models/perceiver.py:108-111): the
+/* out[B,P,M] = rows sel of softmax(q k^T * scale) with q [B,N,D], k [B,M,D], D in {32, 64, 128, 256} (models/perceiver.py:108-111): the
  * kernel of fc_flow_attention_weights_f32 alone.  sel: device int32 [P] (sel_per_scene = 0) or [B,P] (1); NULL = all rows (P = N). */
 int fc_op_attention_weights_f32(const float* q, const float* k, float* out, const int32_t* sel, int32_t P, int32_t sel_per_scene,
                                 int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream);
@@ -342,8 +343,9 @@ int fc_train_act_fwd_f32(const float* u, float* y, int32_t rows_pad, int32_t ld,
 int fc_train_act_bwd_f32(const float* dy, const float* u, float* du, int32_t rows_pad, int32_t rows, int32_t ld, int32_t act, void* stream);
 
 /* Cross-attention core out = softmax(q k^T scale) v per scene (models/perceiver.py:106-113) on row-major matrices with pitches
- * (q, out, dout, dq: [B*N, ld]; k, v, dk, dv: [B*M, ld]; D = padded head dim, 32 or 64) and its backward, which recomputes the
- * scores tile by tile (nothing of [N, M] is stored).  fwd: ws (fc_train_attention_ws_bytes) + ovf select the split-fp16 kernel.
+ * (q, out, dout, dq: [B*N, ld]; k, v, dk, dv: [B*M, ld]; D = padded head dim: 32, 64, 128 or 256 -- a caller with another width, such as the 96 or 160 columns of a
+ * 32-padded panel, zero-pads its matrices to the next of these, as train_ops.AttentionFn does) and its backward, which recomputes the
+ * scores tile by tile (nothing of [N, M] is stored; at D = 256 the dQ and dK accumulators are walked in two 128-column halves).  fwd: ws (fc_train_attention_ws_bytes) + ovf select the split-fp16 kernel.
  * stats = device buffer of 2*B*N floats (log-sum-exp and dO.O per query): the split-fp16 forward leaves the log-sum-exp in its first
  * half and sets *stats_valid (host int), which the backward takes back to skip its own pass; ovf selects the split-fp16 kernels (D = 64). */
 size_t fc_train_attention_ws_bytes(int32_t B, int32_t N, int32_t M, int32_t D);

@@ -304,9 +304,6 @@ struct TrainWideArgs {
 };
 void launch_train_wide(const TrainWideArgs& a, hipStream_t s);
 extern int g_train_wide;         // knob 31: 1 = training Linear layers with at least 1024 outputs run on it (shipped), 0 = on the fp32-A 128 x 128 loop
-// row maxima of a gradient panel, handed from the kernel that writes it (training spline backward) to the data-gradient GEMM that reads it
-float* train_rowmax_reserve(const float* tensor, int rows, hipStream_t s);
-const float* train_rowmax_take(const float* tensor, int rows, hipStream_t s);
 // staging.hip: the steps either side of the path
 void launch_fps_nd(const float* pts, int ld, int C, int64_t* idx, int B, int n, int m, float* dist_scratch, hipStream_t s);
 void launch_co_unit_sphere(const float* p0, int n0, const float* p1, int n1, int ld, float* o0, float* o1, float* inverse, int B, hipStream_t s);

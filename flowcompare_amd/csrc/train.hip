@@ -19,8 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <mutex>
 
 #include "activations.h"
 #include "common.h"
@@ -532,50 +530,23 @@ static PackedLinear packed_transposed(const TrainLinearLayout& L, const void* pa
     return P;
 }
 
-// ---------------------------------------------------------------- row maxima of a gradient panel (producer -> data-gradient GEMM)
-// The training spline backward holds a whole row of d(parameters) in LDS when it writes it, so it also writes max |row|; the data gradient of
-// the parameter layer (the next launch that reads the panel, same stream) scales every row by an exact power of two with it before the
-// limb split (spline_wide.hip EPI 3).  One entry per device; taking it consumes it (a panel that reached the GEMM by another route finds none
-// and runs on the fp32-A loop).
-namespace {
-struct RowMaxSlot { float* buf = nullptr; int cap = 0; const float* tensor = nullptr; int rows = 0; hipStream_t s = nullptr; unsigned long long stamp = 0; };
-std::mutex g_rowmax_mu;
-RowMaxSlot g_rowmax[16];
-// an entry is good for the next few training-Linear calls only (the parameter layer's weight and data gradient follow its spline backward
-// directly): a panel that is merely allocated where an earlier gradient panel lived never meets that panel's row maxima
-std::atomic<unsigned long long> g_train_calls{0};
-constexpr unsigned long long kRowMaxLifetime = 4;
-}
-void train_call_tick() { g_train_calls.fetch_add(1); }
-float* train_rowmax_reserve(const float* tensor, int rows, hipStream_t s) {
-    int dev = 0;
-    FC_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) return nullptr;
-    std::lock_guard<std::mutex> lk(g_rowmax_mu);
-    RowMaxSlot& r = g_rowmax[dev];
-    if (r.cap < rows) {
-        if (r.buf) { FC_HIP(hipStreamSynchronize(r.s)); FC_HIP(hipFree(r.buf)); r.buf = nullptr; r.cap = 0; }
-        FC_HIP(hipMalloc((void**)&r.buf, (size_t)rows * 4));
-        r.cap = rows;
-    }
-    r.tensor = tensor; r.rows = rows; r.s = s; r.stamp = g_train_calls.fetch_add(1) + 1;
-    return r.buf;
-}
-const float* train_rowmax_take(const float* tensor, int rows, hipStream_t s) {
-    int dev = 0;
-    FC_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) return nullptr;
-    std::lock_guard<std::mutex> lk(g_rowmax_mu);
-    RowMaxSlot& r = g_rowmax[dev];
-    const unsigned long long now = g_train_calls.load();
-    if (!r.buf || r.tensor != tensor || r.rows < rows || r.s != s || now - r.stamp > kRowMaxLifetime) return nullptr;
-    r.tensor = nullptr;
-    return r.buf;
-}
-
 // the wide layers on the 256 x 256 one-accumulator loop (forward: constant activation scale; data gradient: per-row scales)
 static bool train_wide_fwd_ok(const TrainLinearLayout& L, int rows_pad, const int32_t* ovf, const float* residual) {
     return g_train_wide && L.wide && ovf && !residual && rows_pad % 256 == 0 && gemm_fp16_enabled();
+}
+
+// the data gradient of such a layer on the same loop: every row of du scaled by an exact power of two from `row_absmax` ([rows_pad], each >=
+// max |du[row, :]|, written by the kernel that produced du -- fc_train_rqspline_bwd_f32); false = not eligible, the fp32-A loop runs
+static bool train_wide_dgrad(const TrainLinearLayout& L, const void* pack, const float* du, int ldu, int rows_pad, const float* row_absmax, float* dx,
+                             int lddx, const float* addend, const float* u_prev, int act, int32_t* ovf, hipStream_t s) {
+    if (!(g_train_wide && L.wide && ovf && row_absmax && rows_pad % 256 == 0 && (!u_prev || act == FC_ACT_GELU) && gemm_fp16_enabled())) return false;
+    TrainWideArgs w;
+    w.A = du; w.lda = ldu; w.W1 = (const unsigned short*)((const char*)pack + L.off_WT1); w.K_pad = L.N_pad; w.rows_pad = rows_pad; w.n_cols = L.K_pad;
+    w.row_absmax = row_absmax; w.C = dx; w.ldc = lddx; w.ovf = (int*)ovf;
+    if (u_prev) { w.addend = addend; w.gradu = u_prev; w.ldgu = lddx; w.gact = act; }
+    w.flops = 2.0 * rows_pad * (double)L.N * (double)L.K;
+    launch_train_wide(w, s);
+    return true;
 }
 
 static void check_panel(const void* p, int ld, int width_pad, const char* what) {
@@ -610,7 +581,6 @@ int fc_train_linear_pack_f32(const float* W, const float* bias, int32_t N, const
 int fc_train_linear_fwd_f32(const void* pack, int32_t N, const int32_t* seg_widths, int32_t nseg, const float* const* x, const int32_t* ldx,
                             int32_t rows_pad, const float* residual, int32_t ldr, float* u, int32_t ldu, int32_t* ovf, void* stream) {
     FC_API_BEGIN
-    train_call_tick();
     const TrainLinearLayout L = train_layout(N, seg_widths, nseg);
     if (!pack || !x || !ldx || rows_pad < 1 || rows_pad % ROW_PAD != 0) throw Error(FC_ERR_INVALID, "fc_train_linear_fwd_f32: bad argument (rows_pad must be a multiple of 256)");
     ASeg a[3] = {};
@@ -639,7 +609,6 @@ int fc_train_linear_act_fwd_f32(const void* pack, int32_t N, const int32_t* seg_
                                 int32_t rows_pad, const float* residual, int32_t ldr, float* u, float* y, int32_t ldu, int32_t act, int32_t* ovf,
                                 void* stream) {
     FC_API_BEGIN
-    train_call_tick();
     const TrainLinearLayout L = train_layout(N, seg_widths, nseg);
     if (!pack || !x || !ldx || rows_pad < 1 || rows_pad % ROW_PAD != 0) throw Error(FC_ERR_INVALID, "fc_train_linear_act_fwd_f32: bad argument (rows_pad must be a multiple of 256)");
     if (act != FC_ACT_GELU && act != FC_ACT_RELU && act != FC_ACT_ELU) throw Error(FC_ERR_INVALID, "fc_train_linear_act_fwd_f32: act must be GELU, RELU or ELU");
@@ -657,23 +626,13 @@ int fc_train_linear_act_fwd_f32(const void* pack, int32_t N, const int32_t* seg_
 }
 
 int fc_train_linear_dgrad_f32(const void* pack, int32_t N, const int32_t* seg_widths, int32_t nseg, const float* du, int32_t ldu, int32_t rows_pad,
-                              float* dx, int32_t lddx, int32_t* ovf, void* stream) {
+                              float* dx, int32_t lddx, const float* row_absmax, int32_t* ovf, void* stream) {
     FC_API_BEGIN
-    train_call_tick();
     const TrainLinearLayout L = train_layout(N, seg_widths, nseg);
     if (!pack || rows_pad < 1 || rows_pad % ROW_PAD != 0) throw Error(FC_ERR_INVALID, "fc_train_linear_dgrad_f32: bad argument (rows_pad must be a multiple of 256)");
     check_panel(du, ldu, L.N_pad, "du");
     check_panel(dx, lddx, L.K_pad, "dx");
-    if (g_train_wide && L.wide && ovf && rows_pad % 256 == 0 && gemm_fp16_enabled()) {
-        if (const float* rmax = train_rowmax_take(du, rows_pad, (hipStream_t)stream)) {
-            TrainWideArgs w;
-            w.A = du; w.lda = ldu; w.W1 = (const unsigned short*)((const char*)pack + L.off_WT1); w.K_pad = L.N_pad; w.rows_pad = rows_pad; w.n_cols = L.K_pad;
-            w.row_absmax = rmax; w.C = dx; w.ldc = lddx; w.ovf = (int*)ovf;
-            w.flops = 2.0 * rows_pad * (double)L.N * (double)L.K;
-            launch_train_wide(w, (hipStream_t)stream);
-            return FC_OK;
-        }
-    }
+    if (train_wide_dgrad(L, pack, du, ldu, rows_pad, row_absmax, dx, lddx, nullptr, nullptr, 0, ovf, (hipStream_t)stream)) return FC_OK;
     const PackedLinear P = packed_transposed(L, pack, ovf != nullptr);
     ASeg a{du, ldu};
     GemmEpi e{};
@@ -688,9 +647,9 @@ int fc_train_linear_dgrad_f32(const void* pack, int32_t N, const int32_t* seg_wi
 // gradients consume -- no separate fc_train_act_bwd_f32 pass over the panel (6 % of a C2 training step went into the activation passes).
 // One input segment; u_prev and addend are [rows_pad, lddx] panels like dx.
 int fc_train_linear_dgrad_act_f32(const void* pack, int32_t N, const int32_t* seg_widths, int32_t nseg, const float* du, int32_t ldu, int32_t rows_pad,
-                                  float* dx, int32_t lddx, const float* addend, const float* u_prev, int32_t act, int32_t* ovf, void* stream) {
+                                  float* dx, int32_t lddx, const float* addend, const float* u_prev, int32_t act, const float* row_absmax, int32_t* ovf,
+                                  void* stream) {
     FC_API_BEGIN
-    train_call_tick();
     const TrainLinearLayout L = train_layout(N, seg_widths, nseg);
     if (!pack || rows_pad < 1 || rows_pad % ROW_PAD != 0 || nseg != 1) throw Error(FC_ERR_INVALID, "fc_train_linear_dgrad_act_f32: bad argument (one input segment, rows_pad a multiple of 256)");
     if (act != FC_ACT_GELU && act != FC_ACT_RELU && act != FC_ACT_ELU) throw Error(FC_ERR_INVALID, "fc_train_linear_dgrad_act_f32: act must be GELU, RELU or ELU");
@@ -698,16 +657,7 @@ int fc_train_linear_dgrad_act_f32(const void* pack, int32_t N, const int32_t* se
     check_panel(dx, lddx, L.K_pad, "dx");
     check_panel(u_prev, lddx, L.K_pad, "u_prev");
     if (addend) check_panel(addend, lddx, L.K_pad, "addend");
-    if (g_train_wide && L.wide && ovf && rows_pad % 256 == 0 && act == FC_ACT_GELU && gemm_fp16_enabled()) {
-        if (const float* rmax = train_rowmax_take(du, rows_pad, (hipStream_t)stream)) {
-            TrainWideArgs w;
-            w.A = du; w.lda = ldu; w.W1 = (const unsigned short*)((const char*)pack + L.off_WT1); w.K_pad = L.N_pad; w.rows_pad = rows_pad; w.n_cols = L.K_pad;
-            w.row_absmax = rmax; w.C = dx; w.ldc = lddx; w.addend = addend; w.gradu = u_prev; w.ldgu = lddx; w.gact = act; w.ovf = (int*)ovf;
-            w.flops = 2.0 * rows_pad * (double)L.N * (double)L.K;
-            launch_train_wide(w, (hipStream_t)stream);
-            return FC_OK;
-        }
-    }
+    if (train_wide_dgrad(L, pack, du, ldu, rows_pad, row_absmax, dx, lddx, addend, u_prev, act, ovf, (hipStream_t)stream)) return FC_OK;
     const PackedLinear P = packed_transposed(L, pack, ovf != nullptr);
     ASeg a{du, ldu};
     GemmEpi e{};
@@ -725,7 +675,6 @@ int fc_train_linear_wgrad_f32(int32_t N, const int32_t* seg_widths, int32_t nseg
                               const int32_t* ldx, int32_t rows, float* dW, float* db, int32_t accumulate, void* ws, size_t ws_bytes, int32_t* ovf,
                               void* stream) {
     FC_API_BEGIN
-    train_call_tick();
     const TrainLinearLayout L = train_layout(N, seg_widths, nseg);
     if (!x || !ldx || rows < 1 || (!dW && !db)) throw Error(FC_ERR_INVALID, "fc_train_linear_wgrad_f32: bad argument");
     check_panel(du, ldu, L.N_pad, "du");

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void spline_train_bwd_kernel(const float* __re
         if (!(v.x == v.x && v.y == v.y && v.z == v.z && v.w == v.w)) m = INFINITY;      // (fmaxf drops a NaN: the consumer must see it)
     }
     if (rowmax) {
-        // max |row| for the data-gradient GEMM of the parameter layer (train.hip: train_rowmax_reserve / _take)
+        // max |row| for the data-gradient GEMM of the parameter layer (the caller's buffer, fc_train_rqspline_bwd_f32)
         __shared__ float red[4];
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
@@ -522,10 +522,9 @@ static void spline_fwd_k(const float* x2, int ldx, const float* params, int ldp,
 }
 template <int K>
 static void spline_bwd_k(const float* x2, int ldx, const float* params, int ldp, const float* dy2, int lddy, const float* dldj, float* dx2, int lddx,
-                         float* dparams, int lddp, int rows, int d2, hipStream_t s) {
+                         float* dparams, int lddp, int rows, int d2, float* rowmax, hipStream_t s) {
     // rows beyond `rows` of the row-maximum buffer (the GEMM reads a multiple of 256) are zero: scale 1 on zero rows
     const int rows_pad = round_up(rows, ROW_PAD);
-    float* rowmax = lddp % 64 == 0 ? train_rowmax_reserve(dparams, rows_pad, s) : nullptr;
     if (rowmax && rows_pad > rows) FC_HIP(hipMemsetAsync(rowmax + rows, 0, (size_t)(rows_pad - rows) * 4, s));
     ProfScope ps("fc::spline_train_bwd_kernel", 0.0, (double)rows * d2 * (6 * K + 5) * 4.0, s);
     const size_t lds = (size_t)round_up(d2 * (3 * K + 1), 32) * sizeof(float);
@@ -559,16 +558,17 @@ int fc_train_rqspline_fwd_f32(const float* x2, int32_t ldx, const float* params,
 }
 
 int fc_train_rqspline_bwd_f32(const float* x2, int32_t ldx, const float* params, int32_t ldp, const float* dy2, int32_t lddy, const float* dldj,
-                              float* dx2, int32_t lddx, float* dparams, int32_t lddp, int32_t rows, int32_t d2, int32_t K, void* stream) {
+                              float* dx2, int32_t lddx, float* dparams, int32_t lddp, int32_t rows, int32_t d2, int32_t K, float* row_absmax,
+                              void* stream) {
     FC_API_BEGIN
     if (!x2 || !params || !dy2 || !dldj || !dx2 || !dparams || rows < 1 || d2 < 1 || ldx < d2 || lddy < d2 || lddx < round_up(d2, 32) ||
         ldp < round_up(d2 * (3 * K + 1), 4) || ldp % 4 != 0 || lddp < round_up(d2 * (3 * K + 1), 32) || lddp % 4 != 0 || (((uintptr_t)params | (uintptr_t)dparams) & 15))
         throw Error(FC_ERR_INVALID, "fc_train_rqspline_bwd_f32: bad argument (params / dparams: 16-byte aligned rows, pitches multiples of 4)");
     hipStream_t s = (hipStream_t)stream;
     switch (K) {
-        case 4: spline_bwd_k<4>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, s); break;
-        case 8: spline_bwd_k<8>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, s); break;
-        case 16: spline_bwd_k<16>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, s); break;
+        case 4: spline_bwd_k<4>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, row_absmax, s); break;
+        case 8: spline_bwd_k<8>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, row_absmax, s); break;
+        case 16: spline_bwd_k<16>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, row_absmax, s); break;
         default: throw Error(FC_ERR_UNSUPPORTED, "fc_train_rqspline_bwd_f32: num_bins must be 4, 8 or 16");
     }
     FC_API_END

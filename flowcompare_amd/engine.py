@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FCFLOW_LIB", os.path.join(_HERE, "libfcflow.so"))   # FCFLOW_LIB: A/B another build in profiles/kernel_bench.py
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 FLOW_TYPES = {"AffineCoupling": 0, "RationalQuadraticSplineCoupling": 1, "ExponentialCoupling": 2}
 SCALE_FNS = {"exp": 0, "sigmoid": 1}
@@ -85,6 +85,13 @@ def lib():
         _P, _I = ctypes.c_void_p, ctypes.c_int32
         L.fc_train_expm_wide_bwd_f32.restype = ctypes.c_int
         L.fc_train_expm_wide_bwd_f32.argtypes = [_P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P]
+        # the entries that carry the row maxima of a gradient panel (ABI 10): a miscounted argument fails at the call
+        L.fc_train_rqspline_bwd_f32.restype = ctypes.c_int
+        L.fc_train_rqspline_bwd_f32.argtypes = [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P]
+        L.fc_train_linear_dgrad_f32.restype = ctypes.c_int
+        L.fc_train_linear_dgrad_f32.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]
+        L.fc_train_linear_dgrad_act_f32.restype = ctypes.c_int
+        L.fc_train_linear_dgrad_act_f32.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P]
         if L.fc_abi_version() != ABI_VERSION:
             raise RuntimeError("libfcflow.so ABI version mismatch: rebuild with `python -m flowcompare_amd.build --force`")
         _lib = L

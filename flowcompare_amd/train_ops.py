@@ -111,6 +111,26 @@ def _vec_out(rows_pad, rows, device):
     return t
 
 
+def _attach_rowmax(dparams, rowmax):
+    """Records on the gradient panel `dparams` (as SplineFn.backward returns it) the buffer of its row maxima and the panel's version
+    counter: the tensor object owns its maxima, so a panel that merely lives at a reused address carries none."""
+    dparams._fc_rowmax = (rowmax, dparams._version)
+
+
+def _rowmax_for(du):
+    """The row maxima recorded on `du` if it is still the very panel the spline backward wrote (same tensor object, no in-place edit since:
+    torch's version counter), else None.  A gradient that was accumulated, scaled by a hook or copied is a new tensor without the record;
+    None is always safe: the data gradient then runs on the fp32-A loop."""
+    rec = getattr(du, "_fc_rowmax", None)
+    if rec is None:
+        return None
+    rowmax, version = rec
+    if (du._version != version or du.dim() != 2 or rowmax.shape != (du.shape[0],) or du.dtype != torch.float32
+            or rowmax.dtype != torch.float32 or rowmax.device != du.device):
+        return None
+    return rowmax
+
+
 def _segs(widths):
     return (ctypes.c_int32 * len(widths))(*widths)
 
@@ -187,6 +207,7 @@ class LinearActFn(torch.autograd.Function):
                 engine._check(L.fc_train_act_bwd_f32(engine._ptr(dy), engine._ptr(u), engine._ptr(du), rows_pad, rows, N_pad, act, s))
             else:
                 du = dy
+            rowmax = _rowmax_for(du)
             dW = db = None
             if need[0] or (has_bias and need[1]):
                 nb = L.fc_train_linear_wgrad_ws_bytes(N, segs, len(widths), rows)
@@ -201,7 +222,7 @@ class LinearActFn(torch.autograd.Function):
                 K_pad = sum(_round_up(w, 32) for w in widths)
                 dx = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
                 engine._check(L.fc_train_linear_dgrad_f32(engine._ptr(pack), N, segs, len(widths), engine._ptr(du), N_pad, rows_pad,
-                                                          engine._ptr(dx), K_pad, _flag_ptr(), s))
+                                                          engine._ptr(dx), K_pad, engine._ptr(rowmax), _flag_ptr(), s))
                 off = 0
                 for i, (x, w) in enumerate(zip(xs, widths)):
                     wp = _round_up(w, 32)
@@ -288,6 +309,7 @@ class MlpFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         grads = [None] * (4 + nx + 2 * nl)
         du = dy.contiguous()                                             # out_layer has no activation
+        rowmax = _rowmax_for(du)                                         # row maxima of the incoming panel: the last layer's data gradient alone
         du_next = None                                                   # du of layer l + 1 (the residual branch's gradient when l is an even hidden layer)
         with _OnDevice(dev):
             s = engine._stream()
@@ -312,7 +334,7 @@ class MlpFn(torch.autograd.Function):
                         K_pad = sum(_round_up(w, 32) for w in in_w)
                         dx = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
                         engine._check(L.fc_train_linear_dgrad_f32(engine._ptr(packs[0]), N, segs, len(in_w), engine._ptr(du), N_pad, rows_pad,
-                                                                  engine._ptr(dx), K_pad, _flag_ptr(), s))
+                                                                  engine._ptr(dx), K_pad, engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s))
                         off = 0
                         for i, (x, w) in enumerate(zip(xs, in_w)):
                             wp = _round_up(w, 32)
@@ -330,7 +352,7 @@ class MlpFn(torch.autograd.Function):
                 du_prev = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
                 engine._check(L.fc_train_linear_dgrad_act_f32(engine._ptr(packs[l]), N, segs, 1, engine._ptr(du), N_pad, rows_pad,
                                                               engine._ptr(du_prev), K_pad, engine._ptr(addend), engine._ptr(us[l - 1]), act,
-                                                              _flag_ptr(), s))
+                                                              engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s))
                 du_next, du = du, du_prev
         return tuple(grads)
 
@@ -456,10 +478,14 @@ class SplineFn(torch.autograd.Function):
         dx2 = _panel_out(x2.shape[0], x2.shape[1], rows, x2.device) if x2.shape[1] == _round_up(d2, 32) else torch.zeros_like(x2)
         dparams = (_panel_out(params.shape[0], params.shape[1], rows, x2.device) if params.shape[1] == _round_up(d2 * (3 * K + 1), 32)
                    else torch.zeros_like(params))
+        # max |row| of dparams for the data gradient of the layer that made `params` (one-accumulator loop: pitches in multiples of 64)
+        rowmax = torch.empty(_round_up(rows, ROW_PAD), dtype=torch.float32, device=x2.device) if dparams.shape[1] % 64 == 0 else None
         with _OnDevice(x2.device):
             engine._check(L.fc_train_rqspline_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(params), params.shape[1], engine._ptr(dy2),
                                                       dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(dparams),
-                                                      dparams.shape[1], rows, d2, K, engine._stream()))
+                                                      dparams.shape[1], rows, d2, K, engine._ptr(rowmax), engine._stream()))
+        if rowmax is not None:
+            _attach_rowmax(dparams, rowmax)                       # after the call: _panel_out's zero_() of the pad rows counts as an edit
         return dx2, dparams, None, None, None
 
 

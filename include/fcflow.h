@@ -24,6 +24,8 @@
  * 6 = + fc_profile_stride (sampled bracketing of the in-library kernel timing), fc_train_linear_act_fwd_f32 / fc_train_linear_dgrad_act_f32 (activation and its backward in the GEMM epilogues).
  * 8 = + fc_op_expm_action_f32; ExponentialCoupling up to d2 = 256 (inference, training forward).
  * 9 = + fc_flow_attention_weights_f32 / fc_op_attention_weights_f32: the cross-attention softmax rows of selected target points.
+ * 10 = row_absmax argument of fc_train_rqspline_bwd_f32 (writes it), fc_train_linear_dgrad_f32 and fc_train_linear_dgrad_act_f32 (read it):
+ *      the row maxima of a gradient panel travel in a buffer of the caller's, the library keeps no training state between calls.
  */
 #ifndef FCFLOW_H
 #define FCFLOW_H
@@ -35,7 +37,7 @@
 extern "C" {
 #endif
 
-#define FC_ABI_VERSION 9
+#define FC_ABI_VERSION 10
 
 enum fc_status {
     FC_OK = 0,
@@ -323,14 +325,22 @@ int fc_train_linear_fwd_f32(const void* pack, int32_t N, const int32_t* seg_widt
 int fc_train_linear_act_fwd_f32(const void* pack, int32_t N, const int32_t* seg_widths, int32_t nseg, const float* const* x, const int32_t* ldx,
                                 int32_t rows_pad, const float* residual, int32_t ldr, float* u, float* y, int32_t ldu, int32_t act, int32_t* ovf,
                                 void* stream);
-/* dx [rows_pad, lddx >= sum of padded segment widths] = du W  (columns in padded-segment order). */
+/* dx [rows_pad, lddx >= sum of padded segment widths] = du W  (columns in padded-segment order).
+ * row_absmax (may be NULL; ABI v10): the caller's device buffer of rows_pad floats, entry r >= max |du[r, :]| (+inf for a row with a NaN),
+ * complete on `stream` before this call and describing du as it is NOW -- what fc_train_rqspline_bwd_f32 wrote beside the panel it
+ * produced, as long as nobody has written to the panel since.  Only read.  With it a layer of at least 1024 outputs (one input segment,
+ * padded widths multiples of 64, ovf non-NULL) runs on the 256 x 256 one-accumulator loop, every row of du scaled by an exact power of two;
+ * an entry below the true maximum raises ovf, one above it costs gradient precision.  NULL, or a layer that is not eligible (the pointer
+ * is then ignored): the fp32-A loop. */
 int fc_train_linear_dgrad_f32(const void* pack, int32_t N, const int32_t* seg_widths, int32_t nseg, const float* du, int32_t ldu,
-                              int32_t rows_pad, float* dx, int32_t lddx, int32_t* ovf, void* stream);
+                              int32_t rows_pad, float* dx, int32_t lddx, const float* row_absmax, int32_t* ovf, void* stream);
 /* Data gradient of a hidden Linear fused with the backward of the activation in front of it:
  * dx = (du . W + addend) * act'(u_prev), i.e. the gradient w.r.t. the previous layer's PRE-activation (addend: optional gradient of a
- * residual branch that joins at the previous layer's output; u_prev / addend / dx are [rows_pad, lddx] panels; one input segment).  ABI v6. */
+ * residual branch that joins at the previous layer's output; u_prev / addend / dx are [rows_pad, lddx] panels; one input segment).  ABI v6.
+ * row_absmax (may be NULL; ABI v10): as for fc_train_linear_dgrad_f32; the one-accumulator loop also needs act == FC_ACT_GELU. */
 int fc_train_linear_dgrad_act_f32(const void* pack, int32_t N, const int32_t* seg_widths, int32_t nseg, const float* du, int32_t ldu, int32_t rows_pad,
-                                  float* dx, int32_t lddx, const float* addend, const float* u_prev, int32_t act, int32_t* ovf, void* stream);
+                                  float* dx, int32_t lddx, const float* addend, const float* u_prev, int32_t act, const float* row_absmax,
+                                  int32_t* ovf, void* stream);
 size_t fc_train_linear_wgrad_ws_bytes(int32_t N, const int32_t* seg_widths, int32_t nseg, int32_t rows);
 /* dW [N,K] (=|+=) du[:rows]^T cat(x...)[:rows],  db [N] (=|+=) column sums of du[:rows]; either may be NULL.  fp32-input MFMA,
  * fixed summation order (bit-reproducible).  ws: 256-byte aligned scratch of fc_train_linear_wgrad_ws_bytes. */
@@ -359,11 +369,16 @@ int fc_train_attention_bwd_f32(const float* q, int32_t ldq, const float* k, int3
 
 /* Rational-quadratic spline coupling element in the reference's parameter layout (models/spline_coupling.py:187-210: the coupling
  * MLP's output row is [d2][K width | K height | K+1 derivative logits]), forward (y2, ldj[row] = sum over dims of log|dy/dx|) and
- * the analytic backward w.r.t. x2 and every logit.  Pad columns of y2 / dx2 / dparams are written as zeros. */
+ * the analytic backward w.r.t. x2 and every logit.  Pad columns of y2 / dx2 / dparams are written as zeros.
+ * bwd, row_absmax (may be NULL; ABI v10): the caller's device buffer of round_up(rows, 256) floats.  The kernel writes entry r =
+ * max |dparams[r, :]| over the columns it writes (+inf if the row holds a NaN) for r < rows while it still holds the row, and the entry
+ * zeroes the rest on `stream`.  The caller owns the buffer and keeps it with the panel: it is what fc_train_linear_dgrad_f32 /
+ * fc_train_linear_dgrad_act_f32 take for du = dparams, valid until the panel is written to again. */
 int fc_train_rqspline_fwd_f32(const float* x2, int32_t ldx, const float* params, int32_t ldp, float* y2, int32_t ldy, float* ldj, int32_t rows,
                               int32_t d2, int32_t K, void* stream);
 int fc_train_rqspline_bwd_f32(const float* x2, int32_t ldx, const float* params, int32_t ldp, const float* dy2, int32_t lddy, const float* dldj,
-                              float* dx2, int32_t lddx, float* dparams, int32_t lddp, int32_t rows, int32_t d2, int32_t K, void* stream);
+                              float* dx2, int32_t lddx, float* dparams, int32_t lddp, int32_t rows, int32_t d2, int32_t K, float* row_absmax,
+                              void* stream);
 /* torch.nn.LayerNorm(width) of PreNorm (models/perceiver.py:18-27).  stats [2*rows] = (mean, rstd) per row, kept for the backward;
  * bwd writes dx and the panel dy*xhat, whose column sums are d gamma (d beta = column sums of dy): fc_train_colsum_f32. */
 int fc_train_layernorm_fwd_f32(const float* x, int32_t ldx, const float* gamma, const float* beta, float* y, int32_t ldy, float* stats,

@@ -119,7 +119,7 @@ def test_header_declares_the_entry_and_engine_exports_it():
     header = open(os.path.join(ROOT, "include", "fcflow.h")).read()
     assert re.search(r"\bint\s+fc_train_expm_wide_bwd_f32\s*\(", header)
     assert "fc_train_expm_wide_bwd_f32" in engine.EXPORTS
-    assert re.search(r"FC_ABI_VERSION\s+9\b", header) and engine.ABI_VERSION == 9
+    assert re.search(r"FC_ABI_VERSION\s+10\b", header) and engine.ABI_VERSION == 10
 
 
 @pytest.mark.parametrize("d2", [33, 150])

@@ -258,6 +258,107 @@ def test_spline_parameter_layer_on_the_wide_loop_matches_fp64_and_the_fp32a_loop
         assert wide[k] < 2.0 * base[k] + 2e-6, (k, wide[k], base[k])
 
 
+def _spline_layer_step(hook=None, wide=True):
+    """One forward + backward of the coupling net MLP(214, [512, 512], 3750) + spline (K 8, d1 = d2 = 150, 300 rows, rows_pad 512, gradients
+    of order one) under step_guard with the in-library profile on; `hook` is registered on the MLP's output panel.  Returns (launches of
+    the 256 x 256 one-accumulator kernel, range flag, [a.grad, b.grad, xx.grad, every MLP parameter's gradient])."""
+    from flowcompare_amd import engine
+    L = engine.lib()
+    K, d1, d2, rows = 8, 150, 150, 300
+    torch.manual_seed(11)
+    mlp = M.MLP(d1 + 64, [512, 512], d2 * (3 * K + 1)).to(DEV)
+    with torch.no_grad():
+        mlp.out_layer.weight.mul_(0.5)
+    g = torch.Generator().manual_seed(rows)
+    x1, c = torch.randn(rows, d1, generator=g), torch.randn(rows, 64, generator=g)
+    x2 = torch.rand(rows, d2, generator=g) * 7 - 3.5
+    gy, gl = torch.randn(rows, d2, generator=g), torch.randn(rows, generator=g)
+    a, b, xx = x1.to(DEV).requires_grad_(True), c.to(DEV).requires_grad_(True), x2.to(DEV).requires_grad_(True)
+    try:
+        assert L.fc_debug_set(31, 1 if wide else 0) == 0
+        engine.profile_enable(True); engine.profile_stride(1); engine.profile_reset()
+        with T.step_guard(device=DEV) as guard:
+            pp = T.mlp_panels(mlp, [T.to_panel(a), T.to_panel(b)], [d1, 64], rows, "GELU")
+            if hook is not None:
+                pp.register_hook(hook)
+            yp, ldj = T.rq_spline(T.to_panel(xx), pp, rows, d2, K)
+            ((T.from_panel(yp, rows, d2) * gy.to(DEV)).sum() + (ldj[:rows] * gl.to(DEV)).sum()).backward()
+            overflowed = guard.overflowed()
+        launches = sum(r["launches"] for r in engine.profile_report() if r["kernel"].startswith("void fc::spline_wide_kernel<3,"))
+    finally:
+        engine.profile_enable(False); engine.profile_stride(1); engine.profile_reset()
+        L.fc_debug_set(31, 1)
+    return launches, overflowed, [a.grad, b.grad, xx.grad] + [q.grad for q in mlp.parameters()]
+
+
+def test_spline_row_maxima_reach_the_parameter_layers_data_gradient():
+    """The handoff is visible: SplineFn.backward records the row maxima on the gradient panel it returns, MlpFn.backward finds them on
+    its incoming panel and the out layer's data gradient runs on the one-accumulator loop -- 2 launches of that kernel per step (the out
+    layer's forward and its data gradient), none with knob 31 = 0."""
+    launches, overflowed, _ = _spline_layer_step()
+    launches0, overflowed0, _ = _spline_layer_step(wide=False)
+    print(f"one-accumulator launches per step: {launches} (knob 31 = 0: {launches0}), range flag {overflowed} / {overflowed0}")
+    assert launches == 2 and not overflowed
+    assert launches0 == 0 and not overflowed0
+
+
+def test_an_edited_gradient_panel_is_not_paired_with_stale_row_maxima():
+    """A hook that scales the MLP output's gradient IN PLACE leaves the panel object -- and the record on it -- in place, but bumps its version
+    counter: the lookup misses and the data gradient runs on the fp32-A loop (1 one-accumulator launch, the forward), on the same operands
+    as with a hook that returns a new tensor (which never carried a record): every gradient bit for bit the same."""
+    n_in, ovf_in, g_in = _spline_layer_step(hook=lambda g: g.mul_(1000.0))
+    n_new, ovf_new, g_new = _spline_layer_step(hook=lambda g: g * 1000.0)
+    print(f"one-accumulator launches per step: in-place hook {n_in}, new-tensor hook {n_new}; range flag {ovf_in} / {ovf_new}; "
+          f"gradients equal: {[torch.equal(p, q) for p, q in zip(g_in, g_new)]}")
+    assert n_in == 1 and not ovf_in
+    assert n_new == 1 and not ovf_new
+    assert len(g_in) == len(g_new) == 9
+    for p, q in zip(g_in, g_new):
+        assert torch.equal(p, q)
+
+
+def test_spline_backward_writes_the_row_maxima_into_the_callers_buffer():
+    """fc_train_rqspline_bwd_f32 with an explicit row_absmax buffer (K 8, d2 150, 300 rows, the inputs of the spline test above): entry r is
+    max |dparams[r, :]| exactly (a maximum does not round), the tail up to rows_pad is zeroed, a row with a NaN (through dldj) reads +inf;
+    with a NULL buffer dx2 and dparams come out bit for bit the same."""
+    from flowcompare_amd import engine
+    L = engine.lib()
+    K, d2, rows = 8, 150, 300
+    g = torch.Generator().manual_seed(K + d2)
+    x = torch.rand(rows, d2, generator=g) * 8 - 4
+    x[0, :3] = torch.tensor([-3.0, 3.0, 0.0])
+    p = torch.randn(rows, d2, 3 * K + 1, generator=g) * 0.5
+    gy, gl = torch.randn(rows, d2, generator=g), torch.randn(rows, generator=g)
+    x2, params, dy2 = T.to_panel(x.to(DEV)), T.to_panel(p.reshape(rows, -1).to(DEV)), T.to_panel(gy.to(DEV))
+    rows_pad = x2.shape[0]
+    assert rows_pad == 512 and params.shape[1] % 64 == 0
+
+    def bwd(dldj, with_buffer=True):
+        dx2 = T._panel_out(rows_pad, x2.shape[1], rows, DEV)
+        dparams = T._panel_out(rows_pad, params.shape[1], rows, DEV)
+        rowmax = torch.full((rows_pad,), -1.0, device=DEV) if with_buffer else None
+        engine._check(L.fc_train_rqspline_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(params), params.shape[1], engine._ptr(dy2), dy2.shape[1],
+                                                  engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(dparams), dparams.shape[1],
+                                                  rows, d2, K, engine._ptr(rowmax), engine._stream()))
+        torch.cuda.synchronize()
+        return dx2, dparams, rowmax
+    dldj = torch.zeros(rows_pad, device=DEV)
+    dldj[:rows] = gl.to(DEV)
+    dx2, dparams, rowmax = bwd(dldj)
+    assert torch.equal(rowmax[:rows], dparams[:rows].abs().amax(1))
+    assert rowmax[:rows].min().item() > 0.0
+    assert torch.equal(rowmax[rows:], torch.zeros(rows_pad - rows, device=DEV))
+    dx2_0, dparams_0, _ = bwd(dldj, with_buffer=False)
+    assert torch.equal(dx2_0, dx2) and torch.equal(dparams_0, dparams)
+    bad = dldj.clone()
+    bad[7] = float("nan")
+    _, dparams_n, rowmax_n = bwd(bad)
+    assert torch.isnan(dparams_n[7]).any()
+    assert rowmax_n[7].item() == float("inf")
+    keep = torch.arange(rows, device=DEV) != 7
+    assert torch.equal(rowmax_n[:rows][keep], rowmax[:rows][keep]) and torch.equal(rowmax_n[rows:], rowmax[rows:])
+
+
 @pytest.mark.parametrize("rows,width", [(300, 256), (1000, 8), (5, 100)])
 def test_layernorm_forward_and_backward_match_fp64(rows, width):
     g = torch.Generator().manual_seed(rows)

@@ -51,7 +51,7 @@ def test_layer_ids_of_the_fixture_prefixes():
 
 def test_host_surface():
     assert callable(fa.attention_weights) and "attention_weights" in fa.__all__
-    assert engine.ABI_VERSION == 9
+    assert engine.ABI_VERSION == 10
     assert "fc_flow_attention_weights_f32" in engine.EXPORTS and "fc_op_attention_weights_f32" in engine.EXPORTS
     assert hasattr(engine.FlowHandle, "attention_weights") and callable(engine.op_attention_weights)
 

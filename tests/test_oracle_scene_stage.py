@@ -54,7 +54,7 @@ def test_host_surface():
     header = open(os.path.join(ROOT, "include", "fcflow.h")).read()
     for name in NEW_EXPORTS:
         assert name in engine.EXPORTS and re.search(r"\b%s\s*\(" % name, header), name
-    assert engine.ABI_VERSION == 9 and "#define FC_ABI_VERSION 9" in header
+    assert engine.ABI_VERSION == 10 and "#define FC_ABI_VERSION 10" in header
     for name in ("voxel_centers", "voxel_counts", "voxel_rows", "fps_ragged", "stage_scene"):
         assert callable(getattr(staging, name)), name
     assert callable(fa.scene_change) and "scene_change" in fa.__all__

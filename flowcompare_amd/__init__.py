@@ -5,6 +5,6 @@ library (libfcflow.so, include/fcflow.h).  There is no PyTorch/CPU fallback: eve
 the HIP library is missing.
 """
 from .config import config_loader, named_config  # noqa: F401
-from .model_initialization import initialize_flow, inner_loop, make_sample, save_flow, load_flow, attention_weights, scene_change  # noqa: F401
+from .model_initialization import initialize_flow, inner_loop, make_sample, save_flow, load_flow, attention_weights, scene_change, dense_log_prob  # noqa: F401
 
-__all__ = ["config_loader", "named_config", "initialize_flow", "inner_loop", "make_sample", "save_flow", "load_flow", "attention_weights", "scene_change"]
+__all__ = ["config_loader", "named_config", "initialize_flow", "inner_loop", "make_sample", "save_flow", "load_flow", "attention_weights", "scene_change", "dense_log_prob"]

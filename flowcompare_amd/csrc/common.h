@@ -310,6 +310,8 @@ void launch_co_unit_sphere(const float* p0, int n0, const float* p1, int n1, int
 void launch_clamp_infs(float* t, long n, float* stats4, int* status, hipStream_t s);
 void launch_change_map(float* lp10, int N, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff, int use_cutoff,
                        float* stats4, int* status, hipStream_t s);
+void launch_change_map_ragged(float* lp10, const int64_t* offsets, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff,
+                              int use_cutoff, float* stats4, int* status, hipStream_t s);
 void launch_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out, int ldo,
                       int B, int N, int n_stride_rows, int M, int m_stride_rows, int dh_pad, void* limb_ws, hipStream_t s);
 bool attention_fp16_enabled();

@@ -320,6 +320,21 @@ int fc_change_map_f32(float* lp10, int32_t N, float* lp00, int32_t N0, float* ou
     FC_API_END
 }
 
+int fc_change_map_ragged_f32(float* lp10, const int64_t* offsets, float* lp00, int32_t N0, float* out, int32_t B, float multiple, float hard_cutoff,
+                             int32_t use_cutoff, int32_t* invalid, void* stream) {
+    FC_API_BEGIN
+    if (!lp10 || !offsets || !lp00 || !out || !invalid) throw fc::Error(FC_ERR_INVALID, "fc_change_map_ragged_f32: null pointer");
+    fc::TmpBuf tmp(4 * sizeof(float) + sizeof(int));
+    int* status = (int*)(tmp.f() + 4);
+    fc::launch_change_map_ragged(lp10, offsets, lp00, N0, out, B, multiple, hard_cutoff, use_cutoff, tmp.f(), status, (hipStream_t)stream);
+    int h = 0;
+    FC_HIP(hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    FC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    if (h & 2) throw fc::Error(FC_ERR_INVALID, "fc_change_map_ragged_f32: offsets are not an ascending prefix sum of row counts below 2^31");
+    *invalid = h & 1;
+    FC_API_END
+}
+
 int fc_op_expm_action_f32(const float* params, int32_t ldp, const float* x2, int32_t ldx, const float* scal4, float* y2, int32_t ldy, float* ldj,
                           float* info, int32_t rows, int32_t d2, int32_t inverse, void* stream) {
     FC_API_BEGIN

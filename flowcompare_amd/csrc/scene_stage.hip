@@ -247,6 +247,59 @@ void launch_fps_ragged(const float* cloud, int ld, int C, long P, const int64_t*
     FC_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------- dense blocks: ALL members of the staged voxels
+// Block b of the i-th listed voxel holds its members b * block ... min((b + 1) * block, count) - 1 in the list's ascending order, xyz as
+// (x - mean) / furthest_distance with co_unit_sphere_kernel's operations (staging.hip), the other columns as they are.  A slot of a
+// voxel's last block beyond its count repeats the voxel's FIRST member (a real point: nothing downstream sees garbage) with index -1.
+// One workgroup per block; the number of blocks is block_offsets[n_voxels] on the device, so a launch of fixed width strides over the
+// blocks and the host needs neither that number nor a synchronisation.  Member rows ascend, so a block's gather walks forward through the
+// cloud; consecutive threads take consecutive floats of `out`.  Nothing is accumulated: the same input gives the same bytes.
+constexpr int kDenseThreads = 256, kDenseGrid = 4096;
+
+__global__ __launch_bounds__(kDenseThreads) void dense_blocks_kernel(const float* __restrict__ cloud, int ld, int C, int P, const int64_t* __restrict__ offsets,
+                                                                     const int32_t* __restrict__ rows, const int32_t* __restrict__ voxel_ids, int n_voxels,
+                                                                     const float* __restrict__ inverse, const int64_t* __restrict__ block_offsets, int block,
+                                                                     float* __restrict__ out, int64_t* __restrict__ index, int32_t* __restrict__ block_voxel) {
+    const int64_t n_blocks = block_offsets[n_voxels];
+    for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        int lo = 0, hi = n_voxels;                            // the last i with block_offsets[i] <= b: voxels without blocks are stepped over
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (block_offsets[mid] <= b) lo = mid; else hi = mid;
+        }
+        const int i = lo;
+        const int v = voxel_ids ? voxel_ids[i] : i;
+        const int64_t off = offsets[v], count = offsets[v + 1] - off;
+        const int64_t first = (b - block_offsets[i]) * block;
+        if (count < 1 || first >= count) continue;            // block_offsets that do not belong to this list; uniform over the workgroup
+        const float far = inverse[4 * (size_t)i], mx = inverse[4 * (size_t)i + 1], my = inverse[4 * (size_t)i + 2], mz = inverse[4 * (size_t)i + 3];
+        const int32_t* vr = rows + off;
+        float* ob = out + (size_t)b * block * C;
+        for (int e = threadIdx.x; e < block * C; e += kDenseThreads) {
+            const int slot = e / C, col = e - slot * C;
+            const bool member = first + slot < count;
+            const int r = min(max(vr[member ? first + slot : 0], 0), P - 1);       // clamped: a bad list cannot read outside the cloud
+            const float x = cloud[(size_t)r * ld + col];
+            ob[e] = col == 0 ? (x - mx) / far : col == 1 ? (x - my) / far : col == 2 ? (x - mz) / far : x;
+            if (col == 0) index[(size_t)b * block + slot] = member ? (int64_t)r : (int64_t)-1;
+        }
+        if (threadIdx.x == 0) block_voxel[b] = i;
+    }
+}
+
+void launch_dense_blocks(const float* cloud, int ld, int C, long P, const int64_t* offsets, const int32_t* rows, const int32_t* voxel_ids, int n_voxels,
+                         const float* inverse, const int64_t* block_offsets, int block, float* out, int64_t* index, int32_t* block_voxel, hipStream_t s) {
+    if (n_voxels <= 0) return;
+    if (!cloud || !offsets || !rows || !inverse || !block_offsets || !out || !index || !block_voxel) throw Error(FC_ERR_INVALID, "dense blocks: null pointer");
+    if (C < 3 || C > 8 || ld < C) throw Error(FC_ERR_UNSUPPORTED, "dense blocks: 3..8 columns supported (xyz first)");
+    if (P < 1 || P > 0x7fffffffL) throw Error(FC_ERR_INVALID, "dense blocks: bad cloud size");
+    if (block < 1 || (long)block * C > 0x7fffffffL) throw Error(FC_ERR_INVALID, "dense blocks: bad block size");
+    ProfScope ps("fc::dense_blocks_kernel", 0.0, 0.0, s);     // the traffic depends on block_offsets, which the host does not read
+    hipLaunchKernelGGL(dense_blocks_kernel, dim3(kDenseGrid), dim3(kDenseThreads), 0, s, cloud, ld, C, (int)P, offsets, rows, voxel_ids, n_voxels, inverse,
+                       block_offsets, block, out, index, block_voxel);
+    FC_HIP(hipGetLastError());
+}
+
 }  // namespace fc
 
 extern "C" {
@@ -272,6 +325,16 @@ int fc_stage_fps_ragged_f32(const float* cloud, int32_t ld, int32_t C, int64_t P
     FC_API_BEGIN
     if (n_voxels < 0 || m < 1) throw fc::Error(FC_ERR_INVALID, "fc_stage_fps_ragged_f32: bad argument");
     fc::launch_fps_ragged(cloud, ld, C, (long)P, offsets, rows, voxel_ids, n_voxels, max_rows, m, idx, dist_scratch, (hipStream_t)stream);
+    FC_API_END
+}
+
+int fc_stage_dense_blocks_f32(const float* cloud, int32_t ld, int32_t C, int64_t P, const int64_t* offsets, const int32_t* rows, const int32_t* voxel_ids,
+                              int32_t n_voxels, const float* inverse, const int64_t* block_offsets, int32_t block, float* out, int64_t* index,
+                              int32_t* block_voxel, void* stream) {
+    FC_API_BEGIN
+    if (n_voxels < 0) throw fc::Error(FC_ERR_INVALID, "fc_stage_dense_blocks_f32: bad argument");
+    fc::launch_dense_blocks(cloud, ld, C, (long)P, offsets, rows, voxel_ids, n_voxels, inverse, block_offsets, block, out, index, block_voxel,
+                            (hipStream_t)stream);
     FC_API_END
 }
 

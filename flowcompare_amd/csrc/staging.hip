@@ -169,13 +169,12 @@ __global__ void change_init_kernel(float* stats4, int* status) {
 // One workgroup per scene.  lp10 / lp00 are clamped IN PLACE when their tensor held an inf (the reference's clamp_infs mutates
 // its argument).  out = 1 - (lp10 - min)/(max - min) where lp10 < mean(lp00) - multiple * std(lp00) (unbiased) or < hard_cutoff,
 // else 0.  status[0] is raised when a result is NaN / inf (the reference asserts is_valid).
-__global__ __launch_bounds__(256) void change_map_kernel(float* __restrict__ lp10, int N, float* __restrict__ lp00, int N0, float* __restrict__ out,
-                                                         const float* __restrict__ st10, const float* __restrict__ st00, float multiple,
-                                                         float hard_cutoff, int use_cutoff, int* __restrict__ status) {
-    __shared__ float red[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    float* r1 = lp10 + (size_t)b * N;
-    float* r0 = lp00 + (size_t)b * N0;
+// change_map_rows is one scene: r1 / o its N rows of lp10 / out, r0 its N0 rows of lp00.  Both kernels below run it, so a scene's
+// arithmetic and summation order do not depend on how its rows were found.
+__device__ __forceinline__ void change_map_rows(float* __restrict__ r1, int N, float* __restrict__ r0, int N0, float* __restrict__ o,
+                                                const float* __restrict__ st10, const float* __restrict__ st00, float multiple, float hard_cutoff,
+                                                int use_cutoff, int* __restrict__ status, float* red) {
+    const int tid = threadIdx.x;
     const bool c1 = st10[1] != 0.f, c0 = st00[1] != 0.f;
     const float m1 = st10[0], m0 = st00[0];
     float thr = hard_cutoff;
@@ -208,11 +207,47 @@ __global__ __launch_bounds__(256) void change_map_kernel(float* __restrict__ lp1
     for (int k = tid; k < N; k += 256) {
         const float v = r1[k];
         const float scaled = 1.0f - (v - mn) / (mx - mn);
-        const float o = v < thr ? scaled : 0.0f;
-        bad |= !(fabsf(o) <= FLT_MAX);
-        out[(size_t)b * N + k] = o;
+        const float out = v < thr ? scaled : 0.0f;
+        bad |= !(fabsf(out) <= FLT_MAX);
+        o[k] = out;
     }
     if (bad) atomicOr(status, 1);
+}
+
+__global__ __launch_bounds__(256) void change_map_kernel(float* __restrict__ lp10, int N, float* __restrict__ lp00, int N0, float* __restrict__ out,
+                                                         const float* __restrict__ st10, const float* __restrict__ st00, float multiple,
+                                                         float hard_cutoff, int use_cutoff, int* __restrict__ status) {
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    change_map_rows(lp10 + (size_t)b * N, N, lp00 + (size_t)b * N0, N0, out + (size_t)b * N, st10, st00, multiple, hard_cutoff, use_cutoff, status, red);
+}
+
+// Voxels of different sizes: voxel k owns rows [offsets[k], offsets[k + 1]) of the flat lp10 / out and row k of
+// lp00 [B, N0].  A voxel without rows writes nothing to `out` (its lp00 row is still clamped: that rule is the tensor's).
+__global__ __launch_bounds__(256) void change_map_ragged_kernel(float* __restrict__ lp10, const int64_t* __restrict__ offsets, float* __restrict__ lp00,
+                                                                int N0, float* __restrict__ out, const float* __restrict__ st10,
+                                                                const float* __restrict__ st00, float multiple, float hard_cutoff, int use_cutoff,
+                                                                int* __restrict__ status) {
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const int64_t off = offsets[b], n = offsets[b + 1] - off;
+    if (n < 0 || n > 0x7fffffff) { if (threadIdx.x == 0) atomicOr(status, 2); return; }        // not a prefix sum; uniform over the workgroup
+    change_map_rows(lp10 + off, (int)n, lp00 + (size_t)b * N0, N0, out + off, st10, st00, multiple, hard_cutoff, use_cutoff, status, red);
+}
+
+// inf_stats_kernel over t[0 .. *n_dev): the length of the flat tensor is the last offset, which the host does not read
+__global__ __launch_bounds__(256) void inf_stats_devn_kernel(const float* __restrict__ t, const int64_t* __restrict__ n_dev, float* __restrict__ stats) {
+    __shared__ float red[4];
+    const long n = (long)*n_dev;
+    float mn = INFINITY;
+    bool inf = false;
+    for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < n; k += (long)gridDim.x * 256) {
+        const float v = t[k];
+        if (isinf(v)) inf = true; else mn = fminf(mn, v);
+    }
+    const float bm = block_min(mn, red);
+    if (threadIdx.x == 0 && bm < INFINITY) atomic_min_float(stats, bm);
+    if (__syncthreads_or(inf) && threadIdx.x == 0) stats[1] = 1.0f;
 }
 
 __global__ __launch_bounds__(256) void clamp_infs_kernel(float* __restrict__ t, long n, const float* __restrict__ stats) {
@@ -242,6 +277,19 @@ void launch_change_map(float* lp10, int N, float* lp00, int N0, float* out, int 
     hipLaunchKernelGGL(inf_stats_kernel, dim3((unsigned)std::min<long>((n0 + 255) / 256, 1024)), dim3(256), 0, s, lp00, n0, stats4 + 2);
     hipLaunchKernelGGL(change_map_kernel, dim3(B), dim3(256), 0, s, lp10, N, lp00, N0, out, stats4, stats4 + 2, multiple, hard_cutoff, use_cutoff,
                        status);
+    FC_HIP(hipGetLastError());
+}
+
+void launch_change_map_ragged(float* lp10, const int64_t* offsets, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff,
+                              int use_cutoff, float* stats4, int* status, hipStream_t s) {
+    if (B <= 0 || N0 <= 0) throw Error(FC_ERR_INVALID, "ragged change map: empty input");
+    hipLaunchKernelGGL(change_init_kernel, dim3(1), dim3(64), 0, s, stats4, status);
+    ProfScope ps("fc::change_map_ragged_kernel", 0.0, 0.0, s);                 // the row count is offsets[B], on the device
+    const long n0 = (long)B * N0;
+    hipLaunchKernelGGL(inf_stats_devn_kernel, dim3(1024), dim3(256), 0, s, lp10, offsets + B, stats4);
+    hipLaunchKernelGGL(inf_stats_kernel, dim3((unsigned)std::min<long>((n0 + 255) / 256, 1024)), dim3(256), 0, s, lp00, n0, stats4 + 2);
+    hipLaunchKernelGGL(change_map_ragged_kernel, dim3(B), dim3(256), 0, s, lp10, offsets, lp00, N0, out, stats4, stats4 + 2, multiple, hard_cutoff,
+                       use_cutoff, status);
     FC_HIP(hipGetLastError());
 }
 

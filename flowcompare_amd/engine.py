@@ -41,6 +41,7 @@ EXPORTS = [
     "fc_op_paconv_knn_f32", "fc_train_paconv_group_f32", "fc_train_softmax_fwd_f32", "fc_train_softmax_bwd_f32", "fc_train_assign_fwd_f32", "fc_train_assign_bwd_f32",
     "fc_train_centerdiff_fwd_f32", "fc_train_centerdiff_bwd_f32", "fc_train_rows_gather_bwd_f32", "fc_train_three_nn_f32", "fc_train_interp_fwd_f32",
     "fc_train_sqnorm_ws_bytes", "fc_train_sqnorm_f32", "fc_train_adam_f32",
+    "fc_stage_dense_blocks_f32", "fc_change_map_ragged_f32",
 ]
 
 
@@ -508,6 +509,22 @@ def stage_fps_ragged(cloud, offsets, rows, m, max_rows, voxel_ids=None):
     return idx
 
 
+def stage_dense_blocks(cloud, offsets, rows, inverse, block_offsets, n_blocks, block, voxel_ids=None):
+    """(blocks [n_blocks, block, C] fp32, index [n_blocks, block] int64, block_voxel [n_blocks] int32): all members of the listed voxels of
+    a CSR list (offsets int64, rows int32) in blocks, normalised with inverse [n_voxels, 4] (fc_stage_dense_blocks_f32).  block_offsets
+    [n_voxels + 1] int64 on the device; n_blocks = its last entry, which sizes the outputs."""
+    n_vox = inverse.shape[0]
+    C = cloud.shape[1]
+    blocks = torch.empty(n_blocks, block, C, dtype=torch.float32, device=cloud.device)
+    index = torch.empty(n_blocks, block, dtype=torch.int64, device=cloud.device)
+    block_voxel = torch.empty(n_blocks, dtype=torch.int32, device=cloud.device)
+    if n_blocks:
+        with torch.cuda.device(cloud.device):
+            _check(lib().fc_stage_dense_blocks_f32(_ptr(cloud), C, C, ctypes.c_int64(cloud.shape[0]), _ptr(offsets), _ptr(rows), _ptr(voxel_ids), n_vox,
+                                                   _ptr(inverse), _ptr(block_offsets), int(block), _ptr(blocks), _ptr(index), _ptr(block_voxel), _stream()))
+    return blocks, index, block_voxel
+
+
 def clamp_infs(t):
     """fc_clamp_infs_f32 in place on a contiguous fp32 device tensor."""
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
@@ -531,6 +548,29 @@ def change_map(lp10, lp00, multiple, hard_cutoff=None):
         _check(lib().fc_change_map_f32(_ptr(lp10), N, _ptr(lp00), lp00.shape[1], _ptr(out), B, ctypes.c_float(multiple),
                                        ctypes.c_float(0.0 if hard_cutoff is None else hard_cutoff), 0 if hard_cutoff is None else 1,
                                        ctypes.byref(bad), _stream()))
+    return out, bool(bad.value)
+
+
+def change_map_ragged(lp10, offsets, lp00, multiple, hard_cutoff=None):
+    """fc_change_map_ragged_f32: lp10 flat [offsets[-1]], offsets [B + 1] int64, lp00 [B, N0], contiguous device tensors (clamped in place);
+    returns (out flat, invalid flag)."""
+    for t, dt, nd in ((lp10, torch.float32, 1), (lp00, torch.float32, 2), (offsets, torch.int64, 1)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == nd):
+            raise RuntimeError("change_map_ragged: expects contiguous float32 lp10 [total] / lp00 [B, N0] and int64 offsets [B + 1] on the GPU "
+                               "(flowcompare_amd has no CPU fallback)")
+    B = lp00.shape[0]
+    if offsets.numel() != B + 1:
+        raise RuntimeError("change_map_ragged: offsets must have one entry more than lp00 has rows")
+    if B < 1 or not bool((offsets[0] == 0) & (offsets[-1] == lp10.numel()) & (offsets[1:] >= offsets[:-1]).all()):
+        raise RuntimeError("change_map_ragged: offsets must ascend from 0 to the length of lp10, one voxel at least")
+    out = torch.empty_like(lp10)
+    if lp10.numel() == 0:                                  # no voxel has a row: nothing to scale
+        return out, False
+    bad = ctypes.c_int32(0)
+    with torch.cuda.device(lp10.device):
+        _check(lib().fc_change_map_ragged_f32(_ptr(lp10), _ptr(offsets), _ptr(lp00), lp00.shape[1], _ptr(out), B, ctypes.c_float(multiple),
+                                              ctypes.c_float(0.0 if hard_cutoff is None else hard_cutoff), 0 if hard_cutoff is None else 1,
+                                              ctypes.byref(bad), _stream()))
     return out, bool(bad.value)
 
 

@@ -207,8 +207,56 @@ def attention_weights(batch, models_dict, config, layers=("aug",), points=None, 
                                                  return_log_prob=return_log_prob)
 
 
+def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None):
+    """Log-probs of ALL members of the staged voxels against their voxel's staged context: st = the SceneStage (context st.extract_0,
+    st.extra_context), dense = staging.stage_dense(...) of the same voxels.  In eval mode a target point's log-likelihood depends on
+    that point, the context and the point's own augmenter noise only, so any member can be scored, not just
+    the FPS sample.  The embedder runs once per staged voxel (chunks of blocks_per_batch voxels); every batch of blocks_per_batch blocks
+    is one flow.log_prob with the blocks' voxels' embeddings / extra context gathered by index_select and expanded over the block as
+    inner_loop does.  eps: None draws per batch as inner_loop does; otherwise one tensor [total, width_i] per noise site of the flow
+    (flow.noise_shapes) in CSR row order -- pad slots get zeros.  Returns flat [total] log-probs in CSR order (dense.offsets /
+    dense.rows); pad slots are dropped.  Eval mode, under torch.no_grad(); the batch is taken as given under config['data_parallel']."""
+    if not (torch.is_tensor(st.extract_0) and st.extract_0.is_cuda and torch.is_tensor(dense.blocks) and dense.blocks.is_cuda):
+        raise RuntimeError("dense_log_prob: expects a SceneStage and a DenseStage on the GPU (flowcompare_amd has no CPU fallback)")
+    flow, embedder = models_dict["flow"], models_dict["input_embedder"]
+    if flow.training or embedder.training:
+        raise RuntimeError("dense_log_prob is eval-mode only (train-mode statistics couple the rows of a batch): call .eval() first")
+    blocks_per_batch = int(blocks_per_batch)
+    if blocks_per_batch < 1:
+        raise RuntimeError("dense_log_prob: blocks_per_batch must be at least 1")
+    K1, (n_blocks, block), Din = st.extract_0.shape[0], dense.index.shape, config["input_dim"]
+    if dense.offsets.numel() != K1 + 1:
+        raise RuntimeError(f"dense_log_prob: the DenseStage lists {dense.offsets.numel() - 1} voxels, the SceneStage staged {K1}")
+    member = dense.index.reshape(-1) >= 0
+    if eps is not None:
+        widths = [s[2] for s in flow.noise_shapes(1, 1)]
+        total = dense.rows.numel()
+        if len(eps) != len(widths) or any(not e.is_cuda or tuple(e.shape) != (total, w) for e, w in zip(eps, widths)):
+            raise RuntimeError(f"dense_log_prob: eps must be one GPU tensor [{total}, width] per noise site, widths {widths}")
+        csr_pos = (torch.cumsum(member, 0) - 1).clamp_(min=0)                     # CSR position of every slot (pads: any valid row, zeroed below)
+    out = torch.empty(n_blocks, block, dtype=torch.float32, device=dense.blocks.device)
+    with torch.no_grad():
+        if n_blocks:
+            emb = torch.cat([embedder(st.extract_0[a:a + blocks_per_batch, :, :Din]) for a in range(0, K1, blocks_per_batch)])
+        for a in range(0, n_blocks, blocks_per_batch):
+            b = min(a + blocks_per_batch, n_blocks)
+            voxel = dense.block_voxel[a:b].long()
+            context = emb.index_select(0, voxel)
+            if config["global"]:
+                context = context[:, None, :].expand(-1, block, -1)
+            extra = None
+            if config.get("using_extra_context"):
+                extra = st.extra_context.index_select(0, voxel)[:, None, :].expand(-1, block, -1)
+            noise = None
+            if eps is not None:
+                sl = slice(a * block, b * block)
+                noise = [torch.where(member[sl, None], e.index_select(0, csr_pos[sl]), e.new_zeros(())).reshape(b - a, block, -1) for e in eps]
+            out[a:b] = flow.log_prob(dense.blocks[a:b, :, :Din], context=context, extra_context=extra, eps=noise)
+    return out.reshape(-1)[member]
+
+
 def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=None, multiple=5.4, hard_cutoff=None, voxels_per_batch=16,
-                 final_voxel_size=None, context_voxel_size=None):
+                 final_voxel_size=None, context_voxel_size=None, dense=False, block=None):
     """test_flow.py:151-166 for a whole scene, one direction: the change of cloud_1 [P1, C] given cloud_0 [P0, C] at the voxel centres
     `centers` [K, 3].  Sample counts are config['sample_size'] / config['n_samples_context'] as the reference's loader takes them
     (test_flow.py:141-143); the box sizes default to the config's 'final_voxel_size' / 'context_voxel_size'.  Evaluated are the centres
@@ -217,7 +265,15 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
     (0 | 0) batch takes the extra context of the (1 | 0) batch.  log_prob_to_change acts per chunk: its clamp_infs takes the minimum
     over the tensor it is given, i.e. per chunk here exactly as per loader batch in the reference.  Returns (change [P1], the (1 | 0)
     SceneStage with `voxel` / counts referring to `centers`): NaN where a point was not evaluated, the larger value where two voxels
-    share a sampled point.  The augmenter noise is drawn as inner_loop draws it: seed torch's device generator for a reproducible map."""
+    share a sampled point.  The augmenter noise is drawn as inner_loop draws it: seed torch's device generator for a reproducible map.
+
+    dense=True scores EVERY point of cloud_1 inside an evaluated voxel, not only the FPS sample.  Validity,
+    both stagings, the context, the normalisation, the extra context and the sampled (0 | 0) baseline (chunks of voxels_per_batch) stay
+    as above; (1 | 0) is dense_log_prob over all members of the final box in blocks of `block` rows (default config['sample_size'],
+    voxels_per_batch blocks per flow call), and ONE log_prob_to_change_ragged call covers the scene: min / max scaling over all of a
+    voxel's members, threshold from its sampled (0 | 0) row.  Unlike the sampled mode, whose clamp_infs acts per chunk, the dense mode's
+    clamp_infs acts over the whole scene's tensor.  Every point inside an evaluated voxel comes back finite (the larger value where boxes
+    share a face), points of voxels that fail the validity mask stay NaN, and the returned SceneStage carries the DenseStage as `.dense`."""
     from . import change as change_ops
     from . import staging
     fin = config.get("final_voxel_size") if final_voxel_size is None else final_voxel_size
@@ -235,6 +291,20 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
     st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height)
     assert st10.voxel.numel() == st00.voxel.numel() == both.numel()
     out = torch.full((cloud_1.shape[0],), float("nan"), dtype=torch.float32, device=cloud_1.device)
+    if dense:
+        st10.dense = staging.stage_dense(cloud_1, st10, fin, sel, N if block is None else block)
+        if both.numel():
+            lp_1_0 = dense_log_prob(st10, st10.dense, models_dict, config, blocks_per_batch=voxels_per_batch)
+            lp_0_0 = []
+            with torch.no_grad():
+                for a in range(0, both.numel(), voxels_per_batch):
+                    sl = slice(a, a + voxels_per_batch)
+                    extra = st10.extra_context[sl] if config.get("using_extra_context") else None
+                    lp_0_0.append(inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config)[1])
+            change = change_ops.log_prob_to_change_ragged(lp_1_0, st10.dense.offsets, torch.cat(lp_0_0), multiple, hard_cutoff)
+            out.scatter_reduce_(0, st10.dense.rows, change, "amax", include_self=False)
+        st10.voxel, st10.count_0, st10.count_1 = both, c0_ctx, c1_fin
+        return out, st10
     chunks = []
     with torch.no_grad():
         for a in range(0, both.numel(), voxels_per_batch):

@@ -194,3 +194,49 @@ def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size,
     extra = None if ground_height is None else (inverse['mean'][:, 2] - ground_height).unsqueeze(-1)
     return SceneStage(extract_0=o0, extract_1=o1, extra_context=extra, inverse=inverse, index_0=index_0, index_1=index_1, voxel=voxel,
                       count_0=count_0, count_1=count_1)
+
+
+# ---------------------------------------------------------------- every member of the staged voxels (csrc/scene_stage.hip)
+class DenseStage:
+    """What `stage_dense` returns: ALL members of the K' staged voxels, packed into blocks of `block` rows.
+    blocks [n_blocks, block, C] (normalised like the sample), index [n_blocks, block] int64 (row of the cloud, -1 in pad slots),
+    block_voxel [n_blocks] int32 (which staged voxel), offsets [K' + 1] / rows [total] int64 (the CSR member lists of the staged voxels),
+    block_offsets [K' + 1] int64 (first block of every voxel), block.  Masking a per-slot result with `index >= 0` leaves it in CSR order."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def stage_dense(cloud, st, final_voxel_size, centers, block):
+    """All members of every voxel that `st` (a SceneStage of stage_scene(..., cloud, centers, final_voxel_size, ...)) staged, as
+    engine-shaped batches: voxel i = centre centers[st.voxel[i]] owns ceil(count / block) consecutive blocks holding its member rows of
+    `cloud` in ascending order, xyz normalised with the SAMPLE's mean and furthest_distance (st.inverse) by the operations of
+    co_unit_sphere, other columns as they are.  A member that is also an FPS pick has the same bits as in st.extract_1.  The slots of a
+    voxel's last block beyond its count repeat the voxel's first member (index -1).  furthest_distance comes from the sample, so dense
+    points can lie slightly OUTSIDE the unit ball.  The member lists are voxel_rows'; one read-back sizes the blocks.  Returns a
+    DenseStage; for an empty `st` its tensors are empty and nothing is launched."""
+    _cloud_and_centers("stage_dense", cloud, centers)
+    block = int(block)
+    if block < 1:
+        raise RuntimeError(f"stage_dense: block must be at least 1, got {block}")
+    K1, dev, C = st.voxel.numel(), cloud.device, cloud.shape[1]
+    if st.count_1.numel() != centers.shape[0] or st.extract_1.shape[0] != K1 or st.inverse["mean"].shape[0] != K1 or st.extract_1.shape[2] != C:
+        raise RuntimeError(f"stage_dense: the SceneStage does not belong to these centres: it counted {st.count_1.numel()} centres and staged "
+                           f"{st.extract_1.shape[0]} voxels of {st.extract_1.shape[2]} columns, given are {centers.shape[0]} centres and {C} columns")
+    i64 = dict(dtype=torch.int64, device=dev)
+    if K1 == 0:
+        return DenseStage(blocks=torch.zeros(0, block, C, dtype=torch.float32, device=dev), index=torch.zeros(0, block, **i64),
+                          block_voxel=torch.zeros(0, dtype=torch.int32, device=dev), offsets=torch.zeros(1, **i64), rows=torch.zeros(0, **i64),
+                          block_offsets=torch.zeros(1, **i64), block=block)
+    sel = centers.index_select(0, st.voxel).contiguous()
+    counts, offsets, rows32 = _rows("stage_dense", cloud, sel, final_voxel_size)
+    block_offsets = torch.zeros(K1 + 1, **i64)
+    torch.cumsum((counts.long() + (block - 1)) // block, 0, out=block_offsets[1:])
+    same = (counts == st.count_1.index_select(0, st.voxel)).all()
+    n_blocks, same = torch.stack((block_offsets[-1], same.long())).tolist()       # the one read-back: sizes the blocks
+    if not same:
+        raise RuntimeError("stage_dense: the voxels' member counts differ from the SceneStage's count_1: another cloud, centres or box size")
+    inverse = torch.cat((st.inverse["furthest_distance"].reshape(K1, 1), st.inverse["mean"].reshape(K1, 3)), 1).contiguous()
+    blocks, index, block_voxel = engine.stage_dense_blocks(cloud, offsets, rows32, inverse, block_offsets, n_blocks, block)
+    return DenseStage(blocks=blocks, index=index, block_voxel=block_voxel, offsets=offsets, rows=rows32.long(), block_offsets=block_offsets,
+                      block=block)

@@ -481,6 +481,31 @@ int fc_train_sqnorm_f32(const float* g, int64_t n, double* out, int32_t slot, vo
 int fc_train_adam_f32(float* const* params, const int64_t* offsets, const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t n_chunks, const float* g,
                       float* m, float* v, const float* coef, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream);
 
+/* ---- dense change maps: every member of a staged voxel, not only its FPS sample ----------------------
+ * Additions after everything above: FC_ABI_VERSION stays 10, nothing declared before changes.
+ *
+ * All members of the listed voxels as blocks of `block` rows.  offsets / rows are CSR member lists as fc_stage_voxel_select_f32 writes
+ * them; voxel i of the list is voxel_ids[i] (or i when voxel_ids is NULL), i < n_voxels; inverse [n_voxels, 4] = furthest_distance,
+ * mean x, y, z per listed voxel (fc_stage_co_unit_sphere_f32's layout); block_offsets [n_voxels + 1] (device) = exclusive prefix of
+ * ceil(count_i / block), so n_blocks = block_offsets[n_voxels].  Block b of voxel i holds its members b * block ...
+ * min((b + 1) * block, count) - 1 in the list's ascending order: out [n_blocks, block, C] with xyz = (x - mean) / furthest_distance
+ * (fp32, a true division: the operations of fc_stage_co_unit_sphere_f32, so a member that is also an FPS pick has the bits it has in
+ * the staged sample) and columns 3 .. C - 1 as they are; index [n_blocks, block] = the row of `cloud`; block_voxel [n_blocks] = i.
+ * A slot of a voxel's last block beyond its count is a copy of the voxel's FIRST member, normalised like it, with index -1: a real
+ * point whose result is computed and thrown away.  Caller-owned buffers, no allocation, no synchronisation, no atomics, the same
+ * input gives the same bytes; one launch for the whole list; C = 3 .. 8, ld >= C, P < 2^31. */
+int fc_stage_dense_blocks_f32(const float* cloud, int32_t ld, int32_t C, int64_t P, const int64_t* offsets, const int32_t* rows,
+                              const int32_t* voxel_ids, int32_t n_voxels, const float* inverse, const int64_t* block_offsets, int32_t block,
+                              float* out, int64_t* index, int32_t* block_voxel, void* stream);
+/* fc_change_map_f32 for voxels of different sizes: lp10 / out are flat [offsets[B]], voxel k owns [offsets[k], offsets[k + 1])
+ * (offsets [B + 1] on the device, ascending); lp00 [B, N0] is the sampled self evaluation.  Same rules, arithmetic and summation
+ * order per voxel as fc_change_map_f32 (with offsets[k] = k * N the output is the same bit for bit): infs of each tensor -> that
+ * tensor's smallest non-inf IN PLACE, threshold mean - multiple * std of the voxel's lp00 row (unbiased) or hard_cutoff, 1 - (lp - min)
+ * / (max - min) over the voxel's own lp10 rows, 0 elsewhere.  A voxel without rows writes nothing.  *invalid as for
+ * fc_change_map_f32.  Synchronises the stream. */
+int fc_change_map_ragged_f32(float* lp10, const int64_t* offsets, float* lp00, int32_t N0, float* out, int32_t B, float multiple,
+                             float hard_cutoff, int32_t use_cutoff, int32_t* invalid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,9 +21,6 @@ namespace fc {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-int g_attn_fp16 = 1;      // tuning knob (fc_debug_set 5): 0 keeps the fp32-input MFMA kernel
-bool attention_fp16_enabled() { return g_attn_fp16 != 0; }
-
 struct AttnParams {
     const float* q; int ldq;
     const float* k; int ldk;
@@ -539,7 +536,7 @@ static void launch_attention_scaled(const float* q, int ldq, const float* k, int
     if ((ldq | ldk | ldv) % 4 != 0 || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15))
         throw Error(FC_ERR_INVALID, "attention: q/k/v must be 16-byte aligned with pitches that are multiples of 4 floats");
     int* flag = gemm_fp16_flag();
-    if (flag && limb_ws && dh_pad <= 64 && g_attn_fp16) {
+    if (flag && limb_ws && dh_pad <= 64 && g_knobs.attn_fp16) {      // (knob 5)
         // split-fp16 path (needs the caller's Fp16Guard scope for its range check and limb_ws for the K/V limb images)
         const long rows = (long)(B - 1) * m_stride_rows + M;
         unsigned short* k16 = (unsigned short*)limb_ws;

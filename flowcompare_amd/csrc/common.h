@@ -11,6 +11,7 @@
 #include <functional>
 
 #include "../../include/fcflow.h"
+#include "knobs.h"
 
 namespace fc {
 
@@ -110,7 +111,7 @@ struct PackedLinear {
                                    // [round_up(N_pad, 256)][K_pad/16][2][16]: w 2^w1_exp = hi + lo with lo UNSCALED, rows in that kernel's column order
     float* bias1 = nullptr;        // its bias in the same order, times kOneAccActScale 2^w1_exp
     int w1_exp = 0;
-    bool w1_folded = false;        // ... and folded to 22 parameters per dim on 112-column wave tiles (spline_wide.hip, knob 34)
+    bool w1_folded = false;        // ... and folded to 22 parameters per dim on 112-column wave tiles (spline_wide.hip; spline_fold, knob 34)
     bool w1_permuted = false;      // W1 rows in the fused spline kernel's register-slot order (else natural order: a Linear layer of the coupling MLP)
     float wmax = 0.f;              // max |w| of the packed matrix (pack_linear)
     int N_pad = 0;             // columns written (multiple of 32)
@@ -164,7 +165,7 @@ struct GemmEpi {
     const float* eps = nullptr; int d_in = 0, d1 = 0, d1_pad = 0;   // AUGMENT: latent index = d_in + q ; x1|x2 split
     float clamp = 0.f;         // AUGMENT/SLICE: std clamp (0 = none)
     int inverse = 0;           // AFFINE: x2 = (y2 - t) / (s*g), no log-det ; AUGMENT: sample only (no log-det)
-    int prefetch_dist = 0;     // SPLINE (persistent kernel): != 0 rotates each tile's k loop by a column-tile dependent offset (launch_gemm fills it from knob 21)
+    int prefetch_dist = 0;     // SPLINE (persistent kernel): != 0 rotates each tile's k loop by a column-tile dependent offset (launch_gemm fills it from spline_prefetch, knob 21)
     int split = 1 << 30, split_pad = 0;   // AFFINE: transformed dim j lives at column x2_col0 + (j < split ? j : split_pad + j - split)
     const float* post_scale = nullptr;    // AFFINE: optional per-dim factor g folded behind s (CIF: ActNorm of the x part)
     const float* val = nullptr; int ldval = 0;             // SLICE: values whose log N(.; mu, sigma) is ADDED to logprob
@@ -283,9 +284,7 @@ void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStre
 void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);
 bool linear_wide_eligible(const PackedLinear& L, const GemmEpi& e, int rows_alloc);   // a GELU Linear layer with one-accumulator images in and out
 void launch_linear_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);
-bool gemm_linear_wide_on();      // knob 29 (1: for scenes of at least 2048 target points, 2: at any size)
-int gemm_linear_wide_knob();
-bool gemm_spline_wide_on();      // knob 13 = 5 (shipped): launch_gemm routes eligible EPI_SPLINE launches there
+bool gemm_spline_wide_on();      // spline_kernel (knob 13) = 5 (shipped): launch_gemm routes eligible EPI_SPLINE launches there
 // the same 256 x 256 main loop for the wide Linear layers of a TRAINING step (train.hip: the spline parameter layer's forward and its data
 // gradient): the point operand is an fp32 panel, split into limbs after its LDS read; C = (A W^T + bias (+ addend)) (* act'(gradu))
 constexpr int kTrainWideWExp = 11;         // weights of those layers are stored as hi + lo of w 2^11 (|w| < 32; the pack kernel raises the range flag beyond)
@@ -302,8 +301,7 @@ struct TrainWideArgs {
     int* ovf = nullptr;
     double flops = 0.0;
 };
-void launch_train_wide(const TrainWideArgs& a, hipStream_t s);
-extern int g_train_wide;         // knob 31: 1 = training Linear layers with at least 1024 outputs run on it (shipped), 0 = on the fp32-A 128 x 128 loop
+void launch_train_wide(const TrainWideArgs& a, hipStream_t s);      // train_wide (knob 31) routes training Linear layers with at least 1024 outputs here
 // staging.hip: the steps either side of the path
 void launch_fps_nd(const float* pts, int ld, int C, int64_t* idx, int B, int n, int m, float* dist_scratch, hipStream_t s);
 void launch_co_unit_sphere(const float* p0, int n0, const float* p1, int n1, int ld, float* o0, float* o1, float* inverse, int B, hipStream_t s);
@@ -314,7 +312,6 @@ void launch_change_map_ragged(float* lp10, const int64_t* offsets, float* lp00, 
                               int use_cutoff, float* stats4, int* status, hipStream_t s);
 void launch_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out, int ldo,
                       int B, int N, int n_stride_rows, int M, int m_stride_rows, int dh_pad, void* limb_ws, hipStream_t s);
-bool attention_fp16_enabled();
 // un-normalised q of the LayerNorm -> q fold: the attention kernel finishes it (rstd from the per-row sums of squares, bias) on load
 struct AttnLnq { const float* sumsq; int slots; size_t pitch; float inv_width; const float* bias; };
 void launch_attention_c16(const float* q, int ldq, const unsigned short* kv_c16, int n_pad, int col0, float* out, int ldo, int B, int N,

@@ -98,10 +98,6 @@ struct fc_flow {
 
 namespace fc {
 
-int g_spline_fold = 1;       // knob 34, read when a flow is created: 1 = the wide spline kernel's image holds the 22 informative parameters per dim on
-                             // 112-column wave tiles (shipped), 0 = all 25 on 128-column tiles
-int g_kv_fold = 1;           // knob 33, read when a flow is created: 1 = fold to_kv away where the gate allows it (shipped), 0 = stacked K|V projection
-
 // The K|V fold keeps every weight shape only when the context embedding is as wide as the attention's inner dimension (every shipped
 // configuration: 64 = 64), and the algebra above has no place for a bias on to_q / to_kv (the reference has none, models/perceiver.py:89-95).
 // The attention kernels then read the context panel (pitch E_pad = E rounded up to 32) as I_pad-column keys and values, so the two padded
@@ -117,7 +113,7 @@ bool kv_fold_gate_dims(int E, int inner, bool q_bias, bool kv_bias) {
     return E > 0 && E == inner && inner <= 128 && round_up(E, 32) == pad_inner(inner) && !q_bias && !kv_bias;
 }
 static bool kv_fold_gate(const fc_flow_config& c, const WeightTable& wt, const std::vector<std::string>& attn_prefixes) {
-    if (!g_kv_fold || attn_prefixes.empty()) return false;
+    if (!g_knobs.kv_fold || attn_prefixes.empty()) return false;      // (knob 33)
     for (const std::string& p : attn_prefixes) {
         const HostTensor& wq = wt.get(p + ".fn.attention.to_q.weight");
         if (wq.shape.size() != 2 || !kv_fold_gate_dims(c.input_embedding_dim, (int)wq.shape[0], wt.has(p + ".fn.attention.to_q.bias"),
@@ -367,11 +363,11 @@ static void build_out_layer(fc_flow& f, const WeightTable& wt, const std::string
     if (f.cfg.flow_type == FC_FLOW_SPLINE && f.cfg.num_bins_spline == 8) {
         // the one-accumulator image of the 256 x 256 fused spline kernel (spline_wide.hip): rows in that kernel's register-slot order, pre-scaled by
         // the power of two that puts max |w| into [2^14, 2^15).
-        // Folded (knob 34): softmax is shift-invariant and the reference never reads derivative logit 8 (models/spline_coupling.py:24-66: F.pad, then
+        // Folded (spline_fold, knob 34): softmax is shift-invariant and the reference never reads derivative logit 8 (models/spline_coupling.py:24-66: F.pad, then
         // both end entries overwritten), so only 22 of a dim's 25 parameters carry information: width and height rows i < 7 become W_i - W_7 with
         // b_i - b_7, rows 7 / 15 / 24 of every dim leave the image.  The subtraction is made in double from the checkpoint's values (the image
         // kernel, from the fp32 pack that holds them exactly); the scale is taken HERE over the same folded rows.  W / W2 / W3 / bias keep all 25.
-        const bool fold = g_spline_fold != 0;
+        const bool fold = g_knobs.spline_fold != 0;      // (knob 34)
         float wmax = 0.f;
         const int hk = (int)w.shape[1];
         for (int r = 0; r < n; ++r) {
@@ -658,14 +654,12 @@ thread_local float* t_expm_info = nullptr;      // fc_debug_expm_info: per-point
 thread_local size_t t_expm_info_floats = 0;
 void flow_set_expm_info(float* buf, size_t floats) { t_expm_info = buf; t_expm_info_floats = floats; }
 
-int g_premlp_chain = 0;      // knob 19: limb chain through the pre-attention MLP into the LayerNorm -> q GEMM (K = 256: 8 k-tiles per
-                             // output tile, the tile-boundary cost of the DMA loop outweighs its main loop: measured 1 % slower end to end)
 static int run_mlp_hidden(const fc_flow& f, const PackedMLP& m, const ASeg* in_segs, const float* rowscal, FlowWs& w, int act, hipStream_t s,
                           unsigned short* last_limbs = nullptr, float last_scale = 0.f, int n_scene = 0) {
     // round 4: hidden layers of a 512-wide coupling net on the 256 x 256 one-accumulator kernel (spline_wide.hip EPI 1).  The gate is the SCENE's
     // size (target points per scene), never the batch's: a scene's log-probs must not depend on the batch it sits in, and this arithmetic
     // (one accumulator, k32 MFMAs) is not the per-layer 128 x 128 / 64 x 64 loops' or the row-resident chain's.
-    const int wk = gemm_linear_wide_knob();
+    const int wk = g_knobs.linear_wide;      // (knob 29)
     if (last_limbs && f.d.H_pad == 512 && gemm_limb_chain_all_ok() && act == FC_ACT_GELU && (wk == 2 || (wk == 1 && n_scene >= 2048)) && w.P_pad % 256 == 0 && !m.mid.empty()) {
         bool ok = true;
         for (const PackedLinear& L : m.mid) ok = ok && L.W1 && !L.w1_permuted && L.N_pad % 256 == 0 && L.K_pad % 64 == 0;
@@ -737,7 +731,7 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
         if (lu) throw Error(FC_ERR_INVALID, "run_attention: a pending ActNorm + LU pre-layer needs the row-resident pre-attention kernel");
         // limb chain through the pre-attention MLP into the LayerNorm -> q GEMM (every hidden activation as a limb image, DMA loops)
         const PackedLinear& pre_last = pre.mid.empty() ? pre.in_layer : pre.mid.back();
-        const bool chain = g_premlp_chain && at.has_lnq && gemm_lnq_ok() && gemm_limb_chain_all_ok() && w.h16 && !pre.mid.empty() && at.lnq.W2 != nullptr &&
+        const bool chain = g_knobs.premlp_chain && at.has_lnq && gemm_lnq_ok() && gemm_limb_chain_all_ok() && w.h16 && !pre.mid.empty() && at.lnq.W2 != nullptr &&
                            pre_last.W2 != nullptr && pre_last.N_pad == at.lnq.K_pad && pre_last.N_pad % 128 == 0 && at.lnq.nseg == 1;
         const int cur = run_mlp_hidden(f, pre, &in, nullptr, w, act, s, chain ? w.h16 : nullptr);
         if (at.has_lnq && gemm_lnq_ok()) {
@@ -895,15 +889,15 @@ static Prep prepare(fc_flow& f, const float* ctx, const float* extra, int B, int
     if (d.X) { launch_repeat_extra(extra, d.X, w.rowscal, B, N, s); p.rowscal = w.rowscal; }
     if (f.n_attn && f.kv_fold) {
         // keys = values = the context panel: one limb image per forward for the split-fp16 attention (range flag as the projection's epilogue
-        // raised it); the fp32-input attention (knob 5 = 0, the bf16-limb repeat of a pass) reads the panel itself
-        if (gemm_fp16_flag() && attention_fp16_enabled() && d.I_pad <= 64) {
+        // raised it); the fp32-input attention (attn_fp16, knob 5, = 0; the bf16-limb repeat of a pass) reads the panel itself
+        if (gemm_fp16_flag() && g_knobs.attn_fp16 && d.I_pad <= 64) {
             launch_context_limbs(w.ctxp, d.E_pad, reinterpret_cast<unsigned short*>(w.kv16), w.Pc, d.I_pad, s);
             w.ctx16 = reinterpret_cast<const unsigned short*>(w.kv16);
         }
     } else if (f.n_attn) {
         // inside a guard scope the stacked K|V projection writes its output straight as the limb image the split-fp16 attention
         // stages (same bytes, same buffer): no fp32 K/V, no per-layer conversion pass
-        w.kv_limbs = gemm_limb_chain_ok() && attention_fp16_enabled() && d.I_pad <= 64 && f.kv_all.W2 != nullptr && w.ldkv % 128 == 0 && w.ldkv == f.kv_all.N_pad;
+        w.kv_limbs = gemm_limb_chain_ok() && g_knobs.attn_fp16 && d.I_pad <= 64 && f.kv_all.W2 != nullptr && w.ldkv % 128 == 0 && w.ldkv == f.kv_all.N_pad;
         GemmEpi e{};
         e.rows_valid = w.Pc;
         if (w.kv_limbs) { e.C16 = reinterpret_cast<unsigned short*>(w.kv); e.c16_scale = kOneAccActScale; }      // (the one-accumulator image the attention kernel multiplies)

@@ -51,14 +51,15 @@ struct GemmParams {
     int N_pad;
     int nbm, nbn;
     int col_group;      // > 0: row-band / column-group tile order for weight matrices that do not fit L2
-    unsigned long long* stamps;   // diagnostic knob 20: 16 x u64 per workgroup (s_memtime at the phase boundaries, HW_ID, wall clock); null otherwise
+    unsigned long long* stamps;   // diagnostic stamps (knob 20): 16 x u64 per workgroup (s_memtime at the phase boundaries, HW_ID, wall clock); null otherwise
+    int ablate;         // diagnostic spline_ablate (knob 14), results invalid: 1 = no spline evaluation, 2 = main loop only, 3 = no parameter-tile write, 4 = no x2 store, 5 = stop behind the tile write; 0 otherwise
     GemmEpi e;
 };
 
 
 constexpr int LDS_LD = 36;   // floats per LDS row (32 + 4 pad)
 
-// In-kernel phase stamps of the LDS-DMA kernels (diagnostic knob 20; profiles/micro/spline_gemm_stamps.py): thread 0 of a workgroup stores
+// In-kernel phase stamps of the LDS-DMA kernels (diagnostic stamps, knob 20; profiles/micro/spline_gemm_stamps.py): thread 0 of a workgroup stores
 // the shader-clock counter.  Slot 0 entry, 1 prologue issued, 2 first k tile landed, 3 main loop done, 4 epilogue operands ready (LDS tile
 // written / register exchange done), 5 splines evaluated, 6 results stored, 7 HW_ID | XCC_ID << 32, 8 / 9 wall clock (100 MHz) at entry / exit.
 #define FC_STAMP(K_)                                                                                                 \
@@ -568,7 +569,7 @@ void gemm_f32_kernel(const GemmParams p) {
     // ------------------------------------------------------------------ epilogues
     // C/D layout of the 32x32 MFMA: column = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5), r = 0..15
     if constexpr (EPI == EPI_LINEAR) {
-        if (VAR == 9 && e.inverse == 2) return;        // (diagnostic knob 14 = 2: main loop only, results invalid)
+        if (VAR == 9 && p.ablate == 2) return;         // (diagnostic spline_ablate, knob 14, = 2: main loop only, results invalid)
         if constexpr (RES_EARLY) {
             if (e.residual16 && nvalid > 0) {
 #pragma unroll
@@ -721,10 +722,10 @@ void gemm_f32_kernel(const GemmParams p) {
         //      [rows, 25*d2] parameter matrix is written to or re-read from HBM.
         static_assert(BN == 128, "spline epilogue: the column layout is built for 128-column tiles");
         constexpr int TP = BN + 1;                                   // odd pitch: lanes walk rows conflict-free
-        if (e.inverse == 2) return;                                  // (diagnostic knob 14: main loop only)
+        if (p.ablate == 2) return;                                   // (diagnostic knob 14: main loop only)
         float* tile = smem;                                          // aliases the staging buffers (all reads are behind the loop's last barrier)
         float* part = smem + BM * TP;                                // [DPT][BM] log-det terms
-        if (e.inverse != 3) {                                        // (diagnostic knob 14 = 3: no parameter-tile write)
+        if (p.ablate != 3) {                                         // (diagnostic knob 14 = 3: no parameter-tile write)
         int tpos[TN];                                                // column -> (dim, parameter) position (K = 8: spline.h's slot order)
 #pragma unroll
         for (int j = 0; j < TN; ++j) tpos[j] = spline_tile_pos(wc * TN * 32 + j * 32 + li, e.spline_K);
@@ -738,7 +739,7 @@ void gemm_f32_kernel(const GemmParams p) {
         } else { asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[TM - 1][TN - 1][15])); }
         __syncthreads();
         if constexpr (VAR == 9) FC_STAMP(4)
-        if (e.inverse == 5) return;                                  // (diagnostic knob 14 = 5: main loop + parameter-tile write + barrier)
+        if (p.ablate == 5) return;                                   // (diagnostic knob 14 = 5: main loop + parameter-tile write + barrier)
         const int K = e.spline_K, per = 3 * K + 1, DPT = BN / per;
         const int dim0 = bn * DPT;
         if (DPT == 5) {
@@ -749,9 +750,9 @@ void gemm_f32_kernel(const GemmParams p) {
                     float lad = 0.f;
                     if (dim0 + dl < e.d2 && m0 + row < e.rows_valid) {
                         float y;
-                        if (e.inverse == 1) { y = spl_x[k] + tile[row * TP + dl * per]; lad = tile[row * TP + dl * per + 1]; }   // (diagnostic knob 14: no spline evaluation)
+                        if (p.ablate == 1) { y = spl_x[k] + tile[row * TP + dl * per]; lad = tile[row * TP + dl * per + 1]; }    // (diagnostic knob 14: no spline evaluation)
                         else rq_spline_fwd<8>(spl_x[k], tile + row * TP + dl * per, 1, y, lad);        // DPT == 5 <=> K == 8
-                        if (e.inverse != 4) e.xbuf[(size_t)(m0 + row) * e.ldx + e.x2_col0 + dim0 + dl] = y;      // (diagnostic knob 14 = 4: no x2 store)
+                        if (p.ablate != 4) e.xbuf[(size_t)(m0 + row) * e.ldx + e.x2_col0 + dim0 + dl] = y;       // (diagnostic knob 14 = 4: no x2 store)
                         else asm volatile("" :: "v"(y));
                     }
                     part[dl * BM + row] = lad;
@@ -882,7 +883,7 @@ void gemm_f32_kernel(const GemmParams p) {
 // holds, per lane, 64 parameters of ONE point (the other 64 sit in lane ^ 32).  With the column order of spline.h that is every parameter
 // of 2-3 transformed dims in registers with compile-time indices: the spline is evaluated straight from the accumulators, the tile never
 // goes through LDS (no 66 KB parameter tile, no transposition, no epilogue barrier).  Persistent because with one tile per workgroup the
-// tile boundary is expensive: the in-kernel stamps (knob 20, profiles/micro/spline_gemm_stamps.py) priced it at 6.5 of a workgroup's 25.5 us
+// tile boundary is expensive: the in-kernel stamps (stamps, knob 20, profiles/micro/spline_gemm_stamps.py) priced it at 6.5 of a workgroup's 25.5 us
 // per tile: 2.6 us from entry until the first k tile has landed, 0.8 us between a workgroup's exit and its successor's entry, 3.1 us of
 // epilogue during which the slot fetches nothing.
 //   * grid = 2 workgroups per CU, each walks tiles t = blockIdx.x, + gridDim.x, ... (the XCD-aware order of the one-tile-per-workgroup
@@ -1067,7 +1068,7 @@ __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, floa
         FC_PSTAMP(3)
         // ---- epilogue in registers: slot s = 16 j + r of this lane is tile column spline_slot_col(s, lh): slots 0..24 / 25..49 are dims
         //      2 lh / 2 lh + 1, slots 50.. of the lower half are parameters 0..13 of dim 4, slots 50..60 of the upper half its parameters 14..24
-        if (e.inverse != 2) {                                           // (diagnostic knob 14 = 2: main loop only)
+        if (p.ablate != 2) {                                            // (diagnostic knob 14 = 2: main loop only)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -1081,7 +1082,7 @@ __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, floa
             const bool rv = row < e.rows_valid;
             const bool vA = rv && dim0 + 2 * lh < e.d2, vB = rv && dim0 + 2 * lh + 1 < e.d2, vC = rv && lh == 0 && dim0 + 4 < e.d2;
             float lA, lB, lC;
-            if (e.inverse == 1) {                                       // (diagnostic knob 14 = 1: no spline evaluation)
+            if (p.ablate == 1) {                                        // (diagnostic knob 14 = 1: no spline evaluation)
                 pyA = spl_x[0] + P(0); lA = P(1); pyB = spl_x[1] + P(25); lB = P(26); pyC = spl_x[2] + P(50); lC = P(51);
             } else {
                 rq_spline_fwd_regs<8>(spl_x[0], [&](int q) { return P(q); }, pyA, lA);
@@ -1119,10 +1120,7 @@ void gemm_f32_kernel<128, 128, 4, 1, EPI_SPLINE, 11>(const GemmParams p) {
     spline_gemm_persistent(p, smem);
 }
 
-// tuning knobs (fc_debug_set), defaults = shipped configuration.  Every alternative below is kept because a test pins it against the
-// shipped path (tests/test_gpu_flow.py::test_every_kernel_variant_in_the_library_agrees...) and DESIGN.md section 6 quotes its measurement.
-int g_gemm_variant = 5, g_gemm_colgroup = 10, g_limb_chain = 1, g_lnq_fold = 1, g_fused_spline = 1;
-int g_gemm_stamp = 0;        // knob 20: the LDS-DMA fused-spline launches record in-kernel phase stamps (read back with gemm_read_stamps)
+// the stamp buffer of the diagnostic stamps (knob 20), grown on demand and read back with gemm_read_stamps
 static unsigned long long* g_stamp_buf = nullptr;
 static size_t g_stamp_cap = 0, g_stamp_n = 0;
 unsigned long long* gemm_stamp_buffer(size_t n) {
@@ -1140,21 +1138,15 @@ size_t gemm_read_stamps(unsigned long long* host, size_t max_n) {
     if (n) FC_HIP(hipMemcpy(host, g_stamp_buf, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return n;
 }
-int g_spline_prefetch = 0;   // knob 21: persistent fused spline GEMM (VAR 11): 1 = a tile's k loop starts at a column-tile dependent step and wraps around (measured: no gain, other summation order); 0 = every tile starts at k = 0 (shipped, bit-identical to VAR 9)
-int g_gemm_dma = 5;          // knob 13: fused spline GEMM: 5 = 256 x 256 one-accumulator tile on 16x16x32 MFMAs (spline_wide.hip, shipped round 4; K = 8 bins, limb-chained input; other launches fall to 4), 4 = persistent transposed LDS-DMA loop, splines evaluated from the accumulator registers (VAR 11; K = 8 bins), 2 = LDS-DMA loop on the 128x128 four-wave tile with the LDS parameter tile (VAR 9; 4 and 16 bins always); bit-identical results
-int g_spline_ablate = 0;     // knob 14: diagnostics, results invalid (1 = no spline evaluation, 2 = main loop only, 3 = no parameter-tile write, 4 = no x2 store, 5 = stop behind the tile write)
-int g_gemm_small_tiles = 1;  // knob 22: limb-chained Linear launches with at most 256 tiles of 128x128 run on 64x64 tiles
-int g_limb_chain_all = 1;    // knob 16: every hidden activation of the coupling MLP exists only as a limb image (A16 / residual16 / C16)
-
 static thread_local int* t_fp16_flag = nullptr;
 static std::atomic<long> g_fp16_fallbacks{0};
 
-bool gemm_fp16_enabled() { return g_gemm_variant == 5; }
-bool gemm_lnq_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_lnq_fold; }
-bool gemm_limb_chain_all_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_fused_spline && g_limb_chain && g_limb_chain_all; }
-bool gemm_limb_chain_ok() { return g_gemm_variant == 5 && t_fp16_flag != nullptr && g_fused_spline && g_limb_chain; }
-bool gemm_split_enabled() { return (g_gemm_variant == 5 || g_gemm_variant == 3) && g_fused_spline; }
-int* gemm_fp16_flag() { return g_gemm_variant == 5 ? t_fp16_flag : nullptr; }
+bool gemm_fp16_enabled() { return g_knobs.gemm_variant == 5; }
+bool gemm_lnq_ok() { return g_knobs.gemm_variant == 5 && t_fp16_flag != nullptr && g_knobs.lnq_fold; }
+bool gemm_limb_chain_all_ok() { return g_knobs.gemm_variant == 5 && t_fp16_flag != nullptr && g_knobs.fused_spline && g_knobs.limb_chain && g_knobs.limb_chain_all; }
+bool gemm_limb_chain_ok() { return g_knobs.gemm_variant == 5 && t_fp16_flag != nullptr && g_knobs.fused_spline && g_knobs.limb_chain; }
+bool gemm_split_enabled() { return (g_knobs.gemm_variant == 5 || g_knobs.gemm_variant == 3) && g_knobs.fused_spline; }
+int* gemm_fp16_flag() { return g_knobs.gemm_variant == 5 ? t_fp16_flag : nullptr; }
 long gemm_fp16_fallbacks() { return g_fp16_fallbacks.load(); }
 Fp16Guard::Fp16Guard(int* dev_flag, hipStream_t s) : flag(dev_flag), stream(s), open(true) {
     FC_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
@@ -1254,19 +1246,12 @@ static void launch_cfg(const GemmParams& p, hipStream_t s) {
     GemmParams q = p;
     q.nbn = (p.N_pad + BN - 1) / BN;
     q.col_group = 0;
-    if ((size_t)p.N_pad * p.K_pad * sizeof(float) > (size_t)(3u << 19) && q.nbm % 8 == 0 && q.nbn > g_gemm_colgroup && g_gemm_colgroup > 0)
-        q.col_group = g_gemm_colgroup;
+    if ((size_t)p.N_pad * p.K_pad * sizeof(float) > (size_t)(3u << 19) && q.nbm % 8 == 0 && q.nbn > g_knobs.gemm_colgroup && g_knobs.gemm_colgroup > 0)
+        q.col_group = g_knobs.gemm_colgroup;
     q.stamps = nullptr;
     if constexpr ((EPI == EPI_SPLINE || EPI == EPI_LINEAR) && (VAR == 9 || VAR == 11)) {
-        if (g_gemm_stamp == (EPI == EPI_SPLINE ? 1 : 2)) {                  // knob 20: 1 = the fused spline launches, 2 = the limb-chained Linear launches
-            const size_t n = (size_t)q.nbm * q.nbn * 16;
-            if (n > g_stamp_cap) {
-                if (g_stamp_buf) FC_HIP(hipFree(g_stamp_buf));
-                FC_HIP(hipMalloc(&g_stamp_buf, n * sizeof(unsigned long long)));
-                g_stamp_cap = n;
-            }
-            q.stamps = g_stamp_buf;
-            g_stamp_n = n;
+        if (g_knobs.stamps == (EPI == EPI_SPLINE ? 1 : 2)) {                  // stamps (knob 20): 1 = the fused spline launches, 2 = the limb-chained Linear launches
+            q.stamps = gemm_stamp_buffer((size_t)q.nbm * q.nbn * 16);
         }
     }
     char name[96];
@@ -1287,7 +1272,7 @@ static void launch_cfg(const GemmParams& p, hipStream_t s) {
     FC_HIP(hipGetLastError());
 }
 
-bool gemm_spline_wide_on() { return g_gemm_dma == 5 && g_gemm_variant == 5 && g_fused_spline && g_limb_chain && g_spline_ablate != 3 && g_spline_ablate != 4 && g_spline_ablate != 5; }
+bool gemm_spline_wide_on() { return g_knobs.spline_kernel == 5 && g_knobs.gemm_variant == 5 && g_knobs.fused_spline && g_knobs.limb_chain && g_knobs.spline_ablate != 3 && g_knobs.spline_ablate != 4 && g_knobs.spline_ablate != 5; }
 
 static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_alloc, const GemmEpi& e_in, int epi_kind, hipStream_t s);
 void launch_gemm(const PackedLinear& L, const ASeg* segs, int rows_alloc, const GemmEpi& e_in, int epi_kind, hipStream_t s) {
@@ -1323,8 +1308,9 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
                    (double)(L.k_true ? L.k_true : L.K_pad);
     p.W = L.W; p.W3 = L.W3; p.W2 = L.W2; p.ovf = t_fp16_flag; p.K_pad = L.K_pad; p.bias = L.bias; p.colvec = L.colvec; p.N_pad = L.N_pad;
     p.e = e;
-    const bool split = (g_gemm_variant == 3 || g_gemm_variant == 5) && L.W3 != nullptr;
-    const bool f16 = g_gemm_variant == 5 && L.W2 != nullptr && t_fp16_flag != nullptr;
+    p.ablate = g_knobs.spline_ablate;
+    const bool split = (g_knobs.gemm_variant == 3 || g_knobs.gemm_variant == 5) && L.W3 != nullptr;
+    const bool f16 = g_knobs.gemm_variant == 5 && L.W2 != nullptr && t_fp16_flag != nullptr;
     if (epi_kind == EPI_LINEAR) {
         if ((!e.C && !e.C16) || (e.C && e.ldc < L.N_pad)) throw Error(FC_ERR_INVALID, "launch_gemm: output pitch smaller than N_pad");
         if ((e.gradu || e.Cpre) && e.A16) throw Error(FC_ERR_INVALID, "launch_gemm: the training epilogues exist on the fp32-A loops only");
@@ -1340,18 +1326,17 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
         }
         if (e.r16_scale != 0.f) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator residual image goes with a one-accumulator A image");
         if (e.A16) {
-            p.e.inverse = g_spline_ablate;
             // A arrives as the limb image of the producing layer (limb-chained MLP): the copy-only main loops
             if (!(f16 && L.nseg == 1 && L.N_pad > 64 && L.n_alloc >= round_up(L.N_pad, 128)))
                 throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: a limb-image A operand needs the split-fp16 loop, one segment and N > 64");
-            if (g_gemm_small_tiles && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 256 && L.N_pad % 64 == 0) {
+            if (g_knobs.small_tiles && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 256 && L.N_pad % 64 == 0) {
                 // fewer 128x128 tiles than workgroup slots (C1: 2 x 1024 points = 16 row tiles): four times as many 64x64 tiles, each a
                 // quarter of the MFMA work per k step -- the launch is bound by one workgroup's k loop, not by throughput
                 p.nbm = rows_alloc / 64;
                 launch_cfg<64, 64, 2, 2, EPI_LINEAR, 9>(p, s);
             }
             else { p.nbm = rows_alloc / 128; launch_cfg<128, 128, 2, 2, EPI_LINEAR, 9>(p, s); }
-        } else if (L.N_pad <= 64 || (f16 && g_gemm_small_tiles && !e.C16 && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 128 && L.n_alloc >= round_up(L.N_pad, 64))) {
+        } else if (L.N_pad <= 64 || (f16 && g_knobs.small_tiles && !e.C16 && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 128 && L.n_alloc >= round_up(L.N_pad, 64))) {
             // (64-wide layers; and fp32-A launches with at most 128 tiles of 128x128: twice as many 128x64 tiles)
             p.nbm = rows_alloc / 128;
             if (f16) launch_cfg<128, 64, 4, 1, EPI_LINEAR, 5>(p, s);
@@ -1381,8 +1366,7 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
         } else launch_cfg<128, 128, 4, 2, EPI_LNQ, 5>(p, s);
     } else if (epi_kind == EPI_SPLINE) {
         const int K = e.spline_K;
-        p.e.inverse = g_spline_ablate;
-        p.e.prefetch_dist = g_spline_prefetch;
+        p.e.prefetch_dist = g_knobs.spline_prefetch;
         if (!split) throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: the fused spline epilogue exists for the split GEMM loops only");
         if ((K != 4 && K != 8 && K != 16) || L.N_pad != spline_ncols(e.d2, K) || !e.xbuf || !e.ldj_part || e.ldj_pitch < (size_t)rows_alloc)
             throw Error(FC_ERR_INVALID, "launch_gemm: bad fused-spline arguments (layout of spline.h, per-tile log-det buffer)");
@@ -1392,10 +1376,10 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
             if (L.nseg != 1) throw Error(FC_ERR_INVALID, "launch_gemm: a limb-image A operand must be the only segment");
             if (L.n_alloc < round_up(L.N_pad, 128)) throw Error(FC_ERR_INVALID, "launch_gemm: fused spline layer not padded to the 128-column tile grid");
             if (e.a16_scale != 0.f) {                                   // the one-accumulator image: only spline_wide.hip reads it
-                if (!(g_gemm_dma == 5 && spline_wide_eligible(L, K))) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator activation image needs the wide fused spline kernel (knob 13 = 5)");
+                if (!(g_knobs.spline_kernel == 5 && spline_wide_eligible(L, K))) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator activation image needs the wide fused spline kernel (spline_kernel, knob 13, = 5)");
                 launch_spline_wide(L, p.e, rows_alloc, s);
             }
-            else if (g_gemm_dma != 2 && K == 8 && L.bias) launch_cfg<128, 128, 4, 1, EPI_SPLINE, 11>(p, s);      // (knob 13 = 4; 5 where the wide kernel does not apply)
+            else if (g_knobs.spline_kernel != 2 && K == 8 && L.bias) launch_cfg<128, 128, 4, 1, EPI_SPLINE, 11>(p, s);      // (spline_kernel, knob 13, = 4; 5 where the wide kernel does not apply)
             else launch_cfg<128, 128, 2, 2, EPI_SPLINE, 9>(p, s);      // (4 and 16 bins, knob 13 = 2: the LDS-tile epilogue on the four-wave DMA tile)
         }
         else if (f16) launch_cfg<128, 128, 4, 2, EPI_SPLINE, 5>(p, s);
@@ -1410,7 +1394,7 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
             throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: a limb-image A operand in a pair-packed epilogue exists for the forward affine coupling only");
         if (f16 && e.ldj_part && !e.inverse) {
             if (e.ldj_pitch < (size_t)rows_alloc) throw Error(FC_ERR_INVALID, "launch_gemm: log-det slot pitch smaller than the row count");
-            if (e.A16 && g_gemm_small_tiles && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 256) { p.nbm = rows_alloc / 64; launch_cfg<64, 64, 2, 1, EPI_AFFINE, 9>(p, s); }   // (small launch: 64x64 tiles, see EPI_LINEAR)
+            if (e.A16 && g_knobs.small_tiles && (rows_alloc / 128) * ((L.N_pad + 127) / 128) <= 256) { p.nbm = rows_alloc / 64; launch_cfg<64, 64, 2, 1, EPI_AFFINE, 9>(p, s); }   // (small launch: 64x64 tiles, see EPI_LINEAR)
             else if (e.A16) launch_cfg<128, 128, 2, 2, EPI_AFFINE, 9>(p, s);       // limb-chained MLP: copy-only LDS-DMA loop (a wave's 64 columns = one pair block)
             else if (epi_kind == EPI_AFFINE) launch_cfg<128, 128, 4, 2, EPI_AFFINE, 5>(p, s);
             else if (epi_kind == EPI_AUGMENT) launch_cfg<128, 128, 4, 2, EPI_AUGMENT, 5>(p, s);

@@ -395,25 +395,21 @@ static void launch_knn_mfma(const float* f, int ldf, int C, int32_t* idx, int B,
     FC_HIP(hipGetLastError());
 }
 
-int g_knn_warm = 1;          // knob 32: 1 = a level's search starts from the previous level's neighbour sets where the caller hands them over (shipped), 0 = never
-int g_knn_mfma = 1;          // knob 24: 1 = Gram tiles on the matrix cores + sorted register lists where the launch fills the chip (shipped), 2 = always (tests),
-                             // 0 = the lane-per-candidate kernel above
-
 // warm: k neighbours per query of the same cloud from another feature space (may alias idx: a workgroup reads its own queries' sets before it
 // writes them), or null; used by the matrix-core kernel only -- the result is the exact top-k set either way
 void launch_knn(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm) {
-    if (!g_knn_warm) warm = nullptr;
+    if (!g_knobs.knn_warm) warm = nullptr;                          // (knob 32)
     if (k > 64 || k < 1) throw Error(FC_ERR_UNSUPPORTED, "knn: k must be in [1, 64]");
     if (M < k) throw Error(FC_ERR_INVALID, "knn: fewer points than neighbours (torch.topk would raise as well)");
     const int Cp = round_up(C, 4);
     if (ldf < Cp || ldf % 4 != 0 || ((uintptr_t)f & 15)) throw Error(FC_ERR_INVALID, "knn: feature pitch must cover round_up(C,4) and be 16-byte aligned");
-    if (g_knn_mfma) {
+    if (g_knobs.knn_mfma) {                                         // (knob 24)
         const int Cp8 = C <= 8 ? 8 : (C <= 16 ? 16 : (C <= 32 ? 32 : (C <= 64 ? 64 : (C <= 128 ? 128 : 0))));
         // (wider features or a pitch that does not cover the padded row: the kernel below; so do small scenes -- a workgroup of the MFMA kernel
         // owns 128 queries for ALL M candidates, which takes as long with two scenes in the batch as with sixteen, so the choice depends on
         // M alone (a scene's neighbour sets, near-ties included, must not depend on the batch it sits in); at M = 1024 the 16-query
         // workgroups of the kernel below finish a C1 batch in 0.37 ms against 2.7)
-        if (Cp8 && ldf >= Cp8 && (g_knn_mfma == 2 || M >= 2048)) {
+        if (Cp8 && ldf >= Cp8 && (g_knobs.knn_mfma == 2 || M >= 2048)) {
             switch (Cp8) {
                 case 8: launch_knn_mfma<8>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm); break;
                 case 16: launch_knn_mfma<16>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm); break;

@@ -28,7 +28,7 @@ struct MlpRowsParams {
     float out_s1, out_s2;                           // the last layer's limb split: hi = rn16(v s1), lo = rn16((v s1 - hi) s2): (1, 2048) or the one-accumulator form (kOneAccActScale, 1)
     float range_limit;                              // |activation| at or beyond this raises the flag (65504 / out_s1)
     int rows_valid;
-    unsigned long long* stamps;                     // diagnostic knob 20 = 4 (in-kernel phase stamps), else null
+    unsigned long long* stamps;                     // diagnostic stamps (knob 20) = 4 (in-kernel phase stamps), else null
 };
 
 }  // namespace fc

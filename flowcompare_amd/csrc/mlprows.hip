@@ -93,7 +93,7 @@ __device__ __forceinline__ float mr_act(float v) {
     else return v;
 }
 
-// diagnostic knob 20 = 4 (profiles/micro/mlp_rows_stamps.py): thread 0 of workgroups 0 and 300 stores the shader clock at six points of every
+// diagnostic stamps (knob 20) = 4 (profiles/micro/mlp_rows_stamps.py): thread 0 of workgroups 0 and 300 stores the shader clock at six points of every
 // stage -- 0 stage entry, 1 own DMA pieces landed, 2 barrier passed, 3 next stage's DMA issued, 4 inline-asm section done (bias prefetch,
 // residual loads / swaps, fragment flush), 5 the stage's 24 MFMAs + epilogue micro-steps issued -- as stamps[(wg slot * 256 + stage) * 8 + point]
 #define MR_STAMP(K_)                                                                                                  \
@@ -547,9 +547,7 @@ void launch_limb_decode(const unsigned short* img, float* out, int ldo, int rows
     FC_HIP(hipGetLastError());
 }
 
-extern int g_gemm_stamp;
 unsigned long long* gemm_stamp_buffer(size_t n);
-int g_mlp_rows = 1;          // knob 23: 1 = row-resident coupling MLP chain where it fills the chip (shipped), 2 = at any size, 0 = one GEMM launch per layer
 
 template <int KS0, int ACT, bool STAMPS = false>
 static void mr_launch(const MlpRowsParams& p, int rows_alloc, double flops, hipStream_t s) {
@@ -570,11 +568,11 @@ bool mlp_rows_fills_the_chip(int rows_alloc) {
         FC_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
         return n;
     });
-    return g_mlp_rows == 2 || rows_alloc / 128 >= (3 * cus) / 4;      // (knob 23 = 2: the chain at any size -- tests)
+    return g_knobs.mlp_rows == 2 || rows_alloc / 128 >= (3 * cus) / 4;      // (mlp_rows, knob 23, = 2: the chain at any size -- tests)
 }
 
 bool mlp_rows_eligible(const PackedLinear& in, const std::vector<PackedLinear>& mid, int act) {
-    if (!g_mlp_rows || act != FC_ACT_GELU) return false;
+    if (!g_knobs.mlp_rows || act != FC_ACT_GELU) return false;
     if (!in.Wf || in.N_pad != MR_HID || in.K_pad > MR_HID || in.nseg < 1 || in.nseg > 3 || !in.bias) return false;
     for (int i = 0; i < in.nseg; ++i) if (in.seg_k[i] % 16 != 0) return false;
     if (mid.empty() || (int)mid.size() + 1 > MR_MAXL) return false;
@@ -617,7 +615,7 @@ void launch_mlp_rows(const PackedLinear& in, const std::vector<PackedLinear>& mi
         macs += (double)(mid[i].k_true ? mid[i].k_true : mid[i].K_pad) * (mid[i].n_true ? mid[i].n_true : mid[i].N_pad);
         cur = nxt;
     }
-    if (g_gemm_stamp == 4) {
+    if (g_knobs.stamps == 4) {
         p.stamps = gemm_stamp_buffer(2 * 256 * 8);
         FC_HIP(hipMemsetAsync(p.stamps, 0, 2 * 256 * 8 * sizeof(unsigned long long), s));
     }

@@ -17,44 +17,44 @@ struct TmpBuf {
 }  // namespace fc
 
 
-namespace fc { void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t); long gemm_fp16_fallbacks(); extern int g_train_wgrad16; extern int g_train_attn16; extern int g_gemm_dma; extern int g_spline_ablate; extern int g_limb_chain_all; extern int g_premlp_chain; extern int g_gemm_stamp; extern int g_gemm_small_tiles; extern int g_spline_prefetch; extern int g_mlp_rows; extern int g_knn_mfma; extern int g_premlp_lu; extern int g_spline_wide_colgroup; extern int g_linear_wide; extern int g_knn_warm; extern int g_kv_fold; extern int g_spline_fold; bool kv_fold_gate_dims(int, int, bool, bool); size_t gemm_read_stamps(unsigned long long*, size_t); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t); }
-namespace fc { extern int g_gemm_variant, g_gemm_colgroup, g_attn_fp16, g_fused_spline, g_premlp_fused, g_limb_chain, g_lnq_fold; }
+namespace fc {
+void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t);      // spline_wide.hip
+long gemm_fp16_fallbacks(); size_t gemm_read_stamps(unsigned long long*, size_t);                                      // gemm.hip
+bool kv_fold_gate_dims(int, int, bool, bool); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t);      // flow_engine.cpp
+
+Knobs g_knobs;
+
+struct KnobEntry { int key; const char* name; int Knobs::*field; bool (*accepts)(int v); };
+#define FC_KNOB_ENTRY(key, field, def, accept, doc) {key, #field, &Knobs::field, [](int v) { return accept; }},
+static const KnobEntry kKnobTable[] = {FC_KNOBS(FC_KNOB_ENTRY)};
+#undef FC_KNOB_ENTRY
+static const KnobEntry* find_knob(int key) {
+    for (const KnobEntry& k : kKnobTable) if (k.key == key) return &k;
+    return nullptr;
+}
+}  // namespace fc
 
 extern "C" {
 
-/* tuning knobs for profiles/kernel_bench.py (not part of the stable ABI surface in fcflow.h on purpose).  A value a knob no longer has (its
-   kernel variant lost an A/B and was removed: DESIGN.md section 6) is refused with FC_ERR_UNSUPPORTED and leaves the setting as it was. */
+/* the kernel-choice knobs of csrc/knobs.h by key (profiles/kernel_bench.py, bench.py --knob, the parity tests; not part of the stable ABI surface
+   in fcflow.h on purpose).  An unknown or retired key is FC_ERR_INVALID; a value outside the knob's accepted set (a kernel variant that lost an
+   A/B and was removed: DESIGN.md section 6) is refused with FC_ERR_UNSUPPORTED and leaves the setting as it was. */
 int fc_debug_set(int32_t key, int32_t value) {
-    if ((key == 0 && value != 2 && value != 3 && value != 5) || (key == 8 && value != 0 && value != 2) || (key == 13 && value != 2 && value != 4 && value != 5))
-        return FC_ERR_UNSUPPORTED;
-    if (key == 0) fc::g_gemm_variant = value;             /* GEMM main loop: 5 = split-fp16 (default), 3 = split-bf16, 2 = fp32-input MFMA */
-    else if (key == 2) fc::g_gemm_colgroup = value;
-    else if (key == 5) fc::g_attn_fp16 = value;
-    else if (key == 7) fc::g_fused_spline = value;
-    else if (key == 8) fc::g_premlp_fused = value;        /* pre-attention chain: 2 = the row-resident kernel (premlp.hip, default), 0 = separate launches */
-    else if (key == 9) fc::g_limb_chain = value;
-    else if (key == 10) fc::g_lnq_fold = value;
-    else if (key == 11) fc::g_train_wgrad16 = value;
-    else if (key == 12) fc::g_train_attn16 = value;
-    else if (key == 13) fc::g_gemm_dma = value;           /* fused spline GEMM: 5 = the wide kernel (spline_wide.hip, default), 4 = persistent LDS-DMA loop (VAR 11), 2 = LDS-tile epilogue (VAR 9) */
-    else if (key == 16) fc::g_limb_chain_all = value;    /* 1 = the coupling MLP's hidden activations exist only as limb images (default), 0 = also as fp32 */
-    else if (key == 19) fc::g_premlp_chain = value;
-    else if (key == 21) fc::g_spline_prefetch = value;
-    else if (key == 22) fc::g_gemm_small_tiles = value;
-    else if (key == 23) fc::g_mlp_rows = value;          /* 1 = row-resident coupling MLP chain (mlprows.hip, default), 0 = one GEMM launch per layer */
-    else if (key == 26) fc::g_premlp_lu = value;         /* 1 = ActNorm + LU as a pre-layer of the row-resident pre-attention kernel (default), 0 = its own GEMM launch */
-    else if (key == 24) fc::g_knn_mfma = value;          /* 1 = k-NN Gram tiles on the matrix cores (default), 0 = lane-per-candidate kernel */
-    else if (key == 29) fc::g_linear_wide = value;       /* hidden layers of the coupling MLP on the 256 x 256 one-accumulator kernel: 0 = off (default: measured no faster than the chain), 1 = for scenes of >= 2048 target points, 2 = at any size */
-    else if (key == 32) fc::g_knn_warm = value;         /* 1 = DGCNN levels 1-3 start their k-NN stream from the previous level's neighbour sets (default; exact either way), 0 = from -inf */
-    else if (key == 33) fc::g_kv_fold = value;          /* read by fc_flow_create: 1 = to_kv folded into the q projections and the consumers' in_layers, keys = values = the context panel (default, where embedding dim == inner dim), 0 = the stacked K|V projection */
-    else if (key == 34) fc::g_spline_fold = value;      /* read by fc_flow_create: 1 = the wide fused spline kernel runs on the folded 22-parameter image, 112-column wave tiles (default), 0 = the 25-parameter image on 128-column tiles */
-    else if (key == 31) fc::g_train_wide = value;       /* 1 = training Linear layers with >= 1024 outputs (the spline parameter layer) on the 256 x 256 one-accumulator loop (default), 0 = on the fp32-A 128 x 128 loop, 3 = 1 with non-temporal stores of a GB-sized output (measured slower) */
-    else if (key == 28) fc::g_spline_wide_colgroup = value;   /* column-group size of its tile order (-1 = shipped) */
-    else if (key == 20) fc::g_gemm_stamp = value;        /* diagnostic: in-kernel phase stamps, 1 = fused spline launches, 2 = limb-chained Linear launches, 3 = row-resident pre-attention kernel, 4 = row-resident coupling MLP */
-    else if (key == 14) fc::g_spline_ablate = value;     /* diagnostic: 1 = fused spline epilogue without the spline evaluation, 2 = main loop only (results invalid) */
-    else return FC_ERR_INVALID;
+    const fc::KnobEntry* k = fc::find_knob(key);
+    if (!k) return FC_ERR_INVALID;
+    if (!k->accepts(value)) return FC_ERR_UNSUPPORTED;
+    fc::g_knobs.*(k->field) = value;
     return FC_OK;
 }
+int fc_debug_get(int32_t key, int32_t* value) {
+    const fc::KnobEntry* k = fc::find_knob(key);
+    if (!k || !value) return FC_ERR_INVALID;
+    *value = fc::g_knobs.*(k->field);
+    return FC_OK;
+}
+int fc_debug_reset(void) { fc::g_knobs = fc::Knobs{}; return FC_OK; }      /* every knob back to its shipped default */
+/* the knob's field name in csrc/knobs.h, or NULL for an unknown key (a script lists the table by walking the keys) */
+const char* fc_debug_name(int32_t key) { const fc::KnobEntry* k = fc::find_knob(key); return k ? k->name : nullptr; }
 
 /* diagnostic / test entry (not part of fcflow.h): out[rows, N] = x[rows, K] W[N, K]^T + bias through the ONE-ACCUMULATOR limb form on the 256 x 256 main loop of
    spline_wide.hip, nothing else -- the product the fused spline layer is built on, measurable against fp64 by itself; device pointers, wmax = max |W| */
@@ -70,10 +70,10 @@ int32_t fc_debug_spline_col(int32_t j, int32_t pp, int32_t K) { return fc::splin
 int32_t fc_debug_spline_tile_pos(int32_t c, int32_t K) { return fc::spline_tile_pos(c, K); }
 
 /* host-side view of the K|V fold's gate (flow_engine.cpp kv_fold_gate_dims) for the CPU tests: 1 when a flow whose attentions have this
-   embedding width, inner width and these biases gets to_kv folded away at fc_flow_create (with knob 33 at its default); no device call */
+   embedding width, inner width and these biases gets to_kv folded away at fc_flow_create (with kv_fold, knob 33, at its default); no device call */
 int32_t fc_debug_kv_fold_gate(int32_t E, int32_t inner, int32_t q_bias, int32_t kv_bias) { return fc::kv_fold_gate_dims(E, inner, q_bias != 0, kv_bias != 0) ? 1 : 0; }
 
-/* diagnostic (knob 20): copies the phase stamps of the last stamped fused-spline launch (16 x u64 per workgroup) to host memory; returns the count */
+/* diagnostic (stamps, knob 20): copies the phase stamps of the last stamped fused-spline launch (16 x u64 per workgroup) to host memory; returns the count */
 int64_t fc_debug_gemm_stamps(uint64_t* host, int64_t max_n) {
     try { return (int64_t)fc::gemm_read_stamps(reinterpret_cast<unsigned long long*>(host), (size_t)max_n); } catch (...) { return -1; }
 }
@@ -134,7 +134,7 @@ int fc_op_linear_f32(const float* x, const float* W, const float* bias, const fl
     L.n_true = N; L.k_true = K;
     std::unique_ptr<TmpBuf> w3buf, w2buf;
     TmpBuf flag(sizeof(int));
-    if (g_gemm_variant == 3 || g_gemm_variant == 5) {           // split variants: limb images via a host round trip (test path only)
+    if (g_knobs.gemm_variant == 3 || g_knobs.gemm_variant == 5) {   // split variants: limb images via a host round trip (test path only)
         FC_HIP(hipStreamSynchronize(s));
         std::vector<float> hw((size_t)na * kp);
         FC_HIP(hipMemcpy(hw.data(), wp.f(), hw.size() * 4, hipMemcpyDeviceToHost));
@@ -231,10 +231,10 @@ int fc_debug_attention_ctx_f32(const float* q, const float* c, float* out, int32
     if (((uintptr_t)q | (uintptr_t)c | (uintptr_t)out) & 15) throw fc::Error(FC_ERR_INVALID, "fc_debug_attention_ctx_f32: operands must be 16-byte aligned");
     fc::TmpBuf limbs(fc::attention_limb_ws_bytes((long)B * M, D) / 2), flag(sizeof(int));
     fc::run_fp16_guarded((int*)flag.p, (hipStream_t)stream, [&] {
-        if (fc::gemm_fp16_flag() && fc::attention_fp16_enabled()) {
+        if (fc::gemm_fp16_flag() && fc::g_knobs.attn_fp16) {
             fc::launch_context_limbs(c, D, (unsigned short*)limbs.p, (long)B * M, D, (hipStream_t)stream);
             fc::launch_attention_ctx16(q, D, (const unsigned short*)limbs.p, out, D, B, N, N, M, M, D, (hipStream_t)stream, nullptr, scale * 1.4426950408889634f);
-        } else {                                        // as in the engine: the repeat after a raised range flag (and knob 5 = 0) takes c itself, in fp32
+        } else {                                        // as in the engine: the repeat after a raised range flag (and attn_fp16, knob 5, = 0) takes c itself, in fp32
             fc::launch_attention_op(q, c, c, out, B, N, M, D, scale, nullptr, (hipStream_t)stream);
         }
     });

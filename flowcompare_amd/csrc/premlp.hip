@@ -32,7 +32,7 @@ struct PreMlpParams {
     int act;
     float* qout; int ldq;
     int rows;                           // rows allocated (multiple of 64)
-    unsigned long long* stamps;         // diagnostic knob 20 = 3: 16 x u64 per workgroup (s_memtime at the layer boundaries; wall clock in 14 / 15)
+    unsigned long long* stamps;         // diagnostic stamps (knob 20) = 3: 16 x u64 per workgroup (s_memtime at the layer boundaries; wall clock in 14 / 15)
     float* keep_ws;                     // row-resident kernel: rows x 256 floats of scratch (the second hidden layer's residual, parked as limb fragments)
     int* ovf;
     // row-resident kernel with the PREVIOUS layer's folded ActNorm + permuter matrix as a pre-layer (premlp_rows_kernel<.., .., NLU > 0>):
@@ -45,7 +45,7 @@ struct PreMlpParams {
 constexpr int PM_H = 256;                                  // hidden width = attention input width
 
 // =====================================================================================================================================
-// The row-resident kernel (knob 8 = 2): the chain's activations never leave the REGISTERS.
+// The row-resident kernel (premlp_fused, knob 8, = 2): the chain's activations never leave the REGISTERS.
 //   The product is transposed (weights as the MFMA's A operand, points as B) on the 16x16x32 shape: a wave owns 16 points, a point is
 //   spread over the four lanes n, n + 16, n + 32, n + 48 (lane row kg = lane >> 4 supplies in-features 32 s + 8 kg + 0..7 of k step s).
 //   Per lane: the layer's input as B-operand fragments (8 k steps x [hi | lo'] x 8 fp16 = 64 registers), the output being assembled in
@@ -489,10 +489,6 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 #undef PR_STAMP
 }
 
-int g_premlp_fused = 2;       // tuning knob (fc_debug_set 8): 2 = the row-resident kernel (activations in registers; shipped: 190 us against ~250 us for the
-                              // five launches it replaces, -1.4 ... -2 % per C2 step; the removed LDS-tile kernel, value 1, took 263 us: one 64-row workgroup per CU
-                              // re-streams every layer's weights from L2, 16 % MFMA busy), 0 = separate GEMM launches + the LayerNorm -> q fold
-
 static bool premlp_layer_ok(const PackedLinear& L, int n, int kmax) {
     return L.W2 != nullptr && L.bias != nullptr && L.nseg == 1 && L.N_pad == n && L.n_true == n && L.K_pad % 32 == 0 && L.K_pad <= kmax &&
            L.n_alloc >= n;
@@ -500,7 +496,7 @@ static bool premlp_layer_ok(const PackedLinear& L, int n, int kmax) {
 
 // true when the fused kernel can run this pre-conditioner (shapes above, fp16 limb images present, inside a guard scope)
 bool premlp_fusable(const PackedLinear& in, const std::vector<PackedLinear>& mid, const PackedLinear& out, const PackedLinear& q) {
-    return gemm_fp16_flag() != nullptr && g_premlp_fused && mid.size() == 2 && premlp_layer_ok(in, PM_H, PM_H) &&
+    return gemm_fp16_flag() != nullptr && g_knobs.premlp_fused && mid.size() == 2 && premlp_layer_ok(in, PM_H, PM_H) &&
            premlp_layer_ok(mid[0], PM_H, PM_H) && mid[0].K_pad == PM_H && premlp_layer_ok(mid[1], PM_H, PM_H) && mid[1].K_pad == PM_H &&
            premlp_layer_ok(out, PM_H, PM_H) && out.K_pad == PM_H && out.k_true == PM_H && q.W2 != nullptr && q.nseg == 1 && q.N_pad == 64 &&
            q.K_pad == PM_H && q.k_true == PM_H;
@@ -513,15 +509,12 @@ bool premlp_rows_ok(int rows_alloc, int ldq, const float* qout, const float* kee
            keep_floats >= (size_t)rows_alloc * PM_H;
 }
 
-extern int g_gemm_stamp;
-unsigned long long* gemm_stamp_buffer(size_t n);      // gemm.hip: the knob-20 stamp buffer (grown on demand), read back by fc_debug_gemm_stamps
-
-int g_premlp_lu = 1;          // knob 26: 1 = the previous layer's folded ActNorm + LU runs as a pre-layer of the row-resident kernel (shipped), 0 = as its own GEMM launch
+unsigned long long* gemm_stamp_buffer(size_t n);      // gemm.hip: the buffer of the diagnostic stamps (knob 20), grown on demand, read back by fc_debug_gemm_stamps
 
 // true when `lu` (the previous flow layer's folded ActNorm + permuter, latent pitch ldx) can run as the pre-layer of this pre-conditioner's
 // row-resident kernel: square 320 x 320 in the latent's padded layout, the in_layer reading its first 160 columns, GELU (the instantiated case)
 bool premlp_lu_fusable(const PackedLinear& lu, const PackedLinear& in, int act, int ldx) {
-    return g_premlp_lu && act == FC_ACT_GELU && lu.W2 != nullptr && lu.bias != nullptr && lu.nseg == 1 && lu.K_pad == 320 && lu.N_pad == 320 && ldx == 320 &&
+    return g_knobs.premlp_lu && act == FC_ACT_GELU && lu.W2 != nullptr && lu.bias != nullptr && lu.nseg == 1 && lu.K_pad == 320 && lu.N_pad == 320 && ldx == 320 &&
            lu.n_alloc >= 320 && in.K_pad == 160;
 }
 
@@ -535,7 +528,7 @@ void launch_premlp(const float* x, int ldx, const PackedLinear& in, const std::v
     auto L = [](const PackedLinear& l) { return PreMlpLayer{l.W2, l.bias, l.K_pad}; };
     p.in = L(in); p.mid0 = L(mid[0]); p.mid1 = L(mid[1]); p.out = L(out); p.q = L(q);
     p.act = act; p.qout = qout; p.ldq = ldq; p.rows = rows_alloc; p.ovf = gemm_fp16_flag(); p.keep_ws = keep_ws;
-    p.stamps = g_gemm_stamp == 3 ? gemm_stamp_buffer((size_t)(rows_alloc / PR_ROWS) * 16) : nullptr;
+    p.stamps = g_knobs.stamps == 3 ? gemm_stamp_buffer((size_t)(rows_alloc / PR_ROWS) * 16) : nullptr;
     const double rv = rows_valid > 0 ? rows_valid : rows_alloc;
     double flops = 2.0 * rv * ((double)in.k_true * PM_H + 3.0 * PM_H * PM_H + (double)PM_H * (q.n_true ? q.n_true : 64));
     if (premlp_rows_ok(rows_alloc, ldq, qout, keep_ws, keep_floats)) {

@@ -27,7 +27,7 @@
 // whole-wave evaluations (every lane busy: 16 points x 4 dims) and a fifth in which row kq takes dim 4 of point block kq after a 4 x 4
 // transpose of those seven registers across the rows (v_permlane16_swap + v_permlane32_swap, one swap per register).  64 points x 5 dims =
 // 5 full wave evaluations (VAR 11: 6 for the same points, one half empty).
-// Shipped form of the spline layer (knob 34 = 1, read at fc_flow_create): the image is FOLDED to the 22 parameters per dim that carry
+// Shipped form of the spline layer (spline_fold, knob 34, = 1, read at fc_flow_create): the image is FOLDED to the 22 parameters per dim that carry
 // information (softmax's shift invariance removes width / height logit 7, derivative logit 8 is read for no bin: spline_wide_src_col_folded,
 // spline.h rq_spline_fwd_regs_folded), 22 + a 6 + 6 + 6 + 4 share of dim 4 = 28 slots per lane row = SEVEN 16-parameter blocks: a 64 x 112 wave
 // tile, a 256 x 224 workgroup tile, 84 instead of 96 MFMAs per wave and k step in a kernel bound by the MFMAs it issues.
@@ -53,7 +53,7 @@ struct SplineWideParams {
     int ntile128;                // 128-column spline tiles that exist (the last pair may be half empty)
     int col_group;
     float out_scale;             // 1 / (kOneAccActScale * 2^w1_exp)
-    int ablate;                  // diagnostic knob 14: 1 no spline evaluation, 2 main loop only (results invalid)
+    int ablate;                  // diagnostic spline_ablate (knob 14): 1 no spline evaluation, 2 main loop only (results invalid)
     // EPI 1 (a Linear layer of the coupling MLP: bias in the accumulators, residual, exact-erf GELU, output as a limb image)
     unsigned short* out16;       // [rows][N/16][hi 16 | lo 16] fp16
     const unsigned short* res16; // residual as a one-accumulator image of the same shape, or null (models/nets.py:27: odd hidden layers)
@@ -83,7 +83,7 @@ __host__ __device__ inline int spline_wide_src_col(int c) {
     return i < cnt ? spline_col(4, base + i, 8) : -1;
 }
 
-// The FOLDED tile order (knob 34, shipped): 22 informative parameters per dim, [7 width | 7 height | 8 derivative] (spline.h
+// The FOLDED tile order (spline_fold, knob 34, shipped): 22 informative parameters per dim, [7 width | 7 height | 8 derivative] (spline.h
 // rq_spline_fwd_regs_folded), on a wave tile of 7 blocks of 16 = 112 columns.  Column c as above; slot s = 4 jb + r < 28 of row kq:
 //   s < 22: folded parameter s of the tile's dim kq;  s >= 22: folded parameter 6 kq + s - 22 of dim 4 (rows 0..2 carry 6, row 3 carries 4:
 //   its last two slots are spare)
@@ -130,8 +130,6 @@ __global__ __launch_bounds__(256) void spline_wide_image_kernel(const float* __r
     W1[blk * 32 + 16 + (k & 15)] = __builtin_bit_cast(unsigned short, l);
     if (k == 0 && bias1) bias1[row] = bv * bscale;
 }
-
-int g_spline_wide_colgroup = -1;   // knob 28: column-group size of the tile order in 256-column tiles (-1 = shipped: 5)
 
 // rows of 16 lanes (a0,a1,a2,a3 | b0,b1,b2,b3):  swap32 -> a = (a0,a1,b0,b1), b = (a2,a3,b2,b3) ;  swap16 -> a = (a0,b0,a2,b2), b = (a1,b1,a3,b3)
 __device__ __forceinline__ void sw_swap32(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b)); }
@@ -627,8 +625,6 @@ void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStre
     FC_HIP(hipGetLastError());
 }
 
-extern int g_spline_ablate;
-
 void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s) {
     if (!spline_wide_eligible(L, e.spline_K) || !e.A16 || e.a16_scale != kOneAccActScale || rows_alloc % 256 != 0 || !e.xbuf || !e.ldj_part ||
         e.ldj_pitch < (size_t)rows_alloc || L.N_pad != spline_ncols(e.d2, 8))
@@ -643,8 +639,9 @@ void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
     p.nbn = (p.ntile128 + 1) / 2;
     p.col_group = (p.nbm % 8 == 0 && p.nbn > 5) ? 5 : 0;
     p.out_scale = 1.0f / (kOneAccActScale * ldexpf(1.f, L.w1_exp));
-    p.ablate = g_spline_ablate;
-    if (g_spline_wide_colgroup >= 0) p.col_group = (p.nbm % 8 == 0 && p.nbn > g_spline_wide_colgroup) ? g_spline_wide_colgroup : 0;
+    p.ablate = g_knobs.spline_ablate;
+    const int cg = g_knobs.spline_wide_colgroup;      // (knob 28)
+    if (cg >= 0) p.col_group = (p.nbm % 8 == 0 && p.nbn > cg) ? cg : 0;
     static PerDeviceOnce slots_once;
     // (the weight pieces of the folded form: 2 + 3 + 2 per k step)
     auto kern = L.w1_folded ? spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 2, 0> : spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>;
@@ -670,16 +667,13 @@ void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
 namespace fc {
 
 // ---------------------------------------------------------------- EPI 1: a GELU Linear layer of the coupling MLP on the same tile
-int g_linear_wide = 0;       // knob 29: 0 = off (SHIPPED: measured, not faster -- below), 1 = hidden layers of 512-wide coupling nets on this kernel for scenes of at
-                             // least 2048 target points (the gate is the scene's size, never the batch's), 2 = at any size (tests)
-// Measured on C2 (16 x 4096, same box, profiles/r04o_*): 133 us per hidden-layer launch = ~75 us of main loop (459 TF-eq at N = 512:
+// Behind linear_wide (knob 29), off as shipped.  Measured on C2 (16 x 4096, same box, profiles/r04o_*): 133 us per hidden-layer launch = ~75 us of main loop (459 TF-eq at N = 512:
 // profiles/micro/wide_gemm_probe.hip) + ~55 us of epilogue that nothing overlaps (4471 VALU instructions per wave and tile: 128 exact-erf
 // GELUs, limb splits, lane swaps; with one workgroup per CU there is no second tile's main loop to hide them behind), and the in_layer stays
 // on its fp32-A loop (100 us): 30.6 + 11.5 = 42 ms per step against 40.8 ms for the row-resident chain (mlprows.hip), whose epilogue runs
 // in micro-steps under the next block's MFMAs.  The arithmetic also differs from the chain's (one accumulator, k32 MFMAs), so shipping it for
 // large scenes only would make a row's log-prob depend on the size of the scene it sits in (tests/test_gpu_fullsize.py compares rows of a
 // 512-point run with the 16 x 4096 run bit for bit).  Kept behind the knob with its tests; not on the default path.
-int gemm_linear_wide_knob() { return g_linear_wide; }
 
 bool linear_wide_eligible(const PackedLinear& L, const GemmEpi& e, int rows_alloc) {
     return L.W1 && !L.w1_permuted && L.bias1 && L.nseg == 1 && L.K_pad % 64 == 0 && L.N_pad % 256 == 0 && rows_alloc % 256 == 0 && e.A16 &&
@@ -699,7 +693,7 @@ void launch_linear_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
     p.ntile128 = L.N_pad / 128;
     p.col_group = (p.nbm % 8 == 0) ? p.nbn : 0;      // (a 512-wide layer: both column tiles of a row tile side by side on one XCD)
     p.out_scale = 1.0f / (kOneAccActScale * ldexpf(1.f, L.w1_exp));
-    p.ablate = g_spline_ablate == 2 ? 2 : 0;
+    p.ablate = g_knobs.spline_ablate == 2 ? 2 : 0;
     p.out16 = e.C16; p.res16 = e.residual16; p.n16 = L.N_pad / 16;
     p.s1 = e.c16_scale > 0.f ? e.c16_scale : 1.0f;
     p.s2 = e.c16_scale > 0.f ? 1.0f : 2048.0f;
@@ -777,7 +771,6 @@ void one_acc_gemm_debug(const float* x, const float* W, const float* bias, float
 namespace fc {
 
 // ---------------------------------------------------------------- EPI 3: the wide Linear layers of a training step (train.hip)
-int g_train_wide = 1;
 
 void launch_train_wide(const TrainWideArgs& a, hipStream_t s) {
     if (!a.A || !a.W1 || !a.C || a.K_pad < 64 || a.K_pad % 64 != 0 || a.rows_pad < 256 || a.rows_pad % 256 != 0 || a.n_cols < 4 || a.n_cols % 4 != 0 ||
@@ -796,9 +789,9 @@ void launch_train_wide(const TrainWideArgs& a, hipStream_t s) {
     p.out_scale = a.row_absmax ? ldexpf(1.f, -kTrainWideWExp) : 1.0f / (a.a_scale * ldexpf(1.f, kTrainWideWExp));
     p.C = a.C; p.ldc = a.ldc; p.addend = a.addend; p.gradu = a.gradu; p.ldgu = a.ldgu; p.gact = a.gact; p.n_cols = a.n_cols;
     p.ovf = a.ovf;
-    // knob 31 = 3: a C panel of 256 MB or more streams out with non-temporal stores (measured on the C2 training step, same box: 1116 against 1092 ms
+    // train_wide (knob 31) = 3: a C panel of 256 MB or more streams out with non-temporal stores (measured on the C2 training step, same box: 1116 against 1092 ms
     // with ordinary stores, profiles/r04w_train_*.json -- not shipped)
-    p.nt_store = g_train_wide == 3 && (size_t)a.rows_pad * a.n_cols * 4 >= ((size_t)256 << 20);
+    p.nt_store = g_knobs.train_wide == 3 && (size_t)a.rows_pad * a.n_cols * 4 >= ((size_t)256 << 20);
     static PerDeviceOnce attr_once, slots_once;
     auto kern = spline_wide_kernel<3, 4, 4, 0, 0, 2, 3, 3, 0>;
     attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });

@@ -484,7 +484,6 @@ __global__ void colsum_reduce_kernel(const float* __restrict__ part, int S, int 
 }
 
 // ---------------------------------------------------------------- host side
-int g_train_wgrad16 = 1;      // tuning knob (fc_debug_set 11): weight gradients on the split-fp16 loop inside a guard scope
 static int grid_for(size_t n, int block) { return (int)std::min<size_t>((n + block - 1) / block, 256 * 16); }
 
 struct WgradPlan { int S, chunk, n128, k128max, S2, chunk2; size_t part_floats, colsum_floats, bytes; };
@@ -532,14 +531,14 @@ static PackedLinear packed_transposed(const TrainLinearLayout& L, const void* pa
 
 // the wide layers on the 256 x 256 one-accumulator loop (forward: constant activation scale; data gradient: per-row scales)
 static bool train_wide_fwd_ok(const TrainLinearLayout& L, int rows_pad, const int32_t* ovf, const float* residual) {
-    return g_train_wide && L.wide && ovf && !residual && rows_pad % 256 == 0 && gemm_fp16_enabled();
+    return g_knobs.train_wide && L.wide && ovf && !residual && rows_pad % 256 == 0 && gemm_fp16_enabled();
 }
 
 // the data gradient of such a layer on the same loop: every row of du scaled by an exact power of two from `row_absmax` ([rows_pad], each >=
 // max |du[row, :]|, written by the kernel that produced du -- fc_train_rqspline_bwd_f32); false = not eligible, the fp32-A loop runs
 static bool train_wide_dgrad(const TrainLinearLayout& L, const void* pack, const float* du, int ldu, int rows_pad, const float* row_absmax, float* dx,
                              int lddx, const float* addend, const float* u_prev, int act, int32_t* ovf, hipStream_t s) {
-    if (!(g_train_wide && L.wide && ovf && row_absmax && rows_pad % 256 == 0 && (!u_prev || act == FC_ACT_GELU) && gemm_fp16_enabled())) return false;
+    if (!(g_knobs.train_wide && L.wide && ovf && row_absmax && rows_pad % 256 == 0 && (!u_prev || act == FC_ACT_GELU) && gemm_fp16_enabled())) return false;
     TrainWideArgs w;
     w.A = du; w.lda = ldu; w.W1 = (const unsigned short*)((const char*)pack + L.off_WT1); w.K_pad = L.N_pad; w.rows_pad = rows_pad; w.n_cols = L.K_pad;
     w.row_absmax = row_absmax; w.C = dx; w.ldc = lddx; w.ovf = (int*)ovf;
@@ -688,7 +687,7 @@ int fc_train_linear_wgrad_f32(int32_t N, const int32_t* seg_widths, int32_t nseg
         for (int i = 0; i < L.nseg; ++i) {
             check_panel(x[i], ldx[i], L.seg_pad[i], "x");
             const int k128 = round_up(L.seg_pad[i], 128), tiles_k = k128 / 128, tiles_n = w.n128 / 128;
-            if (ovf && g_train_wgrad16) {
+            if (ovf && g_knobs.train_wgrad16) {                   // (knob 11)
                 ProfScope ps("fc::wgrad16_kernel", 2.0 * rows * (double)L.N * L.seg[i], 0.0, s);
                 hipLaunchKernelGGL(wgrad16_kernel, dim3(tiles_n * tiles_k, w.S), dim3(256), 0, s, du, ldu, L.N_pad, x[i], ldx[i], L.seg_pad[i], rows,
                                    w.chunk, tiles_k, part, w.n128, k128, (db && i == 0) ? cpart : nullptr, w.n128, (int*)ovf);

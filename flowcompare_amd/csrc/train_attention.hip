@@ -576,8 +576,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef FC_TR16x2
 #undef FC_TR16
 
-int g_train_attn16 = 1;       // tuning knob (fc_debug_set 12): attention backward on the split-fp16 loop inside a guard scope (head dim 64)
-
 static void launch_attn_bwd16(const AttnBwdParams& p, int B, int* ovf, hipStream_t s) {
     const double fl = 2.0 * B * (double)p.N * p.M * 64;
     {
@@ -656,8 +654,8 @@ int fc_train_attention_bwd_f32(const float* q, int32_t ldq, const float* k, int3
     check_mat(dq, lddq, D, "dq"); check_mat(dk, lddk, D, "dk"); check_mat(dv, lddv, D, "dv");
     if (!stats) throw Error(FC_ERR_INVALID, "fc_train_attention_bwd_f32: stats scratch [2 * B * N] is required");
     AttnBwdParams p{q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, dq, lddq, dk, lddk, dv, lddv, stats, stats + (size_t)B * N, N, M, scale, 0};
-    p.have_lse = (stats_valid && D == 64 && ovf && g_train_attn16) ? 1 : 0;
-    if (D == 64 && ovf && g_train_attn16) launch_attn_bwd16(p, B, (int*)ovf, (hipStream_t)stream);
+    p.have_lse = (stats_valid && D == 64 && ovf && g_knobs.train_attn16) ? 1 : 0;
+    if (D == 64 && ovf && g_knobs.train_attn16) launch_attn_bwd16(p, B, (int*)ovf, (hipStream_t)stream);
     else if (D == 32) launch_attn_bwd<32>(p, B, (hipStream_t)stream);
     else if (D == 64) launch_attn_bwd<64>(p, B, (hipStream_t)stream);
     else if (D == 128) launch_attn_bwd<128>(p, B, (hipStream_t)stream);

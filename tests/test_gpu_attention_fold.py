@@ -3,6 +3,7 @@ DESIGN.md sections 4, 5, 9): to_kv folded into the q projections and the consume
 image of the context panel, a 64-key tile staged once for the S and the PV phase.  fc_debug_set key 33 (read when a flow is created)
 selects the folded (1, shipped) or the projected-K|V engine (0); a test that flips it drops the module's engine handle so that the next
 call packs a fresh one.  Which kernels ran is read from the in-library profiler, never assumed."""
+import contextlib
 import ctypes
 
 import pytest
@@ -11,6 +12,7 @@ import torch
 import attn_weights_util as U
 import flowcompare_amd as fa
 from flowcompare_amd import engine
+from knob_util import knobs
 from oracle import flow_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -43,24 +45,19 @@ class _kernels:
         return any(substr in n for n in self.launches)
 
 
-class _fold:
+@contextlib.contextmanager
+def _fold(value, *mds):
     """knob 33 = value for the engines created inside the block; `mds` lose their handles on the way in and out"""
-
-    def __init__(self, value, *mds):
-        self.value, self.mds = value, mds
-
-    def _drop(self):
-        for md in self.mds:
+    def drop():
+        for md in mds:
             md["flow"]._handle = None
 
-    def __enter__(self):
-        assert engine.lib().fc_debug_set(33, self.value) == 0
-        self._drop()
-
-    def __exit__(self, *exc):
-        engine.lib().fc_debug_set(33, 1)
-        self._drop()
-        return False
+    try:
+        with knobs({33: value}):
+            drop()
+            yield
+    finally:
+        drop()
 
 
 def _rand(*shape, seed, scale=1.0):

@@ -12,6 +12,7 @@ import torch
 
 import attn_weights_util as U
 import flowcompare_amd as fa
+import knob_util
 from conftest import Fixture
 from flowcompare_amd import engine
 from fullsize_util import build_conditioned, state_dicts, synth_pairs
@@ -19,7 +20,6 @@ from oracle import flow_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-KNOB_DEFAULTS = {0: 5, 5: 1, 8: 2, 10: 1}
 
 
 class _kernels:
@@ -205,17 +205,6 @@ def test_exact_properties(case):
 
 
 # ------------------------------------------------------------------ 4. operand forms
-def _with_knobs(knobs, fn):
-    lib = engine.lib()
-    try:
-        for k, v in knobs.items():
-            assert lib.fc_debug_set(k, v) == 0, f"knob {k} = {v} refused"
-        return fn()
-    finally:
-        for k in knobs:
-            lib.fc_debug_set(k, KNOB_DEFAULTS[k])
-
-
 # (label, knobs, K form of the weight kernel, the kernels that mark the q forms of the run: premlp_rows = final from the row-resident chain,
 #  lnq_finalize = finalised by that pass, layernorm = three-launch fallback; none of them = the LayerNorm -> q GEMM whose q the consumer
 #  finishes on load).  The augmenter's 6-wide input never admits the row-resident chain: by default ITS q is the fold finished on load.
@@ -241,8 +230,8 @@ def test_every_operand_form_on_the_sharp_fixture(label, knobs, kform, qmarks):
     from the in-library profiler, so each form is known to have been produced."""
     fx, ref = U.load_case(U.SHARP)
     cfg, md = _build(fx)
-    with _kernels() as kn:
-        worst = _with_knobs(knobs, lambda: _check_fixture(U.SHARP, label, cfg, md, fx, ref))
+    with _kernels() as kn, knob_util.knobs(knobs):
+        worst = _check_fixture(U.SHARP, label, cfg, md, fx, ref)
     assert worst <= 1.0
     assert kn.ran(f"attn_weights_kernel<64, {kform}>") and not kn.ran(f"attn_weights_kernel<64, {1 - kform}>"), kn.names
     for mark in ("premlp_rows_kernel", "lnq_finalize_kernel", "layernorm_kernel"):

@@ -11,6 +11,7 @@ import torch
 
 import flowcompare_amd as fa
 from conftest import Fixture
+from knob_util import knobs
 from oracle import flow_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -249,8 +250,6 @@ def test_every_kernel_variant_in_the_library_agrees_on_the_c2_layer_stack():
     against the paths that stay in the library beside them -- the per-layer launches small batches take, the unfused spline of the inverse
     direction, the bf16-limb range fallback, the fp32-input reference loop: same log-probs within the fp32 noise of a 4-layer flow at the
     real layer widths, and bit-identical ones where the arithmetic is the same.  Every case runs: a refused knob value fails the test."""
-    from flowcompare_amd import engine
-    lib = engine.lib()
     cfg = fa.named_config("c2_dgcnn_attn_spline", n_flow_layers=4, sample_size=300)
     torch.manual_seed(7)
     md = fa.initialize_flow(cfg, device=DEV, mode="test")
@@ -259,59 +258,49 @@ def test_every_kernel_variant_in_the_library_agrees_on_the_c2_layer_stack():
     e0, e1 = torch.rand(B, M, 6, generator=g), torch.rand(B, N, 6, generator=g)
     eps = [torch.randn(B, N, 294, generator=g).to(DEV)]
     batch = (e0.to(DEV), e1.to(DEV), None)
-    defaults = {0: 5, 5: 1, 7: 1, 8: 2, 9: 1, 10: 1, 13: 5, 16: 1, 19: 0, 21: 0, 22: 1, 23: 1, 29: 0}
 
-    def run_with(knobs):
+    def run_with(settings):
         """log-probs under the given knob values"""
-        try:
-            for k, v in knobs.items():
-                assert lib.fc_debug_set(k, v) == 0, f"knob {k} = {v} refused"
+        with knobs(settings):
             return fa.inner_loop(batch, md, cfg, eps=eps)[1]
-        finally:
-            for k in knobs:
-                lib.fc_debug_set(k, defaults[k])
 
-    try:
-        _, ref, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-        for name, knobs in (("unfused spline", {7: 0}), ("separate pre-attention GEMM launches + LayerNorm -> q fold", {8: 0}), ("separate LayerNorm + q projection", {8: 0, 10: 0}), ("no limb chain", {9: 0}), ("limb chain into the spline GEMM only", {16: 0}), ("limb-chained pre-attention MLP", {8: 0, 19: 1}), ("fp32-input attention", {5: 0}),
-                            ("bf16-limb GEMM", {0: 3}), ("fp32-input MFMA GEMM", {0: 2})):
-            lp = run_with(knobs)
-            err = (lp - ref).abs().max().item()
-            print(f"{name}: max |log-prob - default path| {err:.2e}")
-            assert err < 5e-4, name
-        # the row-resident coupling-MLP chain (the engine takes it where a launch fills the chip; this batch is 3 row tiles: forced) issues the
-        # same MFMAs in the same k order as the per-layer launches and adds bias, residual, GELU and limb split alike: bit-identical
-        lp = run_with({23: 2})
-        assert torch.equal(lp, ref), "the row-resident chain differs from the per-layer launches"
-        # round 4: the hidden layers on the 256 x 256 one-accumulator Linear kernel (spline_wide.hip EPI 1; measured no faster than the row-resident
-        # chain and not on the default path: forced here) -- another arithmetic than the per-layer loops: fp32 noise, not bit for bit
-        lp = run_with({29: 2})
+    _, ref, _ = fa.inner_loop(batch, md, cfg, eps=eps)
+    for name, settings in (("unfused spline", {7: 0}), ("separate pre-attention GEMM launches + LayerNorm -> q fold", {8: 0}), ("separate LayerNorm + q projection", {8: 0, 10: 0}), ("no limb chain", {9: 0}), ("limb chain into the spline GEMM only", {16: 0}), ("limb-chained pre-attention MLP", {8: 0, 19: 1}), ("fp32-input attention", {5: 0}),
+                        ("bf16-limb GEMM", {0: 3}), ("fp32-input MFMA GEMM", {0: 2})):
+        lp = run_with(settings)
         err = (lp - ref).abs().max().item()
-        print(f"hidden layers on the wide one-accumulator kernel: max |log-prob - default path| {err:.2e}")
-        assert err < 5e-4
-        lp = run_with({23: 2, 16: 0})
-        assert (lp - ref).abs().max().item() < 5e-4
-        # round 4: the shipped fused spline layer is the 256 x 256 one-accumulator kernel on 16x16x32 MFMAs (spline_wide.hip, knob 13 = 5): another
-        # arithmetic (one fp32 accumulator, unscaled low limbs, k32 MFMAs) than the 128 x 128 loops beside it -- same log-probs within fp32 noise
-        ref4 = run_with({13: 4})
-        err = (ref4 - ref).abs().max().item()
-        print(f"persistent 128x128 fused spline GEMM (knob 13 = 4): max |log-prob - default path| {err:.2e}")
-        assert err < 5e-4
-        # both main loops of the 128 x 128 family issue the same MFMAs in the same k order and hand the same parameters to the same
-        # spline arithmetic: the LDS-DMA loop with the LDS parameter tile (2) and the persistent transposed product evaluated from the
-        # accumulator registers (4) give bit-identical log-probs
-        lp = run_with({13: 2})
-        print(f"knob 13 = 2: max |diff| {(lp - ref4).abs().max().item():.3e}")
-        assert torch.equal(lp, ref4), "fused spline GEMM variant (knob 13 = 2) differs from the persistent 128x128 loop"
-        lp = run_with({13: 4, 21: 1})                             # rotated k order: another fp32 summation order, same sums
-        err = (lp - ref4).abs().max().item()
-        print(f"persistent fused spline GEMM with rotated k loops: max |log-prob - knob 13 = 4| {err:.2e}")
-        assert err < 5e-4
-        lp = run_with({22: 0})                                    # 128x128 tiles also for launches with few tiles (this test: 5 row tiles -> 64x64 tiles by default)
-        assert torch.equal(lp, ref), "64x64 tiles for small launches changed the limb-chained GEMMs' results"
-    finally:
-        for k, v in defaults.items():
-            lib.fc_debug_set(k, v)
+        print(f"{name}: max |log-prob - default path| {err:.2e}")
+        assert err < 5e-4, name
+    # the row-resident coupling-MLP chain (the engine takes it where a launch fills the chip; this batch is 3 row tiles: forced) issues the
+    # same MFMAs in the same k order as the per-layer launches and adds bias, residual, GELU and limb split alike: bit-identical
+    lp = run_with({23: 2})
+    assert torch.equal(lp, ref), "the row-resident chain differs from the per-layer launches"
+    # round 4: the hidden layers on the 256 x 256 one-accumulator Linear kernel (spline_wide.hip EPI 1; measured no faster than the row-resident
+    # chain and not on the default path: forced here) -- another arithmetic than the per-layer loops: fp32 noise, not bit for bit
+    lp = run_with({29: 2})
+    err = (lp - ref).abs().max().item()
+    print(f"hidden layers on the wide one-accumulator kernel: max |log-prob - default path| {err:.2e}")
+    assert err < 5e-4
+    lp = run_with({23: 2, 16: 0})
+    assert (lp - ref).abs().max().item() < 5e-4
+    # round 4: the shipped fused spline layer is the 256 x 256 one-accumulator kernel on 16x16x32 MFMAs (spline_wide.hip, knob 13 = 5): another
+    # arithmetic (one fp32 accumulator, unscaled low limbs, k32 MFMAs) than the 128 x 128 loops beside it -- same log-probs within fp32 noise
+    ref4 = run_with({13: 4})
+    err = (ref4 - ref).abs().max().item()
+    print(f"persistent 128x128 fused spline GEMM (knob 13 = 4): max |log-prob - default path| {err:.2e}")
+    assert err < 5e-4
+    # both main loops of the 128 x 128 family issue the same MFMAs in the same k order and hand the same parameters to the same
+    # spline arithmetic: the LDS-DMA loop with the LDS parameter tile (2) and the persistent transposed product evaluated from the
+    # accumulator registers (4) give bit-identical log-probs
+    lp = run_with({13: 2})
+    print(f"knob 13 = 2: max |diff| {(lp - ref4).abs().max().item():.3e}")
+    assert torch.equal(lp, ref4), "fused spline GEMM variant (knob 13 = 2) differs from the persistent 128x128 loop"
+    lp = run_with({13: 4, 21: 1})                             # rotated k order: another fp32 summation order, same sums
+    err = (lp - ref4).abs().max().item()
+    print(f"persistent fused spline GEMM with rotated k loops: max |log-prob - knob 13 = 4| {err:.2e}")
+    assert err < 5e-4
+    lp = run_with({22: 0})                                    # 128x128 tiles also for launches with few tiles (this test: 5 row tiles -> 64x64 tiles by default)
+    assert torch.equal(lp, ref), "64x64 tiles for small launches changed the limb-chained GEMMs' results"
 
 
 def test_persistent_spline_gemm_walks_several_tiles_per_workgroup():
@@ -321,8 +310,6 @@ def test_persistent_spline_gemm_walks_several_tiles_per_workgroup():
     (bit for bit the run of that scene alone, one tile per workgroup), and must agree with the 128 x 128 persistent loop (knob 13 = 4: two
     workgroups per CU, 18 x 30 = 540 / 24 x 30 = 720 tiles) within fp32 noise.  That loop in turn must come out exactly as the
     one-tile-per-workgroup kernel of its family (knob 13 = 2: the LDS-DMA loop with the LDS parameter tile)."""
-    from flowcompare_amd import engine
-    lib = engine.lib()
     for B, N in ((3, 768), (3, 1000), (3, 1600), (3, 2048)):       # 2304 rows; 3000 rows + 72 padding rows; 4800 rows = 19 tiles of 256; 6144 = 24
         cfg = fa.named_config("c2_dgcnn_attn_spline", n_flow_layers=2, sample_size=N)
         torch.manual_seed(21)
@@ -335,22 +322,19 @@ def test_persistent_spline_gemm_walks_several_tiles_per_workgroup():
         e0, e1 = torch.rand(B, 200, 6, generator=g), torch.rand(B, N, 6, generator=g)
         eps = [torch.randn(B, N, 294, generator=g).to(DEV)]
         batch = (e0.to(DEV), e1.to(DEV), None)
-        try:
-            _, ref, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-            _, again, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-            assert torch.equal(again, ref), f"{B} x {N}: the wide fused spline kernel is not deterministic"
-            _, solo, _ = fa.inner_loop((batch[0][1:2], batch[1][1:2], None), md, cfg, eps=[eps[0][1:2]])
-            assert torch.equal(solo[0], ref[1]), f"{B} x {N}: a scene's log-probs depend on the tiles it falls on (wide fused spline kernel)"
-            assert lib.fc_debug_set(13, 4) == 0
+        _, ref, _ = fa.inner_loop(batch, md, cfg, eps=eps)
+        _, again, _ = fa.inner_loop(batch, md, cfg, eps=eps)
+        assert torch.equal(again, ref), f"{B} x {N}: the wide fused spline kernel is not deterministic"
+        _, solo, _ = fa.inner_loop((batch[0][1:2], batch[1][1:2], None), md, cfg, eps=[eps[0][1:2]])
+        assert torch.equal(solo[0], ref[1]), f"{B} x {N}: a scene's log-probs depend on the tiles it falls on (wide fused spline kernel)"
+        with knobs({13: 4}):
             _, ref4, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-            err = (ref4 - ref).abs().max().item()
-            print(f"{B} x {N}: wide kernel vs the 128 x 128 persistent loop: max |diff| {err:.2e}")
-            assert err < 1e-3
-            assert lib.fc_debug_set(13, 2) == 0
+        err = (ref4 - ref).abs().max().item()
+        print(f"{B} x {N}: wide kernel vs the 128 x 128 persistent loop: max |diff| {err:.2e}")
+        assert err < 1e-3
+        with knobs({13: 2}):
             _, lp, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-            assert torch.equal(lp, ref4), f"{B} x {N}: persistent fused spline GEMM differs from knob 13 = 2"
-        finally:
-            lib.fc_debug_set(13, 5)
+        assert torch.equal(lp, ref4), f"{B} x {N}: persistent fused spline GEMM differs from knob 13 = 2"
         assert torch.isfinite(ref).all()
 
 
@@ -360,8 +344,6 @@ def test_row_resident_pre_attention_kernel_other_widths_and_activations(latent_d
     x1 widths 100 / 150 / 132 columns (k padded to 128 / 160 / 160: the in_layer's k steps read at run time or compile time, weight
     rows of 32 / 40 sixteen-byte chunks with their two swizzle masks and piece-to-row maps) and the three activations the reference
     accepts, against the separate GEMM launches."""
-    from flowcompare_amd import engine
-    lib = engine.lib()
     cfg = fa.named_config("c2_dgcnn_attn_spline", n_flow_layers=3, sample_size=300, latent_dim=latent_dim, coupling_block_nonlinearity=act)
     torch.manual_seed(31)
     md = fa.initialize_flow(cfg, device=DEV, mode="test")
@@ -370,12 +352,9 @@ def test_row_resident_pre_attention_kernel_other_widths_and_activations(latent_d
     e0, e1 = torch.rand(B, M, 6, generator=g), torch.rand(B, N, 6, generator=g)
     eps = [torch.randn(*sh, generator=g).to(DEV) for sh in md["flow"].noise_shapes(B, N)]      # (a CIF block per layer when cif_latent_dim > latent_dim)
     batch = (e0.to(DEV), e1.to(DEV), None)
-    try:
-        _, lp, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-        lib.fc_debug_set(8, 0)
+    _, lp, _ = fa.inner_loop(batch, md, cfg, eps=eps)
+    with knobs({8: 0}):
         _, ref, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-    finally:
-        lib.fc_debug_set(8, 2)
     err = (lp - ref).abs().max().item()
     print(f"latent {latent_dim}, {act}: max |row-resident - separate launches| {err:.2e}")
     assert torch.isfinite(lp).all() and err < 5e-4
@@ -407,8 +386,6 @@ def test_spline_bin_counts_other_than_eight_match_the_oracle(bins):
     """num_bins_spline 4 and 16 (models/spline_coupling.py:69-169): 13 / 49 parameters per transformed dim, 9 / 2 dims per 128-column tile in
     the dim-major column order (only K = 8 uses the register-slot order and the transposed kernels), evaluated in the GEMM epilogue
     through the LDS parameter tile and, with knob 7 = 0, by the stand-alone spline kernel -- both against the fp64 oracle."""
-    from flowcompare_amd import engine
-    lib = engine.lib()
     cfg = fa.named_config("c2_dgcnn_attn_spline", n_flow_layers=2, sample_size=200, num_bins_spline=bins)
     torch.manual_seed(41)
     md = fa.initialize_flow(cfg, device=DEV, mode="test")
@@ -421,15 +398,12 @@ def test_spline_bin_counts_other_than_eight_match_the_oracle(bins):
     sd_e = {k: v.cpu().double() for k, v in md["input_embedder"].state_dict().items()}
     with torch.no_grad():
         _, lp_o, bpd_o = O.inner_loop(cfg, sd_f, sd_e, (e0.double(), e1.double(), None), [e.double() for e in eps])
-    try:
-        for fused in (1, 0):
-            lib.fc_debug_set(7, fused)
+    for fused in (1, 0):
+        with knobs({7: fused}):
             _, lp, bpd = fa.inner_loop(batch, md, cfg, eps=[e.to(DEV) for e in eps])
-            d = (lp.cpu().double() - lp_o).abs()
-            print(f"{bins} bins, fused spline {fused}: max {d.max():.2e} bpd diff {abs(float(bpd) - float(bpd_o)):.2e}")
-            assert abs(float(bpd) - float(bpd_o)) < BPD_TOL and d.max() < PER_POINT_TOL
-    finally:
-        lib.fc_debug_set(7, 1)
+        d = (lp.cpu().double() - lp_o).abs()
+        print(f"{bins} bins, fused spline {fused}: max {d.max():.2e} bpd diff {abs(float(bpd) - float(bpd_o)):.2e}")
+        assert abs(float(bpd) - float(bpd_o)) < BPD_TOL and d.max() < PER_POINT_TOL
 
 
 def test_cif_stack_at_real_layer_widths_matches_the_oracle():
@@ -455,17 +429,12 @@ def test_cif_stack_at_real_layer_widths_matches_the_oracle():
     assert abs(float(bpd) - float(bpd_o)) < BPD_TOL and d.max() < PER_POINT_TOL
     # the tiles the range guard falls back to (bf16 limbs on the 128x320 tile, two column tiles -> atomics on the log-prob) and the
     # fp32-input MFMA variant run the same pair epilogues
-    from flowcompare_amd import engine
-    lib = engine.lib()
-    try:
-        for name, v in (("bf16-limb GEMM", 3), ("fp32-input MFMA GEMM", 2)):
-            lib.fc_debug_set(0, v)
+    for name, v in (("bf16-limb GEMM", 3), ("fp32-input MFMA GEMM", 2)):
+        with knobs({0: v}):
             _, lp_v, _ = fa.inner_loop((e0.to(DEV), e1.to(DEV), None), md, cfg, eps=[e.to(DEV) for e in eps])
-            err = (lp_v.cpu().double() - lp_o).abs().max().item()
-            print(f"CIF real widths, {name}: max {err:.2e}")
-            assert err < PER_POINT_TOL, name
-    finally:
-        lib.fc_debug_set(0, 5)
+        err = (lp_v.cpu().double() - lp_o).abs().max().item()
+        print(f"CIF real widths, {name}: max {err:.2e}")
+        assert err < PER_POINT_TOL, name
     # the inverse pass (Slice.inverse draws z2, then the affine_cif inverse epilogue) at the same widths, against the oracle's
     h = md["flow"]._engine()
     emb = md["input_embedder"](e0.to(DEV))

@@ -9,6 +9,7 @@ import torch
 
 from conftest import GOLDEN
 from flowcompare_amd import engine
+from knob_util import knobs
 from oracle import flow_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -173,30 +174,26 @@ def test_one_accumulator_limb_form_is_at_least_as_accurate_as_an_fp32_fmaf_chain
 def test_split_variants_match_fp64_like_fp32():
     """The split GEMM main loops -- 2 fp16 limbs / 3 MFMAs per product block (variant 5, the default) and 3 bf16 limbs / 6 MFMAs
     (variant 3, its unbounded-range fallback) -- must be as accurate as the fp32-input MFMA loop (variant 2)."""
-    lib = engine.lib()
-    try:
-        for rows, N, K, act, xs in ((1000, 512, 512, "gelu", 3.0), (513, 3750, 512, "none", 3.0), (300, 256, 150, "none", 3.0),
-                                    (300, 64, 256, "none", 3.0), (600, 512, 512, "none", 1e-3), (600, 512, 512, "none", 300.0)):
-            x, W, b = _rand(rows, K, seed=1, scale=xs), _rand(N, K, seed=2, scale=K ** -0.5), _rand(N, seed=3, scale=0.1 * min(xs, 1.0))
-            ref = torch.nn.functional.linear(x.double(), W.double(), b.double())
-            if act == "gelu":
-                ref = torch.nn.functional.gelu(ref)
-            errs = {}
-            for var in (2, 3, 5):
-                lib.fc_debug_set(0, var)
+    for rows, N, K, act, xs in ((1000, 512, 512, "gelu", 3.0), (513, 3750, 512, "none", 3.0), (300, 256, 150, "none", 3.0),
+                                (300, 64, 256, "none", 3.0), (600, 512, 512, "none", 1e-3), (600, 512, 512, "none", 300.0)):
+        x, W, b = _rand(rows, K, seed=1, scale=xs), _rand(N, K, seed=2, scale=K ** -0.5), _rand(N, seed=3, scale=0.1 * min(xs, 1.0))
+        ref = torch.nn.functional.linear(x.double(), W.double(), b.double())
+        if act == "gelu":
+            ref = torch.nn.functional.gelu(ref)
+        errs = {}
+        for var in (2, 3, 5):
+            with knobs({0: var}):
                 y = engine.op_linear(x.to(DEV), W.to(DEV), b.to(DEV), None, act).cpu().double()
-                errs[var] = (y - ref).abs().max().item()
-            print(f"split {rows}x{N}x{K} |x|~{xs}: fp32-mfma err {errs[2]:.2e}  split-bf16 err {errs[3]:.2e}  split-fp16 err {errs[5]:.2e}")
-            for var in (3, 5):
-                assert errs[var] < 2e-6 * max(1.0, K ** 0.5) * max(xs / 3.0, 1e-3) and errs[var] < 4 * errs[2] + 1e-7 * xs
-        g = torch.Generator().manual_seed(5)
-        x = torch.randint(-8, 9, (384, 200), generator=g).float()
-        W = torch.randint(-8, 9, (512, 200), generator=g).float()
+            errs[var] = (y - ref).abs().max().item()
+        print(f"split {rows}x{N}x{K} |x|~{xs}: fp32-mfma err {errs[2]:.2e}  split-bf16 err {errs[3]:.2e}  split-fp16 err {errs[5]:.2e}")
         for var in (3, 5):
-            lib.fc_debug_set(0, var)
+            assert errs[var] < 2e-6 * max(1.0, K ** 0.5) * max(xs / 3.0, 1e-3) and errs[var] < 4 * errs[2] + 1e-7 * xs
+    g = torch.Generator().manual_seed(5)
+    x = torch.randint(-8, 9, (384, 200), generator=g).float()
+    W = torch.randint(-8, 9, (512, 200), generator=g).float()
+    for var in (3, 5):
+        with knobs({0: var}):
             assert torch.equal(engine.op_linear(x.to(DEV), W.to(DEV)).cpu(), x @ W.t())      # small integers: every limb product exact
-    finally:
-        lib.fc_debug_set(0, 5)            # shipped default
 
 
 def test_split_fp16_out_of_range_falls_back_to_bf16_limbs():
@@ -229,14 +226,10 @@ def test_attention_matches_fp64(B, N, M, D):
     scale = D ** -0.5
     w = torch.softmax(q.double() @ k.double().transpose(1, 2) * scale, -1)
     ref = w @ v.double()
-    lib = engine.lib()
-    try:
-        for fp16 in (1, 0):
-            lib.fc_debug_set(5, fp16)
+    for fp16 in (1, 0):
+        with knobs({5: fp16}):
             out = engine.op_attention(q.to(DEV), k.to(DEV), v.to(DEV), scale).cpu().double()
-            assert (out - ref).abs().max().item() < 5e-6, f"attention kernel fp16={fp16}"
-    finally:
-        lib.fc_debug_set(5, 1)
+        assert (out - ref).abs().max().item() < 5e-6, f"attention kernel fp16={fp16}"
 
 
 def test_attention_key_order_and_out_of_range_fallback():
@@ -296,9 +289,8 @@ def test_attention_lazy_reference_on_score_ramps(per_tile):
 def knn_kernel(request):
     """Both k-NN kernels (csrc/knn.hip): 2 = the matrix-core kernel forced at any size (the engine picks it where the launch fills the chip),
     0 = the lane-per-candidate kernel (small launches)."""
-    engine.lib().fc_debug_set(24, request.param)
-    yield request.param
-    engine.lib().fc_debug_set(24, 1)
+    with knobs({24: request.param}):
+        yield request.param
 
 
 def test_knn_golden_and_ties(knn_kernel):
@@ -336,13 +328,11 @@ def test_knn_warm_start_returns_the_same_sets(B, M, C):
     four searches of one cloud in successive feature spaces).  The warm sets only give the initial threshold, so the result must be the
     SAME SET as the cold search whatever they hold: the true neighbours in a nearby feature space (the real case), random indices (a useless
     bound), sets with repeated indices or the query in every slot (no bound at all), out-of-range indices."""
-    L = engine.lib()
     k = 40
     f = _rand(B, M, C, seed=21)
     g = torch.Generator().manual_seed(22)
     near = f + 0.3 * torch.randn(B, M, C, generator=g)
-    try:
-        assert L.fc_debug_set(24, 2) == 0                          # the matrix-core kernel at any size
+    with knobs({24: 2}):                                           # the matrix-core kernel at any size
         cold = engine.op_knn(f.to(DEV), k).cpu().long().sort(-1)[0]
         warm_sets = {
             "neighbours of a perturbed cloud": engine.op_knn(near.to(DEV), k).cpu(),
@@ -355,8 +345,6 @@ def test_knn_warm_start_returns_the_same_sets(B, M, C):
         for name, w in warm_sets.items():
             got = engine.op_knn(f.to(DEV), k, warm=w.to(DEV)).cpu().long().sort(-1)[0]
             assert torch.equal(got, cold), f"warm start from {name}: {(got != cold).any(-1).sum().item()} of {B * M} sets differ"
-    finally:
-        L.fc_debug_set(24, 1)
 
 
 def test_spline_golden_forward_and_inverse():

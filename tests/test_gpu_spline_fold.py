@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import flowcompare_amd as fa
+from knob_util import knobs
 from oracle import flow_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -45,16 +46,12 @@ def _state(cfg, seed, lively=3.0):
 
 def _module(cfg, sd_f, sd_e, fold):
     """a module packed with knob 34 = fold (the pack happens at the first call: `warm` makes it)"""
-    lib = _lib()
-    assert lib.fc_debug_set(34, fold) == 0
-    try:
+    with knobs({34: fold}):
         md = fa.initialize_flow(cfg, device=DEV, mode="test")
         fa.load_flow({"flow": sd_f, "input_embedder": sd_e}, md)
         g = torch.Generator().manual_seed(0)
         e = torch.rand(1, 64, 6, generator=g).to(DEV)
         fa.inner_loop((e, e, None), md, cfg, eps=[torch.randn(*s, generator=g).to(DEV) for s in md["flow"].noise_shapes(1, 64)])
-    finally:
-        lib.fc_debug_set(34, 1)
     return md
 
 
@@ -70,7 +67,6 @@ def _oracle(cfg, sd_f, sd_e, batch, eps, dtype):
 @functools.lru_cache(maxsize=None)
 def _case(latent_dim, B, N, M, layers):
     """every run of one shape, made once and shared by the tests below (nothing here is modified afterwards)"""
-    lib = _lib()
     cfg = fa.named_config("c2_dgcnn_attn_spline", n_flow_layers=layers, sample_size=N, latent_dim=latent_dim, cif_latent_dim=latent_dim)
     sd_f, sd_e, noise_shapes = _state(cfg, 41 + latent_dim)
     g = torch.Generator().manual_seed(42)
@@ -85,11 +81,8 @@ def _case(latent_dim, B, N, M, layers):
         for fold in (1, 0):
             _, lp, bpd = fa.inner_loop(batch_d, mods[fold], cfg, eps=eps_d)
             r[f"lp{fold}"], r[f"bpd{fold}"] = lp, float(bpd)
-        try:
-            assert lib.fc_debug_set(13, 4) == 0
+        with knobs({13: 4}):
             r["lp_128"] = fa.inner_loop(batch_d, mods[0], cfg, eps=eps_d)[1]
-        finally:
-            lib.fc_debug_set(13, 5)
         r["lp64"], r["bpd64"], r["outside"] = _oracle(cfg, sd_f, sd_e, (e0, e1, None), eps, torch.float64)
         r["lp32"] = _oracle(cfg, sd_f, sd_e, (e0, e1, None), eps, torch.float32)[0]
         out["runs"].append(r)

@@ -7,6 +7,7 @@ import torch.nn.functional as F
 import flowcompare_amd as fa
 from flowcompare_amd import modules as M
 from flowcompare_amd import train_ops as T
+from knob_util import knobs
 from oracle import flow_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -215,8 +216,6 @@ def test_spline_parameter_layer_on_the_wide_loop_matches_fp64_and_the_fp32a_loop
     power-of-two scale PER ROW taken from the row maxima the spline backward writes beside it.  Coupling net + spline + backward against
     fp64 autograd through the pinned oracle, no worse than the fp32-A loop (debug knob 31 = 0) -- at gradient magnitudes of a loss that is
     a mean over 65 536 points (1e-5), of order one, and large (300)."""
-    from flowcompare_amd import engine
-    L = engine.lib()
     K, d1, d2 = 8, 150, 150
     torch.manual_seed(11)
     mlp = M.MLP(d1 + 64, [512, 512], d2 * (3 * K + 1)).to(DEV)
@@ -234,7 +233,6 @@ def test_spline_parameter_layer_on_the_wide_loop_matches_fp64_and_the_fp32a_loop
     ((yo * gy.double()).sum() + (lado.sum(-1) * gl.double()).sum()).backward()
 
     def run(wide):
-        assert L.fc_debug_set(31, 1 if wide else 0) == 0
         mlp.zero_grad()
         a, b, xx = x1.to(DEV).requires_grad_(True), c.to(DEV).requires_grad_(True), x2.to(DEV).requires_grad_(True)
         with T.step_guard(device=DEV) as guard:
@@ -248,10 +246,10 @@ def test_spline_parameter_layer_on_the_wide_loop_matches_fp64_and_the_fp32a_loop
         for k, q in mlp.named_parameters():
             errs["d" + k] = _rel(q.grad, sd["m." + k].grad, floor=1e-2 * grad_scale)
         return errs
-    try:
-        wide, base = run(True), run(False)
-    finally:
-        L.fc_debug_set(31, 1)
+    with knobs({31: 1}):
+        wide = run(True)
+    with knobs({31: 0}):
+        base = run(False)
     print(f"rows {rows} gradient scale {grad_scale}: wide loop " + " ".join(f"{k} {v:.1e}" for k, v in wide.items()))
     print(f"{'':>{len(str(rows)) + len(str(grad_scale)) + 22}}fp32-A loop " + " ".join(f"{k} {v:.1e}" for k, v in base.items()))
     for k in wide:
@@ -263,7 +261,6 @@ def _spline_layer_step(hook=None, wide=True):
     of order one) under step_guard with the in-library profile on; `hook` is registered on the MLP's output panel.  Returns (launches of
     the 256 x 256 one-accumulator kernel, range flag, [a.grad, b.grad, xx.grad, every MLP parameter's gradient])."""
     from flowcompare_amd import engine
-    L = engine.lib()
     K, d1, d2, rows = 8, 150, 150, 300
     torch.manual_seed(11)
     mlp = M.MLP(d1 + 64, [512, 512], d2 * (3 * K + 1)).to(DEV)
@@ -275,9 +272,8 @@ def _spline_layer_step(hook=None, wide=True):
     gy, gl = torch.randn(rows, d2, generator=g), torch.randn(rows, generator=g)
     a, b, xx = x1.to(DEV).requires_grad_(True), c.to(DEV).requires_grad_(True), x2.to(DEV).requires_grad_(True)
     try:
-        assert L.fc_debug_set(31, 1 if wide else 0) == 0
         engine.profile_enable(True); engine.profile_stride(1); engine.profile_reset()
-        with T.step_guard(device=DEV) as guard:
+        with knobs({31: 1 if wide else 0}), T.step_guard(device=DEV) as guard:
             pp = T.mlp_panels(mlp, [T.to_panel(a), T.to_panel(b)], [d1, 64], rows, "GELU")
             if hook is not None:
                 pp.register_hook(hook)
@@ -287,7 +283,6 @@ def _spline_layer_step(hook=None, wide=True):
         launches = sum(r["launches"] for r in engine.profile_report() if r["kernel"].startswith("void fc::spline_wide_kernel<3,"))
     finally:
         engine.profile_enable(False); engine.profile_stride(1); engine.profile_reset()
-        L.fc_debug_set(31, 1)
     return launches, overflowed, [a.grad, b.grad, xx.grad] + [q.grad for q in mlp.parameters()]
 
 

@@ -10,6 +10,7 @@ import torch
 import flowcompare_amd as fa
 from flowcompare_amd import engine
 from conftest import E2E_REAL, E2E_TINY, ROOT, Fixture
+from knob_util import knob_get
 
 
 @pytest.mark.parametrize("name", E2E_REAL + E2E_TINY)
@@ -78,24 +79,70 @@ def test_library_exports_every_declared_symbol():
     assert lib.fc_abi_version() == engine.ABI_VERSION
 
 
+# The shipped configuration and each knob's accepted values, by fc_debug_set key: pinned here and nowhere else outside csrc/knobs.h, the list of
+# record.  key: (shipped default, accepted values -- a tuple, or ("min", n) for every value >= n)
+KNOBS = {0: (5, (2, 3, 5)), 2: (10, ("min", 0)), 5: (1, (0, 1)), 7: (1, (0, 1)), 8: (2, (0, 2)), 9: (1, (0, 1)), 10: (1, (0, 1)), 11: (1, (0, 1)),
+         12: (1, (0, 1)), 13: (5, (2, 4, 5)), 14: (0, (0, 1, 2, 3, 4, 5)), 16: (1, (0, 1)), 19: (0, (0, 1)), 20: (0, (0, 1, 2, 3, 4)), 21: (0, (0, 1)),
+         22: (1, (0, 1)), 23: (1, (0, 1, 2)), 24: (1, (0, 1, 2)), 26: (1, (0, 1)), 28: (-1, ("min", -1)), 29: (0, (0, 1, 2)), 31: (1, (0, 1, 3)),
+         32: (1, (0, 1)), 33: (1, (0, 1)), 34: (1, (0, 1))}
+RETIRED_KEYS = (3, 15, 17, 27, 30)
+FC_ERR_INVALID, FC_ERR_UNSUPPORTED = 1, 6
+
+
 def test_debug_knobs_accept_kept_values_and_refuse_removed_ones():
     """fc_debug_set (csrc/ops_api.cpp, host code only) takes the shipped and kept values of the kernel-choice knobs; the values of the
     variants that lost an A/B and were removed come back FC_ERR_UNSUPPORTED, the retired keys FC_ERR_INVALID."""
-    FC_ERR_INVALID, FC_ERR_UNSUPPORTED = 1, 6
     lib = ctypes.CDLL(engine.LIB_PATH)
-    defaults = {0: 5, 8: 2, 13: 5}
     try:
         for key, kept, removed in ((0, (2, 3, 5), (0, 1, 4, 6, 7)), (8, (0, 2), (1,)), (13, (2, 4, 5), (0, 1, 3))):
             for v in kept:
                 assert lib.fc_debug_set(key, v) == 0, (key, v)
             for v in removed:
                 assert lib.fc_debug_set(key, v) == FC_ERR_UNSUPPORTED, (key, v)
-        for key in (3, 15, 17, 27, 30):
+        for key in RETIRED_KEYS:
             for v in (0, 1, 2, 3):
                 assert lib.fc_debug_set(key, v) == FC_ERR_INVALID, (key, v)
     finally:
-        for key, v in defaults.items():
-            assert lib.fc_debug_set(key, v) == 0
+        assert lib.fc_debug_reset() == 0
+
+
+def test_debug_knob_table_defaults_accepted_values_and_reset():
+    """The knob table (csrc/knobs.h) through fc_debug_set / _get / _reset / _name on the built library, host code only: the shipped
+    configuration is KNOBS above; every accepted value round-trips; the nearest values outside a knob's accepted set are refused
+    (FC_ERR_UNSUPPORTED) and leave the setting as it was; retired and unknown keys are FC_ERR_INVALID for set and get and have no name;
+    fc_debug_reset restores the shipped configuration."""
+    lib = ctypes.CDLL(engine.LIB_PATH)
+    lib.fc_debug_name.restype = ctypes.c_char_p
+    shipped = {key: default for key, (default, _) in KNOBS.items()}
+    def values():
+        return {key: knob_get(key, lib) for key in KNOBS}
+    assert values() == shipped, "a knob is not at its shipped default (csrc/knobs.h changed, or an earlier test leaked a setting)"
+    try:
+        for key, (default, accepted) in KNOBS.items():
+            if accepted[0] == "min":
+                inside, outside = (accepted[1], accepted[1] + 1, default, 1000, 2 ** 31 - 1), (accepted[1] - 1, accepted[1] - 2, -2 ** 31)
+            else:
+                inside, outside = accepted, [v for v in range(min(accepted) - 1, max(accepted) + 2) if v not in accepted]
+            assert default in inside
+            for v in inside:
+                assert lib.fc_debug_set(key, v) == 0, (key, v)
+                assert knob_get(key, lib) == v, (key, v)
+                for bad in outside:
+                    assert lib.fc_debug_set(key, bad) == FC_ERR_UNSUPPORTED, (key, bad)
+                    assert knob_get(key, lib) == v, (key, v, bad)
+        assert values() != shipped
+        probe = ctypes.c_int32(77)
+        for key in RETIRED_KEYS + (max(KNOBS) + 1, -1):
+            assert lib.fc_debug_set(key, 1) == FC_ERR_INVALID, key
+            assert lib.fc_debug_get(key, ctypes.byref(probe)) == FC_ERR_INVALID and probe.value == 77, key
+            assert lib.fc_debug_name(key) is None, key
+        names = [lib.fc_debug_name(key) for key in KNOBS]
+        assert all(names) and len(set(names)) == len(names), names
+        assert [key for key in range(-1, max(KNOBS) + 2) if lib.fc_debug_name(key) is not None] == sorted(KNOBS)      # the table has no key beyond KNOBS
+        assert lib.fc_debug_reset() == 0
+        assert values() == shipped
+    finally:
+        lib.fc_debug_reset()
 
 
 def test_no_cpu_fallback():

@@ -2,12 +2,15 @@
 
 PyTorch is plumbing here: device memory (tensors), the current HIP stream and torch.distributed.  Every function
 below hands raw device pointers to the C ABI; nothing is computed in PyTorch and there is no CPU fallback —
-a missing or unloadable library raises immediately.
+a missing or unloadable library raises immediately.  The signature of every entry point is in abi.py: lib() types them all, so a call
+takes plain Python numbers and None, a miscounted or mistyped argument is refused, and an entry that returns an FC_* status raises FcError.
 """
 import ctypes
 import os
 
 import torch
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FCFLOW_LIB", os.path.join(_HERE, "libfcflow.so"))   # FCFLOW_LIB: A/B another build in profiles/kernel_bench.py
@@ -19,30 +22,7 @@ ACTS = {"GELU": 1, "RELU": 2, "ELU": 3}
 PERMUTERS = {"LinearLU": 0, "random_permute": 1, "FullCombiner": 2, "ExponentialCombiner": 3}
 EXPM = {"torch": 0, "original": 1}
 
-EXPORTS = [
-    "fc_abi_version", "fc_last_error",
-    "fc_flow_create", "fc_flow_destroy", "fc_flow_workspace_bytes", "fc_flow_noise_count", "fc_flow_noise_width",
-    "fc_flow_logprob_f32", "fc_flow_inverse_f32", "fc_flow_attention_weights_f32",
-    "fc_dgcnn_create", "fc_dgcnn_destroy", "fc_dgcnn_out_dim", "fc_dgcnn_workspace_bytes", "fc_dgcnn_embed_f32",
-    "fc_paconv_create", "fc_paconv_destroy", "fc_paconv_out_dim", "fc_paconv_workspace_bytes", "fc_paconv_embed_f32", "fc_op_fps_f32",
-    "fc_range_check_defer", "fc_range_check_resolve", "fc_range_check_pending",
-    "fc_profile_enable", "fc_profile_reset", "fc_profile_filter", "fc_profile_stride", "fc_profile_report",
-    "fc_op_linear_f32", "fc_op_mlp_hidden_f32", "fc_op_attention_f32", "fc_op_attention_weights_f32", "fc_op_knn_f32", "fc_op_knn_warm_f32", "fc_op_rqspline_f32", "fc_op_expm_action_f32",
-    "fc_stage_fps_f32", "fc_stage_co_unit_sphere_f32", "fc_clamp_infs_f32", "fc_change_map_f32",
-    "fc_stage_voxel_ws_bytes", "fc_stage_voxel_count_f32", "fc_stage_voxel_select_f32", "fc_stage_fps_ragged_f32",
-    "fc_train_linear_pack_bytes", "fc_train_linear_pack_f32", "fc_train_linear_fwd_f32", "fc_train_linear_act_fwd_f32", "fc_train_linear_dgrad_f32", "fc_train_linear_dgrad_act_f32",
-    "fc_train_linear_wgrad_ws_bytes", "fc_train_linear_wgrad_f32", "fc_train_act_fwd_f32", "fc_train_act_bwd_f32",
-    "fc_train_attention_ws_bytes", "fc_train_attention_fwd_f32", "fc_train_attention_bwd_f32",
-    "fc_train_rqspline_fwd_f32", "fc_train_rqspline_bwd_f32", "fc_train_layernorm_fwd_f32", "fc_train_layernorm_bwd_f32",
-    "fc_train_colsum_ws_bytes", "fc_train_colsum_f32",
-    "fc_train_affine_fwd_f32", "fc_train_affine_bwd_f32", "fc_train_gauss_fwd_f32", "fc_train_gauss_bwd_f32", "fc_train_base_fwd_f32", "fc_train_base_bwd_f32",
-    "fc_train_normlp_fwd_f32", "fc_train_normlp_bwd_f32", "fc_train_expm_fwd_f32", "fc_train_expm_bwd_f32", "fc_train_expm_wide_bwd_f32",
-    "fc_train_edge_ws_bytes", "fc_train_edge_stats_f32", "fc_train_edge_fwd_f32", "fc_train_edge_bwd_prep_f32", "fc_train_edge_bwd_scatter_f32", "fc_train_edge_bwd_gather_f32", "fc_train_pool_fwd_f32", "fc_train_pool_bwd_f32",
-    "fc_op_paconv_knn_f32", "fc_train_paconv_group_f32", "fc_train_softmax_fwd_f32", "fc_train_softmax_bwd_f32", "fc_train_assign_fwd_f32", "fc_train_assign_bwd_f32",
-    "fc_train_centerdiff_fwd_f32", "fc_train_centerdiff_bwd_f32", "fc_train_rows_gather_bwd_f32", "fc_train_three_nn_f32", "fc_train_interp_fwd_f32",
-    "fc_train_sqnorm_ws_bytes", "fc_train_sqnorm_f32", "fc_train_adam_f32",
-    "fc_stage_dense_blocks_f32", "fc_change_map_ragged_f32",
-]
+EXPORTS = list(abi.ENTRIES)          # every entry point include/fcflow.h declares
 
 
 class FcTensor(ctypes.Structure):
@@ -73,35 +53,21 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} not found: build it with `python -m flowcompare_amd.build` "
                                "(flowcompare_amd has no PyTorch/CPU fallback for the flow)")
         L = ctypes.CDLL(LIB_PATH)
-        L.fc_last_error.restype = ctypes.c_char_p
-        L.fc_flow_destroy.restype = None
-        L.fc_dgcnn_destroy.restype = None
-        L.fc_paconv_destroy.restype = None
-        L.fc_train_linear_pack_bytes.restype = ctypes.c_size_t
-        L.fc_train_linear_wgrad_ws_bytes.restype = ctypes.c_size_t
-        L.fc_train_attention_ws_bytes.restype = ctypes.c_size_t
-        L.fc_train_colsum_ws_bytes.restype = ctypes.c_size_t
-        L.fc_train_edge_ws_bytes.restype = ctypes.c_size_t
-        L.fc_train_sqnorm_ws_bytes.restype = ctypes.c_size_t
-        _P, _I = ctypes.c_void_p, ctypes.c_int32
-        L.fc_train_expm_wide_bwd_f32.restype = ctypes.c_int
-        L.fc_train_expm_wide_bwd_f32.argtypes = [_P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P]
-        # the entries that carry the row maxima of a gradient panel (ABI 10): a miscounted argument fails at the call
-        L.fc_train_rqspline_bwd_f32.restype = ctypes.c_int
-        L.fc_train_rqspline_bwd_f32.argtypes = [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P]
-        L.fc_train_linear_dgrad_f32.restype = ctypes.c_int
-        L.fc_train_linear_dgrad_f32.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]
-        L.fc_train_linear_dgrad_act_f32.restype = ctypes.c_int
-        L.fc_train_linear_dgrad_act_f32.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P]
+        abi.bind(L, _errcheck)
         if L.fc_abi_version() != ABI_VERSION:
             raise RuntimeError("libfcflow.so ABI version mismatch: rebuild with `python -m flowcompare_amd.build --force`")
         _lib = L
     return _lib
 
 
-def _check(code):
+def _errcheck(code, func=None, args=None):
+    """errcheck of every entry that returns an FC_* status (abi.bind): a failing call raises by itself."""
     if code != 0:
         raise FcError(code, lib().fc_last_error().decode())
+    return code
+
+
+_check = _errcheck          # earlier spelling, for callers that still wrap a call: the status it is handed is 0 by then
 
 
 def _ptr(t):
@@ -179,12 +145,12 @@ class deferred_range_check:
         self.repeated = 0
 
     def __enter__(self):
-        _check(lib().fc_range_check_defer(1))
+        lib().fc_range_check_defer(1)
         return self
 
     def resolve(self):
         n = ctypes.c_int32(0)
-        _check(lib().fc_range_check_resolve(ctypes.byref(n)))
+        lib().fc_range_check_resolve(ctypes.byref(n))
         del _deferred_keep[:]
         self.repeated += n.value
         return n.value
@@ -230,6 +196,12 @@ class _Workspace:
             self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
         return self.buf
 
+    def query(self, size_entry, *args, device):
+        """The buffer at the size that `size_entry(*args, &bytes)` (one of the *_workspace_bytes entries) asks for."""
+        need = ctypes.c_size_t()
+        size_entry(*args, ctypes.byref(need))
+        return self.get(need.value, device)
+
 
 class FlowHandle:
     """fc_flow wrapper: replaces the compute of models.Flow (reference models/transform.py:61-84)."""
@@ -259,7 +231,7 @@ class FlowHandle:
         arr, keep = _tensor_table(state_dict)
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _check(lib().fc_flow_create(ctypes.byref(c), arr, len(arr), ctypes.byref(self._h)))
+            lib().fc_flow_create(ctypes.byref(c), arr, len(arr), ctypes.byref(self._h))
         del keep
         self._ws = _Workspace()
         self.n_noise = lib().fc_flow_noise_count(self._h)
@@ -297,14 +269,11 @@ class FlowHandle:
         x, ctx, extra, eps, B, N, M = self._prep(x, context, extra_context, eps)
         L = lib()
         with torch.cuda.device(self.device):
-            need = ctypes.c_size_t()
-            _check(L.fc_flow_workspace_bytes(self._h, B, N, M, ctypes.byref(need)))
-            ws = self._ws.get(need.value, self.device)
+            ws = self._ws.query(L.fc_flow_workspace_bytes, self._h, B, N, M, device=self.device)
             out = torch.empty(B, N, dtype=torch.float32, device=self.device)
             z = torch.empty(B, N, self.latent_dim, dtype=torch.float32, device=self.device) if return_latent else None
             eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
-            _check(L.fc_flow_logprob_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), _ptr(out), _ptr(z),
-                                         B, N, M, _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
+            L.fc_flow_logprob_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), _ptr(out), _ptr(z), B, N, M, _ptr(ws), ws.numel(), _stream())
             _keep_if_deferred(x, ctx, extra, out, z, ws, *eps)
         return (out, z) if return_latent else out
 
@@ -319,16 +288,14 @@ class FlowHandle:
         L = lib()
         with torch.cuda.device(self.device):
             sel, P, per_scene = _points_table(points, B, N, self.device)
-            need = ctypes.c_size_t()
-            _check(L.fc_flow_workspace_bytes(self._h, B, N, M, ctypes.byref(need)))
-            ws = self._ws.get(need.value, self.device)
+            ws = self._ws.query(L.fc_flow_workspace_bytes, self._h, B, N, M, device=self.device)
             outs = [torch.empty(B, P, M, dtype=torch.float32, device=self.device) for _ in layers]
             lp = torch.empty(B, N, dtype=torch.float32, device=self.device) if return_log_prob else None
             eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
             lay_arr = (ctypes.c_int32 * len(layers))(*layers)
             out_arr = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-            _check(L.fc_flow_attention_weights_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), lay_arr, len(layers), _ptr(sel), P,
-                                                   per_scene, out_arr, _ptr(lp), B, N, M, _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
+            L.fc_flow_attention_weights_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), lay_arr, len(layers), _ptr(sel), P,
+                                            per_scene, out_arr, _ptr(lp), B, N, M, _ptr(ws), ws.numel(), _stream())
             _keep_if_deferred(x, ctx, extra, sel, lp, ws, *eps, *outs)
         return (outs, lp) if return_log_prob else outs
 
@@ -353,13 +320,10 @@ class FlowHandle:
         eps = [_dev_f32(e) for e in eps]
         L = lib()
         with torch.cuda.device(self.device):
-            need = ctypes.c_size_t()
-            _check(L.fc_flow_workspace_bytes(self._h, B, N, M, ctypes.byref(need)))
-            ws = self._ws.get(need.value, self.device)
+            ws = self._ws.query(L.fc_flow_workspace_bytes, self._h, B, N, M, device=self.device)
             out = torch.empty(B, N, self.input_dim, dtype=torch.float32, device=self.device)
             eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
-            _check(L.fc_flow_inverse_f32(self._h, _ptr(z), _ptr(ctx), _ptr(extra), eps_arr, len(eps), _ptr(out), B, N, M,
-                                         _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
+            L.fc_flow_inverse_f32(self._h, _ptr(z), _ptr(ctx), _ptr(extra), eps_arr, len(eps), _ptr(out), B, N, M, _ptr(ws), ws.numel(), _stream())
         return out
 
 
@@ -375,7 +339,7 @@ class DgcnnHandle:
         arr, keep = _tensor_table(state_dict)
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _check(lib().fc_dgcnn_create(int(n_neighbors), int(self.is_global), arr, len(arr), ctypes.byref(self._h)))
+            lib().fc_dgcnn_create(int(n_neighbors), int(self.is_global), arr, len(arr), ctypes.byref(self._h))
         del keep
         self.out_dim = lib().fc_dgcnn_out_dim(self._h)
         self._ws = _Workspace()
@@ -390,12 +354,10 @@ class DgcnnHandle:
         B, M = pts.shape[0], pts.shape[1]
         L = lib()
         with torch.cuda.device(self.device):
-            need = ctypes.c_size_t()
-            _check(L.fc_dgcnn_workspace_bytes(self._h, B, M, ctypes.byref(need)))
-            ws = self._ws.get(need.value, self.device)
+            ws = self._ws.query(L.fc_dgcnn_workspace_bytes, self._h, B, M, device=self.device)
             shape = (B, self.out_dim) if self.is_global else (B, M, self.out_dim)
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
-            _check(L.fc_dgcnn_embed_f32(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
+            L.fc_dgcnn_embed_f32(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
             _keep_if_deferred(pts, out, ws)
         return out
 
@@ -411,7 +373,7 @@ class PaconvHandle:
         arr, keep = _tensor_table(state_dict)
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _check(lib().fc_paconv_create(arr, len(arr), ctypes.byref(self._h)))
+            lib().fc_paconv_create(arr, len(arr), ctypes.byref(self._h))
         del keep
         self.out_dim = lib().fc_paconv_out_dim(self._h)
         self._ws = _Workspace()
@@ -426,11 +388,9 @@ class PaconvHandle:
         B, M = pts.shape[0], pts.shape[1]
         L = lib()
         with torch.cuda.device(self.device):
-            need = ctypes.c_size_t()
-            _check(L.fc_paconv_workspace_bytes(self._h, B, M, ctypes.byref(need)))
-            ws = self._ws.get(need.value, self.device)
+            ws = self._ws.query(L.fc_paconv_workspace_bytes, self._h, B, M, device=self.device)
             out = torch.empty(B, M, self.out_dim, dtype=torch.float32, device=self.device)
-            _check(L.fc_paconv_embed_f32(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
+            L.fc_paconv_embed_f32(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
             _keep_if_deferred(pts, out, ws)
         return out
 
@@ -441,7 +401,7 @@ def op_fps(xyz, m):
     B, n, _ = xyz.shape
     idx = torch.empty(B, m, dtype=torch.int32, device=xyz.device)
     with torch.cuda.device(xyz.device):
-        _check(lib().fc_op_fps_f32(_ptr(xyz), _ptr(idx), B, n, m, _stream()))
+        lib().fc_op_fps_f32(_ptr(xyz), _ptr(idx), B, n, m, _stream())
     return idx
 
 
@@ -451,7 +411,7 @@ def stage_fps(pts, m, n_coord=None):
     B, n, ld = pts.shape
     idx = torch.empty(B, m, dtype=torch.int64, device=pts.device)
     with torch.cuda.device(pts.device):
-        _check(lib().fc_stage_fps_f32(_ptr(pts), ld, ld if n_coord is None else n_coord, _ptr(idx), B, n, m, _stream()))
+        lib().fc_stage_fps_f32(_ptr(pts), ld, ld if n_coord is None else n_coord, _ptr(idx), B, n, m, _stream())
     return idx
 
 
@@ -464,15 +424,14 @@ def stage_co_unit_sphere(p0, p1):
     o0, o1 = torch.empty_like(p0), torch.empty_like(p1)
     inv = torch.empty(B, 4, dtype=torch.float32, device=p0.device)
     with torch.cuda.device(p0.device):
-        _check(lib().fc_stage_co_unit_sphere_f32(_ptr(p0), n0, _ptr(p1), p1.shape[1], ld, _ptr(o0), _ptr(o1), _ptr(inv), B, _stream()))
+        lib().fc_stage_co_unit_sphere_f32(_ptr(p0), n0, _ptr(p1), p1.shape[1], ld, _ptr(o0), _ptr(o1), _ptr(inv), B, _stream())
     return o0, o1, inv
 
 
 def _voxel_args(cloud, centers, dims):
     if len(dims) != 3:
         raise RuntimeError("voxel membership: box dimensions must be three numbers")
-    return (_ptr(cloud), cloud.shape[1], ctypes.c_int64(cloud.shape[0]), _ptr(centers), centers.shape[0],
-            ctypes.c_float(dims[0]), ctypes.c_float(dims[1]), ctypes.c_float(dims[2]))
+    return (_ptr(cloud), cloud.shape[1], cloud.shape[0], _ptr(centers), centers.shape[0], *dims)
 
 
 def stage_voxel_count(cloud, centers, dims):
@@ -480,10 +439,9 @@ def stage_voxel_count(cloud, centers, dims):
     get_voxel box (fc_stage_voxel_count_f32).  `ws` is what stage_voxel_select needs for the same cloud, centers and dims."""
     P, K = cloud.shape[0], centers.shape[0]
     counts = torch.empty(K, dtype=torch.int32, device=cloud.device)
-    lib().fc_stage_voxel_ws_bytes.restype = ctypes.c_size_t        # here, not in lib(): an FCFLOW_LIB built before these entries still loads
     with torch.cuda.device(cloud.device):
-        ws = torch.empty(lib().fc_stage_voxel_ws_bytes(ctypes.c_int64(P), K), dtype=torch.uint8, device=cloud.device)
-        _check(lib().fc_stage_voxel_count_f32(*_voxel_args(cloud, centers, dims), _ptr(counts), _ptr(ws), ctypes.c_size_t(ws.numel()), _stream()))
+        ws = torch.empty(lib().fc_stage_voxel_ws_bytes(P, K), dtype=torch.uint8, device=cloud.device)
+        lib().fc_stage_voxel_count_f32(*_voxel_args(cloud, centers, dims), _ptr(counts), _ptr(ws), ws.numel(), _stream())
     return counts, ws
 
 
@@ -492,8 +450,7 @@ def stage_voxel_select(cloud, centers, dims, offsets, total, ws):
     device = exclusive prefix of stage_voxel_count's counts, ws = that call's workspace."""
     rows = torch.empty(total, dtype=torch.int32, device=cloud.device)
     with torch.cuda.device(cloud.device):
-        _check(lib().fc_stage_voxel_select_f32(*_voxel_args(cloud, centers, dims), _ptr(offsets), _ptr(rows), ctypes.c_int64(total), _ptr(ws),
-                                               ctypes.c_size_t(ws.numel()), _stream()))
+        lib().fc_stage_voxel_select_f32(*_voxel_args(cloud, centers, dims), _ptr(offsets), _ptr(rows), total, _ptr(ws), ws.numel(), _stream())
     return rows
 
 
@@ -504,8 +461,8 @@ def stage_fps_ragged(cloud, offsets, rows, m, max_rows, voxel_ids=None):
     idx = torch.empty(n_vox, m, dtype=torch.int64, device=cloud.device)
     scratch = torch.empty(rows.numel(), dtype=torch.float32, device=cloud.device) if max_rows > 24576 else None
     with torch.cuda.device(cloud.device):
-        _check(lib().fc_stage_fps_ragged_f32(_ptr(cloud), cloud.shape[1], cloud.shape[1], ctypes.c_int64(cloud.shape[0]), _ptr(offsets), _ptr(rows),
-                                             _ptr(voxel_ids), n_vox, int(max_rows), int(m), _ptr(idx), _ptr(scratch), _stream()))
+        lib().fc_stage_fps_ragged_f32(_ptr(cloud), cloud.shape[1], cloud.shape[1], cloud.shape[0], _ptr(offsets), _ptr(rows),
+                                      _ptr(voxel_ids), n_vox, int(max_rows), int(m), _ptr(idx), _ptr(scratch), _stream())
     return idx
 
 
@@ -520,8 +477,8 @@ def stage_dense_blocks(cloud, offsets, rows, inverse, block_offsets, n_blocks, b
     block_voxel = torch.empty(n_blocks, dtype=torch.int32, device=cloud.device)
     if n_blocks:
         with torch.cuda.device(cloud.device):
-            _check(lib().fc_stage_dense_blocks_f32(_ptr(cloud), C, C, ctypes.c_int64(cloud.shape[0]), _ptr(offsets), _ptr(rows), _ptr(voxel_ids), n_vox,
-                                                   _ptr(inverse), _ptr(block_offsets), int(block), _ptr(blocks), _ptr(index), _ptr(block_voxel), _stream()))
+            lib().fc_stage_dense_blocks_f32(_ptr(cloud), C, C, cloud.shape[0], _ptr(offsets), _ptr(rows), _ptr(voxel_ids), n_vox,
+                                            _ptr(inverse), _ptr(block_offsets), int(block), _ptr(blocks), _ptr(index), _ptr(block_voxel), _stream())
     return blocks, index, block_voxel
 
 
@@ -530,7 +487,7 @@ def clamp_infs(t):
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
         raise RuntimeError("clamp_infs: expects a contiguous float32 tensor on the GPU (flowcompare_amd has no CPU fallback)")
     with torch.cuda.device(t.device):
-        _check(lib().fc_clamp_infs_f32(_ptr(t), ctypes.c_int64(t.numel()), _stream()))
+        lib().fc_clamp_infs_f32(_ptr(t), t.numel(), _stream())
     return t
 
 
@@ -545,9 +502,8 @@ def change_map(lp10, lp00, multiple, hard_cutoff=None):
     out = torch.empty_like(lp10)
     bad = ctypes.c_int32(0)
     with torch.cuda.device(lp10.device):
-        _check(lib().fc_change_map_f32(_ptr(lp10), N, _ptr(lp00), lp00.shape[1], _ptr(out), B, ctypes.c_float(multiple),
-                                       ctypes.c_float(0.0 if hard_cutoff is None else hard_cutoff), 0 if hard_cutoff is None else 1,
-                                       ctypes.byref(bad), _stream()))
+        lib().fc_change_map_f32(_ptr(lp10), N, _ptr(lp00), lp00.shape[1], _ptr(out), B, multiple, 0.0 if hard_cutoff is None else hard_cutoff,
+                                0 if hard_cutoff is None else 1, ctypes.byref(bad), _stream())
     return out, bool(bad.value)
 
 
@@ -568,9 +524,8 @@ def change_map_ragged(lp10, offsets, lp00, multiple, hard_cutoff=None):
         return out, False
     bad = ctypes.c_int32(0)
     with torch.cuda.device(lp10.device):
-        _check(lib().fc_change_map_ragged_f32(_ptr(lp10), _ptr(offsets), _ptr(lp00), lp00.shape[1], _ptr(out), B, ctypes.c_float(multiple),
-                                              ctypes.c_float(0.0 if hard_cutoff is None else hard_cutoff), 0 if hard_cutoff is None else 1,
-                                              ctypes.byref(bad), _stream()))
+        lib().fc_change_map_ragged_f32(_ptr(lp10), _ptr(offsets), _ptr(lp00), lp00.shape[1], _ptr(out), B, multiple,
+                                       0.0 if hard_cutoff is None else hard_cutoff, 0 if hard_cutoff is None else 1, ctypes.byref(bad), _stream())
     return out, bool(bad.value)
 
 
@@ -583,7 +538,7 @@ def op_linear(x, W, bias=None, residual=None, act="none"):
     b = _dev_f32(bias) if bias is not None else None
     r = _dev_f32(residual) if residual is not None else None
     with torch.cuda.device(x.device):
-        _check(lib().fc_op_linear_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(r), _ptr(y), rows, N, K, code, _stream()))
+        lib().fc_op_linear_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(r), _ptr(y), rows, N, K, code, _stream())
     return y
 
 
@@ -599,8 +554,8 @@ def op_mlp_hidden(x0, x1, state_dict, rowscal=None, act="gelu", use_rows=True):
     out = torch.empty(rows, 512, dtype=torch.float32, device=x0.device)
     arr, keep = _tensor_table({k: v.detach().cpu() for k, v in state_dict.items()})
     with torch.cuda.device(x0.device):
-        _check(lib().fc_op_mlp_hidden_f32(_ptr(x0), x0.shape[1], _ptr(x1), x1.shape[1] if x1 is not None else 0, _ptr(rs), arr, len(arr),
-                                          _ptr(out), rows, code, 2 if use_rows == "wide" else int(bool(use_rows)), _stream()))
+        lib().fc_op_mlp_hidden_f32(_ptr(x0), x0.shape[1], _ptr(x1), x1.shape[1] if x1 is not None else 0, _ptr(rs), arr, len(arr),
+                                   _ptr(out), rows, code, 2 if use_rows == "wide" else int(bool(use_rows)), _stream())
     del keep
     return out
 
@@ -611,7 +566,7 @@ def op_attention(q, k, v, scale):
     M = k.shape[1]
     out = torch.empty_like(q)
     with torch.cuda.device(q.device):
-        _check(lib().fc_op_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, N, M, D, ctypes.c_float(scale), _stream()))
+        lib().fc_op_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, N, M, D, scale, _stream())
     return out
 
 
@@ -621,7 +576,7 @@ def op_attention_ctx(q, c, scale):
     B, N, D = q.shape
     out = torch.empty_like(q)
     with torch.cuda.device(q.device):
-        _check(lib().fc_debug_attention_ctx_f32(_ptr(q), _ptr(c), _ptr(out), B, N, c.shape[1], D, ctypes.c_float(scale), _stream()))
+        _errcheck(lib().fc_debug_attention_ctx_f32(_ptr(q), _ptr(c), _ptr(out), B, N, c.shape[1], D, scale, _stream()))
     return out
 
 
@@ -633,7 +588,7 @@ def op_attention_weights(q, k, scale, points=None):
     with torch.cuda.device(q.device):
         sel, P, per_scene = _points_table(points, B, N, q.device)
         out = torch.empty(B, P, M, dtype=torch.float32, device=q.device)
-        _check(lib().fc_op_attention_weights_f32(_ptr(q), _ptr(k), _ptr(out), _ptr(sel), P, per_scene, B, N, M, D, ctypes.c_float(scale), _stream()))
+        lib().fc_op_attention_weights_f32(_ptr(q), _ptr(k), _ptr(out), _ptr(sel), P, per_scene, B, N, M, D, scale, _stream())
     return out
 
 
@@ -645,12 +600,12 @@ def op_knn(f, k, warm=None):
     idx = torch.empty(B, M, k, dtype=torch.int32, device=f.device)
     with torch.cuda.device(f.device):
         if warm is None:
-            _check(lib().fc_op_knn_f32(_ptr(f), _ptr(idx), B, M, C, k, _stream()))
+            lib().fc_op_knn_f32(_ptr(f), _ptr(idx), B, M, C, k, _stream())
         else:
             warm = warm.to(device=f.device, dtype=torch.int32).contiguous()
             if tuple(warm.shape) != (B, M, k):
                 raise RuntimeError(f"op_knn: warm sets have shape {tuple(warm.shape)}, expected {(B, M, k)}")
-            _check(lib().fc_op_knn_warm_f32(_ptr(f), _ptr(warm), _ptr(idx), B, M, C, k, _stream()))
+            lib().fc_op_knn_warm_f32(_ptr(f), _ptr(warm), _ptr(idx), B, M, C, k, _stream())
     return idx
 
 
@@ -660,32 +615,32 @@ def op_rqspline(x, params, num_bins, inverse=False):
     assert params.numel() == n * (3 * num_bins + 1)
     y, lad = torch.empty_like(x), torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _check(lib().fc_op_rqspline_f32(_ptr(x), _ptr(params), _ptr(y), _ptr(lad), ctypes.c_int64(n), num_bins, int(inverse), _stream()))
+        lib().fc_op_rqspline_f32(_ptr(x), _ptr(params), _ptr(y), _ptr(lad), n, num_bins, int(inverse), _stream())
     return y, lad
 
 
 # ---------------------------------------------------------------- in-library kernel timing
 def profile_enable(on=True):
-    _check(lib().fc_profile_enable(int(bool(on))))
+    lib().fc_profile_enable(int(bool(on)))
 
 
 def profile_filter(kernel_substr=None):
     """Bracket only launches whose kernel name contains `kernel_substr` (None = all)."""
-    _check(lib().fc_profile_filter(kernel_substr.encode() if kernel_substr else None))
+    lib().fc_profile_filter(kernel_substr.encode() if kernel_substr else None)
 
 
 def profile_stride(n=1):
     """Of the launches that pass the filter bracket every `n`-th one only (1 = all); the report then counts the bracketed launches."""
-    _check(lib().fc_profile_stride(int(n)))
+    lib().fc_profile_stride(int(n))
 
 
 def profile_reset():
-    _check(lib().fc_profile_reset())
+    lib().fc_profile_reset()
 
 
 def profile_report():
     """[{kernel, launches, ms, flops, bytes}] accumulated since the last reset (HIP events on the launch stream)."""
     import json
     buf = ctypes.create_string_buffer(1 << 16)
-    _check(lib().fc_profile_report(buf, ctypes.c_size_t(len(buf))))
+    lib().fc_profile_report(buf, len(buf))
     return json.loads(buf.value.decode())

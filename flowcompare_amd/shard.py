@@ -220,7 +220,6 @@ class FlatAdam:
     keeps one per parameter; they only differ for parameters that were skipped in some steps)."""
 
     def __init__(self, reducer, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        import ctypes
         from . import engine
         self.reducer = reducer
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
@@ -236,7 +235,7 @@ class FlatAdam:
                     raise RuntimeError("FlatAdam: parameters must be contiguous")
         self.tables, self._table_key = None, None
         L = engine.lib()
-        nb = max(L.fc_train_sqnorm_ws_bytes(ctypes.c_int64(f.numel())) for f in reducer.flat)
+        nb = max(L.fc_train_sqnorm_ws_bytes(f.numel()) for f in reducer.flat)
         self.ws = torch.empty(nb, dtype=torch.uint8, device=dev)
         self.sq = torch.zeros(len(reducer.flat), dtype=torch.float64, device=dev)
         self.coef = torch.ones(1, dtype=torch.float32, device=dev)
@@ -271,7 +270,6 @@ class FlatAdam:
 
     def step(self, max_norm=None):
         """Global-norm clip (optional) + Adam update; returns the gradient norm (device scalar, before clipping)."""
-        import ctypes
         from . import engine
         L = engine.lib()
         r = self.reducer
@@ -280,8 +278,7 @@ class FlatAdam:
         with torch.cuda.device(dev):
             s = engine._stream()
             for i, f in enumerate(r.flat):
-                engine._check(L.fc_train_sqnorm_f32(engine._ptr(f), ctypes.c_int64(f.numel()), engine._ptr(self.sq), i, engine._ptr(self.ws),
-                                                    ctypes.c_size_t(self.ws.numel()), s))
+                L.fc_train_sqnorm_f32(engine._ptr(f), f.numel(), engine._ptr(self.sq), i, engine._ptr(self.ws), self.ws.numel(), s)
             norm = self.sq.sum().sqrt()                                           # parameter-sized: 39 numbers
             if max_norm:
                 self.coef.copy_((max_norm / (norm + 1e-6)).clamp(max=1.0).to(torch.float32).reshape(1))
@@ -290,10 +287,9 @@ class FlatAdam:
                 ptrs, offs, ct, co, n_chunks = tables[i]
                 if n_chunks == 0:
                     continue
-                engine._check(L.fc_train_adam_f32(engine._ptr(ptrs), engine._ptr(offs), engine._ptr(ct), engine._ptr(co), n_chunks, engine._ptr(f),
-                                                  engine._ptr(self.m[i]), engine._ptr(self.v[i]), engine._ptr(self.coef) if max_norm else ctypes.c_void_p(0),
-                                                  ctypes.c_float(self.lr), ctypes.c_float(self.betas[0]), ctypes.c_float(self.betas[1]),
-                                                  ctypes.c_float(self.eps), ctypes.c_float(self.weight_decay), self.t, s))
+                L.fc_train_adam_f32(engine._ptr(ptrs), engine._ptr(offs), engine._ptr(ct), engine._ptr(co), n_chunks, engine._ptr(f),
+                                    engine._ptr(self.m[i]), engine._ptr(self.v[i]), engine._ptr(self.coef) if max_norm else None,
+                                    self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.t, s)
         return norm.to(torch.float32)
 
     def state_dict(self):

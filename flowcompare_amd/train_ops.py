@@ -166,24 +166,21 @@ class LinearActFn(torch.autograd.Function):
             nb = L.fc_train_linear_pack_bytes(N, segs, len(widths))
             pack = torch.empty(nb, dtype=torch.uint8, device=dev)
             s = engine._stream()
-            engine._check(L.fc_train_linear_pack_f32(engine._ptr(w32), engine._ptr(b32), N, segs, len(widths), engine._ptr(pack),
-                                                     ctypes.c_size_t(nb), _flag_ptr(), s))
+            L.fc_train_linear_pack_f32(engine._ptr(w32), engine._ptr(b32), N, segs, len(widths), engine._ptr(pack), nb, _flag_ptr(), s)
             u = torch.empty(rows_pad, N_pad, dtype=torch.float32, device=dev)
             ldx = _segs([x.shape[1] for x in xs])
             if residual is not None:
                 _check_panel(residual, N)
             if FUSED_ACT and act in (1, 2, 3):                    # GELU / RELU / ELU: u and y = act(u) from the GEMM's epilogue, one launch
                 y = torch.empty_like(u)
-                engine._check(L.fc_train_linear_act_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad,
-                                                            engine._ptr(residual), 0 if residual is None else residual.shape[1],
-                                                            engine._ptr(u), engine._ptr(y), N_pad, act, _flag_ptr(), s))
+                L.fc_train_linear_act_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual),
+                                              0 if residual is None else residual.shape[1], engine._ptr(u), engine._ptr(y), N_pad, act, _flag_ptr(), s)
             else:
-                engine._check(L.fc_train_linear_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad,
-                                                        engine._ptr(residual), 0 if residual is None else residual.shape[1],
-                                                        engine._ptr(u), N_pad, _flag_ptr(), s))
+                L.fc_train_linear_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual),
+                                          0 if residual is None else residual.shape[1], engine._ptr(u), N_pad, _flag_ptr(), s)
                 if act:
                     y = torch.empty_like(u)
-                    engine._check(L.fc_train_act_fwd_f32(engine._ptr(u), engine._ptr(y), rows_pad, N_pad, act, s))
+                    L.fc_train_act_fwd_f32(engine._ptr(u), engine._ptr(y), rows_pad, N_pad, act, s)
                 else:
                     y = u
         ctx.save_for_backward(pack, u if act else None, *xs)
@@ -204,7 +201,7 @@ class LinearActFn(torch.autograd.Function):
             s = engine._stream()
             if act:
                 du = torch.empty_like(dy)
-                engine._check(L.fc_train_act_bwd_f32(engine._ptr(dy), engine._ptr(u), engine._ptr(du), rows_pad, rows, N_pad, act, s))
+                L.fc_train_act_bwd_f32(engine._ptr(dy), engine._ptr(u), engine._ptr(du), rows_pad, rows, N_pad, act, s)
             else:
                 du = dy
             rowmax = _rowmax_for(du)
@@ -215,14 +212,14 @@ class LinearActFn(torch.autograd.Function):
                 dW = torch.empty(N, K, dtype=torch.float32, device=dev) if need[0] else None
                 db = torch.empty(N, dtype=torch.float32, device=dev) if (has_bias and need[1]) else None
                 ldx = _segs([x.shape[1] for x in xs])
-                engine._check(L.fc_train_linear_wgrad_f32(N, segs, len(widths), engine._ptr(du), N_pad, _ptr_array(xs), ldx, rows,
-                                                          engine._ptr(dW), engine._ptr(db), 0, engine._ptr(ws), ctypes.c_size_t(nb), _flag_ptr(), s))
+                L.fc_train_linear_wgrad_f32(N, segs, len(widths), engine._ptr(du), N_pad, _ptr_array(xs), ldx, rows,
+                                            engine._ptr(dW), engine._ptr(db), 0, engine._ptr(ws), nb, _flag_ptr(), s)
             dxs = [None] * len(xs)
             if any(need[6:]):
                 K_pad = sum(_round_up(w, 32) for w in widths)
                 dx = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
-                engine._check(L.fc_train_linear_dgrad_f32(engine._ptr(pack), N, segs, len(widths), engine._ptr(du), N_pad, rows_pad,
-                                                          engine._ptr(dx), K_pad, engine._ptr(rowmax), _flag_ptr(), s))
+                L.fc_train_linear_dgrad_f32(engine._ptr(pack), N, segs, len(widths), engine._ptr(du), N_pad, rows_pad,
+                                            engine._ptr(dx), K_pad, engine._ptr(rowmax), _flag_ptr(), s)
                 off = 0
                 for i, (x, w) in enumerate(zip(xs, widths)):
                     wp = _round_up(w, 32)
@@ -272,8 +269,7 @@ class MlpFn(torch.autograd.Function):
                 N_pad = _round_up(N, 32)
                 nb = L.fc_train_linear_pack_bytes(N, segs, len(cur_w))
                 pack = torch.empty(nb, dtype=torch.uint8, device=dev)
-                engine._check(L.fc_train_linear_pack_f32(engine._ptr(w32), engine._ptr(b32), N, segs, len(cur_w), engine._ptr(pack),
-                                                         ctypes.c_size_t(nb), _flag_ptr(), s))
+                L.fc_train_linear_pack_f32(engine._ptr(w32), engine._ptr(b32), N, segs, len(cur_w), engine._ptr(pack), nb, _flag_ptr(), s)
                 h = l - 1                                             # hidden index: even -> keep = input, odd -> residual = keep
                 last = l == nl - 1
                 residual = keep if (0 < l < nl - 1 and h % 2 == 1) else None
@@ -282,14 +278,13 @@ class MlpFn(torch.autograd.Function):
                 u = torch.empty(rows_pad, N_pad, dtype=torch.float32, device=dev)
                 ldx = _segs([x.shape[1] for x in cur])
                 if last:
-                    engine._check(L.fc_train_linear_fwd_f32(engine._ptr(pack), N, segs, len(cur_w), _ptr_array(cur), ldx, rows_pad,
-                                                            None, 0, engine._ptr(u), N_pad, _flag_ptr(), s))
+                    L.fc_train_linear_fwd_f32(engine._ptr(pack), N, segs, len(cur_w), _ptr_array(cur), ldx, rows_pad,
+                                              None, 0, engine._ptr(u), N_pad, _flag_ptr(), s)
                     y = u
                 else:
                     y = torch.empty_like(u)
-                    engine._check(L.fc_train_linear_act_fwd_f32(engine._ptr(pack), N, segs, len(cur_w), _ptr_array(cur), ldx, rows_pad,
-                                                                engine._ptr(residual), 0 if residual is None else residual.shape[1],
-                                                                engine._ptr(u), engine._ptr(y), N_pad, act, _flag_ptr(), s))
+                    L.fc_train_linear_act_fwd_f32(engine._ptr(pack), N, segs, len(cur_w), _ptr_array(cur), ldx, rows_pad, engine._ptr(residual),
+                                                  0 if residual is None else residual.shape[1], engine._ptr(u), engine._ptr(y), N_pad, act, _flag_ptr(), s)
                 packs.append(pack); us.append(None if last else u); ys.append(y)
                 metas.append((N, K, tuple(cur_w), b is not None, W.dtype))
                 cur, cur_w = [y], [N]
@@ -325,16 +320,16 @@ class MlpFn(torch.autograd.Function):
                     ws = _ws(nb, dev)
                     dW = torch.empty(N, K, dtype=torch.float32, device=dev) if need[wi] else None
                     db = torch.empty(N, dtype=torch.float32, device=dev) if (has_bias and need[wi + 1]) else None
-                    engine._check(L.fc_train_linear_wgrad_f32(N, segs, len(in_w), engine._ptr(du), N_pad, _ptr_array(ins), ldx, rows,
-                                                              engine._ptr(dW), engine._ptr(db), 0, engine._ptr(ws), ctypes.c_size_t(nb), _flag_ptr(), s))
+                    L.fc_train_linear_wgrad_f32(N, segs, len(in_w), engine._ptr(du), N_pad, _ptr_array(ins), ldx, rows,
+                                                engine._ptr(dW), engine._ptr(db), 0, engine._ptr(ws), nb, _flag_ptr(), s)
                     grads[wi] = None if dW is None else dW.to(wdtype)
                     grads[wi + 1] = db
                 if l == 0:
                     if any(need[4:4 + nx]):
                         K_pad = sum(_round_up(w, 32) for w in in_w)
                         dx = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
-                        engine._check(L.fc_train_linear_dgrad_f32(engine._ptr(packs[0]), N, segs, len(in_w), engine._ptr(du), N_pad, rows_pad,
-                                                                  engine._ptr(dx), K_pad, engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s))
+                        L.fc_train_linear_dgrad_f32(engine._ptr(packs[0]), N, segs, len(in_w), engine._ptr(du), N_pad, rows_pad,
+                                                    engine._ptr(dx), K_pad, engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s)
                         off = 0
                         for i, (x, w) in enumerate(zip(xs, in_w)):
                             wp = _round_up(w, 32)
@@ -350,9 +345,8 @@ class MlpFn(torch.autograd.Function):
                 addend = du_next if (l < nl - 1 and h % 2 == 0 and l + 1 < nl - 1) else None
                 K_pad = _round_up(K, 32)
                 du_prev = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
-                engine._check(L.fc_train_linear_dgrad_act_f32(engine._ptr(packs[l]), N, segs, 1, engine._ptr(du), N_pad, rows_pad,
-                                                              engine._ptr(du_prev), K_pad, engine._ptr(addend), engine._ptr(us[l - 1]), act,
-                                                              engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s))
+                L.fc_train_linear_dgrad_act_f32(engine._ptr(packs[l]), N, segs, 1, engine._ptr(du), N_pad, rows_pad, engine._ptr(du_prev), K_pad,
+                                                engine._ptr(addend), engine._ptr(us[l - 1]), act, engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s)
                 du_next, du = du, du_prev
         return tuple(grads)
 
@@ -422,9 +416,8 @@ class AttentionFn(torch.autograd.Function):
             ws = _ws(nb, dev) if _Step.flag is not None else None
             stats = torch.empty(2 * B * N, dtype=torch.float32, device=dev)
             valid = ctypes.c_int32(0)
-            engine._check(L.fc_train_attention_fwd_f32(engine._ptr(q), D, engine._ptr(k), D, engine._ptr(v), D, engine._ptr(out), D, B, N, M, D,
-                                                       ctypes.c_float(scale), engine._ptr(ws), ctypes.c_size_t(nb), engine._ptr(stats),
-                                                       ctypes.byref(valid), _flag_ptr(), engine._stream()))
+            L.fc_train_attention_fwd_f32(engine._ptr(q), D, engine._ptr(k), D, engine._ptr(v), D, engine._ptr(out), D, B, N, M, D, scale, engine._ptr(ws), nb,
+                                         engine._ptr(stats), ctypes.byref(valid), _flag_ptr(), engine._stream())
         ctx.save_for_backward(q, k, v, out, stats)
         ctx.meta = (B, N, M, D, scale, int(valid.value), D0)
         return out if D == D0 else out[:, :D0].contiguous()
@@ -438,10 +431,9 @@ class AttentionFn(torch.autograd.Function):
         dq = _panel_out(q.shape[0], D, B * N, q.device)
         dk, dv = _panel_out(k.shape[0], D, B * M, q.device), _panel_out(k.shape[0], D, B * M, q.device)
         with _OnDevice(q.device):
-            engine._check(L.fc_train_attention_bwd_f32(engine._ptr(q), D, engine._ptr(k), D, engine._ptr(v), D, engine._ptr(out), D,
-                                                       engine._ptr(dout), D, engine._ptr(dq), D, engine._ptr(dk), D, engine._ptr(dv), D,
-                                                       engine._ptr(stats), stats_valid if _Step.flag is not None else 0, B, N, M, D,
-                                                       ctypes.c_float(scale), _flag_ptr(), engine._stream()))
+            L.fc_train_attention_bwd_f32(engine._ptr(q), D, engine._ptr(k), D, engine._ptr(v), D, engine._ptr(out), D, engine._ptr(dout), D, engine._ptr(dq), D,
+                                         engine._ptr(dk), D, engine._ptr(dv), D, engine._ptr(stats), stats_valid if _Step.flag is not None else 0, B, N, M, D,
+                                         scale, _flag_ptr(), engine._stream())
         if D != D0:
             dq, dk, dv = (t[:, :D0].contiguous() for t in (dq, dk, dv))
         return dq, dk, dv, None, None, None, None
@@ -463,8 +455,8 @@ class SplineFn(torch.autograd.Function):
         y2 = _panel_out(x2.shape[0], _round_up(d2, 32), rows, x2.device)
         ldj = _vec_out(x2.shape[0], rows, x2.device)
         with _OnDevice(x2.device):
-            engine._check(L.fc_train_rqspline_fwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(params), params.shape[1], engine._ptr(y2),
-                                                      y2.shape[1], engine._ptr(ldj), rows, d2, K, engine._stream()))
+            L.fc_train_rqspline_fwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(params), params.shape[1], engine._ptr(y2),
+                                        y2.shape[1], engine._ptr(ldj), rows, d2, K, engine._stream())
         ctx.save_for_backward(x2, params)
         ctx.meta = (rows, d2, K)
         return y2, ldj
@@ -481,9 +473,9 @@ class SplineFn(torch.autograd.Function):
         # max |row| of dparams for the data gradient of the layer that made `params` (one-accumulator loop: pitches in multiples of 64)
         rowmax = torch.empty(_round_up(rows, ROW_PAD), dtype=torch.float32, device=x2.device) if dparams.shape[1] % 64 == 0 else None
         with _OnDevice(x2.device):
-            engine._check(L.fc_train_rqspline_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(params), params.shape[1], engine._ptr(dy2),
-                                                      dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(dparams),
-                                                      dparams.shape[1], rows, d2, K, engine._ptr(rowmax), engine._stream()))
+            L.fc_train_rqspline_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(params), params.shape[1], engine._ptr(dy2),
+                                        dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(dparams),
+                                        dparams.shape[1], rows, d2, K, engine._ptr(rowmax), engine._stream())
         if rowmax is not None:
             _attach_rowmax(dparams, rowmax)                       # after the call: _panel_out's zero_() of the pad rows counts as an edit
         return dx2, dparams, None, None, None
@@ -498,8 +490,7 @@ def _colsum(a, cols, rows):
     out = torch.empty(cols, dtype=torch.float32, device=a.device)
     nb = L.fc_train_colsum_ws_bytes(cols, rows)
     ws = _ws(nb, a.device)
-    engine._check(L.fc_train_colsum_f32(engine._ptr(a), a.shape[1], cols, rows, engine._ptr(out), 0, engine._ptr(ws), ctypes.c_size_t(nb),
-                                        engine._stream()))
+    L.fc_train_colsum_f32(engine._ptr(a), a.shape[1], cols, rows, engine._ptr(out), 0, engine._ptr(ws), nb, engine._stream())
     return out
 
 
@@ -515,8 +506,8 @@ class LayerNormFn(torch.autograd.Function):
         stats = torch.empty(2 * rows, dtype=torch.float32, device=x.device)
         g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
         with _OnDevice(x.device):
-            engine._check(L.fc_train_layernorm_fwd_f32(engine._ptr(x), x.shape[1], engine._ptr(g32), engine._ptr(b32), engine._ptr(y), y.shape[1],
-                                                       engine._ptr(stats), rows, width, ctypes.c_float(eps), engine._stream()))
+            L.fc_train_layernorm_fwd_f32(engine._ptr(x), x.shape[1], engine._ptr(g32), engine._ptr(b32), engine._ptr(y), y.shape[1],
+                                         engine._ptr(stats), rows, width, eps, engine._stream())
         ctx.save_for_backward(x, g32, stats)
         ctx.meta = (rows, width, gamma.dtype)
         return y
@@ -533,8 +524,8 @@ class LayerNormFn(torch.autograd.Function):
             dx.zero_()
         t = torch.empty(x.shape[0], wp, dtype=torch.float32, device=x.device)
         with _OnDevice(x.device):
-            engine._check(L.fc_train_layernorm_bwd_f32(engine._ptr(x), x.shape[1], engine._ptr(g32), engine._ptr(dy), dy.shape[1], engine._ptr(stats),
-                                                       engine._ptr(dx), dx.shape[1], engine._ptr(t), wp, x.shape[0], rows, width, engine._stream()))
+            L.fc_train_layernorm_bwd_f32(engine._ptr(x), x.shape[1], engine._ptr(g32), engine._ptr(dy), dy.shape[1], engine._ptr(stats),
+                                         engine._ptr(dx), dx.shape[1], engine._ptr(t), wp, x.shape[0], rows, width, engine._stream())
             dgamma = _colsum(t, width, rows).to(pdtype)
             dbeta = _colsum(dy, width, rows).to(pdtype)
         return dx, dgamma, dbeta, None, None
@@ -558,8 +549,8 @@ class AffineFn(torch.autograd.Function):
         y2 = _panel_out(x2.shape[0], _round_up(d2, 32), rows, x2.device)
         ldj = _vec_out(x2.shape[0], rows, x2.device)
         with _OnDevice(x2.device):
-            engine._check(L.fc_train_affine_fwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(st), st.shape[1], engine._ptr(y2), y2.shape[1],
-                                                    engine._ptr(ldj), rows, d2, scale_fn, engine._stream()))
+            L.fc_train_affine_fwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(st), st.shape[1], engine._ptr(y2), y2.shape[1],
+                                      engine._ptr(ldj), rows, d2, scale_fn, engine._stream())
         ctx.save_for_backward(x2, st)
         ctx.meta = (rows, d2, scale_fn)
         return y2, ldj
@@ -573,9 +564,8 @@ class AffineFn(torch.autograd.Function):
         dx2 = _panel_out(x2.shape[0], x2.shape[1], rows, x2.device) if x2.shape[1] == _round_up(d2, 32) else torch.zeros_like(x2)
         dst = _panel_out(st.shape[0], st.shape[1], rows, x2.device) if st.shape[1] == _round_up(2 * d2, 32) else torch.zeros_like(st)
         with _OnDevice(x2.device):
-            engine._check(L.fc_train_affine_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(st), st.shape[1], engine._ptr(dy2), dy2.shape[1],
-                                                    engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(dst), dst.shape[1], rows, d2,
-                                                    scale_fn, engine._stream()))
+            L.fc_train_affine_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(st), st.shape[1], engine._ptr(dy2), dy2.shape[1], engine._ptr(dldj),
+                                      engine._ptr(dx2), dx2.shape[1], engine._ptr(dst), dst.shape[1], rows, d2, scale_fn, engine._stream())
         return dx2, dst, None, None, None
 
 
@@ -595,8 +585,8 @@ class GaussDrawFn(torch.autograd.Function):
         z = _panel_out(p.shape[0], _round_up(nz, 32), rows, p.device)
         ldj = _vec_out(p.shape[0], rows, p.device)
         with _OnDevice(p.device):
-            engine._check(L.fc_train_gauss_fwd_f32(engine._ptr(p), p.shape[1], engine._ptr(eps), engine._ptr(z), z.shape[1], engine._ptr(ldj), rows, nz,
-                                                   ctypes.c_float(clamp), engine._stream()))
+            L.fc_train_gauss_fwd_f32(engine._ptr(p), p.shape[1], engine._ptr(eps), engine._ptr(z), z.shape[1], engine._ptr(ldj), rows, nz,
+                                     clamp, engine._stream())
         ctx.save_for_backward(p, eps)
         ctx.meta = (rows, nz, clamp)
         return z, ldj
@@ -609,8 +599,8 @@ class GaussDrawFn(torch.autograd.Function):
         dz, dldj = dz.contiguous(), dldj.contiguous()
         dp = _panel_out(p.shape[0], p.shape[1], rows, p.device) if p.shape[1] == _round_up(2 * nz, 32) else torch.zeros_like(p)
         with _OnDevice(p.device):
-            engine._check(L.fc_train_gauss_bwd_f32(engine._ptr(p), p.shape[1], engine._ptr(eps), engine._ptr(dz), dz.shape[1], engine._ptr(dldj),
-                                                   engine._ptr(dp), dp.shape[1], rows, nz, ctypes.c_float(clamp), engine._stream()))
+            L.fc_train_gauss_bwd_f32(engine._ptr(p), p.shape[1], engine._ptr(eps), engine._ptr(dz), dz.shape[1], engine._ptr(dldj),
+                                     engine._ptr(dp), dp.shape[1], rows, nz, clamp, engine._stream())
         return dp, None, None, None, None
 
 
@@ -628,8 +618,7 @@ class NormalLogProbFn(torch.autograd.Function):
         _check_panel(p, 2 * nz)
         out = _vec_out(v.shape[0], rows, v.device)
         with _OnDevice(v.device):
-            engine._check(L.fc_train_normlp_fwd_f32(engine._ptr(v), v.shape[1], engine._ptr(p), p.shape[1], engine._ptr(out), rows, nz,
-                                                    ctypes.c_float(clamp), engine._stream()))
+            L.fc_train_normlp_fwd_f32(engine._ptr(v), v.shape[1], engine._ptr(p), p.shape[1], engine._ptr(out), rows, nz, clamp, engine._stream())
         ctx.save_for_backward(v, p)
         ctx.meta = (rows, nz, clamp)
         return out
@@ -643,8 +632,8 @@ class NormalLogProbFn(torch.autograd.Function):
         dv = _panel_out(v.shape[0], v.shape[1], rows, v.device) if v.shape[1] == _round_up(nz, 32) else torch.zeros_like(v)
         dp = _panel_out(p.shape[0], p.shape[1], rows, v.device) if p.shape[1] == _round_up(2 * nz, 32) else torch.zeros_like(p)
         with _OnDevice(v.device):
-            engine._check(L.fc_train_normlp_bwd_f32(engine._ptr(v), v.shape[1], engine._ptr(p), p.shape[1], engine._ptr(g), engine._ptr(dv), dv.shape[1],
-                                                    engine._ptr(dp), dp.shape[1], rows, nz, ctypes.c_float(clamp), engine._stream()))
+            L.fc_train_normlp_bwd_f32(engine._ptr(v), v.shape[1], engine._ptr(p), p.shape[1], engine._ptr(g), engine._ptr(dv), dv.shape[1],
+                                      engine._ptr(dp), dp.shape[1], rows, nz, clamp, engine._stream())
         return dv, dp, None, None, None
 
 
@@ -661,7 +650,7 @@ class BaseDensityFn(torch.autograd.Function):
         _check_panel(x, width)
         out = _vec_out(x.shape[0], rows, x.device)
         with _OnDevice(x.device):
-            engine._check(L.fc_train_base_fwd_f32(engine._ptr(x), x.shape[1], engine._ptr(out), rows, width, engine._stream()))
+            L.fc_train_base_fwd_f32(engine._ptr(x), x.shape[1], engine._ptr(out), rows, width, engine._stream())
         ctx.save_for_backward(x)
         ctx.meta = (rows, width)
         return out
@@ -674,7 +663,7 @@ class BaseDensityFn(torch.autograd.Function):
         g = g.contiguous()
         dx = _panel_out(x.shape[0], x.shape[1], rows, x.device) if x.shape[1] == _round_up(width, 32) else torch.zeros_like(x)
         with _OnDevice(x.device):
-            engine._check(L.fc_train_base_bwd_f32(engine._ptr(x), x.shape[1], engine._ptr(g), engine._ptr(dx), dx.shape[1], rows, width, engine._stream()))
+            L.fc_train_base_bwd_f32(engine._ptr(x), x.shape[1], engine._ptr(g), engine._ptr(dx), dx.shape[1], rows, width, engine._stream())
         return dx, None, None
 
 
@@ -700,15 +689,14 @@ class EdgeBNMaxFn(torch.autograd.Function):
         stats = torch.empty(3 * C, dtype=torch.float32, device=dev)
         out = _panel_out(pq.shape[0], C, rows, dev)
         arg = torch.empty(rows, C, dtype=torch.uint8, device=dev)
-        q_ptr = ctypes.c_void_p(pq.data_ptr() + 4 * C) if has_q else ctypes.c_void_p(0)
+        q_ptr = pq.data_ptr() + 4 * C if has_q else None
         with _OnDevice(dev):
             s = engine._stream()
             nb = L.fc_train_edge_ws_bytes(rows, C)
             ws = _ws(nb, dev)
-            engine._check(L.fc_train_edge_stats_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, ctypes.c_float(bn.eps),
-                                                    engine._ptr(stats), engine._ptr(ws), ctypes.c_size_t(nb), s))
-            engine._check(L.fc_train_edge_fwd_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32),
-                                                  engine._ptr(b32), ctypes.c_float(0.2), engine._ptr(out), C, engine._ptr(arg), s))
+            L.fc_train_edge_stats_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, bn.eps, engine._ptr(stats), engine._ptr(ws), nb, s)
+            L.fc_train_edge_fwd_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32),
+                                    engine._ptr(b32), 0.2, engine._ptr(out), C, engine._ptr(arg), s)
         if bn.track_running_stats and bn.running_mean is not None:
             # torch.nn.BatchNorm train-mode side effect (parameter-sized vectors): running <- (1 - m) running + m batch, unbiased variance
             with torch.no_grad():
@@ -741,30 +729,28 @@ class EdgeBNMaxFn(torch.autograd.Function):
         dev = pq.device
         g = g.contiguous()
         ld = pq.shape[1]
-        q_ptr = ctypes.c_void_p(pq.data_ptr() + 4 * C) if has_q else ctypes.c_void_p(0)
+        q_ptr = pq.data_ptr() + 4 * C if has_q else None
         rows_pad = pq.shape[0]
         t1 = torch.empty(rows_pad, C, dtype=torch.float32, device=dev)
         t2 = torch.empty(rows_pad, C, dtype=torch.float32, device=dev)
         dpq = torch.zeros_like(pq)
         with _OnDevice(dev):
             s = engine._stream()
-            engine._check(L.fc_train_edge_bwd_prep_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32),
-                                                       engine._ptr(b32), ctypes.c_float(0.2), engine._ptr(arg), engine._ptr(g), g.shape[1], engine._ptr(t1),
-                                                       engine._ptr(t2), C, rows_pad, s))
+            L.fc_train_edge_bwd_prep_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32), engine._ptr(b32),
+                                         0.2, engine._ptr(arg), engine._ptr(g), g.shape[1], engine._ptr(t1), engine._ptr(t2), C, rows_pad, s)
             dbeta, dgamma = _colsum(t1, C, rows), _colsum(t2, C, rows)
-            dq_ptr = ctypes.c_void_p(dpq.data_ptr() + 4 * C) if has_q else ctypes.c_void_p(0)
+            dq_ptr = dpq.data_ptr() + 4 * C if has_q else None
             if has_q:
                 # dQ by row sums, dP by an owner-computes gather over the sorted edges: no atomics, bit-reproducible
-                engine._check(L.fc_train_edge_bwd_scatter_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                                              engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta),
-                                                              engine._ptr(dgamma), ctypes.c_void_p(0), ld, dq_ptr, ld, s))
-                engine._check(L.fc_train_edge_bwd_gather_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                                             engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta),
-                                                             engine._ptr(dgamma), engine._ptr(order), engine._ptr(offsets), engine._ptr(dpq), ld, s))
+                L.fc_train_edge_bwd_scatter_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32),
+                                                engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta), engine._ptr(dgamma), None, ld, dq_ptr, ld, s)
+                L.fc_train_edge_bwd_gather_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats),
+                                               engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta),
+                                               engine._ptr(dgamma), engine._ptr(order), engine._ptr(offsets), engine._ptr(dpq), ld, s)
             else:
-                engine._check(L.fc_train_edge_bwd_scatter_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                                              engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta),
-                                                              engine._ptr(dgamma), engine._ptr(dpq), ld, dq_ptr, ld, s))
+                L.fc_train_edge_bwd_scatter_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats),
+                                                engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta),
+                                                engine._ptr(dgamma), engine._ptr(dpq), ld, dq_ptr, ld, s)
         return dpq, dgamma.to(pdtype), dbeta.to(pdtype), None, None, None, None, None
 
 
@@ -793,8 +779,8 @@ class ExpmCouplingFn(torch.autograd.Function):
         ldj = _vec_out(x2.shape[0], rows, x2.device)
         status = torch.zeros(1, dtype=torch.int32, device=x2.device)
         with _OnDevice(x2.device):
-            engine._check(L.fc_train_expm_fwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(y2), y2.shape[1],
-                                                  engine._ptr(ldj), rows, d2, engine._ptr(status), engine._stream()))
+            L.fc_train_expm_fwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(y2), y2.shape[1],
+                                    engine._ptr(ldj), rows, d2, engine._ptr(status), engine._stream())
         if int(status.item()):
             if d2 > EXPM_TRAIN_BWD_MAX_D2:
                 raise RuntimeError("ExponentialCoupling (training forward): " + _EXPM_BOUND_MSG)
@@ -821,15 +807,15 @@ class ExpmCouplingFn(torch.autograd.Function):
         with _OnDevice(x2.device):
             if d2 > EXPM_TRAIN_BWD_MAX_D2:
                 status = torch.zeros(1, dtype=torch.int32, device=x2.device)
-                engine._check(L.fc_train_expm_wide_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(dy2),
-                                                           dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(do), do.shape[1],
-                                                           engine._ptr(dscal), rows, d2, engine._ptr(status), engine._stream()))
+                L.fc_train_expm_wide_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(dy2),
+                                             dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(do), do.shape[1],
+                                             engine._ptr(dscal), rows, d2, engine._ptr(status), engine._stream())
                 if int(status.item()):
                     raise RuntimeError("ExponentialCoupling (training backward): " + _EXPM_BOUND_MSG)
             else:
-                engine._check(L.fc_train_expm_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(dy2),
-                                                      dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(do), do.shape[1],
-                                                      engine._ptr(dscal), rows, d2, engine._stream()))
+                L.fc_train_expm_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(o), o.shape[1], engine._ptr(s4), engine._ptr(dy2),
+                                        dy2.shape[1], engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(do), do.shape[1],
+                                        engine._ptr(dscal), rows, d2, engine._stream())
             ds4 = _colsum(dscal, 4, rows).to(sdtype)
         return dx2, do, ds4, None, None, None
 
@@ -848,7 +834,7 @@ class PoolMaxMeanFn(torch.autograd.Function):
         out = torch.empty(B, 2 * width, dtype=torch.float32, device=t.device)
         arg = torch.empty(B, width, dtype=torch.int32, device=t.device)
         with _OnDevice(t.device):
-            engine._check(L.fc_train_pool_fwd_f32(engine._ptr(t), t.shape[1], width, B, M, engine._ptr(out), 2 * width, engine._ptr(arg), engine._stream()))
+            L.fc_train_pool_fwd_f32(engine._ptr(t), t.shape[1], width, B, M, engine._ptr(out), 2 * width, engine._ptr(arg), engine._stream())
         ctx.save_for_backward(arg)
         ctx.meta = (B, M, width, t.shape)
         return out
@@ -861,7 +847,7 @@ class PoolMaxMeanFn(torch.autograd.Function):
         g = g.contiguous()
         dt = torch.zeros(shape, dtype=torch.float32, device=g.device)
         with _OnDevice(g.device):
-            engine._check(L.fc_train_pool_bwd_f32(engine._ptr(g), g.shape[1], engine._ptr(arg), width, B, M, engine._ptr(dt), shape[1], engine._stream()))
+            L.fc_train_pool_bwd_f32(engine._ptr(g), g.shape[1], engine._ptr(arg), width, B, M, engine._ptr(dt), shape[1], engine._stream())
         return dt, None, None, None
 
 
@@ -878,6 +864,6 @@ def column_stats(panel, width, rows, eps=0.0):
     with _OnDevice(panel.device):
         nb = L.fc_train_edge_ws_bytes(rows, width)
         ws = _ws(nb, panel.device)
-        engine._check(L.fc_train_edge_stats_f32(engine._ptr(panel), panel.shape[1], ctypes.c_void_p(0), 0, ctypes.c_void_p(0), rows, 1, width,
-                                                ctypes.c_float(eps), engine._ptr(stats), engine._ptr(ws), ctypes.c_size_t(nb), engine._stream()))
+        L.fc_train_edge_stats_f32(engine._ptr(panel), panel.shape[1], None, 0, None, rows, 1, width,
+                                  eps, engine._ptr(stats), engine._ptr(ws), nb, engine._stream())
     return stats[:width], stats[2 * width:]

@@ -12,7 +12,6 @@ BatchNorm kernel family with slope 0; softmax, assign_score, the centre differen
 are csrc/train_paconv.hip.  torch on activations: padding / views (panels), nothing else; torch on indices: argsort / bincount of the
 edge lists for the fixed-order gather backwards.
 """
-import ctypes
 
 import torch
 
@@ -50,8 +49,8 @@ class GroupFn(torch.autograd.Function):
         E = T._panel_out(T._round_up(edges, T.ROW_PAD), ldE, edges, feat.device)
         gdiff = torch.zeros(T._round_up(edges, T.ROW_PAD), 4, dtype=torch.float32, device=feat.device)
         with T._OnDevice(feat.device):
-            engine._check(L.fc_train_paconv_group_f32(engine._ptr(xyz), engine._ptr(feat), feat.shape[1], C, engine._ptr(qxyz), engine._ptr(nidx),
-                                                      engine._ptr(E), ldE, engine._ptr(gdiff), B, n, m, K, engine._stream()))
+            L.fc_train_paconv_group_f32(engine._ptr(xyz), engine._ptr(feat), feat.shape[1], C, engine._ptr(qxyz), engine._ptr(nidx),
+                                        engine._ptr(E), ldE, engine._ptr(gdiff), B, n, m, K, engine._stream())
         ctx.save_for_backward(nidx)
         ctx.meta = (C, B, n, m, K, feat.shape)
         ctx.mark_non_differentiable(gdiff)
@@ -72,9 +71,9 @@ class GroupFn(torch.autograd.Function):
         dfeat = torch.empty(fshape, dtype=torch.float32, device=dev)
         with T._OnDevice(dev):
             s = engine._stream()
-            engine._check(L.fc_train_centerdiff_bwd_f32(engine._ptr(dE), dE.shape[1], Cin, K, B * m, engine._ptr(dx), dx.shape[1], s))
-            engine._check(L.fc_train_rows_gather_bwd_f32(engine._ptr(dx), dx.shape[1], 3, C, engine._ptr(order), engine._ptr(offsets), ctypes.c_void_p(0), 1,
-                                                         B * n, fshape[0], engine._ptr(dfeat), fshape[1], s))
+            L.fc_train_centerdiff_bwd_f32(engine._ptr(dE), dE.shape[1], Cin, K, B * m, engine._ptr(dx), dx.shape[1], s)
+            L.fc_train_rows_gather_bwd_f32(engine._ptr(dx), dx.shape[1], 3, C, engine._ptr(order), engine._ptr(offsets), None, 1,
+                                           B * n, fshape[0], engine._ptr(dfeat), fshape[1], s)
         return dfeat, None, None, None, None, None, None, None
 
 
@@ -87,7 +86,7 @@ class CenterDiffFn(torch.autograd.Function):
         rows = groups * K
         E = T._panel_out(x.shape[0], _r32(2 * C), rows, x.device)
         with T._OnDevice(x.device):
-            engine._check(L.fc_train_centerdiff_fwd_f32(engine._ptr(x), x.shape[1], C, K, groups, engine._ptr(E), E.shape[1], engine._stream()))
+            L.fc_train_centerdiff_fwd_f32(engine._ptr(x), x.shape[1], C, K, groups, engine._ptr(E), E.shape[1], engine._stream())
         ctx.meta = (C, K, groups, x.shape)
         return E
 
@@ -98,7 +97,7 @@ class CenterDiffFn(torch.autograd.Function):
         dE = dE.contiguous()
         dx = T._panel_out(xshape[0], xshape[1], groups * K, dE.device)
         with T._OnDevice(dE.device):
-            engine._check(L.fc_train_centerdiff_bwd_f32(engine._ptr(dE), dE.shape[1], C, K, groups, engine._ptr(dx), dx.shape[1], engine._stream()))
+            L.fc_train_centerdiff_bwd_f32(engine._ptr(dE), dE.shape[1], C, K, groups, engine._ptr(dx), dx.shape[1], engine._stream())
         return dx, None, None, None
 
 
@@ -110,7 +109,7 @@ class SoftmaxFn(torch.autograd.Function):
         L = engine.lib()
         y = T._panel_out(x.shape[0], x.shape[1], rows, x.device)
         with T._OnDevice(x.device):
-            engine._check(L.fc_train_softmax_fwd_f32(engine._ptr(x), x.shape[1], width, rows, engine._ptr(y), y.shape[1], engine._stream()))
+            L.fc_train_softmax_fwd_f32(engine._ptr(x), x.shape[1], width, rows, engine._ptr(y), y.shape[1], engine._stream())
         ctx.save_for_backward(y)
         ctx.meta = (width, rows)
         return y
@@ -123,8 +122,8 @@ class SoftmaxFn(torch.autograd.Function):
         dy = dy.contiguous()
         dx = torch.empty_like(y)
         with T._OnDevice(y.device):
-            engine._check(L.fc_train_softmax_bwd_f32(engine._ptr(y), y.shape[1], engine._ptr(dy), dy.shape[1], width, rows, y.shape[0], engine._ptr(dx),
-                                                     dx.shape[1], engine._stream()))
+            L.fc_train_softmax_bwd_f32(engine._ptr(y), y.shape[1], engine._ptr(dy), dy.shape[1], width, rows, y.shape[0], engine._ptr(dx),
+                                       dx.shape[1], engine._stream())
         return dx, None, None
 
 
@@ -136,8 +135,8 @@ class AssignFn(torch.autograd.Function):
         L = engine.lib()
         out = torch.empty(G.shape[0], _r32(Cout), dtype=torch.float32, device=G.device)
         with T._OnDevice(G.device):
-            engine._check(L.fc_train_assign_fwd_f32(engine._ptr(G), G.shape[1], engine._ptr(S), S.shape[1], m, Cout, rows, G.shape[0], engine._ptr(out),
-                                                    out.shape[1], engine._stream()))
+            L.fc_train_assign_fwd_f32(engine._ptr(G), G.shape[1], engine._ptr(S), S.shape[1], m, Cout, rows, G.shape[0], engine._ptr(out),
+                                      out.shape[1], engine._stream())
         ctx.save_for_backward(G, S)
         ctx.meta = (m, Cout, rows)
         return out
@@ -150,8 +149,8 @@ class AssignFn(torch.autograd.Function):
         dout = dout.contiguous()
         dG, dS = torch.empty_like(G), torch.empty_like(S)
         with T._OnDevice(G.device):
-            engine._check(L.fc_train_assign_bwd_f32(engine._ptr(G), G.shape[1], engine._ptr(S), S.shape[1], engine._ptr(dout), dout.shape[1], m, Cout, rows,
-                                                    G.shape[0], engine._ptr(dG), dG.shape[1], engine._ptr(dS), dS.shape[1], engine._stream()))
+            L.fc_train_assign_bwd_f32(engine._ptr(G), G.shape[1], engine._ptr(S), S.shape[1], engine._ptr(dout), dout.shape[1], m, Cout, rows,
+                                      G.shape[0], engine._ptr(dG), dG.shape[1], engine._ptr(dS), dS.shape[1], engine._stream())
         return dG, dS, None, None, None
 
 
@@ -176,10 +175,9 @@ class BNActMaxFn(torch.autograd.Function):
             s = engine._stream()
             nb = L.fc_train_edge_ws_bytes(rows, C)
             ws = T._ws(nb, dev)
-            engine._check(L.fc_train_edge_stats_f32(engine._ptr(P), P.shape[1], ctypes.c_void_p(0), 0, engine._ptr(idx), rows, k, C, ctypes.c_float(bn.eps),
-                                                    engine._ptr(stats), engine._ptr(ws), ctypes.c_size_t(nb), s))
-            engine._check(L.fc_train_edge_fwd_f32(engine._ptr(P), P.shape[1], ctypes.c_void_p(0), 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                                  engine._ptr(g32), engine._ptr(b32), ctypes.c_float(slope), engine._ptr(out), C, engine._ptr(arg), s))
+            L.fc_train_edge_stats_f32(engine._ptr(P), P.shape[1], None, 0, engine._ptr(idx), rows, k, C, bn.eps, engine._ptr(stats), engine._ptr(ws), nb, s)
+            L.fc_train_edge_fwd_f32(engine._ptr(P), P.shape[1], None, 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
+                                    engine._ptr(g32), engine._ptr(b32), slope, engine._ptr(out), C, engine._ptr(arg), s)
         if bn.track_running_stats and bn.running_mean is not None:
             with torch.no_grad():
                 n = rows * k
@@ -209,14 +207,14 @@ class BNActMaxFn(torch.autograd.Function):
         dP = torch.zeros_like(P)
         with T._OnDevice(dev):
             s = engine._stream()
-            engine._check(L.fc_train_edge_bwd_prep_f32(engine._ptr(P), P.shape[1], ctypes.c_void_p(0), 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                                       engine._ptr(g32), engine._ptr(b32), ctypes.c_float(slope), engine._ptr(arg), engine._ptr(g), g.shape[1],
-                                                       engine._ptr(t1), engine._ptr(t2), C, rows_pad, s))
+            L.fc_train_edge_bwd_prep_f32(engine._ptr(P), P.shape[1], None, 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
+                                         engine._ptr(g32), engine._ptr(b32), slope, engine._ptr(arg), engine._ptr(g), g.shape[1],
+                                         engine._ptr(t1), engine._ptr(t2), C, rows_pad, s)
             dbeta, dgamma = T._colsum(t1, C, rows), T._colsum(t2, C, rows)
             # identity indices: every row of P is the target of exactly one edge, so the "scatter" writes each element once (deterministic)
-            engine._check(L.fc_train_edge_bwd_scatter_f32(engine._ptr(P), P.shape[1], ctypes.c_void_p(0), 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                                          engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta), engine._ptr(dgamma),
-                                                          engine._ptr(dP), dP.shape[1], ctypes.c_void_p(0), 0, s))
+            L.fc_train_edge_bwd_scatter_f32(engine._ptr(P), P.shape[1], None, 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
+                                            engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta), engine._ptr(dgamma),
+                                            engine._ptr(dP), dP.shape[1], None, 0, s)
         return dP, dgamma.to(pdtype), dbeta.to(pdtype), None, None, None, None, None, None
 
 
@@ -240,8 +238,8 @@ class InterpFn(torch.autograd.Function):
         L = engine.lib()
         out = torch.empty(T._round_up(rows, T.ROW_PAD), _r32(C), dtype=torch.float32, device=Fk.device)
         with T._OnDevice(Fk.device):
-            engine._check(L.fc_train_interp_fwd_f32(engine._ptr(Fk), Fk.shape[1], C, engine._ptr(idx), engine._ptr(w), rows, out.shape[0], engine._ptr(out),
-                                                    out.shape[1], engine._stream()))
+            L.fc_train_interp_fwd_f32(engine._ptr(Fk), Fk.shape[1], C, engine._ptr(idx), engine._ptr(w), rows, out.shape[0], engine._ptr(out),
+                                      out.shape[1], engine._stream())
         ctx.save_for_backward(idx, w)
         ctx.meta = (C, rows, Fk.shape)
         return out
@@ -256,8 +254,8 @@ class InterpFn(torch.autograd.Function):
         order, offsets = _sorted_edges(idx, n_known)
         dFk = torch.empty(kshape, dtype=torch.float32, device=dout.device)
         with T._OnDevice(dout.device):
-            engine._check(L.fc_train_rows_gather_bwd_f32(engine._ptr(dout), dout.shape[1], 0, C, engine._ptr(order), engine._ptr(offsets), engine._ptr(w), 3,
-                                                         n_known, n_known, engine._ptr(dFk), kshape[1], engine._stream()))
+            L.fc_train_rows_gather_bwd_f32(engine._ptr(dout), dout.shape[1], 0, C, engine._ptr(order), engine._ptr(offsets), engine._ptr(w), 3,
+                                           n_known, n_known, engine._ptr(dFk), kshape[1], engine._stream())
         return dFk, None, None, None, None
 
 
@@ -296,7 +294,7 @@ def paconv_embed(emb, pts):
             gi = (fidx.long() + (torch.arange(B, device=dev) * n)[:, None]).reshape(-1)
             qxyz = xyz[l][gi].contiguous()                                                           # [B*m, 4] (row gather: data movement)
             nidx = torch.empty(B * m, K, dtype=torch.int32, device=dev)
-            engine._check(L.fc_op_paconv_knn_f32(engine._ptr(xyz[l]), engine._ptr(qxyz), engine._ptr(nidx), B, n, m, K, engine._stream()))
+            L.fc_op_paconv_knn_f32(engine._ptr(xyz[l]), engine._ptr(qxyz), engine._ptr(nidx), B, n, m, K, engine._stream())
         edges = B * m * K
         E, gdiff = GroupFn.apply(f_panel, xyz[l], qxyz, nidx, C, B, n, m)
         gd_panel = T.to_panel(gdiff[:edges, :3])
@@ -325,7 +323,7 @@ def paconv_embed(emb, pts):
         with torch.no_grad(), T._OnDevice(dev):
             idx3 = torch.empty(rows, 3, dtype=torch.int32, device=dev)
             w3 = torch.empty(rows, 3, dtype=torch.float32, device=dev)
-            engine._check(L.fc_train_three_nn_f32(engine._ptr(xyz[i]), engine._ptr(xyz[i + 1]), B, nu, mk, engine._ptr(idx3), engine._ptr(w3), engine._stream()))
+            L.fc_train_three_nn_f32(engine._ptr(xyz[i]), engine._ptr(xyz[i + 1]), B, nu, mk, engine._ptr(idx3), engine._ptr(w3), engine._stream())
         x = InterpFn.apply(fk, idx3, w3, C2, rows)
         segs, widths = [x, fu], [C2, C1]
         for blk in emb.FP_modules[i].mlp:

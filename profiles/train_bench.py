@@ -67,7 +67,7 @@ if a.profile:
     lib.fc_profile_enable(0)
     import ctypes
     buf = ctypes.create_string_buffer(1 << 16)
-    lib.fc_profile_report(buf, ctypes.c_size_t(len(buf)))
+    lib.fc_profile_report(buf, len(buf))
     print(buf.value.decode())
 ms = 1e3 * sum(times) / len(times)
 print(json.dumps({"metric": "training step (forward + backward + Adam), points/s", "value": B * N / (ms / 1e3), "ms_per_step": ms, "layers": a.layers,

@@ -88,19 +88,17 @@ def hip_rows_with_decisions(cfg, md, ctx_dev, x, extra, eps):
     """The HIP flow on the given target rows x [1, n, 6] against the device context ctx_dev [1, M, E], with the engine's diagnostic trace
     (fc_debug_flow_trace) switched on: returns (log_prob [n] on the CPU, the inside / outside decision |x2| <= 3 of every spline evaluation
     of the run as one [1, n, d2] bool mask per layer -- taken on the fp32 x2 the coupling kernel reads, with its own comparison)."""
-    import ctypes
     from flowcompare_amd import engine
     h = md["flow"]._engine()
     L = engine.lib()
     n, n_layers, d2 = x.shape[1], cfg["n_flow_layers"], h.latent_dim - h.latent_dim // 2
     buf = torch.zeros(n_layers, n, d2, dtype=torch.float32, device=ctx_dev.device)
-    L.fc_debug_flow_trace.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-    assert L.fc_debug_flow_trace(ctypes.c_void_p(buf.data_ptr()), buf.numel()) == 0
+    assert L.fc_debug_flow_trace(buf.data_ptr(), buf.numel()) == 0
     try:
         lp = h.log_prob(x.to(ctx_dev.device), ctx_dev, None if extra is None else extra.to(ctx_dev.device), [e.to(ctx_dev.device) for e in eps])
         torch.cuda.synchronize()
     finally:
-        L.fc_debug_flow_trace(ctypes.c_void_p(0), 0)
+        L.fc_debug_flow_trace(None, 0)
     x2 = buf.cpu()
     return lp[0].cpu(), [((x2[l] >= -3.0) & (x2[l] <= 3.0))[None] for l in range(n_layers)]
 

@@ -4,7 +4,6 @@ rows the reference materialises as `attn_weights` (models/perceiver.py:108-115) 
 Gate everywhere a comparison with fp64 is made (attn_weights_util.gate):  max |w - w64| <= 4 x E,
 E = max(max |w32 - w64|, 4 * 2^-24 * max w64), with w32 the same quantity from an fp32 evaluation that is NOT the code under test (torch
 on the CPU, the reference's fp32 run in the fixture, the oracle in fp32).  Every test prints the measured ratio max |w - w64| / E."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -304,7 +303,6 @@ def test_range_fallback_pass_rewrites_the_weights():
     net raise the fp16 range flag, the pass repeats on the bf16 limbs (no guard scope: three-launch q, fp32 K) and rewrites the weight
     buffers.  Against the fp64 oracle recorder, gated at 4 x the oracle's own fp32-vs-fp64 error; the log-prob equals inner_loop's."""
     lib = engine.lib()
-    lib.fc_debug_fp16_fallbacks.restype = ctypes.c_int64
     fx = Fixture("e2e_tiny_spline_relu")
     cfg = dict(fx.cfg)
     sd_flow, sd_emb = fx.state_dicts()

@@ -35,8 +35,8 @@ def expm_action(raw, x2, scal4, d2, inverse=False):
     y2 = torch.empty(P, d2, dtype=torch.float32, device=DEV)
     ldj = torch.empty(P, dtype=torch.float32, device=DEV)
     info = torch.empty(P, 4, dtype=torch.float32, device=DEV)
-    engine._check(engine.lib().fc_op_expm_action_f32(engine._ptr(raw), raw.shape[1], engine._ptr(x2), x2.shape[1], engine._ptr(scal4), engine._ptr(y2), d2,
-                                                     engine._ptr(ldj), engine._ptr(info), P, d2, int(inverse), engine._stream()))
+    engine.lib().fc_op_expm_action_f32(engine._ptr(raw), raw.shape[1], engine._ptr(x2), x2.shape[1], engine._ptr(scal4), engine._ptr(y2), d2,
+                                       engine._ptr(ldj), engine._ptr(info), P, d2, int(inverse), engine._stream())
     return y2, ldj, info
 
 

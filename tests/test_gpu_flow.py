@@ -166,10 +166,8 @@ def test_out_of_fp16_range_activations_repeat_on_the_bf16_limb_path():
     GEMMs, and still matches the reference golden.  A ReLU MLP is positively homogeneous, so scaling its
     in_layer and every hidden bias by alpha and its out_layer weight by 1/alpha leaves the flow unchanged while every hidden
     activation of that net grows by alpha."""
-    import ctypes
     from flowcompare_amd import engine
     lib = engine.lib()
-    lib.fc_debug_fp16_fallbacks.restype = ctypes.c_int64
     fx = Fixture("e2e_tiny_spline_relu")
     cfg = dict(fx.cfg)
     sd_flow, sd_emb = fx.state_dicts()
@@ -200,10 +198,8 @@ def test_deferred_range_check_queues_forwards_back_to_back_and_still_repeats_out
     fast pass (no stream synchronisation per call); the flags are read at resolve.  (i) Two forwards queued back to back equal the
     synchronously checked ones bit for bit and nothing is repeated; (ii) a pass that leaves fp16's range (the alpha = 1e6 ReLU net of the
     test above) is repeated at resolve on the bf16-limb loops, its output is rewritten in place and matches the golden."""
-    import ctypes
     from flowcompare_amd import engine
     lib = engine.lib()
-    lib.fc_debug_fp16_fallbacks.restype = ctypes.c_int64
     fx = Fixture("e2e_tiny_spline_relu")
     cfg = dict(fx.cfg)
     sd_flow, sd_emb = fx.state_dicts()

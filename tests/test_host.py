@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import flowcompare_amd as fa
-from flowcompare_amd import engine
+from flowcompare_amd import abi, engine
 from conftest import E2E_REAL, E2E_TINY, ROOT, Fixture
 from knob_util import knob_get
 
@@ -141,6 +141,105 @@ def test_debug_knob_table_defaults_accepted_values_and_reset():
         assert [key for key in range(-1, max(KNOBS) + 2) if lib.fc_debug_name(key) is not None] == sorted(KNOBS)      # the table has no key beyond KNOBS
         assert lib.fc_debug_reset() == 0
         assert values() == shipped
+    finally:
+        lib.fc_debug_reset()
+
+
+# ---- the ctypes signature tables (flowcompare_amd/abi.py) against the C sources
+VALUE_INT_ENTRIES = {"fc_abi_version", "fc_flow_noise_count", "fc_flow_noise_width", "fc_dgcnn_out_dim", "fc_paconv_out_dim", "fc_range_check_pending"}
+C_PROTOTYPE = r"([A-Za-z_][\w ]*?[\s*]+)(fc_\w+)\s*\(([^()]*)\)\s*"
+
+
+def _c_signatures(text, name_prefix, terminator):
+    """{name: (return type as written, parameter kinds)} of every `ret name(args)<terminator>` in C text, comments stripped: a parameter
+    with a `*` is a pointer (P), then int32_t / int (i), int64_t (l), float (f), size_t (z); anything else fails the test."""
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    found = {}
+    for ret, name, args in re.findall(C_PROTOTYPE + re.escape(terminator), text):
+        if not name.startswith(name_prefix):
+            continue
+        kinds = ""
+        for param in ([] if args.strip() in ("", "void") else args.split(",")):
+            words = param.replace("*", " * ").split()
+            kind = "P" if "*" in words else next((k for t, k in (("int64_t", "l"), ("int32_t", "i"), ("int", "i"), ("float", "f"), ("size_t", "z"))
+                                                   if t in words), None)
+            assert kind, f"{name}: parameter '{param.strip()}' has no ctypes kind"
+            kinds += kind
+        assert name not in found, f"{name} found twice"
+        found[name] = (" ".join(ret.replace("*", " * ").split()), kinds)
+    return found
+
+
+def _return_kind(name, ret, status_entries):
+    if "*" in ret:
+        assert ret == "const char *", (name, ret)
+        return "str"
+    kind = {"void": "void", "size_t": "size_t", "int64_t": "int64", "int": "int", "int32_t": "int"}[ret]
+    return "status" if kind == "int" and status_entries and name not in VALUE_INT_ENTRIES else kind
+
+
+def test_signature_table_equals_the_header():
+    """abi.ENTRIES restates include/fcflow.h: the same names, and per entry the return kind and every parameter's kind.  The header cannot
+    tell an int that is a value from an FC_* status: the six value entries are VALUE_INT_ENTRIES above."""
+    declared = _c_signatures(open(os.path.join(ROOT, "include", "fcflow.h")).read(), "fc_", ";")
+    assert len(declared) == 99 and set(declared) == set(abi.ENTRIES) == set(engine.EXPORTS), set(declared) ^ set(abi.ENTRIES)
+    assert VALUE_INT_ENTRIES <= set(declared)
+    for name, (ret, kinds) in declared.items():
+        assert abi.ENTRIES[name] == (_return_kind(name, ret, True), kinds), name
+    by_kind = lambda k: {n for n, (r, _) in abi.ENTRIES.items() if r == k}
+    assert by_kind("int") == VALUE_INT_ENTRIES and by_kind("str") == {"fc_last_error"}
+    assert by_kind("void") == {"fc_flow_destroy", "fc_dgcnn_destroy", "fc_paconv_destroy"}
+    assert len(by_kind("size_t")) == 7 and all(n.endswith("_bytes") for n in by_kind("size_t"))
+
+
+def test_debug_table_equals_the_definitions():
+    """abi.DEBUG_ENTRIES restates the extern "C" fc_debug_* definitions of csrc/ (they have no declaration in the header); none is missing."""
+    csrc = os.path.join(ROOT, "flowcompare_amd", "csrc")
+    defined = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".cpp", ".hip")):
+            for name, sig in _c_signatures(open(os.path.join(csrc, f)).read(), "fc_debug_", "{").items():
+                assert name not in defined, f"{name} defined twice"
+                defined[name] = sig
+    assert {"fc_debug_set", "fc_debug_get", "fc_debug_reset", "fc_debug_name", "fc_debug_fp16_fallbacks", "fc_debug_gemm_stamps"} <= set(defined)
+    assert set(defined) == set(abi.DEBUG_ENTRIES), set(defined) ^ set(abi.DEBUG_ENTRIES)
+    for name, (ret, kinds) in defined.items():
+        assert abi.DEBUG_ENTRIES[name] == (_return_kind(name, ret, False), kinds), name
+    assert abi.DEBUG_ENTRIES["fc_debug_fp16_fallbacks"][0] == abi.DEBUG_ENTRIES["fc_debug_gemm_stamps"][0] == "int64"
+    assert abi.DEBUG_ENTRIES["fc_debug_name"][0] == "str"
+
+
+def test_lib_binds_every_table_entry():
+    """engine.lib() gives every table entry the library exports its argtypes and restype; FC_* status entries raise by themselves, value
+    entries and the fc_debug_* entries hand back what the C function returned."""
+    lib = engine.lib()
+    for table in (abi.ENTRIES, abi.DEBUG_ENTRIES):
+        for name, (ret, kinds) in table.items():
+            assert hasattr(lib, name), f"{name} not exported"               # this build has all of them
+            fn = getattr(lib, name)
+            assert fn.argtypes is not None and len(fn.argtypes) == len(kinds), name
+            assert list(fn.argtypes) == [abi.PARAM_KINDS[k] for k in kinds], name
+            assert fn.restype is abi.RETURN_KINDS[ret], name
+            assert (fn.errcheck is engine._errcheck) == (ret == "status" and table is abi.ENTRIES), name
+
+
+def test_binding_refuses_bad_calls_on_the_host():
+    """What the signature table buys, on host-only paths: a missing argument and a float in an int32_t slot never reach the library; a
+    failing status entry raises FcError with the library's code and message; a debug entry returns its code and raises nothing."""
+    lib = engine.lib()
+    segs = (ctypes.c_int32 * 1)(64)
+    assert lib.fc_train_linear_wgrad_ws_bytes(64, segs, 1, 256) > 0
+    with pytest.raises(TypeError):
+        lib.fc_train_linear_wgrad_ws_bytes(64, segs, 1)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.fc_train_linear_wgrad_ws_bytes(64, segs, 1, 256.0)
+    n = ctypes.c_size_t()
+    with pytest.raises(engine.FcError) as err:
+        lib.fc_flow_workspace_bytes(None, 1, 1, 1, ctypes.byref(n))
+    message = lib.fc_last_error().decode()
+    assert err.value.code == FC_ERR_INVALID and message and message in str(err.value)
+    try:
+        assert lib.fc_debug_set(3, 1) == FC_ERR_INVALID                      # key 3 is retired
     finally:
         lib.fc_debug_reset()
 

@@ -145,6 +145,101 @@ def _check_panel(t, width):
         raise RuntimeError("flowcompare_amd.train_ops: expected a contiguous fp32 HIP panel [rows_pad % 256 == 0, width padded to 32]")
 
 
+def _act_id(act):
+    return act if isinstance(act, int) else ACT_IDS[act]
+
+
+def _grad_panel(x, width, rows):
+    """The gradient panel of the input panel `x`, of which a row-wise kernel writes `rows` rows of round_up(width, 32) columns: zeroed only
+    where that kernel does not write.  A panel of exactly that width comes uninitialised with zero pad rows (_panel_out); a wider one
+    is all zeros, so that the columns the operator never read get no gradient."""
+    if x.shape[1] == _round_up(width, 32):
+        return _panel_out(x.shape[0], x.shape[1], rows, x.device)
+    return torch.zeros_like(x)
+
+
+def _sorted_edges(src_rows, n_src):
+    """edge ids sorted (stable) by the source row they read + start offset of each source row's segment (index plumbing): a backward
+    then sums each row's incoming gradients in a fixed order."""
+    flat = src_rows.reshape(-1).long()
+    order = torch.argsort(flat, stable=True).to(torch.int32)
+    offsets = torch.zeros(n_src + 1, dtype=torch.int32, device=flat.device)
+    offsets[1:] = torch.cumsum(torch.bincount(flat, minlength=n_src), 0).to(torch.int32)
+    return order, offsets
+
+
+# ---------------------------------------------------------------- the training Linear: one implementation under LinearActFn and MlpFn
+def _linear_pack(weight, bias, widths, dev, s):
+    """The weight pack of y = cat(x...) W^T + b for input segments of `widths` columns (forward and data gradient read it)."""
+    L = engine.lib()
+    N = weight.shape[0]
+    w32 = weight.detach().to(torch.float32).contiguous()
+    b32 = None if bias is None else bias.detach().to(torch.float32).contiguous()
+    segs = _segs(widths)
+    nb = L.fc_train_linear_pack_bytes(N, segs, len(widths))
+    pack = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.fc_train_linear_pack_f32(engine._ptr(w32), engine._ptr(b32), N, segs, len(widths), engine._ptr(pack), nb, _flag_ptr(), s)
+    return pack
+
+
+def _linear_fwd(pack, N, widths, xs, rows_pad, residual, act, s):
+    """u = cat(xs) W^T + b (+ residual) -> (u, y).  act 1 / 2 / 3 (GELU / RELU / ELU): y = act(u) from the GEMM's epilogue, one launch;
+    act 0: y is u."""
+    L = engine.lib()
+    N_pad = _round_up(N, 32)
+    u = torch.empty(rows_pad, N_pad, dtype=torch.float32, device=pack.device)
+    segs, ldx = _segs(widths), _segs([x.shape[1] for x in xs])
+    ldr = 0 if residual is None else residual.shape[1]
+    if act:
+        y = torch.empty_like(u)
+        L.fc_train_linear_act_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual), ldr,
+                                      engine._ptr(u), engine._ptr(y), N_pad, act, _flag_ptr(), s)
+    else:
+        y = u
+        L.fc_train_linear_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual), ldr,
+                                  engine._ptr(u), N_pad, _flag_ptr(), s)
+    return u, y
+
+
+def _linear_wgrad(N, K, widths, du, xs, rows, want_dW, want_db, wdtype, s):
+    """(dW in the parameter's dtype, db) from the pre-activation gradient `du` and the input panels; None for what is not wanted."""
+    if not (want_dW or want_db):
+        return None, None
+    L = engine.lib()
+    dev = du.device
+    segs, ldx = _segs(widths), _segs([x.shape[1] for x in xs])
+    nb = L.fc_train_linear_wgrad_ws_bytes(N, segs, len(widths), rows)
+    ws = _ws(nb, dev)
+    dW = torch.empty(N, K, dtype=torch.float32, device=dev) if want_dW else None
+    db = torch.empty(N, dtype=torch.float32, device=dev) if want_db else None
+    L.fc_train_linear_wgrad_f32(N, segs, len(widths), engine._ptr(du), _round_up(N, 32), _ptr_array(xs), ldx, rows,
+                                engine._ptr(dW), engine._ptr(db), 0, engine._ptr(ws), nb, _flag_ptr(), s)
+    return (None if dW is None else dW.to(wdtype)), db
+
+
+def _linear_dgrad(pack, N, widths, du, rows_pad, rowmax, xs, need, s):
+    """The gradient panel of every input panel whose `need` is set (None for the others): du W into one [rows_pad, K_pad] buffer, cut
+    per segment.  `rowmax`: the row maxima of `du` (_rowmax_for) or None."""
+    dxs = [None] * len(xs)
+    if not any(need):
+        return dxs
+    L = engine.lib()
+    K_pad = sum(_round_up(w, 32) for w in widths)
+    dx = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=du.device)
+    L.fc_train_linear_dgrad_f32(engine._ptr(pack), N, _segs(widths), len(widths), engine._ptr(du), _round_up(N, 32), rows_pad,
+                                engine._ptr(dx), K_pad, engine._ptr(rowmax), _flag_ptr(), s)
+    off = 0
+    for i, (x, w) in enumerate(zip(xs, widths)):
+        wp = _round_up(w, 32)
+        if need[i]:
+            g = dx[:, off:off + wp]
+            if x.shape[1] != wp:                                  # a wider panel than the segment reads: its other columns get no gradient
+                g = torch.nn.functional.pad(g, (0, x.shape[1] - wp))
+            dxs[i] = g
+        off += wp
+    return dxs
+
+
 class LinearActFn(torch.autograd.Function):
     """y = act(cat(x...) W^T + b (+ residual)) on panels; forward and backward are HIP kernels (csrc/train.hip)."""
 
@@ -158,31 +253,16 @@ class LinearActFn(torch.autograd.Function):
             _check_panel(x, w)
         rows_pad = xs[0].shape[0]
         dev = weight.device
-        w32 = weight.detach().to(torch.float32).contiguous()
-        b32 = None if bias is None else bias.detach().to(torch.float32).contiguous()
-        segs = _segs(widths)
-        N_pad = _round_up(N, 32)
         with _OnDevice(dev):
-            nb = L.fc_train_linear_pack_bytes(N, segs, len(widths))
-            pack = torch.empty(nb, dtype=torch.uint8, device=dev)
             s = engine._stream()
-            L.fc_train_linear_pack_f32(engine._ptr(w32), engine._ptr(b32), N, segs, len(widths), engine._ptr(pack), nb, _flag_ptr(), s)
-            u = torch.empty(rows_pad, N_pad, dtype=torch.float32, device=dev)
-            ldx = _segs([x.shape[1] for x in xs])
+            pack = _linear_pack(weight, bias, widths, dev, s)
             if residual is not None:
                 _check_panel(residual, N)
-            if FUSED_ACT and act in (1, 2, 3):                    # GELU / RELU / ELU: u and y = act(u) from the GEMM's epilogue, one launch
+            fused = FUSED_ACT and act in (1, 2, 3)
+            u, y = _linear_fwd(pack, N, widths, xs, rows_pad, residual, act if fused else 0, s)
+            if act and not fused:                                 # FUSED_ACT off: the activation as its own pass behind the Linear
                 y = torch.empty_like(u)
-                L.fc_train_linear_act_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual),
-                                              0 if residual is None else residual.shape[1], engine._ptr(u), engine._ptr(y), N_pad, act, _flag_ptr(), s)
-            else:
-                L.fc_train_linear_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual),
-                                          0 if residual is None else residual.shape[1], engine._ptr(u), N_pad, _flag_ptr(), s)
-                if act:
-                    y = torch.empty_like(u)
-                    L.fc_train_act_fwd_f32(engine._ptr(u), engine._ptr(y), rows_pad, N_pad, act, s)
-                else:
-                    y = u
+                L.fc_train_act_fwd_f32(engine._ptr(u), engine._ptr(y), rows_pad, u.shape[1], act, s)
         ctx.save_for_backward(pack, u if act else None, *xs)
         ctx.meta = (N, K, tuple(widths), act, rows, bias is not None, residual is not None, weight.dtype)
         return y
@@ -192,51 +272,25 @@ class LinearActFn(torch.autograd.Function):
         L = engine.lib()
         pack, u, *xs = ctx.saved_tensors
         N, K, widths, act, rows, has_bias, has_res, wdtype = ctx.meta
-        dev = dy.device
-        rows_pad, N_pad = xs[0].shape[0], _round_up(N, 32)
+        rows_pad = xs[0].shape[0]
         dy = dy.contiguous()
-        segs = _segs(widths)
         need = ctx.needs_input_grad
-        with _OnDevice(dev):
+        with _OnDevice(dy.device):
             s = engine._stream()
             if act:
                 du = torch.empty_like(dy)
-                L.fc_train_act_bwd_f32(engine._ptr(dy), engine._ptr(u), engine._ptr(du), rows_pad, rows, N_pad, act, s)
+                L.fc_train_act_bwd_f32(engine._ptr(dy), engine._ptr(u), engine._ptr(du), rows_pad, rows, _round_up(N, 32), act, s)
             else:
                 du = dy
             rowmax = _rowmax_for(du)
-            dW = db = None
-            if need[0] or (has_bias and need[1]):
-                nb = L.fc_train_linear_wgrad_ws_bytes(N, segs, len(widths), rows)
-                ws = _ws(nb, dev)
-                dW = torch.empty(N, K, dtype=torch.float32, device=dev) if need[0] else None
-                db = torch.empty(N, dtype=torch.float32, device=dev) if (has_bias and need[1]) else None
-                ldx = _segs([x.shape[1] for x in xs])
-                L.fc_train_linear_wgrad_f32(N, segs, len(widths), engine._ptr(du), N_pad, _ptr_array(xs), ldx, rows,
-                                            engine._ptr(dW), engine._ptr(db), 0, engine._ptr(ws), nb, _flag_ptr(), s)
-            dxs = [None] * len(xs)
-            if any(need[6:]):
-                K_pad = sum(_round_up(w, 32) for w in widths)
-                dx = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
-                L.fc_train_linear_dgrad_f32(engine._ptr(pack), N, segs, len(widths), engine._ptr(du), N_pad, rows_pad,
-                                            engine._ptr(dx), K_pad, engine._ptr(rowmax), _flag_ptr(), s)
-                off = 0
-                for i, (x, w) in enumerate(zip(xs, widths)):
-                    wp = _round_up(w, 32)
-                    if need[6 + i]:
-                        g = dx[:, off:off + wp]
-                        if x.shape[1] != wp:                      # a wider panel than the segment reads: its other columns get no gradient
-                            g = torch.nn.functional.pad(g, (0, x.shape[1] - wp))
-                        dxs[i] = g
-                    off += wp
-        if dW is not None:
-            dW = dW.to(wdtype)
+            dW, db = _linear_wgrad(N, K, widths, du, xs, rows, need[0], has_bias and need[1], wdtype, s)
+            dxs = _linear_dgrad(pack, N, widths, du, rows_pad, rowmax, xs, need[6:], s)
         return (dW, db, du if (has_res and need[2]) else None, None, None, None, *dxs)
 
 
 def linear_act(xs, widths, weight, bias, rows, act=None, residual=None):
     """act(cat(xs) W^T + b + residual) on panels; `widths` = true widths of the input panels, `rows` = valid rows."""
-    return LinearActFn.apply(weight, bias, residual, ACT_IDS[act] if not isinstance(act, int) else act, rows, tuple(widths), *xs)
+    return LinearActFn.apply(weight, bias, residual, _act_id(act), rows, tuple(widths), *xs)
 
 
 class MlpFn(torch.autograd.Function):
@@ -248,7 +302,6 @@ class MlpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows, act, widths, nx, *t):
-        L = engine.lib()
         xs, params = t[:nx], t[nx:]
         nl = len(params) // 2
         for x, w in zip(xs, widths):
@@ -263,28 +316,13 @@ class MlpFn(torch.autograd.Function):
                 N, K = W.shape
                 if sum(cur_w) != K:
                     raise RuntimeError(f"MlpFn: layer {l} reads {K} features, its input panels hold {cur_w}")
-                w32 = W.detach().to(torch.float32).contiguous()
-                b32 = None if b is None else b.detach().to(torch.float32).contiguous()
-                segs = _segs(cur_w)
-                N_pad = _round_up(N, 32)
-                nb = L.fc_train_linear_pack_bytes(N, segs, len(cur_w))
-                pack = torch.empty(nb, dtype=torch.uint8, device=dev)
-                L.fc_train_linear_pack_f32(engine._ptr(w32), engine._ptr(b32), N, segs, len(cur_w), engine._ptr(pack), nb, _flag_ptr(), s)
+                pack = _linear_pack(W, b, cur_w, dev, s)
                 h = l - 1                                             # hidden index: even -> keep = input, odd -> residual = keep
                 last = l == nl - 1
                 residual = keep if (0 < l < nl - 1 and h % 2 == 1) else None
                 if 0 < l < nl - 1 and h % 2 == 0:
                     keep = cur[0]
-                u = torch.empty(rows_pad, N_pad, dtype=torch.float32, device=dev)
-                ldx = _segs([x.shape[1] for x in cur])
-                if last:
-                    L.fc_train_linear_fwd_f32(engine._ptr(pack), N, segs, len(cur_w), _ptr_array(cur), ldx, rows_pad,
-                                              None, 0, engine._ptr(u), N_pad, _flag_ptr(), s)
-                    y = u
-                else:
-                    y = torch.empty_like(u)
-                    L.fc_train_linear_act_fwd_f32(engine._ptr(pack), N, segs, len(cur_w), _ptr_array(cur), ldx, rows_pad, engine._ptr(residual),
-                                                  0 if residual is None else residual.shape[1], engine._ptr(u), engine._ptr(y), N_pad, act, _flag_ptr(), s)
+                u, y = _linear_fwd(pack, N, cur_w, cur, rows_pad, residual, 0 if last else act, s)     # out_layer has no activation
                 packs.append(pack); us.append(None if last else u); ys.append(y)
                 metas.append((N, K, tuple(cur_w), b is not None, W.dtype))
                 cur, cur_w = [y], [N]
@@ -310,43 +348,19 @@ class MlpFn(torch.autograd.Function):
             s = engine._stream()
             for l in range(nl - 1, -1, -1):
                 N, K, in_w, has_bias, wdtype = metas[l]
-                N_pad = _round_up(N, 32)
                 ins = list(xs) if l == 0 else [ys[l - 1]]
-                segs = _segs(in_w)
-                ldx = _segs([x.shape[1] for x in ins])
                 wi = 4 + nx + 2 * l
-                if need[wi] or (has_bias and need[wi + 1]):
-                    nb = L.fc_train_linear_wgrad_ws_bytes(N, segs, len(in_w), rows)
-                    ws = _ws(nb, dev)
-                    dW = torch.empty(N, K, dtype=torch.float32, device=dev) if need[wi] else None
-                    db = torch.empty(N, dtype=torch.float32, device=dev) if (has_bias and need[wi + 1]) else None
-                    L.fc_train_linear_wgrad_f32(N, segs, len(in_w), engine._ptr(du), N_pad, _ptr_array(ins), ldx, rows,
-                                                engine._ptr(dW), engine._ptr(db), 0, engine._ptr(ws), nb, _flag_ptr(), s)
-                    grads[wi] = None if dW is None else dW.to(wdtype)
-                    grads[wi + 1] = db
+                grads[wi], grads[wi + 1] = _linear_wgrad(N, K, in_w, du, ins, rows, need[wi], has_bias and need[wi + 1], wdtype, s)
                 if l == 0:
-                    if any(need[4:4 + nx]):
-                        K_pad = sum(_round_up(w, 32) for w in in_w)
-                        dx = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
-                        L.fc_train_linear_dgrad_f32(engine._ptr(packs[0]), N, segs, len(in_w), engine._ptr(du), N_pad, rows_pad,
-                                                    engine._ptr(dx), K_pad, engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s)
-                        off = 0
-                        for i, (x, w) in enumerate(zip(xs, in_w)):
-                            wp = _round_up(w, 32)
-                            if need[4 + i]:
-                                g = dx[:, off:off + wp]
-                                if x.shape[1] != wp:
-                                    g = torch.nn.functional.pad(g, (0, x.shape[1] - wp))
-                                grads[4 + i] = g
-                            off += wp
+                    grads[4:4 + nx] = _linear_dgrad(packs[0], N, in_w, du, rows_pad, rowmax if l == nl - 1 else None, xs, need[4:4 + nx], s)
                     break
                 # gradient w.r.t. the previous layer's pre-activation: (du . W + [residual branch]) * act'(u_{l-1})
                 h = l - 1
                 addend = du_next if (l < nl - 1 and h % 2 == 0 and l + 1 < nl - 1) else None
                 K_pad = _round_up(K, 32)
                 du_prev = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
-                L.fc_train_linear_dgrad_act_f32(engine._ptr(packs[l]), N, segs, 1, engine._ptr(du), N_pad, rows_pad, engine._ptr(du_prev), K_pad,
-                                                engine._ptr(addend), engine._ptr(us[l - 1]), act, engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s)
+                L.fc_train_linear_dgrad_act_f32(engine._ptr(packs[l]), N, _segs(in_w), 1, engine._ptr(du), _round_up(N, 32), rows_pad, engine._ptr(du_prev),
+                                                K_pad, engine._ptr(addend), engine._ptr(us[l - 1]), act, engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s)
                 du_next, du = du, du_prev
         return tuple(grads)
 
@@ -356,7 +370,7 @@ FUSED_MLP = os.environ.get("FC_TRAIN_FUSED_MLP", "1") != "0"       # 0: the MLP 
 
 def mlp_panels(mlp, xs, widths, rows, act):
     """models/nets.py:19-30 on panels: act(in) ; even hidden layer: r = x, x = act(W x) ; odd: x = act(r + W x) ; out (no activation)."""
-    act_id = ACT_IDS[act] if not isinstance(act, int) else act
+    act_id = _act_id(act)
     if FUSED_MLP and FUSED_ACT and act_id in (1, 2, 3) and all(l.in_features % 32 == 0 for l in list(mlp.layers) + [mlp.out_layer]):
         params = [mlp.in_layer.weight, mlp.in_layer.bias]
         for layer in mlp.layers:
@@ -467,9 +481,8 @@ class SplineFn(torch.autograd.Function):
         x2, params = ctx.saved_tensors
         rows, d2, K = ctx.meta
         dy2, dldj = dy2.contiguous(), dldj.contiguous()
-        dx2 = _panel_out(x2.shape[0], x2.shape[1], rows, x2.device) if x2.shape[1] == _round_up(d2, 32) else torch.zeros_like(x2)
-        dparams = (_panel_out(params.shape[0], params.shape[1], rows, x2.device) if params.shape[1] == _round_up(d2 * (3 * K + 1), 32)
-                   else torch.zeros_like(params))
+        dx2 = _grad_panel(x2, d2, rows)
+        dparams = _grad_panel(params, d2 * (3 * K + 1), rows)
         # max |row| of dparams for the data gradient of the layer that made `params` (one-accumulator loop: pitches in multiples of 64)
         rowmax = torch.empty(_round_up(rows, ROW_PAD), dtype=torch.float32, device=x2.device) if dparams.shape[1] % 64 == 0 else None
         with _OnDevice(x2.device):
@@ -561,8 +574,8 @@ class AffineFn(torch.autograd.Function):
         x2, st = ctx.saved_tensors
         rows, d2, scale_fn = ctx.meta
         dy2, dldj = dy2.contiguous(), dldj.contiguous()
-        dx2 = _panel_out(x2.shape[0], x2.shape[1], rows, x2.device) if x2.shape[1] == _round_up(d2, 32) else torch.zeros_like(x2)
-        dst = _panel_out(st.shape[0], st.shape[1], rows, x2.device) if st.shape[1] == _round_up(2 * d2, 32) else torch.zeros_like(st)
+        dx2 = _grad_panel(x2, d2, rows)
+        dst = _grad_panel(st, 2 * d2, rows)
         with _OnDevice(x2.device):
             L.fc_train_affine_bwd_f32(engine._ptr(x2), x2.shape[1], engine._ptr(st), st.shape[1], engine._ptr(dy2), dy2.shape[1], engine._ptr(dldj),
                                       engine._ptr(dx2), dx2.shape[1], engine._ptr(dst), dst.shape[1], rows, d2, scale_fn, engine._stream())
@@ -597,7 +610,7 @@ class GaussDrawFn(torch.autograd.Function):
         p, eps = ctx.saved_tensors
         rows, nz, clamp = ctx.meta
         dz, dldj = dz.contiguous(), dldj.contiguous()
-        dp = _panel_out(p.shape[0], p.shape[1], rows, p.device) if p.shape[1] == _round_up(2 * nz, 32) else torch.zeros_like(p)
+        dp = _grad_panel(p, 2 * nz, rows)
         with _OnDevice(p.device):
             L.fc_train_gauss_bwd_f32(engine._ptr(p), p.shape[1], engine._ptr(eps), engine._ptr(dz), dz.shape[1], engine._ptr(dldj),
                                      engine._ptr(dp), dp.shape[1], rows, nz, clamp, engine._stream())
@@ -629,8 +642,8 @@ class NormalLogProbFn(torch.autograd.Function):
         v, p = ctx.saved_tensors
         rows, nz, clamp = ctx.meta
         g = g.contiguous()
-        dv = _panel_out(v.shape[0], v.shape[1], rows, v.device) if v.shape[1] == _round_up(nz, 32) else torch.zeros_like(v)
-        dp = _panel_out(p.shape[0], p.shape[1], rows, v.device) if p.shape[1] == _round_up(2 * nz, 32) else torch.zeros_like(p)
+        dv = _grad_panel(v, nz, rows)
+        dp = _grad_panel(p, 2 * nz, rows)
         with _OnDevice(v.device):
             L.fc_train_normlp_bwd_f32(engine._ptr(v), v.shape[1], engine._ptr(p), p.shape[1], engine._ptr(g), engine._ptr(dv), dv.shape[1],
                                       engine._ptr(dp), dp.shape[1], rows, nz, clamp, engine._stream())
@@ -661,7 +674,7 @@ class BaseDensityFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         rows, width = ctx.meta
         g = g.contiguous()
-        dx = _panel_out(x.shape[0], x.shape[1], rows, x.device) if x.shape[1] == _round_up(width, 32) else torch.zeros_like(x)
+        dx = _grad_panel(x, width, rows)
         with _OnDevice(x.device):
             L.fc_train_base_bwd_f32(engine._ptr(x), x.shape[1], engine._ptr(g), engine._ptr(dx), dx.shape[1], rows, width, engine._stream())
         return dx, None, None
@@ -671,91 +684,92 @@ def base_density(x, rows, width):
     return BaseDensityFn.apply(x, rows, width)
 
 
-class EdgeBNMaxFn(torch.autograd.Function):
-    """One EdgeConv level of the DGCNN embedder in training mode, after the two per-point products (csrc/train_edge.hip):
-    pq panel [rows_pad, 2C] = [P | Q] (or [rows_pad, C] = P alone when idx is None: BatchNorm1d + LeakyReLU of conv5), idx [rows, k]
-    int32 global row indices -> max_j lrelu(BN_batch(P[idx_ij] + Q[i])) as a panel [rows_pad, C].  `bn` is the BatchNorm module:
-    its running statistics are updated exactly as torch does in train mode (momentum, unbiased variance)."""
+def _bn_update_running(bn, stats, C, c_real, n):
+    """torch.nn.BatchNorm's train-mode side effect (parameter-sized vectors) from the batch statistics `stats` = [mean C | . | biased
+    variance C] over n values per channel, on the module's c_real channels: running <- (1 - m) running + m batch, unbiased variance."""
+    if not (bn.track_running_stats and bn.running_mean is not None):
+        return
+    with torch.no_grad():
+        bn.num_batches_tracked += 1
+        if bn.momentum is not None:
+            m = bn.momentum
+            bn.running_mean.mul_(1 - m).add_(stats[:c_real].to(bn.running_mean.dtype), alpha=m)
+            bn.running_var.mul_(1 - m).add_(stats[2 * C:2 * C + c_real].to(bn.running_var.dtype) * (n / max(n - 1, 1)), alpha=m)
+        else:                                                     # momentum=None: cumulative average, factor 1 / num_batches_tracked
+            m = 1.0 / bn.num_batches_tracked.to(bn.running_mean.dtype)
+            bn.running_mean.mul_(1 - m).add_(stats[:c_real].to(bn.running_mean.dtype) * m)
+            bn.running_var.mul_(1 - m).add_(stats[2 * C:2 * C + c_real].to(bn.running_var.dtype) * (n / max(n - 1, 1)) * m)
+
+
+class BatchNormMaxFn(torch.autograd.Function):
+    """BatchNorm (batch statistics over rows * k values per channel) + LeakyReLU(slope) + max over k neighbours (csrc/train_edge.hip),
+    x panel -> panel [out_rows, C].  Three ways to name the neighbours of output row i:
+      idx [rows, k] int32 global rows, x = [P | Q] at least 2C wide: max_j lrelu(BN(P[idx_ij] + Q[i])), one EdgeConv level of the DGCNN
+        embedder after its two per-point products;
+      idx None, k = 1, x = P: BN + lrelu of row i itself (conv5's BatchNorm1d, the dense BatchNorms of PAConv);
+      idx None, k > 1, x = P: rows i k .. i k + k - 1 (PAConv's max over the neighbours; identity indices are made here).
+    `bn` is the BatchNorm module: its running statistics are updated exactly as torch does in train mode, on its c_real channels (a
+    panel may carry zero-padded channels, e.g. ScoreNet's 16 hidden units in a 32-wide panel)."""
 
     @staticmethod
-    def forward(ctx, pq, gamma, beta, idx, rows, C, k, bn):
+    def forward(ctx, x, gamma, beta, idx, rows, C, k, slope, bn, c_real, out_rows):
         L = engine.lib()
-        dev = pq.device
+        dev = x.device
         has_q = idx is not None
-        ld = pq.shape[1]
-        if ld < (2 * C if has_q else C) or C % 32 != 0:
-            raise RuntimeError("EdgeBNMaxFn: panel narrower than the channels, or channel count not a multiple of 32")
+        ld = x.shape[1]
+        if C % 32 != 0 or ld < (2 * C if has_q else C) or x.shape[0] < (rows if has_q else rows * k):
+            raise RuntimeError("BatchNormMaxFn: panel too small for the rows and channels, or channel count not a multiple of 32")
         g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        if not has_q and k > 1:
+            idx = torch.arange(rows * k, dtype=torch.int32, device=dev).view(rows, k)
         stats = torch.empty(3 * C, dtype=torch.float32, device=dev)
-        out = _panel_out(pq.shape[0], C, rows, dev)
+        out = _panel_out(out_rows, C, rows, dev)
         arg = torch.empty(rows, C, dtype=torch.uint8, device=dev)
-        q_ptr = pq.data_ptr() + 4 * C if has_q else None
+        edges = (engine._ptr(x), ld, x.data_ptr() + 4 * C if has_q else None, ld, engine._ptr(idx), rows, k, C)
         with _OnDevice(dev):
             s = engine._stream()
             nb = L.fc_train_edge_ws_bytes(rows, C)
             ws = _ws(nb, dev)
-            L.fc_train_edge_stats_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, bn.eps, engine._ptr(stats), engine._ptr(ws), nb, s)
-            L.fc_train_edge_fwd_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32),
-                                    engine._ptr(b32), 0.2, engine._ptr(out), C, engine._ptr(arg), s)
-        if bn.track_running_stats and bn.running_mean is not None:
-            # torch.nn.BatchNorm train-mode side effect (parameter-sized vectors): running <- (1 - m) running + m batch, unbiased variance
-            with torch.no_grad():
-                n = rows * k
-                bn.num_batches_tracked += 1
-                if bn.momentum is not None:
-                    m = bn.momentum
-                    bn.running_mean.mul_(1 - m).add_(stats[:C].to(bn.running_mean.dtype), alpha=m)
-                    bn.running_var.mul_(1 - m).add_(stats[2 * C:].to(bn.running_var.dtype) * (n / max(n - 1, 1)), alpha=m)
-                else:                                                 # momentum=None: cumulative average, factor 1 / num_batches_tracked
-                    m = 1.0 / bn.num_batches_tracked.to(bn.running_mean.dtype)
-                    bn.running_mean.mul_(1 - m).add_(stats[:C].to(bn.running_mean.dtype) * m)
-                    bn.running_var.mul_(1 - m).add_(stats[2 * C:].to(bn.running_var.dtype) * (n / max(n - 1, 1)) * m)
-        order = offsets = None
-        if has_q:
-            # edges sorted by the row they point at (index plumbing): the backward then sums each row's incoming gradients in a fixed order
-            flat = idx.reshape(-1).long()
-            order = torch.argsort(flat, stable=True).to(torch.int32)
-            offsets = torch.zeros(rows + 1, dtype=torch.int32, device=dev)
-            offsets[1:] = torch.cumsum(torch.bincount(flat, minlength=rows), 0).to(torch.int32)
-        ctx.save_for_backward(pq, g32, b32, stats, arg, idx, order, offsets)
-        ctx.meta = (rows, C, k, has_q, gamma.dtype)
+            L.fc_train_edge_stats_f32(*edges, bn.eps, engine._ptr(stats), engine._ptr(ws), nb, s)
+            L.fc_train_edge_fwd_f32(*edges, engine._ptr(stats), engine._ptr(g32), engine._ptr(b32), slope, engine._ptr(out), C, engine._ptr(arg), s)
+        _bn_update_running(bn, stats, C, c_real, rows * k)
+        # edges sorted by the row they point at: the backward then sums each row's incoming gradients in a fixed order
+        order, offsets = _sorted_edges(idx, rows) if has_q else (None, None)
+        ctx.save_for_backward(x, g32, b32, stats, arg, idx, order, offsets)
+        ctx.meta = (rows, C, k, slope, has_q, gamma.dtype)
         return out
 
     @staticmethod
     def backward(ctx, g):
         L = engine.lib()
-        pq, g32, b32, stats, arg, idx, order, offsets = ctx.saved_tensors
-        rows, C, k, has_q, pdtype = ctx.meta
-        dev = pq.device
+        x, g32, b32, stats, arg, idx, order, offsets = ctx.saved_tensors
+        rows, C, k, slope, has_q, pdtype = ctx.meta
+        dev = x.device
         g = g.contiguous()
-        ld = pq.shape[1]
-        q_ptr = pq.data_ptr() + 4 * C if has_q else None
-        rows_pad = pq.shape[0]
+        ld, rows_pad = x.shape[1], g.shape[0]
         t1 = torch.empty(rows_pad, C, dtype=torch.float32, device=dev)
         t2 = torch.empty(rows_pad, C, dtype=torch.float32, device=dev)
-        dpq = torch.zeros_like(pq)
+        dx = torch.zeros_like(x)
+        edges = (engine._ptr(x), ld, x.data_ptr() + 4 * C if has_q else None, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32))
         with _OnDevice(dev):
             s = engine._stream()
-            L.fc_train_edge_bwd_prep_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32), engine._ptr(b32),
-                                         0.2, engine._ptr(arg), engine._ptr(g), g.shape[1], engine._ptr(t1), engine._ptr(t2), C, rows_pad, s)
+            L.fc_train_edge_bwd_prep_f32(*edges, engine._ptr(b32), slope, engine._ptr(arg), engine._ptr(g), g.shape[1], engine._ptr(t1),
+                                         engine._ptr(t2), C, rows_pad, s)
             dbeta, dgamma = _colsum(t1, C, rows), _colsum(t2, C, rows)
-            dq_ptr = dpq.data_ptr() + 4 * C if has_q else None
+            tail = (engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta), engine._ptr(dgamma))
             if has_q:
                 # dQ by row sums, dP by an owner-computes gather over the sorted edges: no atomics, bit-reproducible
-                L.fc_train_edge_bwd_scatter_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats), engine._ptr(g32),
-                                                engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta), engine._ptr(dgamma), None, ld, dq_ptr, ld, s)
-                L.fc_train_edge_bwd_gather_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                               engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta),
-                                               engine._ptr(dgamma), engine._ptr(order), engine._ptr(offsets), engine._ptr(dpq), ld, s)
+                L.fc_train_edge_bwd_scatter_f32(*edges, *tail, None, ld, dx.data_ptr() + 4 * C, ld, s)
+                L.fc_train_edge_bwd_gather_f32(*edges, *tail, engine._ptr(order), engine._ptr(offsets), engine._ptr(dx), ld, s)
             else:
-                L.fc_train_edge_bwd_scatter_f32(engine._ptr(pq), ld, q_ptr, ld, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                                engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta),
-                                                engine._ptr(dgamma), engine._ptr(dpq), ld, dq_ptr, ld, s)
-        return dpq, dgamma.to(pdtype), dbeta.to(pdtype), None, None, None, None, None
+                # no table or identity indices: every row of P is the target of at most one edge, so the "scatter" writes each element once
+                L.fc_train_edge_bwd_scatter_f32(*edges, *tail, engine._ptr(dx), ld, None, ld, s)
+        return dx, dgamma.to(pdtype), dbeta.to(pdtype), None, None, None, None, None, None, None, None
 
 
 def edge_bn_max(pq, bn, idx, rows, C, k):
-    return EdgeBNMaxFn.apply(pq, bn.weight, bn.bias, idx, rows, C, k, bn)
+    """One EdgeConv level in training mode: pq = [P | Q] with the neighbour table idx, or P alone with idx None (k = 1); slope 0.2."""
+    return BatchNormMaxFn.apply(pq, bn.weight, bn.bias, idx, rows, C, k, 0.2, bn, C, pq.shape[0])
 
 
 EXPM_TRAIN_BWD_MAX_D2 = 16       # fc_train_expm_bwd_f32 (one lane per point); the forward runs up to d2 = 256
@@ -801,8 +815,8 @@ class ExpmCouplingFn(torch.autograd.Function):
         L = engine.lib()
         x2, o, s4 = ctx.saved_tensors
         dy2, dldj = dy2.contiguous(), dldj.contiguous()
-        dx2 = _panel_out(x2.shape[0], x2.shape[1], rows, x2.device) if x2.shape[1] == _round_up(d2, 32) else torch.zeros_like(x2)
-        do = _panel_out(o.shape[0], o.shape[1], rows, x2.device) if o.shape[1] == _round_up(d2 * d2 + d2, 32) else torch.zeros_like(o)
+        dx2 = _grad_panel(x2, d2, rows)
+        do = _grad_panel(o, d2 * d2 + d2, rows)
         dscal = torch.zeros(x2.shape[0], 4, dtype=torch.float32, device=x2.device)
         with _OnDevice(x2.device):
             if d2 > EXPM_TRAIN_BWD_MAX_D2:

@@ -8,7 +8,7 @@ product, assign_score, BatchNorm2d, ReLU -- and the max over the 32 neighbours),
 
 What runs where: index kernels (FPS, k-NN, 3-NN) are the inference kernels, indices carry no gradient; every product (weight bank,
 ScoreNet convs, FP convs, head) is the training Linear of train_ops.py; BatchNorm (+ ReLU, + max over the neighbours) is the EdgeConv
-BatchNorm kernel family with slope 0; softmax, assign_score, the centre difference, the gathered-row gradients and the interpolation
+BatchNorm node of train_ops.py with slope 0; softmax, assign_score, the centre difference, the gathered-row gradients and the interpolation
 are csrc/train_paconv.hip.  torch on activations: padding / views (panels), nothing else; torch on indices: argsort / bincount of the
 edge lists for the fixed-order gather backwards.
 """
@@ -23,16 +23,7 @@ M_KERNELS = 8
 
 
 def _r32(x):
-    return (x + 31) // 32 * 32
-
-
-def _sorted_edges(src_rows, n_src):
-    """edge ids sorted (stable) by the source row they read + start offset of each source row's segment (index plumbing)."""
-    flat = src_rows.reshape(-1).long()
-    order = torch.argsort(flat, stable=True).to(torch.int32)
-    offsets = torch.zeros(n_src + 1, dtype=torch.int32, device=flat.device)
-    offsets[1:] = torch.cumsum(torch.bincount(flat, minlength=n_src), 0).to(torch.int32)
-    return order, offsets
+    return T._round_up(x, 32)
 
 
 class GroupFn(torch.autograd.Function):
@@ -67,7 +58,7 @@ class GroupFn(torch.autograd.Function):
         edges = B * m * K
         dx = torch.empty(edges, _r32(Cin), dtype=torch.float32, device=dev)
         src = nidx.view(B, m * K) + (torch.arange(B, device=dev, dtype=torch.int32) * n)[:, None]
-        order, offsets = _sorted_edges(src, B * n)
+        order, offsets = T._sorted_edges(src, B * n)
         dfeat = torch.empty(fshape, dtype=torch.float32, device=dev)
         with T._OnDevice(dev):
             s = engine._stream()
@@ -154,70 +145,6 @@ class AssignFn(torch.autograd.Function):
         return dG, dS, None, None, None
 
 
-class BNActMaxFn(torch.autograd.Function):
-    """BatchNorm (batch statistics over rows*k values per channel) + LeakyReLU(slope) (+ max over groups of k consecutive rows when
-    k > 1) of a dense panel P [rows*k (padded), >= C]: the EdgeConv BatchNorm kernels (csrc/train_edge.hip) with identity indices and
-    no per-query term.  `bn`: the BatchNorm module whose running statistics are updated as torch does in train mode (first c_real
-    channels: a panel may carry zero-padded channels, e.g. ScoreNet's 16 hidden units in a 32-wide panel)."""
-
-    @staticmethod
-    def forward(ctx, P, gamma, beta, rows, C, k, slope, bn, c_real):
-        L = engine.lib()
-        dev = P.device
-        if C % 32 != 0 or P.shape[1] < C or P.shape[0] < rows * k:
-            raise RuntimeError("BNActMaxFn: panel too small or channel count not a multiple of 32")
-        g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        idx = None if k == 1 else torch.arange(rows * k, dtype=torch.int32, device=dev).view(rows, k)
-        stats = torch.empty(3 * C, dtype=torch.float32, device=dev)
-        out = T._panel_out(T._round_up(rows, T.ROW_PAD), C, rows, dev)
-        arg = torch.empty(rows, C, dtype=torch.uint8, device=dev)
-        with T._OnDevice(dev):
-            s = engine._stream()
-            nb = L.fc_train_edge_ws_bytes(rows, C)
-            ws = T._ws(nb, dev)
-            L.fc_train_edge_stats_f32(engine._ptr(P), P.shape[1], None, 0, engine._ptr(idx), rows, k, C, bn.eps, engine._ptr(stats), engine._ptr(ws), nb, s)
-            L.fc_train_edge_fwd_f32(engine._ptr(P), P.shape[1], None, 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                    engine._ptr(g32), engine._ptr(b32), slope, engine._ptr(out), C, engine._ptr(arg), s)
-        if bn.track_running_stats and bn.running_mean is not None:
-            with torch.no_grad():
-                n = rows * k
-                bn.num_batches_tracked += 1
-                if bn.momentum is not None:
-                    mom = bn.momentum
-                    bn.running_mean.mul_(1 - mom).add_(stats[:c_real].to(bn.running_mean.dtype), alpha=mom)
-                    bn.running_var.mul_(1 - mom).add_(stats[2 * C:2 * C + c_real].to(bn.running_var.dtype) * (n / max(n - 1, 1)), alpha=mom)
-                else:                                                 # momentum=None: cumulative average, factor 1 / num_batches_tracked
-                    mom = 1.0 / bn.num_batches_tracked.to(bn.running_mean.dtype)
-                    bn.running_mean.mul_(1 - mom).add_(stats[:c_real].to(bn.running_mean.dtype) * mom)
-                    bn.running_var.mul_(1 - mom).add_(stats[2 * C:2 * C + c_real].to(bn.running_var.dtype) * (n / max(n - 1, 1)) * mom)
-        ctx.save_for_backward(P, g32, b32, stats, arg, idx)
-        ctx.meta = (rows, C, k, slope, gamma.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        L = engine.lib()
-        P, g32, b32, stats, arg, idx = ctx.saved_tensors
-        rows, C, k, slope, pdtype = ctx.meta
-        dev = P.device
-        g = g.contiguous()
-        rows_pad = g.shape[0]
-        t1 = torch.empty(rows_pad, C, dtype=torch.float32, device=dev)
-        t2 = torch.empty(rows_pad, C, dtype=torch.float32, device=dev)
-        dP = torch.zeros_like(P)
-        with T._OnDevice(dev):
-            s = engine._stream()
-            L.fc_train_edge_bwd_prep_f32(engine._ptr(P), P.shape[1], None, 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                         engine._ptr(g32), engine._ptr(b32), slope, engine._ptr(arg), engine._ptr(g), g.shape[1],
-                                         engine._ptr(t1), engine._ptr(t2), C, rows_pad, s)
-            dbeta, dgamma = T._colsum(t1, C, rows), T._colsum(t2, C, rows)
-            # identity indices: every row of P is the target of exactly one edge, so the "scatter" writes each element once (deterministic)
-            L.fc_train_edge_bwd_scatter_f32(engine._ptr(P), P.shape[1], None, 0, engine._ptr(idx), rows, k, C, engine._ptr(stats),
-                                            engine._ptr(g32), engine._ptr(arg), engine._ptr(t1), C, engine._ptr(dbeta), engine._ptr(dgamma),
-                                            engine._ptr(dP), dP.shape[1], None, 0, s)
-        return dP, dgamma.to(pdtype), dbeta.to(pdtype), None, None, None, None, None, None
-
-
 def bn_act(P, bn, rows, C, k=1, slope=0.0):
     """BatchNorm(batch statistics) + (Leaky)ReLU (+ max over k consecutive rows) with the module's affine parameters, zero-padded to the
     panel's channel count when the module has fewer channels."""
@@ -226,7 +153,7 @@ def bn_act(P, bn, rows, C, k=1, slope=0.0):
     if c_real < C:
         z = torch.zeros(C - c_real, dtype=gamma.dtype, device=gamma.device)
         gamma, beta = torch.cat((gamma, z)), torch.cat((beta, z))
-    return BNActMaxFn.apply(P, gamma, beta, rows, C, k, slope, bn, c_real)
+    return T.BatchNormMaxFn.apply(P, gamma, beta, None, rows, C, k, slope, bn, c_real, T._round_up(rows, T.ROW_PAD))
 
 
 class InterpFn(torch.autograd.Function):
@@ -251,7 +178,7 @@ class InterpFn(torch.autograd.Function):
         C, rows, kshape = ctx.meta
         dout = dout.contiguous()
         n_known = int(kshape[0])
-        order, offsets = _sorted_edges(idx, n_known)
+        order, offsets = T._sorted_edges(idx, n_known)
         dFk = torch.empty(kshape, dtype=torch.float32, device=dout.device)
         with T._OnDevice(dout.device):
             L.fc_train_rows_gather_bwd_f32(engine._ptr(dout), dout.shape[1], 0, C, engine._ptr(order), engine._ptr(offsets), engine._ptr(w), 3,

@@ -126,6 +126,70 @@ def test_fused_mlp_node_agrees_with_the_chain_of_linear_nodes(monkeypatch):
     assert worst < 2e-6
 
 
+def test_input_panel_wider_than_its_segment_gets_a_padded_gradient(monkeypatch):
+    """Segments [40, 32] where the first input panel is 96 columns wide (its segment reads 64) and columns 40..95 hold random data, 300
+    rows (one 256-row tile and a partial one): once through linear_act (N = 64) and once through the fused MlpFn node of
+    MLP(72, [64, 64, 64], 32).  Outputs and every gradient against fp64 autograd on the true 40 + 32 columns (gates of
+    test_linear_act_forward_and_backward_match_fp64 and test_mlp_at_coupling_widths_matches_oracle_autograd); the first input's gradient
+    has the panel's shape and is exactly zero in the columns 64..95 that the segment does not read."""
+    monkeypatch.setattr(T, "FUSED_MLP", True)
+    monkeypatch.setattr(T, "FUSED_ACT", True)
+    rows, widths, wide = 300, [40, 32], 96
+    g = torch.Generator().manual_seed(17)
+    x0, x1 = torch.randn(rows, 40, generator=g), torch.randn(rows, 32, generator=g)
+    junk = torch.randn(rows, wide - 40, generator=g)
+    W = torch.randn(64, 72, generator=g) / 72 ** 0.5
+    b = torch.randn(64, generator=g) * 0.3
+    torch.manual_seed(18)
+    mlp = M.MLP(72, [64, 64, 64], 32).to(DEV)
+
+    def panels():
+        p0 = torch.zeros(T._round_up(rows, T.ROW_PAD), wide)
+        p0[:rows, :40], p0[:rows, 40:] = x0, junk
+        return p0.to(DEV).requires_grad_(True), T.to_panel(x1.to(DEV)).requires_grad_(True)
+
+    def check_inputs(errs, p0, p1, x0o, x1o):
+        assert p0.grad.shape == p0.shape and p0.grad[:, 64:].abs().max().item() == 0.0
+        errs["dx0"], errs["dx1"] = _rel(p0.grad[:rows, :40], x0o.grad), _rel(p1.grad[:rows, :32], x1o.grad)
+
+    # ---- one Linear
+    dy = torch.randn(rows, 64, generator=g)
+    Wo, bo = W.double().requires_grad_(True), b.double().requires_grad_(True)
+    x0o, x1o = x0.double().requires_grad_(True), x1.double().requires_grad_(True)
+    yo = F.gelu(F.linear(torch.cat((x0o, x1o), -1), Wo, bo))
+    yo.backward(dy.double())
+    Wd, bd = W.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+    p0, p1 = panels()
+    with T.step_guard(device=DEV) as guard:
+        y = T.from_panel(T.linear_act([p0, p1], widths, Wd, bd, rows, "GELU"), rows, 64)
+        y.backward(dy.to(DEV))
+        assert not guard.overflowed()
+    errs = dict(y=_rel(y.detach(), yo.detach()), dW=_rel(Wd.grad, Wo.grad), db=_rel(bd.grad, bo.grad))
+    check_inputs(errs, p0, p1, x0o, x1o)
+    print("linear_act, panel 96 wide for a 40-column segment: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    assert max(errs.values()) < 5e-6, errs
+
+    # ---- the fused MLP node
+    dy = torch.randn(rows, 32, generator=g)
+    sd = {("m." + k): v.detach().cpu().double().requires_grad_(True) for k, v in mlp.state_dict().items()}
+    x0o, x1o = x0.double().requires_grad_(True), x1.double().requires_grad_(True)
+    yo = O.mlp(sd, "m", torch.cat((x0o, x1o), -1), O._act("GELU"))
+    yo.backward(dy.double())
+    p0, p1 = panels()
+    with T.step_guard(device=DEV) as guard:
+        yp = T.mlp_panels(mlp, [p0, p1], widths, rows, "GELU")
+        assert type(yp.grad_fn).__name__.startswith("MlpFn")
+        y = T.from_panel(yp, rows, 32)
+        y.backward(dy.to(DEV))
+        assert not guard.overflowed()
+    errs = dict(y=_rel(y.detach(), yo.detach()))
+    check_inputs(errs, p0, p1, x0o, x1o)
+    for k, p in mlp.named_parameters():
+        errs["d" + k] = _rel(p.grad, sd["m." + k].grad)
+    print("MLP 72 -> 64^3 -> 32 (fused node), panel 96 wide for a 40-column segment: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    assert max(errs.values()) < 2e-5, errs
+
+
 def test_mlp_forward_on_plain_tensors_and_range_guard():
     torch.manual_seed(8)
     mlp = M.MLP(6, [64, 64, 64], 32).to(DEV)

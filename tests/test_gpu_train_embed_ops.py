@@ -1,5 +1,5 @@
-"""The embedder training operators one by one (csrc/train_edge.hip through train_ops.EdgeBNMaxFn / PoolMaxMeanFn / column_stats and
-train_paconv.BNActMaxFn; csrc/train_paconv.hip through train_paconv.GroupFn / CenterDiffFn / SoftmaxFn / AssignFn / InterpFn): forward and
+"""The embedder training operators one by one (csrc/train_edge.hip through train_ops.BatchNormMaxFn / PoolMaxMeanFn / column_stats;
+csrc/train_paconv.hip through train_paconv.GroupFn / CenterDiffFn / SoftmaxFn / AssignFn / InterpFn): forward and
 backward element-wise against the plain fp64 references of tests/embed_ops_ref.py (pinned to the oracle by test_oracle_embed_ops.py).
 
 Gate (embed_ops_ref.gate): per tensor err = max |hip - f64| / max(1e-2, max |f64|) < max(5e-6, 3 e32) with e32 the error of the same
@@ -60,7 +60,7 @@ def _zero(t):
 
 # ================================================================ BatchNorm(batch statistics) + LeakyReLU + max: train_edge.hip
 def _edge_stats(pq, has_q, idx, rows, k, C, eps=R.EPS):
-    """fc_train_edge_stats_f32 on a panel as EdgeBNMaxFn calls it -> (mean [C], biased var [C])"""
+    """fc_train_edge_stats_f32 on a panel as BatchNormMaxFn calls it -> (mean [C], biased var [C])"""
     L = engine.lib()
     stats = torch.empty(3 * C, dtype=torch.float32, device=DEV)
     nb = L.fc_train_edge_ws_bytes(rows, C)
@@ -83,7 +83,7 @@ def _bn_module(c, momentum):
 
 def _run_bn_max(c, junk=0.0, momentum=0.1, steps=1):
     """One case through its autograd Function (`steps` forward passes, one backward): slope 0.2 with random indices or none ->
-    train_ops.EdgeBNMaxFn; identity groups, slope 0 or a module narrower than the panel -> train_paconv.bn_act."""
+    train_ops.edge_bn_max; identity groups, slope 0 or a module narrower than the panel -> train_paconv.bn_act."""
     rows, k, C, ld = c["rows"], c["k"], c["C"], c["ld"]
     groups, c16 = c["variant"] == "groups", c["variant"] == "c16"
     has_q = c["Q"] is not None
@@ -212,7 +212,7 @@ def test_scatter_against_gather():
     d_sc, d_ga = torch.zeros(rows_pad, ld, device=DEV), torch.zeros(rows_pad, ld, device=DEV)
     L.fc_train_edge_bwd_scatter_f32(*common, *tail, engine._ptr(d_sc), ld, d_sc.data_ptr() + 4 * C, ld, s)
     L.fc_train_edge_bwd_scatter_f32(*common, *tail, None, ld, d_ga.data_ptr() + 4 * C, ld, s)
-    order, offsets = TP._sorted_edges(idx, rows)
+    order, offsets = T._sorted_edges(idx, rows)
     L.fc_train_edge_bwd_gather_f32(*common, *tail, engine._ptr(order), engine._ptr(offsets), engine._ptr(d_ga), ld, s)
     for tag, d in (("scatter (atomics)", d_sc), ("gather (sorted)", d_ga)):
         R.gate(f"{name} {tag}", dict(out=out[:rows], dP=d[:rows, :C], dQ=d[:rows, C:2 * C], dgamma=dgamma, dbeta=dbeta), r64, r32)

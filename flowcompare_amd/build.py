@@ -19,8 +19,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-ffp-contract=off"]
 # per-file additions.  premlp.hip: hipcc packs adjacent scalar f32 adds / muls of the epilogue into v_pk_add_f32 / v_pk_mul_f32 (the guide lists
 # packed f32 VALU beside MFMAs as an anti-lever; measured here: no difference).  attention.hip: the same packing in the softmax: -1.9 % kernel time
-# without it (28.2 -> 27.7 ms per C2 step, same box); gemm.hip is 1 % FASTER with the packing and keeps it.  Developer option for same-box A/B runs:
-# FC_EXTRA_FLAGS="attention.hip:-fno-slp-vectorize;gemm.hip:-fno-slp-vectorize" adds flags to single files.
+# without it (28.2 -> 27.7 ms per C2 step, same box); the GEMM kernels (gemm_*.hip) are 1 % FASTER with the packing and keep it.  Developer option for same-box A/B runs:
+# FC_EXTRA_FLAGS="attention.hip:-fno-slp-vectorize;gemm_split.hip:-fno-slp-vectorize" adds flags to single files.
 EXTRA_FLAGS = {"premlp.hip": ["-fno-slp-vectorize"], "attention.hip": ["-fno-slp-vectorize"],
                # mlprows.hip: the epilogue is hand-placed in micro-steps behind single MFMAs; SLP packing merges steps of different slots
                "mlprows.hip": ["-fno-slp-vectorize"]}

@@ -96,7 +96,7 @@ struct WsCarver {
     }
 };
 
-// ---------------------------------------------------------------- packed Linear (see gemm.h)
+// ---------------------------------------------------------------- packed Linear (see gemm.hip)
 struct PackedLinear {
     float* W = nullptr;        // [N_alloc][K_pad] row-major, zero padded
     float* bias = nullptr;     // [N_alloc]
@@ -238,6 +238,7 @@ bool gemm_lnq_ok();             // the LayerNorm -> q fold (EPI_LNQ) can run: gu
 void launch_lnq_finalize(float* q, int ldq, const float* sumsq, int nslots, size_t pitch, int width, const float* q_bias, int rows, hipStream_t s);      // inside a guard scope on the default tile: producers may emit / consumers may take limb images
 bool gemm_split_enabled();        // a split (limb) GEMM loop is the active variant: the fused spline epilogue is available
 int* gemm_fp16_flag();         // the open scope's device flag of the calling thread, or null
+int* gemm_scope_flag();        // the same flag whichever GEMM variant is active (launch_gemm hands it to the kernels)
 template <class F>
 inline void run_fp16_guarded(int* dev_flag, hipStream_t s, F&& fn, bool deferrable = false) {
     if (!dev_flag || !gemm_fp16_enabled()) { fn(); return; }

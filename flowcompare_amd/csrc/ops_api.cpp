@@ -19,7 +19,7 @@ struct TmpBuf {
 
 namespace fc {
 void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t);      // spline_wide.hip
-long gemm_fp16_fallbacks(); size_t gemm_read_stamps(unsigned long long*, size_t);                                      // gemm.hip
+long gemm_fp16_fallbacks(); size_t gemm_read_stamps(unsigned long long*, size_t);                                      // gemm_guard.cpp
 bool kv_fold_gate_dims(int, int, bool, bool); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t);      // flow_engine.cpp
 
 Knobs g_knobs;

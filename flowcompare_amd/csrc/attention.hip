@@ -518,69 +518,10 @@ static void launch_attn_dh(const AttnParams& p, int B, hipStream_t s) {
     FC_HIP(hipGetLastError());
 }
 
-static void launch_attention_scaled(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out, int ldo,
-                                    int B, int N, int n_stride_rows, int M, int m_stride_rows, int dh_pad, float qscale, void* limb_ws,
-                                    hipStream_t s, const unsigned short* k_c16 = nullptr, const unsigned short* v_c16 = nullptr, int c16_pitch = 0,
-                                    const AttnLnq* lnq = nullptr, float* lse = nullptr, bool* lse_written = nullptr) {
-    if (B <= 0 || N <= 0 || M <= 0) throw Error(FC_ERR_INVALID, "attention: empty problem");
-    if (k_c16) {
-        // K / V arrive as slices of the projection GEMM's limb-image output: no fp32 K / V, no conversion pass
-        int* flag16 = gemm_fp16_flag();
-        if (!flag16 || dh_pad > 64 || !v_c16 || c16_pitch <= 0 || (ldq % 4) != 0)
-            throw Error(FC_ERR_INVALID, "attention: limb-image K / V need a guard scope, head dim <= 64 and a pitch");
-        Attn16Params p{q, ldq, k_c16, v_c16, out, ldo, N, n_stride_rows, M, m_stride_rows, qscale, flag16, lnq ? lnq->sumsq : nullptr,
-                       lnq ? lnq->slots : 0, lnq ? lnq->pitch : 0, lnq ? lnq->inv_width : 0.f, lnq ? lnq->bias : nullptr, c16_pitch, 1};
-        if (dh_pad == 32) launch_attn16_dh<32>(p, B, s); else launch_attn16_dh<64>(p, B, s);
-        return;
-    }
-    if ((ldq | ldk | ldv) % 4 != 0 || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15))
-        throw Error(FC_ERR_INVALID, "attention: q/k/v must be 16-byte aligned with pitches that are multiples of 4 floats");
-    int* flag = gemm_fp16_flag();
-    if (flag && limb_ws && dh_pad <= 64 && g_knobs.attn_fp16) {      // (knob 5)
-        // split-fp16 path (needs the caller's Fp16Guard scope for its range check and limb_ws for the K/V limb images)
-        const long rows = (long)(B - 1) * m_stride_rows + M;
-        unsigned short* k16 = (unsigned short*)limb_ws;
-        unsigned short* v16 = k16 + (size_t)rows * 2 * dh_pad;
-        {
-            ProfScope ps("fc::kv_limbs_kernel", 0.0, (double)rows * dh_pad * 16.0, s);
-            const long n = rows * (dh_pad / 4);
-            hipLaunchKernelGGL(kv_limbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, k, ldk, v, ldv, k16, v16, rows, dh_pad, flag);
-            FC_HIP(hipGetLastError());
-        }
-        Attn16Params p{q, ldq, k16, v16, out, ldo, N, n_stride_rows, M, m_stride_rows, qscale, flag, nullptr, 0, 0, 0.f, nullptr, dh_pad / 4, 0};
-        p.lse = lse;
-        if (lse_written) *lse_written = lse != nullptr;
-        if (dh_pad == 32) launch_attn16_dh<32>(p, B, s); else launch_attn16_dh<64>(p, B, s);
-        return;
-    }
-    AttnParams p{q, ldq, k, ldk, v, ldv, out, ldo, N, n_stride_rows, M, m_stride_rows, qscale};
-    switch (dh_pad) {
-        case 32: launch_attn_dh<32>(p, B, s); break;
-        case 64: launch_attn_dh<64>(p, B, s); break;
-        case 128: launch_attn_dh<128>(p, B, s); break;
-        case 256: launch_attn_dh<256>(p, B, s); break;
-        default: throw Error(FC_ERR_UNSUPPORTED, "attention: inner dim (padded) must be 32, 64, 128 or 256");
-    }
-}
-
 size_t attention_limb_ws_bytes(long kv_rows, int dh_pad) { return dh_pad <= 64 ? (size_t)kv_rows * dh_pad * 8 : 0; }
 
-void launch_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out, int ldo,
-                      int B, int N, int n_stride_rows, int M, int m_stride_rows, int dh_pad, void* limb_ws, hipStream_t s) {
-    launch_attention_scaled(q, ldq, k, ldk, v, ldv, out, ldo, B, N, n_stride_rows, M, m_stride_rows, dh_pad, 1.0f, limb_ws, s);
-}
-
-// K | V of this layer as columns [col0, col0 + 2 * dh_pad) of a GEMM limb-image output with n_pad columns per row (GemmEpi::C16)
-void launch_attention_c16(const float* q, int ldq, const unsigned short* kv_c16, int n_pad, int col0, float* out, int ldo, int B, int N,
-                          int n_stride_rows, int M, int m_stride_rows, int dh_pad, hipStream_t s, const AttnLnq* lnq) {
-    if (col0 % 16 != 0 || n_pad % 16 != 0 || dh_pad % 16 != 0) throw Error(FC_ERR_INVALID, "attention: limb-image slices must start on 16-column tiles");
-    const unsigned short* kp = kv_c16 + (size_t)(col0 / 16) * 32;
-    const unsigned short* vp = kp + (size_t)(dh_pad / 16) * 32;
-    launch_attention_scaled(q, ldq, nullptr, 4, nullptr, 4, out, ldo, B, N, n_stride_rows, M, m_stride_rows, dh_pad, 1.0f, nullptr, s, kp, vp, n_pad / 4, lnq);
-}
-
 // The folded engine (flow_engine.cpp, fc_debug_set 33): keys and values of every attention are the context panel itself.  Its limb image
-// [row][hi dh_pad | lo dh_pad] (kv_limbs_kernel's K image alone) is made once per forward ...
+// [row][hi dh_pad | lo dh_pad] (kv_limbs_kernel's K image alone) is made once per forward; every layer then attends over it (AttnKeys::CONTEXT)
 void launch_context_limbs(const float* ctx, int ldc, unsigned short* img, long rows, int dh_pad, hipStream_t s) {
     int* flag = gemm_fp16_flag();
     if (!flag || dh_pad > 64 || dh_pad % 4 != 0 || ldc % 4 != 0 || ldc < dh_pad || (((uintptr_t)ctx | (uintptr_t)img) & 15))
@@ -590,33 +531,65 @@ void launch_context_limbs(const float* ctx, int ldc, unsigned short* img, long r
     hipLaunchKernelGGL(kv_limbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctx, ldc, nullptr, 0, img, nullptr, rows, dh_pad, flag);
     FC_HIP(hipGetLastError());
 }
-// ... and every layer attends over it: at head dim 64 with ONE staged tile per 64 keys (attn16_kernel<64, 1>), at 32 with the two-image kernel
-// reading the same image twice
-void launch_attention_ctx16(const float* q, int ldq, const unsigned short* ctx16, float* out, int ldo, int B, int N, int n_stride_rows, int M,
-                            int m_stride_rows, int dh_pad, hipStream_t s, const AttnLnq* lnq, float qscale) {
-    if (B <= 0 || N <= 0 || M <= 0) throw Error(FC_ERR_INVALID, "attention: empty problem");
+
+// the split-fp16 kernel's parameters over limb images k16 / v16 of row pitch kv_pitch (16-byte chunks); c16: 1 = slices of a GEMM limb-image output
+static Attn16Params attn16_params(const AttnQuery& qy, const AttnProblem& pb, const unsigned short* k16, const unsigned short* v16, float* out, int ldo,
+                                  int* flag, int kv_pitch, int c16) {
+    const AttnLnq* l = qy.lnq;
+    return Attn16Params{qy.q, qy.ldq, k16, v16, out, ldo, pb.N, pb.n_stride_rows, pb.M, pb.m_stride_rows, qy.qscale, flag, l ? l->sumsq : nullptr,
+                        l ? l->slots : 0, l ? l->pitch : 0, l ? l->inv_width : 0.f, l ? l->bias : nullptr, kv_pitch, c16};
+}
+
+bool launch_attention(const AttnQuery& qy, const AttnKeys& kv, const AttnProblem& pb, float* out, int ldo, hipStream_t s, float* lse) {
+    const int B = pb.B, dh_pad = pb.dh_pad;
+    if (kv.form == AttnKeys::SLICE && (kv.col0 % 16 != 0 || kv.n_pad % 16 != 0 || dh_pad % 16 != 0))
+        throw Error(FC_ERR_INVALID, "attention: limb-image slices must start on 16-column tiles");
+    if (B <= 0 || pb.N <= 0 || pb.M <= 0) throw Error(FC_ERR_INVALID, "attention: empty problem");
     int* flag = gemm_fp16_flag();
-    if (!flag || !ctx16 || (dh_pad != 32 && dh_pad != 64) || (ldq % 4) != 0 || (((uintptr_t)q | (uintptr_t)ctx16) & 15))
+    if (kv.form == AttnKeys::SLICE) {
+        // K / V arrive as slices of the projection GEMM's limb-image output: no fp32 K / V, no conversion pass
+        if (!flag || dh_pad > 64 || !kv.img || kv.n_pad / 4 <= 0 || (qy.ldq % 4) != 0)
+            throw Error(FC_ERR_INVALID, "attention: limb-image K / V need a guard scope, head dim <= 64 and a pitch");
+        const unsigned short* kp = kv.img + (size_t)(kv.col0 / 16) * 32;
+        const Attn16Params p = attn16_params(qy, pb, kp, kp + (size_t)(dh_pad / 16) * 32, out, ldo, flag, kv.n_pad / 4, 1);
+        if (dh_pad == 32) launch_attn16_dh<32>(p, B, s); else launch_attn16_dh<64>(p, B, s);
+        return false;
+    }
+    if (kv.form == AttnKeys::PANELS) {
+        if ((qy.ldq | kv.ldk | kv.ldv) % 4 != 0 || (((uintptr_t)qy.q | (uintptr_t)kv.k | (uintptr_t)kv.v) & 15))
+            throw Error(FC_ERR_INVALID, "attention: q/k/v must be 16-byte aligned with pitches that are multiples of 4 floats");
+        if (flag && kv.limb_ws && dh_pad <= 64 && g_knobs.attn_fp16) {      // (knob 5)
+            // split-fp16 path (needs the caller's Fp16Guard scope for its range check and limb_ws for the K/V limb images)
+            const long rows = (long)(B - 1) * pb.m_stride_rows + pb.M;
+            unsigned short* k16 = (unsigned short*)kv.limb_ws;
+            unsigned short* v16 = k16 + (size_t)rows * 2 * dh_pad;
+            {
+                ProfScope ps("fc::kv_limbs_kernel", 0.0, (double)rows * dh_pad * 16.0, s);
+                const long n = rows * (dh_pad / 4);
+                hipLaunchKernelGGL(kv_limbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kv.k, kv.ldk, kv.v, kv.ldv, k16, v16, rows, dh_pad, flag);
+                FC_HIP(hipGetLastError());
+            }
+            Attn16Params p = attn16_params(qy, pb, k16, v16, out, ldo, flag, dh_pad / 4, 0);
+            p.lse = lse;
+            if (dh_pad == 32) launch_attn16_dh<32>(p, B, s); else launch_attn16_dh<64>(p, B, s);
+            return lse != nullptr;
+        }
+        AttnParams p{qy.q, qy.ldq, kv.k, kv.ldk, kv.v, kv.ldv, out, ldo, pb.N, pb.n_stride_rows, pb.M, pb.m_stride_rows, qy.qscale};
+        switch (dh_pad) {
+            case 32: launch_attn_dh<32>(p, B, s); break;
+            case 64: launch_attn_dh<64>(p, B, s); break;
+            case 128: launch_attn_dh<128>(p, B, s); break;
+            case 256: launch_attn_dh<256>(p, B, s); break;
+            default: throw Error(FC_ERR_UNSUPPORTED, "attention: inner dim (padded) must be 32, 64, 128 or 256");
+        }
+        return false;
+    }
+    // CONTEXT: at head dim 64 with ONE staged tile per 64 keys (attn16_kernel<64, 1>), at 32 with the two-image kernel reading the same image twice
+    if (!flag || !kv.img || (dh_pad != 32 && dh_pad != 64) || (qy.ldq % 4) != 0 || (((uintptr_t)qy.q | (uintptr_t)kv.img) & 15))
         throw Error(FC_ERR_INVALID, "attention: the context limb image needs a guard scope, head dim 32 or 64 and 16-byte aligned operands");
-    Attn16Params p{q, ldq, ctx16, ctx16, out, ldo, N, n_stride_rows, M, m_stride_rows, qscale, flag, lnq ? lnq->sumsq : nullptr,
-                   lnq ? lnq->slots : 0, lnq ? lnq->pitch : 0, lnq ? lnq->inv_width : 0.f, lnq ? lnq->bias : nullptr, dh_pad / 4, 0};
+    const Attn16Params p = attn16_params(qy, pb, kv.img, kv.img, out, ldo, flag, dh_pad / 4, 0);
     if (dh_pad == 32) launch_attn16_dh<32>(p, B, s); else launch_attn16_dh<64, 1>(p, B, s);
-}
-
-// training path (train_attention.hip): strided q / k / v (columns of wider panels), explicit softmax scale
-// lse (optional, [B * N]): filled by the split-fp16 kernel only; the return value says whether it was
-bool launch_attention_scaled_op(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out, int ldo, int B, int N, int M,
-                                int dh_pad, float scale, void* limb_ws, hipStream_t s, float* lse) {
-    bool written = false;
-    launch_attention_scaled(q, ldq, k, ldk, v, ldv, out, ldo, B, N, N, M, M, dh_pad, scale * 1.4426950408889634f, limb_ws, s, nullptr, nullptr, 0,
-                            nullptr, lse, &written);
-    return written;
-}
-
-void launch_attention_op(const float* q, const float* k, const float* v, float* out, int B, int N, int M, int dh_pad, float scale,
-                         void* limb_ws, hipStream_t s) {
-    launch_attention_scaled(q, dh_pad, k, dh_pad, v, dh_pad, out, dh_pad, B, N, N, M, M, dh_pad,
-                            scale * 1.4426950408889634f, limb_ws, s);
+    return false;
 }
 
 }  // namespace fc

@@ -193,38 +193,36 @@ static void launch_attnw_dh(const AttnWParams& p, int B, hipStream_t s) {
     FC_HIP(hipGetLastError());
 }
 
-void launch_attention_weights(const float* q, int ldq, const float* k, int ldk, const unsigned short* kv_c16, int c16_n_pad, int c16_col0,
-                              float* out, const int32_t* sel, int P, int sel_per_scene, int B, int N, int n_stride_rows, int M, int m_stride_rows,
-                              int dh_pad, float qscale, const AttnLnq* lnq, hipStream_t s, const unsigned short* k_rows16) {
-    if (B <= 0 || N <= 0 || M <= 0 || P <= 0) throw Error(FC_ERR_INVALID, "attention weights: empty problem");
-    if (!q || !out || (!k && !kv_c16 && !k_rows16)) throw Error(FC_ERR_INVALID, "attention weights: null pointer");
-    if (!sel && P != N) throw Error(FC_ERR_INVALID, "attention weights: without a selection table P must equal N");
-    if (ldq % 4 != 0 || ((uintptr_t)q & 15)) throw Error(FC_ERR_INVALID, "attention weights: q must be 16-byte aligned with a pitch that is a multiple of 4 floats");
+void launch_attention_weights(const AttnQuery& qy, const AttnKeys& kv, const AttnProblem& pb, const int32_t* sel, int P, int sel_per_scene,
+                              float* out, hipStream_t s) {
+    const int B = pb.B, dh_pad = pb.dh_pad;
+    const bool limbs = kv.form != AttnKeys::PANELS;
+    if (B <= 0 || pb.N <= 0 || pb.M <= 0 || P <= 0) throw Error(FC_ERR_INVALID, "attention weights: empty problem");
+    if (!qy.q || !out || (limbs ? !kv.img : !kv.k)) throw Error(FC_ERR_INVALID, "attention weights: null pointer");
+    if (!sel && P != pb.N) throw Error(FC_ERR_INVALID, "attention weights: without a selection table P must equal N");
+    if (qy.ldq % 4 != 0 || ((uintptr_t)qy.q & 15)) throw Error(FC_ERR_INVALID, "attention weights: q must be 16-byte aligned with a pitch that is a multiple of 4 floats");
     AttnWParams p{};
-    p.q = q; p.ldq = ldq; p.out = out; p.sel = sel; p.sel_stride = sel && sel_per_scene ? P : 0;
-    p.P = P; p.N = N; p.n_stride = n_stride_rows; p.M = M; p.m_stride = m_stride_rows; p.qscale = qscale;
-    if (lnq) { p.q_sumsq = lnq->sumsq; p.q_slots = lnq->slots; p.q_pitch = lnq->pitch; p.q_inv_width = lnq->inv_width; p.q_bias = lnq->bias; }
-    if (k_rows16) {
-        if (((uintptr_t)k_rows16 & 15)) throw Error(FC_ERR_INVALID, "attention weights: the context limb image must be 16-byte aligned");
-        p.k16 = k_rows16;
-        p.ld16 = 2 * dh_pad;
-        p.k16_rows = 1;
+    p.q = qy.q; p.ldq = qy.ldq; p.out = out; p.sel = sel; p.sel_stride = sel && sel_per_scene ? P : 0;
+    p.P = P; p.N = pb.N; p.n_stride = pb.n_stride_rows; p.M = pb.M; p.m_stride = pb.m_stride_rows; p.qscale = qy.qscale;
+    if (const AttnLnq* l = qy.lnq) { p.q_sumsq = l->sumsq; p.q_slots = l->slots; p.q_pitch = l->pitch; p.q_inv_width = l->inv_width; p.q_bias = l->bias; }
+    if (limbs) {
+        if (kv.form == AttnKeys::CONTEXT) {
+            if (((uintptr_t)kv.img & 15)) throw Error(FC_ERR_INVALID, "attention weights: the context limb image must be 16-byte aligned");
+            p.k16 = kv.img;
+            p.ld16 = 2 * dh_pad;
+            p.k16_rows = 1;
+        } else {
+            if (kv.col0 % 16 != 0 || kv.n_pad % 16 != 0 || dh_pad > 64) throw Error(FC_ERR_INVALID, "attention weights: limb-image K needs 16-column tiles and head dim <= 64");
+            p.k16 = kv.img + (size_t)(kv.col0 / 16) * 32;
+            p.ld16 = kv.n_pad * 2;
+        }
         if (dh_pad == 32) launch_attnw_dh<32, 1>(p, B, s);
         else if (dh_pad == 64) launch_attnw_dh<64, 1>(p, B, s);
         else throw Error(FC_ERR_UNSUPPORTED, "attention weights: inner dim (padded) must be 32 or 64 with a limb-image K");
         return;
     }
-    if (kv_c16) {
-        if (c16_col0 % 16 != 0 || c16_n_pad % 16 != 0 || dh_pad > 64) throw Error(FC_ERR_INVALID, "attention weights: limb-image K needs 16-column tiles and head dim <= 64");
-        p.k16 = kv_c16 + (size_t)(c16_col0 / 16) * 32;
-        p.ld16 = c16_n_pad * 2;
-        if (dh_pad == 32) launch_attnw_dh<32, 1>(p, B, s);
-        else if (dh_pad == 64) launch_attnw_dh<64, 1>(p, B, s);
-        else throw Error(FC_ERR_UNSUPPORTED, "attention weights: inner dim (padded) must be 32 or 64 with a limb-image K");
-        return;
-    }
-    if (ldk % 4 != 0 || ((uintptr_t)k & 15)) throw Error(FC_ERR_INVALID, "attention weights: k must be 16-byte aligned with a pitch that is a multiple of 4 floats");
-    p.k = k; p.ldk = ldk;
+    if (kv.ldk % 4 != 0 || ((uintptr_t)kv.k & 15)) throw Error(FC_ERR_INVALID, "attention weights: k must be 16-byte aligned with a pitch that is a multiple of 4 floats");
+    p.k = kv.k; p.ldk = kv.ldk;
     switch (dh_pad) {
         case 32: launch_attnw_dh<32, 0>(p, B, s); break;
         case 64: launch_attnw_dh<64, 0>(p, B, s); break;

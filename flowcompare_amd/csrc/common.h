@@ -21,6 +21,7 @@ struct Error : std::runtime_error {
     Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 void set_last_error(const std::string& m);
+const char* get_last_error();
 
 #define FC_HIP(expr)                                                                         \
     do {                                                                                     \
@@ -45,6 +46,11 @@ inline size_t round_up_sz(size_t x, size_t m) { return (x + m - 1) / m * m; }
 // |x| < 4094: a producer that meets more raises the range flag like any other split-fp16 kernel (the pass then repeats on the bf16 limbs).
 constexpr float kOneAccActScale = 16.0f;
 
+// log2(e): the softmax kernels work in the log2 domain, so every softmax scale carries it (double where a fold is done in double, float at a launch)
+constexpr double kLog2e = 1.4426950408889634074;
+constexpr float kLog2eF = (float)kLog2e;
+static_assert(kLog2eF == 1.4426950408889634f, "kLog2eF must equal the float literal the kernels were validated with");
+
 constexpr int ROW_PAD = 256;   // row counts of every workspace matrix are padded to this (largest GEMM BM)
 constexpr int COL_PAD = 32;    // feature widths are padded to this (GEMM BK / MFMA tile)
 
@@ -53,6 +59,9 @@ constexpr int COL_PAD = 32;    // feature widths are padded to this (GEMM BK / M
 // name (as rocprofv3 prints it), launches, total milliseconds and the useful FLOPs / algorithmic bytes the launches
 // processed.  bench.py derives its `roofline` object from this over the timed region.
 bool prof_enabled();
+void prof_set(bool on);
+void prof_reset();
+std::string prof_report_json();
 void prof_filter(const char* substr);
 void prof_stride(int n);
 struct ProfScope {
@@ -171,7 +180,7 @@ struct GemmEpi {
     const float* val = nullptr; int ldval = 0;             // SLICE: values whose log N(.; mu, sigma) is ADDED to logprob
     const float* val_shift = nullptr; const float* val_scale = nullptr;   // SLICE: v = (val - shift) * scale ; AUGMENT(+inverse): z = z / scale + shift
     int rows_valid = 0;        // rows that exist in user-visible outputs
-    // EPI_LNQ (LayerNorm folded through a linear layer, flow_engine.cpp build_lnq): columns [0, d2) are the centred layer's outputs --
+    // EPI_LNQ (LayerNorm folded through a linear layer, flow_pack.cpp build_lnq): columns [0, d2) are the centred layer's outputs --
     // only their per-row sums of squares leave the kernel, ldj_part[(64-column block) * ldj_pitch + row] = sum -- and columns
     // [d2, d2 + 64) go to C (pitch ldc) as the un-normalised q projection
     // EPI_SPLINE (forward rational-quadratic spline coupling evaluated by the workgroup that produced the parameters; uses
@@ -253,6 +262,8 @@ inline void run_fp16_guarded(int* dev_flag, hipStream_t s, F&& fn, bool deferrab
     if (over) fn();
 }
 void launch_gemm(const PackedLinear& L, const ASeg* segs, int rows_alloc, const GemmEpi& e, int epi_kind, hipStream_t s);
+long gemm_fp16_fallbacks();                                          // gemm_guard.cpp: passes repeated on the bf16 limbs so far
+size_t gemm_read_stamps(unsigned long long* host, size_t max_n);     // gemm_guard.cpp: phase stamps of the last stamped launch (stamps, knob 20)
 
 // ---------------------------------------------------------------- other kernels (misc.hip / attention.hip / knn.hip)
 void launch_pack_rows(const float* src, int src_ld, int src_cols, float* dst, int dst_ld, int dst_col0, int dst_cols_zero_to,
@@ -260,9 +271,6 @@ void launch_pack_rows(const float* src, int src_ld, int src_cols, float* dst, in
 void launch_fill(float* p, float v, size_t n, hipStream_t s);
 void launch_repeat_extra(const float* extra, int X, float* rowscal, int B, int N, hipStream_t s);
 void launch_layernorm(float* h, int ld, int width, int rows, hipStream_t s);   // in place, no affine (folded into q-proj)
-// limb_ws: scratch of attention_limb_ws_bytes(rows of k/v, dh_pad) bytes for the split-fp16 kernel's K/V limb images; with a null
-// limb_ws, outside an Fp16Guard scope or for dh_pad > 64 the fp32-input MFMA kernel runs
-size_t attention_limb_ws_bytes(long kv_rows, int dh_pad);
 // premlp.hip: fused pre-attention MLP -> LayerNorm -> q projection (one launch instead of six) when the shapes allow it
 bool premlp_rows_ok(int rows_alloc, int ldq, const float* qout, const float* keep_ws, size_t keep_floats);   // the row-resident kernel's launch conditions
 bool premlp_fusable(const PackedLinear& in, const std::vector<PackedLinear>& mid, const PackedLinear& out, const PackedLinear& q);
@@ -283,6 +291,7 @@ void launch_limb_decode(const unsigned short* img, float* out, int ldo, int rows
 bool spline_wide_eligible(const PackedLinear& L, int K_bins);
 void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool permute = true, bool fold = false);
 void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);
+void one_acc_gemm_debug(const float* x, const float* W, const float* bias, float wmax, float* out, int rows, int N, int K, hipStream_t s);   // fc_debug_one_acc_gemm_f32
 bool linear_wide_eligible(const PackedLinear& L, const GemmEpi& e, int rows_alloc);   // a GELU Linear layer with one-accumulator images in and out
 void launch_linear_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);
 bool gemm_spline_wide_on();      // spline_kernel (knob 13) = 5 (shipped): launch_gemm routes eligible EPI_SPLINE launches there
@@ -311,26 +320,40 @@ void launch_change_map(float* lp10, int N, float* lp00, int N0, float* out, int 
                        float* stats4, int* status, hipStream_t s);
 void launch_change_map_ragged(float* lp10, const int64_t* offsets, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff,
                               int use_cutoff, float* stats4, int* status, hipStream_t s);
-void launch_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out, int ldo,
-                      int B, int N, int n_stride_rows, int M, int m_stride_rows, int dh_pad, void* limb_ws, hipStream_t s);
+// ---- attention (attention.hip / attention_weights.hip): one call = a query, a key/value source and a problem
 // un-normalised q of the LayerNorm -> q fold: the attention kernel finishes it (rstd from the per-row sums of squares, bias) on load
 struct AttnLnq { const float* sumsq; int slots; size_t pitch; float inv_width; const float* bias; };
-void launch_attention_c16(const float* q, int ldq, const unsigned short* kv_c16, int n_pad, int col0, float* out, int ldo, int B, int N,
-                          int n_stride_rows, int M, int m_stride_rows, int dh_pad, hipStream_t s, const AttnLnq* lnq = nullptr);
-// the folded engine's attention: keys = values = the context panel, as ONE limb row image [row][hi dh_pad | lo dh_pad] of x 16 (made once per
-// forward by launch_context_limbs from the fp32 panel; raises the scope's range flag like the K|V projection's epilogue does)
+struct AttnQuery {
+    const float* q; int ldq;
+    float qscale = 1.0f;             // multiplier applied to q at load: softmax scale x log2(e), or 1 when the projection is pre-scaled
+    const AttnLnq* lnq = nullptr;    // launch_attention: read with limb-image keys only (on PANELS the caller finishes q first, launch_lnq_finalize);
+                                     // launch_attention_weights: applied with every key form
+};
+// Where the keys and values are: exactly one of three forms.
+struct AttnKeys {
+    enum Form { PANELS, SLICE, CONTEXT } form;
+    // PANELS: fp32 panels.  limb_ws (optional): scratch of attention_limb_ws_bytes(rows of k / v, dh_pad) bytes for the split-fp16 kernel's K / V limb
+    // images; with a null limb_ws, outside an Fp16Guard scope or for dh_pad > 64 the fp32-input MFMA kernel runs
+    const float* k = nullptr; int ldk = 0;
+    const float* v = nullptr; int ldv = 0;
+    void* limb_ws = nullptr;
+    // SLICE: K = columns [col0, col0 + dh_pad) of a GEMM limb-image output (GemmEpi::C16, one-accumulator form) with n_pad columns per row, V the
+    // dh_pad columns behind them.  CONTEXT: keys = values = the packed row image [row][hi dh_pad | lo dh_pad] of launch_context_limbs
+    const unsigned short* img = nullptr; int n_pad = 0, col0 = 0;
+    static AttnKeys panels(const float* k, int ldk, const float* v, int ldv, void* limb_ws) { AttnKeys a{PANELS}; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.limb_ws = limb_ws; return a; }
+    static AttnKeys slice(const unsigned short* img, int n_pad, int col0) { AttnKeys a{SLICE}; a.img = img; a.n_pad = n_pad; a.col0 = col0; return a; }
+    static AttnKeys context(const unsigned short* img) { AttnKeys a{CONTEXT}; a.img = img; return a; }
+};
+struct AttnProblem { int B, N, n_stride_rows, M, m_stride_rows, dh_pad; };      // B scenes of N queries x M keys; rows between scenes; padded head dim
+size_t attention_limb_ws_bytes(long kv_rows, int dh_pad);
+// the context panel's limb image, made once per forward from the fp32 panel; raises the scope's range flag like the K|V projection's epilogue does
 void launch_context_limbs(const float* ctx, int ldc, unsigned short* img, long rows, int dh_pad, hipStream_t s);
-void launch_attention_ctx16(const float* q, int ldq, const unsigned short* ctx16, float* out, int ldo, int B, int N, int n_stride_rows, int M,
-                            int m_stride_rows, int dh_pad, hipStream_t s, const AttnLnq* lnq = nullptr, float qscale = 1.0f);
-void launch_attention_op(const float* q, const float* k, const float* v, float* out, int B, int N, int M, int dh_pad, float scale,
-                         void* limb_ws, hipStream_t s);
-// attention_weights.hip: out[b, p, :] = softmax row of query sel[b, p] (null sel: query p, P == N) over the M keys, dense [B][P][M].  K is the fp32
-// panel k, or -- kv_c16 non-null -- columns [c16_col0, c16_col0 + dh_pad) of a GEMM limb-image output with c16_n_pad columns per row in the
-// one-accumulator form (what launch_attention_c16 reads), or -- k_rows16 non-null -- the packed row image [key][hi dh_pad | lo dh_pad] of
-// launch_context_limbs; lnq as for launch_attention_c16.  No range check on sel on the device.
-void launch_attention_weights(const float* q, int ldq, const float* k, int ldk, const unsigned short* kv_c16, int c16_n_pad, int c16_col0,
-                              float* out, const int32_t* sel, int P, int sel_per_scene, int B, int N, int n_stride_rows, int M, int m_stride_rows,
-                              int dh_pad, float qscale, const AttnLnq* lnq, hipStream_t s, const unsigned short* k_rows16 = nullptr);
+// out[b, n, :dh_pad] = softmax(q k^T) v.  lse (optional, [B * N]): filled by the split-fp16 kernel on PANELS only; returns whether it was
+bool launch_attention(const AttnQuery& query, const AttnKeys& keys, const AttnProblem& pb, float* out, int ldo, hipStream_t s, float* lse = nullptr);
+// out[b, p, :] = softmax row of query sel[b, p] (null sel: query p, P == N) over the M keys, dense [B][P][M]; reads K only.  No range check on
+// sel on the device.
+void launch_attention_weights(const AttnQuery& query, const AttnKeys& keys, const AttnProblem& pb, const int32_t* sel, int P, int sel_per_scene,
+                              float* out, hipStream_t s);
 void launch_base_density(const float* x, int ldx, int d1, int d1_pad, int d2, float* logprob, float log_const,
                          float* z_out, int D, int rows, hipStream_t s);
 void launch_spline(const float* params, int ldp, float* xbuf, int ldx, int x2_col0, int d2, int K, float* logprob, int rows, int inverse,

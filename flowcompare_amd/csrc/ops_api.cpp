@@ -1,9 +1,10 @@
-// Single-operator entry points of the C ABI (fc_op_*): the SAME kernels the engines launch, wrapped so that
-// unit-level parity tests can drive them with dense tensors.  These wrappers allocate temporary device
-// memory for the padded layouts (they are test/diagnostic conveniences, not the hot path).
+// The entry points of the C ABI that are not about one engine: version, last error, the in-library profiler, the knobs and diagnostics, and the
+// single-operator calls (fc_op_*): the SAME kernels the engines launch, wrapped so that unit-level parity tests can drive them with dense
+// tensors.  These wrappers allocate temporary device memory for the padded layouts (they are test/diagnostic conveniences, not the hot path).
+#include <cstring>
 #include <memory>
 
-#include "hostpack.h"
+#include "flow_model.h"
 #include "spline.h"
 
 namespace fc {
@@ -14,13 +15,6 @@ struct TmpBuf {
     ~TmpBuf() { (void)hipFree(p); }
     float* f() const { return (float*)p; }
 };
-}  // namespace fc
-
-
-namespace fc {
-void one_acc_gemm_debug(const float*, const float*, const float*, float, float*, int, int, int, hipStream_t);      // spline_wide.hip
-long gemm_fp16_fallbacks(); size_t gemm_read_stamps(unsigned long long*, size_t);                                      // gemm_guard.cpp
-bool kv_fold_gate_dims(int, int, bool, bool); void flow_set_trace(float*, size_t); void flow_set_expm_info(float*, size_t);      // flow_engine.cpp
 
 Knobs g_knobs;
 
@@ -35,6 +29,21 @@ static const KnobEntry* find_knob(int key) {
 }  // namespace fc
 
 extern "C" {
+
+int fc_abi_version(void) { return FC_ABI_VERSION; }
+const char* fc_last_error(void) { return fc::get_last_error(); }
+
+int fc_profile_enable(int32_t on) { fc::prof_set(on != 0); return FC_OK; }
+int fc_profile_reset(void) { fc::prof_reset(); return FC_OK; }
+int fc_profile_filter(const char* kernel_substr) { fc::prof_filter(kernel_substr); return FC_OK; }
+int fc_profile_stride(int32_t n) { fc::prof_stride(n); return FC_OK; }
+int fc_profile_report(char* buf, size_t cap) {
+    FC_API_BEGIN
+    const std::string r = fc::prof_report_json();
+    if (!buf || cap < r.size() + 1) throw fc::Error(FC_ERR_INVALID, "fc_profile_report: buffer too small");
+    memcpy(buf, r.c_str(), r.size() + 1);
+    FC_API_END
+}
 
 /* the kernel-choice knobs of csrc/knobs.h by key (profiles/kernel_bench.py, bench.py --knob, the parity tests; not part of the stable ABI surface
    in fcflow.h on purpose).  An unknown or retired key is FC_ERR_INVALID; a value outside the knob's accepted set (a kernel variant that lost an
@@ -69,7 +78,7 @@ int fc_debug_one_acc_gemm_f32(const float* x, const float* W, const float* bias,
 int32_t fc_debug_spline_col(int32_t j, int32_t pp, int32_t K) { return fc::spline_col(j, pp, K); }
 int32_t fc_debug_spline_tile_pos(int32_t c, int32_t K) { return fc::spline_tile_pos(c, K); }
 
-/* host-side view of the K|V fold's gate (flow_engine.cpp kv_fold_gate_dims) for the CPU tests: 1 when a flow whose attentions have this
+/* host-side view of the K|V fold's gate (flow_pack.cpp kv_fold_gate_dims) for the CPU tests: 1 when a flow whose attentions have this
    embedding width, inner width and these biases gets to_kv folded away at fc_flow_create (with kv_fold, knob 33, at its default); no device call */
 int32_t fc_debug_kv_fold_gate(int32_t E, int32_t inner, int32_t q_bias, int32_t kv_bias) { return fc::kv_fold_gate_dims(E, inner, q_bias != 0, kv_bias != 0) ? 1 : 0; }
 
@@ -216,7 +225,7 @@ int fc_op_attention_f32(const float* q, const float* k, const float* v, float* o
     if (D != 32 && D != 64 && D != 128 && D != 256) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_f32: D must be 32, 64 or 128, or 256");
     fc::TmpBuf limbs(fc::attention_limb_ws_bytes((long)B * M, D)), flag(sizeof(int));
     fc::run_fp16_guarded((int*)flag.p, (hipStream_t)stream,
-                         [&] { fc::launch_attention_op(q, k, v, out, B, N, M, D, scale, limbs.p, (hipStream_t)stream); });
+                         [&] { fc::launch_attention({q, D, scale * fc::kLog2eF}, fc::AttnKeys::panels(k, D, v, D, limbs.p), {B, N, N, M, M, D}, out, D, (hipStream_t)stream); });
     FC_HIP(hipStreamSynchronize((hipStream_t)stream));
     FC_API_END
 }
@@ -233,9 +242,9 @@ int fc_debug_attention_ctx_f32(const float* q, const float* c, float* out, int32
     fc::run_fp16_guarded((int*)flag.p, (hipStream_t)stream, [&] {
         if (fc::gemm_fp16_flag() && fc::g_knobs.attn_fp16) {
             fc::launch_context_limbs(c, D, (unsigned short*)limbs.p, (long)B * M, D, (hipStream_t)stream);
-            fc::launch_attention_ctx16(q, D, (const unsigned short*)limbs.p, out, D, B, N, N, M, M, D, (hipStream_t)stream, nullptr, scale * 1.4426950408889634f);
+            fc::launch_attention({q, D, scale * fc::kLog2eF}, fc::AttnKeys::context((const unsigned short*)limbs.p), {B, N, N, M, M, D}, out, D, (hipStream_t)stream);
         } else {                                        // as in the engine: the repeat after a raised range flag (and attn_fp16, knob 5, = 0) takes c itself, in fp32
-            fc::launch_attention_op(q, c, c, out, B, N, M, D, scale, nullptr, (hipStream_t)stream);
+            fc::launch_attention({q, D, scale * fc::kLog2eF}, fc::AttnKeys::panels(c, D, c, D, nullptr), {B, N, N, M, M, D}, out, D, (hipStream_t)stream);
         }
     });
     FC_HIP(hipStreamSynchronize((hipStream_t)stream));
@@ -247,8 +256,8 @@ int fc_op_attention_weights_f32(const float* q, const float* k, float* out, cons
     FC_API_BEGIN
     if (!q || !k || !out) throw fc::Error(FC_ERR_INVALID, "fc_op_attention_weights_f32: null pointer");
     if (D != 32 && D != 64 && D != 128 && D != 256) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_weights_f32: D must be 32, 64 or 128, or 256");
-    fc::launch_attention_weights(q, D, k, D, nullptr, 0, 0, out, sel, sel ? P : N, sel_per_scene, B, N, N, M, M, D, scale * 1.4426950408889634f,
-                                 nullptr, (hipStream_t)stream);
+    fc::launch_attention_weights({q, D, scale * fc::kLog2eF}, fc::AttnKeys::panels(k, D, nullptr, 0, nullptr), {B, N, N, M, M, D}, sel, sel ? P : N, sel_per_scene, out,
+                                 (hipStream_t)stream);
     FC_HIP(hipStreamSynchronize((hipStream_t)stream));
     FC_API_END
 }

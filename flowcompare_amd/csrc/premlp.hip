@@ -342,7 +342,7 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 #pragma unroll
         for (int e = 0; e < 8; ++e) { nh[b][e] = 0; nl[b][e] = 0; }
     // ---- pre-layer (NLU > 0): z = W_lu xprev + b_lu, the previous flow layer's folded ActNorm + permuter (models/act_norm.py:37-43,
-    //      models/permuters.py:164-169; flow_engine.cpp build_lin) -- one launch per layer fewer, and its output never crosses HBM on the way
+    //      models/permuters.py:164-169; flow_pack.cpp build_lin) -- one launch per layer fewer, and its output never crosses HBM on the way
     //      to this kernel.  Same chunk pipeline as `layer`: iteration c multiplies chunk c (32 outputs, K = 32 NLU from the uh / ul fragments)
     //      and finishes chunk c - 1: bias, fp32 store of the lane's 8 consecutive columns of its row into xnext (every later kernel of the
     //      layer reads the latent there), and -- for the first KSIN chunks, x1' -- the limb split into the in_layer's input fragments.

@@ -612,9 +612,6 @@ static void launch_attn_bwd(const AttnBwdParams& p, int B, hipStream_t s) {
     FC_HIP(hipGetLastError());
 }
 
-bool launch_attention_scaled_op(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out, int ldo, int B, int N, int M,
-                                int dh_pad, float scale, void* limb_ws, hipStream_t s, float* lse);      // attention.hip
-
 }  // namespace fc
 
 using namespace fc;
@@ -639,8 +636,9 @@ int fc_train_attention_fwd_f32(const float* q, int32_t ldq, const float* k, int3
     check_mat(q, ldq, D, "q"); check_mat(k, ldk, D, "k"); check_mat(v, ldv, D, "v"); check_mat(out, ldo, D, "out");
     const bool f16 = ovf && ws && ws_bytes >= fc_train_attention_ws_bytes(B, N, M, D) && !((uintptr_t)ws & 15);
     Fp16FlagScope scope(f16 ? (int*)ovf : nullptr);
-    const bool wrote = launch_attention_scaled_op(q, ldq, k, ldk, v, ldv, out, ldo, B, N, M, D, scale, f16 ? ws : nullptr, (hipStream_t)stream,
-                                                  (f16 && D == 64) ? stats : nullptr);
+    // strided q / k / v (columns of wider panels), explicit softmax scale; the log-sum-exp rows come from the split-fp16 kernel only
+    const bool wrote = launch_attention({q, ldq, scale * kLog2eF}, AttnKeys::panels(k, ldk, v, ldv, f16 ? ws : nullptr), {B, N, N, M, M, D}, out, ldo,
+                                        (hipStream_t)stream, (f16 && D == 64) ? stats : nullptr);
     if (stats_valid) *stats_valid = wrote ? 1 : 0;
     FC_API_END
 }

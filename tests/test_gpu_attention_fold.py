@@ -1,4 +1,4 @@
-"""The K|V fold of the inference engine on the GPU (csrc/flow_engine.cpp build_attn / prepare, csrc/attention.hip attn16_kernel<64, 1>;
+"""The K|V fold of the inference engine on the GPU (csrc/flow_pack.cpp build_attn, csrc/flow_engine.cpp prepare, csrc/attention.hip attn16_kernel<64, 1>;
 DESIGN.md sections 4, 5, 9): to_kv folded into the q projections and the consumers' in_layers, every attention attending over ONE limb
 image of the context panel, a 64-key tile staged once for the S and the PV phase.  fc_debug_set key 33 (read when a flow is created)
 selects the folded (1, shipped) or the projected-K|V engine (0); a test that flips it drops the module's engine handle so that the next

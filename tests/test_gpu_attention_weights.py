@@ -217,7 +217,7 @@ PATHS = [("row-resident chain q (augmenter: fold finished on load), limb-image K
 
 @pytest.mark.parametrize("label,knobs,kform,qmarks", PATHS, ids=["default", "fold_on_load", "fold_finalize-fp32_K", "three_launch", "chain-fp32_K", "no_guard_scope"])
 def test_every_operand_form_on_the_sharp_fixture(label, knobs, kform, qmarks):
-    """Which run leaves q / K in which form (csrc/flow_engine.cpp run_attention, prepare), all at the real dims of attnw_sharp_L3 (head dim 64,
+    """Which run leaves q / K in which form (csrc/flow_engine.cpp attention_keys / run_attention, prepare), all at the real dims of attnw_sharp_L3 (head dim 64,
     pre-attention MLP 256 wide), selected with the fc_debug_set keys tests/test_gpu_flow.py uses and restored afterwards:
       q final from launch_premlp            default (knob 8 = 2), flow layers        K limb image: whenever knob 5 = 1 inside a guard scope
       q un-normalised, finished on load     default, the augmenter; knob 8 = 0: all  K fp32 panel: knob 5 = 0, knob 0 = 3 (no guard scope)

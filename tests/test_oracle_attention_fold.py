@@ -1,4 +1,4 @@
-"""The K|V fold of the inference engine (csrc/flow_engine.cpp build_attn), checked on the CPU in fp64 against the
+"""The K|V fold of the inference engine (csrc/flow_pack.cpp build_attn), checked on the CPU in fp64 against the
 oracle's cross attention (oracle/flow_oracle.py::cross_attention, reference models/perceiver.py:89-115):
 
     q k^T             = LN(h) (Wk^T Wq)^T ctx^T
@@ -79,7 +79,7 @@ def test_fold_needs_no_shape_change_only_at_equal_widths():
 
 
 def test_gate_refuses_other_widths_and_biased_projections():
-    """The engine's gate (csrc/flow_engine.cpp kv_fold_gate_dims, host code; read through fc_debug_kv_fold_gate without a device): the fold is
+    """The engine's gate (csrc/flow_pack.cpp kv_fold_gate_dims, host code; read through fc_debug_kv_fold_gate without a device): the fold is
     taken when the embedding is as wide as the attention's inner dimension, the two pad to the same kernel width (the embedding panel to a
     multiple of 32, the inner dimension to 32 / 64 / 128: 65..96 do not) and neither to_q nor to_kv has a bias, and only then."""
     from flowcompare_amd import engine

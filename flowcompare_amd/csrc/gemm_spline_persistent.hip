@@ -188,9 +188,9 @@ __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, floa
             if (p.ablate == 1) {                                        // (diagnostic knob 14 = 1: no spline evaluation)
                 pyA = spl_x[0] + P(0); lA = P(1); pyB = spl_x[1] + P(25); lB = P(26); pyC = spl_x[2] + P(50); lC = P(51);
             } else {
-                rq_spline_fwd_regs<8>(spl_x[0], [&](int q) { return P(q); }, pyA, lA);
-                rq_spline_fwd_regs<8>(spl_x[1], [&](int q) { return P(25 + q); }, pyB, lB);
-                rq_spline_fwd_regs<8>(spl_x[2], [&](int q) { return q < 14 ? P(50 + q) : t4[q - 14]; }, pyC, lC);
+                rq_spline_fwd_regs<8>(spl_x[0], [&](int q) { return P(q); }, rq_unscaled{}, pyA, lA);
+                rq_spline_fwd_regs<8>(spl_x[1], [&](int q) { return P(25 + q); }, rq_unscaled{}, pyB, lB);
+                rq_spline_fwd_regs<8>(spl_x[2], [&](int q) { return q < 14 ? P(50 + q) : t4[q - 14]; }, rq_unscaled{}, pyC, lC);
             }
             lA = vA ? lA : 0.f; lB = vB ? lB : 0.f; lC = vC ? lC : 0.f;
             const float l2 = upper_to_lower(lA), l3 = upper_to_lower(lB);

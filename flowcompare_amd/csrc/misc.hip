@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void spline_rows_kernel(const float* __restric
 }
 void launch_spline(const float* params, int ldp, float* xbuf, int ldx, int x2_col0, int d2, int K, float* logprob, int rows, int inverse,
                    hipStream_t s) {
-    if (K != 4 && K != 8 && K != 16) throw Error(FC_ERR_UNSUPPORTED, "spline: num_bins_spline must be 4, 8 or 16");
+    spline_bins_require(K, "spline: num_bins_spline");
     if (ldp < spline_ncols(d2, K)) throw Error(FC_ERR_INVALID, "spline: parameter pitch too small");
     ProfScope ps("fc::spline_rows_kernel", 0.0, 4.0 * rows * ((3.0 * K + 1) * d2 + 2.0 * d2 + 2.0), s);
     hipLaunchKernelGGL(spline_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, params, ldp, xbuf, ldx, x2_col0, d2, K, logprob, rows, inverse);
@@ -229,7 +229,7 @@ __global__ void spline_flat_kernel(const float* x, const float* params, float* y
     lad[i] = ll;
 }
 void launch_spline_flat(const float* x, const float* params, float* y, float* lad, int64_t n, int K, int inverse, hipStream_t s) {
-    if (K != 4 && K != 8 && K != 16) throw Error(FC_ERR_UNSUPPORTED, "spline: num_bins_spline must be 4, 8 or 16");
+    spline_bins_require(K, "spline: num_bins_spline");
     if (n <= 0) return;
     hipLaunchKernelGGL(spline_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, params, y, lad, n, K, inverse);
     FC_HIP(hipGetLastError());

@@ -1,6 +1,11 @@
-// Rational-quadratic spline element (shared by the stand-alone spline kernels in misc.hip and the fused GEMM epilogue in gemm.hip).
+// Rational-quadratic spline element: the general routine of the stand-alone spline kernels (misc.hip) and the training forward
+// (train_elem.hip), the branch-free forward evaluator of the fused GEMM epilogues (gemm_kernel.h, gemm_spline_persistent.hip,
+// spline_wide.hip), and the column layout of the spline parameter layer's output.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
+
+#include "common.h"
 
 namespace fc {
 
@@ -9,50 +14,47 @@ namespace fc {
 // u points at 3K+1 parameters [K widths | K heights | K+1 derivative logits] with element stride `us`.
 // Quirks reproduced: derivative logits are padded left with log(exp(1-min_d-1)); knot i>=1 uses ud[i-1];
 // ud[K] is never used; last knot + 1e-6 only for the bin search; outside [-3,3] identity with logabsdet 0.
+constexpr float RQ_BOUND = 3.0f;                                 // tail bound: identity outside [-RQ_BOUND, RQ_BOUND]
+constexpr float RQ_MIN_W = 1e-3f, RQ_MIN_H = 1e-3f, RQ_MIN_D = 1e-3f;       // minimum bin width, bin height, knot derivative
+constexpr float RQ_PAD_LOGIT = -1e-3f;                           // log(exp(1 - min_derivative - 1)): left pad of the derivative logits
+constexpr float RQ_SEARCH_EPS = 1e-6f;                           // added to the last knot, for the bin search only
+
 // v_exp_f32 / v_log_f32 / v_rcp_f32 based helpers (about 1 ulp on the base-2 function): the spline evaluates 16 exponentials,
 // 2 softplus, 2 logs and ~10 divisions per element, which made the ocml versions the kernel's dominant VALU cost.
 __device__ __forceinline__ float fast_exp(float v) { return __builtin_amdgcn_exp2f(v * 1.4426950408889634f); }
 __device__ __forceinline__ float fast_log(float v) { return __builtin_amdgcn_logf(v) * 0.6931471805599453f; }
 __device__ __forceinline__ float fast_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
+// Forward and inverse, with divergent branches for the bin selection.  rq_spline_bwd_elem (train_elem.hip) is the gradient of THIS
+// routine's forward direction in its own arithmetic (expf, true division, probabilities kept): merging the two would change training bits.
 template <int K>
 __device__ __forceinline__ void rq_spline_elem(float x, const float* u, int us, bool inverse, float& y, float& lad) {
-    constexpr float B = 3.0f, MINW = 1e-3f, MINH = 1e-3f, MIND = 1e-3f;
+    constexpr float B = RQ_BOUND, MIND = RQ_MIN_D;
     if (!(x >= -B && x <= B)) { y = x; lad = 0.f; return; }
-    float cw[K + 1], ch[K + 1];
-    {
-        float e[K], mx = u[0];
+    // cumulative knots of the widths (pass 0) and heights (pass 1): c[0] = -B, c[i] = -B + 2B sum_{k<i} (min + (1 - K min) softmax_k), c[K] = B
+    float knots[2][K + 1];
 #pragma unroll
-        for (int i = 0; i < K; ++i) { e[i] = u[i * us]; mx = fmaxf(mx, e[i]); }
+    for (int h = 0; h < 2; ++h) {
+        const float min_size = h ? RQ_MIN_H : RQ_MIN_W;
+        float e[K], mx = u[h * K * us];
+#pragma unroll
+        for (int i = 0; i < K; ++i) { e[i] = u[(h * K + i) * us]; mx = fmaxf(mx, e[i]); }
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < K; ++i) { e[i] = fast_exp(e[i] - mx); sum += e[i]; }
         float c = 0.f;
         const float rs = __builtin_amdgcn_rcpf(sum);
-        cw[0] = -B;
+        knots[h][0] = -B;
 #pragma unroll
-        for (int i = 0; i < K; ++i) { c += MINW + (1.0f - MINW * K) * (e[i] * rs); cw[i + 1] = 2.0f * B * c - B; }
-        cw[K] = B;
+        for (int i = 0; i < K; ++i) { c += min_size + (1.0f - min_size * K) * (e[i] * rs); knots[h][i + 1] = 2.0f * B * c - B; }
+        knots[h][K] = B;
     }
-    {
-        float e[K], mx = u[K * us];
-#pragma unroll
-        for (int i = 0; i < K; ++i) { e[i] = u[(K + i) * us]; mx = fmaxf(mx, e[i]); }
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < K; ++i) { e[i] = fast_exp(e[i] - mx); sum += e[i]; }
-        float c = 0.f;
-        const float rs = __builtin_amdgcn_rcpf(sum);
-        ch[0] = -B;
-#pragma unroll
-        for (int i = 0; i < K; ++i) { c += MINH + (1.0f - MINH * K) * (e[i] * rs); ch[i + 1] = 2.0f * B * c - B; }
-        ch[K] = B;
-    }
+    const float (&cw)[K + 1] = knots[0], (&ch)[K + 1] = knots[1];
     // bin = #{knots <= x} - 1 over the searched knots (last one + 1e-6)
     int bin = 0;
 #pragma unroll
     for (int i = 1; i <= K; ++i) {
-        const float knot = (inverse ? ch[i] : cw[i]) + (i == K ? 1e-6f : 0.f);
+        const float knot = (inverse ? ch[i] : cw[i]) + (i == K ? RQ_SEARCH_EPS : 0.f);
         bin += (x >= knot) ? 1 : 0;
     }
     float in_cw = cw[0], in_w = cw[1] - cw[0], in_ch = ch[0], in_h = ch[1] - ch[0];
@@ -64,8 +66,7 @@ __device__ __forceinline__ void rq_spline_elem(float x, const float* u, int us, 
             ud0 = u[(2 * K + i - 1) * us]; ud1 = u[(2 * K + i) * us];
         }
     }
-    const float cst = -1e-3f;                                   // log(exp(1 - min_derivative - 1))
-    const float raw0 = bin == 0 ? cst : ud0;
+    const float raw0 = bin == 0 ? RQ_PAD_LOGIT : ud0;
     auto softplus = [](float v) { return v > 20.f ? v : fast_log(1.0f + fast_exp(v)); };
     const float d0 = MIND + softplus(raw0), d1 = MIND + softplus(ud1);
     const float rw = __builtin_amdgcn_rcpf(in_w);
@@ -96,132 +97,24 @@ __device__ __forceinline__ void rq_spline_elem(float x, const float* u, int us, 
     }
 }
 
-// Forward direction only, BRANCH-FREE (the fused GEMM epilogue evaluates 2-3 independent elements per thread as straight-line code, so
-// the compiler can interleave their dependency chains; the general routine above compiles to ~14 divergent branches per element for
-// its bin selection).  Same algorithm and quirks; differences are rounding-level only: exp via one fma + v_exp (log2 e folded into the
-// argument), the softmax scale folded into the prefix sums, bin edges picked by running selects instead of knot arrays, the two
-// derivative logits by an indexed read.  u must be readable at every index 0 .. 3K (it is: the LDS parameter tile).
-template <int K>
-__device__ __forceinline__ void rq_spline_fwd(float x, const float* u, int us, float& y, float& lad) {
-    constexpr float B = 3.0f, MINW = 1e-3f, MINH = 1e-3f, MIND = 1e-3f, L2E = 1.4426950408889634f;
-    const bool inside = x >= -B && x <= B;
-    float ew[K], eh[K], mw = u[0], mh = u[K * us];
-#pragma unroll
-    for (int i = 0; i < K; ++i) { ew[i] = u[i * us]; eh[i] = u[(K + i) * us]; mw = fmaxf(mw, ew[i]); mh = fmaxf(mh, eh[i]); }
-    float sw = 0.f, sh = 0.f;
-    const float ow = -mw * L2E, oh = -mh * L2E;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        ew[i] = __builtin_amdgcn_exp2f(fmaf(ew[i], L2E, ow)); sw += ew[i];
-        eh[i] = __builtin_amdgcn_exp2f(fmaf(eh[i], L2E, oh)); sh += eh[i];
-    }
-    const float fw = (1.0f - MINW * K) * __builtin_amdgcn_rcpf(sw), fh = (1.0f - MINH * K) * __builtin_amdgcn_rcpf(sh);
-    // widths: bin = #{knots <= x} (last knot + 1e-6), in_cw = largest knot <= x, hi = smallest knot > x
-    float c = 0.f, in_cw = -B, hi = INFINITY;
-    int bin = 0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        c += fmaf(fw, ew[i], MINW);
-        const float knot = i == K - 1 ? B : fmaf(2.0f * B, c, -B);
-        const bool ge = x >= (i == K - 1 ? knot + 1e-6f : knot);
-        bin += ge ? 1 : 0;
-        in_cw = ge ? knot : in_cw;
-        hi = ge ? hi : fminf(hi, knot);
-    }
-    const float in_w = hi - in_cw;
-    // heights: knot index bin (lower edge) and bin + 1 (upper edge) of the cumulative heights
-    float ch = 0.f, in_ch = -B, ch_hi = B;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        ch += fmaf(fh, eh[i], MINH);
-        const float knot = i == K - 1 ? B : fmaf(2.0f * B, ch, -B);
-        in_ch = (i + 1 == bin) ? knot : in_ch;
-        ch_hi = (i == bin) ? knot : ch_hi;
-    }
-    const float in_h = ch_hi - in_ch;
-    const int b0 = bin > 0 ? bin - 1 : 0;
-    const float ud0 = u[(2 * K + b0) * us], ud1 = u[(2 * K + bin) * us];
-    const float raw0 = bin == 0 ? -1e-3f : ud0;                  // log(exp(1 - min_derivative - 1))
-    const float d0 = MIND + (raw0 > 20.f ? raw0 : fast_log(1.0f + fast_exp(raw0)));
-    const float d1 = MIND + (ud1 > 20.f ? ud1 : fast_log(1.0f + fast_exp(ud1)));
-    const float rw = __builtin_amdgcn_rcpf(in_w);
-    const float delta = in_h * rw;
-    const float th = (x - in_cw) * rw;
-    const float tt = th * (1.0f - th);
-    const float num = in_h * (delta * th * th + d0 * tt);
-    const float den = delta + (d0 + d1 - 2.0f * delta) * tt;
-    const float yy = in_ch + fast_div(num, den);
-    const float omt = 1.0f - th;
-    const float dnum = delta * delta * (d1 * th * th + 2.0f * delta * tt + d0 * omt * omt);
-    const float ll = fast_log(dnum) - 2.0f * fast_log(den);
-    y = inside ? yy : x;
-    lad = inside ? ll : 0.f;
-}
-
-// The same forward evaluation on parameters held in REGISTERS: every index is a compile-time constant after unrolling (the two
-// derivative logits are picked by running selects along the bin search instead of an indexed read), so a caller can hand over
-// accumulator registers.  Same operations in the same order as rq_spline_fwd: results are bit-identical.
-template <int K, class U>
-__device__ __forceinline__ void rq_spline_fwd_regs(float x, const U& u, float& y, float& lad) {
-    constexpr float B = 3.0f, MINW = 1e-3f, MINH = 1e-3f, MIND = 1e-3f, L2E = 1.4426950408889634f;
-    const bool inside = x >= -B && x <= B;
-    float ew[K], eh[K], mw = u(0), mh = u(K);
-#pragma unroll
-    for (int i = 0; i < K; ++i) { ew[i] = u(i); eh[i] = u(K + i); mw = fmaxf(mw, ew[i]); mh = fmaxf(mh, eh[i]); }
-    float sw = 0.f, sh = 0.f;
-    const float ow = -mw * L2E, oh = -mh * L2E;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        ew[i] = __builtin_amdgcn_exp2f(fmaf(ew[i], L2E, ow)); sw += ew[i];
-        eh[i] = __builtin_amdgcn_exp2f(fmaf(eh[i], L2E, oh)); sh += eh[i];
-    }
-    const float fw = (1.0f - MINW * K) * __builtin_amdgcn_rcpf(sw), fh = (1.0f - MINH * K) * __builtin_amdgcn_rcpf(sh);
-    float c = 0.f, in_cw = -B, hi = INFINITY;
-    float ud0 = -1e-3f, ud1 = u(2 * K);                          // bin 0: left pad log(exp(1 - min_derivative - 1)) and logit 0
-    int bin = 0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        c += fmaf(fw, ew[i], MINW);
-        const float knot = i == K - 1 ? B : fmaf(2.0f * B, c, -B);
-        const bool ge = x >= (i == K - 1 ? knot + 1e-6f : knot);
-        bin += ge ? 1 : 0;
-        in_cw = ge ? knot : in_cw;
-        hi = ge ? hi : fminf(hi, knot);
-        ud0 = ge ? u(2 * K + i) : ud0;                           // knots increase: the last `ge` is i = bin - 1
-        ud1 = ge ? u(2 * K + i + 1) : ud1;
-    }
-    const float in_w = hi - in_cw;
-    float ch = 0.f, in_ch = -B, ch_hi = B;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        ch += fmaf(fh, eh[i], MINH);
-        const float knot = i == K - 1 ? B : fmaf(2.0f * B, ch, -B);
-        in_ch = (i + 1 == bin) ? knot : in_ch;
-        ch_hi = (i == bin) ? knot : ch_hi;
-    }
-    const float in_h = ch_hi - in_ch;
-    const float d0 = MIND + (ud0 > 20.f ? ud0 : fast_log(1.0f + fast_exp(ud0)));
-    const float d1 = MIND + (ud1 > 20.f ? ud1 : fast_log(1.0f + fast_exp(ud1)));
-    const float rw = __builtin_amdgcn_rcpf(in_w);
-    const float delta = in_h * rw;
-    const float th = (x - in_cw) * rw;
-    const float tt = th * (1.0f - th);
-    const float num = in_h * (delta * th * th + d0 * tt);
-    const float den = delta + (d0 + d1 - 2.0f * delta) * tt;
-    const float yy = in_ch + fast_div(num, den);
-    const float omt = 1.0f - th;
-    const float dnum = delta * delta * (d1 * th * th + 2.0f * delta * tt + d0 * omt * omt);
-    const float ll = fast_log(dnum) - 2.0f * fast_log(den);
-    y = inside ? yy : x;
-    lad = inside ? ll : 0.f;
-}
-
-// rq_spline_fwd_regs on parameters that arrive SCALED: logical parameter i = u(i) * os with os an exact power of two.  The
-// scale rides inside the softmax's existing fma (fma(u, L2E os, -max u L2E os) is bit for bit fma(u os, L2E, -max(u os) L2E)), the two
-// derivative logits are scaled after their selection: same operations and roundings as the unscaled routine on u os.
-template <int K, class U>
-__device__ __forceinline__ void rq_spline_fwd_regs_scaled(float x, const U& u, float os, float& y, float& lad) {
-    constexpr float B = 3.0f, MINW = 1e-3f, MINH = 1e-3f, MIND = 1e-3f, L2E = 1.4426950408889634f;
+// Forward direction only, BRANCH-FREE: the fused GEMM epilogues evaluate 2-5 independent elements per thread as straight-line code, so
+// the compiler can interleave their dependency chains (the general routine above compiles to ~14 divergent branches per element for
+// its bin selection).  Same algorithm and quirks; differences to it are rounding-level only: exp via one fma + v_exp (log2 e folded into
+// the argument), the softmax scale folded into the prefix sums, bin edges picked by running selects instead of knot arrays.
+// ONE body serves every caller, so all of them round alike and their results are bit-identical.  u(i) returns parameter i:
+//   INDEXED  the two derivative logits of the bin are read at a run-time index after the search (u in memory: the LDS parameter tile,
+//            readable at every index 0 .. 3K); otherwise they are picked by running selects along the bin search, so every index is a
+//            compile-time constant after unrolling and u may be accumulator registers.
+//   os       the parameters arrive SCALED: logical parameter i = u(i) * os with os an exact power of two.  The scale rides inside the
+//            softmax's existing fma (fma(u, L2E os, -max u L2E os) is bit for bit fma(u os, L2E, -max(u os) L2E)); the two derivative
+//            logits are scaled after their selection: same operations and roundings as os = 1 on u os.
+//            rq_unscaled{} in place of os: the parameters arrive as they are.  With no scale to apply behind the pick, the pad logit
+//            seeds the select chain of the non-INDEXED form instead of being selected at the end (same value, one select fewer).
+struct rq_unscaled { __device__ constexpr operator float() const { return 1.0f; } };
+template <int K, bool INDEXED = false, class U, class S>
+__device__ __forceinline__ void rq_spline_fwd_regs(float x, const U& u, S os, float& y, float& lad) {
+    constexpr float B = RQ_BOUND, MINW = RQ_MIN_W, MINH = RQ_MIN_H, MIND = RQ_MIN_D, L2E = 1.4426950408889634f;
+    constexpr bool SEEDED = std::is_same<S, rq_unscaled>::value && !INDEXED;
     const bool inside = x >= -B && x <= B;
     const float l2s = L2E * os;
     float ew[K], eh[K], mw = u(0), mh = u(K);
@@ -235,21 +128,25 @@ __device__ __forceinline__ void rq_spline_fwd_regs_scaled(float x, const U& u, f
         eh[i] = __builtin_amdgcn_exp2f(fmaf(eh[i], l2s, oh)); sh += eh[i];
     }
     const float fw = (1.0f - MINW * K) * __builtin_amdgcn_rcpf(sw), fh = (1.0f - MINH * K) * __builtin_amdgcn_rcpf(sh);
+    // widths: bin = #{knots <= x} (last knot + 1e-6), in_cw = largest knot <= x, hi = smallest knot > x
     float c = 0.f, in_cw = -B, hi = INFINITY;
-    float ud0r = 0.f, ud1r = u(2 * K);
+    float ud0r = SEEDED ? RQ_PAD_LOGIT : 0.f, ud1r = u(2 * K);   // bin 0: the left pad and logit 0
     int bin = 0;
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         c += fmaf(fw, ew[i], MINW);
         const float knot = i == K - 1 ? B : fmaf(2.0f * B, c, -B);
-        const bool ge = x >= (i == K - 1 ? knot + 1e-6f : knot);
+        const bool ge = x >= (i == K - 1 ? knot + RQ_SEARCH_EPS : knot);
         bin += ge ? 1 : 0;
         in_cw = ge ? knot : in_cw;
         hi = ge ? hi : fminf(hi, knot);
-        ud0r = ge ? u(2 * K + i) : ud0r;
-        ud1r = ge ? u(2 * K + i + 1) : ud1r;
+        if constexpr (!INDEXED) {
+            ud0r = ge ? u(2 * K + i) : ud0r;                     // knots increase: the last `ge` is i = bin - 1
+            ud1r = ge ? u(2 * K + i + 1) : ud1r;
+        }
     }
     const float in_w = hi - in_cw;
+    // heights: knot index bin (lower edge) and bin + 1 (upper edge) of the cumulative heights
     float ch = 0.f, in_ch = -B, ch_hi = B;
 #pragma unroll
     for (int i = 0; i < K; ++i) {
@@ -259,7 +156,8 @@ __device__ __forceinline__ void rq_spline_fwd_regs_scaled(float x, const U& u, f
         ch_hi = (i == bin) ? knot : ch_hi;
     }
     const float in_h = ch_hi - in_ch;
-    const float ud0 = bin == 0 ? -1e-3f : ud0r * os, ud1 = ud1r * os;      // bin 0: left pad log(exp(1 - min_derivative - 1))
+    if constexpr (INDEXED) { ud0r = u(2 * K + (bin > 0 ? bin - 1 : 0)); ud1r = u(2 * K + bin); }
+    const float ud0 = SEEDED ? ud0r : bin == 0 ? RQ_PAD_LOGIT : ud0r * os, ud1 = ud1r * os;
     const float d0 = MIND + (ud0 > 20.f ? ud0 : fast_log(1.0f + fast_exp(ud0)));
     const float d1 = MIND + (ud1 > 20.f ? ud1 : fast_log(1.0f + fast_exp(ud1)));
     const float rw = __builtin_amdgcn_rcpf(in_w);
@@ -276,6 +174,12 @@ __device__ __forceinline__ void rq_spline_fwd_regs_scaled(float x, const U& u, f
     lad = inside ? ll : 0.f;
 }
 
+// the same on parameters in memory, element stride `us`
+template <int K>
+__device__ __forceinline__ void rq_spline_fwd(float x, const float* u, int us, float& y, float& lad) {
+    rq_spline_fwd_regs<K, true>(x, [&](int i) { return u[i * us]; }, rq_unscaled{}, y, lad);
+}
+
 // The K = 8 spline on its 22 INFORMATIVE parameters [7 width logits | 7 height logits | derivative logits 0..7], scaled as above (the folded
 // image of spline_wide.hip).  softmax is shift-invariant, so the parameter layer was folded at pack time to emit w_i - w_7 and h_i - h_7:
 // logit 7 of either softmax is the literal 0 and still takes part in the maximum, the exponentials and the sum (today's operation sequence on
@@ -283,19 +187,34 @@ __device__ __forceinline__ void rq_spline_fwd_regs_scaled(float x, const U& u, f
 // result is discarded, so a literal stands in for it as well.
 template <class U>
 __device__ __forceinline__ void rq_spline_fwd_regs_folded(float x, const U& u, float os, float& y, float& lad) {
-    rq_spline_fwd_regs_scaled<8>(x, [&](int i) { return i < 7 ? u(i) : i == 7 || i == 15 || i == 24 ? 0.f : i < 15 ? u(i - 1) : u(i - 2); }, os, y, lad);
+    rq_spline_fwd_regs<8>(x, [&](int i) { return i < 7 ? u(i) : i == 7 || i == 15 || i == 24 ? 0.f : i < 15 ? u(i - 1) : u(i - 2); }, os, y, lad);
 }
 
-template <int K>
-__device__ __forceinline__ void rq_dispatch(float x, const float* u, int us, bool inv, float& y, float& lad) {
-    rq_spline_elem<K>(x, u, us, inv, y, lad);
+// The bin counts the kernels are instantiated for (host side): calls f(std::integral_constant<int, K>) and returns whether K is one of them.
+template <class F>
+inline bool spline_bins_dispatch(int K, F&& f) {
+    switch (K) {
+        case 4: f(std::integral_constant<int, 4>{}); return true;
+        case 8: f(std::integral_constant<int, 8>{}); return true;
+        case 16: f(std::integral_constant<int, 16>{}); return true;
+        default: return false;
+    }
 }
+inline bool spline_bins_ok(int K) { return spline_bins_dispatch(K, [](auto) {}); }
+// host entry points: dispatch, or refuse in the caller's words ("<who>: <its name of the bin count>")
+template <class F>
+inline void spline_bins_require(int K, const char* what, F&& f) {
+    if (!spline_bins_dispatch(K, f)) throw Error(FC_ERR_UNSUPPORTED, std::string(what) + " must be 4, 8 or 16");
+}
+inline void spline_bins_require(int K, const char* what) { spline_bins_require(K, what, [](auto) {}); }
 
+// The device side keeps its own switch over the same three counts: routed through spline_bins_dispatch and a lambda, the kernels that
+// call rq_any compile to different code.
 __device__ __forceinline__ void rq_any(int K, float x, const float* u, int us, bool inv, float& y, float& lad) {
     switch (K) {
-        case 4: rq_dispatch<4>(x, u, us, inv, y, lad); break;
-        case 8: rq_dispatch<8>(x, u, us, inv, y, lad); break;
-        case 16: rq_dispatch<16>(x, u, us, inv, y, lad); break;
+        case 4: rq_spline_elem<4>(x, u, us, inv, y, lad); break;
+        case 8: rq_spline_elem<8>(x, u, us, inv, y, lad); break;
+        case 16: rq_spline_elem<16>(x, u, us, inv, y, lad); break;
         default: y = x; lad = 0.f; break;     // rejected on the host
     }
 }

@@ -553,9 +553,9 @@ void spline_wide_kernel(const SplineWideParams p) {
             } else {
 #pragma unroll
                 for (int ib = 0; ib < 4; ++ib)
-                    rq_spline_fwd_regs_scaled<8>(spl_x[ib], [&](int q) { return acc[ib][q >> 2][q & 3]; }, os, yv[ib], lv[ib]);
+                    rq_spline_fwd_regs<8>(spl_x[ib], [&](int q) { return acc[ib][q >> 2][q & 3]; }, os, yv[ib], lv[ib]);
                 // dim 4: parameters 0..6 from (transposed) block 0, 7..12 from block 1, 13..18 from block 2, 19..24 from block 3, slots 25 + i
-                rq_spline_fwd_regs_scaled<8>(spl_x[4], [&](int q) {
+                rq_spline_fwd_regs<8>(spl_x[4], [&](int q) {
                     const int part = q < 7 ? 0 : (q - 1) / 6, s = 25 + (q < 7 ? q : (q - 1) % 6);
                     return acc[part][s >> 2][s & 3];
                 }, os, yv[4], lv[4]);

@@ -51,45 +51,38 @@ __global__ __launch_bounds__(256) void spline_train_fwd_kernel(const float* __re
 // gradient of (y, lad) of ONE spline element: gx = dL/dx, gu[3K+1] = dL/d logits, given gy = dL/dy and gl = dL/dlad
 template <int K>
 __device__ __forceinline__ void rq_spline_bwd_elem(float x, const float* __restrict__ u, float gy, float gl, float& gx, float* __restrict__ gu) {
-    constexpr float B = 3.0f, MINW = 1e-3f, MINH = 1e-3f, MIND = 1e-3f;
+    constexpr float B = RQ_BOUND, MINW = RQ_MIN_W, MINH = RQ_MIN_H, MIND = RQ_MIN_D;
     if (!(x >= -B && x <= B)) {
         gx = gy;
 #pragma unroll
         for (int i = 0; i < 3 * K + 1; ++i) gu[i] = 0.f;
         return;
     }
-    float pw[K], ph[K], cw[K + 1], ch[K + 1];
-    {
-        float mx = u[0];
+    // softmax probabilities and cumulative knots of the widths (pass 0) and heights (pass 1), as in rq_spline_elem (spline.h) but in this
+    // routine's own arithmetic (expf, true division) and with the probabilities kept: sharing that block would change training bits
+    float probs[2][K], knots[2][K + 1];
 #pragma unroll
-        for (int i = 0; i < K; ++i) { pw[i] = u[i]; mx = fmaxf(mx, pw[i]); }
+    for (int hh = 0; hh < 2; ++hh) {
+        const float min_size = hh ? MINH : MINW;
+        float* p = probs[hh];
+        float mx = u[hh * K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) { p[i] = u[hh * K + i]; mx = fmaxf(mx, p[i]); }
         float sum = 0.f;
 #pragma unroll
-        for (int i = 0; i < K; ++i) { pw[i] = expf(pw[i] - mx); sum += pw[i]; }
+        for (int i = 0; i < K; ++i) { p[i] = expf(p[i] - mx); sum += p[i]; }
         float c = 0.f;
-        cw[0] = -B;
+        knots[hh][0] = -B;
 #pragma unroll
-        for (int i = 0; i < K; ++i) { pw[i] = pw[i] / sum; c += MINW + (1.0f - MINW * K) * pw[i]; cw[i + 1] = 2.0f * B * c - B; }
-        cw[K] = B;
+        for (int i = 0; i < K; ++i) { p[i] = p[i] / sum; c += min_size + (1.0f - min_size * K) * p[i]; knots[hh][i + 1] = 2.0f * B * c - B; }
+        knots[hh][K] = B;
     }
-    {
-        float mx = u[K];
-#pragma unroll
-        for (int i = 0; i < K; ++i) { ph[i] = u[K + i]; mx = fmaxf(mx, ph[i]); }
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < K; ++i) { ph[i] = expf(ph[i] - mx); sum += ph[i]; }
-        float c = 0.f;
-        ch[0] = -B;
-#pragma unroll
-        for (int i = 0; i < K; ++i) { ph[i] = ph[i] / sum; c += MINH + (1.0f - MINH * K) * ph[i]; ch[i + 1] = 2.0f * B * c - B; }
-        ch[K] = B;
-    }
+    const float (&pw)[K] = probs[0], (&ph)[K] = probs[1], (&cw)[K + 1] = knots[0], (&ch)[K + 1] = knots[1];
     int bin = 0;
 #pragma unroll
-    for (int i = 1; i <= K; ++i) bin += (x >= cw[i] + (i == K ? 1e-6f : 0.f)) ? 1 : 0;
+    for (int i = 1; i <= K; ++i) bin += (x >= cw[i] + (i == K ? RQ_SEARCH_EPS : 0.f)) ? 1 : 0;
     float in_cw = cw[0], w = cw[1] - cw[0], in_ch = ch[0], h = ch[1] - ch[0];
-    float raw0 = -1e-3f, raw1 = u[2 * K];
+    float raw0 = RQ_PAD_LOGIT, raw1 = u[2 * K];
 #pragma unroll
     for (int i = 1; i < K; ++i)
         if (bin == i) { in_cw = cw[i]; w = cw[i + 1] - cw[i]; in_ch = ch[i]; h = ch[i + 1] - ch[i]; raw0 = u[2 * K + i - 1]; raw1 = u[2 * K + i]; }
@@ -548,12 +541,7 @@ int fc_train_rqspline_fwd_f32(const float* x2, int32_t ldx, const float* params,
         ((uintptr_t)params & 15))
         throw Error(FC_ERR_INVALID, "fc_train_rqspline_fwd_f32: bad argument (params: 16-byte aligned rows, pitch a multiple of 4)");
     hipStream_t s = (hipStream_t)stream;
-    switch (K) {
-        case 4: spline_fwd_k<4>(x2, ldx, params, ldp, y2, ldy, ldj, rows, d2, s); break;
-        case 8: spline_fwd_k<8>(x2, ldx, params, ldp, y2, ldy, ldj, rows, d2, s); break;
-        case 16: spline_fwd_k<16>(x2, ldx, params, ldp, y2, ldy, ldj, rows, d2, s); break;
-        default: throw Error(FC_ERR_UNSUPPORTED, "fc_train_rqspline_fwd_f32: num_bins must be 4, 8 or 16");
-    }
+    spline_bins_require(K, "fc_train_rqspline_fwd_f32: num_bins", [&](auto k) { spline_fwd_k<decltype(k)::value>(x2, ldx, params, ldp, y2, ldy, ldj, rows, d2, s); });
     FC_API_END
 }
 
@@ -565,12 +553,9 @@ int fc_train_rqspline_bwd_f32(const float* x2, int32_t ldx, const float* params,
         ldp < round_up(d2 * (3 * K + 1), 4) || ldp % 4 != 0 || lddp < round_up(d2 * (3 * K + 1), 32) || lddp % 4 != 0 || (((uintptr_t)params | (uintptr_t)dparams) & 15))
         throw Error(FC_ERR_INVALID, "fc_train_rqspline_bwd_f32: bad argument (params / dparams: 16-byte aligned rows, pitches multiples of 4)");
     hipStream_t s = (hipStream_t)stream;
-    switch (K) {
-        case 4: spline_bwd_k<4>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, row_absmax, s); break;
-        case 8: spline_bwd_k<8>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, row_absmax, s); break;
-        case 16: spline_bwd_k<16>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, row_absmax, s); break;
-        default: throw Error(FC_ERR_UNSUPPORTED, "fc_train_rqspline_bwd_f32: num_bins must be 4, 8 or 16");
-    }
+    spline_bins_require(K, "fc_train_rqspline_bwd_f32: num_bins", [&](auto k) {
+        spline_bwd_k<decltype(k)::value>(x2, ldx, params, ldp, dy2, lddy, dldj, dx2, lddx, dparams, lddp, rows, d2, row_absmax, s);
+    });
     FC_API_END
 }
 

@@ -1,7 +1,8 @@
 """The C ABI of libfcflow.so as ctypes sees it: one line per entry point, (return kind, parameter kinds).
 
 ENTRIES follows include/fcflow.h in the header's order; DEBUG_ENTRIES are the fc_debug_* diagnostics that csrc/ops_api.cpp defines
-without a declaration in the header.  tests/test_host.py compares both tables with the C sources.
+without a declaration in the header.  tests/test_host.py compares both tables with the C sources.  EXTRA_ENTRIES are the entry points
+declared in headers of their own behind fcflow.h (include/fcflow_attention_mass.h; tests/test_attention_mass_host.py).
 
 Parameter kinds:  P  any pointer (handles, struct pointers, const char*, the stream)     i  int32_t / int     l  int64_t
                   f  float     z  size_t
@@ -116,6 +117,15 @@ ENTRIES = {
     "fc_change_map_ragged_f32":              ("status", "PPPiPiffiPP"),
 }
 
+# Entry points declared in a header of their own behind fcflow.h: include/fcflow_attention_mass.h, in that header's order
+# (tests/test_attention_mass_host.py compares).  Status entries raise like those of ENTRIES.
+EXTRA_ENTRIES = {
+    "fc_flow_attention_mass_workspace_bytes": ("status", "PiiiP"),
+    "fc_flow_attention_mass_f32":            ("status", "PPPPPiPiPPPiiiPzP"),
+    "fc_op_attention_mass_scratch_bytes":    ("size_t", "iii"),
+    "fc_op_attention_mass_f32":              ("status", "PPPPiiiifPzP"),
+}
+
 # Diagnostics and test hooks: they hand back their raw code and never raise (a caller compares fc_debug_set(...) with 0).
 DEBUG_ENTRIES = {
     "fc_debug_set":                          ("int", "ii"),
@@ -138,12 +148,12 @@ def bind(L, status_errcheck):
     """Sets argtypes and restype of every table entry the loaded library has; a status entry of ENTRIES also gets `status_errcheck`.
     A symbol the library lacks is skipped (an FCFLOW_LIB build of this ABI version that predates an entry still loads) and fails
     with AttributeError at the call."""
-    for table in (ENTRIES, DEBUG_ENTRIES):
+    for table in (ENTRIES, EXTRA_ENTRIES, DEBUG_ENTRIES):
         for name, (ret, params) in table.items():
             fn = getattr(L, name, None)
             if fn is None:
                 continue
             fn.argtypes = [PARAM_KINDS[k] for k in params]
             fn.restype = RETURN_KINDS[ret]
-            if ret == "status" and table is ENTRIES:
+            if ret == "status" and table is not DEBUG_ENTRIES:
                 fn.errcheck = status_errcheck

@@ -11,6 +11,7 @@
 #include <functional>
 
 #include "../../include/fcflow.h"
+#include "../../include/fcflow_attention_mass.h"
 #include "knobs.h"
 
 namespace fc {
@@ -354,6 +355,11 @@ bool launch_attention(const AttnQuery& query, const AttnKeys& keys, const AttnPr
 // sel on the device.
 void launch_attention_weights(const AttnQuery& query, const AttnKeys& keys, const AttnProblem& pb, const int32_t* sel, int P, int sel_per_scene,
                               float* out, hipStream_t s);
+// out[b, j] = sum_p row_weight[b, p] * (softmax row of query p)[j] over all N queries (attention_mass.hip): row_weight dense [B][N] or null =
+// ones, out dense [B][M]; slab = attention_mass_slab_bytes(B, N, M) bytes of scratch.  Two launches, no atomics: the same bytes on every run.
+size_t attention_mass_slab_bytes(int B, int N, int M);
+void launch_attention_mass(const AttnQuery& query, const AttnKeys& keys, const AttnProblem& pb, const float* row_weight, float* slab, float* out,
+                           hipStream_t s);
 void launch_base_density(const float* x, int ldx, int d1, int d1_pad, int d2, float* logprob, float log_const,
                          float* z_out, int D, int rows, hipStream_t s);
 void launch_spline(const float* params, int ldp, float* xbuf, int ldx, int x2_col0, int d2, int K, float* logprob, int rows, int inverse,

@@ -140,6 +140,11 @@ struct AttnProbe {
     std::vector<float*> out;        // one [B][P][M] device buffer per entry of `layers`
     const int32_t* sel = nullptr;   // device [P] or [B][P]; null = all N points
     int P = 0, sel_per_scene = 0;
+    // the second kind of request (fc_flow_attention_mass_f32, attention_mass.hip): the weighted column sums of the same rows over all N points
+    std::vector<int> mass_layers;
+    std::vector<float*> mass_out;            // one [B][M] device buffer per entry of `mass_layers`
+    const float* row_weight = nullptr;       // device [B][N], or null = ones
+    float* slab = nullptr;                   // attention_mass_slab_bytes(B, N, M) behind the forward's workspace plan; every layer reuses it (stream order)
 };
 constexpr int kNoProbeLayer = -2;
 
@@ -167,6 +172,9 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
         if (probe)
             for (size_t i = 0; i < probe->layers.size(); ++i)
                 if (probe->layers[i] == probe_layer) launch_attention_weights(qy, keys, pb, probe->sel, probe->P, probe->sel_per_scene, probe->out[i], s);
+        if (probe)
+            for (size_t i = 0; i < probe->mass_layers.size(); ++i)
+                if (probe->mass_layers[i] == probe_layer) launch_attention_mass(qy, keys, pb, probe->row_weight, probe->slab, probe->mass_out[i], s);
         launch_attention(qy, keys, pb, w.a, d.I_pad, s);
     };
     if (premlp_fusable(pre.in_layer, pre.mid, pre.out_layer, at.q) && in.lda >= pre.in_layer.K_pad &&
@@ -520,6 +528,21 @@ int fc_flow_logprob_f32(fc_flow* flow, const float* x, const float* ctx, const f
     FC_API_END
 }
 
+// every request of a probe call is checked before anything is launched: layer ids -1 (augmenter) and 0 .. n_flow_layers - 1 with an attention
+static void check_probe_layer(const fc_flow* flow, const std::string& who, int l) {
+    if (l == -1) {
+        if (!flow->has_augment)
+            throw fc::Error(FC_ERR_INVALID, who + ": layer -1 (the augmenter's attention) does not exist: this flow's first transform "
+                                            "is IdentityTransform (latent_dim == input_dim)");
+    } else if (l < 0 || l >= flow->cfg.n_flow_layers) {
+        throw fc::Error(FC_ERR_INVALID, who + ": layer id " + std::to_string(l) + " is out of range: valid ids are -1 (augmenter) and 0 .. " +
+                                        std::to_string(flow->cfg.n_flow_layers - 1));
+    } else if (!flow->blocks[l].has_attn) {
+        throw fc::Error(FC_ERR_INVALID, who + ": flow layer " + std::to_string(l) + " has no attention: a global-context flow hands the "
+                                        "embedding to its couplings directly (only layer -1, the augmenter, attends)");
+    }
+}
+
 int fc_flow_attention_weights_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int32_t n_eps,
                                   const int32_t* layers, int32_t n_layers, const int32_t* sel, int32_t P, int32_t sel_per_scene, float* const* out,
                                   float* logprob, int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
@@ -534,17 +557,7 @@ int fc_flow_attention_weights_f32(fc_flow* flow, const float* x, const float* ct
     for (int i = 0; i < n_layers; ++i) {
         const int l = layers[i];
         if (!out[i]) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: null output buffer for request " + std::to_string(i));
-        if (l == -1) {
-            if (!flow->has_augment)
-                throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: layer -1 (the augmenter's attention) does not exist: this flow's first transform "
-                                                "is IdentityTransform (latent_dim == input_dim)");
-        } else if (l < 0 || l >= flow->cfg.n_flow_layers) {
-            throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: layer id " + std::to_string(l) + " is out of range: valid ids are -1 (augmenter) and 0 .. " +
-                                            std::to_string(flow->cfg.n_flow_layers - 1));
-        } else if (!flow->blocks[l].has_attn) {
-            throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: flow layer " + std::to_string(l) + " has no attention: a global-context flow hands the "
-                                            "embedding to its couplings directly (only layer -1, the augmenter, attends)");
-        }
+        check_probe_layer(flow, "fc_flow_attention_weights_f32", l);
         probe.layers.push_back(l);
         probe.out.push_back(out[i]);
     }
@@ -552,6 +565,50 @@ int fc_flow_attention_weights_f32(fc_flow* flow, const float* x, const float* ct
     const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
     fc::run_fp16_guarded(flow->fp16_flag, (hipStream_t)stream, [=] {
         fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, nullptr, B, N, M, workspace, workspace_bytes, (hipStream_t)stream, &probe);
+    }, true);
+    fc::check_expm_status(*flow, (hipStream_t)stream);
+    FC_API_END
+}
+
+// the slab region of an attention-mass call sits behind the forward's workspace plan, which therefore stays what fc_flow_workspace_bytes reports
+static size_t mass_slab_offset(const fc_flow& flow, int B, int N, int M) {
+    size_t fwd = 0;
+    fc::plan_ws(flow, B, N, M, nullptr, 0, true, &fwd);
+    return (fwd + 255) / 256 * 256;
+}
+
+int fc_flow_attention_mass_workspace_bytes(const fc_flow* flow, int32_t B, int32_t N, int32_t M, size_t* bytes) {
+    FC_API_BEGIN
+    if (!flow || !bytes || B < 1 || N < 1 || M < 1) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_workspace_bytes: bad argument");
+    *bytes = mass_slab_offset(*flow, B, N, M) + fc::attention_mass_slab_bytes(B, N, M);
+    FC_API_END
+}
+
+int fc_flow_attention_mass_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int32_t n_eps,
+                               const int32_t* layers, int32_t n_layers, const float* row_weight, float* const* out, float* logprob, int32_t B, int32_t N,
+                               int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
+    FC_API_BEGIN
+    if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_f32: null flow / workspace");
+    if (n_layers < 1 || !layers || !out) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_f32: no layers requested (layers / out are null or n_layers < 1)");
+    if (B < 1 || N < 1 || M < 1) throw fc::Error(FC_ERR_INVALID, "B, N, M must be positive");
+    // every request is checked before anything is launched
+    fc::AttnProbe probe;
+    probe.row_weight = row_weight;
+    for (int i = 0; i < n_layers; ++i) {
+        if (!out[i]) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_f32: null output buffer for request " + std::to_string(i));
+        check_probe_layer(flow, "fc_flow_attention_mass_f32", layers[i]);
+        probe.mass_layers.push_back(layers[i]);
+        probe.mass_out.push_back(out[i]);
+    }
+    const size_t slab_off = mass_slab_offset(*flow, B, N, M), need = slab_off + fc::attention_mass_slab_bytes(B, N, M);
+    if (workspace_bytes < need)
+        throw fc::Error(FC_ERR_WORKSPACE, "fc_flow_attention_mass_f32: workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " + std::to_string(need) +
+                                          " needed (fc_flow_attention_mass_workspace_bytes: the forward's workspace plus the slab region)");
+    probe.slab = reinterpret_cast<float*>(static_cast<char*>(workspace) + slab_off);
+    // the guarded pass of fc_flow_logprob_f32; a pass repeated on the bf16 limbs rewrites slabs and outputs too.  Deferred: it owns its arguments
+    const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
+    fc::run_fp16_guarded(flow->fp16_flag, (hipStream_t)stream, [=] {
+        fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, nullptr, B, N, M, workspace, slab_off, (hipStream_t)stream, &probe);
     }, true);
     fc::check_expm_status(*flow, (hipStream_t)stream);
     FC_API_END

@@ -262,6 +262,24 @@ int fc_op_attention_weights_f32(const float* q, const float* k, float* out, cons
     FC_API_END
 }
 
+size_t fc_op_attention_mass_scratch_bytes(int32_t B, int32_t N, int32_t M) { return B < 1 || N < 1 || M < 1 ? 0 : fc::attention_mass_slab_bytes(B, N, M); }
+
+int fc_op_attention_mass_f32(const float* q, const float* k, const float* row_weight, float* out, int32_t B, int32_t N, int32_t M, int32_t D, float scale,
+                             void* scratch, size_t scratch_bytes, void* stream) {
+    FC_API_BEGIN
+    if (!q || !k || !out || !scratch) throw fc::Error(FC_ERR_INVALID, "fc_op_attention_mass_f32: null pointer");
+    if (B < 1 || N < 1 || M < 1) throw fc::Error(FC_ERR_INVALID, "fc_op_attention_mass_f32: B, N, M must be positive");
+    if (D != 32 && D != 64 && D != 128 && D != 256) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_mass_f32: D must be 32, 64, 128 or 256");
+    if (scratch_bytes < fc::attention_mass_slab_bytes(B, N, M))
+        throw fc::Error(FC_ERR_WORKSPACE, "fc_op_attention_mass_f32: scratch too small: " + std::to_string(scratch_bytes) + " bytes given, " +
+                                          std::to_string(fc::attention_mass_slab_bytes(B, N, M)) + " needed (fc_op_attention_mass_scratch_bytes)");
+    if ((uintptr_t)scratch & 15) throw fc::Error(FC_ERR_INVALID, "fc_op_attention_mass_f32: scratch must be 16-byte aligned");
+    fc::launch_attention_mass({q, D, scale * fc::kLog2eF}, fc::AttnKeys::panels(k, D, nullptr, 0, nullptr), {B, N, N, M, M, D}, row_weight, (float*)scratch, out,
+                              (hipStream_t)stream);
+    FC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    FC_API_END
+}
+
 int fc_op_knn_f32(const float* f, int32_t* idx, int32_t B, int32_t M, int32_t C, int32_t k, void* stream) {
     FC_API_BEGIN
     using namespace fc;

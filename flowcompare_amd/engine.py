@@ -23,6 +23,7 @@ PERMUTERS = {"LinearLU": 0, "random_permute": 1, "FullCombiner": 2, "Exponential
 EXPM = {"torch": 0, "original": 1}
 
 EXPORTS = list(abi.ENTRIES)          # every entry point include/fcflow.h declares
+EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES)      # ... and those of the headers behind it (include/fcflow_attention_mass.h)
 
 
 class FcTensor(ctypes.Structure):
@@ -186,6 +187,25 @@ def _points_table(points, B, N, device):
     return t.to(device=device, dtype=torch.int32).contiguous(), t.shape[-1], int(t.dim() == 2)
 
 
+def _row_weights(weights, B, N, device):
+    """Row weights of the attention-mass entry points -> dense fp32 device tensor [B, N], or None (= ones).  Checked here, before the
+    library is called: a tensor on the GPU, shape [N] or [B, N], float or bool, finite."""
+    if weights is None:
+        return None
+    if not torch.is_tensor(weights):
+        raise RuntimeError(f"weights must be None or a tensor of shape [N] or [B, N], got {type(weights).__name__}")
+    if not weights.is_cuda:
+        raise RuntimeError("flowcompare_amd: tensors must live on a HIP device (there is no CPU path)")
+    if not (weights.is_floating_point() or weights.dtype == torch.bool):
+        raise RuntimeError(f"weights must be a float or bool tensor, got dtype {weights.dtype}")
+    if tuple(weights.shape) not in ((N,), (B, N)):
+        raise RuntimeError(f"weights must have shape [N] or [B, N] with B = {B} and N = {N}, got {tuple(weights.shape)}")
+    g = weights.detach().to(device=device, dtype=torch.float32)
+    if not bool(torch.isfinite(g).all()):
+        raise RuntimeError("weights must be finite (a NaN or an infinity was found)")
+    return g.expand(B, N).contiguous()
+
+
 class _Workspace:
     """Grow-only device scratch owned by a handle (the C ABI never allocates inside compute calls)."""
     def __init__(self):
@@ -297,6 +317,29 @@ class FlowHandle:
             L.fc_flow_attention_weights_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), lay_arr, len(layers), _ptr(sel), P,
                                             per_scene, out_arr, _ptr(lp), B, N, M, _ptr(ws), ws.numel(), _stream())
             _keep_if_deferred(x, ctx, extra, sel, lp, ws, *eps, *outs)
+        return (outs, lp) if return_log_prob else outs
+
+    def attention_mass(self, x, context, extra_context, eps, layers, weights=None, return_log_prob=False):
+        """fc_flow_attention_mass_f32: the forward of log_prob that also writes, at the requested attentions, the attention mass of the M
+        context points, mass[b, j] = sum_p weights[b, p] * softmax row p [j] over all N target points.  layers: ints as in
+        attention_weights; weights: None (ones) or [N] / [B, N], float or bool.  Returns a list of [B, M] fp32 tensors in the order of
+        `layers` (and the log-prob).  The [B, N, M] maps are never formed; the result is the same bytes on every run."""
+        x, ctx, extra, eps, B, N, M = self._prep(x, context, extra_context, eps)
+        layers = [int(l) for l in layers]
+        if not layers:
+            raise RuntimeError("attention_mass: no layers requested")
+        L = lib()
+        with torch.cuda.device(self.device):
+            g = _row_weights(weights, B, N, self.device)
+            ws = self._ws.query(L.fc_flow_attention_mass_workspace_bytes, self._h, B, N, M, device=self.device)
+            outs = [torch.empty(B, M, dtype=torch.float32, device=self.device) for _ in layers]
+            lp = torch.empty(B, N, dtype=torch.float32, device=self.device) if return_log_prob else None
+            eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
+            lay_arr = (ctypes.c_int32 * len(layers))(*layers)
+            out_arr = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+            L.fc_flow_attention_mass_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), lay_arr, len(layers), _ptr(g), out_arr,
+                                         _ptr(lp), B, N, M, _ptr(ws), ws.numel(), _stream())
+            _keep_if_deferred(x, ctx, extra, g, lp, ws, *eps, *outs)
         return (outs, lp) if return_log_prob else outs
 
     def inverse(self, z, context, extra_context, eps):
@@ -589,6 +632,21 @@ def op_attention_weights(q, k, scale, points=None):
         sel, P, per_scene = _points_table(points, B, N, q.device)
         out = torch.empty(B, P, M, dtype=torch.float32, device=q.device)
         lib().fc_op_attention_weights_f32(_ptr(q), _ptr(k), _ptr(out), _ptr(sel), P, per_scene, B, N, M, D, scale, _stream())
+    return out
+
+
+def op_attention_mass(q, k, scale, weights=None):
+    """Weighted column sums of softmax(q k^T * scale): q [B,N,D], k [B,M,D], weights None (ones) or [N] / [B,N] -> [B,M]
+    (fc_op_attention_mass_f32; the [B,N,M] map is never formed)."""
+    q, k = _dev_f32(q), _dev_f32(k)
+    B, N, D = q.shape
+    M = k.shape[1]
+    L = lib()
+    with torch.cuda.device(q.device):
+        g = _row_weights(weights, B, N, q.device)
+        scratch = torch.empty(max(L.fc_op_attention_mass_scratch_bytes(B, N, M), 16), dtype=torch.uint8, device=q.device)
+        out = torch.empty(B, M, dtype=torch.float32, device=q.device)
+        L.fc_op_attention_mass_f32(_ptr(q), _ptr(k), _ptr(g), _ptr(out), B, N, M, D, scale, _ptr(scratch), scratch.numel(), _stream())
     return out
 
 

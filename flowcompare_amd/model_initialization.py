@@ -207,6 +207,31 @@ def attention_weights(batch, models_dict, config, layers=("aug",), points=None, 
                                                  return_log_prob=return_log_prob)
 
 
+def attention_mass(batch, models_dict, config, layers=("aug",), weights=None, eps=None, return_log_prob=False):
+    """Attention mass per context point, from the same pass as inner_loop (batch = (extract_0, extract_1, extra_context), sliced,
+    embedded and expanded exactly as inner_loop does): mass[b, j] = sum_p weights[b, p] * w[b, p, j] with w the cross-attention softmax
+    rows of attention_weights -- which points of the context cloud the target cloud (weights None = ones), its change score or a 0/1
+    subset of its points relied on.  layers: "aug", 0-based flow-layer indices, or the string "all" (every attention of the flow in call
+    order: flow.attention_layers()); weights: None or a GPU tensor [N] / [B, N], float or bool, finite -- a wrong shape, a non-finite
+    value or a CPU tensor raises before the library is called.  Returns a list of [B, M] fp32 tensors in the order of `layers`, or
+    (masses, log_prob) with return_log_prob.  No [B, N, M] map is formed (4 B M bytes per layer against 4 B N M), and the bytes are
+    the same on every run.  The batch is taken as given: no scene sharding under config['data_parallel']."""
+    extract_0, extract_1, extra_context = batch
+    if not (extract_0.is_cuda and extract_1.is_cuda):
+        raise RuntimeError("flowcompare_amd: tensors must live on a HIP device (there is no CPU path)")
+    Din = config["input_dim"]
+    extract_0, extract_1 = extract_0[:, :, :Din], extract_1[:, :, :Din]
+    from . import engine as _engine
+    _engine._row_weights(weights, extract_1.shape[0], extract_1.shape[1], extract_1.device)
+    if extra_context is not None:
+        extra_context = extra_context[:, None, :].expand(-1, config["sample_size"], -1)
+    emb = models_dict["input_embedder"](extract_0)
+    if config["global"]:
+        emb = emb[:, None, :].expand(-1, extract_1.shape[1], -1)
+    return models_dict["flow"].attention_mass(extract_1, context=emb, extra_context=extra_context, layers=layers, weights=weights, eps=eps,
+                                              return_log_prob=return_log_prob)
+
+
 def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None):
     """Log-probs of ALL members of the staged voxels against their voxel's staged context: st = the SceneStage (context st.extract_0,
     st.extra_context), dense = staging.stage_dense(...) of the same voxels.  In eval mode a target point's log-likelihood depends on
@@ -317,6 +342,61 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
         out.scatter_reduce_(0, st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1), "amax", include_self=False)
     st10.voxel, st10.count_0, st10.count_1 = both, c0_ctx, c1_fin
     return out, st10
+
+
+def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, layers=("aug",), ground_height=None, multiple=5.4, hard_cutoff=None,
+                              voxels_per_batch=16, weight="change"):
+    """Which points of the OLD scan the change map relied on: the sampled mode of scene_change (same validity rule, stagings, sample
+    counts, chunks of `voxels_per_batch` voxels, log_prob_to_change per chunk) plus, per chunk, attention_mass on the (1 | 0) batch with
+    weights = that chunk's change (weight="change") or ones (weight="uniform").  Per chunk ONE set of augmenter / CIF noise is drawn from
+    flow.noise_shapes and used by all three passes, so the mass belongs to the very pass that scored the change.  (scene_change lets
+    every inner_loop draw its own noise: the change here equals scene_change's bit for bit under the same seed for a flow that draws
+    none, and is another sample of the same quantity otherwise.)  layers as in attention_mass ("all" included).
+    Returns (mass_0 [len(layers), P0], change_1 [P1], the (1 | 0) SceneStage): mass_0[i, r] = layer i's mass on row r of cloud_0, scattered
+    through st10.index_0 -- NaN where no evaluated voxel sampled the row as context, the larger value where two voxels share it (the
+    rule scene_change applies to shared points; deterministic); change_1 as scene_change returns it."""
+    from . import change as change_ops
+    from . import staging
+    if weight not in ("change", "uniform"):
+        raise RuntimeError(f"scene_context_attribution: weight must be \"change\" or \"uniform\", got {weight!r}")
+    fin, ctx = config.get("final_voxel_size"), config.get("context_voxel_size")
+    if fin is None or ctx is None:
+        raise RuntimeError("scene_context_attribution: final_voxel_size / context_voxel_size are not in the config")
+    if config.get("using_extra_context") and ground_height is None:
+        raise RuntimeError("scene_context_attribution: this config uses the extra z-value context and needs ground_height")
+    flow = models_dict["flow"]
+    if isinstance(layers, str):
+        layers = flow.attention_layers() if layers == "all" else (layers,)
+    layers = list(layers)
+    N, M = config["sample_size"], config["n_samples_context"]
+    c0_ctx, c1_fin, c0_fin = (staging.voxel_counts(cloud_0, centers, ctx), staging.voxel_counts(cloud_1, centers, fin),
+                              staging.voxel_counts(cloud_0, centers, fin))
+    both = torch.nonzero((c0_ctx >= M) & (c1_fin >= N) & (c0_fin >= N)).flatten()
+    sel = centers[both].contiguous()
+    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height)
+    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height)
+    assert st10.voxel.numel() == st00.voxel.numel() == both.numel()
+    change_1 = torch.full((cloud_1.shape[0],), float("nan"), dtype=torch.float32, device=cloud_1.device)
+    mass_0 = torch.full((len(layers), cloud_0.shape[0]), float("nan"), dtype=torch.float32, device=cloud_0.device)
+    chunks, masses = [], []
+    with torch.no_grad():
+        for a in range(0, both.numel(), voxels_per_batch):
+            sl = slice(a, a + voxels_per_batch)
+            extra = st10.extra_context[sl] if config.get("using_extra_context") else None
+            batch_10 = (st10.extract_0[sl], st10.extract_1[sl], extra)
+            eps = [torch.randn(s, device=cloud_1.device, dtype=torch.float32) for s in flow.noise_shapes(st10.extract_1[sl].shape[0], N)]
+            _, lp_1_0, _ = inner_loop(batch_10, models_dict, config, eps=eps)
+            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config, eps=eps)
+            change = change_ops.log_prob_to_change(lp_1_0, lp_0_0, multiple, hard_cutoff)
+            chunks.append(change)
+            masses.append(torch.stack(attention_mass(batch_10, models_dict, config, layers=layers, weights=change if weight == "change" else None,
+                                                     eps=eps)))
+    if chunks:
+        change_1.scatter_reduce_(0, st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1), "amax", include_self=False)
+        rows = st10.index_0.reshape(1, -1).expand(len(layers), -1)
+        mass_0.scatter_reduce_(1, rows, torch.cat(masses, dim=1).reshape(len(layers), -1), "amax", include_self=False)
+    st10.voxel, st10.count_0, st10.count_1 = both, c0_ctx, c1_fin
+    return mass_0, change_1, st10
 
 
 def make_sample(n_points, extract_0, models_dict, config, sample_distrib=None, extra_context=None):

@@ -336,23 +336,56 @@ class Flow(nn.Module):
         pass's log-prob comes back too.  Eval mode only.  A full map is 4 B N M bytes per layer: large scenes want `points`."""
         if self.training:
             raise RuntimeError("Flow.attention_weights is eval-mode only (the training path has no attention probe): call .eval() first")
-        ids = []
-        n_layers = self._config["n_flow_layers"]
-        for l in layers:
-            if isinstance(l, str):
-                if l != "aug":
-                    raise RuntimeError(f"attention_weights: unknown layer {l!r}: entries are \"aug\" or a flow-layer index 0 .. {n_layers - 1}")
-                ids.append(-1)
-            else:
-                if isinstance(l, bool) or int(l) != l or not 0 <= int(l) < n_layers:
-                    raise RuntimeError(f"attention_weights: layer index {l!r} is out of range: entries are \"aug\" or a flow-layer index 0 .. {n_layers - 1}")
-                ids.append(int(l))
+        ids = self._probe_layer_ids(layers, "attention_weights")
         B, N = x.shape[0], x.shape[1]
         if eps is None:
             eps = [torch.randn(s, device=x.device, dtype=torch.float32) for s in self.noise_shapes(B, N)]
         self.last_eps = eps
         with torch.no_grad():
             return self._engine().attention_weights(x, context, extra_context, list(eps), ids, points=points, return_log_prob=return_log_prob)
+
+    def _probe_layer_ids(self, layers, what):
+        """`layers` of attention_weights / attention_mass -> the engine's layer ids: "aug" = -1, an int l = flow layer l."""
+        ids = []
+        n_layers = self._config["n_flow_layers"]
+        for l in layers:
+            if isinstance(l, str):
+                if l != "aug":
+                    raise RuntimeError(f"{what}: unknown layer {l!r}: entries are \"aug\" or a flow-layer index 0 .. {n_layers - 1}")
+                ids.append(-1)
+            else:
+                if isinstance(l, bool) or int(l) != l or not 0 <= int(l) < n_layers:
+                    raise RuntimeError(f"{what}: layer index {l!r} is out of range: entries are \"aug\" or a flow-layer index 0 .. {n_layers - 1}")
+                ids.append(int(l))
+        return ids
+
+    def attention_layers(self):
+        """Every attention of the flow in call order, as `layers` entries: "aug" when the flow augments, then the flow layers whose
+        pre-conditioner attends (none of them in a global-context flow)."""
+        c = self._config
+        aug = ["aug"] if c["latent_dim"] > c["input_dim"] else []
+        return aug + ([] if c["global"] else list(range(c["n_flow_layers"])))
+
+    def attention_mass(self, x, context=None, extra_context=None, layers=("aug",), weights=None, eps=None, return_log_prob=False):
+        """Attention mass per context point: for every entry of `layers` (as in attention_weights, or the string "all" = every attention
+        of the flow in call order, attention_layers()) a tensor [B, M] with mass[b, j] = sum_p weights[b, p] * w[b, p, j], the weighted
+        column sums of that attention's softmax rows w over ALL N target points -- which context points the target cloud (weights None
+        = ones), its change score or a 0/1 subset of it relied on.  weights: None or a GPU tensor [N] / [B, N], float or bool, finite.
+        The [B, N, M] maps are never formed (the result is 4 B M bytes per layer) and the bytes are the same on every run.  x, context,
+        extra_context, eps and return_log_prob are those of attention_weights.  Eval mode only."""
+        if self.training:
+            raise RuntimeError("Flow.attention_mass is eval-mode only (the training path has no attention probe): call .eval() first")
+        if isinstance(layers, str) and layers == "all":
+            layers = self.attention_layers()
+        elif isinstance(layers, str):
+            layers = (layers,)
+        ids = self._probe_layer_ids(layers, "attention_mass")
+        B, N = x.shape[0], x.shape[1]
+        if eps is None:
+            eps = [torch.randn(s, device=x.device, dtype=torch.float32) for s in self.noise_shapes(B, N)]
+        self.last_eps = eps
+        with torch.no_grad():
+            return self._engine().attention_mass(x, context, extra_context, list(eps), ids, weights=weights, return_log_prob=return_log_prob)
 
     def sample(self, num_samples, n_points, context=None, sample_distrib=None, extra_context=None, eps=None):
         dist = sample_distrib if sample_distrib is not None else self.sample_dist

@@ -122,8 +122,6 @@ struct PackedLinear {
     float* bias1 = nullptr;        // its bias in the same order, times kOneAccActScale 2^w1_exp
     int w1_exp = 0;
     bool w1_folded = false;        // ... and folded to 22 parameters per dim on 112-column wave tiles (spline_wide.hip; spline_fold, knob 34)
-    bool w1_permuted = false;      // W1 rows in the fused spline kernel's register-slot order (else natural order: a Linear layer of the coupling MLP)
-    float wmax = 0.f;              // max |w| of the packed matrix (pack_linear)
     int N_pad = 0;             // columns written (multiple of 32)
     int K_pad = 0;             // multiple of 32 (sum of segment widths)
     int seg_k[3] = {0, 0, 0};  // padded K of each A segment
@@ -163,8 +161,7 @@ struct GemmEpi {
                                               // following split-fp16 GEMM, which then copies it instead of re-splitting it per column tile)
     const unsigned short* A16 = nullptr;      // input: the A operand given as such an image (single segment of K_pad columns)
     float c16_scale = 0.f;                    // C16 in the one-accumulator form instead: hi + lo of value * c16_scale, lo unscaled (0: the hi + lo'/2048 form)
-    float a16_scale = 0.f;                    // A16 arrives in that form (spline_wide.hip: the fused spline layer and the 512-wide Linear layers)
-    float r16_scale = 0.f;                    // residual16 arrives in that form
+    float a16_scale = 0.f;                    // A16 arrives in that form (EPI_SPLINE only: the fused spline layer of spline_wide.hip)
     // EPI_AFFINE (W pair-packed [s 32 | t 32] x pairs): in-place y2 = x2*s + t on xbuf, logprob[row] += sum log s
     // EPI_AUGMENT (W pair-packed [mu 32 | logsigma 32]): z2 = mu + eps*sigma scattered into xbuf, logprob += -log N(z2)
     float* xbuf = nullptr; int ldx = 0;
@@ -175,7 +172,6 @@ struct GemmEpi {
     const float* eps = nullptr; int d_in = 0, d1 = 0, d1_pad = 0;   // AUGMENT: latent index = d_in + q ; x1|x2 split
     float clamp = 0.f;         // AUGMENT/SLICE: std clamp (0 = none)
     int inverse = 0;           // AFFINE: x2 = (y2 - t) / (s*g), no log-det ; AUGMENT: sample only (no log-det)
-    int prefetch_dist = 0;     // SPLINE (persistent kernel): != 0 rotates each tile's k loop by a column-tile dependent offset (launch_gemm fills it from spline_prefetch, knob 21)
     int split = 1 << 30, split_pad = 0;   // AFFINE: transformed dim j lives at column x2_col0 + (j < split ? j : split_pad + j - split)
     const float* post_scale = nullptr;    // AFFINE: optional per-dim factor g folded behind s (CIF: ActNorm of the x part)
     const float* val = nullptr; int ldval = 0;             // SLICE: values whose log N(.; mu, sigma) is ADDED to logprob
@@ -290,11 +286,9 @@ void launch_mlp_rows(const PackedLinear& in, const std::vector<PackedLinear>& mi
 void launch_limb_decode(const unsigned short* img, float* out, int ldo, int rows, int width, hipStream_t s);   // row-major limb image -> fp32 (tests)
 // spline_wide.hip: the fused spline parameter layer on 256 x 256 tiles with one accumulator per output (K = 8 bins, limb-chained input)
 bool spline_wide_eligible(const PackedLinear& L, int K_bins);
-void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool permute = true, bool fold = false);
+void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool fold = false);
 void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);
 void one_acc_gemm_debug(const float* x, const float* W, const float* bias, float wmax, float* out, int rows, int N, int K, hipStream_t s);   // fc_debug_one_acc_gemm_f32
-bool linear_wide_eligible(const PackedLinear& L, const GemmEpi& e, int rows_alloc);   // a GELU Linear layer with one-accumulator images in and out
-void launch_linear_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);
 bool gemm_spline_wide_on();      // spline_kernel (knob 13) = 5 (shipped): launch_gemm routes eligible EPI_SPLINE launches there
 // the same 256 x 256 main loop for the wide Linear layers of a TRAINING step (train.hip: the spline parameter layer's forward and its data
 // gradient): the point operand is an fp32 panel, split into limbs after its LDS read; C = (A W^T + bias (+ addend)) (* act'(gradu))

@@ -103,16 +103,7 @@ static bool limb_chain_pair(const PackedLinear& producer, const PackedLinear& co
 }
 
 static int run_mlp_hidden(const fc_flow& f, const PackedMLP& m, const ASeg* in_segs, const float* rowscal, FlowWs& w, int act, hipStream_t s,
-                          unsigned short* last_limbs = nullptr, float last_scale = 0.f, int n_scene = 0) {
-    // round 4: hidden layers of a 512-wide coupling net on the 256 x 256 one-accumulator kernel (spline_wide.hip EPI 1).  The gate is the SCENE's
-    // size (target points per scene), never the batch's: a scene's log-probs must not depend on the batch it sits in, and this arithmetic
-    // (one accumulator, k32 MFMAs) is not the per-layer 128 x 128 / 64 x 64 loops' or the row-resident chain's.
-    const int wk = g_knobs.linear_wide;      // (knob 29)
-    if (last_limbs && f.d.H_pad == 512 && gemm_limb_chain_all_ok() && act == FC_ACT_GELU && (wk == 2 || (wk == 1 && n_scene >= 2048)) && w.P_pad % 256 == 0 && !m.mid.empty()) {
-        bool ok = true;
-        for (const PackedLinear& L : m.mid) ok = ok && L.W1 && !L.w1_permuted && L.N_pad % 256 == 0 && L.K_pad % 64 == 0;
-        if (ok) return run_mlp_hidden_generic(m, in_segs, rowscal, act, w.h, f.d.ldh(), w.P_pad, s, w.P, last_limbs, last_scale, true);
-    }
+                          unsigned short* last_limbs = nullptr, float last_scale = 0.f) {
     // 512-wide coupling nets inside a guard scope: in_layer + hidden layers as ONE row-resident launch (mlprows.hip); the scratch images
     // of its intermediate activations live in the h[] buffers (same 2 KB per row as a 512-wide fp32 panel)
     // (a workgroup owns 128 rows for the whole chain: with fewer workgroups than ~3/4 of the CUs -- C1's 2 x 1024 points are 16 -- the chain
@@ -184,17 +175,12 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
         launch_premlp(in.ptr, in.lda, pre.in_layer, pre.mid, pre.out_layer, at.q, act, w.q, d.I_pad, w.P_pad, w.P, s, w.h[0], (size_t)w.P_pad * ldh, lu, xprev);
     } else {
         if (lu) throw Error(FC_ERR_INVALID, "run_attention: a pending ActNorm + LU pre-layer needs the row-resident pre-attention kernel");
-        // limb chain through the pre-attention MLP into the LayerNorm -> q GEMM (every hidden activation as a limb image, DMA loops)
-        const PackedLinear& pre_last = pre.mid.empty() ? pre.in_layer : pre.mid.back();
-        const bool chain = g_knobs.premlp_chain && at.has_lnq && gemm_lnq_ok() && gemm_limb_chain_all_ok() && w.h16 && !pre.mid.empty() &&
-                           limb_chain_pair(pre_last, at.lnq) && pre_last.N_pad % 128 == 0;
-        const int cur = run_mlp_hidden(f, pre, &in, nullptr, w, act, s, chain ? w.h16 : nullptr);
+        const int cur = run_mlp_hidden(f, pre, &in, nullptr, w, act, s);
         if (at.has_lnq && gemm_lnq_ok()) {
             // out_layer, LayerNorm and the q projection as ONE GEMM (AttnPack::lnq) + a 16 MB finalize pass
             GemmEpi e{};
             e.C = w.q; e.ldc = d.I_pad; e.d2 = d.A_in; e.ldj_part = w.lnss; e.ldj_pitch = (size_t)w.P_pad; e.rows_valid = w.P;
-            if (chain) e.A16 = w.h16;
-            ASeg a{chain ? w.h[0] : w.h[cur], ldh};
+            ASeg a{w.h[cur], ldh};
             launch_gemm(at.lnq, &a, w.P_pad, e, EPI_LNQ, s);
             if (keys.form != AttnKeys::PANELS) {
                 // the attention kernel applies rstd and the bias while it loads its queries
@@ -250,7 +236,7 @@ static void run_coupling(fc_flow& f, const BlockPack& b, FlowWs& w, float* xc, c
                            last_hidden.N_pad % 128 == 0 && !b.net.mid.empty();
     // round 4: the chain's last activation in the one-accumulator form (common.h kOneAccActScale) for the 256 x 256 fused spline kernel (spline_wide.hip)
     const bool wide = chain && gemm_spline_wide_on() && spline_wide_eligible(b.net.out_layer, c.num_bins_spline) && w.P_pad % 256 == 0;
-    const int cur = run_mlp_hidden(f, b.net, segs, rowscal, w, c.nonlinearity, s, (chain || chain_aff) ? w.h16 : nullptr, wide ? kOneAccActScale : 0.f, N);
+    const int cur = run_mlp_hidden(f, b.net, segs, rowscal, w, c.nonlinearity, s, (chain || chain_aff) ? w.h16 : nullptr, wide ? kOneAccActScale : 0.f);
     ASeg a{(chain || chain_aff) ? w.h[0] : w.h[cur], d.ldh()};
     if (c.flow_type == FC_FLOW_AFFINE) {
         GemmEpi e{};

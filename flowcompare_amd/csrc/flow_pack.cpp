@@ -324,7 +324,7 @@ static void build_out_layer(fc_flow& f, const WeightTable& wt, const std::string
             const float* ws = fold && pp < 16 ? w.data + (size_t)(r - pp + (pp < 8 ? 7 : 15)) * hk : nullptr;
             for (int k = 0; k < hk; ++k) wmax = std::max(wmax, std::fabs(ws ? (float)((double)wr[k] - (double)ws[k]) : wr[k]));
         }
-        spline_wide_attach(f.arena, net.out_layer, wmax, nullptr, true, fold);
+        spline_wide_attach(f.arena, net.out_layer, wmax, nullptr, fold);
     }
 }
 

@@ -50,7 +50,6 @@ extern template void launch_cfg<128, 320, 4, 1, EPI_AUGMENT, 3>(const GemmParams
 extern template void launch_cfg<128, 320, 4, 1, EPI_SLICE, 3>(const GemmParams&, hipStream_t);
 extern template void launch_cfg<64, 64, 2, 2, EPI_LINEAR, 9>(const GemmParams&, hipStream_t);
 extern template void launch_cfg<128, 128, 2, 2, EPI_LINEAR, 9>(const GemmParams&, hipStream_t);
-extern template void launch_cfg<128, 128, 2, 2, EPI_LNQ, 9>(const GemmParams&, hipStream_t);
 extern template void launch_cfg<128, 128, 2, 2, EPI_SPLINE, 9>(const GemmParams&, hipStream_t);
 extern template void launch_cfg<64, 64, 2, 1, EPI_AFFINE, 9>(const GemmParams&, hipStream_t);
 extern template void launch_cfg<128, 128, 2, 2, EPI_AFFINE, 9>(const GemmParams&, hipStream_t);
@@ -103,12 +102,7 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
         if (e.Cpre && (!e.C || e.C16)) throw Error(FC_ERR_INVALID, "launch_gemm: a pre-activation output goes with an fp32 C and no limb image");
         if (e.C16 && !(f16 && L.N_pad > 64 && L.N_pad % 16 == 0))
             throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: limb-image output exists on the eight-wave split-fp16 tile only");
-        if (e.a16_scale != 0.f) {                                       // a one-accumulator activation image: the 256 x 256 Linear kernel (spline_wide.hip EPI 1) only
-            if (!(f16 && linear_wide_eligible(L, e, rows_alloc))) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator activation image needs the wide Linear kernel (GELU layer, images in and out, N % 256 == 0)");
-            launch_linear_wide(L, e, rows_alloc, s);
-            return;
-        }
-        if (e.r16_scale != 0.f) throw Error(FC_ERR_INVALID, "launch_gemm: a one-accumulator residual image goes with a one-accumulator A image");
+        if (e.a16_scale != 0.f) throw Error(FC_ERR_INVALID, "launch_gemm: a Linear layer takes no one-accumulator activation image (only the fused spline layer reads that form)");
         if (e.A16) {
             // A arrives as the limb image of the producing layer (limb-chained MLP): the copy-only main loops
             if (!(f16 && L.nseg == 1 && L.N_pad > 64 && L.n_alloc >= round_up(L.N_pad, 128)))
@@ -144,13 +138,10 @@ static void launch_gemm_impl(const PackedLinear& L, const ASeg* segs, int rows_a
         if (!e.C || !e.ldj_part || e.d2 % 64 != 0 || L.N_pad != e.d2 + 64 || e.ldc < 64 || e.ldj_pitch < (size_t)rows_alloc || !L.bias)
             throw Error(FC_ERR_INVALID, "launch_gemm: bad LayerNorm -> q fold arguments");
         p.nbm = rows_alloc / 128;
-        if (e.A16) {
-            if (L.nseg != 1 || L.n_alloc < round_up(L.N_pad, 128)) throw Error(FC_ERR_INVALID, "launch_gemm: a limb-image A operand must be the only segment");
-            launch_cfg<128, 128, 2, 2, EPI_LNQ, 9>(p, s);
-        } else launch_cfg<128, 128, 4, 2, EPI_LNQ, 5>(p, s);
+        if (e.A16) throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: the LayerNorm -> q fold takes an fp32 A panel");
+        launch_cfg<128, 128, 4, 2, EPI_LNQ, 5>(p, s);
     } else if (epi_kind == EPI_SPLINE) {
         const int K = e.spline_K;
-        p.e.prefetch_dist = g_knobs.spline_prefetch;
         if (!split) throw Error(FC_ERR_UNSUPPORTED, "launch_gemm: the fused spline epilogue exists for the split GEMM loops only");
         if (!spline_bins_ok(K) || L.N_pad != spline_ncols(e.d2, K) || !e.xbuf || !e.ldj_part || e.ldj_pitch < (size_t)rows_alloc)
             throw Error(FC_ERR_INVALID, "launch_gemm: bad fused-spline arguments (layout of spline.h, per-tile log-det buffer)");

@@ -6,7 +6,6 @@ namespace fc {
 
 template void launch_cfg<64, 64, 2, 2, EPI_LINEAR, 9>(const GemmParams&, hipStream_t);
 template void launch_cfg<128, 128, 2, 2, EPI_LINEAR, 9>(const GemmParams&, hipStream_t);
-template void launch_cfg<128, 128, 2, 2, EPI_LNQ, 9>(const GemmParams&, hipStream_t);
 template void launch_cfg<128, 128, 2, 2, EPI_SPLINE, 9>(const GemmParams&, hipStream_t);
 template void launch_cfg<64, 64, 2, 1, EPI_AFFINE, 9>(const GemmParams&, hipStream_t);
 template void launch_cfg<128, 128, 2, 2, EPI_AFFINE, 9>(const GemmParams&, hipStream_t);

@@ -77,7 +77,7 @@ __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, floa
         p.stamps[(size_t)t * 16 + 8] = wall_clock64();
     }
     FC_STAMP_AT(t, 0)
-    FC_PDMA(src, (e.prefetch_dist != 0 ? (int)(((unsigned)(bn % 10) * 3u + (unsigned)(bm & 15) * 5u) % (unsigned)p.KT) : 0), 0)
+    FC_PDMA(src, 0, 0)
     bias_dma(bn, 0);
     float spl_x[3], spl_ldj;
     load_x(bm, bn, spl_x, spl_ldj);
@@ -101,30 +101,22 @@ __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, floa
         if (lh == 0) e.ldj_part[(size_t)pbn * e.ldj_pitch + row] = pldj;
     };
 
-    // K rotation (knob 21): the ~10 workgroups of an XCD that share a 128-row panel (same row tile, the column tiles of one column group)
-    // run concurrently and, started together, walk its k steps together: every step's first touch of the panel misses L2 for all of
-    // them at once, and a miss holds back the hits queued behind it in the CU's in-order return path (PMC: 92 % L2 hits, yet the texture
-    // data unit waits on the cache a third of the time and a DMA issued a whole k step earlier still kept its wave waiting).  A tile
-    // therefore starts its k loop at step rot(column tile) and wraps around: the sharers are spread over the panel's k range, each k
-    // step is missed by one of them and hit by the others.  fp32 accumulation order changes with it (not bit-identical to VAR 9).
-    const bool rotate = e.prefetch_dist != 0;
-    auto rot_of = [&](int bm_, int bn_) -> int { return rotate ? (int)(((unsigned)(bn_ % 10) * 3u + (unsigned)(bm_ & 15) * 5u) % (unsigned)KT) : 0; };
     for (;;) {
         const int tn = t + G;
         const bool has_next = tn < ntiles;
         int nbm = 0, nbn = 0;
         if (has_next) xcd_tile(p, tn, nbm, nbn);
         float nx[3] = {0.f, 0.f, 0.f}, nldj = 0.f;
-        int kidx = rot_of(bm, bn);                                          // k step being multiplied; the DMA runs one ahead
         for (int kt = 0; kt < KT; ++kt) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's pieces of this k step (and anything older) have landed
             __builtin_amdgcn_s_barrier();                               // ... everybody's have; everybody is done reading the other stage
-            kidx = kidx + 1 < KT ? kidx + 1 : 0;
-            if (kt + 1 < KT) {
-                FC_PDMA(src, kidx, (st ^ 1))
+            if (kt + 1 < KT) {                                          // the DMA runs one k step ahead
+                // (readfirstlane keeps the step a scalar offset: with a plain kt + 1 hipcc carries the pieces' addresses as per-lane
+                //  induction variables instead -- 256 VGPRs and 3 spilled, against 245 and none)
+                FC_PDMA(src, __builtin_amdgcn_readfirstlane(kt + 1), (st ^ 1))
             } else if (has_next) {                                      // the stream runs on into the next tile
                 src = src_of(nbm, nbn);
-                FC_PDMA(src, rot_of(nbm, nbn), (st ^ 1))
+                FC_PDMA(src, 0, (st ^ 1))
                 bias_dma(nbn, par ^ 1);
                 load_x(nbm, nbn, nx, nldj);
             }

@@ -169,14 +169,15 @@ int fc_op_linear_f32(const float* x, const float* W, const float* bias, const fl
 }
 
 /* in_layer + hidden layers of one reference MLP (models/nets.py:19-30) at hidden width 512 over cat(x0, x1) (+ the rank-1 extra-context
-   term rowscal[row] * net.colvec): the last hidden activation, decoded from the limb image the output GEMM would consume.  use_rows != 0:
-   the row-resident chain kernel (mlprows.hip); 0: one GEMM launch per layer (limb-chained).  Tensors (host fp32): net.in_layer.{weight,bias},
+   term rowscal[row] * net.colvec): the last hidden activation, decoded from the limb image the output GEMM would consume.  use_rows 1:
+   the row-resident chain kernel (mlprows.hip); 0: one GEMM launch per layer (limb-chained); any other value is FC_ERR_INVALID.  Tensors (host fp32): net.in_layer.{weight,bias},
    net.layers.i.{weight,bias}, net.out_layer.weight (shape check only), optional net.colvec [512]. */
 int fc_op_mlp_hidden_f32(const float* x0, int32_t k0, const float* x1, int32_t k1, const float* rowscal, const fc_tensor* tensors, int32_t n_tensors,
                          float* out, int32_t rows, int32_t act, int32_t use_rows, void* stream) {
     FC_API_BEGIN
     using namespace fc;
     if (!x0 || !out || rows < 1 || k0 < 1 || k1 < 0 || (k1 > 0 && !x1)) throw Error(FC_ERR_INVALID, "fc_op_mlp_hidden_f32: bad argument");
+    if (use_rows != 0 && use_rows != 1) throw Error(FC_ERR_INVALID, "fc_op_mlp_hidden_f32: use_rows must be 0 (one GEMM launch per layer) or 1 (the row-resident chain kernel)");
     hipStream_t s = (hipStream_t)stream;
     WeightTable wt(tensors, n_tensors);
     DeviceArena arena;
@@ -210,7 +211,7 @@ int fc_op_mlp_hidden_f32(const float* x0, int32_t k0, const float* x1, int32_t k
     FC_HIP(hipDeviceSynchronize());                       // (the images were built on the null stream)
     run_fp16_guarded((int*)flag.p, s, [&] {
         if (use_rows == 1) launch_mlp_rows(m.in_layer, m.mid, segs, rsp, act, h, (unsigned short*)h16.p, rp, rows, s);
-        else if (run_mlp_hidden_generic(m, segs, rsp, act, h, 512, rp, s, rows, (unsigned short*)h16.p, 0.f, use_rows == 2) != -1)      // (2: hidden layers on the 256 x 256 one-accumulator kernel)
+        else if (run_mlp_hidden_generic(m, segs, rsp, act, h, 512, rp, s, rows, (unsigned short*)h16.p, 0.f) != -1)
             throw Error(FC_ERR_INVALID, "fc_op_mlp_hidden_f32: the limb chain is off");
     });
     launch_limb_decode((const unsigned short*)h16.p, out, 512, rows, 512, s);

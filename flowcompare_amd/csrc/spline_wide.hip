@@ -54,12 +54,7 @@ struct SplineWideParams {
     int col_group;
     float out_scale;             // 1 / (kOneAccActScale * 2^w1_exp)
     int ablate;                  // diagnostic spline_ablate (knob 14): 1 no spline evaluation, 2 main loop only (results invalid)
-    // EPI 1 (a Linear layer of the coupling MLP: bias in the accumulators, residual, exact-erf GELU, output as a limb image)
-    unsigned short* out16;       // [rows][N/16][hi 16 | lo 16] fp16
-    const unsigned short* res16; // residual as a one-accumulator image of the same shape, or null (models/nets.py:27: odd hidden layers)
-    int n16;                     // 16-column blocks per row of out16 / res16
-    float s1, s2;                // output limb split: hi = rn16(v s1), lo = rn16((v s1 - hi) s2): (kOneAccActScale, 1) or (1, 2048)
-    int* ovf;                    // split-fp16 range flag (common.h Fp16Guard)
+    int* ovf;                    // split-fp16 range flag (common.h Fp16Guard; EPI 3)
     // EPI 2 (plain product, fc_debug_one_acc_gemm_f32: the one-accumulator limb form by itself, for the accuracy test)
     float* C; int ldc;
     // EPI 3 (training Linear, csrc/train.hip): the point operand is an fp32 PANEL [rows][lda] that is split into limbs after its LDS read
@@ -70,7 +65,6 @@ struct SplineWideParams {
     float a_scale;
     const float* addend; const float* gradu; int ldgu; int gact;
     int n_cols;                  // columns of C that exist (a multiple of 4; the last 256-column tile may be partly empty)
-    int nt_store;                // C is written with non-temporal stores
 };
 
 // column of the kernel's tile order: row kq = (c >> 2) & 3 of 16-parameter block jb = c >> 4, register r = c & 3 -> slot s = 4 jb + r
@@ -175,15 +169,15 @@ constexpr int SW_LDS = 4 * 32768 + 2 * 1024;      // two stages of (256 point ro
 
 // DMA pieces per LOAD segment of a k step, for the group that fetches the points (waves 0-3: P*) and the weights (waves 4-7: Q*); the
 // lagging group must not issue in its last segment (it waits for its pieces there)
-// EPI 0: the fused spline coupling; EPI 1: a 512-wide Linear layer of the coupling MLP with GELU (same main loop, same one-accumulator
-// arithmetic; the weight image in natural row order)
+// EPI 0: the fused spline coupling; EPI 2: the plain product (debug ABI); EPI 3: a training Linear layer (same main loop, same
+// one-accumulator arithmetic; the weight image in natural row order)
 template <int EPI, int P0, int P1, int P2, int P3, int Q0, int Q1, int Q2, int Q3>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
 void spline_wide_kernel(const SplineWideParams p) {
     // NB: 16-parameter blocks of a wave tile = weight DMA pieces per fetching wave and k step.  8: the 64 x 128 wave tile (every EPI);
     // 7: the folded spline image, a 64 x 112 wave tile (EPI 0 only): 84 instead of 96 MFMAs per wave and k step, 224 weight rows per stage
     constexpr int NB = Q0 + Q1 + Q2;
-    static_assert(P0 + P1 + P2 + P3 == 8 && (NB == 8 || (NB == 7 && EPI == 0)) && Q3 == 0, "eight point pieces and NB weight pieces per wave and k step");
+    static_assert((EPI == 0 || EPI == 2 || EPI == 3) && P0 + P1 + P2 + P3 == 8 && (NB == 8 || (NB == 7 && EPI == 0)) && Q3 == 0, "eight point pieces and NB weight pieces per wave and k step");
     extern __shared__ char smc[];
     typedef __attribute__((address_space(3))) char lds_char;
     typedef const __attribute__((address_space(1))) char glb_char;
@@ -311,7 +305,6 @@ void spline_wide_kernel(const SplineWideParams p) {
     bias_dma(bn, 0);
     float spl_x[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, spl_ldj = 0.f;
     if constexpr (EPI == 0) load_x(bm, bn, spl_x, spl_ldj);
-    float omax = 0.f;
     if constexpr (EPI == 3) row_scale(bm, 2 * grp, 2, csc);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -433,8 +426,7 @@ void spline_wide_kernel(const SplineWideParams p) {
                         }
                         typedef float sw_f4 __attribute__((ext_vector_type(4)));
                         const sw_f4 v4 = {v.x, v.y, v.z, v.w};
-                        if (p.nt_store) __builtin_nontemporal_store(v4, reinterpret_cast<sw_f4*>(p.C + row * p.ldc + col));      // (a GB-sized panel streams out past the L2)
-                        else *reinterpret_cast<sw_f4*>(p.C + row * p.ldc + col) = v4;
+                        *reinterpret_cast<sw_f4*>(p.C + row * p.ldc + col) = v4;
                     }
                 }
             }
@@ -447,77 +439,6 @@ void spline_wide_kernel(const SplineWideParams p) {
 #pragma unroll
                 for (int jb = 0; jb < 8; ++jb)
                     *reinterpret_cast<float4*>(cr + jb * 16) = make_float4(acc[ib][jb][0] * os, acc[ib][jb][1] * os, acc[ib][jb][2] * os, acc[ib][jb][3] * os);
-            }
-        } else
-        if constexpr (EPI == 1) {
-            // ---- Linear + GELU: value = acc os (+ residual), y = gelu(value), stored as the limb image the next layer copies.  A lane holds features
-            // 16 jb + 4 kq + 0..3 of point (ib, l15); one v_permlane16_swap per limb word pairs the rows kq = 2 h, 2 h + 1 so that an even row holds
-            // the hi limbs of features 8 h .. 8 h + 7 of its 16-block and the odd row their lo limbs: ONE 16-byte store per lane and block, 64
-            // contiguous bytes per point (the image's [hi 16 | lo 16] block).  The residual image is read the same way and un-swapped.
-            if (p.ablate != 2) {
-                const float os = p.out_scale, s1 = p.s1, s2 = p.s2, rinv = 1.0f / kOneAccActScale;
-                const size_t rowb = (size_t)p.n16 * 64;
-                const size_t col_off = (size_t)(bn * 16 + grp * 8) * 64 + (kq & 1) * 32 + (kq >> 1) * 16;
-                // the residual words of point block ib + 1 are requested before block ib is evaluated (two register sets): left inside the block
-                // loop every load was waited for where it was issued, ~1 us of exposed latency per block and 32 blocks per tile
-                uint4 rr[2][4];                                   // (half a point block = four 16-column blocks per set: a whole block per set spills)
-                auto res_issue = [&](int hb, uint4 (&r)[4]) {
-                    const char* src = reinterpret_cast<const char*>(p.res16) + (size_t)(bm * 256 + pw * 64 + (hb >> 1) * 16 + l15) * rowb + col_off + (hb & 1) * 256;
-#pragma unroll
-                    for (int jq = 0; jq < 4; ++jq) r[jq] = *reinterpret_cast<const uint4*>(src + jq * 64);
-                };
-                if (p.res16) res_issue(0, rr[0]);
-#pragma unroll
-                for (int hb = 0; hb < 8; ++hb) {
-                    const int ib = hb >> 1;
-                    const size_t off = (size_t)(bm * 256 + pw * 64 + ib * 16 + l15) * rowb + col_off;
-                    if (p.res16 && hb + 1 < 8) res_issue(hb + 1, rr[(hb + 1) & 1]);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int jb = (hb & 1) * 4; jb < (hb & 1) * 4 + 4; ++jb) {
-                        float v[4];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = acc[ib][jb][r] * os;
-                        if (p.res16) {
-                            // even row: {hi f0-3 (own), hi f4-7 (partner's)}, odd row: {lo f0-3 (partner's), lo f4-7 (own)} -> swap back -> own hi / lo words
-                            const uint4 rw = rr[hb & 1][jb & 3];
-                            float h0 = __builtin_bit_cast(float, rw.x), h1 = __builtin_bit_cast(float, rw.y);
-                            float l0 = __builtin_bit_cast(float, rw.z), l1 = __builtin_bit_cast(float, rw.w);
-                            sw_swap16(h0, l0);
-                            sw_swap16(h1, l1);
-                            const unsigned hw[2] = {__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
-                            const unsigned lw[2] = {__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const unsigned short hb = (unsigned short)(hw[r >> 1] >> (16 * (r & 1))), lb = (unsigned short)(lw[r >> 1] >> (16 * (r & 1)));
-                                v[r] += ((float)__builtin_bit_cast(_Float16, hb) + (float)__builtin_bit_cast(_Float16, lb)) * rinv;      // (hi + lo is exact in fp32)
-                            }
-                        }
-                        unsigned hw2[2], lw2[2];
-#pragma unroll
-                        for (int r = 0; r < 4; r += 2) {
-                            const float y0 = fc_gelu(v[r]) * s1, y1 = fc_gelu(v[r + 1]) * s1;
-                            omax = fmaxf(omax, fmaxf(fabsf(y0), fabsf(y1)));
-                            asm volatile("" : "+v"(omax));              // (pins the running maximum here: hipcc otherwise keeps all 128 values for one reduction tree at the end and spills them)
-                            const _Float16 a0 = (_Float16)y0, a1 = (_Float16)y1;
-                            const _Float16 b0 = (_Float16)((y0 - (float)a0) * s2), b1 = (_Float16)((y1 - (float)a1) * s2);
-                            hw2[r >> 1] = (unsigned)__builtin_bit_cast(unsigned short, a0) | ((unsigned)__builtin_bit_cast(unsigned short, a1) << 16);
-                            lw2[r >> 1] = (unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
-                        }
-                        float x0 = __builtin_bit_cast(float, hw2[0]), x1 = __builtin_bit_cast(float, hw2[1]);
-                        float y0 = __builtin_bit_cast(float, lw2[0]), y1 = __builtin_bit_cast(float, lw2[1]);
-                        sw_swap16(x0, y0);
-                        sw_swap16(x1, y1);
-                        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(p.out16) + off + jb * 64) =
-                            make_uint4(__builtin_bit_cast(unsigned, x0), __builtin_bit_cast(unsigned, x1), __builtin_bit_cast(unsigned, y0), __builtin_bit_cast(unsigned, y1));
-                        if (jb & 1) __builtin_amdgcn_sched_barrier(0);            // (left alone the scheduler interleaves all 32 blocks' GELU chains and spills the accumulators)
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(acc[i][j]));
             }
         } else
         if (p.ablate != 2) {
@@ -590,7 +511,6 @@ void spline_wide_kernel(const SplineWideParams p) {
         spl_ldj = nldj;
     }
     if (grp == 0) __builtin_amdgcn_s_barrier();
-    if constexpr (EPI == 1) { if (!(omax < 65504.0f) && p.ovf) atomicOr(p.ovf, 1); }      // (also on a NaN)
     if constexpr (EPI == 3) { if (p.ovf && (bad_row || !(amax < 65504.0f))) atomicOr(p.ovf, 1); }      // (amax: of the scaled values; also on a NaN)
 #undef SW_DMA
 #undef SW_PHASE
@@ -599,15 +519,14 @@ void spline_wide_kernel(const SplineWideParams p) {
 
 // ---------------------------------------------------------------- host side
 bool spline_wide_eligible(const PackedLinear& L, int K_bins) {
-    return K_bins == 8 && L.W1 != nullptr && L.w1_permuted && L.bias1 != nullptr && L.nseg == 1 && L.K_pad % 64 == 0 && L.N_pad % 128 == 0;
+    return K_bins == 8 && L.W1 != nullptr && L.bias1 != nullptr && L.nseg == 1 && L.K_pad % 64 == 0 && L.N_pad % 128 == 0;
 }
 
 // Attaches the kernel's weight image and bias to the packed spline parameter layer (K = 8 bins; W / bias hold spline.h's column order).
 // wmax = max |w| over the rows the image holds (host side, from the checkpoint tensor; fold: over the FOLDED rows, up to twice the tensor's).
-// fold (with permute): the 22-parameter image on 112-column wave tiles (spline_wide_src_col_folded); W / W2 / W3 / bias stay as they are.
-void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool permute, bool fold) {
-    fold = fold && permute;
-    if (!L.W || !L.bias || !L.W2 || L.nseg != 1 || L.K_pad % 64 != 0 || L.N_pad % (permute ? 128 : 256) != 0 || L.n_alloc < L.N_pad) return;
+// fold: the 22-parameter image on 112-column wave tiles (spline_wide_src_col_folded); W / W2 / W3 / bias stay as they are.
+void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStream_t s, bool fold) {
+    if (!L.W || !L.bias || !L.W2 || L.nseg != 1 || L.K_pad % 64 != 0 || L.N_pad % 128 != 0 || L.n_alloc < L.N_pad) return;
     if (!(wmax < 65504.0f)) return;
     int e = 0;
     if (wmax > 0.f) {
@@ -619,9 +538,8 @@ void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStre
     L.W1 = (unsigned short*)arena.alloc_bytes(n * 2 * sizeof(unsigned short));
     L.bias1 = arena.alloc_floats((size_t)rows + (fold ? 32 : 0));      // (the kernel fetches 256 floats per workgroup tile)
     L.w1_exp = e;
-    L.w1_permuted = permute;
     L.w1_folded = fold;
-    spline_wide_image_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(L.W, L.bias, L.N_pad, L.K_pad, ldexpf(1.f, e), kOneAccActScale * ldexpf(1.f, e), L.W1, L.bias1, n, fold ? 2 : permute ? 1 : 0);
+    spline_wide_image_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(L.W, L.bias, L.N_pad, L.K_pad, ldexpf(1.f, e), kOneAccActScale * ldexpf(1.f, e), L.W1, L.bias1, n, fold ? 2 : 1);
     FC_HIP(hipGetLastError());
 }
 
@@ -660,66 +578,6 @@ void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
                              : "void fc::spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>(fc::SplineWideParams)", flops, 0.0, s);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SW_LDS, s, p);
     FC_HIP(hipGetLastError());
-}
-
-}  // namespace fc
-
-namespace fc {
-
-// ---------------------------------------------------------------- EPI 1: a GELU Linear layer of the coupling MLP on the same tile
-// Behind linear_wide (knob 29), off as shipped.  Measured on C2 (16 x 4096, same box, profiles/r04o_*): 133 us per hidden-layer launch = ~75 us of main loop (459 TF-eq at N = 512:
-// profiles/micro/wide_gemm_probe.hip) + ~55 us of epilogue that nothing overlaps (4471 VALU instructions per wave and tile: 128 exact-erf
-// GELUs, limb splits, lane swaps; with one workgroup per CU there is no second tile's main loop to hide them behind), and the in_layer stays
-// on its fp32-A loop (100 us): 30.6 + 11.5 = 42 ms per step against 40.8 ms for the row-resident chain (mlprows.hip), whose epilogue runs
-// in micro-steps under the next block's MFMAs.  The arithmetic also differs from the chain's (one accumulator, k32 MFMAs), so shipping it for
-// large scenes only would make a row's log-prob depend on the size of the scene it sits in (tests/test_gpu_fullsize.py compares rows of a
-// 512-point run with the 16 x 4096 run bit for bit).  Kept behind the knob with its tests; not on the default path.
-
-bool linear_wide_eligible(const PackedLinear& L, const GemmEpi& e, int rows_alloc) {
-    return L.W1 && !L.w1_permuted && L.bias1 && L.nseg == 1 && L.K_pad % 64 == 0 && L.N_pad % 256 == 0 && rows_alloc % 256 == 0 && e.A16 &&
-           e.a16_scale == kOneAccActScale && e.C16 && !e.C && !e.Cpre && !e.gradu && !e.residual && !e.rowscal && e.act == FC_ACT_GELU &&
-           (!e.residual16 || (e.r16_scale == kOneAccActScale && e.ldr16 == L.N_pad)) && (e.c16_scale == 0.f || e.c16_scale == kOneAccActScale);
-}
-
-void launch_linear_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s) {
-    if (!linear_wide_eligible(L, e, rows_alloc)) throw Error(FC_ERR_INVALID, "launch_linear_wide: needs one-accumulator images in and out, GELU, N % 256 == 0, K % 64 == 0, rows % 256 == 0");
-    int* flag = gemm_fp16_flag();
-    if (!flag) throw Error(FC_ERR_INVALID, "launch_linear_wide: needs an open split-fp16 guard scope");
-    SplineWideParams p{};
-    p.A16 = e.A16; p.W1 = L.W1; p.bias1 = L.bias1;
-    p.KT = L.K_pad / 32;
-    p.nbm = rows_alloc / 256;
-    p.nbn = L.N_pad / 256;
-    p.ntile128 = L.N_pad / 128;
-    p.col_group = (p.nbm % 8 == 0) ? p.nbn : 0;      // (a 512-wide layer: both column tiles of a row tile side by side on one XCD)
-    p.out_scale = 1.0f / (kOneAccActScale * ldexpf(1.f, L.w1_exp));
-    p.ablate = g_knobs.spline_ablate == 2 ? 2 : 0;
-    p.out16 = e.C16; p.res16 = e.residual16; p.n16 = L.N_pad / 16;
-    p.s1 = e.c16_scale > 0.f ? e.c16_scale : 1.0f;
-    p.s2 = e.c16_scale > 0.f ? 1.0f : 2048.0f;
-    p.ovf = flag;
-    static PerDeviceOnce attr_once, slots_once;
-    auto kern = spline_wide_kernel<1, 2, 3, 3, 0, 2, 3, 3, 0>;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });
-    const int slots = slots_once.run([](int dev) {
-        int cus = 0;
-        FC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        const int n = cus & ~7;
-        return n < 8 ? 8 : n;
-    });
-    int grid = p.nbm * p.nbn;
-    if (grid > slots) grid = slots;
-    const double flops = 2.0 * (double)(e.rows_valid > 0 ? e.rows_valid : rows_alloc) * (double)(L.n_true ? L.n_true : L.N_pad) * (double)(L.k_true ? L.k_true : L.K_pad);
-    ProfScope ps("void fc::spline_wide_kernel<1, 2, 3, 3, 0, 2, 3, 3, 0>(fc::SplineWideParams)", flops, 0.0, s);
-    static const bool trace = getenv("FC_FLAG_TRACE") != nullptr;
-    int before = 0, after = 0;
-    if (trace) { FC_HIP(hipStreamSynchronize(s)); FC_HIP(hipMemcpy(&before, flag, 4, hipMemcpyDeviceToHost)); }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SW_LDS, s, p);
-    FC_HIP(hipGetLastError());
-    if (trace) {
-        FC_HIP(hipStreamSynchronize(s)); FC_HIP(hipMemcpy(&after, flag, 4, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[flag trace] linear_wide rows %d N %d res %d s1 %g: flag %d -> %d\n", rows_alloc, L.N_pad, e.residual16 != nullptr, p.s1, before, after);
-    }
 }
 
 }  // namespace fc
@@ -789,9 +647,6 @@ void launch_train_wide(const TrainWideArgs& a, hipStream_t s) {
     p.out_scale = a.row_absmax ? ldexpf(1.f, -kTrainWideWExp) : 1.0f / (a.a_scale * ldexpf(1.f, kTrainWideWExp));
     p.C = a.C; p.ldc = a.ldc; p.addend = a.addend; p.gradu = a.gradu; p.ldgu = a.ldgu; p.gact = a.gact; p.n_cols = a.n_cols;
     p.ovf = a.ovf;
-    // train_wide (knob 31) = 3: a C panel of 256 MB or more streams out with non-temporal stores (measured on the C2 training step, same box: 1116 against 1092 ms
-    // with ordinary stores, profiles/r04w_train_*.json -- not shipped)
-    p.nt_store = g_knobs.train_wide == 3 && (size_t)a.rows_pad * a.n_cols * 4 >= ((size_t)256 << 20);
     static PerDeviceOnce attr_once, slots_once;
     auto kern = spline_wide_kernel<3, 4, 4, 0, 0, 2, 3, 3, 0>;
     attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });

@@ -269,8 +269,8 @@ int fc_op_linear_f32(const float* x, const float* W, const float* bias, const fl
 /* The in_layer and hidden layers of one reference MLP (models/nets.py:19-30: act(in_layer(x)); even hidden layer i: keep = x, x = act(W x + b);
  * odd: x = act(keep + W x + b)) at hidden width 512 -- the coupling nets of models/affine_coupling.py:30-46 / models/spline_coupling.py:187-210
  * -- over cat(x0 [rows,k0], x1 [rows,k1]) (+ rowscal[row] * net.colvec, the rank-1 form of an extra-context column).  out [rows,512] = the last
- * hidden activation (what out_layer consumes).  use_rows != 0: the row-resident chain kernel (one launch, csrc/mlprows.hip), 0: one GEMM
- * launch per layer.  tensors are HOST fp32: net.in_layer.{weight,bias}, net.layers.<i>.{weight,bias}, net.out_layer.weight (shape check
+ * hidden activation (what out_layer consumes).  use_rows 1: the row-resident chain kernel (one launch, csrc/mlprows.hip), 0: one GEMM
+ * launch per layer; any other value is FC_ERR_INVALID.  tensors are HOST fp32: net.in_layer.{weight,bias}, net.layers.<i>.{weight,bias}, net.out_layer.weight (shape check
  * only), optional net.colvec [512]; x0 / x1 / rowscal / out are DEVICE pointers (x1, rowscal may be NULL). */
 int fc_op_mlp_hidden_f32(const float* x0, int32_t k0, const float* x1, int32_t k1, const float* rowscal, const fc_tensor* tensors,
                          int32_t n_tensors, float* out, int32_t rows, int32_t act, int32_t use_rows, void* stream);

@@ -30,4 +30,4 @@ for spec in sys.argv[2:] or [""]:
         d = (solo[0] - ref[sc]).abs()
         print(f"knobs {spec or '(shipped)'} scene {sc}: max |solo - batch| {d.max().item():.3e}, rows differing {(d > 0).sum().item()} of {N}, first {(d > 0).nonzero()[:4].flatten().tolist()} fallbacks so far {fb}")
     for k, _ in sets:
-        lib.fc_debug_set(k, {29: 0, 13: 5, 23: 1, 16: 1, 9: 1, 8: 2, 26: 1}[k])
+        lib.fc_debug_set(k, {13: 5, 23: 1, 16: 1, 9: 1, 8: 2, 26: 1}[k])

@@ -1,4 +1,4 @@
-"""The one way a test selects a kernel variant: `with knobs({13: 4, 21: 1}): ...` sets kernel-choice knobs (csrc/knobs.h, by their
+"""The one way a test selects a kernel variant: `with knobs({13: 4, 22: 0}): ...` sets kernel-choice knobs (csrc/knobs.h, by their
 fc_debug_set keys) for the block and puts back what they held before.  No table of defaults lives here or in any test: the shipped
 configuration is csrc/knobs.h, pinned once by tests/test_host.py."""
 import contextlib

@@ -19,13 +19,13 @@ from flowcompare_amd import shard  # noqa: E402
 
 
 class _Args:
-    gpus, config, batch, points, ctx_points, layers, weights, knob, train_steps = 4, "c4_dgcnn_attn_extra_affine", 20, 1024, 1250, None, "conditioned", ["29=1"], 2
+    gpus, config, batch, points, ctx_points, layers, weights, knob, train_steps = 4, "c4_dgcnn_attn_extra_affine", 20, 1024, 1250, None, "conditioned", ["23=2"], 2
 
 
 def test_training_child_command_and_rendezvous():
     cmd = bench.training_child_command(_Args, 2)
     assert cmd[0] == sys.executable and cmd[1].endswith("bench.py") and "--train-child" in cmd
-    for flag, val in (("--gpus", "4"), ("--steps", "2"), ("--config", _Args.config), ("--batch", "20"), ("--points", "1024"), ("--ctx-points", "1250"), ("--knob", "29=1")):
+    for flag, val in (("--gpus", "4"), ("--steps", "2"), ("--config", _Args.config), ("--batch", "20"), ("--points", "1024"), ("--ctx-points", "1250"), ("--knob", "23=2")):
         assert cmd[cmd.index(flag) + 1] == val
     env = bench.training_child_env({"MASTER_PORT": "29500", "MASTER_ADDR": "127.0.0.1", "RANK": "3", "LOCAL_RANK": "3", "WORLD_SIZE": "4", "TORCHELASTIC_USE_AGENT_STORE": "True"})
     assert env["MASTER_PORT"] == "29501" and env["RANK"] == "3" and env["WORLD_SIZE"] == "4"      # same ranks, the next port

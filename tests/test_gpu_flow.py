@@ -261,7 +261,7 @@ def test_every_kernel_variant_in_the_library_agrees_on_the_c2_layer_stack():
             return fa.inner_loop(batch, md, cfg, eps=eps)[1]
 
     _, ref, _ = fa.inner_loop(batch, md, cfg, eps=eps)
-    for name, settings in (("unfused spline", {7: 0}), ("separate pre-attention GEMM launches + LayerNorm -> q fold", {8: 0}), ("separate LayerNorm + q projection", {8: 0, 10: 0}), ("no limb chain", {9: 0}), ("limb chain into the spline GEMM only", {16: 0}), ("limb-chained pre-attention MLP", {8: 0, 19: 1}), ("fp32-input attention", {5: 0}),
+    for name, settings in (("unfused spline", {7: 0}), ("separate pre-attention GEMM launches + LayerNorm -> q fold", {8: 0}), ("separate LayerNorm + q projection", {8: 0, 10: 0}), ("no limb chain", {9: 0}), ("limb chain into the spline GEMM only", {16: 0}), ("fp32-input attention", {5: 0}),
                         ("bf16-limb GEMM", {0: 3}), ("fp32-input MFMA GEMM", {0: 2})):
         lp = run_with(settings)
         err = (lp - ref).abs().max().item()
@@ -271,12 +271,6 @@ def test_every_kernel_variant_in_the_library_agrees_on_the_c2_layer_stack():
     # same MFMAs in the same k order as the per-layer launches and adds bias, residual, GELU and limb split alike: bit-identical
     lp = run_with({23: 2})
     assert torch.equal(lp, ref), "the row-resident chain differs from the per-layer launches"
-    # round 4: the hidden layers on the 256 x 256 one-accumulator Linear kernel (spline_wide.hip EPI 1; measured no faster than the row-resident
-    # chain and not on the default path: forced here) -- another arithmetic than the per-layer loops: fp32 noise, not bit for bit
-    lp = run_with({29: 2})
-    err = (lp - ref).abs().max().item()
-    print(f"hidden layers on the wide one-accumulator kernel: max |log-prob - default path| {err:.2e}")
-    assert err < 5e-4
     lp = run_with({23: 2, 16: 0})
     assert (lp - ref).abs().max().item() < 5e-4
     # round 4: the shipped fused spline layer is the 256 x 256 one-accumulator kernel on 16x16x32 MFMAs (spline_wide.hip, knob 13 = 5): another
@@ -291,10 +285,6 @@ def test_every_kernel_variant_in_the_library_agrees_on_the_c2_layer_stack():
     lp = run_with({13: 2})
     print(f"knob 13 = 2: max |diff| {(lp - ref4).abs().max().item():.3e}")
     assert torch.equal(lp, ref4), "fused spline GEMM variant (knob 13 = 2) differs from the persistent 128x128 loop"
-    lp = run_with({13: 4, 21: 1})                             # rotated k order: another fp32 summation order, same sums
-    err = (lp - ref4).abs().max().item()
-    print(f"persistent fused spline GEMM with rotated k loops: max |log-prob - knob 13 = 4| {err:.2e}")
-    assert err < 5e-4
     lp = run_with({22: 0})                                    # 128x128 tiles also for launches with few tiles (this test: 5 row tiles -> 64x64 tiles by default)
     assert torch.equal(lp, ref), "64x64 tiles for small launches changed the limb-chained GEMMs' results"
 

@@ -82,10 +82,10 @@ def test_library_exports_every_declared_symbol():
 # The shipped configuration and each knob's accepted values, by fc_debug_set key: pinned here and nowhere else outside csrc/knobs.h, the list of
 # record.  key: (shipped default, accepted values -- a tuple, or ("min", n) for every value >= n)
 KNOBS = {0: (5, (2, 3, 5)), 2: (10, ("min", 0)), 5: (1, (0, 1)), 7: (1, (0, 1)), 8: (2, (0, 2)), 9: (1, (0, 1)), 10: (1, (0, 1)), 11: (1, (0, 1)),
-         12: (1, (0, 1)), 13: (5, (2, 4, 5)), 14: (0, (0, 1, 2, 3, 4, 5)), 16: (1, (0, 1)), 19: (0, (0, 1)), 20: (0, (0, 1, 2, 3, 4)), 21: (0, (0, 1)),
-         22: (1, (0, 1)), 23: (1, (0, 1, 2)), 24: (1, (0, 1, 2)), 26: (1, (0, 1)), 28: (-1, ("min", -1)), 29: (0, (0, 1, 2)), 31: (1, (0, 1, 3)),
+         12: (1, (0, 1)), 13: (5, (2, 4, 5)), 14: (0, (0, 1, 2, 3, 4, 5)), 16: (1, (0, 1)), 20: (0, (0, 1, 2, 3, 4)),
+         22: (1, (0, 1)), 23: (1, (0, 1, 2)), 24: (1, (0, 1, 2)), 26: (1, (0, 1)), 28: (-1, ("min", -1)), 31: (1, (0, 1)),
          32: (1, (0, 1)), 33: (1, (0, 1)), 34: (1, (0, 1))}
-RETIRED_KEYS = (3, 15, 17, 27, 30)
+RETIRED_KEYS = (3, 15, 17, 19, 21, 27, 29, 30)
 FC_ERR_INVALID, FC_ERR_UNSUPPORTED = 1, 6
 
 
@@ -131,6 +131,11 @@ def test_debug_knob_table_defaults_accepted_values_and_reset():
                     assert lib.fc_debug_set(key, bad) == FC_ERR_UNSUPPORTED, (key, bad)
                     assert knob_get(key, lib) == v, (key, v, bad)
         assert values() != shipped
+        # the variants removed last: their keys are gone (even the value that used to mean "off"), and train_wide lost its value 3
+        for key in (19, 21, 29):
+            assert lib.fc_debug_set(key, 0) == FC_ERR_INVALID, key
+        assert lib.fc_debug_set(31, 1) == 0
+        assert lib.fc_debug_set(31, 3) == FC_ERR_UNSUPPORTED and knob_get(31, lib) == 1
         probe = ctypes.c_int32(77)
         for key in RETIRED_KEYS + (max(KNOBS) + 1, -1):
             assert lib.fc_debug_set(key, 1) == FC_ERR_INVALID, key

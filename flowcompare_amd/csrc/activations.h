@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fcflow.h"
+#include "device.h"
 
 namespace fc {
 
@@ -74,31 +75,29 @@ __device__ __forceinline__ float limb_join(unsigned hi, unsigned lo) {
     return r;
 }
 // eight values -> one MFMA operand fragment per limb
-typedef _Float16 fc_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned fc_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void limb_split8(const float (&x)[8], fc_f16x8& hi, fc_f16x8& lo) {
-    fc_u32x4 h, l;
+__device__ __forceinline__ void limb_split8(const float (&x)[8], f16x8& hi, f16x8& lo) {
+    u32x4 h, l;
     unsigned a, b;
     limb_split2(x[0], x[1], a, b); h[0] = a; l[0] = b;
     limb_split2(x[2], x[3], a, b); h[1] = a; l[1] = b;
     limb_split2(x[4], x[5], a, b); h[2] = a; l[2] = b;
     limb_split2(x[6], x[7], a, b); h[3] = a; l[3] = b;
-    hi = __builtin_bit_cast(fc_f16x8, h);
-    lo = __builtin_bit_cast(fc_f16x8, l);
+    hi = __builtin_bit_cast(f16x8, h);
+    lo = __builtin_bit_cast(f16x8, l);
 }
-__device__ __forceinline__ void limb_split8_unscaled(const float (&x)[8], fc_f16x8& hi, fc_f16x8& lo) {
-    fc_u32x4 h, l;
+__device__ __forceinline__ void limb_split8_unscaled(const float (&x)[8], f16x8& hi, f16x8& lo) {
+    u32x4 h, l;
     unsigned a, b;
     limb_split2u(x[0], x[1], a, b); h[0] = a; l[0] = b;
     limb_split2u(x[2], x[3], a, b); h[1] = a; l[1] = b;
     limb_split2u(x[4], x[5], a, b); h[2] = a; l[2] = b;
     limb_split2u(x[6], x[7], a, b); h[3] = a; l[3] = b;
-    hi = __builtin_bit_cast(fc_f16x8, h);
-    lo = __builtin_bit_cast(fc_f16x8, l);
+    hi = __builtin_bit_cast(f16x8, h);
+    lo = __builtin_bit_cast(f16x8, l);
 }
 // and back: one fragment per limb -> eight values
-__device__ __forceinline__ void limb_join8(const fc_f16x8& hi, const fc_f16x8& lo, float (&x)[8]) {
-    const fc_u32x4 h = __builtin_bit_cast(fc_u32x4, hi), l = __builtin_bit_cast(fc_u32x4, lo);
+__device__ __forceinline__ void limb_join8(const f16x8& hi, const f16x8& lo, float (&x)[8]) {
+    const u32x4 h = __builtin_bit_cast(u32x4, hi), l = __builtin_bit_cast(u32x4, lo);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { x[2 * i] = limb_join<0>(h[i], l[i]); x[2 * i + 1] = limb_join<1>(h[i], l[i]); }
 }
@@ -111,6 +110,15 @@ __device__ __forceinline__ float act_apply(float v, int act) {
         case FC_ACT_LRELU02: return v > 0.f ? v : 0.2f * v;
         default: return v;
     }
+}
+// the same with the activation known at compile time (the kernels templated on it)
+template <int ACT>
+__device__ __forceinline__ float fc_act(float v) {
+    if constexpr (ACT == FC_ACT_GELU) return fc_gelu(v);
+    else if constexpr (ACT == FC_ACT_RELU) return v > 0.f ? v : 0.f;
+    else if constexpr (ACT == FC_ACT_ELU) return v > 0.f ? v : expm1f(v);
+    else if constexpr (ACT == FC_ACT_LRELU02) return v > 0.f ? v : 0.2f * v;
+    else return v;
 }
 
 // d/dv [v Phi(v)] = Phi(v) + v phi(v) on fc_gelu's machinery: Phi(-|v|) = erfc(u) / 2 from the same fit, phi(v) = exp2(-u^2 log2 e) / sqrt(2 pi)

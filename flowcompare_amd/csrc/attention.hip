@@ -15,11 +15,11 @@
 // No LDS round trip for P, no transposed V image.
 #include "common.h"
 #include "activations.h"
+#include "launch.h"
 #include <cstdio>
 
 namespace fc {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct AttnParams {
     const float* q; int ldq;
@@ -196,8 +196,6 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
 //   * V: B operand wants, per lane (column d), those same 8 keys: two ds_read_b64_tr_b16 (hardware transposing read of a
 //     4-key x 16-column block per 16-lane group) on the row-major V image.  Row pitches: K 4*DH+16 B (conflict-free b128 reads),
 //     V 4*DH+64 B (the 4 rows x 64 B a half-wave's transposed read touches land on 64 distinct banks).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef short v4i16 __attribute__((__vector_size__(4 * sizeof(short))));
 
 struct Attn16Params {
@@ -494,28 +492,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
 template <int DH, int SH = 0>
 static void launch_attn16_dh(const Attn16Params& p, int B, hipStream_t s) {
     constexpr size_t lds = SH ? 2 * 64 * (size_t)(4 * DH) : 2 * 64 * (size_t)(8 * DH + 80);
-    static PerDeviceOnce attr_once;
-    auto kern = attn16_kernel<DH, SH>;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
     char name[64];
     if (SH) snprintf(name, sizeof name, "void fc::attn16_kernel<%d, 1>(fc::Attn16Params)", DH);
     else snprintf(name, sizeof name, "void fc::attn16_kernel<%d>(fc::Attn16Params)", DH);
-    ProfScope ps(name, 4.0 * B * (double)p.N * (double)p.M * DH, 0.0, s);
-    hipLaunchKernelGGL(kern, dim3((p.N + 127) / 128, B), dim3(256), lds, s, p);
-    FC_HIP(hipGetLastError());
+    launch_kernel<attn16_kernel<DH, SH>, (int)lds>(name, 4.0 * B * (double)p.N * (double)p.M * DH, 0.0, dim3((p.N + 127) / 128, B), dim3(256), lds, s, p);
 }
 
 template <int DH>
 static void launch_attn_dh(const AttnParams& p, int B, hipStream_t s) {
     constexpr size_t lds = 2 * 2 * (size_t)(DH > 128 ? 32 : 64) * (DH + 4) * sizeof(float);      // 135 KB at head dim 128, 133 KB at 256 (32-key tiles)
-    static PerDeviceOnce attr_once;
-    auto kern = attn_kernel<DH>;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
     char name[64];
     snprintf(name, sizeof name, "void fc::attn_kernel<%d>(fc::AttnParams)", DH);
-    ProfScope ps(name, 4.0 * B * (double)p.N * (double)p.M * DH, 0.0, s);
-    hipLaunchKernelGGL(kern, dim3((p.N + 127) / 128, B), dim3(256), lds, s, p);
-    FC_HIP(hipGetLastError());
+    launch_kernel<attn_kernel<DH>, (int)lds>(name, 4.0 * B * (double)p.N * (double)p.M * DH, 0.0, dim3((p.N + 127) / 128, B), dim3(256), lds, s, p);
 }
 
 size_t attention_limb_ws_bytes(long kv_rows, int dh_pad) { return dh_pad <= 64 ? (size_t)kv_rows * dh_pad * 8 : 0; }

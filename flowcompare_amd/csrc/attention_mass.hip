@@ -11,6 +11,7 @@
 // and attn_mass_reduce_kernel adds the rows of a scene in ascending workgroup order, so the result is the same bytes on every run.
 // Keys beyond M are masked and never written.
 #include "attention_rows.h"
+#include "launch.h"
 #include <cstdio>
 
 namespace fc {
@@ -76,15 +77,11 @@ __global__ __launch_bounds__(256) void attn_mass_reduce_kernel(const float* __re
 template <int DH, int KF>
 static void launch_attn_mass_dh(const AttnMassParams& p, int B, hipStream_t s) {
     constexpr size_t lds = attn_rows_lds_bytes<DH>(4 * 64);
-    static PerDeviceOnce attr_once;
-    auto kern = attn_mass_kernel<DH, KF>;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
     char name[80];
     snprintf(name, sizeof name, "void fc::attn_mass_kernel<%d, %d>(fc::AttnMassParams)", DH, KF);
     const int nwg = (p.P + 127) / 128;
-    ProfScope ps(name, 4.0 * B * (double)p.P * (double)p.M * DH, 4.0 * B * (double)nwg * (double)p.M, s);      // two passes of Q K^T; the slab bytes
-    hipLaunchKernelGGL(kern, dim3(nwg, B), dim3(256), lds, s, p);
-    FC_HIP(hipGetLastError());
+    launch_kernel<attn_mass_kernel<DH, KF>, (int)lds>(name, 4.0 * B * (double)p.P * (double)p.M * DH, 4.0 * B * (double)nwg * (double)p.M,      // two passes of Q K^T; the slab bytes
+                                                      dim3(nwg, B), dim3(256), lds, s, p);
 }
 
 size_t attention_mass_slab_bytes(int B, int N, int M) { return sizeof(float) * (size_t)B * (size_t)((N + 127) / 128) * (size_t)M; }

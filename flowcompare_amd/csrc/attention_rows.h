@@ -4,10 +4,10 @@
 // probabilities exp2(S - m) * (1 / l) are the same bits in both kernels.
 #pragma once
 #include "common.h"
+#include "device.h"
 
 namespace fc {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct AttnRowParams {
     const float* q; int ldq;

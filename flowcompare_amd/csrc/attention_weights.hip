@@ -18,6 +18,7 @@
 // -inf before the maximum and never stored; the pad rows of the K panel are never read.
 // The operands, the q fragment, the staged tile, the scores and pass 1 live in attention_rows.h, which attention_mass.hip shares.
 #include "attention_rows.h"
+#include "launch.h"
 #include <cstdio>
 
 namespace fc {
@@ -65,14 +66,10 @@ __global__ __launch_bounds__(256) void attn_weights_kernel(const AttnWParams p) 
 template <int DH, int KF>
 static void launch_attnw_dh(const AttnWParams& p, int B, hipStream_t s) {
     constexpr size_t lds = attn_rows_lds_bytes<DH>();      // 67 KB at head dim 128, 100 KB at 256
-    static PerDeviceOnce attr_once;
-    auto kern = attn_weights_kernel<DH, KF>;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
     char name[80];
     snprintf(name, sizeof name, "void fc::attn_weights_kernel<%d, %d>(fc::AttnWParams)", DH, KF);
-    ProfScope ps(name, 4.0 * B * (double)p.P * (double)p.M * DH, 4.0 * B * (double)p.P * (double)p.M, s);      // two passes of Q K^T; the output bytes
-    hipLaunchKernelGGL(kern, dim3((p.P + 127) / 128, B), dim3(256), lds, s, p);
-    FC_HIP(hipGetLastError());
+    launch_kernel<attn_weights_kernel<DH, KF>, (int)lds>(name, 4.0 * B * (double)p.P * (double)p.M * DH, 4.0 * B * (double)p.P * (double)p.M,      // two passes of Q K^T; the output bytes
+                                                         dim3((p.P + 127) / 128, B), dim3(256), lds, s, p);
 }
 
 int attn_rows_params(const char* what, const AttnQuery& qy, const AttnKeys& kv, const AttnProblem& pb, AttnRowParams& p) {

@@ -261,6 +261,7 @@ inline void run_fp16_guarded(int* dev_flag, hipStream_t s, F&& fn, bool deferrab
 void launch_gemm(const PackedLinear& L, const ASeg* segs, int rows_alloc, const GemmEpi& e, int epi_kind, hipStream_t s);
 long gemm_fp16_fallbacks();                                          // gemm_guard.cpp: passes repeated on the bf16 limbs so far
 size_t gemm_read_stamps(unsigned long long* host, size_t max_n);     // gemm_guard.cpp: phase stamps of the last stamped launch (stamps, knob 20)
+unsigned long long* gemm_stamp_buffer(size_t n);                     // gemm_guard.cpp: the buffer of those stamps, grown on demand (every stamping kernel's launcher)
 
 // ---------------------------------------------------------------- other kernels (misc.hip / attention.hip / knn.hip)
 void launch_pack_rows(const float* src, int src_ld, int src_cols, float* dst, int dst_ld, int dst_col0, int dst_cols_zero_to,

@@ -4,17 +4,12 @@
 #include "common.h"
 #include "activations.h"
 #include "spline.h"
+#include "launch.h"
 #include <type_traits>
 #include <cstdio>
 #include <cstdlib>
 
 namespace fc {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 struct GemmParams {
     const float* A[3];
@@ -65,12 +60,10 @@ constexpr size_t gemm_lds_bytes() {
 #define FC_STAMP(K_) FC_STAMP_AT(blockIdx.x, K_)
 
 // Lanes 0..31 of the result receive lanes 32..63 of v (v_permlane32_swap_b32 swaps the upper half of its first operand with the lower
-// half of its second; lanes 32..63 of the result are unspecified).  Inline assembly: this hipcc's __builtin_amdgcn_permlane32_swap
-// hands back its first result for both elements (profiles/micro/permlane32_swap_probe.hip); the s_nops cover the VALU <-> permlane-swap
-// wait states the compiler cannot schedule around an asm block.
+// half of its second; lanes 32..63 of the result are unspecified): device.h swap32.
 __device__ __forceinline__ float upper_to_lower(float v) {
     float a = v, b = 0.f;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
+    swap32(a, b);
     return b;
 }
 
@@ -275,8 +268,6 @@ void gemm_f32_kernel(const GemmParams p) {
         constexpr int ROWB8 = gemm_row_bytes<VAR>(), STAGE8 = gemm_stage_bytes<BM, BN, VAR>();
         static_assert(ROWB8 == 128 && (size_t)NST8 * STAGE8 <= gemm_lds_bytes<BM, BN, EPI, VAR>(), "the swizzle below is built for 128-byte rows; launch_cfg reserves the stages");
         constexpr int PPW = STAGE8 / 1024 / (NT / 64);                       // 1-KB DMA pieces per wave and stage: 8 on the 128 x 128 tile
-        typedef __attribute__((address_space(3))) char lds_char;
-        typedef const __attribute__((address_space(1))) char glb_char;
         char* smc = reinterpret_cast<char*>(smem);
         const int KT = p.KT;                                                // k32 tiles
         const size_t rowbytes = (size_t)KT * 128;
@@ -294,8 +285,7 @@ void gemm_f32_kernel(const GemmParams p) {
 #define FC_DMA8(KT_, ST_)                                                                                          \
         {                                                                                                          \
             _Pragma("unroll") for (int i = 0; i < PPW; ++i)                                                        \
-                __builtin_amdgcn_global_load_lds((glb_char*)(gsrc[i] + (size_t)(KT_) * 128),                       \
-                                                 (lds_char*)(smc + (ST_) * STAGE8 + (wave * PPW + i) * 1024), 16, 0, 0); \
+                lds_dma16(gsrc[i] + (size_t)(KT_) * 128, smc + (ST_) * STAGE8 + (wave * PPW + i) * 1024);          \
         }
         floatx16 corr[TM][TN];
 #pragma unroll
@@ -604,10 +594,7 @@ void gemm_f32_kernel(const GemmParams p) {
                             float v = acc[i][j][r];
                             if constexpr (ACT >= 16) v *= fc_act_grad(gu[i][r], ACT - 16);
                             if constexpr ((FMT & 4) != 0) pbase[rl * e.ldc + cl] = v;
-                            if constexpr (ACT == FC_ACT_GELU) v = fc_gelu(v);
-                            else if constexpr (ACT == FC_ACT_RELU) v = v > 0.f ? v : 0.f;
-                            else if constexpr (ACT == FC_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-                            else if constexpr (ACT == FC_ACT_LRELU02) v = v > 0.f ? v : 0.2f * v;
+                            v = fc_act<ACT>(v);                  // (the 16 + gact codes of the line above: identity)
                             if constexpr (FMT & 1) cbase[rl * e.ldc + cl] = v;
                             if constexpr (FMT & 2) {
                                 // the output ALSO / ONLY as the fp16 limb image a following split-fp16 GEMM copies (its 30 column tiles
@@ -828,14 +815,9 @@ template <>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 void gemm_f32_kernel<128, 128, 4, 1, EPI_SPLINE, 11>(const GemmParams p);
 
-unsigned long long* gemm_stamp_buffer(size_t n);      // gemm_guard.cpp
-
 template <int BM, int BN, int WM, int WN, int EPI, int VAR = 2>
 void launch_cfg(const GemmParams& p, hipStream_t s) {
-    static PerDeviceOnce attr_once;
     constexpr size_t lds = gemm_lds_bytes<BM, BN, EPI, VAR>();
-    auto kern = gemm_f32_kernel<BM, BN, WM, WN, EPI, VAR>;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
     GemmParams q = p;
     q.nbn = (p.N_pad + BN - 1) / BN;
     q.col_group = 0;
@@ -849,7 +831,6 @@ void launch_cfg(const GemmParams& p, hipStream_t s) {
     }
     char name[96];
     snprintf(name, sizeof name, "void fc::gemm_f32_kernel<%d, %d, %d, %d, %d, %d>(fc::GemmParams)", BM, BN, WM, WN, EPI, VAR);
-    ProfScope ps(name, p.e.flops_hint, 0.0, s);
     int grid = q.nbm * q.nbn;
     if constexpr (VAR == 11) {                                          // persistent: two workgroups per CU, a multiple of 8 (XCD order)
         static PerDeviceOnce slots_once;
@@ -861,8 +842,7 @@ void launch_cfg(const GemmParams& p, hipStream_t s) {
         });
         if (grid > slots) grid = slots;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), lds, s, q);
-    FC_HIP(hipGetLastError());
+    launch_kernel<gemm_f32_kernel<BM, BN, WM, WN, EPI, VAR>, (int)lds>(name, p.e.flops_hint, 0.0, dim3(grid), dim3(WM * WN * 64), lds, s, q);
 }
 
 }  // namespace fc

@@ -24,8 +24,6 @@ namespace fc {
 __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, float* smem) {
     constexpr int BM = 128, BN = 128, ROWB = gemm_row_bytes<11>(), STAGE = gemm_stage_bytes<BM, BN, 11>(), PPW = 8;
     static_assert(ROWB == 128 && 2 * (size_t)STAGE + 2 * 128 * sizeof(float) == gemm_lds_bytes<BM, BN, EPI_SPLINE, 11>(), "two stages and the two bias buffers, as launch_cfg reserves them");
-    typedef __attribute__((address_space(3))) char lds_char;
-    typedef const __attribute__((address_space(1))) char glb_char;
     const GemmEpi& e = p.e;
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -53,12 +51,11 @@ __device__ __forceinline__ void spline_gemm_persistent(const GemmParams& p, floa
     {                                                                                                                 \
         const char* src_ = (SRC_) + (size_t)(KT_) * 128;                                                             \
         _Pragma("unroll") for (int i = 0; i < PPW; ++i)                                                              \
-            __builtin_amdgcn_global_load_lds((glb_char*)(src_ + poff[i]), (lds_char*)(smc + (ST_) * STAGE + (wave * PPW + i) * 1024), 16, 0, 0); \
+            lds_dma16(src_ + poff[i], smc + (ST_) * STAGE + (wave * PPW + i) * 1024);                             \
     }
     auto bias_dma = [&](int bn, int par) {                              // 128 floats: waves 0 and 1, 4 bytes per lane
         if (wave < 2)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) float*)(p.bias + bn * BN + wave * 64 + lane),
-                                             (__attribute__((address_space(3))) float*)(biasbuf + par * 128 + wave * 64), 4, 0, 0);
+            lds_dma4(p.bias + bn * BN + wave * 64 + lane, biasbuf + par * 128 + wave * 64);
     };
     auto load_x = [&](int bm, int bn, float (&x)[3], float& ldj) {
         const int row = bm * BM + wave * 32 + li, dim0 = bn * 5;

@@ -13,6 +13,8 @@
 // exceeds 64 entries it is pruned back to k with a 32-step radix select over the two entries each lane holds.
 // Output is the unordered SET of k indices (only max-pooling consumes it).
 #include "common.h"
+#include "device.h"
+#include "launch.h"
 #include <cstdio>
 
 namespace fc {
@@ -171,7 +173,6 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ f, i
 // k (1 + ln(M / k)) per query instead of the ~2x of the lazily pruned LDS set above -- and nothing of it touches LDS.
 // Ranking value as above: pd = fl( fl(2 xi.xj - |xj|^2) - |xi|^2 ), largest first, strict `>` against the k-th best (earlier candidates
 // win ties); norms are summed per half-row and then across the two halves, queries and candidates alike.
-typedef float knn_f16v __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float knn_wave_shr1(float v, float edge) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
@@ -331,7 +332,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (more && t < NPART) gload(blk + 1, t);            // (the next block is complete: cbase < M for both of this block's tiles)
             if (cbase >= M) break;
             const float* brow = cur + (t * 32 + li) * LDC + lh * H;
-            knn_f16v acc;
+            floatx16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
             float cxx = 0.f;
@@ -386,13 +387,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <int CP>
 static void launch_knn_mfma(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm) {
     constexpr size_t lds = (2 * (size_t)KM_TC * (CP + 4) + 256) * sizeof(float);
-    static PerDeviceOnce attr_once;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_mfma_kernel<CP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); return 0; });
     char name[112];
     snprintf(name, sizeof name, "void fc::knn_mfma_kernel<%d>(float const*, int, int, int*, int, int, int, int const*)", CP);
-    ProfScope ps(name, 2.0 * B * (double)M * M * C, 4.0 * B * (double)M * (C + k), s);
-    hipLaunchKernelGGL(knn_mfma_kernel<CP>, dim3((M + 127) / 128, B), dim3(256), lds, s, f, ldf, C, idx, M, m_stride_rows, k, warm);
-    FC_HIP(hipGetLastError());
+    launch_kernel<knn_mfma_kernel<CP>, (int)lds>(name, 2.0 * B * (double)M * M * C, 4.0 * B * (double)M * (C + k), dim3((M + 127) / 128, B), dim3(256), lds, s,
+                                                 f, ldf, C, idx, M, m_stride_rows, k, warm);
 }
 
 // warm: k neighbours per query of the same cloud from another feature space (may alias idx: a workgroup reads its own queries' sets before it
@@ -422,11 +420,8 @@ void launch_knn(const float* f, int ldf, int C, int32_t* idx, int B, int M, int 
     }
     const size_t lds = ((size_t)(64 + 16) * (Cp + 4) + 16 + 16 * KNN_CAP) * sizeof(float) + 16 * KNN_CAP * sizeof(int32_t);
     if (lds > 160 * 1024) throw Error(FC_ERR_UNSUPPORTED, "knn: feature dimension too large for the LDS tile");
-    static PerDeviceOnce attr_once;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); return 0; });
-    ProfScope ps("fc::knn_kernel(float const*, int, int, int*, int, int, int)", 2.0 * B * (double)M * M * C, 4.0 * B * (double)M * (C + k), s);
-    hipLaunchKernelGGL(knn_kernel, dim3((M + 15) / 16, B), dim3(256), lds, s, f, ldf, Cp, idx, M, m_stride_rows, k);
-    FC_HIP(hipGetLastError());
+    launch_kernel<knn_kernel, 160 * 1024>("fc::knn_kernel(float const*, int, int, int*, int, int, int)", 2.0 * B * (double)M * M * C, 4.0 * B * (double)M * (C + k),
+                                          dim3((M + 15) / 16, B), dim3(256), lds, s, f, ldf, Cp, idx, M, m_stride_rows, k);
 }
 
 }  // namespace fc

@@ -1,0 +1,29 @@
+// The one launch sequence of the profiled kernels, for HIP translation units.
+#pragma once
+#include <optional>
+#include <utility>
+
+#include "common.h"
+
+namespace fc {
+
+// Launches Kern under a profile scope named prof_name (the name rocprofv3 prints; null: an unprofiled launch) and checks the launch.
+// MAX_LDS: the most dynamic LDS any launch of Kern asks for; above 64 KB the kernel's limit is raised to it once per device (the template
+// argument gives every kernel its own PerDeviceOnce).
+template <auto Kern>
+PerDeviceOnce& kernel_attr_once() {
+    static PerDeviceOnce once;
+    return once;
+}
+template <auto Kern, int MAX_LDS, class... Args>
+void launch_kernel(const char* prof_name, double flops, double bytes, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args&&... args) {
+    if constexpr (MAX_LDS > 65536) {
+        kernel_attr_once<Kern>().run([](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS)); return 0; });
+    }
+    std::optional<ProfScope> ps;
+    if (prof_name) ps.emplace(prof_name, flops, bytes, s);
+    hipLaunchKernelGGL(Kern, grid, block, lds, s, std::forward<Args>(args)...);
+    FC_HIP(hipGetLastError());
+}
+
+}  // namespace fc

@@ -30,15 +30,11 @@
 #include "common.h"
 #include "activations.h"
 #include "mlprows.h"
+#include "launch.h"
 #include <type_traits>
 #include <cstdio>
 
 namespace fc {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char mr_lds_char;
-typedef const __attribute__((address_space(1))) char mr_glb_char;
 
 constexpr int MR_KSTG = 8;                        // k16 steps per stage
 constexpr int MR_STAGE = MR_KSTG * 2 * 1024;      // bytes per stage: 8 k-steps x [hi | lo'] x 1 KiB fragment
@@ -48,49 +44,32 @@ constexpr int MR_NWAIT = (MR_D - 1) * MR_PPW;     // pieces younger than the sta
 constexpr int MR_BIAS_OFF = MR_R * MR_STAGE;      // [512] floats: the layer's bias, then [512] floats: layer 0's rank-1 extra-context column
 constexpr int MR_LDS = MR_BIAS_OFF + 2 * MR_HID * 4;   // 132 KB
 
-// swaps the upper half of a with the lower half of b (lanes 32..63 of a <-> lanes 0..31 of b); see gemm.hip upper_to_lower for the nops
-// NOT volatile: a volatile asm is a barrier for every memory operation in the scheduler's dependence graph -- the stage's weight-fragment
-// LDS reads (and with them its MFMAs) could not be placed before a swap at the end of the epilogue quarter, which serialised the quarter's
-// VALU work and the stage's MFMAs (first build: 28 % matrix-pipe utilisation)
-__device__ __forceinline__ void mr_swap32(unsigned& a, unsigned& b) {
-    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-}
+// (the lane swaps here are device.h's swap32_free, the flavour the scheduler may move: a stage's weight-fragment LDS reads must be free to pass them)
 __device__ __forceinline__ unsigned mr_pack(_Float16 a, _Float16 b) {
     return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
 }
 __device__ __forceinline__ float mr_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
 __device__ __forceinline__ float mr_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
 
-typedef unsigned mr_u4 __attribute__((ext_vector_type(4)));
-typedef float mr_f4 __attribute__((ext_vector_type(4)));
 // Loads the compiler must not see as loads: beside LDS-DMA traffic hipcc waits vmcnt(0) at the first use of any ordinary global load
 // (and at an LDS read that may alias a DMA'd region), which would drain the weight ring once per block.  The results are only used
 // behind mr_wait_vm / mr_wait_lgkm, which tie the registers to the counted wait (the asm is the data dependence).
-__device__ __forceinline__ mr_u4 mr_gload16(const char* ptr) {
-    mr_u4 r;
+__device__ __forceinline__ u32x4 mr_gload16(const char* ptr) {
+    u32x4 r;
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(ptr) : "memory");
     return r;
 }
 template <int N>
-__device__ __forceinline__ void mr_wait_vm(mr_u4& a, mr_u4& b) {
+__device__ __forceinline__ void mr_wait_vm(u32x4& a, u32x4& b) {
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
 }
-__device__ __forceinline__ mr_f4 mr_lds_read16(unsigned addr) {
-    mr_f4 r;
+__device__ __forceinline__ floatx4 mr_lds_read16(unsigned addr) {
+    floatx4 r;
     asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
     return r;
 }
-__device__ __forceinline__ void mr_wait_lgkm(mr_f4& a, mr_f4& b, mr_f4& c, mr_f4& d) {
+__device__ __forceinline__ void mr_wait_lgkm(floatx4& a, floatx4& b, floatx4& c, floatx4& d) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : : "memory");
-}
-
-template <int ACT>
-__device__ __forceinline__ float mr_act(float v) {
-    if constexpr (ACT == FC_ACT_GELU) return fc_gelu(v);
-    else if constexpr (ACT == FC_ACT_RELU) return v > 0.f ? v : 0.f;
-    else if constexpr (ACT == FC_ACT_ELU) return v > 0.f ? v : expm1f(v);
-    else if constexpr (ACT == FC_ACT_LRELU02) return v > 0.f ? v : 0.2f * v;
-    else return v;
 }
 
 // diagnostic stamps (knob 20) = 4 (profiles/micro/mlp_rows_stamps.py): thread 0 of workgroups 0 and 300 stores the shader clock at six points of every
@@ -125,7 +104,7 @@ void mlp_rows_kernel(const MlpRowsParams p) {
     auto issue_piece = [&](auto i_tag) __attribute__((always_inline)) {
         constexpr int i = decltype(i_tag)::value;
         char* dst = smc + ws_slot * MR_STAGE + (wave * MR_PPW + i) * 1024;
-        __builtin_amdgcn_global_load_lds((mr_glb_char*)(ws_ptr + i * 1024 + lane16), (mr_lds_char*)dst, 16, 0, 0);
+        lds_dma16(ws_ptr + i * 1024 + lane16, dst);
         if constexpr (i == MR_PPW - 1) {
             ws_slot = (ws_slot + 1) % MR_R;
             if (--ws_left > 0) ws_ptr += MR_STAGE;
@@ -137,22 +116,17 @@ void mlp_rows_kernel(const MlpRowsParams p) {
             // (else: the stream has ended; the last stage is re-loaded into slots nobody reads again, so that the counted waits stay uniform)
         }
     };
-    auto issue_stage = [&]() __attribute__((always_inline)) {
-        issue_piece(std::integral_constant<int, 0>{}); issue_piece(std::integral_constant<int, 1>{});
-        issue_piece(std::integral_constant<int, 2>{}); issue_piece(std::integral_constant<int, 3>{});
-    };
-    static_assert(MR_PPW == 4, "issue_stage / the slot table place four DMA pieces per wave and stage");
+    auto issue_stage = [&]() __attribute__((always_inline)) { static_for<MR_PPW>(issue_piece); };
+    static_assert(MR_PPW == 4, "the slot table places four DMA pieces per wave and stage");
     // a layer's bias (and layer 0's extra-context column) live in LDS for the layer: ordinary global loads inside the stream would make
     // hipcc wait vmcnt(0) at their first use and drain the DMA ring with them (scalar loads are not chosen in a kernel that also stores)
     auto stage_bias = [&](int l) __attribute__((always_inline)) {
         const MlpRowsLayer& L = p.L[l];
         if (wave < 2)
-            __builtin_amdgcn_global_load_lds((mr_glb_char*)(reinterpret_cast<const char*>(L.bias) + wave * 1024 + lane * 16),
-                                             (mr_lds_char*)(smc + MR_BIAS_OFF + wave * 1024), 16, 0, 0);
+            lds_dma16(reinterpret_cast<const char*>(L.bias) + wave * 1024 + lane * 16, smc + MR_BIAS_OFF + wave * 1024);
         else if (l == 0) {
             if (p.rowscal && L.colvec)
-                __builtin_amdgcn_global_load_lds((mr_glb_char*)(reinterpret_cast<const char*>(L.colvec) + (wave - 2) * 1024 + lane * 16),
-                                                 (mr_lds_char*)(smc + MR_BIAS_OFF + MR_HID * 4 + (wave - 2) * 1024), 16, 0, 0);
+                lds_dma16(reinterpret_cast<const char*>(L.colvec) + (wave - 2) * 1024 + lane * 16, smc + MR_BIAS_OFF + MR_HID * 4 + (wave - 2) * 1024);
             else
                 *reinterpret_cast<float4*>(smc + MR_BIAS_OFF + MR_HID * 4 + (wave - 2) * 1024 + lane * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
@@ -205,8 +179,8 @@ void mlp_rows_kernel(const MlpRowsParams p) {
 
     // one block of 32 output features over NSB stages; the previous block's accumulators (pa, pc) are finished meanwhile
     floatx16 accA, corrA, accB, corrB;
-    mr_u4 resA_hi, resA_lo, resB_hi, resB_lo;                           // residual fragments of the block being finished: k-steps 2 pb (A), 2 pb + 1 (B)
-    mr_f4 bnext[4], cnext[4];                                           // next block's bias (and layer 0's extra-context column) quads, read a stage ahead
+    u32x4 resA_hi, resA_lo, resB_hi, resB_lo;                           // residual fragments of the block being finished: k-steps 2 pb (A), 2 pb + 1 (B)
+    floatx4 bnext[4], cnext[4];                                           // next block's bias (and layer 0's extra-context column) quads, read a stage ahead
     unsigned outq[4][2][2];                                             // finished quads of the block being finished: [quad][hi | lo'][2 words]
 
     // Control flow inside a block is compile-time only (HAS_RES, the stage count) or branch-free (uniform selects): every runtime branch
@@ -227,7 +201,7 @@ void mlp_rows_kernel(const MlpRowsParams p) {
                              : reinterpret_cast<char*>(p.hbuf[L.out]) + band * band_bytes + lane * 16;
         const int out_ss = last ? 64 : 2048, out_ls = last ? 32 : 1024;
         const float rs = (FIRST && p.rowscal && L.colvec) ? p.rowscal[row_in] : 0.f;     // (without the term the column in LDS is zero)
-        const unsigned bias_lds = (unsigned)(uintptr_t)(mr_lds_char*)smc + (unsigned)(MR_BIAS_OFF + 16 * lh);      // LDS byte address of this lane half's first bias quad
+        const unsigned bias_lds = (unsigned)(uintptr_t)(lds_char*)smc + (unsigned)(MR_BIAS_OFF + 16 * lh);      // LDS byte address of this lane half's first bias quad
 
         // bias quads of block nb -> bnext (cnext): issued a stage before the block starts, waited for in init_acc
         auto bias_fetch = [&](int nb) __attribute__((always_inline)) {
@@ -273,8 +247,8 @@ void mlp_rows_kernel(const MlpRowsParams p) {
                     float v = fmaf(pc[4 * g + t], 1.0f / 2048.0f, pa[4 * g + t]);      // (= pa + pc / 2048 rounded once: the scaling is exact)
                     if constexpr (HAS_RES) {
                         // residual quad in accumulator order (after the reverse lane swap done when the fragment arrived)
-                        const mr_u4& rh = g < 2 ? resA_hi : resB_hi;
-                        const mr_u4& rl = g < 2 ? resA_lo : resB_lo;
+                        const u32x4& rh = g < 2 ? resA_hi : resB_hi;
+                        const u32x4& rl = g < 2 ? resA_lo : resB_lo;
                         const unsigned hw = (g & 1) ? (pr == 0 ? rh.z : rh.w) : (pr == 0 ? rh.x : rh.y);
                         const unsigned lw = (g & 1) ? (pr == 0 ? rl.z : rl.w) : (pr == 0 ? rl.x : rl.y);
                         v += tt ? limb_join<1>(hw, lw) : limb_join<0>(hw, lw);             // (one v_fma_mix_f32, activations.h)
@@ -329,43 +303,37 @@ void mlp_rows_kernel(const MlpRowsParams p) {
 #undef MR_PIN
         };
         auto quarter = [&](const floatx16& pa, const floatx16& pc, auto g_tag) __attribute__((always_inline)) {      // (a whole quarter at once: the layer's last block)
-            auto go = [&](auto... ms) __attribute__((always_inline)) { (epi_step(pa, pc, g_tag, ms), ...); };
-            go(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{},
-               std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{}, std::integral_constant<int, 6>{}, std::integral_constant<int, 7>{},
-               std::integral_constant<int, 8>{}, std::integral_constant<int, 9>{}, std::integral_constant<int, 10>{}, std::integral_constant<int, 11>{},
-               std::integral_constant<int, 12>{}, std::integral_constant<int, 13>{}, std::integral_constant<int, 14>{}, std::integral_constant<int, 15>{},
-               std::integral_constant<int, 16>{}, std::integral_constant<int, 17>{}, std::integral_constant<int, 18>{}, std::integral_constant<int, 19>{},
-               std::integral_constant<int, 20>{}, std::integral_constant<int, 21>{}, std::integral_constant<int, 22>{}, std::integral_constant<int, 23>{});
+            static_for<24>([&](auto m_tag) __attribute__((always_inline)) { epi_step(pa, pc, g_tag, m_tag); });
         };
         // quads 2 h, 2 h + 1 of block fb are k-step 2 fb + h of the next layer's input: accumulator order -> fragment order (one lane-half swap per
-        // register pair), then two 16-byte stores.  Inline asm: runs at a stage's START, outside the stage's scheduling region (see mr_swap32)
+        // register pair), then two 16-byte stores.  Inline asm: runs at a stage's START, outside the stage's scheduling region (see swap32_free)
         auto flush_pair = [&](int fb, auto h_tag) __attribute__((always_inline)) {
             constexpr int h = decltype(h_tag)::value, g = 2 * h + 1;
 #pragma unroll
             for (int limb = 0; limb < 2; ++limb) {
-                mr_swap32(outq[g - 1][limb][0], outq[g][limb][0]);
-                mr_swap32(outq[g - 1][limb][1], outq[g][limb][1]);
+                swap32_free(outq[g - 1][limb][0], outq[g][limb][0]);
+                swap32_free(outq[g - 1][limb][1], outq[g][limb][1]);
                 const uint4 frag = make_uint4(outq[g - 1][limb][0], outq[g - 1][limb][1], outq[g][limb][0], outq[g][limb][1]);
                 *reinterpret_cast<uint4*>(outbase + (2 * fb + h) * out_ss + limb * out_ls) = frag;
             }
         };
         auto flush_limb = [&](int fb, auto h_tag, auto limb_tag) __attribute__((always_inline)) {
             constexpr int h = decltype(h_tag)::value, g = 2 * h + 1, limb = decltype(limb_tag)::value;
-            mr_swap32(outq[g - 1][limb][0], outq[g][limb][0]);
-            mr_swap32(outq[g - 1][limb][1], outq[g][limb][1]);
+            swap32_free(outq[g - 1][limb][0], outq[g][limb][0]);
+            swap32_free(outq[g - 1][limb][1], outq[g][limb][1]);
             const uint4 frag = make_uint4(outq[g - 1][limb][0], outq[g - 1][limb][1], outq[g][limb][0], outq[g][limb][1]);
             *reinterpret_cast<uint4*>(outbase + (2 * fb + h) * out_ss + limb * out_ls) = frag;
         };
         // residual fragments of block rb, half h (k-step 2 rb + h): issue the loads; finish (wait + reverse swap) before use
-        auto res_load = [&](int rb, int h, mr_u4& rh, mr_u4& rl) __attribute__((always_inline)) {
+        auto res_load = [&](int rb, int h, u32x4& rh, u32x4& rl) __attribute__((always_inline)) {
             const char* src = resbase + (size_t)((2 * rb + h) * 2) * 1024;
             rh = mr_gload16(src);
             rl = mr_gload16(src + 1024);
         };
-        auto res_fix = [&](mr_u4& rh, mr_u4& rl) __attribute__((always_inline)) {
+        auto res_fix = [&](u32x4& rh, u32x4& rl) __attribute__((always_inline)) {
             unsigned a0 = rh.x, a1 = rh.y, a2 = rh.z, a3 = rh.w, b0 = rl.x, b1 = rl.y, b2 = rl.z, b3 = rl.w;
-            mr_swap32(a0, a2); mr_swap32(a1, a3);
-            mr_swap32(b0, b2); mr_swap32(b1, b3);
+            swap32_free(a0, a2); swap32_free(a1, a3);
+            swap32_free(b0, b2); swap32_free(b1, b3);
             rh.x = a0; rh.y = a1; rh.z = a2; rh.w = a3; rl.x = b0; rl.y = b1; rl.z = b2; rl.w = b3;
         };
 
@@ -441,15 +409,10 @@ void mlp_rows_kernel(const MlpRowsParams p) {
                     corr = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[cur], xin[sx][1], corr, 0, 0, 0);          // hi * lo'
                     slot(std::integral_constant<int, 3 * j + 2>{});
                 };
-                kstep(std::integral_constant<int, 0>{}); kstep(std::integral_constant<int, 1>{}); kstep(std::integral_constant<int, 2>{});
-                kstep(std::integral_constant<int, 3>{}); kstep(std::integral_constant<int, 4>{}); kstep(std::integral_constant<int, 5>{});
-                kstep(std::integral_constant<int, 6>{}); kstep(std::integral_constant<int, 7>{});
+                static_for<MR_KSTG>(kstep);
                 MR_STAMP(5)
             };
-            stage(std::integral_constant<int, 0>{});
-            stage(std::integral_constant<int, 1>{});
-            if constexpr (NSB > 2) stage(std::integral_constant<int, 2>{});
-            if constexpr (NSB > 3) stage(std::integral_constant<int, 3>{});
+            static_for<NSB>(stage);
         };
 
 #pragma unroll
@@ -547,18 +510,11 @@ void launch_limb_decode(const unsigned short* img, float* out, int ldo, int rows
     FC_HIP(hipGetLastError());
 }
 
-unsigned long long* gemm_stamp_buffer(size_t n);
-
 template <int KS0, int ACT, bool STAMPS = false>
 static void mr_launch(const MlpRowsParams& p, int rows_alloc, double flops, hipStream_t s) {
-    auto kern = mlp_rows_kernel<KS0, ACT, STAMPS>;
-    static PerDeviceOnce attr_once;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, MR_LDS)); return 0; });
     char name[96];
     snprintf(name, sizeof name, "void fc::mlp_rows_kernel<%d, %d, %s>(fc::MlpRowsParams)", KS0, ACT, STAMPS ? "true" : "false");      // (the name rocprofv3 prints)
-    ProfScope ps(name, flops, 0.0, s);
-    hipLaunchKernelGGL(kern, dim3(rows_alloc / 128), dim3(256), MR_LDS, s, p);
-    FC_HIP(hipGetLastError());
+    launch_kernel<mlp_rows_kernel<KS0, ACT, STAMPS>, MR_LDS>(name, flops, 0.0, dim3(rows_alloc / 128), dim3(256), MR_LDS, s, p);
 }
 
 bool mlp_rows_fills_the_chip(int rows_alloc) {

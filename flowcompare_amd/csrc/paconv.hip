@@ -11,6 +11,7 @@
 //   three_nn_interp_kernel .../interpolation/interpolation_cuda_kernel.cu:134-195 + PointNet2FPModule.forward
 //                         (model/pointnet2/pointnet2_paconv_modules.py:224-236): 3-NN, inverse-distance weights, interpolation, skip concat
 #include "common.h"
+#include "launch.h"
 
 namespace fc {
 
@@ -101,20 +102,14 @@ size_t fps_scratch_floats(int B, int n) { return n > 8192 ? (size_t)B * n : 0; }
 void launch_fps(const float* xyz, int ld, int32_t* idx, int B, int n, int m, float* scratch, hipStream_t s) {
     if (m <= 0) return;
     if (m > n) throw Error(FC_ERR_INVALID, "furthest point sampling: m > n");
-    ProfScope ps("fc::fps_kernel", 0.0, 4.0 * B * (3.0 * n + m), s);
+    const double bytes = 4.0 * B * (3.0 * n + m);
     if (n > 8192) {
         if (!scratch) throw Error(FC_ERR_WORKSPACE, "furthest point sampling: more than 8192 points per scene need the [B][n] min-distance scratch (fps_scratch_floats)");
-        hipLaunchKernelGGL(fps_kernel<true>, dim3(B), dim3(1024), 0, s, xyz, ld, idx, n, m, opt_n_threads_host(n), scratch);
+        launch_kernel<fps_kernel<true>, 0>("fc::fps_kernel", 0.0, bytes, dim3(B), dim3(1024), 0, s, xyz, ld, idx, n, m, opt_n_threads_host(n), scratch);
     } else {
-        const size_t lds = (size_t)n * 4 * sizeof(float);
-        static bool attr_done = false;
-        if (!attr_done) {
-            FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fps_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
-            attr_done = true;
-        }
-        hipLaunchKernelGGL(fps_kernel<false>, dim3(B), dim3(1024), lds, s, xyz, ld, idx, n, m, opt_n_threads_host(n), (float*)nullptr);
+        launch_kernel<fps_kernel<false>, 8192 * 16>("fc::fps_kernel", 0.0, bytes, dim3(B), dim3(1024), (size_t)n * 4 * sizeof(float), s, xyz, ld, idx, n, m,
+                                                    opt_n_threads_host(n), (float*)nullptr);
     }
-    FC_HIP(hipGetLastError());
 }
 
 // dst[b, j, 0:3] = src[b, idx[b, j], 0:3] ; dst pitch 4 (last component 0)

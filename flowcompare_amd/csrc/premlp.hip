@@ -8,18 +8,13 @@
 // Removes per layer: 4 activation round trips through HBM (67 MB written + read each), the LayerNorm pass, 5 launches.
 // Shapes: hidden width = attention input width = 256 exactly, q width 64, input width a multiple of 32 up to 256
 // (the engine falls back to the separate kernels otherwise, and always on the bf16-limb range-fallback pass).
-#include <type_traits>
+#include <cstdio>
 
 #include "common.h"
-#include <cstdio>
 #include "activations.h"
+#include "launch.h"
 
 namespace fc {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-typedef __attribute__((address_space(3))) char pm_lds_char;
-typedef const __attribute__((address_space(1))) char pm_glb_char;
 
 struct PreMlpLayer {
     const unsigned short* W2;   // [n_alloc][K_pad/16][2][16]
@@ -29,9 +24,7 @@ struct PreMlpLayer {
 struct PreMlpParams {
     const float* x; int ldx;            // input rows (first in_k columns)
     PreMlpLayer in, mid0, mid1, out, q; // q: LN-folded projection 256 -> 64
-    int act;
     float* qout; int ldq;
-    int rows;                           // rows allocated (multiple of 64)
     unsigned long long* stamps;         // diagnostic stamps (knob 20) = 3: 16 x u64 per workgroup (s_memtime at the layer boundaries; wall clock in 14 / 15)
     float* keep_ws;                     // row-resident kernel: rows x 256 floats of scratch (the second hidden layer's residual, parked as limb fragments)
     int* ovf;
@@ -60,16 +53,10 @@ constexpr int PM_H = 256;                                  // hidden width = att
 //   stage is 4x as long per barrier.
 constexpr int PR_ROWS = 128, PR_NT = 512, PR_CH = 32;
 constexpr int PR_BUF = PR_CH * PM_H * 4;                    // 32 KB: one chunk of 32 weight rows at K = 256
-constexpr int PR_BIAS_OFF = 2 * PR_BUF;                     // [5][256] floats: in, mid0, mid1, out, q
-constexpr int PR_LDS = PR_BIAS_OFF + 5 * PM_H * 4;
-// with the ActNorm + LU pre-layer (NLU chunks of 32 outputs, K = 32 NLU): a chunk is 32 rows x 32 NLU x 4 B, its bias follows the five others
+// LDS: two weight stages, then the biases [5][256] floats (in, mid0, mid1, out, q).  With the ActNorm + LU pre-layer (NLU chunks of 32 outputs,
+// K = 32 NLU) a chunk is 32 rows x 32 NLU x 4 B and its bias follows the five others
 constexpr int pr_buf(int nlu) { return nlu * 32 > PM_H ? PR_CH * nlu * 32 * 4 : PR_BUF; }
 constexpr int pr_lds(int nlu) { return 2 * pr_buf(nlu) + 5 * PM_H * 4 + nlu * 32 * 4; }
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-// rows of 16 lanes (a0,a1,a2,a3 | b0,b1,b2,b3):  swap32 -> a = (a0,a1,b0,b1), b = (a2,a3,b2,b3) ;  swap16 -> a = (a0,b0,a2,b2), b = (a1,b1,a3,b3)
-__device__ __forceinline__ void pr_swap32(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void pr_swap16(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b)); }
 
 // DMA of chunk c (weight rows 32 c .. 32 c + 31, all K) of layer L into `dst`: 1 KiB pieces dealt round-robin to FOUR of the eight waves --
 // waves 0..3 for even chunks of the stream, 4..7 for odd ones.  Waves w and w + 4 share a SIMD, and issuing a piece stalls its wave
@@ -80,6 +67,8 @@ __device__ __forceinline__ void pr_swap16(float& a, float& b) { asm volatile("s_
 // multiply-adds, a division and ~10 more instructions per piece -- about half of the ~190 cycles a piece holds its wave, and the issuing wave's
 // pieces are on the chunk's critical path.  With the row length known a 256-wide row is one piece (lane l reads chunk l ^ (pc & 15) of row pc:
 // one 64-bit add per piece on precomputed lane offsets), and for the other lengths the division is a multiply + shift in 32 bits.
+// The CPRH == 64 arm is NOT redundant with the general compile-time arm below it: without it premlp_rows_kernel<1, 5, 10> goes from 244 to
+// 256 VGPRs and its whole instruction stream changes.
 template <int CPRH>
 __device__ __forceinline__ void pr_dma(const PreMlpLayer& L, int c, char* dst, int wave, int lane, int grp) {
     if ((wave >> 2) != grp) return;
@@ -89,7 +78,7 @@ __device__ __forceinline__ void pr_dma(const PreMlpLayer& L, int c, char* dst, i
         const unsigned l0 = (unsigned)(lane ^ first) << 4;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            __builtin_amdgcn_global_load_lds((pm_glb_char*)(ubase + j * 4096 + (l0 ^ (unsigned)((j & 3) << 6))), (pm_lds_char*)(dst + (first + 4 * j) * 1024), 16, 0, 0);
+            lds_dma16(ubase + j * 4096 + (l0 ^ (unsigned)((j & 3) << 6)), dst + (first + 4 * j) * 1024);
         return;
     } else if constexpr (CPRH > 0) {
         constexpr int SW = (CPRH & 15) == 0 ? 15 : 7, NP = CPRH / 2;
@@ -99,7 +88,7 @@ __device__ __forceinline__ void pr_dma(const PreMlpLayer& L, int c, char* dst, i
         for (int j = 0; j < NP / 4; ++j) {
             const int pc = first + 4 * j;
             const unsigned ci = (unsigned)(pc * 64 + lane), r = ci / CPRH, q = ci - r * CPRH;
-            __builtin_amdgcn_global_load_lds((pm_glb_char*)(ubase + (r * CPRH + (q ^ (r & SW))) * 16u), (pm_lds_char*)(dst + pc * 1024), 16, 0, 0);
+            lds_dma16(ubase + (r * CPRH + (q ^ (r & SW))) * 16u, dst + pc * 1024);
         }
         return;
     }
@@ -111,7 +100,7 @@ __device__ __forceinline__ void pr_dma(const PreMlpLayer& L, int c, char* dst, i
         const int ci = pc * 64 + lane;
         const int r = cpr == 64 ? ci >> 6 : ci / cpr;
         const int q = ci - r * cpr;
-        __builtin_amdgcn_global_load_lds((pm_glb_char*)(base + ((size_t)r * cpr + (q ^ (r & sw))) * 16), (pm_lds_char*)(dst + pc * 1024), 16, 0, 0);
+        lds_dma16(base + ((size_t)r * cpr + (q ^ (r & sw))) * 16, dst + pc * 1024);
     }
 }
 
@@ -199,6 +188,30 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     PR_STAMP(1)
 
     int buf = 0;                                             // stage that holds (is receiving) the chunk about to be multiplied
+    // The 3 x 2 x KS MFMAs of the chunk in stage `buf` against the operand fragments xh / xl, for a row length known at compile time (K = 32 KS:
+    // the 256-wide layers, the in_layer at K_pad 160, the pre-layer at 320): bases + compile-time offsets, see pr_off3 / pr_off4
+    auto mma_static = [&](auto ks_tag, const f16x8* xh, const f16x8* xl, floatx4 (&am)[2], floatx4 (&ac)[2]) __attribute__((always_inline)) {
+        constexpr int KS = decltype(ks_tag)::value, CPR = KS * 8;    // 16-byte chunks per weight row
+        constexpr bool SW4 = (CPR & 15) == 0;
+        const char* wb = smc + buf * PRB + n * (CPR * 16);
+        const int o = SW4 ? pr_off4 : pr_off3;
+        const char* bh0 = wb + o;
+        const char* bl0 = wb + (o ^ 32);
+        const char* bh1 = wb + (SW4 ? (o ^ 128) : o + 128);          // odd k steps
+        const char* bl1 = wb + (SW4 ? (o ^ 160) : (o ^ 32) + 128);
+#pragma unroll
+        for (int s_ = 0; s_ < KS; ++s_) {
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) {
+                const int imm = 256 * (s_ >> 1) + mb * 16 * CPR * 16;
+                const f16x8 wh = *reinterpret_cast<const f16x8*>(((s_ & 1) ? bh1 : bh0) + imm);
+                const f16x8 wl = *reinterpret_cast<const f16x8*>(((s_ & 1) ? bl1 : bl0) + imm);
+                am[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[s_], am[mb], 0, 0, 0);
+                ac[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[s_], ac[mb], 0, 0, 0);
+                ac[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[s_], ac[mb], 0, 0, 0);
+            }
+        }
+    };
     // MFMAs of one chunk: (am, ac) = W[32 c .. 32 c + 31][:] . act  (main / cross-product accumulators of the two 16-feature blocks)
     auto chunk_mma = [&](const PreMlpLayer& L, const PreMlpLayer* nextL, int nextc, auto fullk_tag, floatx4 (&am)[2], floatx4 (&ac)[2], auto&& after_dma) __attribute__((always_inline)) {
         constexpr int KSTAT = decltype(fullk_tag)::value;             // compile-time k steps (8 for the 256-wide layers): the k loop is ONE basic block; 0 = run time
@@ -214,37 +227,18 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         }
         grp ^= 1;
         after_dma();                                                    // (loads that must not sit in front of the wait above: they get this chunk's time to land)
-        if constexpr (KSTAT > 0) {
-            // compile-time row length (K = 32 KSTAT: launch_premlp instantiates KSIN = 5 for K_pad 160 only, the other layers are 256 wide)
-            constexpr int CPR = KSTAT * 8;
-            constexpr bool SW4 = (CPR & 15) == 0;
-            const char* wb = smc + buf * PRB + n * (CPR * 16);
-            const int o = SW4 ? pr_off4 : pr_off3;
-            const char* bh0 = wb + o;
-            const char* bl0 = wb + (o ^ 32);
-            const char* bh1 = wb + (SW4 ? (o ^ 128) : o + 128);          // odd k steps
-            const char* bl1 = wb + (SW4 ? (o ^ 160) : (o ^ 32) + 128);
-#pragma unroll
-            for (int s_ = 0; s_ < KSTAT; ++s_) {
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) {
-                    const int imm = 256 * (s_ >> 1) + mb * 16 * CPR * 16;
-                    const f16x8 wh = *reinterpret_cast<const f16x8*>(((s_ & 1) ? bh1 : bh0) + imm);
-                    const f16x8 wl = *reinterpret_cast<const f16x8*>(((s_ & 1) ? bl1 : bl0) + imm);
-                    am[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ah[s_], am[mb], 0, 0, 0);
-                    ac[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, ah[s_], ac[mb], 0, 0, 0);
-                    ac[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, al[s_], ac[mb], 0, 0, 0);
-                }
-            }
+        if constexpr (KSTAT > 0) {                                      // (launch_premlp instantiates KSIN = 5 for K_pad 160 only, the other layers are 256 wide)
+            mma_static(fullk_tag, ah, al, am, ac);
             buf ^= 1;
             return;
         }
+        // row length read from the layer (the KSIN = 0 instantiations: an in_layer of any width up to 256)
         const int cpr = L.K_pad >> 2, KS = L.K_pad >> 5;
         const int sw = (cpr & 15) == 0 ? n : (n & 7);
         const char* wrow = smc + buf * PRB + n * cpr * 16;
 #pragma unroll
         for (int s_ = 0; s_ < 8; ++s_) {
-            if (KSTAT ? s_ < KSTAT : s_ < KS) {
+            if (s_ < KS) {
                 const int ch = 4 * (2 * s_ + (kg >> 1)) + (kg & 1);      // 16-byte chunk of this lane's 8 k values (hi limb; lo' = + 2)
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb) {
@@ -296,10 +290,7 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         for (int e = 0; e < 8; ++e) {
             float x = t[e] + bs[e];
             if constexpr (RESID) x += res[e];
-            if constexpr (A == FC_ACT_GELU) x = fc_gelu(x);
-            else if constexpr (A == FC_ACT_RELU) x = x > 0.f ? x : 0.f;
-            else if constexpr (A == FC_ACT_ELU) x = x > 0.f ? x : expm1f(x);
-            else if constexpr (A == FC_ACT_LRELU02) x = x > 0.f ? x : 0.2f * x;
+            x = fc_act<A>(x);
             amax = fmaxf(amax, fabsf(x));
             xv[e] = x;
         }
@@ -362,26 +353,7 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             if (c + 1 < NLU) pr_dma<NLU * 8>(p.lu, c + 1, smc + (buf ^ 1) * PRB, wave, lane, grp);
             else pr_dma<KSIN * 8>(p.in, 0, smc + (buf ^ 1) * PRB, wave, lane, grp);
             grp ^= 1;
-            constexpr int cpr = NLU * 8;                                    // 16-byte chunks per weight row
-            constexpr bool SW4 = (cpr & 15) == 0;
-            const char* wb = smc + buf * PRB + n * (cpr * 16);              // (bases + compile-time offsets: see pr_off3 / pr_off4)
-            const int o = SW4 ? pr_off4 : pr_off3;
-            const char* bh0 = wb + o;
-            const char* bl0 = wb + (o ^ 32);
-            const char* bh1 = wb + (SW4 ? (o ^ 128) : o + 128);
-            const char* bl1 = wb + (SW4 ? (o ^ 160) : (o ^ 32) + 128);
-#pragma unroll
-            for (int s_ = 0; s_ < NLU; ++s_) {
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) {
-                    const int imm = 256 * (s_ >> 1) + mb * 16 * cpr * 16;
-                    const f16x8 wh = *reinterpret_cast<const f16x8*>(((s_ & 1) ? bh1 : bh0) + imm);
-                    const f16x8 wl = *reinterpret_cast<const f16x8*>(((s_ & 1) ? bl1 : bl0) + imm);
-                    am[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, uh[s_], am[mb], 0, 0, 0);
-                    ac[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, uh[s_], ac[mb], 0, 0, 0);
-                    ac[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ul[s_], ac[mb], 0, 0, 0);
-                }
-            }
+            mma_static(std::integral_constant<int, NLU>{}, uh, ul, am, ac);
             buf ^= 1;
         };
         auto lu_finish = [&](const float (&t)[8], int c) __attribute__((always_inline)) {       // chunk c >= 0 (wave-uniform)
@@ -471,6 +443,8 @@ __global__ __launch_bounds__(PR_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 
     PR_STAMP(6)
     // ---- q projection 256 -> 64: two chunks; the lane stores 8 consecutive columns of its row
+    //      (bias add + store as in lu_finish, each its own statement sequence: one shared helper moved the kernel-argument loads and changed the
+    //      register allocation of every instantiation from the LayerNorm on)
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         floatx4 am[2], ac[2];
@@ -509,13 +483,18 @@ bool premlp_rows_ok(int rows_alloc, int ldq, const float* qout, const float* kee
            keep_floats >= (size_t)rows_alloc * PM_H;
 }
 
-unsigned long long* gemm_stamp_buffer(size_t n);      // gemm.hip: the buffer of the diagnostic stamps (knob 20), grown on demand, read back by fc_debug_gemm_stamps
-
 // true when `lu` (the previous flow layer's folded ActNorm + permuter, latent pitch ldx) can run as the pre-layer of this pre-conditioner's
 // row-resident kernel: square 320 x 320 in the latent's padded layout, the in_layer reading its first 160 columns, GELU (the instantiated case)
 bool premlp_lu_fusable(const PackedLinear& lu, const PackedLinear& in, int act, int ldx) {
     return g_knobs.premlp_lu && act == FC_ACT_GELU && lu.W2 != nullptr && lu.bias != nullptr && lu.nseg == 1 && lu.K_pad == 320 && lu.N_pad == 320 && ldx == 320 &&
            lu.n_alloc >= 320 && in.K_pad == 160;
+}
+
+template <int ACT, int KSIN, int NLU>
+static void premlp_rows_launch(const PreMlpParams& p, int rows_alloc, double flops, hipStream_t s) {
+    char name[96];
+    snprintf(name, sizeof name, "void fc::premlp_rows_kernel<%d, %d, %d>(fc::PreMlpParams)", ACT, KSIN, NLU);      // (the name rocprofv3 prints: profiles/pmc_traffic.json is keyed by it)
+    launch_kernel<premlp_rows_kernel<ACT, KSIN, NLU>, pr_lds(NLU)>(name, flops, 0.0, dim3(rows_alloc / PR_ROWS), dim3(PR_NT), pr_lds(NLU), s, p);
 }
 
 void launch_premlp(const float* x, int ldx, const PackedLinear& in, const std::vector<PackedLinear>& mid, const PackedLinear& out,
@@ -527,7 +506,7 @@ void launch_premlp(const float* x, int ldx, const PackedLinear& in, const std::v
     p.x = x; p.ldx = ldx;
     auto L = [](const PackedLinear& l) { return PreMlpLayer{l.W2, l.bias, l.K_pad}; };
     p.in = L(in); p.mid0 = L(mid[0]); p.mid1 = L(mid[1]); p.out = L(out); p.q = L(q);
-    p.act = act; p.qout = qout; p.ldq = ldq; p.rows = rows_alloc; p.ovf = gemm_fp16_flag(); p.keep_ws = keep_ws;
+    p.qout = qout; p.ldq = ldq; p.ovf = gemm_fp16_flag(); p.keep_ws = keep_ws;
     p.stamps = g_knobs.stamps == 3 ? gemm_stamp_buffer((size_t)(rows_alloc / PR_ROWS) * 16) : nullptr;
     const double rv = rows_valid > 0 ? rows_valid : rows_alloc;
     double flops = 2.0 * rv * ((double)in.k_true * PM_H + 3.0 * PM_H * PM_H + (double)PM_H * (q.n_true ? q.n_true : 64));
@@ -538,31 +517,17 @@ void launch_premlp(const float* x, int ldx, const PackedLinear& in, const std::v
                 throw Error(FC_ERR_INVALID, "launch_premlp: the ActNorm + LU pre-layer does not fit the row-resident kernel (callers check premlp_lu_fusable)");
             p.lu = L(*lu); p.xprev = xprev; p.ldxp = ldx; p.xnext = const_cast<float*>(x); p.ldxn = ldx;
             flops += 2.0 * rv * (double)(lu->k_true ? lu->k_true : lu->K_pad) * (double)(lu->n_true ? lu->n_true : lu->N_pad);
-            auto kern = premlp_rows_kernel<FC_ACT_GELU, 5, 10>;
-            static PerDeviceOnce attr_once;
-            attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, pr_lds(10))); return 0; });
-            ProfScope ps("void fc::premlp_rows_kernel<1, 5, 10>(fc::PreMlpParams)", flops, 0.0, s);      // (the name rocprofv3 prints: profiles/pmc_traffic.json is keyed by it)
-            hipLaunchKernelGGL(kern, dim3(rows_alloc / PR_ROWS), dim3(PR_NT), pr_lds(10), s, p);
-            FC_HIP(hipGetLastError());
+            premlp_rows_launch<FC_ACT_GELU, 5, 10>(p, rows_alloc, flops, s);
             return;
         }
-        auto go = [&](auto kern, int act_code, int ksin) {
-            static PerDeviceOnce attr_once;                             // (one per kernel instantiation: `go` is a generic lambda)
-            attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PR_LDS)); return 0; });
-            char name[96];
-            snprintf(name, sizeof name, "void fc::premlp_rows_kernel<%d, %d, 0>(fc::PreMlpParams)", act_code, ksin);      // (the name rocprofv3 prints)
-            ProfScope ps(name, flops, 0.0, s);
-            hipLaunchKernelGGL(kern, dim3(rows_alloc / PR_ROWS), dim3(PR_NT), PR_LDS, s, p);
-            FC_HIP(hipGetLastError());
-        };
         const bool k5 = in.K_pad == 160;                                // latent 300: x1 = 150 columns (the shipped configurations)
-        switch (act) {
-            case FC_ACT_GELU: k5 ? go(premlp_rows_kernel<FC_ACT_GELU, 5>, FC_ACT_GELU, 5) : go(premlp_rows_kernel<FC_ACT_GELU, 0>, FC_ACT_GELU, 0); break;
-            case FC_ACT_RELU: k5 ? go(premlp_rows_kernel<FC_ACT_RELU, 5>, FC_ACT_RELU, 5) : go(premlp_rows_kernel<FC_ACT_RELU, 0>, FC_ACT_RELU, 0); break;
-            case FC_ACT_ELU: k5 ? go(premlp_rows_kernel<FC_ACT_ELU, 5>, FC_ACT_ELU, 5) : go(premlp_rows_kernel<FC_ACT_ELU, 0>, FC_ACT_ELU, 0); break;
-            case FC_ACT_LRELU02: k5 ? go(premlp_rows_kernel<FC_ACT_LRELU02, 5>, FC_ACT_LRELU02, 5) : go(premlp_rows_kernel<FC_ACT_LRELU02, 0>, FC_ACT_LRELU02, 0); break;
-            default: k5 ? go(premlp_rows_kernel<FC_ACT_NONE, 5>, FC_ACT_NONE, 5) : go(premlp_rows_kernel<FC_ACT_NONE, 0>, FC_ACT_NONE, 0); break;
-        }
+        const int code = act > FC_ACT_NONE && act <= FC_ACT_LRELU02 ? act : FC_ACT_NONE;
+        static_for<FC_ACT_LRELU02 + 1>([&](auto act_tag) {              // the activation codes FC_ACT_NONE .. FC_ACT_LRELU02
+            constexpr int A = decltype(act_tag)::value;
+            if (A != code) return;
+            if (k5) premlp_rows_launch<A, 5, 0>(p, rows_alloc, flops, s);
+            else premlp_rows_launch<A, 0, 0>(p, rows_alloc, flops, s);
+        });
         return;
     }
     if (lu) throw Error(FC_ERR_INVALID, "launch_premlp: the ActNorm + LU pre-layer exists in the row-resident kernel only");

@@ -6,6 +6,7 @@
 //   * farthest point sampling of every voxel's rows, voxels of different sizes in one launch, one workgroup per voxel, with the
 //     distance arithmetic of fps_nd_kernel (fps_dist.h).
 #include "common.h"
+#include "launch.h"
 #include "fps_dist.h"
 
 #include <algorithm>
@@ -236,15 +237,8 @@ void launch_fps_ragged(const float* cloud, int ld, int C, long P, const int64_t*
         throw Error(FC_ERR_WORKSPACE, "ragged fps: voxels above 24576 rows need a float scratch as long as the row list");
     const long want = (long)max_rows * (C + 1);
     const int lds_floats = want <= kFpsLdsFloats ? (int)want : kFpsLdsFloats;          // >= min(max_rows, 24576) either way
-    static bool attr_done = false;
-    if (!attr_done) {
-        FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fps_ragged_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kFpsLdsFloats * 4));
-        attr_done = true;
-    }
-    ProfScope ps("fc::fps_ragged_kernel", 0.0, 4.0 * n_voxels * ((double)max_rows * (C + 1) + 2.0 * m), s);
-    hipLaunchKernelGGL(fps_ragged_kernel, dim3(n_voxels), dim3(1024), (size_t)lds_floats * sizeof(float), s, cloud, ld, C, (int)P, offsets, rows, voxel_ids,
-                       idx, m, lds_floats, dist_scratch);
-    FC_HIP(hipGetLastError());
+    launch_kernel<fps_ragged_kernel, kFpsLdsFloats * 4>("fc::fps_ragged_kernel", 0.0, 4.0 * n_voxels * ((double)max_rows * (C + 1) + 2.0 * m), dim3(n_voxels), dim3(1024),
+                                                        (size_t)lds_floats * sizeof(float), s, cloud, ld, C, (int)P, offsets, rows, voxel_ids, idx, m, lds_floats, dist_scratch);
 }
 
 // ---------------------------------------------------------------- dense blocks: ALL members of the staged voxels

@@ -34,13 +34,11 @@
 #include "common.h"
 #include "activations.h"
 #include "spline.h"
+#include "launch.h"
 #include <cstdio>
 #include <cstdlib>
 
 namespace fc {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct SplineWideParams {
     const unsigned short* A16;   // [rows][KT][64] fp16: the activation image, one-accumulator form (pre-scaled by kOneAccActScale, lo unscaled)
@@ -125,15 +123,12 @@ __global__ __launch_bounds__(256) void spline_wide_image_kernel(const float* __r
     if (k == 0 && bias1) bias1[row] = bv * bscale;
 }
 
-// rows of 16 lanes (a0,a1,a2,a3 | b0,b1,b2,b3):  swap32 -> a = (a0,a1,b0,b1), b = (a2,a3,b2,b3) ;  swap16 -> a = (a0,b0,a2,b2), b = (a1,b1,a3,b3)
-__device__ __forceinline__ void sw_swap32(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void sw_swap16(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b)); }
 // sum over the four rows of 16 lanes, result in every row (fixed order: (r0 + r1) + (r2 + r3))
 __device__ __forceinline__ float sw_row_sum(float v) {
     float a = v, b = v;
-    sw_swap16(a, b);
+    swap16(a, b);
     float c = a + b, d = c;
-    sw_swap32(c, d);
+    swap32(c, d);
     return c + d;
 }
 
@@ -153,7 +148,6 @@ __device__ __forceinline__ void sw_split2v(sw_f32x2 x, sw_f32x2 sv, unsigned& hi
     asm volatile("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(t[0]), "v"(t[1]));      // (volatile: pins the running maximum; left to hipcc the raw values of a k step are kept for one reduction tree and spill)
 }
 __device__ __forceinline__ void sw_split8(const float4& r0, const float4& r1, float sv, f16x8& hi, f16x8& lo, float& amax) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 h, l;
     unsigned a, b;
     const sw_f32x2 s2 = {sv, sv};
@@ -179,8 +173,6 @@ void spline_wide_kernel(const SplineWideParams p) {
     constexpr int NB = Q0 + Q1 + Q2;
     static_assert((EPI == 0 || EPI == 2 || EPI == 3) && P0 + P1 + P2 + P3 == 8 && (NB == 8 || (NB == 7 && EPI == 0)) && Q3 == 0, "eight point pieces and NB weight pieces per wave and k step");
     extern __shared__ char smc[];
-    typedef __attribute__((address_space(3))) char lds_char;
-    typedef const __attribute__((address_space(1))) char glb_char;
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, pw = wave & 3;
@@ -227,13 +219,11 @@ void spline_wide_kernel(const SplineWideParams p) {
 #define SW_DMA(SRC_, ST_, I0_, N_)                                                                                                      \
     {                                                                                                                                     \
         _Pragma("unroll") for (int i_ = (I0_); i_ < (I0_) + (N_); ++i_)                                                                 \
-            __builtin_amdgcn_global_load_lds((glb_char*)((SRC_) + (size_t)(i_ >> 1) * 16 * rowbytes + poff[i_ & 1]),                      \
-                                             (lds_char*)(smc + dst0 + (ST_) * 32768 + i_ * 1024), 16, 0, 0);                            \
+            lds_dma16((SRC_) + (size_t)(i_ >> 1) * 16 * rowbytes + poff[i_ & 1], smc + dst0 + (ST_) * 32768 + i_ * 1024);               \
     }
     auto bias_dma = [&](int bn, int par) {                              // 256 floats: waves 0-3, 4 bytes per lane (NB = 7: 224 in use; bias1 is padded by 32)
         if (grp == 0 && (EPI != 3 || p.bias1))
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) float*)(p.bias1 + bn * (32 * NB) + pw * 64 + lane),
-                                             (__attribute__((address_space(3))) float*)(biasbuf + par * 256 + pw * 64), 4, 0, 0);
+            lds_dma4(p.bias1 + bn * (32 * NB) + pw * 64 + lane, biasbuf + par * 256 + pw * 64);
     };
     // a k32 step is ONE k extent of the 16x16x32 MFMA: lane (l15, kq) supplies row l15 of a 16-row block, k quarter kq = chunks 0, 1, 4, 5 of
     // the hi limb / 2, 3, 6, 7 of the lo limb
@@ -424,9 +414,8 @@ void spline_wide_kernel(const SplineWideParams p) {
                             const float4 u = *reinterpret_cast<const float4*>(p.gradu + row * p.ldgu + col);
                             v.x *= fc_gelu_grad(u.x); v.y *= fc_gelu_grad(u.y); v.z *= fc_gelu_grad(u.z); v.w *= fc_gelu_grad(u.w);      // (GELU only: launch_train_wide checks)
                         }
-                        typedef float sw_f4 __attribute__((ext_vector_type(4)));
-                        const sw_f4 v4 = {v.x, v.y, v.z, v.w};
-                        *reinterpret_cast<sw_f4*>(p.C + row * p.ldc + col) = v4;
+                        const floatx4 v4 = {v.x, v.y, v.z, v.w};
+                        *reinterpret_cast<floatx4*>(p.C + row * p.ldc + col) = v4;
                     }
                 }
             }
@@ -451,10 +440,10 @@ void spline_wide_kernel(const SplineWideParams p) {
 #pragma unroll
             for (int s = S4; s < 4 * NB; ++s) {
                 float x0 = acc[0][s >> 2][s & 3], x1 = acc[1][s >> 2][s & 3], x2 = acc[2][s >> 2][s & 3], x3 = acc[3][s >> 2][s & 3];
-                sw_swap16(x0, x1);
-                sw_swap16(x2, x3);
-                sw_swap32(x0, x2);
-                sw_swap32(x1, x3);
+                swap16(x0, x1);
+                swap16(x2, x3);
+                swap32(x0, x2);
+                swap32(x1, x3);
                 acc[0][s >> 2][s & 3] = x0; acc[1][s >> 2][s & 3] = x1; acc[2][s >> 2][s & 3] = x2; acc[3][s >> 2][s & 3] = x3;
             }
             float yv[5], lv[5];
@@ -561,10 +550,6 @@ void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
     const int cg = g_knobs.spline_wide_colgroup;      // (knob 28)
     if (cg >= 0) p.col_group = (p.nbm % 8 == 0 && p.nbn > cg) ? cg : 0;
     static PerDeviceOnce slots_once;
-    // (the weight pieces of the folded form: 2 + 3 + 2 per k step)
-    auto kern = L.w1_folded ? spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 2, 0> : spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>;
-    static PerDeviceOnce attr_once[2];
-    attr_once[L.w1_folded ? 1 : 0].run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });
     const int slots = slots_once.run([](int dev) {
         int cus = 0;
         FC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -574,10 +559,12 @@ void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc,
     int grid = p.nbm * p.nbn;
     if (grid > slots) grid = slots;
     const double flops = 2.0 * (double)(e.rows_valid > 0 ? e.rows_valid : rows_alloc) * (double)(L.n_true ? L.n_true : L.N_pad) * (double)(L.k_true ? L.k_true : L.K_pad);
-    ProfScope ps(L.w1_folded ? "void fc::spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 2, 0>(fc::SplineWideParams)"
-                             : "void fc::spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>(fc::SplineWideParams)", flops, 0.0, s);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SW_LDS, s, p);
-    FC_HIP(hipGetLastError());
+    if (L.w1_folded)      // (the weight pieces of the folded form: 2 + 3 + 2 per k step)
+        launch_kernel<spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 2, 0>, SW_LDS>("void fc::spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 2, 0>(fc::SplineWideParams)", flops, 0.0,
+                                                                             dim3(grid), dim3(512), SW_LDS, s, p);
+    else
+        launch_kernel<spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>, SW_LDS>("void fc::spline_wide_kernel<0, 2, 3, 3, 0, 2, 3, 3, 0>(fc::SplineWideParams)", flops, 0.0,
+                                                                             dim3(grid), dim3(512), SW_LDS, s, p);
 }
 
 }  // namespace fc
@@ -609,17 +596,13 @@ void one_acc_gemm_debug(const float* x, const float* W, const float* bias, float
     p.col_group = (p.nbm % 8 == 0 && p.nbn > 5) ? 5 : 0;
     p.out_scale = 1.0f / (kOneAccActScale * ldexpf(1.f, e));
     p.C = cp.f(); p.ldc = N;
-    static PerDeviceOnce attr_once;
-    auto kern = spline_wide_kernel<2, 2, 3, 3, 0, 2, 3, 3, 0>;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });
     int cus = 0, dev = 0;
     FC_HIP(hipGetDevice(&dev));
     FC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     int grid = p.nbm * p.nbn;
     const int slots = (cus & ~7) < 8 ? 8 : (cus & ~7);
     if (grid > slots) grid = slots;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SW_LDS, s, p);
-    FC_HIP(hipGetLastError());
+    launch_kernel<spline_wide_kernel<2, 2, 3, 3, 0, 2, 3, 3, 0>, SW_LDS>(nullptr, 0.0, 0.0, dim3(grid), dim3(512), SW_LDS, s, p);      // (debug entry: not profiled)
     FC_HIP(hipMemcpyAsync(out, cp.f(), (size_t)rows * N * 4, hipMemcpyDeviceToDevice, s));
     FC_HIP(hipStreamSynchronize(s));
 }
@@ -647,9 +630,7 @@ void launch_train_wide(const TrainWideArgs& a, hipStream_t s) {
     p.out_scale = a.row_absmax ? ldexpf(1.f, -kTrainWideWExp) : 1.0f / (a.a_scale * ldexpf(1.f, kTrainWideWExp));
     p.C = a.C; p.ldc = a.ldc; p.addend = a.addend; p.gradu = a.gradu; p.ldgu = a.ldgu; p.gact = a.gact; p.n_cols = a.n_cols;
     p.ovf = a.ovf;
-    static PerDeviceOnce attr_once, slots_once;
-    auto kern = spline_wide_kernel<3, 4, 4, 0, 0, 2, 3, 3, 0>;
-    attr_once.run([&](int) { FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS)); return 0; });
+    static PerDeviceOnce slots_once;
     const int slots = slots_once.run([](int dev) {
         int cus = 0;
         FC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -658,9 +639,8 @@ void launch_train_wide(const TrainWideArgs& a, hipStream_t s) {
     });
     int grid = p.nbm * p.nbn;
     if (grid > slots) grid = slots;
-    ProfScope ps("void fc::spline_wide_kernel<3, 4, 4, 0, 0, 2, 3, 3, 0>(fc::SplineWideParams)", a.flops, 0.0, s);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SW_LDS, s, p);
-    FC_HIP(hipGetLastError());
+    launch_kernel<spline_wide_kernel<3, 4, 4, 0, 0, 2, 3, 3, 0>, SW_LDS>("void fc::spline_wide_kernel<3, 4, 4, 0, 0, 2, 3, 3, 0>(fc::SplineWideParams)", a.flops, 0.0,
+                                                                         dim3(grid), dim3(512), SW_LDS, s, p);
 }
 
 }  // namespace fc

@@ -4,6 +4,7 @@
 //   * change-map post-processing (test_flow.py:241-275): clamp_infs, per-scene mean/std threshold, min-max scaling.
 // Small streaming / reduction kernels: one workgroup per scene, LDS tree reductions in a fixed order (bit-reproducible).
 #include "common.h"
+#include "launch.h"
 #include "fps_dist.h"
 
 #include <cfloat>
@@ -66,19 +67,13 @@ void launch_fps_nd(const float* pts, int ld, int C, int64_t* idx, int B, int n, 
     if (m <= 0) return;
     if (C < 1 || C > 8 || ld < C) throw Error(FC_ERR_UNSUPPORTED, "fps: 1..8 feature columns supported");
     if (m > n) throw Error(FC_ERR_INVALID, "fps: more samples than points");
-    ProfScope ps("fc::fps_nd_kernel", 0.0, 4.0 * B * ((double)n * C + m), s);
+    const double bytes = 4.0 * B * ((double)n * C + m);
     if (n <= 24576) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fps_nd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 24576 * 4));
-            attr_done = true;
-        }
-        hipLaunchKernelGGL(fps_nd_kernel<true>, dim3(B), dim3(1024), (size_t)n * sizeof(float), s, pts, ld, C, idx, n, m, nullptr);
+        launch_kernel<fps_nd_kernel<true>, 24576 * 4>("fc::fps_nd_kernel", 0.0, bytes, dim3(B), dim3(1024), (size_t)n * sizeof(float), s, pts, ld, C, idx, n, m, nullptr);
     } else {
         if (!dist_scratch) throw Error(FC_ERR_WORKSPACE, "fps: clouds above 24576 points need a [B*n] float scratch");
-        hipLaunchKernelGGL(fps_nd_kernel<false>, dim3(B), dim3(1024), 0, s, pts, ld, C, idx, n, m, dist_scratch);
+        launch_kernel<fps_nd_kernel<false>, 0>("fc::fps_nd_kernel", 0.0, bytes, dim3(B), dim3(1024), 0, s, pts, ld, C, idx, n, m, dist_scratch);
     }
-    FC_HIP(hipGetLastError());
 }
 
 // ---------------------------------------------------------------- block reductions (fixed order: reproducible run to run)

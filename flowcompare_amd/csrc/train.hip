@@ -170,7 +170,6 @@ __global__ void act_bwd_kernel(const float4* __restrict__ dy, const float4* __re
 // Both operands are row-major with the contraction index p as the slow one, which is exactly the operand order of
 // v_mfma_f32_32x32x2_f32 (lane l supplies A[m = l % 32][k = l / 32] and B[k = l / 32][n = l % 32]): 32 consecutive floats of one row
 // per half-wave, no transposition anywhere.  Workgroup = 4 waves, tile 128 (n) x 128 (k), each wave 64 x 64; grid.y splits the rows.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int WG_PS = 16;                  // rows per staged slab
 constexpr int WG_LD = 128 + 4;             // LDS pitch in floats
@@ -188,7 +187,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ du
     // staging: thread t moves 2 float4 per operand per slab: rows (t / 32) and (t / 32) + 8, columns 4 (t % 32) ...
     const int lr = tid >> 5, lc = (tid & 31) * 4;
     const bool a_ok = n0 + lc < du_cols, b_ok = k0 + lc < x_cols;
-    f32x16 acc[2][2];
+    floatx16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -260,8 +259,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ du
 // read the forward attention uses for P.V: a 16-lane group reads a [4 rows][16 columns] block and lane i receives column i.  Each
 // lane's k-group therefore holds rows {4h .. 4h+3, 8+4h .. 8+4h+3} of the 16-row step -- the same permutation for both operands, so
 // the contraction is unchanged.  3 MFMAs (v_mfma_f32_32x32x16_f16) per block and step: hi.hi into `main`, hi.lo' + lo'.hi into `cross`.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 
 constexpr int W16_ROWS = 32;               // rows per staged slab (two MFMA k-steps)
@@ -269,7 +266,6 @@ constexpr int W16_PITCH = 512 + 64;        // bytes per LDS row: [hi 128 halfs |
                                            // row to row: the 32 lanes of one read cycle -- 4 rows x 2 column halves x 4 lanes of 8 bytes -- then cover all 64 banks once
                                            // (with 512 + 32 a row advanced 8 banks, the distance of the column halves: 2-way conflicts, SQ_LDS_BANK_CONFLICT 33 % of the LDS cycles)
 
-typedef unsigned w16_u4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void wgrad16_kernel(const float* __restrict__ du, int ldu, int du_cols, const float* __restrict__ x, int ldx,
                                                       int x_cols, int rows_valid, int chunk_rows, int tiles_k, float* __restrict__ part,
                                                       int part_rows, int part_ld, float* __restrict__ colpart, int colpart_ld, int* __restrict__ ovf) {
@@ -284,7 +280,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int lr = tid >> 5, lc = (tid & 31) * 4;
     const bool a_ok = n0 + lc < du_cols, b_ok = k0 + lc < x_cols;
     const bool do_cols = colpart != nullptr && tk == 0;
-    f32x16 om[2][2], oc[2][2];
+    floatx16 om[2][2], oc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll

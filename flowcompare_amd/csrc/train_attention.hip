@@ -15,10 +15,10 @@
 
 #include "common.h"
 #include "activations.h"
+#include "launch.h"
 
 namespace fc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct AttnBwdParams {
     const float* q; int ldq;
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdParams p) {
         // (A = a row's 2 kk + h, B = dOr[kk]).  dS = P (dP - D) is a difference of two sums of ~sqrt(DH) |dO| |v|; summed in two different
         // orders their rounding errors do not cancel, which at these widths showed as dq ~ 4e-6 where a one-key softmax (O = v, dP = D) owes an
         // exact zero.  One extra 32 x 32 tile per wave and launch.  (Head dims 32 and 64 keep the in-lane sum: their bits do not move.)
-        f32x16 dd;
+        floatx16 dd;
 #pragma unroll
         for (int r = 0; r < 16; ++r) dd[r] = 0.f;
 #pragma unroll
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdParams p) {
         __syncthreads();
         stage(kb, p.ldk, sK, t);
         __syncthreads();
-        f32x16 acc;
+        floatx16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdParams p) {
     constexpr int NHALF = DH > 128 ? 2 : 1, NBH = NB / NHALF;
 #pragma unroll 1
     for (int hh = 0; hh < NHALF; ++hh) {
-    f32x16 dqa[NBH];
+    floatx16 dqa[NBH];
 #pragma unroll
     for (int i = 0; i < NBH; ++i)
 #pragma unroll
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdParams p) {
         stage(kb, p.ldk, sK, t);
         stage(vb, p.ldv, sV, t);
         __syncthreads();
-        f32x16 s, dp;
+        floatx16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
@@ -183,7 +183,7 @@ __device__ __forceinline__ void attn_bwd_dkv_sweep(const AttnBwdParams& p, float
 #pragma unroll 1
     for (int hh = 0; hh < NHALF; ++hh) {
     const int c0 = hh * NBH * 32;
-    f32x16 dka[DK ? NBH : 1], dva[DV ? NBH : 1];
+    floatx16 dka[DK ? NBH : 1], dva[DV ? NBH : 1];
 #pragma unroll
     for (int i = 0; i < NBH; ++i)
 #pragma unroll
@@ -207,7 +207,7 @@ __device__ __forceinline__ void attn_bwd_dkv_sweep(const AttnBwdParams& p, float
             sD[tid] = qi < p.N ? p.dvec[q0 + qi] : 0.f;
         }
         __syncthreads();
-        f32x16 s, dp;
+        floatx16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
@@ -268,7 +268,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdParams p) {
 // contracts over the tile's rows reads them through ds_read_b64_tr_b16 (attention.hip, train.hip), whose row order per lane,
 // {4h..4h+3, 8+4h..8+4h+3} + 16 j, is exactly the row order of accumulator registers 8j..8j+7 -- so P^T / dS^T go from the
 // accumulators into the next MFMA's B operand after a limb split only.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 constexpr int A16_PITCH = 256 + 16;        // bytes per staged row: [hi 64 halfs | lo' 64 halfs] + pad
 
@@ -352,7 +351,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __syncthreads();
         stage_store(stage_load(kb, p.ldk, t * 32, p.M, tid), sK, tid, amax);
         __syncthreads();
-        f32x16 sm, sc;
+        floatx16 sm, sc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sm[r] = 0.f; sc[r] = 0.f; }
 #pragma unroll
@@ -380,7 +379,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const float lse2 = lse * 1.4426950408889634f;
     if (qok && h == 0) { if (!p.have_lse) p.lse[grow] = lse; p.dvec[grow] = dsum; }
     // ---- pass B: dQ^T[d][query] += K^T dS^T
-    f32x16 qm[2], qc[2];
+    floatx16 qm[2], qc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -398,7 +397,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __syncthreads();                                               // stage t & 1 is complete; every wave is done reading the other one
         const char* const cK = sK + (t & 1) * ST;
         const char* const cV = sV + (t & 1) * ST;
-        f32x16 sm, sc, pm, pc;
+        floatx16 sm, sc, pm, pc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sm[r] = 0.f; sc[r] = 0.f; pm[r] = 0.f; pc[r] = 0.f; }
 #pragma unroll
@@ -466,7 +465,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         split8(kv, Kh[ds], Kl[ds]);
         split8(vv, Vh[ds], Vl[ds]);
     }
-    f32x16 km[2], kc[2], vm[2], vc[2];
+    floatx16 km[2], kc[2], vm[2], vc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __builtin_amdgcn_sched_barrier(0);
         float pv[16], dsv[16];
         {
-            f32x16 sm, sc;
+            floatx16 sm, sc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { sm[r] = 0.f; sc[r] = 0.f; }
 #pragma unroll
@@ -522,7 +521,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 pv[r] = kok ? __builtin_amdgcn_exp2f((sm[r] + sc[r] * (1.0f / 2048.0f)) * sl2 - sLse[cur][acc_row(r, h)]) : 0.f;
         }
         {
-            f32x16 pm, pc;
+            floatx16 pm, pc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { pm[r] = 0.f; pc[r] = 0.f; }
 #pragma unroll
@@ -592,24 +591,10 @@ template <int DH>
 static void launch_attn_bwd(const AttnBwdParams& p, int B, hipStream_t s) {
     const double fl = 2.0 * B * (double)p.N * p.M * DH;
     constexpr size_t lds = (2 * 32 * (size_t)(DH + 1) + 64) * sizeof(float);      // 16.6 KB at head dim 64, 66 KB at 256
-    auto kq = attn_bwd_dq_kernel<DH>;
-    auto kkv = attn_bwd_dkv_kernel<DH>;
-    if constexpr (lds > 65536) {
-        static PerDeviceOnce attr_once;
-        attr_once.run([&](int) {
-            FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kq), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            FC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kkv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            return 0;
-        });
-    }
-    {
-        ProfScope ps(DH <= 64 ? "fc::attn_bwd_dq_kernel" : DH == 128 ? "fc::attn_bwd_dq_kernel<128>" : "fc::attn_bwd_dq_kernel<256>", 4.0 * fl, 0.0, s);
-        hipLaunchKernelGGL(kq, dim3((p.N + 127) / 128, B), dim3(256), lds, s, p);
-        FC_HIP(hipGetLastError());
-    }
-    ProfScope ps(DH <= 64 ? "fc::attn_bwd_dkv_kernel" : DH == 128 ? "fc::attn_bwd_dkv_kernel<128>" : "fc::attn_bwd_dkv_kernel<256>", (DH > 128 ? 7.0 : 4.0) * fl, 0.0, s);
-    hipLaunchKernelGGL(kkv, dim3((p.M + 127) / 128, B), dim3(256), lds, s, p);
-    FC_HIP(hipGetLastError());
+    launch_kernel<attn_bwd_dq_kernel<DH>, (int)lds>(DH <= 64 ? "fc::attn_bwd_dq_kernel" : DH == 128 ? "fc::attn_bwd_dq_kernel<128>" : "fc::attn_bwd_dq_kernel<256>", 4.0 * fl, 0.0,
+                                                    dim3((p.N + 127) / 128, B), dim3(256), lds, s, p);
+    launch_kernel<attn_bwd_dkv_kernel<DH>, (int)lds>(DH <= 64 ? "fc::attn_bwd_dkv_kernel" : DH == 128 ? "fc::attn_bwd_dkv_kernel<128>" : "fc::attn_bwd_dkv_kernel<256>",
+                                                     (DH > 128 ? 7.0 : 4.0) * fl, 0.0, dim3((p.M + 127) / 128, B), dim3(256), lds, s, p);
 }
 
 }  // namespace fc

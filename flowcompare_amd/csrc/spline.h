@@ -25,6 +25,21 @@ __device__ __forceinline__ float fast_exp(float v) { return __builtin_amdgcn_exp
 __device__ __forceinline__ float fast_log(float v) { return __builtin_amdgcn_logf(v) * 0.6931471805599453f; }
 __device__ __forceinline__ float fast_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
+// Running sums of the spline's softmax terms and bin sizes.  Up to 8 bins: one by one.  16 bins: in blocks of four (a block's terms are added to
+// each other, finished blocks to each other, the two once per step).  Fifteen equal bins beside a wide one round the same way at every step of a
+// plain chain, which put the knots 8.6 units of 2^-22 from their fp64 places and mid-bin y 3.6e-5 off (tests/test_gpu_spline_edges.py); in
+// blocks the same parameters come within 2.5.  K <= 8 keeps the chain and its result bits.  rq_spline_bwd_elem (train_elem.hip) sums the same
+// way, so that the training forward and its gradient pick their bins from knots summed alike.
+template <int K>
+struct rq_prefix {
+    float done = 0.f, part = 0.f;
+    __device__ __forceinline__ float add(int i, float v) {           // i: position of v (a compile-time constant after unrolling); returns the sum so far
+        if (K > 8 && i % 4 == 0) { done += part; part = 0.f; }
+        part += v;
+        return K > 8 ? done + part : part;
+    }
+};
+
 // Forward and inverse, with divergent branches for the bin selection.  rq_spline_bwd_elem (train_elem.hip) is the gradient of THIS
 // routine's forward direction in its own arithmetic (expf, true division, probabilities kept): merging the two would change training bits.
 template <int K>
@@ -40,13 +55,14 @@ __device__ __forceinline__ void rq_spline_elem(float x, const float* u, int us, 
 #pragma unroll
         for (int i = 0; i < K; ++i) { e[i] = u[(h * K + i) * us]; mx = fmaxf(mx, e[i]); }
         float sum = 0.f;
+        rq_prefix<K> se;
 #pragma unroll
-        for (int i = 0; i < K; ++i) { e[i] = fast_exp(e[i] - mx); sum += e[i]; }
-        float c = 0.f;
+        for (int i = 0; i < K; ++i) { e[i] = fast_exp(e[i] - mx); sum = se.add(i, e[i]); }
         const float rs = __builtin_amdgcn_rcpf(sum);
         knots[h][0] = -B;
+        rq_prefix<K> sc;
 #pragma unroll
-        for (int i = 0; i < K; ++i) { c += min_size + (1.0f - min_size * K) * (e[i] * rs); knots[h][i + 1] = 2.0f * B * c - B; }
+        for (int i = 0; i < K; ++i) { const float c = sc.add(i, min_size + (1.0f - min_size * K) * (e[i] * rs)); knots[h][i + 1] = 2.0f * B * c - B; }
         knots[h][K] = B;
     }
     const float (&cw)[K + 1] = knots[0], (&ch)[K + 1] = knots[1];
@@ -87,7 +103,13 @@ __device__ __forceinline__ void rq_spline_elem(float x, const float* u, int us, 
         const float qb = in_h * d0 - dy * t3;
         const float qc = -delta * dy;
         const float disc = qb * qb - 4.0f * qa * qc;
-        const float root = fast_div(2.0f * qc, -qb - sqrtf(disc));
+        // The root lies in [0, 1].  Where the spline is flat the discriminant is a difference of numbers of order one: fp32 can round it below
+        // zero at a bin's upper knot, where it is (h d1)^2 (the root is then 2 qc / -qb to rounding), and can put the root a few 1e-6 beyond 1,
+        // so that the point leaves the bin while log|det| still comes from this bin's formula.  Both are held at the bound (a NaN stays a NaN).
+        // Below 0 the root cannot fall: dy >= 0 from the bin search, so qc <= 0, and -qb - sqrt(disc) < 0 wherever dy is small (qb ~ h d0 > 0);
+        // sign arithmetic is exact.
+        const float r0 = fast_div(2.0f * qc, -qb - sqrtf(disc < 0.f ? 0.f : disc));
+        const float root = r0 > 1.0f ? 1.0f : r0;
         y = root * in_w + in_cw;
         const float tt = root * (1.0f - root);
         const float den = delta + t3 * tt;
@@ -121,20 +143,22 @@ __device__ __forceinline__ void rq_spline_fwd_regs(float x, const U& u, S os, fl
 #pragma unroll
     for (int i = 0; i < K; ++i) { ew[i] = u(i); eh[i] = u(K + i); mw = fmaxf(mw, ew[i]); mh = fmaxf(mh, eh[i]); }
     float sw = 0.f, sh = 0.f;
+    rq_prefix<K> sew, seh;
     const float ow = -mw * l2s, oh = -mh * l2s;
 #pragma unroll
     for (int i = 0; i < K; ++i) {
-        ew[i] = __builtin_amdgcn_exp2f(fmaf(ew[i], l2s, ow)); sw += ew[i];
-        eh[i] = __builtin_amdgcn_exp2f(fmaf(eh[i], l2s, oh)); sh += eh[i];
+        ew[i] = __builtin_amdgcn_exp2f(fmaf(ew[i], l2s, ow)); sw = sew.add(i, ew[i]);
+        eh[i] = __builtin_amdgcn_exp2f(fmaf(eh[i], l2s, oh)); sh = seh.add(i, eh[i]);
     }
     const float fw = (1.0f - MINW * K) * __builtin_amdgcn_rcpf(sw), fh = (1.0f - MINH * K) * __builtin_amdgcn_rcpf(sh);
     // widths: bin = #{knots <= x} (last knot + 1e-6), in_cw = largest knot <= x, hi = smallest knot > x
-    float c = 0.f, in_cw = -B, hi = INFINITY;
+    float in_cw = -B, hi = INFINITY;
+    rq_prefix<K> scw, sch;
     float ud0r = SEEDED ? RQ_PAD_LOGIT : 0.f, ud1r = u(2 * K);   // bin 0: the left pad and logit 0
     int bin = 0;
 #pragma unroll
     for (int i = 0; i < K; ++i) {
-        c += fmaf(fw, ew[i], MINW);
+        const float c = scw.add(i, fmaf(fw, ew[i], MINW));
         const float knot = i == K - 1 ? B : fmaf(2.0f * B, c, -B);
         const bool ge = x >= (i == K - 1 ? knot + RQ_SEARCH_EPS : knot);
         bin += ge ? 1 : 0;
@@ -147,10 +171,10 @@ __device__ __forceinline__ void rq_spline_fwd_regs(float x, const U& u, S os, fl
     }
     const float in_w = hi - in_cw;
     // heights: knot index bin (lower edge) and bin + 1 (upper edge) of the cumulative heights
-    float ch = 0.f, in_ch = -B, ch_hi = B;
+    float in_ch = -B, ch_hi = B;
 #pragma unroll
     for (int i = 0; i < K; ++i) {
-        ch += fmaf(fh, eh[i], MINH);
+        const float ch = sch.add(i, fmaf(fh, eh[i], MINH));
         const float knot = i == K - 1 ? B : fmaf(2.0f * B, ch, -B);
         in_ch = (i + 1 == bin) ? knot : in_ch;
         ch_hi = (i == bin) ? knot : ch_hi;

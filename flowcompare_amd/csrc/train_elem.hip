@@ -69,12 +69,12 @@ __device__ __forceinline__ void rq_spline_bwd_elem(float x, const float* __restr
 #pragma unroll
         for (int i = 0; i < K; ++i) { p[i] = u[hh * K + i]; mx = fmaxf(mx, p[i]); }
         float sum = 0.f;
+        rq_prefix<K> se, sc;                 // the forward's summation order (spline.h): blocks of four at 16 bins, so both pick their bins from knots summed alike
 #pragma unroll
-        for (int i = 0; i < K; ++i) { p[i] = expf(p[i] - mx); sum += p[i]; }
-        float c = 0.f;
+        for (int i = 0; i < K; ++i) { p[i] = expf(p[i] - mx); sum = se.add(i, p[i]); }
         knots[hh][0] = -B;
 #pragma unroll
-        for (int i = 0; i < K; ++i) { p[i] = p[i] / sum; c += min_size + (1.0f - min_size * K) * p[i]; knots[hh][i + 1] = 2.0f * B * c - B; }
+        for (int i = 0; i < K; ++i) { p[i] = p[i] / sum; const float c = sc.add(i, min_size + (1.0f - min_size * K) * p[i]); knots[hh][i + 1] = 2.0f * B * c - B; }
         knots[hh][K] = B;
     }
     const float (&pw)[K] = probs[0], (&ph)[K] = probs[1], (&cw)[K + 1] = knots[0], (&ch)[K + 1] = knots[1];

@@ -84,23 +84,29 @@ def oracle_flow_rows(cfg, md, ctx, x, extra, eps, dtype):
     return lp[0], margin[0]
 
 
-def hip_rows_with_decisions(cfg, md, ctx_dev, x, extra, eps):
-    """The HIP flow on the given target rows x [1, n, 6] against the device context ctx_dev [1, M, E], with the engine's diagnostic trace
-    (fc_debug_flow_trace) switched on: returns (log_prob [n] on the CPU, the inside / outside decision |x2| <= 3 of every spline evaluation
-    of the run as one [1, n, d2] bool mask per layer -- taken on the fp32 x2 the coupling kernel reads, with its own comparison)."""
+def hip_rows_with_trace(cfg, md, ctx_dev, x, extra, eps):
+    """The HIP flow on the target rows x [B, n, 6] against the device context ctx_dev [B, M, E], with the engine's diagnostic trace
+    (fc_debug_flow_trace) switched on: returns (log_prob [B, n] on the CPU, the traced x2 [n_layers, B, n, d2] on the CPU: the fp32 half of the
+    latent exactly as the coupling kernel of each layer reads it)."""
     from flowcompare_amd import engine
     h = md["flow"]._engine()
     L = engine.lib()
-    n, n_layers, d2 = x.shape[1], cfg["n_flow_layers"], h.latent_dim - h.latent_dim // 2
-    buf = torch.zeros(n_layers, n, d2, dtype=torch.float32, device=ctx_dev.device)
+    B, n, n_layers, d2 = x.shape[0], x.shape[1], cfg["n_flow_layers"], h.latent_dim - h.latent_dim // 2
+    buf = torch.zeros(n_layers, B * n, d2, dtype=torch.float32, device=ctx_dev.device)
     assert L.fc_debug_flow_trace(buf.data_ptr(), buf.numel()) == 0
     try:
         lp = h.log_prob(x.to(ctx_dev.device), ctx_dev, None if extra is None else extra.to(ctx_dev.device), [e.to(ctx_dev.device) for e in eps])
         torch.cuda.synchronize()
     finally:
         L.fc_debug_flow_trace(None, 0)
-    x2 = buf.cpu()
-    return lp[0].cpu(), [((x2[l] >= -3.0) & (x2[l] <= 3.0))[None] for l in range(n_layers)]
+    return lp.cpu(), buf.cpu().reshape(n_layers, B, n, d2)
+
+
+def hip_rows_with_decisions(cfg, md, ctx_dev, x, extra, eps):
+    """hip_rows_with_trace for one scene, x [1, n, 6]: returns (log_prob [n] on the CPU, the inside / outside decision |x2| <= 3 of every spline
+    evaluation of the run as one [1, n, d2] bool mask per layer -- taken on the fp32 x2 the coupling kernel reads, with its own comparison)."""
+    lp, x2 = hip_rows_with_trace(cfg, md, ctx_dev, x, extra, eps)
+    return lp[0], [(x2[l] >= -3.0) & (x2[l] <= 3.0) for l in range(x2.shape[0])]
 
 
 def side_by_side(*thunks):

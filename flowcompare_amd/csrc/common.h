@@ -310,6 +310,18 @@ struct TrainWideArgs {
 void launch_train_wide(const TrainWideArgs& a, hipStream_t s);      // train_wide (knob 31) routes training Linear layers with at least 1024 outputs here
 // staging.hip: the steps either side of the path
 void launch_fps_nd(const float* pts, int ld, int C, int64_t* idx, int B, int n, int m, float* dist_scratch, hipStream_t s);
+// paconv.hip: the PAConv embedder's index and point kernels (engine, training path and the single-operator entries)
+size_t fps_scratch_floats(int B, int n);       // floats of launch_fps's [B][n] min-distance scratch: 0 up to 8192 points per scene
+void launch_fps(const float* xyz, int ld, int32_t* idx, int B, int n, int m, float* scratch, hipStream_t s);
+void launch_gather_xyz(const float* src, int ld, const int32_t* idx, float* dst, int B, int n, int m, hipStream_t s);
+void launch_knn_xyz(const float* xyz, int ld, const float* qxyz, int32_t* out, int B, int n, int m, int k, hipStream_t s);
+void launch_paconv_group(const float* xyz, int ldxyz, const float* feat, int ldf, int C, const float* qxyz, const int32_t* nidx, float* E, int ldE,
+                         float* gdiff, int B, int n, int m, int K, hipStream_t s);
+void launch_scorenet(const float* gdiff, const float* w, float* scores, int edges, hipStream_t s);
+void launch_score_reduce(const float* G, int ldg, const float* scores, const float* bn_s, const float* bn_t, int Cout, int K, float* dst, int ldd,
+                         int dst_col0, int mode, int total_queries, hipStream_t s);
+void launch_three_nn_interp(const float* uxyz, int ldu, const float* kxyz, int ldk, const float* Fk, int ldfk, int C2, const float* Fu, int ldfu, int C1,
+                            float* X, int ldX, int B, int nu, int mk, hipStream_t s);
 void launch_co_unit_sphere(const float* p0, int n0, const float* p1, int n1, int ld, float* o0, float* o1, float* inverse, int B, hipStream_t s);
 void launch_clamp_infs(float* t, long n, float* stats4, int* status, hipStream_t s);
 void launch_change_map(float* lp10, int N, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff, int use_cutoff,

@@ -7,9 +7,8 @@
 //                                                                  eval BN = per-channel scale s / shift t, s folded into both halves)
 //               gather-max: out = LeakyReLU( max_j u[idx_j] + v )  (LeakyReLU is increasing, so it commutes with max)
 //   which does k x fewer conv FLOPs and never builds the [B,2C,M,k] edge tensor.
-// conv5 + BN1d fold into one GEMM with a LeakyReLU epilogue; out_mlp is the shared MLP runner (GELU).
+// conv5 + BN1d fold into one GEMM with a LeakyReLU epilogue; out_mlp is the shared head MLP (hostpack.h).
 #include <algorithm>
-#include <cmath>
 #include <memory>
 
 #include "hostpack.h"
@@ -17,26 +16,14 @@
 struct fc_dgcnn {
     int* fp16_flag = nullptr;   // device word raised by the split-fp16 GEMM loop on an activation >= 65504 (common.h: Fp16Guard)
     fc::DeviceArena arena;
-    int k = 0, global_pool = 0, c_in = 0, E = 0, E_pad = 0, H_pad = 0;
+    int k = 0, global_pool = 0, c_in = 0;
     fc::PackedLinear level[4];
     int lvl_cin[4] = {0, 0, 0, 0}, lvl_cout[4] = {64, 64, 128, 256}, lvl_col[4] = {0, 64, 128, 256};
     fc::PackedLinear conv5;
-    fc::PackedMLP mlp;
+    fc::HeadMLP head;
 };
 
 namespace fc {
-
-static void bn_fold(const WeightTable& wt, const std::string& p, int C, VecD& s, VecD& t) {
-    const HostTensor& g = wt.get(p + ".weight", {C});
-    const HostTensor& b = wt.get(p + ".bias", {C});
-    const HostTensor& m = wt.get(p + ".running_mean", {C});
-    const HostTensor& v = wt.get(p + ".running_var", {C});
-    s.resize(C); t.resize(C);
-    for (int i = 0; i < C; ++i) {
-        s[i] = (double)g.data[i] / std::sqrt((double)v.data[i] + 1e-5);
-        t[i] = (double)b.data[i] - (double)m.data[i] * s[i];
-    }
-}
 
 static void build_dgcnn(fc_dgcnn& e, const WeightTable& wt) {
     int cin = -1;
@@ -73,22 +60,7 @@ static void build_dgcnn(fc_dgcnn& e, const WeightTable& wt) {
         for (int o = 0; o < 512; ++o) for (int c = 0; c < 512; ++c) W.at(o, c) *= s[o];
         e.conv5 = pack_linear(e.arena, W, t, {}, map_prefix(512, 512), map_prefix(512, 512), {512});
     }
-    const int in_w = e.global_pool ? 1024 : 512;
-    pack_mlp_mid(e.arena, wt, "out_mlp", e.mlp);
-    {
-        const HostTensor& w = wt.get("out_mlp.in_layer.weight");
-        if (w.shape[1] != in_w) throw Error(FC_ERR_SHAPE, "out_mlp.in_layer.weight: expected input width " + std::to_string(in_w));
-        const int n = (int)w.shape[0];
-        e.mlp.in_layer = pack_linear(e.arena, mat_from(w), vec_from(wt.get("out_mlp.in_layer.bias", {n})), {}, map_prefix(n, round_up(n, 32)),
-                                     map_prefix(in_w, in_w), {in_w});
-        const HostTensor& wo = wt.get("out_mlp.out_layer.weight");
-        const int hl = e.mlp.sizes.back();
-        e.E = (int)wo.shape[0];
-        e.E_pad = round_up(e.E, 32);
-        e.mlp.out_layer = pack_linear(e.arena, mat_from(wo), vec_from(wt.get("out_mlp.out_layer.bias", {e.E})), {}, map_prefix(e.E, e.E_pad),
-                                      map_prefix(hl, round_up(hl, 32)), {round_up(hl, 32)});
-    }
-    e.H_pad = std::max(max_hidden_pad(e.mlp), 32);
+    pack_head_mlp(e.arena, wt, "out_mlp", e.global_pool ? 1024 : 512, e.head);
 }
 
 struct DgWs {
@@ -106,9 +78,9 @@ static DgWs plan_dg(const fc_dgcnn& e, int B, int M, void* ws, size_t bytes, boo
     w.uv = c.floats((size_t)w.P_pad * 512);
     w.t5 = c.floats((size_t)w.P_pad * 512);
     w.idx = (int32_t*)c.bytes((size_t)w.P * e.k * sizeof(int32_t));
-    for (int i = 0; i < 3; ++i) w.h[i] = c.floats((size_t)w.R_pad * e.H_pad);
+    for (int i = 0; i < 3; ++i) w.h[i] = c.floats((size_t)w.R_pad * e.head.H_pad);
     w.pool = c.floats(e.global_pool ? (size_t)w.R_pad * 1024 : 1);
-    w.otmp = c.floats((size_t)w.R_pad * e.E_pad);
+    w.otmp = c.floats((size_t)w.R_pad * e.head.E_pad);
     if (need) *need = c.off + 256;
     return w;
 }
@@ -144,12 +116,7 @@ static void dgcnn_forward(fc_dgcnn& e, const float* pts, float* out, int B, int 
         in = {w.pool, 1024};
         rows = B; rows_pad = w.R_pad;
     }
-    const int cur = run_mlp_hidden_generic(e.mlp, &in, nullptr, FC_ACT_GELU, w.h, e.H_pad, rows_pad, s, rows);
-    GemmEpi g{};
-    g.C = w.otmp; g.ldc = e.E_pad;
-    ASeg a{w.h[cur], e.H_pad};
-    launch_gemm(e.mlp.out_layer, &a, rows_pad, g, EPI_LINEAR, s);
-    launch_pack_rows(w.otmp, e.E_pad, e.E, out, e.E, 0, e.E, rows, s);
+    run_head_mlp(e.head, in, w.h, w.otmp, out, rows, rows_pad, 0, s);       // (the out_layer launch of this engine sets no rows_valid)
 }
 
 const char* get_last_error();
@@ -168,13 +135,11 @@ int fc_dgcnn_create(int32_t n_neighbors, int32_t global_pool, const fc_tensor* t
     e->global_pool = global_pool ? 1 : 0;
     fc::WeightTable wt(tensors, n_tensors);
     fc::build_dgcnn(*e, wt);
-    e->fp16_flag = (int*)e->arena.alloc_floats(1);
-    FC_HIP(hipDeviceSynchronize());
-    *out = e.release();
+    *out = fc::finish_create(e);
     FC_API_END
 }
 void fc_dgcnn_destroy(fc_dgcnn* emb) { delete emb; }
-int fc_dgcnn_out_dim(const fc_dgcnn* emb) { return emb ? emb->E : 0; }
+int fc_dgcnn_out_dim(const fc_dgcnn* emb) { return emb ? emb->head.E : 0; }
 int fc_dgcnn_workspace_bytes(const fc_dgcnn* emb, int32_t B, int32_t M, size_t* bytes) {
     FC_API_BEGIN
     if (!emb || !bytes || B < 1 || M < 1) throw fc::Error(FC_ERR_INVALID, "fc_dgcnn_workspace_bytes: bad argument");
@@ -183,11 +148,9 @@ int fc_dgcnn_workspace_bytes(const fc_dgcnn* emb, int32_t B, int32_t M, size_t* 
 }
 int fc_dgcnn_embed_f32(fc_dgcnn* emb, const float* pts, float* out, int32_t B, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
     FC_API_BEGIN
-    if (!emb || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_dgcnn_embed_f32: null handle / workspace");
-    // fast split-fp16 GEMMs first; the whole pass is repeated with the bf16-limb GEMMs if an activation left fp16's range
-    fc::run_fp16_guarded(emb->fp16_flag, (hipStream_t)stream, [=] {
+    fc::embed_guarded(emb, workspace, "fc_dgcnn_embed_f32", (hipStream_t)stream, [=] {
         fc::dgcnn_forward(*emb, pts, out, B, M, workspace, workspace_bytes, (hipStream_t)stream);
-    }, true);
+    });
     FC_API_END
 }
 

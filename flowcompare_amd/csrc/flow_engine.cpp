@@ -500,17 +500,26 @@ int fc_flow_noise_width(const fc_flow* flow, int32_t i) {
     return flow->d.nz;
 }
 
+// One guarded forward pass: fast split-fp16 GEMMs first; the whole pass is repeated with the bf16-limb GEMMs if an activation left fp16's
+// range, which rewrites every output of the pass (log-probs, latent, weight buffers, slabs, masses).  With a deferred range check
+// (fc_range_check_defer) the pass may be repeated after the entry point has returned, so it owns its arguments: the noise pointers and the
+// probe are copied.  probe: null = a plain log-prob pass.
+static void guarded_forward(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int n_eps, float* logprob,
+                            float* z_out, int B, int N, int M, void* ws, size_t ws_bytes, hipStream_t s, const fc::AttnProbe* probe = nullptr) {
+    const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
+    const bool probing = probe != nullptr;
+    const fc::AttnProbe probe_own = probing ? *probe : fc::AttnProbe();
+    fc::run_fp16_guarded(flow->fp16_flag, s, [=] {
+        fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, z_out, B, N, M, ws, ws_bytes, s, probing ? &probe_own : nullptr);
+    }, true);
+    fc::check_expm_status(*flow, s);
+}
+
 int fc_flow_logprob_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int32_t n_eps,
                         float* logprob, float* z_out, int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
     FC_API_BEGIN
     if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_flow_logprob_f32: null flow / workspace");
-    // fast split-fp16 GEMMs first; the whole pass is repeated with the bf16-limb GEMMs if an activation left fp16's range
-    // (deferred range check, fc_range_check_defer: the pass may be repeated after this call has returned -- it owns its arguments)
-    const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
-    fc::run_fp16_guarded(flow->fp16_flag, (hipStream_t)stream, [=] {
-        fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, z_out, B, N, M, workspace, workspace_bytes, (hipStream_t)stream);
-    }, true);
-    fc::check_expm_status(*flow, (hipStream_t)stream);
+    guarded_forward(flow, x, ctx, extra, eps, n_eps, logprob, z_out, B, N, M, workspace, workspace_bytes, (hipStream_t)stream);
     FC_API_END
 }
 
@@ -528,6 +537,16 @@ static void check_probe_layer(const fc_flow* flow, const std::string& who, int l
                                         "embedding to its couplings directly (only layer -1, the augmenter, attends)");
     }
 }
+// the request list of probe entry `who` into a probe's (layers, output buffers) pair
+static void probe_requests(const fc_flow* flow, const std::string& who, const int32_t* layers, float* const* out, int n_layers,
+                           std::vector<int>& probe_layers, std::vector<float*>& probe_out) {
+    for (int i = 0; i < n_layers; ++i) {
+        if (!out[i]) throw fc::Error(FC_ERR_INVALID, who + ": null output buffer for request " + std::to_string(i));
+        check_probe_layer(flow, who, layers[i]);
+        probe_layers.push_back(layers[i]);
+        probe_out.push_back(out[i]);
+    }
+}
 
 int fc_flow_attention_weights_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int32_t n_eps,
                                   const int32_t* layers, int32_t n_layers, const int32_t* sel, int32_t P, int32_t sel_per_scene, float* const* out,
@@ -537,22 +556,10 @@ int fc_flow_attention_weights_f32(fc_flow* flow, const float* x, const float* ct
     if (n_layers < 1 || !layers || !out) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: no layers requested (layers / out are null or n_layers < 1)");
     if (!sel) P = N;
     if (P < 1) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: P must be positive");
-    // every request is checked before anything is launched
     fc::AttnProbe probe;
     probe.sel = sel; probe.P = P; probe.sel_per_scene = sel ? (sel_per_scene != 0) : 0;
-    for (int i = 0; i < n_layers; ++i) {
-        const int l = layers[i];
-        if (!out[i]) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: null output buffer for request " + std::to_string(i));
-        check_probe_layer(flow, "fc_flow_attention_weights_f32", l);
-        probe.layers.push_back(l);
-        probe.out.push_back(out[i]);
-    }
-    // the guarded pass of fc_flow_logprob_f32; a pass repeated on the bf16 limbs rewrites the weight buffers too.  Deferred: it owns its arguments
-    const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
-    fc::run_fp16_guarded(flow->fp16_flag, (hipStream_t)stream, [=] {
-        fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, nullptr, B, N, M, workspace, workspace_bytes, (hipStream_t)stream, &probe);
-    }, true);
-    fc::check_expm_status(*flow, (hipStream_t)stream);
+    probe_requests(flow, "fc_flow_attention_weights_f32", layers, out, n_layers, probe.layers, probe.out);
+    guarded_forward(flow, x, ctx, extra, eps, n_eps, logprob, nullptr, B, N, M, workspace, workspace_bytes, (hipStream_t)stream, &probe);
     FC_API_END
 }
 
@@ -577,26 +584,15 @@ int fc_flow_attention_mass_f32(fc_flow* flow, const float* x, const float* ctx, 
     if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_f32: null flow / workspace");
     if (n_layers < 1 || !layers || !out) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_f32: no layers requested (layers / out are null or n_layers < 1)");
     if (B < 1 || N < 1 || M < 1) throw fc::Error(FC_ERR_INVALID, "B, N, M must be positive");
-    // every request is checked before anything is launched
     fc::AttnProbe probe;
     probe.row_weight = row_weight;
-    for (int i = 0; i < n_layers; ++i) {
-        if (!out[i]) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_f32: null output buffer for request " + std::to_string(i));
-        check_probe_layer(flow, "fc_flow_attention_mass_f32", layers[i]);
-        probe.mass_layers.push_back(layers[i]);
-        probe.mass_out.push_back(out[i]);
-    }
+    probe_requests(flow, "fc_flow_attention_mass_f32", layers, out, n_layers, probe.mass_layers, probe.mass_out);
     const size_t slab_off = mass_slab_offset(*flow, B, N, M), need = slab_off + fc::attention_mass_slab_bytes(B, N, M);
     if (workspace_bytes < need)
         throw fc::Error(FC_ERR_WORKSPACE, "fc_flow_attention_mass_f32: workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " + std::to_string(need) +
                                           " needed (fc_flow_attention_mass_workspace_bytes: the forward's workspace plus the slab region)");
     probe.slab = reinterpret_cast<float*>(static_cast<char*>(workspace) + slab_off);
-    // the guarded pass of fc_flow_logprob_f32; a pass repeated on the bf16 limbs rewrites slabs and outputs too.  Deferred: it owns its arguments
-    const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
-    fc::run_fp16_guarded(flow->fp16_flag, (hipStream_t)stream, [=] {
-        fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, nullptr, B, N, M, workspace, slab_off, (hipStream_t)stream, &probe);
-    }, true);
-    fc::check_expm_status(*flow, (hipStream_t)stream);
+    guarded_forward(flow, x, ctx, extra, eps, n_eps, logprob, nullptr, B, N, M, workspace, slab_off, (hipStream_t)stream, &probe);
     FC_API_END
 }
 

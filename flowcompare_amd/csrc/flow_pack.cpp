@@ -181,22 +181,14 @@ static PackedLinear build_in_layer(fc_flow& f, const WeightTable& wt, const std:
                        {first_pad, second_pad});
 }
 
-static PackedLinear build_plain(fc_flow& f, const WeightTable& wt, const std::string& name, int k_src, int k_pad) {
-    const HostTensor& w = wt.get(name + ".weight");
-    if (w.shape.size() != 2 || w.shape[1] != k_src) throw Error(FC_ERR_SHAPE, name + ".weight: unexpected input width");
-    const int n = (int)w.shape[0];
-    return pack_linear(f.arena, mat_from(w), vec_from(wt.get(name + ".bias", {n})), {}, map_prefix(n, round_up(n, 32)),
-                       map_prefix(k_src, k_pad), {k_pad});
-}
-
 // One pre-conditioner (augmenter or flow layer): its attention, the pre-attention MLP `pm` reading n_in (padded in_pad) columns, and the
 // LayerNorm -> q fold through that MLP's out_layer.
 static void build_precond(fc_flow& f, const WeightTable& wt, const std::string& attn_prefix, const std::string& pm, int n_in, int in_pad,
                           PackedMLP& pre, AttnPack& at, std::vector<MatD>& kv_rows, int slot) {
     build_attn(f, wt, attn_prefix, at, kv_rows, slot);
     pack_mlp_mid(f.arena, wt, pm, pre);
-    pre.in_layer = build_plain(f, wt, pm + ".in_layer", n_in, in_pad);
-    pre.out_layer = build_plain(f, wt, pm + ".out_layer", pre.sizes.back(), round_up(pre.sizes.back(), 32));
+    pre.in_layer = pack_plain_linear(f.arena, wt, pm + ".in_layer", n_in, in_pad);
+    pre.out_layer = pack_plain_linear(f.arena, wt, pm + ".out_layer", pre.sizes.back(), round_up(pre.sizes.back(), 32));
     if (pre.out_layer.N_pad != f.d.A_in_pad) throw Error(FC_ERR_SHAPE, pm.substr(pm.rfind('.') + 1) + " output width != attn_input_dim");
     build_lnq(f, wt, pm + ".out_layer", at);
 }

@@ -365,6 +365,26 @@ PackedLinear pack_linear(DeviceArena& arena, const MatD& W, const VecD& bias, co
     return L;
 }
 
+PackedLinear pack_plain_linear(DeviceArena& arena, const WeightTable& wt, const std::string& name, int k_src, int k_pad) {
+    const HostTensor& w = wt.get(name + ".weight");
+    if (w.shape.size() != 2 || w.shape[1] != k_src) throw Error(FC_ERR_SHAPE, name + ".weight: unexpected input width");
+    const int n = (int)w.shape[0];
+    return pack_linear(arena, mat_from(w), vec_from(wt.get(name + ".bias", {n})), {}, map_prefix(n, round_up(n, 32)),
+                       map_prefix(k_src, k_pad), {k_pad});
+}
+
+void bn_fold(const WeightTable& wt, const std::string& p, int C, VecD& s, VecD& t) {
+    const HostTensor& g = wt.get(p + ".weight", {C});
+    const HostTensor& b = wt.get(p + ".bias", {C});
+    const HostTensor& m = wt.get(p + ".running_mean", {C});
+    const HostTensor& v = wt.get(p + ".running_var", {C});
+    s.resize(C); t.resize(C);
+    for (int i = 0; i < C; ++i) {
+        s[i] = (double)g.data[i] / std::sqrt((double)v.data[i] + 1e-5);
+        t[i] = (double)b.data[i] - (double)m.data[i] * s[i];
+    }
+}
+
 void pack_mlp_mid(DeviceArena& arena, const WeightTable& wt, const std::string& prefix, PackedMLP& out) {
     out.sizes.clear();
     out.mid.clear();
@@ -439,6 +459,27 @@ int max_hidden_pad(const PackedMLP& m) {
     int mx = 0;
     for (int s : m.sizes) mx = std::max(mx, round_up(s, 32));
     return mx;
+}
+
+void pack_head_mlp(DeviceArena& arena, const WeightTable& wt, const std::string& prefix, int in_w, HeadMLP& out) {
+    pack_mlp_mid(arena, wt, prefix, out.mlp);
+    if (wt.get(prefix + ".in_layer.weight").shape[1] != in_w)
+        throw Error(FC_ERR_SHAPE, prefix + ".in_layer.weight: expected input width " + std::to_string(in_w));
+    out.mlp.in_layer = pack_plain_linear(arena, wt, prefix + ".in_layer", in_w, round_up(in_w, 32));
+    const int hl = out.mlp.sizes.back();
+    out.mlp.out_layer = pack_plain_linear(arena, wt, prefix + ".out_layer", hl, round_up(hl, 32));
+    out.E = out.mlp.out_layer.n_true;
+    out.E_pad = out.mlp.out_layer.N_pad;
+    out.H_pad = std::max(max_hidden_pad(out.mlp), 32);
+}
+void run_head_mlp(const HeadMLP& hd, const ASeg& in, float* const h[3], float* otmp, float* out, int rows, int rows_pad, int out_rows_valid,
+                  hipStream_t s) {
+    const int cur = run_mlp_hidden_generic(hd.mlp, &in, nullptr, FC_ACT_GELU, h, hd.H_pad, rows_pad, s, rows);
+    GemmEpi g{};
+    g.C = otmp; g.ldc = hd.E_pad; g.rows_valid = out_rows_valid;
+    ASeg a{h[cur], hd.H_pad};
+    launch_gemm(hd.mlp.out_layer, &a, rows_pad, g, EPI_LINEAR, s);
+    launch_pack_rows(otmp, hd.E_pad, hd.E, out, hd.E, 0, hd.E, rows, s);
 }
 
 }  // namespace fc

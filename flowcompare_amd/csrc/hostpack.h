@@ -1,8 +1,10 @@
-// Host-side (double precision) weight folding and packing into the kernel layouts.
+// Host-side (double precision) weight folding and packing into the kernel layouts, and what the engines built on them share: the MLP
+// runner, the embedders' head MLP and the tail of their create / embed entry points.
 #pragma once
 #include "common.h"
 
 #include <cmath>
+#include <memory>
 
 namespace fc {
 
@@ -38,6 +40,11 @@ std::vector<unsigned short> make_bf16_limbs(const std::vector<float>& w, int n_a
 PackedLinear pack_linear(DeviceArena& arena, const MatD& W, const VecD& bias, const VecD& colvec, const std::vector<int>& nmap,
                          const std::vector<int>& kmap, const std::vector<int>& seg_k);
 
+// `name`.weight [n, k_src] + `name`.bias as a plain padded Linear: n rows padded to 32, the k_src input columns first among k_pad
+PackedLinear pack_plain_linear(DeviceArena& arena, const WeightTable& wt, const std::string& name, int k_src, int k_pad);
+// eval-mode BatchNorm `prefix` over C channels as a per-channel scale s and shift t (running statistics, eps 1e-5)
+void bn_fold(const WeightTable& wt, const std::string& prefix, int C, VecD& s, VecD& t);
+
 // One reference MLP (models/nets.py) as packed GEMMs. The first layer is built by the caller (its input layout varies).
 struct PackedMLP {
     PackedLinear in_layer;
@@ -58,5 +65,31 @@ void attach_mlp_rows_images(DeviceArena& arena, PackedMLP& m);
 // output only as an fp16 limb image (GemmEpi::C16, pitch = its N_pad) and -1 is returned.
 int run_mlp_hidden_generic(const PackedMLP& m, const ASeg* in_segs, const float* rowscal, int act, float* const h[3], int ldh, int rows,
                            hipStream_t s, int rows_valid = 0, unsigned short* last_limbs = nullptr, float last_scale = 0.f);   // last_scale: GemmEpi::c16_scale of that image
+
+// The context embedders' head: the whole MLP `prefix` (out_mlp) over in_w input columns, plain layers throughout.
+struct HeadMLP {
+    PackedMLP mlp;
+    int E = 0, E_pad = 0, H_pad = 0;      // output width (the embedding), padded; pitch of the hidden activation buffers
+};
+void pack_head_mlp(DeviceArena& arena, const WeightTable& wt, const std::string& prefix, int in_w, HeadMLP& out);
+// hidden chain (GELU) -> out_layer into otmp [rows_pad][E_pad] -> out dense [rows][E].  out_rows_valid: GemmEpi::rows_valid of the out_layer
+// launch (the hidden chain always gets `rows`)
+void run_head_mlp(const HeadMLP& hd, const ASeg& in, float* const h[3], float* otmp, float* out, int rows, int rows_pad, int out_rows_valid,
+                  hipStream_t s);
+
+// Tail of an embedder's create entry: the range flag of its guarded passes, then the packing has to have finished before the handle leaves.
+template <class E>
+E* finish_create(std::unique_ptr<E>& e) {
+    e->fp16_flag = (int*)e->arena.alloc_floats(1);
+    FC_HIP(hipDeviceSynchronize());
+    return e.release();
+}
+// An embedder's embed entry `who`: fast split-fp16 GEMMs first; the whole pass is repeated with the bf16-limb GEMMs if an activation left
+// fp16's range.  `forward` owns its arguments (a deferred range check may run it again after the entry has returned).
+template <class E, class F>
+void embed_guarded(E* emb, const void* workspace, const char* who, hipStream_t s, F forward) {
+    if (!emb || !workspace) throw Error(FC_ERR_INVALID, std::string(who) + ": null handle / workspace");
+    run_fp16_guarded(emb->fp16_flag, s, forward, true);
+}
 
 }  // namespace fc

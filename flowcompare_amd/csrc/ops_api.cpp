@@ -308,6 +308,20 @@ int fc_op_knn_warm_f32(const float* f, const int32_t* idx_warm, int32_t* idx, in
     FC_API_END
 }
 
+int fc_op_fps_f32(const float* xyz, int32_t* idx, int32_t B, int32_t n, int32_t m, void* stream) {
+    FC_API_BEGIN
+    if (!xyz || !idx || B < 1 || n < 1 || m < 0) throw fc::Error(FC_ERR_INVALID, "fc_op_fps_f32: bad argument");
+    /* (single-operator entry of the test / training paths: the one scratch array of the > 8192-point variant is allocated here, stream-ordered;
+     * the engine's own calls carve it from the caller's workspace) */
+    float* scratch = nullptr;
+    const size_t nf = fc::fps_scratch_floats(B, n);
+    if (nf) FC_HIP(hipMallocAsync((void**)&scratch, nf * sizeof(float), (hipStream_t)stream));
+    try { fc::launch_fps(xyz, 3, idx, B, n, m, scratch, (hipStream_t)stream); }
+    catch (...) { if (scratch) (void)hipFreeAsync(scratch, (hipStream_t)stream); throw; }
+    if (scratch) FC_HIP(hipFreeAsync(scratch, (hipStream_t)stream));
+    FC_API_END
+}
+
 int fc_stage_fps_f32(const float* pts, int32_t ld, int32_t C, int64_t* idx, int32_t B, int32_t n, int32_t m, void* stream) {
     FC_API_BEGIN
     if (!pts || !idx || B < 1 || n < 1 || m < 1) throw fc::Error(FC_ERR_INVALID, "fc_stage_fps_f32: bad argument");

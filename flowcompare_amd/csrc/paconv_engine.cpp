@@ -4,26 +4,13 @@
 //   per layer: ScoreNet(xyz_nbr - xyz_centre) -> scores[edges, 8];  G = E @ weightbank  (fp32 MFMA GEMM, rows = edges, N = 8*Cout);
 //              O = ReLU(BN(sum_m score_m G_m)) -> next E, or max over the 32 neighbours after the last layer.
 // Per feature-propagation level: 3-NN inverse-distance interpolation + skip concat, then 1x1 conv + BN + ReLU as GEMMs
-// with the BN folded into the weights.  Head: the shared MLP runner (GELU).
+// with the BN folded into the weights.  Head: the shared head MLP (hostpack.h).
 #include <algorithm>
-#include <cmath>
 #include <memory>
 
 #include "hostpack.h"
 
 namespace fc {
-size_t fps_scratch_floats(int B, int n);
-void launch_fps(const float* xyz, int ld, int32_t* idx, int B, int n, int m, float* scratch, hipStream_t s);
-void launch_gather_xyz(const float* src, int ld, const int32_t* idx, float* dst, int B, int n, int m, hipStream_t s);
-void launch_knn_xyz(const float* xyz, int ld, const float* qxyz, int32_t* out, int B, int n, int m, int k, hipStream_t s);
-void launch_paconv_group(const float* xyz, int ldxyz, const float* feat, int ldf, int C, const float* qxyz, const int32_t* nidx, float* E, int ldE,
-                         float* gdiff, int B, int n, int m, int K, hipStream_t s);
-void launch_scorenet(const float* gdiff, const float* w, float* scores, int edges, hipStream_t s);
-void launch_score_reduce(const float* G, int ldg, const float* scores, const float* bn_s, const float* bn_t, int Cout, int K, float* dst, int ldd,
-                         int dst_col0, int mode, int total_queries, hipStream_t s);
-void launch_three_nn_interp(const float* uxyz, int ldu, const float* kxyz, int ldk, const float* Fk, int ldfk, int C2, const float* Fu, int ldfu, int C1,
-                            float* X, int ldX, int B, int nu, int mk, hipStream_t s);
-
 struct PaLayer {
     int cin = 0, cout = 0;      // PAConv input channels (before the x2 of kernel_input 'neighbor') and output channels
     PackedLinear bank;          // [8*cout][round32(2*cin)]
@@ -41,24 +28,11 @@ struct fc_paconv {
     std::vector<fc::PaLayer> sa[4];
     std::vector<fc::FpLayer> fp[4];
     int sa_out[4] = {0, 0, 0, 0};
-    fc::PackedMLP mlp;
-    int E = 0, E_pad = 0, H_pad = 0;
+    fc::HeadMLP head;
     static constexpr int K = 32;
 };
 
 namespace fc {
-
-static void bn_fold2(const WeightTable& wt, const std::string& p, int C, VecD& s, VecD& t) {
-    const HostTensor& g = wt.get(p + ".weight", {C});
-    const HostTensor& b = wt.get(p + ".bias", {C});
-    const HostTensor& m = wt.get(p + ".running_mean", {C});
-    const HostTensor& v = wt.get(p + ".running_var", {C});
-    s.resize(C); t.resize(C);
-    for (int i = 0; i < C; ++i) {
-        s[i] = (double)g.data[i] / std::sqrt((double)v.data[i] + 1e-5);
-        t[i] = (double)b.data[i] - (double)m.data[i] * s[i];
-    }
-}
 
 static void build_paconv(fc_paconv& e, const WeightTable& wt) {
     int prev = -1;
@@ -85,14 +59,14 @@ static void build_paconv(fc_paconv& e, const WeightTable& wt) {
             const HostTensor& w1 = wt.get(p + ".scorenet.mlp_convs_hidden.1.weight", {8, 16, 1, 1});
             const HostTensor& b1 = wt.get(p + ".scorenet.mlp_convs_hidden.1.bias", {8});
             VecD s0, t0;
-            bn_fold2(wt, p + ".scorenet.mlp_bns_hidden.0", 16, s0, t0);
+            bn_fold(wt, p + ".scorenet.mlp_bns_hidden.0", 16, s0, t0);
             std::vector<float> sw(200);
             for (int i = 0; i < 16; ++i) { for (int c = 0; c < 3; ++c) sw[3 * i + c] = (float)(s0[i] * w0.data[3 * i + c]); sw[48 + i] = (float)t0[i]; }
             for (int i = 0; i < 128; ++i) sw[64 + i] = w1.data[i];
             for (int i = 0; i < 8; ++i) sw[192 + i] = b1.data[i];
             L.score_w = e.arena.upload(sw);
             VecD s, t;
-            bn_fold2(wt, p + ".bn", L.cout, s, t);
+            bn_fold(wt, p + ".bn", L.cout, s, t);
             std::vector<float> fs(s.begin(), s.end()), ft(t.begin(), t.end());
             L.bn_s = e.arena.upload(fs);
             L.bn_t = e.arena.upload(ft);
@@ -117,7 +91,7 @@ static void build_paconv(fc_paconv& e, const WeightTable& wt) {
                 if (ci != c_known + c_skip) throw Error(FC_ERR_SHAPE, p + ".conv.weight: expected " + std::to_string(c_known + c_skip) + " input channels");
             } else if (ci != cin) throw Error(FC_ERR_SHAPE, p + ".conv.weight: channels do not chain");
             VecD s, t;
-            bn_fold2(wt, p + ".bn.bn", co, s, t);
+            bn_fold(wt, p + ".bn.bn", co, s, t);
             MatD W = mat_from(w);
             for (int o = 0; o < co; ++o) for (int c = 0; c < ci; ++c) W.at(o, c) *= s[o];
             FpLayer L;
@@ -128,20 +102,7 @@ static void build_paconv(fc_paconv& e, const WeightTable& wt) {
         }
         if (e.fp[i].empty()) throw Error(FC_ERR_MISSING, "FP_modules." + std::to_string(i) + ": no layers found");
     }
-    const int head_in = e.fp[0].back().cout;
-    pack_mlp_mid(e.arena, wt, "out_mlp", e.mlp);
-    const HostTensor& w = wt.get("out_mlp.in_layer.weight");
-    if (w.shape[1] != head_in) throw Error(FC_ERR_SHAPE, "out_mlp.in_layer.weight: expected input width " + std::to_string(head_in));
-    const int n = (int)w.shape[0];
-    e.mlp.in_layer = pack_linear(e.arena, mat_from(w), vec_from(wt.get("out_mlp.in_layer.bias", {n})), {}, map_prefix(n, round_up(n, 32)),
-                                 map_prefix(head_in, round_up(head_in, 32)), {round_up(head_in, 32)});
-    const HostTensor& wo = wt.get("out_mlp.out_layer.weight");
-    const int hl = e.mlp.sizes.back();
-    e.E = (int)wo.shape[0];
-    e.E_pad = round_up(e.E, 32);
-    e.mlp.out_layer = pack_linear(e.arena, mat_from(wo), vec_from(wt.get("out_mlp.out_layer.bias", {e.E})), {}, map_prefix(e.E, e.E_pad),
-                                  map_prefix(hl, round_up(hl, 32)), {round_up(hl, 32)});
-    e.H_pad = std::max(max_hidden_pad(e.mlp), 32);
+    pack_head_mlp(e.arena, wt, "out_mlp", e.fp[0].back().cout, e.head);
 }
 
 struct PaWs {
@@ -189,8 +150,8 @@ static PaWs plan_pa(const fc_paconv& e, int B, int M, void* ws, size_t bytes, bo
     w.Ya = c.floats(xmax);
     w.Yb = c.floats(xmax);
     w.P_pad = round_up(B * M, ROW_PAD);
-    for (int i = 0; i < 3; ++i) w.h[i] = c.floats((size_t)w.P_pad * e.H_pad);
-    w.otmp = c.floats((size_t)w.P_pad * e.E_pad);
+    for (int i = 0; i < 3; ++i) w.h[i] = c.floats((size_t)w.P_pad * e.head.H_pad);
+    w.otmp = c.floats((size_t)w.P_pad * e.head.E_pad);
     if (need) *need = c.off + 256;
     return w;
 }
@@ -260,13 +221,7 @@ static void paconv_forward(fc_paconv& e, const float* pts, float* out, int B, in
         c_known = e.fp[i].back().cout;
     }
     // ---- head MLP on level 0
-    ASeg in{w.feat[0], w.ldf[0]};
-    const int cur = run_mlp_hidden_generic(e.mlp, &in, nullptr, FC_ACT_GELU, w.h, e.H_pad, w.P_pad, s, B * M);
-    GemmEpi g{};
-    g.C = w.otmp; g.ldc = e.E_pad; g.rows_valid = B * M;
-    ASeg a{w.h[cur], e.H_pad};
-    launch_gemm(e.mlp.out_layer, &a, w.P_pad, g, EPI_LINEAR, s);
-    launch_pack_rows(w.otmp, e.E_pad, e.E, out, e.E, 0, e.E, B * M, s);
+    run_head_mlp(e.head, {w.feat[0], w.ldf[0]}, w.h, w.otmp, out, B * M, w.P_pad, B * M, s);
 }
 
 }  // namespace fc
@@ -281,13 +236,11 @@ int fc_paconv_create(const fc_tensor* tensors, int32_t n_tensors, fc_paconv** ou
     std::unique_ptr<fc_paconv> e(new fc_paconv());
     fc::WeightTable wt(tensors, n_tensors);
     fc::build_paconv(*e, wt);
-    e->fp16_flag = (int*)e->arena.alloc_floats(1);
-    FC_HIP(hipDeviceSynchronize());
-    *out = e.release();
+    *out = fc::finish_create(e);
     FC_API_END
 }
 void fc_paconv_destroy(fc_paconv* emb) { delete emb; }
-int fc_paconv_out_dim(const fc_paconv* emb) { return emb ? emb->E : 0; }
+int fc_paconv_out_dim(const fc_paconv* emb) { return emb ? emb->head.E : 0; }
 int fc_paconv_workspace_bytes(const fc_paconv* emb, int32_t B, int32_t M, size_t* bytes) {
     FC_API_BEGIN
     if (!emb || !bytes || B < 1 || M < 1) throw fc::Error(FC_ERR_INVALID, "fc_paconv_workspace_bytes: bad argument");
@@ -296,24 +249,9 @@ int fc_paconv_workspace_bytes(const fc_paconv* emb, int32_t B, int32_t M, size_t
 }
 int fc_paconv_embed_f32(fc_paconv* emb, const float* pts, float* out, int32_t B, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
     FC_API_BEGIN
-    if (!emb || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_paconv_embed_f32: null handle / workspace");
-    // fast split-fp16 GEMMs first; the whole pass is repeated with the bf16-limb GEMMs if an activation left fp16's range
-    fc::run_fp16_guarded(emb->fp16_flag, (hipStream_t)stream, [=] {
+    fc::embed_guarded(emb, workspace, "fc_paconv_embed_f32", (hipStream_t)stream, [=] {
         fc::paconv_forward(*emb, pts, out, B, M, workspace, workspace_bytes, (hipStream_t)stream);
-    }, true);
-    FC_API_END
-}
-int fc_op_fps_f32(const float* xyz, int32_t* idx, int32_t B, int32_t n, int32_t m, void* stream) {
-    FC_API_BEGIN
-    if (!xyz || !idx || B < 1 || n < 1 || m < 0) throw fc::Error(FC_ERR_INVALID, "fc_op_fps_f32: bad argument");
-    /* (single-operator entry of the test / training paths: the one scratch array of the > 8192-point variant is allocated here, stream-ordered;
-     * the engine's own calls carve it from the caller's workspace) */
-    float* scratch = nullptr;
-    const size_t nf = fc::fps_scratch_floats(B, n);
-    if (nf) FC_HIP(hipMallocAsync((void**)&scratch, nf * sizeof(float), (hipStream_t)stream));
-    try { fc::launch_fps(xyz, 3, idx, B, n, m, scratch, (hipStream_t)stream); }
-    catch (...) { if (scratch) (void)hipFreeAsync(scratch, (hipStream_t)stream); throw; }
-    if (scratch) FC_HIP(hipFreeAsync(scratch, (hipStream_t)stream));
+    });
     FC_API_END
 }
 

@@ -16,10 +16,6 @@
 #include "common.h"
 
 namespace fc {
-void launch_knn_xyz(const float* xyz, int ld, const float* qxyz, int32_t* out, int B, int n, int m, int k, hipStream_t s);
-void launch_paconv_group(const float* xyz, int ldxyz, const float* feat, int ldf, int C, const float* qxyz, const int32_t* nidx, float* E, int ldE,
-                         float* gdiff, int B, int n, int m, int K, hipStream_t s);
-
 __device__ __forceinline__ float sqd3(float ax, float ay, float az, float bx, float by, float bz) {
     const float dx = ax - bx, dy = ay - by, dz = az - bz;
     return fmaf(dz, dz, fmaf(dy, dy, dx * dx));       // nvcc -O2 contracts the kernels' sum of squares (paconv.hip sqdist3, oracle/pointops_oracle.c)

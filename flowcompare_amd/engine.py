@@ -21,6 +21,7 @@ SCALE_FNS = {"exp": 0, "sigmoid": 1}
 ACTS = {"GELU": 1, "RELU": 2, "ELU": 3}
 PERMUTERS = {"LinearLU": 0, "random_permute": 1, "FullCombiner": 2, "ExponentialCombiner": 3}
 EXPM = {"torch": 0, "original": 1}
+OP_ACTS = {"none": 0, "gelu": 1, "relu": 2, "elu": 3, "lrelu": 4}      # `act` of op_linear / op_mlp_hidden (FC_ACT_*)
 
 EXPORTS = list(abi.ENTRIES)          # every entry point include/fcflow.h declares
 EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES)      # ... and those of the headers behind it (include/fcflow_attention_mass.h)
@@ -66,9 +67,6 @@ def _errcheck(code, func=None, args=None):
     if code != 0:
         raise FcError(code, lib().fc_last_error().decode())
     return code
-
-
-_check = _errcheck          # earlier spelling, for callers that still wrap a call: the status it is handed is 0 by then
 
 
 def _ptr(t):
@@ -223,14 +221,40 @@ class _Workspace:
         return self.get(need.value, device)
 
 
-class FlowHandle:
-    """fc_flow wrapper: replaces the compute of models.Flow (reference models/transform.py:61-84)."""
+class _Handle:
+    """What the engine handles share: the device check, the weight table handed to the engine's create entry on the module's device, the
+    re-pack key (`version`), the workspace and the destroy entry.  `abi_prefix` names the engine's entry points (fc_flow, fc_dgcnn, fc_paconv)."""
 
-    def __init__(self, config, state_dict, version, device):
+    def __init__(self, noun, abi_prefix, version, device):
         self.version = version
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("flowcompare_amd: the flow must be on a HIP device (`.to('cuda')`); there is no CPU path")
+            raise RuntimeError(f"flowcompare_amd: the {noun} must be on a HIP device (`.to('cuda')`); there is no CPU path")
+        self._abi = abi_prefix
+        self._ws = _Workspace()
+
+    def _entry(self, name):
+        return getattr(lib(), f"{self._abi}_{name}")
+
+    def _create(self, state_dict, *head):
+        """<abi>_create(*head, tensors, n_tensors, &handle) under the handle's device."""
+        arr, keep = _tensor_table(state_dict)
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            self._entry("create")(*head, arr, len(arr), ctypes.byref(self._h))
+        del keep
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            getattr(_lib, f"{self._abi}_destroy")(self._h)
+            self._h = None
+
+
+class FlowHandle(_Handle):
+    """fc_flow wrapper: replaces the compute of models.Flow (reference models/transform.py:61-84)."""
+
+    def __init__(self, config, state_dict, version, device):
+        super().__init__("flow", "fc_flow", version, device)
         c = FcFlowConfig()
         c.struct_size = ctypes.sizeof(FcFlowConfig)
         c.input_dim, c.latent_dim, c.cif_latent_dim = config["input_dim"], config["latent_dim"], config["cif_latent_dim"]
@@ -248,35 +272,30 @@ class FlowHandle:
         c.linear_lu_eps, c.eps_expm = float(config["linear_lu_eps"]), float(config["eps_expm"])
         c.clamp_dist = float(config["clamp_dist"] or 0.0)
         self.latent_dim, self.input_dim, self.X = c.latent_dim, c.input_dim, c.extra_context_dim
-        arr, keep = _tensor_table(state_dict)
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            lib().fc_flow_create(ctypes.byref(c), arr, len(arr), ctypes.byref(self._h))
-        del keep
-        self._ws = _Workspace()
+        self._create(state_dict, ctypes.byref(c))
         self.n_noise = lib().fc_flow_noise_count(self._h)
         self.noise_width = [lib().fc_flow_noise_width(self._h, i) for i in range(self.n_noise)]
 
-    def __del__(self):
-        if getattr(self, "_h", None) and self._h.value and _lib is not None:
-            _lib.fc_flow_destroy(self._h)
-            self._h = None
+    def _extra(self, extra_context, N=None):
+        """extra_context [B,X], or [B,n,X] as produced by inner_loop's repeat (constant over n) -> fp32 [B,X]; None for a flow built without
+        one.  N: the point count a 3-D extra_context must have (None: not checked)."""
+        if not self.X:
+            return None
+        if extra_context is None:
+            raise RuntimeError("this flow was built with extra context (extra_z_value_context) but extra_context is None")
+        if extra_context.dim() == 3:
+            if N is not None and extra_context.shape[1] != N:
+                raise RuntimeError(f"Sizes of tensors must match: extra_context has {extra_context.shape[1]} points, x has {N} "
+                                   "(extra_context is repeated to config['sample_size'], reference model_initialization.py:213)")
+            extra_context = extra_context[:, 0, :]
+        return _dev_f32(extra_context)
 
     def _prep(self, x, context, extra_context, eps):
         B, N = x.shape[0], x.shape[1]
         x = _dev_f32(x)
         ctx = _dev_f32(context)
         M = ctx.shape[1]
-        extra = None
-        if self.X:
-            if extra_context is None:
-                raise RuntimeError("this flow was built with extra context (extra_z_value_context) but extra_context is None")
-            if extra_context.dim() == 3:                     # [B,n,X] as produced by inner_loop's repeat: constant over n
-                if extra_context.shape[1] != N:
-                    raise RuntimeError(f"Sizes of tensors must match: extra_context has {extra_context.shape[1]} points, x has {N} "
-                                       "(extra_context is repeated to config['sample_size'], reference model_initialization.py:213)")
-                extra_context = extra_context[:, 0, :]
-            extra = _dev_f32(extra_context)
+        extra = self._extra(extra_context, N)
         eps = [_dev_f32(e) for e in (eps or [])]
         if len(eps) != self.n_noise:
             raise RuntimeError(f"flow needs {self.n_noise} noise tensors, got {len(eps)}")
@@ -285,62 +304,65 @@ class FlowHandle:
                 raise RuntimeError(f"noise tensor has shape {tuple(e.shape)}, expected {(B, N, wdt)}")
         return x, ctx, extra, eps, B, N, M
 
-    def log_prob(self, x, context, extra_context, eps, return_latent=False):
+    def _forward(self, entry, x, context, extra_context, eps, outputs, layers=None, size_entry="workspace_bytes"):
+        """One forward pass through fc_flow_<entry>_f32 (entry: logprob, or a probe entry, whose name opens its messages): the checks of
+        _prep, the workspace of fc_flow_<size_entry>, the noise / layer pointer arrays, the call, and the keep-alive of a deferred range check.
+        outputs(B, N, M, n_layers) -> (the entry's own arguments between the noise / layer arrays and B, what the caller returns); among
+        those arguments a tensor (or None) goes as its pointer and a list of tensors as an array of pointers."""
         x, ctx, extra, eps, B, N, M = self._prep(x, context, extra_context, eps)
-        L = lib()
+        lay = ()
+        if layers is not None:
+            layers = [int(l) for l in layers]
+            if not layers:
+                raise RuntimeError(f"{entry}: no layers requested")
+            lay = ((ctypes.c_int32 * len(layers))(*layers), len(layers))
         with torch.cuda.device(self.device):
-            ws = self._ws.query(L.fc_flow_workspace_bytes, self._h, B, N, M, device=self.device)
+            own, ret = outputs(B, N, M, len(layers or ()))
+            ws = self._ws.query(self._entry(size_entry), self._h, B, N, M, device=self.device)
+            eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
+            args, keep = [], []
+            for a in own:
+                if isinstance(a, list):
+                    args.append((ctypes.c_void_p * len(a))(*[o.data_ptr() for o in a]))
+                    keep += a
+                elif isinstance(a, int):
+                    args.append(a)
+                else:
+                    args.append(_ptr(a))
+                    keep.append(a)
+            self._entry(entry + "_f32")(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), *lay, *args, B, N, M, _ptr(ws), ws.numel(), _stream())
+            _keep_if_deferred(x, ctx, extra, ws, *eps, *keep)
+        return ret
+
+    def log_prob(self, x, context, extra_context, eps, return_latent=False):
+        def outputs(B, N, M, _):
             out = torch.empty(B, N, dtype=torch.float32, device=self.device)
             z = torch.empty(B, N, self.latent_dim, dtype=torch.float32, device=self.device) if return_latent else None
-            eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
-            L.fc_flow_logprob_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), _ptr(out), _ptr(z), B, N, M, _ptr(ws), ws.numel(), _stream())
-            _keep_if_deferred(x, ctx, extra, out, z, ws, *eps)
-        return (out, z) if return_latent else out
+            return [out, z], ((out, z) if return_latent else out)
+        return self._forward("logprob", x, context, extra_context, eps, outputs)
 
     def attention_weights(self, x, context, extra_context, eps, layers, points=None, return_log_prob=False):
         """fc_flow_attention_weights_f32: the forward of log_prob that also writes the softmax rows of the selected target points at the
         requested attentions.  layers: ints, -1 = the augmenter's attention, l >= 0 = flow layer l's pre-conditioner; points: None (all N
         points) or an integer tensor [P] / [B, P].  Returns a list of [B, P, M] fp32 tensors in the order of `layers` (and the log-prob)."""
-        x, ctx, extra, eps, B, N, M = self._prep(x, context, extra_context, eps)
-        layers = [int(l) for l in layers]
-        if not layers:
-            raise RuntimeError("attention_weights: no layers requested")
-        L = lib()
-        with torch.cuda.device(self.device):
+        def outputs(B, N, M, n_layers):
             sel, P, per_scene = _points_table(points, B, N, self.device)
-            ws = self._ws.query(L.fc_flow_workspace_bytes, self._h, B, N, M, device=self.device)
-            outs = [torch.empty(B, P, M, dtype=torch.float32, device=self.device) for _ in layers]
+            outs = [torch.empty(B, P, M, dtype=torch.float32, device=self.device) for _ in range(n_layers)]
             lp = torch.empty(B, N, dtype=torch.float32, device=self.device) if return_log_prob else None
-            eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
-            lay_arr = (ctypes.c_int32 * len(layers))(*layers)
-            out_arr = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-            L.fc_flow_attention_weights_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), lay_arr, len(layers), _ptr(sel), P,
-                                            per_scene, out_arr, _ptr(lp), B, N, M, _ptr(ws), ws.numel(), _stream())
-            _keep_if_deferred(x, ctx, extra, sel, lp, ws, *eps, *outs)
-        return (outs, lp) if return_log_prob else outs
+            return [sel, P, per_scene, outs, lp], ((outs, lp) if return_log_prob else outs)
+        return self._forward("attention_weights", x, context, extra_context, eps, outputs, layers)
 
     def attention_mass(self, x, context, extra_context, eps, layers, weights=None, return_log_prob=False):
         """fc_flow_attention_mass_f32: the forward of log_prob that also writes, at the requested attentions, the attention mass of the M
         context points, mass[b, j] = sum_p weights[b, p] * softmax row p [j] over all N target points.  layers: ints as in
         attention_weights; weights: None (ones) or [N] / [B, N], float or bool.  Returns a list of [B, M] fp32 tensors in the order of
         `layers` (and the log-prob).  The [B, N, M] maps are never formed; the result is the same bytes on every run."""
-        x, ctx, extra, eps, B, N, M = self._prep(x, context, extra_context, eps)
-        layers = [int(l) for l in layers]
-        if not layers:
-            raise RuntimeError("attention_mass: no layers requested")
-        L = lib()
-        with torch.cuda.device(self.device):
+        def outputs(B, N, M, n_layers):
             g = _row_weights(weights, B, N, self.device)
-            ws = self._ws.query(L.fc_flow_attention_mass_workspace_bytes, self._h, B, N, M, device=self.device)
-            outs = [torch.empty(B, M, dtype=torch.float32, device=self.device) for _ in layers]
+            outs = [torch.empty(B, M, dtype=torch.float32, device=self.device) for _ in range(n_layers)]
             lp = torch.empty(B, N, dtype=torch.float32, device=self.device) if return_log_prob else None
-            eps_arr = (ctypes.c_void_p * max(1, len(eps)))(*[e.data_ptr() for e in eps])
-            lay_arr = (ctypes.c_int32 * len(layers))(*layers)
-            out_arr = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-            L.fc_flow_attention_mass_f32(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), lay_arr, len(layers), _ptr(g), out_arr,
-                                         _ptr(lp), B, N, M, _ptr(ws), ws.numel(), _stream())
-            _keep_if_deferred(x, ctx, extra, g, lp, ws, *eps, *outs)
-        return (outs, lp) if return_log_prob else outs
+            return [g, outs, lp], ((outs, lp) if return_log_prob else outs)
+        return self._forward("attention_mass", x, context, extra_context, eps, outputs, layers, "attention_mass_workspace_bytes")
 
     def inverse(self, z, context, extra_context, eps):
         """Inverse pass of Flow.sample from a drawn latent z [B,n,latent_dim] -> x [B,n,input_dim]."""
@@ -355,11 +377,7 @@ class FlowHandle:
         if ctx.shape[0] != B:
             raise RuntimeError(f"context batch {ctx.shape[0]} != latent batch {B}")
         M = ctx.shape[1]
-        extra = None
-        if self.X:
-            if extra_context is None:
-                raise RuntimeError("this flow was built with extra context (extra_z_value_context) but extra_context is None")
-            extra = _dev_f32(extra_context[:, 0, :] if extra_context.dim() == 3 else extra_context)
+        extra = self._extra(extra_context)
         eps = [_dev_f32(e) for e in eps]
         L = lib()
         with torch.cuda.device(self.device):
@@ -370,72 +388,40 @@ class FlowHandle:
         return out
 
 
-class DgcnnHandle:
+class _EmbedderHandle(_Handle):
+    """A context embedder's engine: embed(pts [B,M,C]) -> [B,M,out_dim], or [B,out_dim] for a global one."""
+    is_global = False
+
+    def __init__(self, abi_prefix, state_dict, version, device, *head):
+        super().__init__("embedder", abi_prefix, version, device)
+        self._create(state_dict, *head)
+        self.out_dim = self._entry("out_dim")(self._h)
+
+    def embed(self, pts):
+        pts = _dev_f32(pts)
+        B, M = pts.shape[0], pts.shape[1]
+        with torch.cuda.device(self.device):
+            ws = self._ws.query(self._entry("workspace_bytes"), self._h, B, M, device=self.device)
+            shape = (B, self.out_dim) if self.is_global else (B, M, self.out_dim)
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            self._entry("embed_f32")(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
+            _keep_if_deferred(pts, out, ws)
+        return out
+
+
+class DgcnnHandle(_EmbedderHandle):
     """fc_dgcnn wrapper: replaces models.DGCNNembedder / DGCNNembedderGlobal forward (reference models/pytorch_gcn.py:81-188)."""
 
     def __init__(self, n_neighbors, is_global, state_dict, version, device):
-        self.version = version
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("flowcompare_amd: the embedder must be on a HIP device (`.to('cuda')`); there is no CPU path")
         self.is_global = bool(is_global)
-        arr, keep = _tensor_table(state_dict)
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            lib().fc_dgcnn_create(int(n_neighbors), int(self.is_global), arr, len(arr), ctypes.byref(self._h))
-        del keep
-        self.out_dim = lib().fc_dgcnn_out_dim(self._h)
-        self._ws = _Workspace()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and self._h.value and _lib is not None:
-            _lib.fc_dgcnn_destroy(self._h)
-            self._h = None
-
-    def embed(self, pts):
-        pts = _dev_f32(pts)
-        B, M = pts.shape[0], pts.shape[1]
-        L = lib()
-        with torch.cuda.device(self.device):
-            ws = self._ws.query(L.fc_dgcnn_workspace_bytes, self._h, B, M, device=self.device)
-            shape = (B, self.out_dim) if self.is_global else (B, M, self.out_dim)
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-            L.fc_dgcnn_embed_f32(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
-            _keep_if_deferred(pts, out, ws)
-        return out
+        super().__init__("fc_dgcnn", state_dict, version, device, int(n_neighbors), int(self.is_global))
 
 
-class PaconvHandle:
+class PaconvHandle(_EmbedderHandle):
     """fc_paconv wrapper: replaces models.PointNet2SSGSeg.forward (reference pointnet2_paconv_seg.py:63-82)."""
 
     def __init__(self, state_dict, version, device):
-        self.version = version
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("flowcompare_amd: the embedder must be on a HIP device (`.to('cuda')`); there is no CPU path")
-        arr, keep = _tensor_table(state_dict)
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            lib().fc_paconv_create(arr, len(arr), ctypes.byref(self._h))
-        del keep
-        self.out_dim = lib().fc_paconv_out_dim(self._h)
-        self._ws = _Workspace()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and self._h.value and _lib is not None:
-            _lib.fc_paconv_destroy(self._h)
-            self._h = None
-
-    def embed(self, pts):
-        pts = _dev_f32(pts)
-        B, M = pts.shape[0], pts.shape[1]
-        L = lib()
-        with torch.cuda.device(self.device):
-            ws = self._ws.query(L.fc_paconv_workspace_bytes, self._h, B, M, device=self.device)
-            out = torch.empty(B, M, self.out_dim, dtype=torch.float32, device=self.device)
-            L.fc_paconv_embed_f32(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
-            _keep_if_deferred(pts, out, ws)
-        return out
+        super().__init__("fc_paconv", state_dict, version, device)
 
 
 # ---------------------------------------------------------------- single operators (unit-level parity tests)
@@ -573,7 +559,7 @@ def change_map_ragged(lp10, offsets, lp00, multiple, hard_cutoff=None):
 
 
 def op_linear(x, W, bias=None, residual=None, act="none"):
-    code = {"none": 0, "gelu": 1, "relu": 2, "elu": 3, "lrelu": 4}[act]
+    code = OP_ACTS[act]
     x, W = _dev_f32(x), _dev_f32(W)
     rows, K = x.shape
     N = W.shape[0]
@@ -591,7 +577,7 @@ def op_mlp_hidden(x0, x1, state_dict, rowscal=None, act="gelu", use_rows=True):
     use_rows (a bool): True = the row-resident chain kernel, False = one launch per layer."""
     if not isinstance(use_rows, bool):
         raise TypeError(f"op_mlp_hidden: use_rows must be a bool, not {use_rows!r}")
-    code = {"none": 0, "gelu": 1, "relu": 2, "elu": 3, "lrelu": 4}[act]
+    code = OP_ACTS[act]
     x0 = _dev_f32(x0)
     x1 = _dev_f32(x1) if x1 is not None else None
     rs = _dev_f32(rowscal) if rowscal is not None else None

@@ -161,6 +161,21 @@ def initialize_flow(config, device="cuda", mode="train"):
     return md
 
 
+def _embed_batch(batch, models_dict, config):
+    """batch = (extract_0, extract_1, extra_context) -> (extract_1, emb, extra_context) as Flow.log_prob takes them: both clouds sliced to
+    input_dim, the extra context repeated over config['sample_size'] points (einops.repeat 'b c -> b n c' in the reference), extract_0
+    embedded and a global embedding repeated over the target points."""
+    extract_0, extract_1, extra_context = batch
+    Din = config["input_dim"]
+    extract_0, extract_1 = extract_0[:, :, :Din], extract_1[:, :, :Din]
+    if extra_context is not None:
+        extra_context = extra_context[:, None, :].expand(-1, config["sample_size"], -1)
+    emb = models_dict["input_embedder"](extract_0)
+    if config["global"]:
+        emb = emb[:, None, :].expand(-1, extract_1.shape[1], -1)
+    return extract_1, emb, extra_context
+
+
 def inner_loop(batch, models_dict, config, eps=None):
     """model_initialization.py:206-228.  `eps` (optional) pins the augmenter noise."""
     if models_dict.get("sharded") and not models_dict.get("_in_shard"):
@@ -171,19 +186,11 @@ def inner_loop(batch, models_dict, config, eps=None):
             return shard.sharded_inner_loop(batch, models_dict, config, eps=eps)
         finally:
             models_dict["_in_shard"] = False
-    extract_0, extract_1, extra_context = batch
-    Din = config["input_dim"]
-    extract_0, extract_1 = extract_0[:, :, :Din], extract_1[:, :, :Din]
-    if extra_context is not None:
-        # einops.repeat(extra_context, 'b c -> b n c', n=config['sample_size']) in the reference
-        extra_context = extra_context[:, None, :].expand(-1, config["sample_size"], -1)
-    emb = models_dict["input_embedder"](extract_0)
-    if config["global"]:
-        emb = emb[:, None, :].expand(-1, extract_1.shape[1], -1)
+    extract_1, emb, extra_context = _embed_batch(batch, models_dict, config)
     log_prob = models_dict["flow"].log_prob(extract_1, context=emb, extra_context=extra_context, eps=eps)
     loss = -log_prob.mean()
     with torch.no_grad():
-        bpd = loss * math.log2(math.exp(1)) / Din
+        bpd = loss * math.log2(math.exp(1)) / config["input_dim"]
     return loss, log_prob, bpd
 
 
@@ -195,14 +202,7 @@ def attention_weights(batch, models_dict, config, layers=("aug",), points=None, 
     Returns a list of [B, P, M] tensors in the order of `layers` (row p: the weights of target point points[p] over the M context
     points, summing to 1), or (weights, log_prob) with return_log_prob.  The batch is taken as given: no scene sharding under
     config['data_parallel'] (every rank computes the scenes it is handed).  A full map is 4 B N M bytes per layer."""
-    extract_0, extract_1, extra_context = batch
-    Din = config["input_dim"]
-    extract_0, extract_1 = extract_0[:, :, :Din], extract_1[:, :, :Din]
-    if extra_context is not None:
-        extra_context = extra_context[:, None, :].expand(-1, config["sample_size"], -1)
-    emb = models_dict["input_embedder"](extract_0)
-    if config["global"]:
-        emb = emb[:, None, :].expand(-1, extract_1.shape[1], -1)
+    extract_1, emb, extra_context = _embed_batch(batch, models_dict, config)
     return models_dict["flow"].attention_weights(extract_1, context=emb, extra_context=extra_context, layers=layers, points=points, eps=eps,
                                                  return_log_prob=return_log_prob)
 
@@ -216,18 +216,12 @@ def attention_mass(batch, models_dict, config, layers=("aug",), weights=None, ep
     value or a CPU tensor raises before the library is called.  Returns a list of [B, M] fp32 tensors in the order of `layers`, or
     (masses, log_prob) with return_log_prob.  No [B, N, M] map is formed (4 B M bytes per layer against 4 B N M), and the bytes are
     the same on every run.  The batch is taken as given: no scene sharding under config['data_parallel']."""
-    extract_0, extract_1, extra_context = batch
+    from . import engine as _engine
+    extract_0, extract_1, _ = batch
     if not (extract_0.is_cuda and extract_1.is_cuda):
         raise RuntimeError("flowcompare_amd: tensors must live on a HIP device (there is no CPU path)")
-    Din = config["input_dim"]
-    extract_0, extract_1 = extract_0[:, :, :Din], extract_1[:, :, :Din]
-    from . import engine as _engine
-    _engine._row_weights(weights, extract_1.shape[0], extract_1.shape[1], extract_1.device)
-    if extra_context is not None:
-        extra_context = extra_context[:, None, :].expand(-1, config["sample_size"], -1)
-    emb = models_dict["input_embedder"](extract_0)
-    if config["global"]:
-        emb = emb[:, None, :].expand(-1, extract_1.shape[1], -1)
+    _engine._row_weights(weights, extract_1.shape[0], extract_1.shape[1], extract_1.device)      # (refused here, before the embedder runs)
+    extract_1, emb, extra_context = _embed_batch(batch, models_dict, config)
     return models_dict["flow"].attention_mass(extract_1, context=emb, extra_context=extra_context, layers=layers, weights=weights, eps=eps,
                                               return_log_prob=return_log_prob)
 

@@ -35,6 +35,15 @@ from torch import nn
 from . import engine as _engine
 
 
+def _repacked(module, make):
+    """module._handle, rebuilt by make(key) when a parameter or buffer changed since it was packed (engine.params_version: the handle's
+    `version` is the key it was built under)."""
+    key = _engine.params_version(module)
+    if module._handle is None or module._handle.version != key:
+        module._handle = make(key)
+    return module._handle
+
+
 def _no_torch_forward(self, *a, **k):
     raise RuntimeError(
         f"{type(self).__name__} is a parameter container: the computation runs in the HIP engine through "
@@ -295,10 +304,14 @@ class Flow(nn.Module):
 
     # -- engine plumbing
     def _engine(self):
-        key = _engine.params_version(self)
-        if self._handle is None or self._handle.version != key:
-            self._handle = _engine.FlowHandle(self._config, self.state_dict(), key, next(self.parameters()).device)
-        return self._handle
+        return _repacked(self, lambda key: _engine.FlowHandle(self._config, self.state_dict(), key, next(self.parameters()).device))
+
+    def _draw_eps(self, x, eps):
+        """The pass's noise: `eps` as given, or drawn with torch.randn like the reference's rsample(); kept in last_eps."""
+        if eps is None:
+            eps = [torch.randn(s, device=x.device, dtype=torch.float32) for s in self.noise_shapes(x.shape[0], x.shape[1])]
+        self.last_eps = eps
+        return eps
 
     def noise_shapes(self, B, N):
         """Noise tensors one forward consumes, in draw order."""
@@ -315,10 +328,7 @@ class Flow(nn.Module):
         as produced by inner_loop (constant over N) or None.  `eps`: optional list of explicit noise
         tensors (shapes: noise_shapes) making the stochastic forward reproducible; drawn with
         torch.randn when omitted, like the reference's rsample()."""
-        B, N = x.shape[0], x.shape[1]
-        if eps is None:
-            eps = [torch.randn(s, device=x.device, dtype=torch.float32) for s in self.noise_shapes(B, N)]
-        self.last_eps = eps
+        eps = self._draw_eps(x, eps)
         if torch.is_grad_enabled() and (self.training or x.requires_grad or (context is not None and context.requires_grad)):
             # training (train.py:108-112): the differentiable path over the HIP training primitives (train_flow.py); the fused
             # inference engine below has no backward
@@ -337,10 +347,7 @@ class Flow(nn.Module):
         if self.training:
             raise RuntimeError("Flow.attention_weights is eval-mode only (the training path has no attention probe): call .eval() first")
         ids = self._probe_layer_ids(layers, "attention_weights")
-        B, N = x.shape[0], x.shape[1]
-        if eps is None:
-            eps = [torch.randn(s, device=x.device, dtype=torch.float32) for s in self.noise_shapes(B, N)]
-        self.last_eps = eps
+        eps = self._draw_eps(x, eps)
         with torch.no_grad():
             return self._engine().attention_weights(x, context, extra_context, list(eps), ids, points=points, return_log_prob=return_log_prob)
 
@@ -380,10 +387,7 @@ class Flow(nn.Module):
         elif isinstance(layers, str):
             layers = (layers,)
         ids = self._probe_layer_ids(layers, "attention_mass")
-        B, N = x.shape[0], x.shape[1]
-        if eps is None:
-            eps = [torch.randn(s, device=x.device, dtype=torch.float32) for s in self.noise_shapes(B, N)]
-        self.last_eps = eps
+        eps = self._draw_eps(x, eps)
         with torch.no_grad():
             return self._engine().attention_mass(x, context, extra_context, list(eps), ids, weights=weights, return_log_prob=return_log_prob)
 
@@ -414,11 +418,8 @@ class _DGCNNBase(nn.Module):
         if self.training:
             raise RuntimeError("flowcompare_amd: the HIP DGCNN embedder implements eval-mode BatchNorm only "
                                "(forward log-prob path); call .eval() / initialize_flow(mode='test')")
-        key = _engine.params_version(self)
-        if self._handle is None or self._handle.version != key:
-            self._handle = _engine.DgcnnHandle(self.n_neighbors, self.is_global, self.state_dict(), key,
-                                               next(self.parameters()).device)
-        return self._handle
+        return _repacked(self, lambda key: _engine.DgcnnHandle(self.n_neighbors, self.is_global, self.state_dict(), key,
+                                                               next(self.parameters()).device))
 
     def forward(self, x):
         """x [B,M,6] -> [B,M,E] (per-point) or [B,E] (global).  In train() mode: the differentiable HIP path with BatchNorm batch
@@ -533,10 +534,7 @@ class PointNet2SSGSeg(nn.Module):
     def _engine(self):
         if self.training:
             raise RuntimeError("flowcompare_amd: the HIP PAConv embedder implements eval-mode BatchNorm only; call .eval()")
-        key = _engine.params_version(self)
-        if self._handle is None or self._handle.version != key:
-            self._handle = _engine.PaconvHandle(self.state_dict(), key, next(self.parameters()).device)
-        return self._handle
+        return _repacked(self, lambda key: _engine.PaconvHandle(self.state_dict(), key, next(self.parameters()).device))
 
     def forward(self, pointcloud):
         """pointcloud [B,M,3+c] (xyz first) -> [B,M,k].  In train() mode: the differentiable HIP path with BatchNorm batch statistics

@@ -141,6 +141,7 @@ DEBUG_ENTRIES = {
     "fc_debug_expm_info":                    ("int", "Pl"),
     "fc_debug_fp16_fallbacks":               ("int64", ""),
     "fc_debug_attention_ctx_f32":            ("int", "PPPiiiifP"),
+    "fc_debug_premlp_q_f32":                 ("int", "PiiPiPiPPiiiP"),
 }
 
 

@@ -82,6 +82,11 @@ namespace fc {
 void build_flow(fc_flow& f, const WeightTable& wt);                        // everything fc_flow_create packs; launches nothing
 bool kv_fold_gate_dims(int E, int inner, bool q_bias, bool kv_bias);       // the K|V fold's gate on the shapes alone (fc_debug_kv_fold_gate)
 void ensure_lin_inverse(fc_flow& f);                                       // packs the blocks' inverted ActNorm + permuter on the first inverse pass
+// the pieces of an attention's query side that build_flow and the single-chain test entry (ops_api.cpp fc_debug_premlp_q_f32) both pack with
+int pad_inner(int I);                                                      // q columns of an inner width: 32, 64, 128 or 256
+void fold_q_projection(const WeightTable& wt, const std::string& to_q, const std::string& norm, MatD& wq, VecD& bq);   // gamma, beta, I^-0.5, log2 e -> to_q (double)
+void pack_q_projection(DeviceArena& arena, const MatD& wq, const VecD& bq, const Dims& d, AttnPack& out);              // AttnPack::q, q_w, q_b
+void build_lnq(DeviceArena& arena, const Dims& d, const WeightTable& wt, const std::string& out_prefix, AttnPack& at);  // AttnPack::lnq where the shapes allow it
 // flow_engine.cpp
 void flow_set_trace(float* buf, size_t floats);                            // fc_debug_flow_trace
 void flow_set_expm_info(float* buf, size_t floats);                        // fc_debug_expm_info

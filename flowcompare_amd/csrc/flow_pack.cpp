@@ -29,7 +29,7 @@ namespace fc {
 // configuration: 64 = 64), and the algebra above has no place for a bias on to_q / to_kv (the reference has none, models/perceiver.py:89-95).
 // The attention kernels then read the context panel (pitch E_pad = E rounded up to 32) as I_pad-column keys and values, so the two padded
 // widths must agree as well: inner 65..96 pads to 128 (pad_inner) but its panel to 96, and keeps the projection.
-static int pad_inner(int I) {
+int pad_inner(int I) {
     if (I <= 32) return 32;
     if (I <= 64) return 64;
     if (I <= 128) return 128;
@@ -50,23 +50,37 @@ static bool kv_fold_gate(const fc_flow_config& c, const WeightTable& wt, const s
     return true;
 }
 
-// q' = c * Wq (gamma . n + beta),  c = inner^-0.5 * log2(e)   (models/perceiver.py:18-26, 96-110)
-static void build_attn(fc_flow& f, const WeightTable& wt, const std::string& p, AttnPack& out, std::vector<MatD>& kv_rows, int slot) {
-    Dims& d = f.d;
-    const HostTensor& wq_t = wt.get(p + ".fn.attention.to_q.weight");
-    if (wq_t.shape.size() != 2) throw Error(FC_ERR_SHAPE, p + ".fn.attention.to_q.weight must be 2-D");
+// q' = c * Wq (gamma . n + beta),  c = inner^-0.5 * log2(e)   (models/perceiver.py:18-26, 96-110): `to_q`.weight [I, A_in] with LayerNorm `norm`'s
+// gamma / beta, the softmax scale and log2 e folded in, and the bias that beta leaves behind -- in double, nothing packed yet
+void fold_q_projection(const WeightTable& wt, const std::string& to_q, const std::string& norm, MatD& wq, VecD& bq) {
+    const HostTensor& wq_t = wt.get(to_q + ".weight");
+    if (wq_t.shape.size() != 2) throw Error(FC_ERR_SHAPE, to_q + ".weight must be 2-D");
     const int I = (int)wq_t.shape[0], A_in = (int)wq_t.shape[1];
-    if (d.I == 0) { d.I = I; d.I_pad = pad_inner(I); d.A_in = A_in; d.A_in_pad = round_up(A_in, 32); }
-    if (I != d.I || A_in != d.A_in) throw Error(FC_ERR_SHAPE, p + ": all attention blocks must share inner / input dims");
-    MatD wq = mat_from(wq_t);
-    VecD gamma = vec_from(wt.get(p + ".norm.weight", {A_in})), beta = vec_from(wt.get(p + ".norm.bias", {A_in}));
+    wq = mat_from(wq_t);
+    VecD gamma = vec_from(wt.get(norm + ".weight", {A_in})), beta = vec_from(wt.get(norm + ".bias", {A_in}));
     const double c = std::pow((double)I, -0.5) * kLog2e;
-    VecD bq(I, 0.0);
+    bq.assign(I, 0.0);
     for (int i = 0; i < I; ++i)
         for (int k = 0; k < A_in; ++k) {
             bq[i] += c * wq.at(i, k) * beta[k];
             wq.at(i, k) *= c * gamma[k];
         }
+}
+// the folded projection (fold_q_projection, then the K|V fold where it applies) as the attention's packed q layer, with its host copy for build_lnq
+void pack_q_projection(DeviceArena& arena, const MatD& wq, const VecD& bq, const Dims& d, AttnPack& out) {
+    out.q = pack_linear(arena, wq, bq, {}, map_prefix(wq.rows, d.I_pad), map_prefix(wq.cols, d.A_in_pad), {d.A_in_pad});
+    out.q_w = wq;
+    out.q_b = bq;
+}
+
+static void build_attn(fc_flow& f, const WeightTable& wt, const std::string& p, AttnPack& out, std::vector<MatD>& kv_rows, int slot) {
+    Dims& d = f.d;
+    MatD wq;
+    VecD bq;
+    fold_q_projection(wt, p + ".fn.attention.to_q", p + ".norm", wq, bq);
+    const int I = wq.rows, A_in = wq.cols;
+    if (d.I == 0) { d.I = I; d.I_pad = pad_inner(I); d.A_in = A_in; d.A_in_pad = round_up(A_in, 32); }
+    if (I != d.I || A_in != d.A_in) throw Error(FC_ERR_SHAPE, p + ": all attention blocks must share inner / input dims");
     const HostTensor& wkv_t = wt.get(p + ".fn.attention.to_kv.weight", {2 * I, d.E});
     MatD wkv = mat_from(wkv_t);                 // rows [0,I) = K, [I,2I) = V  (chunk(2, dim=-1))
     const HostTensor& wl = wt.get(p + ".fn.lin.weight");
@@ -98,9 +112,7 @@ static void build_attn(fc_flow& f, const WeightTable& wt, const std::string& p, 
         out.kv_col = slot * 2 * d.I_pad;            // column block of this attention in the stacked K|V projection
         kv_rows[slot] = blk;
     }
-    out.q = pack_linear(f.arena, wq, bq, {}, map_prefix(I, d.I_pad), map_prefix(A_in, d.A_in_pad), {d.A_in_pad});
-    out.q_w = wq;
-    out.q_b = bq;
+    pack_q_projection(f.arena, wq, bq, d, out);
 }
 
 // LayerNorm -> q fold (see AttnPack::lnq).  h = W3 a + b3 has no activation, so its centred form h_c = h - mean(h) is linear in a:
@@ -108,8 +120,7 @@ static void build_attn(fc_flow& f, const WeightTable& wt, const std::string& p, 
 // q = Wq' h_c / sigma + bq' = (Wq' W3c a + Wq' b3c) / sigma + bq' with sigma^2 = mean(h_c^2) + eps.  One GEMM with N = A_in + I_pad
 // columns yields h_c (only squared and summed per row in the epilogue, never stored) and q_unnorm; lnq_finalize_kernel applies
 // rstd and bq'.  Replaces out_layer's store, the LayerNorm pass and the q projection GEMM.
-static void build_lnq(fc_flow& f, const WeightTable& wt, const std::string& out_prefix, AttnPack& at) {
-    const Dims& d = f.d;
+void build_lnq(DeviceArena& arena, const Dims& d, const WeightTable& wt, const std::string& out_prefix, AttnPack& at) {
     const HostTensor& w_t = wt.get(out_prefix + ".weight");
     const MatD w3 = mat_from(w_t);
     const int A = w3.rows, K = w3.cols;
@@ -135,10 +146,10 @@ static void build_lnq(fc_flow& f, const WeightTable& wt, const std::string& out_
         for (int o = 0; o < A; ++o) acc += at.q_w.at(i, o) * bias[o];
         bias[A + i] = acc;
     }
-    at.lnq = pack_linear(f.arena, m, bias, {}, map_prefix(A + d.I_pad, A + d.I_pad), map_prefix(K, K), {K});
+    at.lnq = pack_linear(arena, m, bias, {}, map_prefix(A + d.I_pad, A + d.I_pad), map_prefix(K, K), {K});
     std::vector<float> qb(d.I_pad, 0.f);
     for (int i = 0; i < at.q_w.rows; ++i) qb[i] = (float)at.q_b[i];
-    at.q_bias = f.arena.upload(qb);
+    at.q_bias = arena.upload(qb);
     at.has_lnq = at.lnq.W2 != nullptr;
 }
 
@@ -190,7 +201,7 @@ static void build_precond(fc_flow& f, const WeightTable& wt, const std::string& 
     pre.in_layer = pack_plain_linear(f.arena, wt, pm + ".in_layer", n_in, in_pad);
     pre.out_layer = pack_plain_linear(f.arena, wt, pm + ".out_layer", pre.sizes.back(), round_up(pre.sizes.back(), 32));
     if (pre.out_layer.N_pad != f.d.A_in_pad) throw Error(FC_ERR_SHAPE, pm.substr(pm.rfind('.') + 1) + " output width != attn_input_dim");
-    build_lnq(f, wt, pm + ".out_layer", at);
+    build_lnq(f.arena, f.d, wt, pm + ".out_layer", at);
 }
 
 // out_layer of a ConditionalNormal net `pn` over nz noise dims, pair-packed [mean 32 | log_std 32] (EPI_AUGMENT / EPI_SLICE)

@@ -26,6 +26,41 @@ static const KnobEntry* find_knob(int key) {
     for (const KnobEntry& k : kKnobTable) if (k.key == key) return &k;
     return nullptr;
 }
+
+// fc_debug_premlp_q_f32, path 0: which of the row-resident pre-attention kernel's conditions (premlp.hip) does not hold, by the predicate's name
+// and, where the shapes tell, the reason.  The decision itself is the predicates'; this only words it.
+static std::string premlp_refusal(const PackedMLP& m, const AttnPack& at, const Dims& d, bool fusable, bool rows_ok, bool pre, bool lu_ok,
+                                  const PackedLinear& lu, int act, int D) {
+    std::string r;
+    auto add = [&](const std::string& t) { r += (r.empty() ? "" : "; ") + t; };
+    if (!fusable) {
+        std::string w = "premlp_fusable does not hold";
+        if (!gemm_fp16_flag()) w += " (no split-fp16 guard scope: gemm_variant, knob 0, is not 5)";
+        if (!g_knobs.premlp_fused) w += " (premlp_fused, knob 8, is 0)";
+        if (m.mid.size() != 2) w += " (" + std::to_string(m.mid.size()) + " hidden layers, the kernel has two)";
+        for (int h : m.sizes)
+            if (h != 256) { w += " (hidden width " + std::to_string(h) + ", the kernel's is 256)"; break; }
+        if (m.in_layer.K_pad > 256) w += " (the in_layer's input width k_in pads to " + std::to_string(m.in_layer.K_pad) + " columns, the kernel takes at most 256)";
+        if (d.A_in != 256) w += " (attention input width " + std::to_string(d.A_in) + ", the kernel's is 256)";
+        if (at.q.N_pad != 64) w += " (inner width I = " + std::to_string(d.I) + " pads to " + std::to_string(at.q.N_pad) + " q columns, the kernel writes 64)";
+        bool images = m.in_layer.W2 && m.out_layer.W2 && at.q.W2;
+        for (const PackedLinear& L : m.mid) images = images && L.W2;
+        if (!images) w += " (a layer has no fp16 limb image: a weight beyond fp16's range)";
+        add(w);
+    }
+    if (!rows_ok) add("premlp_rows_ok does not hold");
+    if (pre && !lu_ok) {
+        std::string w = "premlp_lu_fusable does not hold";
+        if (!g_knobs.premlp_lu) w += " (premlp_lu, knob 26, is 0)";
+        if (act != FC_ACT_GELU) w += " (activation code " + std::to_string(act) + ": the pre-layer kernel is instantiated for GELU only)";
+        if (lu.K_pad != 320 || m.in_layer.K_pad != 160)
+            w += " (latent width D = " + std::to_string(D) + " pads to " + std::to_string(lu.K_pad) + " columns, x1 to " + std::to_string(m.in_layer.K_pad) +
+                 ": the pre-layer kernel takes 320 and 160)";
+        if (!lu.W2) w += " (lu has no fp16 limb image: a weight beyond fp16's range)";
+        add(w);
+    }
+    return r.empty() ? "the in_layer reads more columns than the staged panel has" : r;
+}
 }  // namespace fc
 
 extern "C" {
@@ -215,6 +250,122 @@ int fc_op_mlp_hidden_f32(const float* x0, int32_t k0, const float* x1, int32_t k
             throw Error(FC_ERR_INVALID, "fc_op_mlp_hidden_f32: the limb chain is off");
     });
     launch_limb_decode((const unsigned short*)h16.p, out, 512, rows, 512, s);
+    FC_HIP(hipStreamSynchronize(s));
+    FC_API_END
+}
+
+/* diagnostic / test entry (not part of fcflow.h): the query side of ONE attention pre-conditioner by itself (models/cif_block.py:14-20, models/perceiver.py:18-35,
+   104-106): q [rows, I] = LayerNorm(mlp(x)) Wq^T I^-0.5 log2 e, packed by the engine's own code (pack_mlp_mid, pack_plain_linear, fold_q_projection /
+   pack_q_projection / build_lnq of flow_pack.cpp; no K|V fold) and run on the path asked for:
+     path 0  the row-resident kernel premlp_rows_kernel (premlp.hip), or FC_ERR_UNSUPPORTED where the engine's own conditions for it (premlp_fusable,
+             premlp_rows_ok, with a pre-layer premlp_lu_fusable) do not hold -- never another path
+     path 1  separate hidden-layer launches, then out_layer + LayerNorm + q as ONE GEMM (EPI_LNQ) and launch_lnq_finalize
+     path 2  separate hidden layers, out_layer, launch_layernorm, q GEMM
+   The repeat after a raised range flag takes path 2 on the bf16 limbs, as the engine's does.
+   x [rows, ldx] (device): the in_layer reads its first k_in columns; columns k_in .. min(ldx, K_pad) - 1 reach the staged panel as they are (the
+   engine's latent has the first x2 columns there; the packed weights are zero in them), everything beyond and the pad rows are zeros.
+   Tensors (host fp32): net.in_layer.*, net.layers.<i>.*, net.out_layer.*, norm.{weight,bias}, to_q.weight [I, A_in]; optionally the previous flow
+   layer's folded ActNorm + permuter lu.weight [D, D], lu.bias [D], packed as BlockPack::lin: then xprev [rows, D] is read instead of x (k_in = D / 2),
+   xnext [rows, D] = lu(xprev) is written, and path 0 runs the map as the kernel's pre-layer (the other paths: as its own GEMM first). */
+int fc_debug_premlp_q_f32(const float* x, int32_t ldx, int32_t k_in, const fc_tensor* tensors, int32_t n_tensors, const float* xprev, int32_t D,
+                          float* xnext, float* q, int32_t rows, int32_t act, int32_t path, void* stream) {
+    FC_API_BEGIN
+    using namespace fc;
+    const std::string who = "fc_debug_premlp_q_f32: ";
+    if (!q || rows < 1 || k_in < 1) throw Error(FC_ERR_INVALID, who + "bad argument");
+    if (path < 0 || path > 2) throw Error(FC_ERR_INVALID, who + "path must be 0 (the row-resident kernel), 1 (LayerNorm -> q fold GEMM) or 2 (separate launches)");
+    if (act < FC_ACT_NONE || act > FC_ACT_LRELU02) throw Error(FC_ERR_INVALID, who + "unknown activation code");
+    hipStream_t s = (hipStream_t)stream;
+    WeightTable wt(tensors, n_tensors);
+    const bool pre = wt.has("lu.weight");
+    if (pre ? (!xprev || !xnext || D < 2) : (!x || ldx < k_in)) throw Error(FC_ERR_INVALID, who + (pre ? "a pre-layer needs xprev, xnext and D" : "x must have at least k_in columns"));
+    DeviceArena arena;
+    PackedMLP m;
+    AttnPack at;
+    Dims d{};
+    {
+        MatD wq;
+        VecD bq;
+        fold_q_projection(wt, "to_q", "norm", wq, bq);
+        d.I = wq.rows; d.I_pad = pad_inner(d.I); d.A_in = wq.cols; d.A_in_pad = round_up(d.A_in, 32);
+        pack_q_projection(arena, wq, bq, d, at);
+    }
+    pack_mlp_mid(arena, wt, "net", m);
+    const int kp = round_up(k_in, 32);
+    m.in_layer = pack_plain_linear(arena, wt, "net.in_layer", k_in, kp);
+    m.out_layer = pack_plain_linear(arena, wt, "net.out_layer", m.sizes.back(), round_up(m.sizes.back(), 32));
+    if (m.out_layer.N_pad != d.A_in_pad) throw Error(FC_ERR_SHAPE, who + "net.out_layer's output width != to_q's input width");
+    build_lnq(arena, d, wt, "net.out_layer", at);
+    // the pre-layer in the latent's padded layout [x1 | 0-pad | x2 | 0-pad] (flow_pack.cpp build_lin)
+    PackedLinear lu;
+    const int d1 = pre ? D / 2 : 0, d2 = D - d1, d1p = round_up(d1, 32), d2p = round_up(d2, 32), ldl = d1p + d2p;
+    if (pre) {
+        if (k_in != d1) throw Error(FC_ERR_INVALID, who + "with a pre-layer the in_layer reads x1, the first D / 2 latent dims");
+        const std::vector<int> xl = map_xlayout(d1, d1p, d2, d2p);
+        lu = pack_linear(arena, mat_from(wt.get("lu.weight", {D, D})), vec_from(wt.get("lu.bias", {D})), {}, xl, xl, {ldl});
+    }
+    const int rp = round_up(rows, ROW_PAD), lda = pre ? ldl : kp, ldh = std::max({max_hidden_pad(m), d.A_in_pad, 32});
+    const size_t nh = (size_t)rp * ldh;
+    TmpBuf xa((size_t)rp * lda * 4), xp(pre ? (size_t)rp * ldl * 4 : 4), h0(nh * 4), h1(nh * 4), h2(nh * 4), qb((size_t)rp * d.I_pad * 4),
+        lnss((size_t)rp * (d.A_in_pad / 64 + 1) * 4), flag(sizeof(int));
+    launch_fill(xa.f(), 0.f, (size_t)rp * lda, s);
+    if (pre) {
+        launch_fill(xp.f(), 0.f, (size_t)rp * ldl, s);
+        launch_pack_rows(xprev, D, d1, xp.f(), ldl, 0, d1, rows, s);
+        launch_pack_rows(xprev + d1, D, d2, xp.f(), ldl, d1p, d2, rows, s);
+    } else {
+        const int carried = std::min((int)ldx, kp);
+        launch_pack_rows(x, ldx, carried, xa.f(), kp, 0, carried, rows, s);
+    }
+    float* const h[3] = {h0.f(), h1.f(), h2.f()};
+    FC_HIP(hipDeviceSynchronize());                       // (the images were built on the null stream)
+    int pass = 0;
+    run_fp16_guarded((int*)flag.p, s, [&] {
+        const int pth = pass++ > 0 ? 2 : path;            // the repeat after a raised range flag: separate launches on the bf16 limbs
+        const ASeg in{xa.f(), lda};
+        if (pth == 0) {
+            const bool fusable = premlp_fusable(m.in_layer, m.mid, m.out_layer, at.q), rows_ok = premlp_rows_ok(rp, d.I_pad, qb.f(), h0.f(), nh),
+                       lu_ok = pre && premlp_lu_fusable(lu, m.in_layer, act, lda);
+            if (!fusable || lda < m.in_layer.K_pad || !rows_ok || (pre && !lu_ok))
+                throw Error(FC_ERR_UNSUPPORTED, who + "path 0 asks for the row-resident kernel, which does not take this chain: " +
+                                                premlp_refusal(m, at, d, fusable, rows_ok, pre, lu_ok, lu, act, D));
+            launch_premlp(xa.f(), lda, m.in_layer, m.mid, m.out_layer, at.q, act, qb.f(), d.I_pad, rp, rows, s, h0.f(), nh, pre ? &lu : nullptr,
+                          pre ? xp.f() : nullptr);
+            return;
+        }
+        if (pre) {
+            const ASeg ax{xp.f(), ldl};
+            GemmEpi e{};
+            e.C = xa.f(); e.ldc = ldl; e.rows_valid = rows;
+            launch_gemm(lu, &ax, rp, e, EPI_LINEAR, s);
+        }
+        const int cur = run_mlp_hidden_generic(m, &in, nullptr, act, h, ldh, rp, s, rows);
+        const ASeg a{h[cur], ldh};
+        if (pth == 1) {
+            if (!at.has_lnq || !gemm_lnq_ok())
+                throw Error(FC_ERR_UNSUPPORTED, who + "path 1 asks for the LayerNorm -> q fold GEMM, which does not take this chain (build_lnq's shapes, lnq_fold (knob 10), a split-fp16 guard scope)");
+            GemmEpi e{};
+            e.C = qb.f(); e.ldc = d.I_pad; e.d2 = d.A_in; e.ldj_part = lnss.f(); e.ldj_pitch = (size_t)rp; e.rows_valid = rows;
+            launch_gemm(at.lnq, &a, rp, e, EPI_LNQ, s);
+            launch_lnq_finalize(qb.f(), d.I_pad, lnss.f(), d.A_in / 64, (size_t)rp, d.A_in, at.q_bias, rows, s);
+            return;
+        }
+        int o = 0;
+        while (o == cur) ++o;
+        GemmEpi e{};
+        e.C = h[o]; e.ldc = ldh; e.rows_valid = rows;
+        launch_gemm(m.out_layer, &a, rp, e, EPI_LINEAR, s);
+        launch_layernorm(h[o], ldh, d.A_in, rows, s);
+        const ASeg aq{h[o], ldh};
+        GemmEpi eq{};
+        eq.C = qb.f(); eq.ldc = d.I_pad; eq.rows_valid = rows;
+        launch_gemm(at.q, &aq, rp, eq, EPI_LINEAR, s);
+    });
+    launch_pack_rows(qb.f(), d.I_pad, d.I, q, d.I, 0, d.I, rows, s);
+    if (pre) {
+        launch_pack_rows(xa.f(), ldl, d1, xnext, D, 0, d1, rows, s);
+        launch_pack_rows(xa.f() + d1p, ldl, d2, xnext, D, d1, d2, rows, s);
+    }
     FC_HIP(hipStreamSynchronize(s));
     FC_API_END
 }

@@ -591,6 +591,33 @@ def op_mlp_hidden(x0, x1, state_dict, rowscal=None, act="gelu", use_rows=True):
     return out
 
 
+def op_premlp_q(x, state_dict, act="gelu", path=0, k_in=None, xprev=None):
+    """The query side of one attention pre-conditioner by itself (fc_debug_premlp_q_f32): q [rows, I] = LayerNorm(mlp(x)) Wq^T I^-0.5 log2 e,
+    packed by the engine's own code.  x [rows, ldx]: the in_layer reads its first k_in columns (default: all), the columns behind them up to
+    the padded width travel as they are.  `state_dict`: net.in_layer / net.layers.<i> / net.out_layer, norm.{weight,bias}, to_q.weight.
+    path 0 = the row-resident kernel (FcError FC_ERR_UNSUPPORTED where it does not apply: never another path), 1 = separate hidden
+    layers + the LayerNorm -> q fold GEMM, 2 = separate launches throughout.
+    With lu.weight [D, D] / lu.bias [D] in `state_dict` (a folded ActNorm + permuter) and xprev [rows, D], x is not read (pass None):
+    xnext = lu(xprev) is the latent, k_in = D // 2, and (q, xnext) is returned; path 0 then runs the map as the kernel's pre-layer."""
+    code = OP_ACTS[act]
+    pre = "lu.weight" in state_dict
+    if pre != (xprev is not None):
+        raise RuntimeError("op_premlp_q: the pre-layer takes both lu.weight / lu.bias in state_dict and xprev")
+    src = _dev_f32(xprev if pre else x)
+    rows, width = src.shape
+    if k_in is None:
+        k_in = width // 2 if pre else width
+    inner = state_dict["to_q.weight"].shape[0]
+    q = torch.empty(rows, inner, dtype=torch.float32, device=src.device)
+    xnext = torch.empty(rows, width, dtype=torch.float32, device=src.device) if pre else None
+    arr, keep = _tensor_table({k: v.detach().cpu() for k, v in state_dict.items()})
+    with torch.cuda.device(src.device):
+        _errcheck(lib().fc_debug_premlp_q_f32(None if pre else _ptr(src), 0 if pre else width, int(k_in), arr, len(arr), _ptr(src) if pre else None,
+                                              width if pre else 0, _ptr(xnext), _ptr(q), rows, code, int(path), _stream()))
+    del keep
+    return (q, xnext) if pre else q
+
+
 def op_attention(q, k, v, scale):
     q, k, v = _dev_f32(q), _dev_f32(k), _dev_f32(v)
     B, N, D = q.shape

@@ -329,7 +329,8 @@ def test_row_resident_pre_attention_kernel_other_widths_and_activations(latent_d
     """The shipped pre-attention chain kernel (activations in registers, csrc/premlp.hip) away from the C2 shape it is specialised for:
     x1 widths 100 / 150 / 132 columns (k padded to 128 / 160 / 160: the in_layer's k steps read at run time or compile time, weight
     rows of 32 / 40 sixteen-byte chunks with their two swizzle masks and piece-to-row maps) and the three activations the reference
-    accepts, against the separate GEMM launches."""
+    accepts, against the separate GEMM launches.  K_pad 128 and 160 are all this test reaches, and through three flow layers; the kernel alone
+    against fp64 at every K_pad from 32 to 256, all five activation codes and odd row counts is tests/test_gpu_premlp.py."""
     cfg = fa.named_config("c2_dgcnn_attn_spline", n_flow_layers=3, sample_size=300, latent_dim=latent_dim, coupling_block_nonlinearity=act)
     torch.manual_seed(31)
     md = fa.initialize_flow(cfg, device=DEV, mode="test")

@@ -22,8 +22,10 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # without it (28.2 -> 27.7 ms per C2 step, same box); the GEMM kernels (gemm_*.hip) are 1 % FASTER with the packing and keep it.  Developer option for same-box A/B runs:
 # FC_EXTRA_FLAGS="attention.hip:-fno-slp-vectorize;gemm_split.hip:-fno-slp-vectorize" adds flags to single files.
 EXTRA_FLAGS = {"premlp.hip": ["-fno-slp-vectorize"], "attention.hip": ["-fno-slp-vectorize"],
-               # mlprows.hip: the epilogue is hand-placed in micro-steps behind single MFMAs; SLP packing merges steps of different slots
-               "mlprows.hip": ["-fno-slp-vectorize"]}
+               # mlprows.hip: the epilogue is hand-placed in micro-steps behind single MFMAs; SLP packing merges steps of different slots.
+               # -amdgpu-mfma-vgpr-form: MFMA accumulators in architectural VGPRs (a one-wave-per-SIMD kernel gets them in AGPRs by default,
+               # and the epilogue, all VALU, then reads each one back with a v_accvgpr_read); the input fragments take the AGPRs
+               "mlprows.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # (spline_wide.hip: measured both ways on one box, profiles/r04D_*: 68.1 against 68.5 ms per C2 step, training step 1052 against 1050 ms -- no flag)
 for _kv in os.environ.get("FC_EXTRA_FLAGS", "").split(";"):
     if ":" in _kv:

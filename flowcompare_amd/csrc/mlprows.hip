@@ -63,6 +63,18 @@ template <int N>
 __device__ __forceinline__ void mr_wait_vm(u32x4& a, u32x4& b) {
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
 }
+// The same pair for a B fragment that lives in AGPRs from the load to its last MFMA (a VMEM load may target either half of the register
+// file, and an MFMA reads its B operand from either): no v_accvgpr_write between the two.
+__device__ __forceinline__ f16x8 mr_gload16_acc(const char* ptr) {
+    f16x8 r;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(r) : "v"(ptr) : "memory");
+    return r;
+}
+__device__ __forceinline__ void mr_pin_acc(f16x8& x) { asm volatile("" : "+a"(x)); }      // a fragment the VALU produced: moved over once
+template <int N>
+__device__ __forceinline__ void mr_wait_vm_acc(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
+    asm volatile("s_waitcnt vmcnt(%4)" : "+a"(a), "+a"(b), "+a"(c), "+a"(d) : "n"(N) : "memory");
+}
 __device__ __forceinline__ floatx4 mr_lds_read16(unsigned addr) {
     floatx4 r;
     asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
@@ -138,44 +150,48 @@ void mlp_rows_kernel(const MlpRowsParams p) {
 
     f16x8 xin[MR_HID / 16][2];                                          // this wave's input rows as B fragments: [k-step][hi | lo']
     float omax = 0.f;
-    // The first MR_XA k-steps of xin are pinned to AGPRs (an MFMA reads its B operand from either file): the wave needs ~450 registers, the
-    // accumulators (AGPR form) take 64 AGPRs, and left alone the allocator keeps xin in VGPRs and SPILLS a part of it to AGPRs -- four
-    // v_accvgpr_read per k-step in front of the MFMAs.
-    constexpr int MR_XA = 24;
-    auto pin_xin = [&](int ks) __attribute__((always_inline)) {
-#pragma unroll
-        for (int s = 0; s < MR_HID / 16; ++s)
-            if (s < MR_XA && s < ks) { asm volatile("" : "+a"(xin[s][0])); asm volatile("" : "+a"(xin[s][1])); }
-    };
+    // The register file is split by use: xin, which only loads write and only MFMAs read (as their B operand, from either file), fills the
+    // 256 AGPRs; the accumulators are VGPRs (the file is built with the MFMAs' VGPR form, build.py), so that the epilogue's VALU works on
+    // them in place and no v_accvgpr_read / v_accvgpr_write stands between an MFMA and its epilogue.  Layer 0's fragments are split from
+    // fp32 rows on the VALU and moved over once per launch (mr_pin_acc); the later layers' are loaded into AGPRs directly (mr_gload16_acc).
 
     // ---------------------------------------------------------------- layer 0 input: fp32 segments -> limb fragments
+    // (MR_CH k-steps at a time: a chunk's fp32 rows, 8 registers per k-step, are dead before the next chunk's arrive -- the whole of a 32-k-step
+    // input at once, 256 registers of rows beside the fragments they become, spilled to scratch)
     {
         const int k0 = p.segk[0], k1 = k0 + p.segk[1], k2 = k1 + p.segk[2];
-        float4 raw[KS0][2];
+        constexpr int MR_CH = KS0 == 16 ? 16 : 8;
+        static_assert(KS0 % MR_CH == 0, "layer 0 is padded to a whole stage");
+        static_for<(KS0 + MR_CH - 1) / MR_CH>([&](auto c_tag) __attribute__((always_inline)) {
+            constexpr int c0 = decltype(c_tag)::value * MR_CH, cn = KS0 - c0 < MR_CH ? KS0 - c0 : MR_CH;
+            float4 raw[cn][2];
 #pragma unroll
-        for (int s = 0; s < KS0; ++s) {
-            const int seg = s < k0 ? 0 : (s < k1 ? 1 : 2);
-            const int sl = s - (seg == 0 ? 0 : (seg == 1 ? k0 : k1));
-            const bool live = s < k2;
-            const float* ptr = p.A[live ? seg : 0] + (size_t)row_in * p.lda[live ? seg : 0] + (live ? sl : 0) * 16 + 8 * lh;
-            raw[s][0] = *reinterpret_cast<const float4*>(ptr);
-            raw[s][1] = *reinterpret_cast<const float4*>(ptr + 4);
-            if (!live) { raw[s][0] = make_float4(0.f, 0.f, 0.f, 0.f); raw[s][1] = raw[s][0]; }
-        }
-#pragma unroll
-        for (int s = 0; s < KS0; ++s) {
-            const float x[8] = {raw[s][0].x, raw[s][0].y, raw[s][0].z, raw[s][0].w, raw[s][1].x, raw[s][1].y, raw[s][1].z, raw[s][1].w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                omax = fmaxf(omax, fabsf(x[e]));
-                const _Float16 h = (_Float16)x[e];
-                xin[s][0][e] = h;
-                xin[s][1][e] = (_Float16)((x[e] - (float)h) * 2048.0f);
+            for (int i = 0; i < cn; ++i) {
+                const int s = c0 + i;
+                const int seg = s < k0 ? 0 : (s < k1 ? 1 : 2);
+                const int sl = s - (seg == 0 ? 0 : (seg == 1 ? k0 : k1));
+                const bool live = s < k2;
+                const float* ptr = p.A[live ? seg : 0] + (size_t)row_in * p.lda[live ? seg : 0] + (live ? sl : 0) * 16 + 8 * lh;
+                raw[i][0] = *reinterpret_cast<const float4*>(ptr);
+                raw[i][1] = *reinterpret_cast<const float4*>(ptr + 4);
+                if (!live) { raw[i][0] = make_float4(0.f, 0.f, 0.f, 0.f); raw[i][1] = raw[i][0]; }
             }
-        }
+            static_for<cn>([&](auto i_tag) __attribute__((always_inline)) {
+                constexpr int i = decltype(i_tag)::value, s = c0 + i;
+                const float x[8] = {raw[i][0].x, raw[i][0].y, raw[i][0].z, raw[i][0].w, raw[i][1].x, raw[i][1].y, raw[i][1].z, raw[i][1].w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    omax = fmaxf(omax, fabsf(x[e]));
+                    const _Float16 h = (_Float16)x[e];
+                    xin[s][0][e] = h;
+                    xin[s][1][e] = (_Float16)((x[e] - (float)h) * 2048.0f);
+                }
+            });
+#pragma unroll
+            for (int i = 0; i < cn; ++i) { mr_pin_acc(xin[c0 + i][0]); mr_pin_acc(xin[c0 + i][1]); }
+            asm volatile("" : "+v"(omax));                                // (or the maxima are taken at the end, from rows kept alive for them)
+        });
     }
-
-    pin_xin(KS0);
 
     // one block of 32 output features over NSB stages; the previous block's accumulators (pa, pc) are finished meanwhile
     floatx16 accA, corrA, accB, corrB;
@@ -450,12 +466,14 @@ void mlp_rows_kernel(const MlpRowsParams p) {
         __builtin_amdgcn_s_barrier();                                        // every wave is done with the previous layer's bias (its last read sits behind that layer's last stage barrier)
         stage_bias(l);
         const char* src = reinterpret_cast<const char*>(p.hbuf[p.L[l].in]) + band * band_bytes + lane * 16;
+        // straight into AGPRs: 64 loads in flight, one drain (the first names the count; every fragment is tied to a wait)
 #pragma unroll
         for (int s = 0; s < MR_HID / 16; ++s) {
-            xin[s][0] = *reinterpret_cast<const f16x8*>(src + (size_t)(2 * s) * 1024);
-            xin[s][1] = *reinterpret_cast<const f16x8*>(src + (size_t)(2 * s + 1) * 1024);
+            xin[s][0] = mr_gload16_acc(src + (size_t)(2 * s) * 1024);
+            xin[s][1] = mr_gload16_acc(src + (size_t)(2 * s + 1) * 1024);
         }
-        pin_xin(MR_HID / 16);
+#pragma unroll
+        for (int s = 0; s < MR_HID / 16; s += 2) mr_wait_vm_acc<0>(xin[s][0], xin[s][1], xin[s + 1][0], xin[s + 1][1]);
         if (p.L[l].res >= 0) run_layer(std::integral_constant<int, MR_HID / 16>{}, std::true_type{}, std::false_type{}, l);
         else run_layer(std::integral_constant<int, MR_HID / 16>{}, std::false_type{}, std::false_type{}, l);
     }

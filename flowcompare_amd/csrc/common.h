@@ -230,7 +230,7 @@ bool guard_deferred();
 int guard_pending();
 void guard_set_deferred(bool on);
 int guard_resolve();              // returns the number of passes it repeated
-// Training primitives (train.hip): the CALLER owns the overflow flag for a whole optimisation step (forward and backward run on
+// Training primitives (train_linear.hip, train_wgrad.hip): the CALLER owns the overflow flag for a whole optimisation step (forward and backward run on
 // different host threads under torch.autograd), so the scope only lends it to launch_gemm for one call -- no reset, no wait.
 struct Fp16FlagScope {
     explicit Fp16FlagScope(int* dev_flag);
@@ -291,7 +291,7 @@ void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStre
 void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s);
 void one_acc_gemm_debug(const float* x, const float* W, const float* bias, float wmax, float* out, int rows, int N, int K, hipStream_t s);   // fc_debug_one_acc_gemm_f32
 bool gemm_spline_wide_on();      // spline_kernel (knob 13) = 5 (shipped): launch_gemm routes eligible EPI_SPLINE launches there
-// the same 256 x 256 main loop for the wide Linear layers of a TRAINING step (train.hip: the spline parameter layer's forward and its data
+// the same 256 x 256 main loop for the wide Linear layers of a TRAINING step (train_linear.hip: the spline parameter layer's forward and its data
 // gradient): the point operand is an fp32 panel, split into limbs after its LDS read; C = (A W^T + bias (+ addend)) (* act'(gradu))
 constexpr int kTrainWideWExp = 11;         // weights of those layers are stored as hi + lo of w 2^11 (|w| < 32; the pack kernel raises the range flag beyond)
 struct TrainWideArgs {

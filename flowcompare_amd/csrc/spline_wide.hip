@@ -55,7 +55,7 @@ struct SplineWideParams {
     int* ovf;                    // split-fp16 range flag (common.h Fp16Guard; EPI 3)
     // EPI 2 (plain product, fc_debug_one_acc_gemm_f32: the one-accumulator limb form by itself, for the accuracy test)
     float* C; int ldc;
-    // EPI 3 (training Linear, csrc/train.hip): the point operand is an fp32 PANEL [rows][lda] that is split into limbs after its LDS read
+    // EPI 3 (training Linear, csrc/train_linear.hip): the point operand is an fp32 PANEL [rows][lda] that is split into limbs after its LDS read
     // (a k32 step of a row is 128 bytes either way), scaled by a_scale or, for gradients, per row so that the row's maximum lands in
     // [2^13, 2^14) (row_absmax: max |a| of every row, written by the producing kernel); C = (acc / scale (+ addend)) (* act'(gradu))
     const float* A32; int lda;
@@ -611,7 +611,7 @@ void one_acc_gemm_debug(const float* x, const float* W, const float* bias, float
 
 namespace fc {
 
-// ---------------------------------------------------------------- EPI 3: the wide Linear layers of a training step (train.hip)
+// ---------------------------------------------------------------- EPI 3: the wide Linear layers of a training step (train_linear.hip)
 
 void launch_train_wide(const TrainWideArgs& a, hipStream_t s) {
     if (!a.A || !a.W1 || !a.C || a.K_pad < 64 || a.K_pad % 64 != 0 || a.rows_pad < 256 || a.rows_pad % 256 != 0 || a.n_cols < 4 || a.n_cols % 4 != 0 ||

@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdParams p) {
 // Operands as fp16 limbs (x ~ hi + lo'/2048, gemm.hip), 3 x v_mfma_f32_32x32x16_f16 per product block: hi.hi into `main`, hi.lo' and lo'.hi into
 // `cross`.  K / V (dq kernel) and Q / dO (dk/dv kernel) tiles are converted once per tile while they are staged into LDS, row-major
 // [32 rows][hi 64 | lo' 64]; a product that contracts over the head dim reads them as they lie (16 bytes per lane), a product that
-// contracts over the tile's rows reads them through ds_read_b64_tr_b16 (attention.hip, train.hip), whose row order per lane,
+// contracts over the tile's rows reads them through ds_read_b64_tr_b16 (attention.hip, train_wgrad.hip), whose row order per lane,
 // {4h..4h+3, 8+4h..8+4h+3} + 16 j, is exactly the row order of accumulator registers 8j..8j+7 -- so P^T / dS^T go from the
 // accumulators into the next MFMA's B operand after a limb split only.
 typedef short v4i16 __attribute__((ext_vector_type(4)));

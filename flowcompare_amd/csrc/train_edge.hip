@@ -2,7 +2,7 @@
 //     y_ij = W cat(f_j - f_i, f_i)  ->  BatchNorm2d with BATCH statistics over (scene, point, neighbour)  ->  LeakyReLU(slope)  ->  max over the k neighbours
 // (slope 0.2 for the DGCNN; slope 0 = ReLU for the PAConv embedder's BatchNorm + ReLU (+ max over the 32 neighbours), train_paconv.hip)
 // forward and backward.  By linearity y_ij = P[idx_ij] + Q[i] with P = f Wa^T, Q = f (Wb - Wa)^T (W = [Wa | Wb]), so the [points, k, C]
-// edge tensor is never formed by a GEMM: the two per-point products come from the training Linear (train.hip) and these kernels gather.
+// edge tensor is never formed by a GEMM: the two per-point products come from the training Linear (train_linear.hip) and these kernels gather.
 // With idx == NULL (k = 1, identity) and Q == NULL the same kernels are BatchNorm1d + LeakyReLU on a [points, C] matrix (conv5).
 //
 //   edge_stats    per-channel sum and sum of squares of y over all (i, j), fp64 accumulators, chunked + fixed-order reduce

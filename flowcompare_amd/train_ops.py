@@ -1,5 +1,5 @@
 """Training path, first slice: the residual MLP of models/nets.py:19-30 as torch.autograd Functions whose
-forward AND backward are HIP kernels behind the C ABI (include/fcflow.h, fc_train_*; kernels in csrc/train.hip + the GEMM of the
+forward AND backward are HIP kernels behind the C ABI (include/fcflow.h, fc_train_*; kernels in csrc/train_linear.hip, train_wgrad.hip + the GEMM of the
 inference path).  torch is plumbing: it owns the tensors, the stream and the autograd graph between the primitives; there is no
 PyTorch arithmetic on activations here and no CPU fallback.
 
@@ -190,14 +190,13 @@ def _linear_fwd(pack, N, widths, xs, rows_pad, residual, act, s):
     u = torch.empty(rows_pad, N_pad, dtype=torch.float32, device=pack.device)
     segs, ldx = _segs(widths), _segs([x.shape[1] for x in xs])
     ldr = 0 if residual is None else residual.shape[1]
+    head = (engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual), ldr, engine._ptr(u))
     if act:
         y = torch.empty_like(u)
-        L.fc_train_linear_act_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual), ldr,
-                                      engine._ptr(u), engine._ptr(y), N_pad, act, _flag_ptr(), s)
+        L.fc_train_linear_act_fwd_f32(*head, engine._ptr(y), N_pad, act, _flag_ptr(), s)
     else:
         y = u
-        L.fc_train_linear_fwd_f32(engine._ptr(pack), N, segs, len(widths), _ptr_array(xs), ldx, rows_pad, engine._ptr(residual), ldr,
-                                  engine._ptr(u), N_pad, _flag_ptr(), s)
+        L.fc_train_linear_fwd_f32(*head, N_pad, _flag_ptr(), s)
     return u, y
 
 
@@ -217,17 +216,27 @@ def _linear_wgrad(N, K, widths, du, xs, rows, want_dW, want_db, wdtype, s):
     return (None if dW is None else dW.to(wdtype)), db
 
 
-def _linear_dgrad(pack, N, widths, du, rows_pad, rowmax, xs, need, s):
-    """The gradient panel of every input panel whose `need` is set (None for the others): du W into one [rows_pad, K_pad] buffer, cut
-    per segment.  `rowmax`: the row maxima of `du` (_rowmax_for) or None."""
-    dxs = [None] * len(xs)
-    if not any(need):
-        return dxs
+def _linear_dgrad(pack, N, widths, du, rows_pad, rowmax, s, addend=None, u_prev=None, act=0):
+    """du W as one [rows_pad, K_pad] buffer.  With u_prev / act (one segment): (du W + addend) * act'(u_prev),
+    the pre-activation gradient of the layer that produced this one's input, `addend` (or None) being its residual branch's gradient.
+    `rowmax`: the row maxima of `du` (_rowmax_for) or None."""
     L = engine.lib()
     K_pad = sum(_round_up(w, 32) for w in widths)
     dx = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=du.device)
-    L.fc_train_linear_dgrad_f32(engine._ptr(pack), N, _segs(widths), len(widths), engine._ptr(du), _round_up(N, 32), rows_pad,
-                                engine._ptr(dx), K_pad, engine._ptr(rowmax), _flag_ptr(), s)
+    head = (engine._ptr(pack), N, _segs(widths), len(widths), engine._ptr(du), _round_up(N, 32), rows_pad, engine._ptr(dx), K_pad)
+    if u_prev is None:
+        L.fc_train_linear_dgrad_f32(*head, engine._ptr(rowmax), _flag_ptr(), s)
+    else:
+        L.fc_train_linear_dgrad_act_f32(*head, engine._ptr(addend), engine._ptr(u_prev), act, engine._ptr(rowmax), _flag_ptr(), s)
+    return dx
+
+
+def _input_grads(pack, N, widths, du, rows_pad, rowmax, xs, need, s):
+    """The gradient panel of every input panel whose `need` is set (None for the others): du W (_linear_dgrad), cut per segment."""
+    dxs = [None] * len(xs)
+    if not any(need):
+        return dxs
+    dx = _linear_dgrad(pack, N, widths, du, rows_pad, rowmax, s)
     off = 0
     for i, (x, w) in enumerate(zip(xs, widths)):
         wp = _round_up(w, 32)
@@ -241,7 +250,7 @@ def _linear_dgrad(pack, N, widths, du, rows_pad, rowmax, xs, need, s):
 
 
 class LinearActFn(torch.autograd.Function):
-    """y = act(cat(x...) W^T + b (+ residual)) on panels; forward and backward are HIP kernels (csrc/train.hip)."""
+    """y = act(cat(x...) W^T + b (+ residual)) on panels; forward and backward are HIP kernels (csrc/train_linear.hip, train_wgrad.hip)."""
 
     @staticmethod
     def forward(ctx, weight, bias, residual, act, rows, widths, *xs):
@@ -284,13 +293,21 @@ class LinearActFn(torch.autograd.Function):
                 du = dy
             rowmax = _rowmax_for(du)
             dW, db = _linear_wgrad(N, K, widths, du, xs, rows, need[0], has_bias and need[1], wdtype, s)
-            dxs = _linear_dgrad(pack, N, widths, du, rows_pad, rowmax, xs, need[6:], s)
+            dxs = _input_grads(pack, N, widths, du, rows_pad, rowmax, xs, need[6:], s)
         return (dW, db, du if (has_res and need[2]) else None, None, None, None, *dxs)
 
 
 def linear_act(xs, widths, weight, bias, rows, act=None, residual=None):
     """act(cat(xs) W^T + b + residual) on panels; `widths` = true widths of the input panels, `rows` = valid rows."""
     return LinearActFn.apply(weight, bias, residual, _act_id(act), rows, tuple(widths), *xs)
+
+
+def _residual_role(l, nl):
+    """models/nets.py:19-30 for layer l of nl (in_layer, the hidden layers, out_layer) -> (this layer stores its input as `keep`, this layer
+    adds `keep` to its product).  The hidden layers alternate, the first one keeping; in_layer and out_layer do neither."""
+    hidden = 0 < l < nl - 1
+    odd = (l - 1) % 2 == 1
+    return hidden and not odd, hidden and odd
 
 
 class MlpFn(torch.autograd.Function):
@@ -317,12 +334,11 @@ class MlpFn(torch.autograd.Function):
                 if sum(cur_w) != K:
                     raise RuntimeError(f"MlpFn: layer {l} reads {K} features, its input panels hold {cur_w}")
                 pack = _linear_pack(W, b, cur_w, dev, s)
-                h = l - 1                                             # hidden index: even -> keep = input, odd -> residual = keep
                 last = l == nl - 1
-                residual = keep if (0 < l < nl - 1 and h % 2 == 1) else None
-                if 0 < l < nl - 1 and h % 2 == 0:
+                keeps, adds = _residual_role(l, nl)
+                if keeps:
                     keep = cur[0]
-                u, y = _linear_fwd(pack, N, cur_w, cur, rows_pad, residual, 0 if last else act, s)     # out_layer has no activation
+                u, y = _linear_fwd(pack, N, cur_w, cur, rows_pad, keep if adds else None, 0 if last else act, s)     # out_layer has no activation
                 packs.append(pack); us.append(None if last else u); ys.append(y)
                 metas.append((N, K, tuple(cur_w), b is not None, W.dtype))
                 cur, cur_w = [y], [N]
@@ -332,7 +348,6 @@ class MlpFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        L = engine.lib()
         rows, act, widths, nx, nl, metas = ctx.meta
         sv = ctx.saved_tensors
         xs, packs = sv[:nx], sv[nx:nx + nl]
@@ -343,7 +358,7 @@ class MlpFn(torch.autograd.Function):
         grads = [None] * (4 + nx + 2 * nl)
         du = dy.contiguous()                                             # out_layer has no activation
         rowmax = _rowmax_for(du)                                         # row maxima of the incoming panel: the last layer's data gradient alone
-        du_next = None                                                   # du of layer l + 1 (the residual branch's gradient when l is an even hidden layer)
+        du_next = None                                                   # du of layer l + 1 (the residual branch's gradient when that layer added `keep`)
         with _OnDevice(dev):
             s = engine._stream()
             for l in range(nl - 1, -1, -1):
@@ -352,16 +367,13 @@ class MlpFn(torch.autograd.Function):
                 wi = 4 + nx + 2 * l
                 grads[wi], grads[wi + 1] = _linear_wgrad(N, K, in_w, du, ins, rows, need[wi], has_bias and need[wi + 1], wdtype, s)
                 if l == 0:
-                    grads[4:4 + nx] = _linear_dgrad(packs[0], N, in_w, du, rows_pad, rowmax if l == nl - 1 else None, xs, need[4:4 + nx], s)
+                    grads[4:4 + nx] = _input_grads(packs[0], N, in_w, du, rows_pad, rowmax, xs, need[4:4 + nx], s)
                     break
-                # gradient w.r.t. the previous layer's pre-activation: (du . W + [residual branch]) * act'(u_{l-1})
-                h = l - 1
-                addend = du_next if (l < nl - 1 and h % 2 == 0 and l + 1 < nl - 1) else None
-                K_pad = _round_up(K, 32)
-                du_prev = torch.empty(rows_pad, K_pad, dtype=torch.float32, device=dev)
-                L.fc_train_linear_dgrad_act_f32(engine._ptr(packs[l]), N, _segs(in_w), 1, engine._ptr(du), _round_up(N, 32), rows_pad, engine._ptr(du_prev),
-                                                K_pad, engine._ptr(addend), engine._ptr(us[l - 1]), act, engine._ptr(rowmax if l == nl - 1 else None), _flag_ptr(), s)
-                du_next, du = du, du_prev
+                # gradient w.r.t. the previous layer's pre-activation: (du . W + [residual branch]) * act'(u_{l-1}); the branch exists when
+                # layer l + 1 added `keep`, which is this layer's input
+                addend = du_next if _residual_role(l + 1, nl)[1] else None
+                du_next, du = du, _linear_dgrad(packs[l], N, in_w, du, rows_pad, rowmax, s, addend, us[l - 1], act)
+                rowmax = None                                            # (the panels computed here carry no row maxima)
         return tuple(grads)
 
 
@@ -379,13 +391,11 @@ def mlp_panels(mlp, xs, widths, rows, act):
         return MlpFn.apply(rows, act_id, tuple(widths), len(xs), *xs, *params)
     x = linear_act(xs, widths, mlp.in_layer.weight, mlp.in_layer.bias, rows, act)
     keep = None
-    for i, layer in enumerate(mlp.layers):
-        w = layer.in_features
-        if i % 2 == 0:
+    for l, layer in enumerate(mlp.layers, 1):
+        keeps, adds = _residual_role(l, len(mlp.layers) + 2)
+        if keeps:
             keep = x
-            x = linear_act([x], [w], layer.weight, layer.bias, rows, act)
-        else:
-            x = linear_act([x], [w], layer.weight, layer.bias, rows, act, residual=keep)
+        x = linear_act([x], [layer.in_features], layer.weight, layer.bias, rows, act, residual=keep if adds else None)
     return linear_act([x], [mlp.out_layer.in_features], mlp.out_layer.weight, mlp.out_layer.bias, rows, None)
 
 

@@ -52,6 +52,41 @@ def test_linear_act_forward_and_backward_match_fp64(rows, widths, N, act, res, f
     assert yp[:, N:].abs().sum().item() == 0.0                              # pad columns stay zero (zero weights and bias, act(0) = 0)
 
 
+@pytest.mark.parametrize("config", ["frozen_weight", "no_bias", "second_input_only"])
+def test_linear_act_computes_only_the_requested_gradients(config):
+    """linear_act on 300 rows (one full 256-row tile and a partial one), segments [40, 33], N = 72, GELU, under step_guard, when only some
+    gradients are asked for: weight frozen and bias trainable (the bias-only column-sum branch of the weight-gradient entry); bias=None
+    (dW without db); only the second input requires grad (no weight-gradient call, one panel cut out of the data gradient).  Every
+    requested gradient against fp64 autograd at the gate of test_linear_act_forward_and_backward_match_fp64, every other one None."""
+    rows, widths, N = 300, [40, 33], 72
+    K = sum(widths)
+    g = torch.Generator().manual_seed(31)
+    host = dict(W=torch.randn(N, K, generator=g) / K ** 0.5, b=torch.randn(N, generator=g) * 0.3,
+                x0=torch.randn(rows, widths[0], generator=g), x1=torch.randn(rows, widths[1], generator=g))
+    dy = torch.randn(rows, N, generator=g)
+    if config == "no_bias":
+        del host["b"]
+    wanted = dict(W=config == "no_bias", b=config == "frozen_weight", x0=config != "second_input_only", x1=True)
+    ref = {k: t.double().requires_grad_(True) for k, t in host.items()}
+    yo = F.gelu(F.linear(torch.cat((ref["x0"], ref["x1"]), -1), ref["W"], ref.get("b")))
+    yo.backward(dy.double())
+
+    dev = {k: t.to(DEV).requires_grad_(wanted[k]) for k, t in host.items()}
+    with T.step_guard(device=DEV) as guard:
+        yp = T.linear_act([T.to_panel(dev["x0"]), T.to_panel(dev["x1"])], widths, dev["W"], dev.get("b"), rows, "GELU")
+        out = T.from_panel(yp, rows, N)
+        out.backward(dy.to(DEV))
+        assert not guard.overflowed()
+    errs = dict(y=_rel(out.detach(), yo.detach()))
+    for k, t in dev.items():
+        if wanted[k]:
+            errs["d" + k] = _rel(t.grad, ref[k].grad)
+        else:
+            assert t.grad is None, k
+    print(f"linear_act {config}: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()))
+    assert max(errs.values()) < 5e-6, errs
+
+
 def test_weight_gradient_is_bit_reproducible_and_ignores_pad_rows():
     g = torch.Generator().manual_seed(5)
     rows, K, N = 1000, 150, 256
@@ -275,7 +310,7 @@ def test_spline_forward_and_backward_match_oracle_autograd(K, d2, rows, spread):
 @pytest.mark.parametrize("rows,grad_scale", [(700, 1.0), (1000, 1e-5), (300, 300.0)])
 def test_spline_parameter_layer_on_the_wide_loop_matches_fp64_and_the_fp32a_loop(rows, grad_scale):
     """Round 4: in a training step the spline parameter layer (512 -> 3750, models/spline_coupling.py:187-210 behind models/nets.py:19-30) runs its
-    forward and its data gradient on the 256 x 256 one-accumulator loop (csrc/spline_wide.hip EPI 3; csrc/train.hip routes layers with at
+    forward and its data gradient on the 256 x 256 one-accumulator loop (csrc/spline_wide.hip EPI 3; csrc/train_linear.hip routes layers with at
     least 1024 outputs): activations are split into limbs after their LDS read at a constant scale, the gradient panel at one exact
     power-of-two scale PER ROW taken from the row maxima the spline backward writes beside it.  Coupling net + spline + backward against
     fp64 autograd through the pinned oracle, no worse than the fp32-A loop (debug knob 31 = 0) -- at gradient magnitudes of a loss that is

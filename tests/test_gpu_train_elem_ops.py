@@ -1,5 +1,5 @@
 """The flow's element training operators one by one (csrc/train_elem.hip through train_ops.AffineFn / GaussDrawFn / NormalLogProbFn /
-BaseDensityFn / ExpmCouplingFn and the C entries fc_train_expm_fwd_f32 / fc_train_expm_bwd_f32; csrc/train.hip through
+BaseDensityFn / ExpmCouplingFn and the C entries fc_train_expm_fwd_f32 / fc_train_expm_bwd_f32; csrc/train_wgrad.hip and train_linear.hip through
 fc_train_colsum_f32, fc_train_act_fwd_f32 and fc_train_act_bwd_f32): forward and backward element-wise against the plain fp64 references
 of tests/elem_ops_ref.py (pinned to the oracle by test_oracle_elem_ops.py).
 
@@ -383,7 +383,7 @@ def test_expm_norm_beyond_32_raises_from_the_status_word():
         T.ExpmCouplingFn.apply(x2, o, c["scal4"].to(DEV), rows, d2)
 
 
-# ================================================================ column sums (csrc/train.hip), called directly
+# ================================================================ column sums (csrc/train_wgrad.hip), called directly
 # rows, cols, lda, base offset in floats, accumulate, splits (colsum_chunks: rows / 128 within [1, 256])
 COLSUM_CASES = [
     (1, 4, 32, 0, 0, 1),
@@ -439,7 +439,7 @@ def test_colsum_matches_fp64(rows, cols, lda, offset, accumulate, splits):
     assert torch.equal(first, _colsum(dev_clean, lda, cols, rows, out0.to(DEV), accumulate)), "rows or columns beyond the asked ones entered"
 
 
-# ================================================================ the stand-alone activation passes (csrc/train.hip), called directly
+# ================================================================ the stand-alone activation passes (csrc/train_linear.hip), called directly
 ACT_SEEDS = {"GELU": 0, "RELU": 1, "ELU": 2}
 
 

@@ -13,6 +13,8 @@
 //   O tile  = P V      consumes those registers DIRECTLY as the A operand (lane (q,h) supplies key
 //     (r&3)+8(r>>2)+4h of step r), with B = V[key][d] read row-wise from LDS (conflict-free ds_read_b32).
 // No LDS round trip for P, no transposed V image.
+// Per-scene key counts (AttnProblem::m_counts): both kernels read Mb = clamp(m_counts[b], 1, M) once per workgroup
+// (attn_scene_keys) and run ceil(Mb / tile) tiles with the index clamp and the mask at Mb; strides stay.  Null m_counts: Mb = M.
 #include "common.h"
 #include "activations.h"
 #include "launch.h"
@@ -28,6 +30,7 @@ struct AttnParams {
     float* out; int ldo;
     int N, n_stride, M, m_stride;
     float qscale;     // extra multiplier applied to q at load (1 when the projection is pre-scaled)
+    const int* m_counts;   // optional [B] per-scene key counts (AttnProblem::m_counts); null: every scene attends over M keys
 };
 
 template <int DH>
@@ -42,6 +45,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int b = blockIdx.y;
+    const int Mb = attn_scene_keys(p.m_counts, b, p.M);       // this scene's keys: tile count, index clamp and mask below; strides stay p.m_stride
     const int q0 = blockIdx.x * 128 + wave * 32;
 
     // ---- Q fragment of this lane's query (B operand of S^T = K Q^T): q[8g + 4h + e]
@@ -74,7 +78,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
 #define FC_GLOAD(T_)                                                                          \
     _Pragma("unroll") for (int i = 0; i < PASSES; ++i) {                                      \
         int key_ = (T_) * KT + srow + RPP * i;                                                \
-        key_ = key_ < p.M ? key_ : p.M - 1; /* clamped rows are masked to -inf below */       \
+        key_ = key_ < Mb ? key_ : Mb - 1; /* clamped rows are masked to -inf below */       \
         rk[i] = *reinterpret_cast<const float4*>(kb + (size_t)key_ * p.ldk);                  \
         rv[i] = *reinterpret_cast<const float4*>(vb + (size_t)key_ * p.ldv);                  \
     }
@@ -84,7 +88,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
         *reinterpret_cast<float4*>(sKst + (ST_) * STAGE + KT * LD + RPP * i * LD) = rv[i];    \
     }
 
-    const int ntiles = (p.M + KT - 1) / KT;
+    const int ntiles = (Mb + KT - 1) / KT;
     FC_GLOAD(0)
     FC_LSTORE(0)
     __syncthreads();
@@ -112,13 +116,13 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
             }
         }
         // ---- mask the tail keys of the last tile
-        if (t * KT + KT > p.M) {
+        if (t * KT + KT > Mb) {
 #pragma unroll
             for (int h2 = 0; h2 < NH2; ++h2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = t * KT + 32 * h2 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= p.M) s[h2][r] = -INFINITY;
+                    if (key >= Mb) s[h2][r] = -INFINITY;
                 }
         }
         // ---- online softmax (this lane's query = lane&31; the other half of its keys lives in lane^32)
@@ -212,6 +216,7 @@ struct Attn16Params {
     int kv_pitch;                   // row pitch of the k16 / v16 images in 16-byte chunks (DH / 4 for the packed images)
     int c16;                        // 1: rows are slices of a GEMM's limb-image output ([16 columns: hi 16 | lo' 16] tiles, GemmEpi::C16)
     float* lse = nullptr;           // optional [B * n_stride]: natural-log sum-exp of every query's scaled scores (training: the backward reuses it)
+    const int* m_counts = nullptr;  // optional [B] per-scene key counts (AttnProblem::m_counts); null: every scene attends over M keys
 };
 
 // fp32 K / V columns of the projected context -> limb row images in the ONE-ACCUMULATOR form (common.h kOneAccActScale): x s = hi + lo with
@@ -266,6 +271,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int b = blockIdx.y;
+    const int Mb = attn_scene_keys(p.m_counts, b, p.M);       // this scene's keys: tile count, index clamp and mask below; strides stay p.m_stride
     const int q0 = blockIdx.x * 128 + wave * 32;
 
     // ---- Q limbs of this lane's query (B operand of S^T = K Q^T): element j of k-step s is q[16 s + 8 h + j]
@@ -324,7 +330,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
 #define FC_GLOAD_SH(T_)                                                                       \
     _Pragma("unroll") for (int i = 0; i < NCH; ++i) {                                         \
         int key_ = (T_) * 64 + (tid >> 4) + 16 * i;                                           \
-        key_ = key_ < p.M ? key_ : p.M - 1; /* clamped rows are masked to -inf below */       \
+        key_ = key_ < Mb ? key_ : Mb - 1; /* clamped rows are masked to -inf below */       \
         const uint4 a_ = kb[(size_t)key_ * CPR + (tid & 15)];                                 \
         rk[4 * i] = a_.x; rk[4 * i + 1] = a_.y; rk[4 * i + 2] = a_.z; rk[4 * i + 3] = a_.w;     \
     }
@@ -336,7 +342,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     _Pragma("unroll") for (int i = 0; i < NCH; ++i) {                                         \
         const int c_ = tid + 256 * i, kr_ = c_ / CPR, part_ = c_ - kr_ * CPR;                 \
         int key_ = (T_) * 64 + kr_;                                                           \
-        key_ = key_ < p.M ? key_ : p.M - 1; /* clamped rows are masked to -inf below */       \
+        key_ = key_ < Mb ? key_ : Mb - 1; /* clamped rows are masked to -inf below */       \
         /* chunk part_ of the [hi DH | lo' DH] row = limb part_/(CPR/2), columns 8 w .. 8 w + 7; in a C16 slice that is chunk   */ \
         /* (w >> 1) * 4 + limb * 2 + (w & 1)                                                                                    */ \
         const int w_ = part_ % (CPR / 2), lb_ = part_ / (CPR / 2);                             \
@@ -362,7 +368,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     const int kr_sh = li * KP + 16 * (lh ^ (((li & 3) << 2) | ((li >> 2) & 3)));
     const int tr_sh = tr_off ^ (16 * ((((lane & 15) >> 2) << 2) | lh));
 
-    const int ntiles = (p.M + 63) / 64;
+    const int ntiles = (Mb + 63) / 64;
     if constexpr (SH) { FC_GLOAD_SH(0) FC_LSTORE_SH(0) } else { FC_GLOAD(0) FC_LSTORE(0) }
     __syncthreads();
 
@@ -389,13 +395,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
             }
         }
         // ---- mask the tail keys of the last tile
-        if (t * 64 + 64 > p.M) {
+        if (t * 64 + 64 > Mb) {
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = t * 64 + 32 * h2 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= p.M) s[h2][r] = -INFINITY;
+                    if (key >= Mb) s[h2][r] = -INFINITY;
                 }
         }
         // ---- online softmax (this lane's query = lane&31; the other half of its keys lives in lane^32)
@@ -525,7 +531,7 @@ static Attn16Params attn16_params(const AttnQuery& qy, const AttnProblem& pb, co
                                   int* flag, int kv_pitch, int c16) {
     const AttnLnq* l = qy.lnq;
     return Attn16Params{qy.q, qy.ldq, k16, v16, out, ldo, pb.N, pb.n_stride_rows, pb.M, pb.m_stride_rows, qy.qscale, flag, l ? l->sumsq : nullptr,
-                        l ? l->slots : 0, l ? l->pitch : 0, l ? l->inv_width : 0.f, l ? l->bias : nullptr, kv_pitch, c16};
+                        l ? l->slots : 0, l ? l->pitch : 0, l ? l->inv_width : 0.f, l ? l->bias : nullptr, kv_pitch, c16, nullptr, pb.m_counts};
 }
 
 bool launch_attention(const AttnQuery& qy, const AttnKeys& kv, const AttnProblem& pb, float* out, int ldo, hipStream_t s, float* lse) {
@@ -562,7 +568,7 @@ bool launch_attention(const AttnQuery& qy, const AttnKeys& kv, const AttnProblem
             if (dh_pad == 32) launch_attn16_dh<32>(p, B, s); else launch_attn16_dh<64>(p, B, s);
             return lse != nullptr;
         }
-        AttnParams p{qy.q, qy.ldq, kv.k, kv.ldk, kv.v, kv.ldv, out, ldo, pb.N, pb.n_stride_rows, pb.M, pb.m_stride_rows, qy.qscale};
+        AttnParams p{qy.q, qy.ldq, kv.k, kv.ldk, kv.v, kv.ldv, out, ldo, pb.N, pb.n_stride_rows, pb.M, pb.m_stride_rows, qy.qscale, pb.m_counts};
         switch (dh_pad) {
             case 32: launch_attn_dh<32>(p, B, s); break;
             case 64: launch_attn_dh<64>(p, B, s); break;

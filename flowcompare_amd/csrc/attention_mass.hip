@@ -24,7 +24,7 @@ struct AttnMassParams : AttnRowParams {
 template <int DH, int KF>
 __global__ __launch_bounds__(256) void attn_mass_kernel(const AttnMassParams p) {
     extern __shared__ float smem[];
-    AttnRows<DH, KF> rows(p, smem);
+    AttnRows<DH, KF> rows(p, smem, attn_scene_keys(p.m_counts, blockIdx.y, p.M));
     constexpr int PL = AttnRows<DH, KF>::PL, LD = AttnRows<DH, KF>::LD;
     float* const sP = rows.sP;
     float* const sC = smem + 64 * LD + 4 * 32 * PL;           // [4 waves][64 keys] column sums of the tile
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void attn_mass_kernel(const AttnMassParams p) 
     float gp = 0.f;                                           // a clamped lane repeats query N - 1: it must not be counted again
     if (rows.p0 + li < p.P) gp = p.g ? p.g[(size_t)b * p.P + rows.p0 + li] : 1.0f;
 
-    const int ntiles = (p.M + 63) / 64;
+    const int Mb = rows.Mb, ntiles = (Mb + 63) / 64;          // (per-scene key counts: a scene with few keys runs few tiles)
     float m_run, l_run;
     rows.pass1(ntiles, m_run, l_run);
     const float inv_l = 1.0f / l_run;
@@ -59,16 +59,19 @@ __global__ __launch_bounds__(256) void attn_mass_kernel(const AttnMassParams p) 
         sC[wave * 64 + lane] = acc;
         __syncthreads();
         const int key = t * 64 + lane;
-        if (wave == 0 && key < p.M) op[key] = ((sC[lane] + sC[64 + lane]) + sC[128 + lane]) + sC[192 + lane];
+        if (wave == 0 && key < Mb) op[key] = ((sC[lane] + sC[64 + lane]) + sC[128 + lane]) + sC[192 + lane];
     }
 }
 
 // out[b, j] = sum over the scene's workgroups, in ascending order
-__global__ __launch_bounds__(256) void attn_mass_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out, int B, int nwg, int M) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)B * M) return;
-    const size_t b = i / M, j = i - b * M;
-    const float* sp = slab + b * nwg * M + j;
+// (per-scene key counts: the slab holds columns below the scene's count only; the dense row's other columns are exact zeros)
+__global__ __launch_bounds__(256) void attn_mass_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out, int B, int nwg, int M,
+                                                               const int* __restrict__ m_counts) {
+    const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    const size_t i = (size_t)b * M + j;
+    if (j >= attn_scene_keys(m_counts, b, M)) { out[i] = 0.f; return; }
+    const float* sp = slab + (size_t)b * nwg * M + j;
     float acc = sp[0];
     for (int w = 1; w < nwg; ++w) acc += sp[(size_t)w * M];
     out[i] = acc;
@@ -106,8 +109,8 @@ void launch_attention_mass(const AttnQuery& qy, const AttnKeys& kv, const AttnPr
     }
     const int nwg = (pb.N + 127) / 128;
     const size_t n = (size_t)B * pb.M;
-    ProfScope ps("void fc::attn_mass_reduce_kernel(const float*, float*, int, int, int)", 0.0, 4.0 * (double)n * (nwg + 1), s);
-    hipLaunchKernelGGL(attn_mass_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slab, out, B, nwg, pb.M);
+    ProfScope ps("void fc::attn_mass_reduce_kernel(const float*, float*, int, int, int, const int*)", 0.0, 4.0 * (double)n * (nwg + 1), s);
+    hipLaunchKernelGGL(attn_mass_reduce_kernel, dim3((unsigned)((pb.M + 255) / 256), B), dim3(256), 0, s, slab, out, B, nwg, pb.M, pb.m_counts);
     FC_HIP(hipGetLastError());
 }
 

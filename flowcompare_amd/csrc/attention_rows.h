@@ -18,6 +18,7 @@ struct AttnRowParams {
     int P, N, n_stride, M, m_stride;
     float qscale;
     const float* q_sumsq; int q_slots; size_t q_pitch; float q_inv_width; const float* q_bias;    // LayerNorm -> q fold (Attn16Params)
+    const int* m_counts;                 // optional [B] per-scene key counts (AttnProblem::m_counts); null: every scene has M keys
 };
 
 // LDS of a 256-thread workgroup: the key tile [64][DH + 4] and one [32 queries][65] slab per wave (+ `extra` floats of the kernel's own)
@@ -31,11 +32,13 @@ struct AttnRows {
     float* const sK;                     // [64][LD]
     float* const sP;                     // [32 queries][PL] of this wave
     const int tid, lane, wave, li, lh, b, p0;
+    const int Mb;                        // keys of this scene, from the kernel: p.M, or its count (attn_scene_keys); tiles, clamp and mask follow it
     float4 qf[NG];                       // Q fragment of this lane's query (B operand of S^T = K Q^T): q[8g + 4h + e]
 
-    __device__ __forceinline__ AttnRows(const AttnRowParams& p_, float* smem)
+    __device__ __forceinline__ AttnRows(const AttnRowParams& p_, float* smem, int scene_keys)
         : p(p_), sK(smem), sP(smem + 64 * LD + (threadIdx.x >> 6) * 32 * PL), tid(threadIdx.x), lane(threadIdx.x & 63), wave(threadIdx.x >> 6),
-          li(threadIdx.x & 31), lh((threadIdx.x & 63) >> 5), b(blockIdx.y), p0(blockIdx.x * 128 + (threadIdx.x >> 6) * 32) {}
+          li(threadIdx.x & 31), lh((threadIdx.x & 63) >> 5), b(blockIdx.y), p0(blockIdx.x * 128 + (threadIdx.x >> 6) * 32),
+          Mb(scene_keys) {}
 
     __device__ __forceinline__ void load_q() {
         int pi = p0 + li;
@@ -60,14 +63,14 @@ struct AttnRows {
         }
     }
 
-    // ---- one key tile into LDS as fp32 rows (rows beyond M repeat key M - 1 and are masked below)
+    // ---- one key tile into LDS as fp32 rows (rows beyond the scene's keys repeat its last key and are masked below)
     __device__ __forceinline__ void stage(int t) {
         if constexpr (KF == 0) {
             constexpr int F4R = DH / 4;
             for (int i = tid; i < 64 * F4R; i += 256) {
                 const int row = i / F4R, c4 = (i - row * F4R) * 4;
                 int key = t * 64 + row;
-                key = key < p.M ? key : p.M - 1;
+                key = key < Mb ? key : Mb - 1;
                 *reinterpret_cast<float4*>(sK + row * LD + c4) = *reinterpret_cast<const float4*>(p.k + ((size_t)b * p.m_stride + key) * p.ldk + c4);
             }
         } else {
@@ -75,7 +78,7 @@ struct AttnRows {
             for (int i = tid; i < 64 * G8; i += 256) {
                 const int row = i / G8, w8 = i - row * G8;
                 int key = t * 64 + row;
-                key = key < p.M ? key : p.M - 1;
+                key = key < Mb ? key : Mb - 1;
                 const unsigned short* src = p.k16 + ((size_t)b * p.m_stride + key) * p.ld16 + (p.k16_rows ? 8 * w8 : (w8 >> 1) * 32 + (w8 & 1) * 8);
                 const uint4 hu = *reinterpret_cast<const uint4*>(src), lu = *reinterpret_cast<const uint4*>(src + (p.k16_rows ? DH : 16));
                 const unsigned hw[4] = {hu.x, hu.y, hu.z, hu.w}, lw[4] = {lu.x, lu.y, lu.z, lu.w};
@@ -109,13 +112,13 @@ struct AttnRows {
                 s[h2] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[g].w, s[h2], 0, 0, 0);
             }
         }
-        if (t * 64 + 64 > p.M) {
+        if (t * 64 + 64 > Mb) {
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = t * 64 + 32 * h2 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= p.M) s[h2][r] = -INFINITY;
+                    if (key >= Mb) s[h2][r] = -INFINITY;
                 }
         }
     }

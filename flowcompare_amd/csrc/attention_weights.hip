@@ -27,16 +27,18 @@ struct AttnWParams : AttnRowParams {
     float* out;                          // [B][P][M]
 };
 
-template <int DH, int KF>
-__global__ __launch_bounds__(256) void attn_weights_kernel(const AttnWParams p) {
+// CNT 1: per-scene key counts (AttnProblem::m_counts).  A template parameter, not a null test: with the count read at run time the shipped
+// attn_weights_kernel<64, 1> went from 92 to 97 VGPRs and from 4 to 3 waves per SIMD; CNT 0 compiles as before.
+template <int DH, int KF, int CNT>
+__device__ __forceinline__ void attn_weights_body(const AttnWParams& p) {
     extern __shared__ float smem[];
-    AttnRows<DH, KF> rows(p, smem);
+    AttnRows<DH, KF> rows(p, smem, CNT ? attn_scene_keys(p.m_counts, blockIdx.y, p.M) : p.M);
     constexpr int PL = AttnRows<DH, KF>::PL;
     float* const sP = rows.sP;
     const int lane = rows.lane, li = rows.li, b = rows.b, p0 = rows.p0;
     rows.load_q();
 
-    const int ntiles = (p.M + 63) / 64;
+    const int Mb = rows.Mb, ntiles = (Mb + 63) / 64;          // (per-scene key counts: a scene with few keys runs few tiles)
     float m_run, l_run;
     rows.pass1(ntiles, m_run, l_run);
     const float inv_l = 1.0f / l_run;
@@ -58,18 +60,31 @@ __global__ __launch_bounds__(256) void attn_weights_kernel(const AttnWParams p) 
         if (key < p.M) {
             const int nrow = p.P - p0 < 32 ? p.P - p0 : 32;                 // (wave-uniform; <= 0 for a wave beyond the selection)
             float* op = p.out + ((size_t)b * p.P + p0) * p.M + key;
-            for (int rr = 0; rr < nrow; ++rr) op[(size_t)rr * p.M] = sP[rr * PL + lane];
+            for (int rr = 0; rr < nrow; ++rr) op[(size_t)rr * p.M] = !CNT || key < Mb ? sP[rr * PL + lane] : 0.f;
+        }
+    }
+    // ---- columns beyond the scene's last tile: the dense [B][P][M] row ends in exact zeros
+    if constexpr (CNT) {
+        for (int key = ntiles * 64 + lane; key < p.M; key += 64) {
+            const int nrow = p.P - p0 < 32 ? p.P - p0 : 32;
+            float* op = p.out + ((size_t)b * p.P + p0) * p.M + key;
+            for (int rr = 0; rr < nrow; ++rr) op[(size_t)rr * p.M] = 0.f;
         }
     }
 }
+template <int DH, int KF>
+__global__ __launch_bounds__(256) void attn_weights_kernel(const AttnWParams p) { attn_weights_body<DH, KF, 0>(p); }
+template <int DH, int KF>
+__global__ __launch_bounds__(256) void attn_weights_counts_kernel(const AttnWParams p) { attn_weights_body<DH, KF, 1>(p); }
 
 template <int DH, int KF>
 static void launch_attnw_dh(const AttnWParams& p, int B, hipStream_t s) {
     constexpr size_t lds = attn_rows_lds_bytes<DH>();      // 67 KB at head dim 128, 100 KB at 256
     char name[80];
-    snprintf(name, sizeof name, "void fc::attn_weights_kernel<%d, %d>(fc::AttnWParams)", DH, KF);
-    launch_kernel<attn_weights_kernel<DH, KF>, (int)lds>(name, 4.0 * B * (double)p.P * (double)p.M * DH, 4.0 * B * (double)p.P * (double)p.M,      // two passes of Q K^T; the output bytes
-                                                         dim3((p.P + 127) / 128, B), dim3(256), lds, s, p);
+    const double flops = 4.0 * B * (double)p.P * (double)p.M * DH, bytes = 4.0 * B * (double)p.P * (double)p.M;      // two passes of Q K^T; the output bytes
+    snprintf(name, sizeof name, "void fc::attn_weights_%skernel<%d, %d>(fc::AttnWParams)", p.m_counts ? "counts_" : "", DH, KF);
+    if (p.m_counts) launch_kernel<attn_weights_counts_kernel<DH, KF>, (int)lds>(name, flops, bytes, dim3((p.P + 127) / 128, B), dim3(256), lds, s, p);
+    else launch_kernel<attn_weights_kernel<DH, KF>, (int)lds>(name, flops, bytes, dim3((p.P + 127) / 128, B), dim3(256), lds, s, p);
 }
 
 int attn_rows_params(const char* what, const AttnQuery& qy, const AttnKeys& kv, const AttnProblem& pb, AttnRowParams& p) {
@@ -80,7 +95,7 @@ int attn_rows_params(const char* what, const AttnQuery& qy, const AttnKeys& kv, 
     if (!qy.q || (limbs ? !kv.img : !kv.k)) throw Error(FC_ERR_INVALID, w + "null pointer");
     if (qy.ldq % 4 != 0 || ((uintptr_t)qy.q & 15)) throw Error(FC_ERR_INVALID, w + "q must be 16-byte aligned with a pitch that is a multiple of 4 floats");
     p.q = qy.q; p.ldq = qy.ldq;
-    p.N = pb.N; p.n_stride = pb.n_stride_rows; p.M = pb.M; p.m_stride = pb.m_stride_rows; p.qscale = qy.qscale;
+    p.N = pb.N; p.n_stride = pb.n_stride_rows; p.M = pb.M; p.m_stride = pb.m_stride_rows; p.qscale = qy.qscale; p.m_counts = pb.m_counts;
     if (const AttnLnq* l = qy.lnq) { p.q_sumsq = l->sumsq; p.q_slots = l->slots; p.q_pitch = l->pitch; p.q_inv_width = l->inv_width; p.q_bias = l->bias; }
     if (limbs) {
         if (kv.form == AttnKeys::CONTEXT) {

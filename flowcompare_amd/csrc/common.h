@@ -12,6 +12,7 @@
 
 #include "../../include/fcflow.h"
 #include "../../include/fcflow_attention_mass.h"
+#include "../../include/fcflow_context_counts.h"
 #include "knobs.h"
 
 namespace fc {
@@ -352,7 +353,14 @@ struct AttnKeys {
     static AttnKeys slice(const unsigned short* img, int n_pad, int col0) { AttnKeys a{SLICE}; a.img = img; a.n_pad = n_pad; a.col0 = col0; return a; }
     static AttnKeys context(const unsigned short* img) { AttnKeys a{CONTEXT}; a.img = img; return a; }
 };
-struct AttnProblem { int B, N, n_stride_rows, M, m_stride_rows, dh_pad; };      // B scenes of N queries x M keys; rows between scenes; padded head dim
+struct AttnProblem {
+    int B, N, n_stride_rows, M, m_stride_rows, dh_pad;      // B scenes of N queries x M keys; rows between scenes; padded head dim
+    // optional per-scene key counts (fcflow_context_counts.h), device [B]: scene b attends over keys 0 .. clamp(m_counts[b], 1, M) - 1, its workgroups
+    // run that many keys' tiles, and dense outputs ([B][P][M] weights, [B][M] masses) get exact zeros in the columns beyond.  Null: all M keys
+    const int32_t* m_counts = nullptr;
+};
+// rows >= clamp(m_counts[b], 1, M) of every scene of a [B][M][ld] fp32 panel := 0 (misc.hip; one launch, 16-byte stores; ld % 4 == 0)
+void launch_zero_pad_rows(float* panel, int ld, const int32_t* m_counts, int B, int M, hipStream_t s);
 size_t attention_limb_ws_bytes(long kv_rows, int dh_pad);
 // the context panel's limb image, made once per forward from the fp32 panel; raises the scope's range flag like the K|V projection's epilogue does
 void launch_context_limbs(const float* ctx, int ldc, unsigned short* img, long rows, int dh_pad, hipStream_t s);

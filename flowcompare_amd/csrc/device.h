@@ -52,6 +52,15 @@ __device__ __forceinline__ void swap32_free(T& a, T& b) {
     asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
 }
 
+// ---------------------------------------------------------------- per-scene key count of an attention launch (AttnProblem::m_counts, common.h)
+// The keys scene b attends over: wave-uniform (blockIdx.y and kernel arguments only: a scalar load, pinned to an SGPR), and clamped into
+// [1, M], because the host cannot check a device array without a synchronisation and a count must never become an out-of-range read.
+__device__ __forceinline__ int attn_scene_keys(const int* m_counts, int b, int M) {
+    if (!m_counts) return M;
+    const int c = __builtin_amdgcn_readfirstlane(m_counts[b]);
+    return c < 1 ? 1 : (c < M ? c : M);
+}
+
 // ---------------------------------------------------------------- compile-time loop: f(integral_constant<int, 0>{}) ... f(integral_constant<int, N - 1>{})
 template <class F, int... I>
 __host__ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {

@@ -24,6 +24,7 @@ struct FlowWs {
     int P, P_pad, Pc, Pc_pad, ldkv;
     int spl_rows;          // rows of w.spl: P_pad, or the row chunk of the wide ExponentialCoupling (expm_chunk_rows)
     float* lp_scratch;     // [P_pad] log-prob accumulator of a pass whose caller wants none (fc_flow_attention_weights_f32 with logprob = NULL)
+    const int32_t* m_counts;   // per-scene context point counts of this call (device [B], fcflow_context_counts.h) or null: every attention's AttnProblem
     void ldj_into(GemmEpi& e) const { e.ldj_part = ldjp; e.ldj_pitch = (size_t)P_pad; }      // the epilogue accumulates its log-det partials in ldjp
 };
 // Log-det partial slots (rows of FlowWs::ldjp): one per 128-column tile of the fused spline epilogue, two (one per wave column)
@@ -159,7 +160,7 @@ static void run_attention(const fc_flow& f, const PackedMLP& pre, const AttnPack
     // q is complete in w.q (`lq` null) or up to rstd and the bias, which the limb-image kernels apply on load: probe if asked, then attend
     auto attend = [&](const AttnLnq* lq) {
         const AttnQuery qy{w.q, d.I_pad, 1.0f, lq};
-        const AttnProblem pb{B, N, N, M, M, d.I_pad};
+        const AttnProblem pb{B, N, N, M, M, d.I_pad, w.m_counts};
         if (probe)
             for (size_t i = 0; i < probe->layers.size(); ++i)
                 if (probe->layers[i] == probe_layer) launch_attention_weights(qy, keys, pb, probe->sel, probe->P, probe->sel_per_scene, probe->out[i], s);
@@ -311,7 +312,7 @@ struct Prep {
     FlowWs w;
     const float* rowscal = nullptr;
 };
-static Prep prepare(fc_flow& f, const float* ctx, const float* extra, int B, int N, int M, void* ws, size_t ws_bytes, hipStream_t s) {
+static Prep prepare(fc_flow& f, const float* ctx, const int32_t* ctx_counts, const float* extra, int B, int N, int M, void* ws, size_t ws_bytes, hipStream_t s) {
     const Dims& d = f.d;
     const fc_flow_config& c = f.cfg;
     if (B < 1 || N < 1 || M < 1) throw Error(FC_ERR_INVALID, "B, N, M must be positive");
@@ -321,11 +322,20 @@ static Prep prepare(fc_flow& f, const float* ctx, const float* extra, int B, int
     Prep p;
     p.w = plan_ws(f, B, N, M, ws, ws_bytes, false, nullptr);
     FlowWs& w = p.w;
+    w.m_counts = ctx_counts;
     launch_pack_rows(ctx, d.E, d.E, w.ctxp, d.E_pad, 0, d.E_pad, w.Pc, s);
+    // per-scene counts: a scene's rows beyond its count are padding the caller may have left anything in.  No attention reads them as keys,
+    // but the limb image and the K|V projection below take every row: zeroed here for the reason given for the panel's tail
+    launch_zero_pad_rows(w.ctxp, d.E_pad, ctx_counts, B, M, s);
     // pad rows of the context panel: the K|V projection stages them like any row, and stale workspace bytes there (a NaN, a value beyond fp16's
     // range) would raise the split-fp16 range flag -- a needless repeat of the whole pass on the bf16 limbs, and a scene whose log-probs then
     // depend on what ran in the workspace before (found in round 4: one scene of 200 context points behind a three-scene batch)
     if (w.Pc_pad > w.Pc) launch_fill(w.ctxp + (size_t)w.Pc * d.E_pad, 0.f, (size_t)(w.Pc_pad - w.Pc) * d.E_pad, s);
+    // pad rows of the attention output: the attention kernels write the P valid rows only, and the coupling net's in_layer GEMM stages all P_pad
+    // rows of w.a as an operand segment.  Stale workspace bytes there (the limb image of a call with another batch size, read as fp32) raised the
+    // range flag and repeated every later pass on the bf16 limbs: seen with the stacked K|V projection (knob 33 = 0), a 4-scene call after
+    // 1-scene calls on the same workspace (tests/test_gpu_context_counts.py compares exactly such calls)
+    if (f.n_attn && w.P_pad > w.P) launch_fill(w.a + (size_t)w.P * d.I_pad, 0.f, (size_t)(w.P_pad - w.P) * d.I_pad, s);
     if (d.X) { launch_repeat_extra(extra, d.X, w.rowscal, B, N, s); p.rowscal = w.rowscal; }
     if (f.n_attn && f.kv_fold) {
         // keys = values = the context panel: one limb image per forward for the split-fp16 attention (range flag as the projection's epilogue
@@ -351,14 +361,14 @@ static Prep prepare(fc_flow& f, const float* ctx, const float* extra, int B, int
 
 static int expected_noise(const fc_flow& f) { return (f.has_augment ? 1 : 0) + (f.d.nz > 0 ? f.cfg.n_flow_layers : 0); }
 
-static void flow_forward(fc_flow& f, const float* x, const float* ctx, const float* extra, const float* const* eps, int n_eps,
+static void flow_forward(fc_flow& f, const float* x, const float* ctx, const int32_t* ctx_counts, const float* extra, const float* const* eps, int n_eps,
                          float* logprob, float* z_out, int B, int N, int M, void* ws, size_t ws_bytes, hipStream_t s, const AttnProbe* probe = nullptr) {
     const Dims& d = f.d;
     const fc_flow_config& c = f.cfg;
     if (!x || (!logprob && !probe)) throw Error(FC_ERR_INVALID, "null x / logprob");
     if (n_eps != expected_noise(f)) throw Error(FC_ERR_INVALID, "wrong number of noise tensors");
     for (int i = 0; i < n_eps; ++i) if (!eps || !eps[i]) throw Error(FC_ERR_INVALID, "null noise tensor");
-    Prep pr = prepare(f, ctx, extra, B, N, M, ws, ws_bytes, s);
+    Prep pr = prepare(f, ctx, ctx_counts, extra, B, N, M, ws, ws_bytes, s);
     FlowWs& w = pr.w;
     if (!logprob) logprob = w.lp_scratch;          // (a probe call that wants no log-prob: the pass still accumulates one)
     if (f.expm_status) FC_HIP(hipMemsetAsync(f.expm_status, 0, sizeof(int), s));
@@ -428,7 +438,7 @@ static void flow_inverse(fc_flow& f, const float* z, const float* ctx, const flo
     if (n_eps != need_eps) throw Error(FC_ERR_INVALID, "wrong number of noise tensors for the inverse pass");
     for (int i = 0; i < n_eps; ++i) if (!eps || !eps[i]) throw Error(FC_ERR_INVALID, "null noise tensor");
     ensure_lin_inverse(f);
-    Prep pr = prepare(f, ctx, extra, B, N, M, ws, ws_bytes, s);
+    Prep pr = prepare(f, ctx, nullptr, extra, B, N, M, ws, ws_bytes, s);      // (one scene is never ragged, and make_sample passes one)
     FlowWs& w = pr.w;
     if (f.expm_status) FC_HIP(hipMemsetAsync(f.expm_status, 0, sizeof(int), s));
     float* xc = w.xa;
@@ -503,23 +513,47 @@ int fc_flow_noise_width(const fc_flow* flow, int32_t i) {
 // One guarded forward pass: fast split-fp16 GEMMs first; the whole pass is repeated with the bf16-limb GEMMs if an activation left fp16's
 // range, which rewrites every output of the pass (log-probs, latent, weight buffers, slabs, masses).  With a deferred range check
 // (fc_range_check_defer) the pass may be repeated after the entry point has returned, so it owns its arguments: the noise pointers and the
-// probe are copied.  probe: null = a plain log-prob pass.
-static void guarded_forward(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int n_eps, float* logprob,
-                            float* z_out, int B, int N, int M, void* ws, size_t ws_bytes, hipStream_t s, const fc::AttnProbe* probe = nullptr) {
+// probe are copied.  probe: null = a plain log-prob pass.  ctx_counts: null, or the per-scene context point counts of the *_counts_* entries.
+static void guarded_forward(fc_flow* flow, const float* x, const float* ctx, const int32_t* ctx_counts, const float* extra, const float* const* eps, int n_eps,
+                            float* logprob, float* z_out, int B, int N, int M, void* ws, size_t ws_bytes, hipStream_t s, const fc::AttnProbe* probe = nullptr) {
     const std::vector<const float*> eps_own(eps, eps + (eps && n_eps > 0 ? n_eps : 0));
     const bool probing = probe != nullptr;
     const fc::AttnProbe probe_own = probing ? *probe : fc::AttnProbe();
     fc::run_fp16_guarded(flow->fp16_flag, s, [=] {
-        fc::flow_forward(*flow, x, ctx, extra, eps_own.data(), n_eps, logprob, z_out, B, N, M, ws, ws_bytes, s, probing ? &probe_own : nullptr);
+        fc::flow_forward(*flow, x, ctx, ctx_counts, extra, eps_own.data(), n_eps, logprob, z_out, B, N, M, ws, ws_bytes, s, probing ? &probe_own : nullptr);
     }, true);
     fc::check_expm_status(*flow, s);
+}
+
+// The entries of fcflow.h / fcflow_attention_mass.h and their namesakes of fcflow_context_counts.h are one body each: `who` is the entry's name
+// (it opens every message), `counted` says which of the two it is.  The namesakes refuse what has no per-scene count.
+static void check_entry(const char* who, const fc_flow* flow, const void* workspace, bool counted, const int32_t* ctx_counts) {
+    if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, std::string(who) + ": null flow / workspace");
+    if (!counted) return;
+    if (!ctx_counts) throw fc::Error(FC_ERR_INVALID, std::string(who) + ": null ctx_counts (the entry without per-scene counts takes one M for the batch)");
+    if (flow->cfg.global_context)
+        throw fc::Error(FC_ERR_INVALID, std::string(who) + ": this flow has a global context (ctx is per target point, [B,N,E]): there are no per-scene context point counts");
+}
+
+static void logprob_entry(const char* who, bool counted, fc_flow* flow, const float* x, const float* ctx, const int32_t* ctx_counts, const float* extra,
+                          const float* const* eps, int32_t n_eps, float* logprob, float* z_out, int32_t B, int32_t N, int32_t M, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    check_entry(who, flow, workspace, counted, ctx_counts);
+    guarded_forward(flow, x, ctx, ctx_counts, extra, eps, n_eps, logprob, z_out, B, N, M, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int fc_flow_logprob_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int32_t n_eps,
                         float* logprob, float* z_out, int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
     FC_API_BEGIN
-    if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_flow_logprob_f32: null flow / workspace");
-    guarded_forward(flow, x, ctx, extra, eps, n_eps, logprob, z_out, B, N, M, workspace, workspace_bytes, (hipStream_t)stream);
+    logprob_entry("fc_flow_logprob_f32", false, flow, x, ctx, nullptr, extra, eps, n_eps, logprob, z_out, B, N, M, workspace, workspace_bytes, stream);
+    FC_API_END
+}
+
+int fc_flow_logprob_counts_f32(fc_flow* flow, const float* x, const float* ctx, const int32_t* ctx_counts, const float* extra, const float* const* eps,
+                               int32_t n_eps, float* logprob, float* z_out, int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    FC_API_BEGIN
+    logprob_entry("fc_flow_logprob_counts_f32", true, flow, x, ctx, ctx_counts, extra, eps, n_eps, logprob, z_out, B, N, M, workspace, workspace_bytes, stream);
     FC_API_END
 }
 
@@ -548,18 +582,37 @@ static void probe_requests(const fc_flow* flow, const std::string& who, const in
     }
 }
 
+static void attention_weights_entry(const char* who_c, bool counted, fc_flow* flow, const float* x, const float* ctx, const int32_t* ctx_counts,
+                                    const float* extra, const float* const* eps, int32_t n_eps, const int32_t* layers, int32_t n_layers, const int32_t* sel,
+                                    int32_t P, int32_t sel_per_scene, float* const* out, float* logprob, int32_t B, int32_t N, int32_t M, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    const std::string who = who_c;
+    check_entry(who_c, flow, workspace, counted, ctx_counts);
+    if (n_layers < 1 || !layers || !out) throw fc::Error(FC_ERR_INVALID, who + ": no layers requested (layers / out are null or n_layers < 1)");
+    if (!sel) P = N;
+    if (P < 1) throw fc::Error(FC_ERR_INVALID, who + ": P must be positive");
+    fc::AttnProbe probe;
+    probe.sel = sel; probe.P = P; probe.sel_per_scene = sel ? (sel_per_scene != 0) : 0;
+    probe_requests(flow, who, layers, out, n_layers, probe.layers, probe.out);
+    guarded_forward(flow, x, ctx, ctx_counts, extra, eps, n_eps, logprob, nullptr, B, N, M, workspace, workspace_bytes, (hipStream_t)stream, &probe);
+}
+
 int fc_flow_attention_weights_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int32_t n_eps,
                                   const int32_t* layers, int32_t n_layers, const int32_t* sel, int32_t P, int32_t sel_per_scene, float* const* out,
                                   float* logprob, int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
     FC_API_BEGIN
-    if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: null flow / workspace");
-    if (n_layers < 1 || !layers || !out) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: no layers requested (layers / out are null or n_layers < 1)");
-    if (!sel) P = N;
-    if (P < 1) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_weights_f32: P must be positive");
-    fc::AttnProbe probe;
-    probe.sel = sel; probe.P = P; probe.sel_per_scene = sel ? (sel_per_scene != 0) : 0;
-    probe_requests(flow, "fc_flow_attention_weights_f32", layers, out, n_layers, probe.layers, probe.out);
-    guarded_forward(flow, x, ctx, extra, eps, n_eps, logprob, nullptr, B, N, M, workspace, workspace_bytes, (hipStream_t)stream, &probe);
+    attention_weights_entry("fc_flow_attention_weights_f32", false, flow, x, ctx, nullptr, extra, eps, n_eps, layers, n_layers, sel, P, sel_per_scene, out, logprob,
+                            B, N, M, workspace, workspace_bytes, stream);
+    FC_API_END
+}
+
+int fc_flow_attention_weights_counts_f32(fc_flow* flow, const float* x, const float* ctx, const int32_t* ctx_counts, const float* extra,
+                                         const float* const* eps, int32_t n_eps, const int32_t* layers, int32_t n_layers, const int32_t* sel, int32_t P,
+                                         int32_t sel_per_scene, float* const* out, float* logprob, int32_t B, int32_t N, int32_t M, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    FC_API_BEGIN
+    attention_weights_entry("fc_flow_attention_weights_counts_f32", true, flow, x, ctx, ctx_counts, extra, eps, n_eps, layers, n_layers, sel, P, sel_per_scene, out,
+                            logprob, B, N, M, workspace, workspace_bytes, stream);
     FC_API_END
 }
 
@@ -577,22 +630,39 @@ int fc_flow_attention_mass_workspace_bytes(const fc_flow* flow, int32_t B, int32
     FC_API_END
 }
 
+static void attention_mass_entry(const char* who_c, bool counted, fc_flow* flow, const float* x, const float* ctx, const int32_t* ctx_counts, const float* extra,
+                                 const float* const* eps, int32_t n_eps, const int32_t* layers, int32_t n_layers, const float* row_weight, float* const* out,
+                                 float* logprob, int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
+    const std::string who = who_c;
+    check_entry(who_c, flow, workspace, counted, ctx_counts);
+    if (n_layers < 1 || !layers || !out) throw fc::Error(FC_ERR_INVALID, who + ": no layers requested (layers / out are null or n_layers < 1)");
+    if (B < 1 || N < 1 || M < 1) throw fc::Error(FC_ERR_INVALID, "B, N, M must be positive");
+    fc::AttnProbe probe;
+    probe.row_weight = row_weight;
+    probe_requests(flow, who, layers, out, n_layers, probe.mass_layers, probe.mass_out);
+    const size_t slab_off = mass_slab_offset(*flow, B, N, M), need = slab_off + fc::attention_mass_slab_bytes(B, N, M);
+    if (workspace_bytes < need)
+        throw fc::Error(FC_ERR_WORKSPACE, who + ": workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " + std::to_string(need) +
+                                          " needed (fc_flow_attention_mass_workspace_bytes: the forward's workspace plus the slab region)");
+    probe.slab = reinterpret_cast<float*>(static_cast<char*>(workspace) + slab_off);
+    guarded_forward(flow, x, ctx, ctx_counts, extra, eps, n_eps, logprob, nullptr, B, N, M, workspace, slab_off, (hipStream_t)stream, &probe);
+}
+
 int fc_flow_attention_mass_f32(fc_flow* flow, const float* x, const float* ctx, const float* extra, const float* const* eps, int32_t n_eps,
                                const int32_t* layers, int32_t n_layers, const float* row_weight, float* const* out, float* logprob, int32_t B, int32_t N,
                                int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
     FC_API_BEGIN
-    if (!flow || !workspace) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_f32: null flow / workspace");
-    if (n_layers < 1 || !layers || !out) throw fc::Error(FC_ERR_INVALID, "fc_flow_attention_mass_f32: no layers requested (layers / out are null or n_layers < 1)");
-    if (B < 1 || N < 1 || M < 1) throw fc::Error(FC_ERR_INVALID, "B, N, M must be positive");
-    fc::AttnProbe probe;
-    probe.row_weight = row_weight;
-    probe_requests(flow, "fc_flow_attention_mass_f32", layers, out, n_layers, probe.mass_layers, probe.mass_out);
-    const size_t slab_off = mass_slab_offset(*flow, B, N, M), need = slab_off + fc::attention_mass_slab_bytes(B, N, M);
-    if (workspace_bytes < need)
-        throw fc::Error(FC_ERR_WORKSPACE, "fc_flow_attention_mass_f32: workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " + std::to_string(need) +
-                                          " needed (fc_flow_attention_mass_workspace_bytes: the forward's workspace plus the slab region)");
-    probe.slab = reinterpret_cast<float*>(static_cast<char*>(workspace) + slab_off);
-    guarded_forward(flow, x, ctx, extra, eps, n_eps, logprob, nullptr, B, N, M, workspace, slab_off, (hipStream_t)stream, &probe);
+    attention_mass_entry("fc_flow_attention_mass_f32", false, flow, x, ctx, nullptr, extra, eps, n_eps, layers, n_layers, row_weight, out, logprob, B, N, M,
+                         workspace, workspace_bytes, stream);
+    FC_API_END
+}
+
+int fc_flow_attention_mass_counts_f32(fc_flow* flow, const float* x, const float* ctx, const int32_t* ctx_counts, const float* extra, const float* const* eps,
+                                      int32_t n_eps, const int32_t* layers, int32_t n_layers, const float* row_weight, float* const* out, float* logprob,
+                                      int32_t B, int32_t N, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
+    FC_API_BEGIN
+    attention_mass_entry("fc_flow_attention_mass_counts_f32", true, flow, x, ctx, ctx_counts, extra, eps, n_eps, layers, n_layers, row_weight, out, logprob, B, N, M,
+                         workspace, workspace_bytes, stream);
     FC_API_END
 }
 

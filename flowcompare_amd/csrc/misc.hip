@@ -2,6 +2,7 @@
 // rational-quadratic spline, DGCNN gather-max and global pooling.  All are one-wave-per-row streaming
 // kernels (coalesced row reads, wave reductions via DPP shuffles); none of them is reshaped into a GEMM.
 #include "common.h"
+#include "device.h"
 #include "spline.h"
 
 namespace fc {
@@ -77,6 +78,24 @@ void launch_fill(float* p, float v, size_t n, hipStream_t s) {
     if (blocks > 4096) blocks = 4096;
     ProfScope ps("fc::fill_kernel", 0.0, 4.0 * n, s);
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, v, n);
+    FC_HIP(hipGetLastError());
+}
+
+// Per-scene context point counts (fcflow_context_counts.h): rows >= the scene's count of a [B][M][ld] panel := 0, so that what a caller left in
+// its pad rows (a NaN, a value beyond fp16's range) reaches neither a limb image's range flag nor the K|V projection.  blockIdx.y = scene,
+// one 16-byte store per thread; the count is clamped like the attention kernels clamp it.
+__global__ __launch_bounds__(256) void zero_pad_rows_kernel(float* __restrict__ panel, int ld4, const int* __restrict__ m_counts, int M) {
+    const int b = blockIdx.y;
+    const int Mb = attn_scene_keys(m_counts, b, M);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x + (long)Mb * ld4;      // float4 index inside the scene, starting at its first pad row
+    if (i < (long)M * ld4) reinterpret_cast<float4*>(panel)[(size_t)b * M * ld4 + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+void launch_zero_pad_rows(float* panel, int ld, const int32_t* m_counts, int B, int M, hipStream_t s) {
+    if (!m_counts || B <= 0 || M <= 1) return;                                  // (a count is at least 1: one key has no pad row)
+    if (ld % 4 != 0 || ((uintptr_t)panel & 15)) throw Error(FC_ERR_INVALID, "zero_pad_rows: the panel must be 16-byte aligned with a pitch that is a multiple of 4 floats");
+    const long n4 = (long)(M - 1) * (ld / 4);                                   // the most pad a scene can have
+    ProfScope ps("fc::zero_pad_rows_kernel", 0.0, 16.0 * (double)n4 * B, s);
+    hipLaunchKernelGGL(zero_pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, s, panel, ld / 4, m_counts, M);
     FC_HIP(hipGetLastError());
 }
 

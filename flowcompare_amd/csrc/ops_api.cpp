@@ -370,15 +370,69 @@ int fc_debug_premlp_q_f32(const float* x, int32_t ldx, int32_t k_in, const fc_te
     FC_API_END
 }
 
+// fc_op_attention_f32 / fc_debug_attention_ctx_f32 and their namesakes with per-scene key counts (fcflow_context_counts.h) share one body each.
+// With counts the key / value tensors are copied and the copies' pad rows zeroed first -- what the flow engine does to its context panel -- so
+// that what a caller left in pad rows reaches no limb image and no range flag.
+namespace fc {
+struct CountedCopy {
+    std::unique_ptr<TmpBuf> buf;
+    // src [B][M][D] as it is (null counts), or a copy whose rows >= clamp(counts[b], 1, M) are zeros
+    const float* of(const char* who, const float* src, const int32_t* counts, int B, int M, int D, hipStream_t s) {
+        if (!counts) return src;
+        if (B < 1 || M < 1) throw Error(FC_ERR_INVALID, std::string(who) + ": B, N, M must be positive");
+        const size_t bytes = (size_t)B * M * D * sizeof(float);
+        buf.reset(new TmpBuf(bytes));
+        FC_HIP(hipMemcpyAsync(buf->p, src, bytes, hipMemcpyDeviceToDevice, s));
+        launch_zero_pad_rows(buf->f(), D, counts, B, M, s);
+        return buf->f();
+    }
+};
+
+static void op_attention(const char* who_c, bool counted, const float* q, const float* k, const float* v, float* out, const int32_t* counts, int B, int N, int M,
+                         int D, float scale, hipStream_t s) {
+    const std::string who = who_c;
+    if (!q || !k || !v || !out || (counted && !counts)) throw Error(FC_ERR_INVALID, who + ": null pointer");
+    if (D != 32 && D != 64 && D != 128 && D != 256) throw Error(FC_ERR_UNSUPPORTED, who + ": D must be 32, 64 or 128, or 256");
+    CountedCopy kc, vc;
+    k = kc.of(who_c, k, counts, B, M, D, s);
+    v = vc.of(who_c, v, counts, B, M, D, s);
+    TmpBuf limbs(attention_limb_ws_bytes((long)B * M, D)), flag(sizeof(int));
+    run_fp16_guarded((int*)flag.p, s, [&] { launch_attention({q, D, scale * kLog2eF}, AttnKeys::panels(k, D, v, D, limbs.p), {B, N, N, M, M, D, counts}, out, D, s); });
+    FC_HIP(hipStreamSynchronize(s));
+}
+
+static void op_attention_ctx(const char* who_c, bool counted, const float* q, const float* c, float* out, const int32_t* counts, int B, int N, int M, int D,
+                             float scale, hipStream_t s) {
+    const std::string who = who_c;
+    if (!q || !c || !out || (counted && !counts)) throw Error(FC_ERR_INVALID, who + ": null pointer");
+    if (D != 32 && D != 64) throw Error(FC_ERR_UNSUPPORTED, who + ": D must be 32 or 64");
+    if (((uintptr_t)q | (uintptr_t)c | (uintptr_t)out) & 15) throw Error(FC_ERR_INVALID, who + ": operands must be 16-byte aligned");
+    CountedCopy cc;
+    c = cc.of(who_c, c, counts, B, M, D, s);
+    TmpBuf limbs(attention_limb_ws_bytes((long)B * M, D) / 2), flag(sizeof(int));
+    run_fp16_guarded((int*)flag.p, s, [&] {
+        if (gemm_fp16_flag() && g_knobs.attn_fp16) {
+            launch_context_limbs(c, D, (unsigned short*)limbs.p, (long)B * M, D, s);
+            launch_attention({q, D, scale * kLog2eF}, AttnKeys::context((const unsigned short*)limbs.p), {B, N, N, M, M, D, counts}, out, D, s);
+        } else {                                        // as in the engine: the repeat after a raised range flag (and attn_fp16, knob 5, = 0) takes c itself, in fp32
+            launch_attention({q, D, scale * kLog2eF}, AttnKeys::panels(c, D, c, D, nullptr), {B, N, N, M, M, D, counts}, out, D, s);
+        }
+    });
+    FC_HIP(hipStreamSynchronize(s));
+}
+}  // namespace fc
+
 int fc_op_attention_f32(const float* q, const float* k, const float* v, float* out, int32_t B, int32_t N, int32_t M, int32_t D, float scale,
                         void* stream) {
     FC_API_BEGIN
-    if (!q || !k || !v || !out) throw fc::Error(FC_ERR_INVALID, "fc_op_attention_f32: null pointer");
-    if (D != 32 && D != 64 && D != 128 && D != 256) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_op_attention_f32: D must be 32, 64 or 128, or 256");
-    fc::TmpBuf limbs(fc::attention_limb_ws_bytes((long)B * M, D)), flag(sizeof(int));
-    fc::run_fp16_guarded((int*)flag.p, (hipStream_t)stream,
-                         [&] { fc::launch_attention({q, D, scale * fc::kLog2eF}, fc::AttnKeys::panels(k, D, v, D, limbs.p), {B, N, N, M, M, D}, out, D, (hipStream_t)stream); });
-    FC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    fc::op_attention("fc_op_attention_f32", false, q, k, v, out, nullptr, B, N, M, D, scale, (hipStream_t)stream);
+    FC_API_END
+}
+
+int fc_op_attention_counts_f32(const float* q, const float* k, const float* v, float* out, const int32_t* ctx_counts, int32_t B, int32_t N, int32_t M,
+                               int32_t D, float scale, void* stream) {
+    FC_API_BEGIN
+    fc::op_attention("fc_op_attention_counts_f32", true, q, k, v, out, ctx_counts, B, N, M, D, scale, (hipStream_t)stream);
     FC_API_END
 }
 
@@ -387,19 +441,15 @@ int fc_op_attention_f32(const float* q, const float* k, const float* v, float* o
    image twice.  For the tests; a value beyond the image's range is an error here (the engine repeats such a pass on its fp32 path). */
 int fc_debug_attention_ctx_f32(const float* q, const float* c, float* out, int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream) {
     FC_API_BEGIN
-    if (!q || !c || !out) throw fc::Error(FC_ERR_INVALID, "fc_debug_attention_ctx_f32: null pointer");
-    if (D != 32 && D != 64) throw fc::Error(FC_ERR_UNSUPPORTED, "fc_debug_attention_ctx_f32: D must be 32 or 64");
-    if (((uintptr_t)q | (uintptr_t)c | (uintptr_t)out) & 15) throw fc::Error(FC_ERR_INVALID, "fc_debug_attention_ctx_f32: operands must be 16-byte aligned");
-    fc::TmpBuf limbs(fc::attention_limb_ws_bytes((long)B * M, D) / 2), flag(sizeof(int));
-    fc::run_fp16_guarded((int*)flag.p, (hipStream_t)stream, [&] {
-        if (fc::gemm_fp16_flag() && fc::g_knobs.attn_fp16) {
-            fc::launch_context_limbs(c, D, (unsigned short*)limbs.p, (long)B * M, D, (hipStream_t)stream);
-            fc::launch_attention({q, D, scale * fc::kLog2eF}, fc::AttnKeys::context((const unsigned short*)limbs.p), {B, N, N, M, M, D}, out, D, (hipStream_t)stream);
-        } else {                                        // as in the engine: the repeat after a raised range flag (and attn_fp16, knob 5, = 0) takes c itself, in fp32
-            fc::launch_attention({q, D, scale * fc::kLog2eF}, fc::AttnKeys::panels(c, D, c, D, nullptr), {B, N, N, M, M, D}, out, D, (hipStream_t)stream);
-        }
-    });
-    FC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    fc::op_attention_ctx("fc_debug_attention_ctx_f32", false, q, c, out, nullptr, B, N, M, D, scale, (hipStream_t)stream);
+    FC_API_END
+}
+
+/* the same with per-scene key counts, declared in fcflow_context_counts.h */
+int fc_op_attention_ctx_counts_f32(const float* q, const float* c, float* out, const int32_t* ctx_counts, int32_t B, int32_t N, int32_t M, int32_t D,
+                                   float scale, void* stream) {
+    FC_API_BEGIN
+    fc::op_attention_ctx("fc_op_attention_ctx_counts_f32", true, q, c, out, ctx_counts, B, N, M, D, scale, (hipStream_t)stream);
     FC_API_END
 }
 

@@ -24,7 +24,7 @@ EXPM = {"torch": 0, "original": 1}
 OP_ACTS = {"none": 0, "gelu": 1, "relu": 2, "elu": 3, "lrelu": 4}      # `act` of op_linear / op_mlp_hidden (FC_ACT_*)
 
 EXPORTS = list(abi.ENTRIES)          # every entry point include/fcflow.h declares
-EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES)      # ... and those of the headers behind it (include/fcflow_attention_mass.h)
+EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES) + list(abi.COUNTS_ENTRIES)      # ... and those of the headers behind it (include/fcflow_attention_mass.h, fcflow_context_counts.h)
 
 
 class FcTensor(ctypes.Structure):
@@ -204,6 +204,26 @@ def _row_weights(weights, B, N, device):
     return g.expand(B, N).contiguous()
 
 
+def _context_counts(counts, B, M, device, name="context_counts"):
+    """Per-scene context point counts of the *_counts_* entry points -> int32 device tensor [B], or None.  The kernels clamp a count into
+    [1, M] and the library cannot check a device array without a synchronisation, so everything is checked here, before the library or an
+    embedder is called: an integer tensor of shape [B] on the HIP device, every value in [1, M].  The one read-back of the call is here."""
+    if counts is None:
+        return None
+    if not torch.is_tensor(counts):
+        raise RuntimeError(f"{name} must be None or an integer tensor of shape [B], got {type(counts).__name__}")
+    if counts.is_floating_point() or counts.is_complex() or counts.dtype == torch.bool:
+        raise RuntimeError(f"{name} must be an integer tensor, got dtype {counts.dtype}")
+    if not counts.is_cuda:
+        raise RuntimeError(f"{name} must live on a HIP device (there is no CPU path), got a tensor on {counts.device}")
+    if tuple(counts.shape) != (B,):
+        raise RuntimeError(f"{name} must have shape [B] with B = {B} (one count per scene), got {tuple(counts.shape)}")
+    lo, hi = (int(v) for v in torch.stack((counts.min(), counts.max())).tolist())
+    if lo < 1 or hi > M:
+        raise RuntimeError(f"{name} out of range: count {lo if lo < 1 else hi} is not in [1, {M}] (the padded context has {M} rows per scene)")
+    return counts.detach().to(device=device, dtype=torch.int32).contiguous()
+
+
 class _Workspace:
     """Grow-only device scratch owned by a handle (the C ABI never allocates inside compute calls)."""
     def __init__(self):
@@ -272,6 +292,7 @@ class FlowHandle(_Handle):
         c.linear_lu_eps, c.eps_expm = float(config["linear_lu_eps"]), float(config["eps_expm"])
         c.clamp_dist = float(config["clamp_dist"] or 0.0)
         self.latent_dim, self.input_dim, self.X = c.latent_dim, c.input_dim, c.extra_context_dim
+        self.is_global = bool(c.global_context)
         self._create(state_dict, ctypes.byref(c))
         self.n_noise = lib().fc_flow_noise_count(self._h)
         self.noise_width = [lib().fc_flow_noise_width(self._h, i) for i in range(self.n_noise)]
@@ -304,12 +325,21 @@ class FlowHandle(_Handle):
                 raise RuntimeError(f"noise tensor has shape {tuple(e.shape)}, expected {(B, N, wdt)}")
         return x, ctx, extra, eps, B, N, M
 
-    def _forward(self, entry, x, context, extra_context, eps, outputs, layers=None, size_entry="workspace_bytes"):
+    def _forward(self, entry, x, context, extra_context, eps, outputs, layers=None, size_entry="workspace_bytes", context_counts=None):
         """One forward pass through fc_flow_<entry>_f32 (entry: logprob, or a probe entry, whose name opens its messages): the checks of
         _prep, the workspace of fc_flow_<size_entry>, the noise / layer pointer arrays, the call, and the keep-alive of a deferred range check.
         outputs(B, N, M, n_layers) -> (the entry's own arguments between the noise / layer arrays and B, what the caller returns); among
-        those arguments a tensor (or None) goes as its pointer and a list of tensors as an array of pointers."""
+        those arguments a tensor (or None) goes as its pointer and a list of tensors as an array of pointers.
+        context_counts (integer GPU tensor [B], values in [1, M]; _context_counts checks it): scene b attends over context[b, :count_b] only,
+        through fc_flow_<entry>_counts_f32 (include/fcflow_context_counts.h); None is the call without it, unchanged."""
         x, ctx, extra, eps, B, N, M = self._prep(x, context, extra_context, eps)
+        counts, cnt = (), None
+        if context_counts is not None:
+            if self.is_global:
+                raise RuntimeError(f"{entry}: context_counts has no meaning for a flow with config['global'] (its context is per target point)")
+            cnt = _context_counts(context_counts, B, M, self.device)
+            counts = (_ptr(cnt),)
+            entry += "_counts"
         lay = ()
         if layers is not None:
             layers = [int(l) for l in layers]
@@ -330,39 +360,41 @@ class FlowHandle(_Handle):
                 else:
                     args.append(_ptr(a))
                     keep.append(a)
-            self._entry(entry + "_f32")(self._h, _ptr(x), _ptr(ctx), _ptr(extra), eps_arr, len(eps), *lay, *args, B, N, M, _ptr(ws), ws.numel(), _stream())
-            _keep_if_deferred(x, ctx, extra, ws, *eps, *keep)
+            self._entry(entry + "_f32")(self._h, _ptr(x), _ptr(ctx), *counts, _ptr(extra), eps_arr, len(eps), *lay, *args, B, N, M, _ptr(ws), ws.numel(), _stream())
+            _keep_if_deferred(x, ctx, cnt, extra, ws, *eps, *keep)
         return ret
 
-    def log_prob(self, x, context, extra_context, eps, return_latent=False):
+    def log_prob(self, x, context, extra_context, eps, return_latent=False, context_counts=None):
         def outputs(B, N, M, _):
             out = torch.empty(B, N, dtype=torch.float32, device=self.device)
             z = torch.empty(B, N, self.latent_dim, dtype=torch.float32, device=self.device) if return_latent else None
             return [out, z], ((out, z) if return_latent else out)
-        return self._forward("logprob", x, context, extra_context, eps, outputs)
+        return self._forward("logprob", x, context, extra_context, eps, outputs, context_counts=context_counts)
 
-    def attention_weights(self, x, context, extra_context, eps, layers, points=None, return_log_prob=False):
+    def attention_weights(self, x, context, extra_context, eps, layers, points=None, return_log_prob=False, context_counts=None):
         """fc_flow_attention_weights_f32: the forward of log_prob that also writes the softmax rows of the selected target points at the
         requested attentions.  layers: ints, -1 = the augmenter's attention, l >= 0 = flow layer l's pre-conditioner; points: None (all N
-        points) or an integer tensor [P] / [B, P].  Returns a list of [B, P, M] fp32 tensors in the order of `layers` (and the log-prob)."""
+        points) or an integer tensor [P] / [B, P].  Returns a list of [B, P, M] fp32 tensors in the order of `layers` (and the log-prob).
+        With context_counts, columns >= count_b of scene b's rows are exact zeros."""
         def outputs(B, N, M, n_layers):
             sel, P, per_scene = _points_table(points, B, N, self.device)
             outs = [torch.empty(B, P, M, dtype=torch.float32, device=self.device) for _ in range(n_layers)]
             lp = torch.empty(B, N, dtype=torch.float32, device=self.device) if return_log_prob else None
             return [sel, P, per_scene, outs, lp], ((outs, lp) if return_log_prob else outs)
-        return self._forward("attention_weights", x, context, extra_context, eps, outputs, layers)
+        return self._forward("attention_weights", x, context, extra_context, eps, outputs, layers, context_counts=context_counts)
 
-    def attention_mass(self, x, context, extra_context, eps, layers, weights=None, return_log_prob=False):
+    def attention_mass(self, x, context, extra_context, eps, layers, weights=None, return_log_prob=False, context_counts=None):
         """fc_flow_attention_mass_f32: the forward of log_prob that also writes, at the requested attentions, the attention mass of the M
         context points, mass[b, j] = sum_p weights[b, p] * softmax row p [j] over all N target points.  layers: ints as in
         attention_weights; weights: None (ones) or [N] / [B, N], float or bool.  Returns a list of [B, M] fp32 tensors in the order of
-        `layers` (and the log-prob).  The [B, N, M] maps are never formed; the result is the same bytes on every run."""
+        `layers` (and the log-prob).  The [B, N, M] maps are never formed; the result is the same bytes on every run.
+        With context_counts, columns >= count_b of scene b's row are exact zeros."""
         def outputs(B, N, M, n_layers):
             g = _row_weights(weights, B, N, self.device)
             outs = [torch.empty(B, M, dtype=torch.float32, device=self.device) for _ in range(n_layers)]
             lp = torch.empty(B, N, dtype=torch.float32, device=self.device) if return_log_prob else None
             return [g, outs, lp], ((outs, lp) if return_log_prob else outs)
-        return self._forward("attention_mass", x, context, extra_context, eps, outputs, layers, "attention_mass_workspace_bytes")
+        return self._forward("attention_mass", x, context, extra_context, eps, outputs, layers, "attention_mass_workspace_bytes", context_counts=context_counts)
 
     def inverse(self, z, context, extra_context, eps):
         """Inverse pass of Flow.sample from a drawn latent z [B,n,latent_dim] -> x [B,n,input_dim]."""
@@ -618,23 +650,34 @@ def op_premlp_q(x, state_dict, act="gelu", path=0, k_in=None, xprev=None):
     return (q, xnext) if pre else q
 
 
-def op_attention(q, k, v, scale):
+def op_attention(q, k, v, scale, counts=None):
+    """softmax(q k^T * scale) v.  counts (integer GPU tensor [B], values in [1, M]): scene b attends over k[b, :counts[b]] / v[b, :counts[b]]
+    only (fc_op_attention_counts_f32); what the rows beyond hold does not matter."""
     q, k, v = _dev_f32(q), _dev_f32(k), _dev_f32(v)
     B, N, D = q.shape
     M = k.shape[1]
     out = torch.empty_like(q)
     with torch.cuda.device(q.device):
-        lib().fc_op_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, N, M, D, scale, _stream())
+        if counts is None:
+            lib().fc_op_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, N, M, D, scale, _stream())
+        else:
+            cnt = _context_counts(counts, B, M, q.device, "counts")
+            lib().fc_op_attention_counts_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(cnt), B, N, M, D, scale, _stream())
     return out
 
 
-def op_attention_ctx(q, c, scale):
-    """softmax(q c^T * scale) c with one tensor as keys and values, on the folded flow engine's kernels (fc_debug_attention_ctx_f32)."""
+def op_attention_ctx(q, c, scale, counts=None):
+    """softmax(q c^T * scale) c with one tensor as keys and values, on the folded flow engine's kernels (fc_debug_attention_ctx_f32).
+    counts: as in op_attention, over the rows of c (fc_op_attention_ctx_counts_f32)."""
     q, c = _dev_f32(q), _dev_f32(c)
     B, N, D = q.shape
     out = torch.empty_like(q)
     with torch.cuda.device(q.device):
-        _errcheck(lib().fc_debug_attention_ctx_f32(_ptr(q), _ptr(c), _ptr(out), B, N, c.shape[1], D, scale, _stream()))
+        if counts is None:
+            _errcheck(lib().fc_debug_attention_ctx_f32(_ptr(q), _ptr(c), _ptr(out), B, N, c.shape[1], D, scale, _stream()))
+        else:
+            cnt = _context_counts(counts, B, c.shape[1], q.device, "counts")
+            lib().fc_op_attention_ctx_counts_f32(_ptr(q), _ptr(c), _ptr(out), _ptr(cnt), B, N, c.shape[1], D, scale, _stream())
     return out
 
 

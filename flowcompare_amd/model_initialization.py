@@ -161,23 +161,89 @@ def initialize_flow(config, device="cuda", mode="train"):
     return md
 
 
-def _embed_batch(batch, models_dict, config):
+def pad_context_batch(clouds):
+    """Context clouds of different sizes -> the padded batch the `context_counts` arguments take: clouds = a list of [M_b, C] GPU tensors
+    (at least one point each, one C), returns (extract_0 [B, max M_b, C] fp32 with zeros behind every cloud, counts [B] int32 on the same
+    device).  inner_loop((extract_0, extract_1, extra), ..., context_counts=counts) then scores scene b against clouds[b]."""
+    clouds = list(clouds)
+    if not clouds:
+        raise RuntimeError("pad_context_batch: no clouds given")
+    for i, c in enumerate(clouds):
+        if not (torch.is_tensor(c) and c.is_cuda):
+            raise RuntimeError(f"pad_context_batch: cloud {i} must be a tensor on a HIP device (there is no CPU path)")
+        if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] != clouds[0].shape[1] or c.device != clouds[0].device:
+            raise RuntimeError(f"pad_context_batch: cloud {i} has shape {tuple(c.shape)} on {c.device}: every cloud must be [M_b, C] with M_b >= 1, "
+                               f"C = {clouds[0].shape[1] if clouds[0].dim() == 2 else '?'} and on {clouds[0].device}")
+    counts = torch.tensor([c.shape[0] for c in clouds], dtype=torch.int32, device=clouds[0].device)
+    extract_0 = torch.zeros(len(clouds), max(c.shape[0] for c in clouds), clouds[0].shape[1], dtype=torch.float32, device=clouds[0].device)
+    for b, c in enumerate(clouds):
+        extract_0[b, :c.shape[0]] = c
+    return extract_0, counts
+
+
+def _check_context_counts(what, context_counts, batch, models_dict, config):
+    """What `context_counts` cannot be combined with, and the tensor itself (engine._context_counts), before an embedder or the library runs.
+    Returns the counts as a Python list."""
+    from . import engine as _engine
+    flow, embedder = models_dict["flow"], models_dict["input_embedder"]
+    if flow.training or embedder.training:
+        raise RuntimeError(f"{what}: context_counts is eval-mode only (the training path has no per-scene context point counts): "
+                           "initialize_flow(mode='test') or .eval() on the flow and the embedder")
+    if config["global"]:
+        raise RuntimeError(f"{what}: context_counts has no meaning with config['global'] (the global embedder pools a whole cloud into one vector: "
+                           "embed clouds of different sizes one by one instead)")
+    if models_dict.get("sharded"):
+        raise RuntimeError(f"{what}: context_counts is not supported with a sharded models_dict (config['data_parallel']): the scene split does not "
+                           "carry the counts -- give every rank its own scenes and counts through an unsharded models_dict")
+    extract_0 = batch[0]
+    if not (torch.is_tensor(extract_0) and extract_0.is_cuda):
+        raise RuntimeError("flowcompare_amd: tensors must live on a HIP device (there is no CPU path)")
+    return _engine._context_counts(context_counts, extract_0.shape[0], extract_0.shape[1], extract_0.device).tolist()
+
+
+def _embed_batch(batch, models_dict, config, context_counts=None, what="inner_loop"):
     """batch = (extract_0, extract_1, extra_context) -> (extract_1, emb, extra_context) as Flow.log_prob takes them: both clouds sliced to
     input_dim, the extra context repeated over config['sample_size'] points (einops.repeat 'b c -> b n c' in the reference), extract_0
-    embedded and a global embedding repeated over the target points."""
+    embedded and a global embedding repeated over the target points.
+    context_counts ([B] integer GPU tensor): scene b's context cloud is extract_0[b, :count_b], the rows behind it are padding.  In eval mode
+    an embedder row depends on its own scene only, so the scenes are embedded in groups of equal count on the unpadded clouds -- groups in
+    ascending order of count, scene order kept inside a group -- with the embedder as it is (its own limits apply: DGCNN needs count >=
+    n_neighbors, PAConv count >= 256) and written into a zero-initialised [B, M, E]: a scene's embedding is bit for bit what the embedder
+    gives for that scene in a uniform batch of its group.  The cost is one embedder call per DISTINCT count; the flow, more than 95 % of
+    a step, still runs once on the padded batch."""
     extract_0, extract_1, extra_context = batch
     Din = config["input_dim"]
+    if context_counts is not None:
+        counts = _check_context_counts(what, context_counts, batch, models_dict, config)
     extract_0, extract_1 = extract_0[:, :, :Din], extract_1[:, :, :Din]
     if extra_context is not None:
         extra_context = extra_context[:, None, :].expand(-1, config["sample_size"], -1)
+    if context_counts is not None:
+        emb = None
+        for c in sorted(set(counts)):
+            idx = torch.tensor([b for b, cb in enumerate(counts) if cb == c], dtype=torch.long, device=extract_0.device)
+            part = models_dict["input_embedder"](extract_0.index_select(0, idx)[:, :c].contiguous())
+            if emb is None:
+                emb = torch.zeros(extract_0.shape[0], extract_0.shape[1], part.shape[-1], dtype=part.dtype, device=part.device)
+            emb[idx, :c] = part
+        return extract_1, emb, extra_context
     emb = models_dict["input_embedder"](extract_0)
     if config["global"]:
         emb = emb[:, None, :].expand(-1, extract_1.shape[1], -1)
     return extract_1, emb, extra_context
 
 
-def inner_loop(batch, models_dict, config, eps=None):
-    """model_initialization.py:206-228.  `eps` (optional) pins the augmenter noise."""
+def inner_loop(batch, models_dict, config, eps=None, context_counts=None):
+    """model_initialization.py:206-228.  `eps` (optional) pins the augmenter noise.
+    context_counts (optional, eval mode): an integer GPU tensor [B] -- scene b's context is extract_0[b, :count_b] (pad_context_batch builds
+    such a batch from clouds of different sizes); embedded per group of equal count (_embed_batch), one flow call on the padded batch."""
+    if context_counts is not None:
+        extract_1, emb, extra_context = _embed_batch(batch, models_dict, config, context_counts, "inner_loop")
+        with torch.no_grad():
+            log_prob = models_dict["flow"].log_prob(extract_1, context=emb, extra_context=extra_context, eps=eps, context_counts=context_counts)
+            loss = -log_prob.mean()
+            bpd = loss * math.log2(math.exp(1)) / config["input_dim"]
+        return loss, log_prob, bpd
     if models_dict.get("sharded") and not models_dict.get("_in_shard"):
         # config['data_parallel']: `batch` is the GLOBAL batch, every rank runs its own scenes; returns (global loss, LOCAL log_prob, global bpd)
         from . import shard
@@ -194,20 +260,21 @@ def inner_loop(batch, models_dict, config, eps=None):
     return loss, log_prob, bpd
 
 
-def attention_weights(batch, models_dict, config, layers=("aug",), points=None, eps=None, return_log_prob=False):
+def attention_weights(batch, models_dict, config, layers=("aug",), points=None, eps=None, return_log_prob=False, context_counts=None):
     """The attention maps visualize_attention.py colours the context cloud with (there: forward hooks on AttentionMine,
     models/perceiver.py:108-115), from the same pass as inner_loop: batch = (extract_0, extract_1, extra_context) is sliced, embedded and
     expanded exactly as inner_loop does.  layers: "aug" (the augmenter's attention) or 0-based flow-layer indices -- the reference
     script's three maps are layers=("aug", 50, 110); points: None (every target point) or integer indices [P] / [B, P] into extract_1.
     Returns a list of [B, P, M] tensors in the order of `layers` (row p: the weights of target point points[p] over the M context
     points, summing to 1), or (weights, log_prob) with return_log_prob.  The batch is taken as given: no scene sharding under
-    config['data_parallel'] (every rank computes the scenes it is handed).  A full map is 4 B N M bytes per layer."""
-    extract_1, emb, extra_context = _embed_batch(batch, models_dict, config)
+    config['data_parallel'] (every rank computes the scenes it is handed).  A full map is 4 B N M bytes per layer.
+    context_counts as in inner_loop: scene b's rows hold its weights over its first count_b context points and exact zeros beyond."""
+    extract_1, emb, extra_context = _embed_batch(batch, models_dict, config, context_counts, "attention_weights")
     return models_dict["flow"].attention_weights(extract_1, context=emb, extra_context=extra_context, layers=layers, points=points, eps=eps,
-                                                 return_log_prob=return_log_prob)
+                                                 return_log_prob=return_log_prob, context_counts=context_counts)
 
 
-def attention_mass(batch, models_dict, config, layers=("aug",), weights=None, eps=None, return_log_prob=False):
+def attention_mass(batch, models_dict, config, layers=("aug",), weights=None, eps=None, return_log_prob=False, context_counts=None):
     """Attention mass per context point, from the same pass as inner_loop (batch = (extract_0, extract_1, extra_context), sliced,
     embedded and expanded exactly as inner_loop does): mass[b, j] = sum_p weights[b, p] * w[b, p, j] with w the cross-attention softmax
     rows of attention_weights -- which points of the context cloud the target cloud (weights None = ones), its change score or a 0/1
@@ -215,15 +282,16 @@ def attention_mass(batch, models_dict, config, layers=("aug",), weights=None, ep
     order: flow.attention_layers()); weights: None or a GPU tensor [N] / [B, N], float or bool, finite -- a wrong shape, a non-finite
     value or a CPU tensor raises before the library is called.  Returns a list of [B, M] fp32 tensors in the order of `layers`, or
     (masses, log_prob) with return_log_prob.  No [B, N, M] map is formed (4 B M bytes per layer against 4 B N M), and the bytes are
-    the same on every run.  The batch is taken as given: no scene sharding under config['data_parallel']."""
+    the same on every run.  The batch is taken as given: no scene sharding under config['data_parallel'].
+    context_counts as in inner_loop: scene b's row holds the mass on its first count_b context points and exact zeros beyond."""
     from . import engine as _engine
     extract_0, extract_1, _ = batch
     if not (extract_0.is_cuda and extract_1.is_cuda):
         raise RuntimeError("flowcompare_amd: tensors must live on a HIP device (there is no CPU path)")
     _engine._row_weights(weights, extract_1.shape[0], extract_1.shape[1], extract_1.device)      # (refused here, before the embedder runs)
-    extract_1, emb, extra_context = _embed_batch(batch, models_dict, config)
+    extract_1, emb, extra_context = _embed_batch(batch, models_dict, config, context_counts, "attention_mass")
     return models_dict["flow"].attention_mass(extract_1, context=emb, extra_context=extra_context, layers=layers, weights=weights, eps=eps,
-                                              return_log_prob=return_log_prob)
+                                              return_log_prob=return_log_prob, context_counts=context_counts)
 
 
 def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None):

@@ -323,12 +323,31 @@ class Flow(nn.Module):
             shapes += [(B, N, c["cif_latent_dim"] - c["latent_dim"])] * c["n_flow_layers"]
         return shapes
 
-    def log_prob(self, x, context=None, extra_context=None, eps=None):
+    def _check_counts(self, what, context_counts, training=None):
+        """The refusals of `context_counts` that are about the flow, not about the tensor (engine._context_counts checks that)."""
+        if context_counts is None:
+            return
+        if self.training if training is None else training:
+            raise RuntimeError(f"Flow.{what}: context_counts is eval-mode only (the training path has no per-scene context point counts): "
+                               "call .eval() and run under torch.no_grad()")
+        if self._config.get("global"):
+            raise RuntimeError(f"Flow.{what}: context_counts has no meaning with config['global'] (the global embedding is one vector per scene, "
+                               "repeated per target point: no scene has fewer context rows than another)")
+
+    def log_prob(self, x, context=None, extra_context=None, eps=None, context_counts=None):
         """x [B,N,input_dim]; context [B,M,E] ([B,N,E] for the global embedder); extra_context [B,N,X]
         as produced by inner_loop (constant over N) or None.  `eps`: optional list of explicit noise
         tensors (shapes: noise_shapes) making the stochastic forward reproducible; drawn with
-        torch.randn when omitted, like the reference's rsample()."""
+        torch.randn when omitted, like the reference's rsample().
+        context_counts: None, or an integer GPU tensor [B] with values in [1, M]: scene b is conditioned on context[b, :count_b] only,
+        exactly as if it had been passed alone with that slice -- rows beyond are padding whose content does not matter
+        (DESIGN.md section 11g).  Inference only: refused in train mode, on inputs that require grad and with config['global']."""
         eps = self._draw_eps(x, eps)
+        if context_counts is not None:
+            self._check_counts("log_prob", context_counts, training=self.training or (torch.is_grad_enabled() and (
+                x.requires_grad or (context is not None and context.requires_grad))))
+            with torch.no_grad():
+                return self._engine().log_prob(x, context, extra_context, list(eps), context_counts=context_counts)
         if torch.is_grad_enabled() and (self.training or x.requires_grad or (context is not None and context.requires_grad)):
             # training (train.py:108-112): the differentiable path over the HIP training primitives (train_flow.py); the fused
             # inference engine below has no backward
@@ -337,19 +356,22 @@ class Flow(nn.Module):
         from . import library_ops                          # the inference call as a torch.library op (torch.ops.flowcompare_amd.flow_log_prob)
         return torch.ops.flowcompare_amd.flow_log_prob(x, context, extra_context, list(eps), library_ops.register(self._engine()))
 
-    def attention_weights(self, x, context=None, extra_context=None, layers=("aug",), points=None, eps=None, return_log_prob=False):
+    def attention_weights(self, x, context=None, extra_context=None, layers=("aug",), points=None, eps=None, return_log_prob=False, context_counts=None):
         """The cross-attention softmax rows the reference materialises as `attn_weights` (models/perceiver.py:108-115; one forward hook
         per AttentionMine there): for every entry of `layers` -- "aug" = the augmenter's attention, an int l = flow layer l's
         pre-conditioner (0-based) -- a tensor [B, P, M] whose row p holds the weights target point points[p] puts on the M context
         points.  points: None (all N points, P = N) or integer indices [P] (shared by the scenes) / [B, P].  x, context, extra_context
         and eps are those of log_prob (the same pass runs; eps is drawn when omitted and kept in last_eps); with return_log_prob the
-        pass's log-prob comes back too.  Eval mode only.  A full map is 4 B N M bytes per layer: large scenes want `points`."""
+        pass's log-prob comes back too.  Eval mode only.  A full map is 4 B N M bytes per layer: large scenes want `points`.
+        context_counts as in log_prob: scene b's rows hold its weights over context[b, :count_b] and exact zeros beyond."""
         if self.training:
             raise RuntimeError("Flow.attention_weights is eval-mode only (the training path has no attention probe): call .eval() first")
+        self._check_counts("attention_weights", context_counts)
         ids = self._probe_layer_ids(layers, "attention_weights")
         eps = self._draw_eps(x, eps)
         with torch.no_grad():
-            return self._engine().attention_weights(x, context, extra_context, list(eps), ids, points=points, return_log_prob=return_log_prob)
+            return self._engine().attention_weights(x, context, extra_context, list(eps), ids, points=points, return_log_prob=return_log_prob,
+                                                    context_counts=context_counts)
 
     def _probe_layer_ids(self, layers, what):
         """`layers` of attention_weights / attention_mass -> the engine's layer ids: "aug" = -1, an int l = flow layer l."""
@@ -373,15 +395,16 @@ class Flow(nn.Module):
         aug = ["aug"] if c["latent_dim"] > c["input_dim"] else []
         return aug + ([] if c["global"] else list(range(c["n_flow_layers"])))
 
-    def attention_mass(self, x, context=None, extra_context=None, layers=("aug",), weights=None, eps=None, return_log_prob=False):
+    def attention_mass(self, x, context=None, extra_context=None, layers=("aug",), weights=None, eps=None, return_log_prob=False, context_counts=None):
         """Attention mass per context point: for every entry of `layers` (as in attention_weights, or the string "all" = every attention
         of the flow in call order, attention_layers()) a tensor [B, M] with mass[b, j] = sum_p weights[b, p] * w[b, p, j], the weighted
         column sums of that attention's softmax rows w over ALL N target points -- which context points the target cloud (weights None
         = ones), its change score or a 0/1 subset of it relied on.  weights: None or a GPU tensor [N] / [B, N], float or bool, finite.
         The [B, N, M] maps are never formed (the result is 4 B M bytes per layer) and the bytes are the same on every run.  x, context,
-        extra_context, eps and return_log_prob are those of attention_weights.  Eval mode only."""
+        extra_context, eps, return_log_prob and context_counts are those of attention_weights.  Eval mode only."""
         if self.training:
             raise RuntimeError("Flow.attention_mass is eval-mode only (the training path has no attention probe): call .eval() first")
+        self._check_counts("attention_mass", context_counts)
         if isinstance(layers, str) and layers == "all":
             layers = self.attention_layers()
         elif isinstance(layers, str):
@@ -389,7 +412,8 @@ class Flow(nn.Module):
         ids = self._probe_layer_ids(layers, "attention_mass")
         eps = self._draw_eps(x, eps)
         with torch.no_grad():
-            return self._engine().attention_mass(x, context, extra_context, list(eps), ids, weights=weights, return_log_prob=return_log_prob)
+            return self._engine().attention_mass(x, context, extra_context, list(eps), ids, weights=weights, return_log_prob=return_log_prob,
+                                                 context_counts=context_counts)
 
     def sample(self, num_samples, n_points, context=None, sample_distrib=None, extra_context=None, eps=None):
         dist = sample_distrib if sample_distrib is not None else self.sample_dist

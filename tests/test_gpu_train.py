@@ -491,7 +491,7 @@ def _build(fx):
     return cfg, md
 
 
-def _train_step(fx, cfg, md, fp16=True):
+def _train_step(fx, cfg, md, fp16=True, **flow_kw):
     Din = cfg["input_dim"]
     e0, e1, ex = fx.t("extract_0").to(DEV), fx.t("extract_1").to(DEV), fx.t("extra")
     with torch.no_grad():
@@ -503,7 +503,7 @@ def _train_step(fx, cfg, md, fp16=True):
     extra = None if ex is None else ex.to(DEV)[:, None, :].expand(-1, e1.shape[1], -1)
     md["flow"].zero_grad()
     with T.step_guard(fp16=fp16, device=DEV) as guard:
-        lp = TF.flow_log_prob(md["flow"], x, ctx, extra, [e.to(DEV) for e in fx.eps()])
+        lp = TF.flow_log_prob(md["flow"], x, ctx, extra, [e.to(DEV) for e in fx.eps()], **flow_kw)
         loss = -lp.mean()
         loss.backward()
         assert not guard.overflowed()
@@ -877,6 +877,25 @@ def test_full_training_step_is_bit_reproducible():
     assert len(runs[0]) > 90 and all(torch.equal(runs[0][k], runs[1][k]) for k in runs[0])
     md["flow"].eval()
     md["input_embedder"].eval()
+
+
+@pytest.mark.parametrize("case", ["tiny_spline_relu", "tiny_cif"])
+def test_kept_and_recomputed_layers_give_the_same_bits(case):
+    """The keep-or-checkpoint decision moves time, not numbers: without checkpointing (every layer keeps its activations), with an
+    activation budget of 0 (every layer recomputed in backward) and of 1 byte (the first layer kept, the rest recomputed) the log-prob,
+    d loss / d x, d loss / d context and every flow parameter's gradient are bit for bit the same (eval mode, inputs that require grad)."""
+    fx = Fixture("e2e_" + case)
+    cfg, md = _build(fx)
+    runs = []
+    for flow_kw in (dict(checkpoint=False), dict(activation_budget_bytes=0), dict(activation_budget_bytes=1)):
+        loss, lp, x, ctx = _train_step(fx, cfg, md, **flow_kw)
+        runs.append(dict({"flow/" + n: p.grad.clone() for n, p in md["flow"].named_parameters() if p.grad is not None},
+                         log_prob=lp.detach().clone(), dx=x.grad.clone(), dctx=ctx.grad.clone()))
+    assert len(runs[0]) > 10 and torch.isfinite(runs[0]["log_prob"]).all() and runs[0]["dx"].abs().max().item() > 0
+    for other in runs[1:]:
+        assert sorted(other) == sorted(runs[0])
+        differ = [k for k in runs[0] if not torch.equal(runs[0][k], other[k])]
+        assert not differ, differ
 
 
 # ---------------------------------------------------------------- first batch under sharding: global ActNorm statistics, live parameters

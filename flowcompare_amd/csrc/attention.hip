@@ -520,10 +520,9 @@ void launch_context_limbs(const float* ctx, int ldc, unsigned short* img, long r
     int* flag = gemm_fp16_flag();
     if (!flag || dh_pad > 64 || dh_pad % 4 != 0 || ldc % 4 != 0 || ldc < dh_pad || (((uintptr_t)ctx | (uintptr_t)img) & 15))
         throw Error(FC_ERR_INVALID, "context limb image: needs a guard scope, a head dim <= 64 within the row pitch and 16-byte aligned operands");
-    ProfScope ps("fc::kv_limbs_kernel", 0.0, (double)rows * dh_pad * 8.0, s);
     const long n = rows * (dh_pad / 4);
-    hipLaunchKernelGGL(kv_limbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctx, ldc, nullptr, 0, img, nullptr, rows, dh_pad, flag);
-    FC_HIP(hipGetLastError());
+    launch_kernel<kv_limbs_kernel>("fc::kv_limbs_kernel", 0.0, (double)rows * dh_pad * 8.0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctx, ldc, nullptr, 0, img, nullptr,
+                                   rows, dh_pad, flag);
 }
 
 // the split-fp16 kernel's parameters over limb images k16 / v16 of row pitch kv_pitch (16-byte chunks); c16: 1 = slices of a GEMM limb-image output
@@ -557,12 +556,9 @@ bool launch_attention(const AttnQuery& qy, const AttnKeys& kv, const AttnProblem
             const long rows = (long)(B - 1) * pb.m_stride_rows + pb.M;
             unsigned short* k16 = (unsigned short*)kv.limb_ws;
             unsigned short* v16 = k16 + (size_t)rows * 2 * dh_pad;
-            {
-                ProfScope ps("fc::kv_limbs_kernel", 0.0, (double)rows * dh_pad * 16.0, s);
-                const long n = rows * (dh_pad / 4);
-                hipLaunchKernelGGL(kv_limbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kv.k, kv.ldk, kv.v, kv.ldv, k16, v16, rows, dh_pad, flag);
-                FC_HIP(hipGetLastError());
-            }
+            const long n = rows * (dh_pad / 4);
+            launch_kernel<kv_limbs_kernel>("fc::kv_limbs_kernel", 0.0, (double)rows * dh_pad * 16.0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kv.k, kv.ldk, kv.v, kv.ldv,
+                                           k16, v16, rows, dh_pad, flag);
             Attn16Params p = attn16_params(qy, pb, k16, v16, out, ldo, flag, dh_pad / 4, 0);
             p.lse = lse;
             if (dh_pad == 32) launch_attn16_dh<32>(p, B, s); else launch_attn16_dh<64>(p, B, s);

@@ -109,9 +109,8 @@ void launch_attention_mass(const AttnQuery& qy, const AttnKeys& kv, const AttnPr
     }
     const int nwg = (pb.N + 127) / 128;
     const size_t n = (size_t)B * pb.M;
-    ProfScope ps("void fc::attn_mass_reduce_kernel(const float*, float*, int, int, int, const int*)", 0.0, 4.0 * (double)n * (nwg + 1), s);
-    hipLaunchKernelGGL(attn_mass_reduce_kernel, dim3((unsigned)((pb.M + 255) / 256), B), dim3(256), 0, s, slab, out, B, nwg, pb.M, pb.m_counts);
-    FC_HIP(hipGetLastError());
+    launch_kernel<attn_mass_reduce_kernel>("void fc::attn_mass_reduce_kernel(const float*, float*, int, int, int, const int*)", 0.0, 4.0 * (double)n * (nwg + 1),
+                                           dim3((unsigned)((pb.M + 255) / 256), B), dim3(256), 0, s, slab, out, B, nwg, pb.M, pb.m_counts);
 }
 
 }  // namespace fc

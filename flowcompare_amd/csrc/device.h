@@ -1,4 +1,4 @@
-// Device-side idioms every kernel file shares, declared once: vector types, the LDS-DMA builtin, the lane swaps and compile-time loops.
+// Device-side idioms every kernel file shares, declared once: vector types, the LDS-DMA builtin, the lane swaps, the workgroup sum and compile-time loops.
 // activations.h includes this header, so a kernel file that includes activations.h sees it already.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -59,6 +59,19 @@ __device__ __forceinline__ int attn_scene_keys(const int* m_counts, int b, int M
     if (!m_counts) return M;
     const int c = __builtin_amdgcn_readfirstlane(m_counts[b]);
     return c < 1 ? 1 : (c < M ? c : M);
+}
+
+// ---------------------------------------------------------------- sum over a workgroup of up to 256 threads (the row kernels of training)
+// deterministic: xor tree inside each wave, then waves in order.  red: blockDim.x / 64 floats of LDS; every thread gets the sum.
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[w] = v;
+    __syncthreads();
+    float s = red[0];
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) s += red[i];
+    return s;
 }
 
 // ---------------------------------------------------------------- compile-time loop: f(integral_constant<int, 0>{}) ... f(integral_constant<int, N - 1>{})

@@ -17,6 +17,7 @@
 // The trace is summed while the matrix is loaded.  A point whose ||A||_1 needs more than kExpmWideMaxSteps steps raises *status and
 // gets NaN outputs: the series is never returned truncated.
 #include "common.h"
+#include "launch.h"
 
 namespace fc {
 
@@ -208,8 +209,8 @@ __global__ __launch_bounds__(NT) void expm_wide_kernel(const float* __restrict__
 template <int NT, int G, int R, int C>
 static void launch_ew(const float* params, int ldp, const float* x2, int ldx, const float* scal4, float* y2, int ldy, int ypad, float* ldj, int ldj_mode,
                       int rows, int d2, int inverse, int* status, float* info, hipStream_t s) {
-    hipLaunchKernelGGL((expm_wide_kernel<NT, G, R, C>), dim3(rows), dim3(NT), 0, s, params, ldp, x2, ldx, scal4, y2, ldy, ypad, ldj, ldj_mode, d2,
-                       inverse, status, info);
+    launch_kernel<expm_wide_kernel<NT, G, R, C>>(nullptr, 0.0, 0.0, dim3(rows), dim3(NT), 0, s, params, ldp, x2, ldx, scal4, y2, ldy, ypad, ldj, ldj_mode, d2,      // (the caller's scope)
+                                                 inverse, status, info);
 }
 
 void launch_expm_wide(const float* params, int ldp, const float* x2, int ldx, const float* scal4, float* y2, int ldy, int ypad, float* ldj,
@@ -229,7 +230,6 @@ void launch_expm_wide(const float* params, int ldp, const float* x2, int ldx, co
     else if (d2 <= 128) launch_ew<256, 16, 8, 8>(params, ldp, x2, ldx, scal4, y2, ldy, ypad, ldj, ldj_mode, rows, d2, inverse, status, info, s);
     else if (d2 <= 160) launch_ew<256, 16, 10, 10>(params, ldp, x2, ldx, scal4, y2, ldy, ypad, ldj, ldj_mode, rows, d2, inverse, status, info, s);
     else launch_ew<1024, 32, 8, 8>(params, ldp, x2, ldx, scal4, y2, ldy, ypad, ldj, ldj_mode, rows, d2, inverse, status, info, s);
-    FC_HIP(hipGetLastError());
 }
 
 // ---------------------------------------------------------------- training backward, 17 <= d2 <= 160
@@ -242,7 +242,7 @@ void launch_expm_wide(const float* params, int ldp, const float* x2, int ldx, co
 // replayed with the same arithmetic, keeping the step inputs F_0 .. F_{s-2}, every K_st and the last step's terms in LDS.  For st = s .. 1:
 // the step's terms t_0 .. t_{K-1} are in LDS (replayed from F_{st-1} for every step but the last), nu = eta lambda_st, mu_K = nu, and for
 // k = K .. 1:  dA += (mu_k / (s k)) t_{k-1}^T,  mu_{k-1} = nu + A^T mu_k / (s k);  lambda_{st-1} = mu_0.  dx2 = lambda_0, db = dy2,
-// dW = dA + dldj I, then the chain through the tanh rescale as in expm_train_bwd_kernel (train_elem.hip).
+// dW = dA + dldj I, then the chain through the tanh rescale as in expm_train_bwd_kernel (train_expm.hip).
 //
 // One workgroup of 256 lanes per point, the forward's register layout: w[r][c] = A[g + NGRP r][q + G c], and dA in the same layout.  The
 // rank-1 update is R C FMAs from R + C LDS reads.  A^T mu gives each lane C partial column sums over its own R rows; the row groups of a
@@ -518,8 +518,8 @@ __global__ __launch_bounds__(NT) void expm_wide_bwd_kernel(const float* __restri
 template <int NT, int G, int R, int C>
 static void launch_ewb(const float* x2, int ldx, const float* o, int ldo, const float* scal4, const float* dy2, int lddy, const float* dldj, float* dx2,
                        int lddx, float* dout, int lddo, float* dscal, int rows, int d2, int* status, hipStream_t s) {
-    hipLaunchKernelGGL((expm_wide_bwd_kernel<NT, G, R, C>), dim3(rows), dim3(NT), 0, s, x2, ldx, o, ldo, scal4, dy2, lddy, dldj, dx2, lddx,
-                       round_up(d2, 32), dout, lddo, round_up(d2 * d2 + d2, 32), dscal, d2, status);
+    launch_kernel<expm_wide_bwd_kernel<NT, G, R, C>>(nullptr, 0.0, 0.0, dim3(rows), dim3(NT), 0, s, x2, ldx, o, ldo, scal4, dy2, lddy, dldj, dx2, lddx,      // (the caller's scope)
+                                                     round_up(d2, 32), dout, lddo, round_up(d2 * d2 + d2, 32), dscal, d2, status);
 }
 
 }  // namespace fc
@@ -542,7 +542,6 @@ int fc_train_expm_wide_bwd_f32(const float* x2, int32_t ldx, const float* o, int
     else if (d2 <= 64) launch_ewb<256, 16, 4, 4>(x2, ldx, o, ldo, scal4, dy2, lddy, dldj, dx2, lddx, dout, lddo, dscal, rows, d2, (int*)status, s);
     else if (d2 <= 128) launch_ewb<256, 16, 8, 8>(x2, ldx, o, ldo, scal4, dy2, lddy, dldj, dx2, lddx, dout, lddo, dscal, rows, d2, (int*)status, s);
     else launch_ewb<256, 16, 10, 10>(x2, ldx, o, ldo, scal4, dy2, lddy, dldj, dx2, lddx, dout, lddo, dscal, rows, d2, (int*)status, s);
-    FC_HIP(hipGetLastError());
     FC_API_END
 }
 

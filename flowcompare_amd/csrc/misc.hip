@@ -3,6 +3,8 @@
 // kernels (coalesced row reads, wave reductions via DPP shuffles); none of them is reshaped into a GEMM.
 #include "common.h"
 #include "device.h"
+#include "expm_narrow.h"
+#include "launch.h"
 #include "spline.h"
 
 namespace fc {
@@ -46,8 +48,7 @@ __global__ void limb_images_kernel(const float* __restrict__ W, size_t n, int K_
 void launch_limb_images(const float* W, int rows, int K_pad, unsigned short* W3, unsigned short* W2, hipStream_t s) {
     const size_t n = (size_t)rows * K_pad;
     if (!n) return;
-    hipLaunchKernelGGL(limb_images_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, n, K_pad, W3, W2);
-    FC_HIP(hipGetLastError());
+    launch_kernel<limb_images_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, n, K_pad, W3, W2);
 }
 
 // ---------------------------------------------------------------- pack / fill
@@ -62,9 +63,8 @@ __global__ void pack_rows_kernel(const float* __restrict__ src, int src_ld, int 
 void launch_pack_rows(const float* src, int src_ld, int src_cols, float* dst, int dst_ld, int dst_col0, int zero_to, int rows,
                       hipStream_t s) {
     if (rows <= 0) return;
-    ProfScope ps("fc::pack_rows_kernel", 0.0, 4.0 * rows * ((double)src_cols + zero_to), s);
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, src, src_ld, src_cols, dst, dst_ld, dst_col0, zero_to, rows);
-    FC_HIP(hipGetLastError());
+    launch_kernel<pack_rows_kernel>("fc::pack_rows_kernel", 0.0, 4.0 * rows * ((double)src_cols + zero_to), dim3((rows + 3) / 4), dim3(256), 0, s, src, src_ld, src_cols,
+                                    dst, dst_ld, dst_col0, zero_to, rows);
 }
 
 __global__ void fill_kernel(float* p, float v, size_t n) {
@@ -76,9 +76,7 @@ void launch_fill(float* p, float v, size_t n, hipStream_t s) {
     if (!n) return;
     size_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    ProfScope ps("fc::fill_kernel", 0.0, 4.0 * n, s);
-    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, v, n);
-    FC_HIP(hipGetLastError());
+    launch_kernel<fill_kernel>("fc::fill_kernel", 0.0, 4.0 * n, dim3((unsigned)blocks), dim3(256), 0, s, p, v, n);
 }
 
 // Per-scene context point counts (fcflow_context_counts.h): rows >= the scene's count of a [B][M][ld] panel := 0, so that what a caller left in
@@ -94,9 +92,7 @@ void launch_zero_pad_rows(float* panel, int ld, const int32_t* m_counts, int B, 
     if (!m_counts || B <= 0 || M <= 1) return;                                  // (a count is at least 1: one key has no pad row)
     if (ld % 4 != 0 || ((uintptr_t)panel & 15)) throw Error(FC_ERR_INVALID, "zero_pad_rows: the panel must be 16-byte aligned with a pitch that is a multiple of 4 floats");
     const long n4 = (long)(M - 1) * (ld / 4);                                   // the most pad a scene can have
-    ProfScope ps("fc::zero_pad_rows_kernel", 0.0, 16.0 * (double)n4 * B, s);
-    hipLaunchKernelGGL(zero_pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, s, panel, ld / 4, m_counts, M);
-    FC_HIP(hipGetLastError());
+    launch_kernel<zero_pad_rows_kernel>("fc::zero_pad_rows_kernel", 0.0, 16.0 * (double)n4 * B, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, s, panel, ld / 4, m_counts, M);
 }
 
 // extra context [B, X] -> per-point scalar rowscal[b*N + i] = extra[b, 0]   (inner_loop's einops.repeat, X == 1)
@@ -105,8 +101,7 @@ __global__ void repeat_extra_kernel(const float* extra, int X, float* rowscal, i
     if (i < B * N) rowscal[i] = extra[(size_t)(i / N) * X];
 }
 void launch_repeat_extra(const float* extra, int X, float* rowscal, int B, int N, hipStream_t s) {
-    hipLaunchKernelGGL(repeat_extra_kernel, dim3((B * N + 255) / 256), dim3(256), 0, s, extra, X, rowscal, B, N);
-    FC_HIP(hipGetLastError());
+    launch_kernel<repeat_extra_kernel>(nullptr, 0.0, 0.0, dim3((B * N + 255) / 256), dim3(256), 0, s, extra, X, rowscal, B, N);
 }
 
 // ---------------------------------------------------------------- LayerNorm (no affine: gamma/beta are folded into the q projection)
@@ -140,9 +135,7 @@ __global__ void layernorm_kernel(float* h, int ld, int width, int rows) {
 }
 void launch_layernorm(float* h, int ld, int width, int rows, hipStream_t s) {
     if (width > 1024) throw Error(FC_ERR_UNSUPPORTED, "layernorm: width > 1024");
-    ProfScope ps("fc::layernorm_kernel(float*, int, int, int)", 0.0, 8.0 * rows * width, s);
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, h, ld, width, rows);
-    FC_HIP(hipGetLastError());
+    launch_kernel<layernorm_kernel>("fc::layernorm_kernel(float*, int, int, int)", 0.0, 8.0 * rows * width, dim3((rows + 3) / 4), dim3(256), 0, s, h, ld, width, rows);
 }
 
 // q[row, :] = q_unnorm[row, :] * rsqrt(sum_blocks(sumsq[b][row]) / width + 1e-5) + q_bias   (LayerNorm -> q fold, common.h EPI_LNQ)
@@ -159,10 +152,8 @@ __global__ __launch_bounds__(256) void lnq_finalize_kernel(float* __restrict__ q
     *qp = make_float4(v.x * rstd + bq.x, v.y * rstd + bq.y, v.z * rstd + bq.z, v.w * rstd + bq.w);
 }
 void launch_lnq_finalize(float* q, int ldq, const float* sumsq, int nslots, size_t pitch, int width, const float* q_bias, int rows, hipStream_t s) {
-    ProfScope ps("fc::lnq_finalize_kernel", 0.0, 4.0 * rows * (128.0 + nslots), s);
-    hipLaunchKernelGGL(lnq_finalize_kernel, dim3((unsigned)(((long)rows * 16 + 255) / 256)), dim3(256), 0, s, q, ldq, sumsq, nslots, pitch,
-                       1.0f / (float)width, q_bias, rows);
-    FC_HIP(hipGetLastError());
+    launch_kernel<lnq_finalize_kernel>("fc::lnq_finalize_kernel", 0.0, 4.0 * rows * (128.0 + nslots), dim3((unsigned)(((long)rows * 16 + 255) / 256)), dim3(256), 0, s, q, ldq,
+                                       sumsq, nslots, pitch, 1.0f / (float)width, q_bias, rows);
 }
 
 // ---------------------------------------------------------------- base density + latent export
@@ -184,9 +175,8 @@ __global__ void base_density_kernel(const float* __restrict__ x, int ldx, int d1
 }
 void launch_base_density(const float* x, int ldx, int d1, int d1_pad, int d2, float* logprob, float log_const, float* z_out, int D,
                          int rows, hipStream_t s) {
-    ProfScope ps("fc::base_density_kernel", 0.0, 4.0 * rows * (D + 2.0 + (z_out ? D : 0)), s);
-    hipLaunchKernelGGL(base_density_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, ldx, d1, d1_pad, d2, logprob, log_const, z_out, D, rows);
-    FC_HIP(hipGetLastError());
+    launch_kernel<base_density_kernel>("fc::base_density_kernel", 0.0, 4.0 * rows * (D + 2.0 + (z_out ? D : 0)), dim3((rows + 3) / 4), dim3(256), 0, s, x, ldx, d1, d1_pad, d2,
+                                       logprob, log_const, z_out, D, rows);
 }
 
 // One wave per point row; lane j handles dims j, j+64, ...  Parameters arrive in the tile-grouped dim-major layout of spline.h
@@ -220,9 +210,8 @@ void launch_spline(const float* params, int ldp, float* xbuf, int ldx, int x2_co
                    hipStream_t s) {
     spline_bins_require(K, "spline: num_bins_spline");
     if (ldp < spline_ncols(d2, K)) throw Error(FC_ERR_INVALID, "spline: parameter pitch too small");
-    ProfScope ps("fc::spline_rows_kernel", 0.0, 4.0 * rows * ((3.0 * K + 1) * d2 + 2.0 * d2 + 2.0), s);
-    hipLaunchKernelGGL(spline_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, params, ldp, xbuf, ldx, x2_col0, d2, K, logprob, rows, inverse);
-    FC_HIP(hipGetLastError());
+    launch_kernel<spline_rows_kernel>("fc::spline_rows_kernel", 0.0, 4.0 * rows * ((3.0 * K + 1) * d2 + 2.0 * d2 + 2.0), dim3((rows + 3) / 4), dim3(256), 0, s, params, ldp, xbuf,
+                                      ldx, x2_col0, d2, K, logprob, rows, inverse);
 }
 
 // logprob[row] += sum over the column tiles of the fused spline epilogue's per-tile log-det partials (fixed order: reproducible)
@@ -234,9 +223,7 @@ __global__ __launch_bounds__(256) void ldj_reduce_kernel(const float* __restrict
     logprob[row] += s;
 }
 void launch_ldj_reduce(const float* part, int ntiles, size_t pitch, float* logprob, int rows, hipStream_t s) {
-    ProfScope ps("fc::ldj_reduce_kernel", 0.0, 4.0 * rows * (ntiles + 2.0), s);
-    hipLaunchKernelGGL(ldj_reduce_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, part, ntiles, pitch, logprob, rows);
-    FC_HIP(hipGetLastError());
+    launch_kernel<ldj_reduce_kernel>("fc::ldj_reduce_kernel", 0.0, 4.0 * rows * (ntiles + 2.0), dim3((rows + 255) / 256), dim3(256), 0, s, part, ntiles, pitch, logprob, rows);
 }
 
 __global__ void spline_flat_kernel(const float* x, const float* params, float* y, float* lad, int64_t n, int K, int inverse) {
@@ -250,14 +237,13 @@ __global__ void spline_flat_kernel(const float* x, const float* params, float* y
 void launch_spline_flat(const float* x, const float* params, float* y, float* lad, int64_t n, int K, int inverse, hipStream_t s) {
     spline_bins_require(K, "spline: num_bins_spline");
     if (n <= 0) return;
-    hipLaunchKernelGGL(spline_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, params, y, lad, n, K, inverse);
-    FC_HIP(hipGetLastError());
+    launch_kernel<spline_flat_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, params, y, lad, n, K, inverse);
 }
 
 // ---------------------------------------------------------------- exponential coupling
 // models/exponential_coupling.py:44-75: per point, W = rescale*tanh(scale*raw + shift) + reshift + 1e-8 (d2 x d2),
-// y2 = expm(W) x2 + b, ldj = tr W ; inverse x2 = expm(-W)(y2 - b).  expm acts on the vector directly (scaling by 2^-s so that
-// |W|_inf <= 1/2, 12-term Taylor action applied 2^s times): both of the reference's algorithms ('torch' = matrix_exp,
+// y2 = expm(W) x2 + b, ldj = tr W ; inverse x2 = expm(-W)(y2 - b).  expm acts on the vector directly (expm_narrow.h: scaling by 2^-s so
+// that |W|_inf <= 1/2, 12-term Taylor action applied 2^s times): both of the reference's algorithms ('torch' = matrix_exp,
 // 'original' = truncated series with a batch-global stopping rule, utils.py:294-327) converge to this value.
 // One thread per point; only feasible for small d2 (the layer emits d2^2 + d2 numbers per point), like in the reference.
 template <int DMAX>
@@ -265,40 +251,16 @@ __global__ void expm_coupling_kernel(const float* __restrict__ params, int ldp, 
                                      const float* __restrict__ scal4, float* logprob, int rows, int inverse) {
     const int row = blockIdx.x * 64 + threadIdx.x;
     if (row >= rows) return;
-    const float sc = scal4[0], sh = scal4[1], rs = scal4[2], rsh = scal4[3];
     const float* pr = params + (size_t)row * ldp;
-    float w[DMAX * DMAX], v[DMAX], term[DMAX], acc[DMAX];
-    float nrm = 0.f, tr = 0.f;
-    for (int i = 0; i < d2; ++i) {
-        float rsum = 0.f;
-        for (int j = 0; j < d2; ++j) {
-            float wij = rs * tanhf(sc * pr[i * d2 + j] + sh) + rsh + 1e-8f;
-            if (i == j) tr += wij;
-            if (inverse) wij = -wij;
-            w[i * DMAX + j] = wij;
-            rsum += fabsf(wij);
-        }
-        nrm = fmaxf(nrm, rsum);
-    }
+    float w[DMAX * DMAX], v[DMAX];
+    float tr;
+    float nrm = expm_narrow_matrix<DMAX>(pr, d2, scal4, inverse != 0, w, tr);
     float* xr = xbuf + (size_t)row * ldx + x2_col0;
     for (int i = 0; i < d2; ++i) v[i] = inverse ? xr[i] - pr[d2 * d2 + i] : xr[i];
     int s = 0;
     while (nrm > 0.5f && s < 24) { nrm *= 0.5f; ++s; }
     const float f = ldexpf(1.0f, -s);
-    for (int rep = 0; rep < (1 << s); ++rep) {
-        for (int i = 0; i < d2; ++i) { acc[i] = v[i]; term[i] = v[i]; }
-        for (int k = 1; k <= 12; ++k) {
-            float nt[DMAX];
-            const float fk = f / (float)k;
-            for (int i = 0; i < d2; ++i) {
-                float a = 0.f;
-                for (int j = 0; j < d2; ++j) a = fmaf(w[i * DMAX + j], term[j], a);
-                nt[i] = a * fk;
-            }
-            for (int i = 0; i < d2; ++i) { term[i] = nt[i]; acc[i] += nt[i]; }
-        }
-        for (int i = 0; i < d2; ++i) v[i] = acc[i];
-    }
+    for (int rep = 0; rep < (1 << s); ++rep) expm_narrow_action<DMAX, false>(w, d2, f, v, v);
     for (int i = 0; i < d2; ++i) xr[i] = inverse ? v[i] : v[i] + pr[d2 * d2 + i];
     if (!inverse) logprob[row] += tr;
 }
@@ -306,9 +268,8 @@ void launch_expm_coupling(const float* params, int ldp, float* xbuf, int ldx, in
                           int rows, int inverse, hipStream_t s) {
     if (d2 > 16) throw Error(FC_ERR_UNSUPPORTED, "ExponentialCoupling: latent_dim - latent_dim/2 > 16 is not supported (the layer emits d2^2 numbers per point)");
     if (ldp < d2 * d2 + d2) throw Error(FC_ERR_INVALID, "expm coupling: parameter pitch too small");
-    ProfScope ps("fc::expm_coupling_kernel", 0.0, 4.0 * rows * (d2 * d2 + 3.0 * d2), s);
-    hipLaunchKernelGGL(expm_coupling_kernel<16>, dim3((rows + 63) / 64), dim3(64), 0, s, params, ldp, xbuf, ldx, x2_col0, d2, scal4, logprob, rows, inverse);
-    FC_HIP(hipGetLastError());
+    launch_kernel<expm_coupling_kernel<EX_D>>("fc::expm_coupling_kernel", 0.0, 4.0 * rows * (d2 * d2 + 3.0 * d2), dim3((rows + 63) / 64), dim3(64), 0, s, params, ldp, xbuf, ldx,
+                                              x2_col0, d2, scal4, logprob, rows, inverse);
 }
 
 // ---------------------------------------------------------------- DGCNN edge-conv tail
@@ -332,9 +293,8 @@ __global__ void gather_max_kernel(const float* __restrict__ uv, int lduv, int c_
 void launch_gather_max(const float* uv, int lduv, int c_out, const int32_t* idx, int k, float* out, int ldo, int out_col0, int B, int M,
                        int m_stride_rows, hipStream_t s) {
     const int total = B * M;
-    ProfScope ps("fc::gather_max_kernel", 0.0, 4.0 * total * ((double)k * c_out + 2.0 * c_out + k), s);
-    hipLaunchKernelGGL(gather_max_kernel, dim3((total + 3) / 4), dim3(256), 0, s, uv, lduv, c_out, idx, k, out, ldo, out_col0, M, m_stride_rows, total);
-    FC_HIP(hipGetLastError());
+    launch_kernel<gather_max_kernel>("fc::gather_max_kernel", 0.0, 4.0 * total * ((double)k * c_out + 2.0 * c_out + k), dim3((total + 3) / 4), dim3(256), 0, s, uv, lduv, c_out, idx, k,
+                                     out, ldo, out_col0, M, m_stride_rows, total);
 }
 
 // global embedder pooling: out[b] = [max_i t[b,i,:] | mean_i t[b,i,:]]  (models/pytorch_gcn.py:178-182)
@@ -358,8 +318,7 @@ __global__ void pool_max_mean_kernel(const float* __restrict__ t, int ldt, int w
     }
 }
 void launch_pool_max_mean(const float* t, int ldt, int width, float* out, int ldo, int B, int M, int m_stride_rows, hipStream_t s) {
-    hipLaunchKernelGGL(pool_max_mean_kernel, dim3((width + 63) / 64, B), dim3(256), 0, s, t, ldt, width, out, ldo, M, m_stride_rows);
-    FC_HIP(hipGetLastError());
+    launch_kernel<pool_max_mean_kernel>(nullptr, 0.0, 0.0, dim3((width + 63) / 64, B), dim3(256), 0, s, t, ldt, width, out, ldo, M, m_stride_rows);
 }
 
 }  // namespace fc

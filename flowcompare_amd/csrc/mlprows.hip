@@ -508,8 +508,7 @@ void launch_mlp_rows_image(const PackedLinear& L, unsigned short* Wf, hipStream_
         throw Error(FC_ERR_INVALID, "launch_mlp_rows_image: layer is not a K <= 512 -> 512 layer with an fp16 limb image");
     const int ksd = mlp_rows_ks_pad(L.K_pad);
     const long n16 = (long)MR_NB * ksd * 2 * 64;
-    mr_frag_image_kernel<<<dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s>>>(L.W2, L.K_pad / 16, ksd, reinterpret_cast<uint4*>(Wf), n16);
-    FC_HIP(hipGetLastError());
+    launch_kernel<mr_frag_image_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, L.W2, L.K_pad / 16, ksd, reinterpret_cast<uint4*>(Wf), n16);
 }
 
 // row-major limb image [rows][width/16][hi 16 | lo' 16] -> fp32 (fc_op_mlp_hidden_f32: unit tests read the chain's output through it)
@@ -524,8 +523,7 @@ __global__ __launch_bounds__(256) void mr_limb_decode_kernel(const unsigned shor
 void launch_limb_decode(const unsigned short* img, float* out, int ldo, int rows, int width, hipStream_t s) {
     const long n = (long)rows * width;
     if (n <= 0) return;
-    mr_limb_decode_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(img, out, ldo, n, width);
-    FC_HIP(hipGetLastError());
+    launch_kernel<mr_limb_decode_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, out, ldo, n, width);
 }
 
 template <int KS0, int ACT, bool STAMPS = false>

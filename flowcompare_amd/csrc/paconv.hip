@@ -124,8 +124,7 @@ __global__ void gather_xyz_kernel(const float* __restrict__ src, int ld, const i
 void launch_gather_xyz(const float* src, int ld, const int32_t* idx, float* dst, int B, int n, int m, hipStream_t s) {
     const int total = B * m;
     if (total <= 0) return;
-    hipLaunchKernelGGL(gather_xyz_kernel, dim3((total + 255) / 256), dim3(256), 0, s, src, ld, idx, dst, n, m, total);
-    FC_HIP(hipGetLastError());
+    launch_kernel<gather_xyz_kernel>(nullptr, 0.0, 0.0, dim3((total + 255) / 256), dim3(256), 0, s, src, ld, idx, dst, n, m, total);
 }
 
 // ---------------------------------------------------------------- k nearest neighbours in xyz, ascending distance
@@ -222,11 +221,10 @@ void launch_knn_xyz(const float* xyz, int ld, const float* qxyz, int32_t* out, i
     if (k > 32) throw Error(FC_ERR_UNSUPPORTED, "xyz k-NN: nsample > 32");
     // a lane sees ceil(n/64) candidates; its list must be able to hold all of them or k of them, whichever is smaller
     const int need = (n + 63) / 64 < k ? (n + 63) / 64 : k;
-    ProfScope ps("fc::knn_xyz_kernel", 8.0 * total * (double)n, 4.0 * total * k, s);
-    if (need <= 8) hipLaunchKernelGGL(knn_xyz_kernel<8>, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
-    else if (need <= 16) hipLaunchKernelGGL(knn_xyz_kernel<16>, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
-    else hipLaunchKernelGGL(knn_xyz_kernel<32>, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
-    FC_HIP(hipGetLastError());
+    ProfScope ps("fc::knn_xyz_kernel", 8.0 * total * (double)n, 4.0 * total * k, s);      // one scope, whichever list length runs
+    if (need <= 8) launch_kernel<knn_xyz_kernel<8>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
+    else if (need <= 16) launch_kernel<knn_xyz_kernel<16>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
+    else launch_kernel<knn_xyz_kernel<32>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
 }
 
 // ---------------------------------------------------------------- grouping + first PAConv layer input
@@ -272,9 +270,8 @@ void launch_paconv_group(const float* xyz, int ldxyz, const float* feat, int ldf
                          float* gdiff, int B, int n, int m, int K, hipStream_t s) {
     const int total = B * m;
     if (total <= 0) return;
-    ProfScope ps("fc::paconv_group_kernel", 0.0, 4.0 * total * K * (ldE + 4.0 + C), s);
-    hipLaunchKernelGGL(paconv_group_kernel, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ldxyz, feat, ldf, C, qxyz, nidx, E, ldE, gdiff, n, m, K, total);
-    FC_HIP(hipGetLastError());
+    launch_kernel<paconv_group_kernel>("fc::paconv_group_kernel", 0.0, 4.0 * total * K * (ldE + 4.0 + C), dim3((total + 3) / 4), dim3(256), 0, s, xyz, ldxyz, feat, ldf, C, qxyz, nidx,
+                                       E, ldE, gdiff, n, m, K, total);
 }
 
 // ---------------------------------------------------------------- ScoreNet: one thread per edge
@@ -310,9 +307,7 @@ __global__ void scorenet_kernel(const float* __restrict__ gdiff, const float* __
 }
 void launch_scorenet(const float* gdiff, const float* w, float* scores, int edges, hipStream_t s) {
     if (edges <= 0) return;
-    ProfScope ps("fc::scorenet_kernel", 0.0, 48.0 * edges, s);
-    hipLaunchKernelGGL(scorenet_kernel, dim3((edges + 255) / 256), dim3(256), 0, s, gdiff, w, scores, edges);
-    FC_HIP(hipGetLastError());
+    launch_kernel<scorenet_kernel>("fc::scorenet_kernel", 0.0, 48.0 * edges, dim3((edges + 255) / 256), dim3(256), 0, s, gdiff, w, scores, edges);
 }
 
 // ---------------------------------------------------------------- score-weighted kernel assembly + BN + ReLU
@@ -354,10 +349,8 @@ __global__ __launch_bounds__(256) void score_reduce_kernel(const float* __restri
 void launch_score_reduce(const float* G, int ldg, const float* scores, const float* bn_s, const float* bn_t, int Cout, int K, float* dst, int ldd,
                          int dst_col0, int mode, int total_queries, hipStream_t s) {
     if (total_queries <= 0) return;
-    ProfScope ps("fc::score_reduce_kernel", 0.0, 4.0 * total_queries * K * (8.0 * Cout + 8.0 + (mode == 0 ? 2.0 * Cout : 0.0)), s);
-    hipLaunchKernelGGL(score_reduce_kernel, dim3((total_queries + 3) / 4), dim3(256), 0, s, G, ldg, scores, bn_s, bn_t, Cout, K, dst, ldd, dst_col0,
-                       mode, total_queries);
-    FC_HIP(hipGetLastError());
+    launch_kernel<score_reduce_kernel>("fc::score_reduce_kernel", 0.0, 4.0 * total_queries * K * (8.0 * Cout + 8.0 + (mode == 0 ? 2.0 * Cout : 0.0)), dim3((total_queries + 3) / 4),
+                                       dim3(256), 0, s, G, ldg, scores, bn_s, bn_t, Cout, K, dst, ldd, dst_col0, mode, total_queries);
 }
 
 // ---------------------------------------------------------------- feature propagation front end
@@ -414,9 +407,8 @@ void launch_three_nn_interp(const float* uxyz, int ldu, const float* kxyz, int l
     const int total = B * nu;
     if (total <= 0) return;
     if (mk < 1) throw Error(FC_ERR_INVALID, "feature propagation: no known points");
-    ProfScope ps("fc::three_nn_interp_kernel", 8.0 * total * (double)mk, 4.0 * total * (ldX + 3.0 * C2 + C1), s);
-    hipLaunchKernelGGL(three_nn_interp_kernel, dim3((total + 3) / 4), dim3(256), 0, s, uxyz, ldu, kxyz, ldk, Fk, ldfk, C2, Fu, ldfu, C1, X, ldX, nu, mk, total);
-    FC_HIP(hipGetLastError());
+    launch_kernel<three_nn_interp_kernel>("fc::three_nn_interp_kernel", 8.0 * total * (double)mk, 4.0 * total * (ldX + 3.0 * C2 + C1), dim3((total + 3) / 4), dim3(256), 0, s, uxyz, ldu,
+                                          kxyz, ldk, Fk, ldfk, C2, Fu, ldfu, C1, X, ldX, nu, mk, total);
 }
 
 }  // namespace fc

@@ -121,14 +121,9 @@ void launch_voxel_count(const float* cloud, int ld, long P, const float* centers
                         size_t ws_bytes, hipStream_t s) {
     check_voxel_args(cloud, ld, P, centers, K, ws, ws_bytes);
     if (!counts) throw Error(FC_ERR_INVALID, "voxel count: null pointer");
-    {
-        ProfScope ps("fc::voxel_member_kernel<false>", 0.0, voxel_pass_bytes(P, K), s);
-        hipLaunchKernelGGL(voxel_member_kernel<false>, voxel_grid(P, K), dim3(64 * kVoxWaves), 0, s, cloud, ld, (int)P, centers, K, dx * 0.5f, dy * 0.5f,
-                           dz * 0.5f, (int*)ws, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0);
-    }
-    ProfScope ps("fc::voxel_scan_kernel", 0.0, 8.0 * voxel_chunks(P) * (double)K, s);
-    hipLaunchKernelGGL(voxel_scan_kernel, dim3((K + 63) / 64), dim3(64), 0, s, (int*)ws, voxel_chunks(P), K, counts);
-    FC_HIP(hipGetLastError());
+    launch_kernel<voxel_member_kernel<false>>("fc::voxel_member_kernel<false>", 0.0, voxel_pass_bytes(P, K), voxel_grid(P, K), dim3(64 * kVoxWaves), 0, s, cloud, ld, (int)P, centers, K,
+                                              dx * 0.5f, dy * 0.5f, dz * 0.5f, (int*)ws, (const int64_t*)nullptr, (int32_t*)nullptr, (int64_t)0);
+    launch_kernel<voxel_scan_kernel>("fc::voxel_scan_kernel", 0.0, 8.0 * voxel_chunks(P) * (double)K, dim3((K + 63) / 64), dim3(64), 0, s, (int*)ws, voxel_chunks(P), K, counts);
 }
 
 void launch_voxel_select(const float* cloud, int ld, long P, const float* centers, int K, float dx, float dy, float dz, const int64_t* offsets,
@@ -136,10 +131,8 @@ void launch_voxel_select(const float* cloud, int ld, long P, const float* center
     check_voxel_args(cloud, ld, P, centers, K, ws, ws_bytes);
     if (!offsets || rows_cap < 0 || (rows_cap > 0 && !rows)) throw Error(FC_ERR_INVALID, "voxel select: bad argument");
     if (rows_cap == 0) return;
-    ProfScope ps("fc::voxel_member_kernel<true>", 0.0, voxel_pass_bytes(P, K) + 4.0 * rows_cap, s);
-    hipLaunchKernelGGL(voxel_member_kernel<true>, voxel_grid(P, K), dim3(64 * kVoxWaves), 0, s, cloud, ld, (int)P, centers, K, dx * 0.5f, dy * 0.5f,
-                       dz * 0.5f, (int*)const_cast<void*>(ws), offsets, rows, rows_cap);
-    FC_HIP(hipGetLastError());
+    launch_kernel<voxel_member_kernel<true>>("fc::voxel_member_kernel<true>", 0.0, voxel_pass_bytes(P, K) + 4.0 * rows_cap, voxel_grid(P, K), dim3(64 * kVoxWaves), 0, s, cloud, ld, (int)P,
+                                             centers, K, dx * 0.5f, dy * 0.5f, dz * 0.5f, (int*)const_cast<void*>(ws), offsets, rows, rows_cap);
 }
 
 // ---------------------------------------------------------------- ragged farthest point sampling
@@ -288,10 +281,9 @@ void launch_dense_blocks(const float* cloud, int ld, int C, long P, const int64_
     if (C < 3 || C > 8 || ld < C) throw Error(FC_ERR_UNSUPPORTED, "dense blocks: 3..8 columns supported (xyz first)");
     if (P < 1 || P > 0x7fffffffL) throw Error(FC_ERR_INVALID, "dense blocks: bad cloud size");
     if (block < 1 || (long)block * C > 0x7fffffffL) throw Error(FC_ERR_INVALID, "dense blocks: bad block size");
-    ProfScope ps("fc::dense_blocks_kernel", 0.0, 0.0, s);     // the traffic depends on block_offsets, which the host does not read
-    hipLaunchKernelGGL(dense_blocks_kernel, dim3(kDenseGrid), dim3(kDenseThreads), 0, s, cloud, ld, C, (int)P, offsets, rows, voxel_ids, n_voxels, inverse,
-                       block_offsets, block, out, index, block_voxel);
-    FC_HIP(hipGetLastError());
+    // (no byte figure: the traffic depends on block_offsets, which the host does not read)
+    launch_kernel<dense_blocks_kernel>("fc::dense_blocks_kernel", 0.0, 0.0, dim3(kDenseGrid), dim3(kDenseThreads), 0, s,
+                                       cloud, ld, C, (int)P, offsets, rows, voxel_ids, n_voxels, inverse, block_offsets, block, out, index, block_voxel);
 }
 
 }  // namespace fc

@@ -1,5 +1,5 @@
 // Rational-quadratic spline element: the general routine of the stand-alone spline kernels (misc.hip) and the training forward
-// (train_elem.hip), the branch-free forward evaluator of the fused GEMM epilogues (gemm_kernel.h, gemm_spline_persistent.hip,
+// (train_spline.hip), the branch-free forward evaluator of the fused GEMM epilogues (gemm_kernel.h, gemm_spline_persistent.hip,
 // spline_wide.hip), and the column layout of the spline parameter layer's output.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,7 +28,7 @@ __device__ __forceinline__ float fast_div(float a, float b) { return a * __built
 // Running sums of the spline's softmax terms and bin sizes.  Up to 8 bins: one by one.  16 bins: in blocks of four (a block's terms are added to
 // each other, finished blocks to each other, the two once per step).  Fifteen equal bins beside a wide one round the same way at every step of a
 // plain chain, which put the knots 8.6 units of 2^-22 from their fp64 places and mid-bin y 3.6e-5 off (tests/test_gpu_spline_edges.py); in
-// blocks the same parameters come within 2.5.  K <= 8 keeps the chain and its result bits.  rq_spline_bwd_elem (train_elem.hip) sums the same
+// blocks the same parameters come within 2.5.  K <= 8 keeps the chain and its result bits.  rq_spline_bwd_elem (train_spline.hip) sums the same
 // way, so that the training forward and its gradient pick their bins from knots summed alike.
 template <int K>
 struct rq_prefix {
@@ -40,7 +40,7 @@ struct rq_prefix {
     }
 };
 
-// Forward and inverse, with divergent branches for the bin selection.  rq_spline_bwd_elem (train_elem.hip) is the gradient of THIS
+// Forward and inverse, with divergent branches for the bin selection.  rq_spline_bwd_elem (train_spline.hip) is the gradient of THIS
 // routine's forward direction in its own arithmetic (expf, true division, probabilities kept): merging the two would change training bits.
 template <int K>
 __device__ __forceinline__ void rq_spline_elem(float x, const float* u, int us, bool inverse, float& y, float& lad) {

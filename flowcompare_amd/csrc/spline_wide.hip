@@ -528,8 +528,8 @@ void spline_wide_attach(DeviceArena& arena, PackedLinear& L, float wmax, hipStre
     L.bias1 = arena.alloc_floats((size_t)rows + (fold ? 32 : 0));      // (the kernel fetches 256 floats per workgroup tile)
     L.w1_exp = e;
     L.w1_folded = fold;
-    spline_wide_image_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(L.W, L.bias, L.N_pad, L.K_pad, ldexpf(1.f, e), kOneAccActScale * ldexpf(1.f, e), L.W1, L.bias1, n, fold ? 2 : 1);
-    FC_HIP(hipGetLastError());
+    launch_kernel<spline_wide_image_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, L.W, L.bias, L.N_pad, L.K_pad, ldexpf(1.f, e),
+                                            kOneAccActScale * ldexpf(1.f, e), L.W1, L.bias1, n, fold ? 2 : 1);
 }
 
 void launch_spline_wide(const PackedLinear& L, const GemmEpi& e, int rows_alloc, hipStream_t s) {
@@ -587,9 +587,10 @@ void one_acc_gemm_debug(const float* x, const float* W, const float* bias, float
     launch_fill(xp.f(), 0.f, (size_t)rp * K, s);
     FC_HIP(hipMemcpyAsync(xp.f(), x, (size_t)rows * K * 4, hipMemcpyDeviceToDevice, s));
     const size_t nx = (size_t)rp * K, nw = (size_t)N * K;
-    spline_wide_image_kernel<<<dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s>>>(xp.f(), nullptr, rp, K, kOneAccActScale, 0.f, (unsigned short*)xa.p, nullptr, nx, 0);
-    spline_wide_image_kernel<<<dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s>>>(W, bias, N, K, ldexpf(1.f, e), kOneAccActScale * ldexpf(1.f, e), (unsigned short*)wi.p, b1.f(), nw, 0);
-    FC_HIP(hipGetLastError());
+    launch_kernel<spline_wide_image_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, xp.f(), nullptr, rp, K, kOneAccActScale, 0.f,
+                                            (unsigned short*)xa.p, nullptr, nx, 0);
+    launch_kernel<spline_wide_image_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, W, bias, N, K, ldexpf(1.f, e), kOneAccActScale * ldexpf(1.f, e),
+                                            (unsigned short*)wi.p, b1.f(), nw, 0);
     SplineWideParams p{};
     p.A16 = (const unsigned short*)xa.p; p.W1 = (const unsigned short*)wi.p; p.bias1 = b1.f();
     p.KT = K / 32; p.nbm = rp / 256; p.nbn = N / 256; p.ntile128 = N / 128;

@@ -131,9 +131,7 @@ __global__ __launch_bounds__(1024) void co_unit_sphere_kernel(const float* __res
 
 void launch_co_unit_sphere(const float* p0, int n0, const float* p1, int n1, int ld, float* o0, float* o1, float* inverse, int B, hipStream_t s) {
     if (B <= 0 || n0 < 0 || n1 < 0 || n0 + n1 < 1 || ld < 3) throw Error(FC_ERR_INVALID, "co_unit_sphere: bad shape");
-    ProfScope ps("fc::co_unit_sphere_kernel", 0.0, 4.0 * B * (double)(n0 + n1) * ld * 2, s);
-    hipLaunchKernelGGL(co_unit_sphere_kernel, dim3(B), dim3(1024), 0, s, p0, n0, p1, n1, ld, o0, o1, inverse);
-    FC_HIP(hipGetLastError());
+    launch_kernel<co_unit_sphere_kernel>("fc::co_unit_sphere_kernel", 0.0, 4.0 * B * (double)(n0 + n1) * ld * 2, dim3(B), dim3(1024), 0, s, p0, n0, p1, n1, ld, o0, o1, inverse);
 }
 
 // ---------------------------------------------------------------- change map (test_flow.py:241-275)
@@ -255,37 +253,33 @@ __global__ __launch_bounds__(256) void clamp_infs_kernel(float* __restrict__ t, 
 // clamp_infs alone (test_flow.py:241-247); stats4 / status as for launch_change_map
 void launch_clamp_infs(float* t, long n, float* stats4, int* status, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(change_init_kernel, dim3(1), dim3(64), 0, s, stats4, status);
+    launch_kernel<change_init_kernel>(nullptr, 0.0, 0.0, dim3(1), dim3(64), 0, s, stats4, status);
     const unsigned g = (unsigned)std::min<long>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(inf_stats_kernel, dim3(g), dim3(256), 0, s, t, n, stats4);
-    hipLaunchKernelGGL(clamp_infs_kernel, dim3(g), dim3(256), 0, s, t, n, stats4);
-    FC_HIP(hipGetLastError());
+    launch_kernel<inf_stats_kernel>(nullptr, 0.0, 0.0, dim3(g), dim3(256), 0, s, t, n, stats4);
+    launch_kernel<clamp_infs_kernel>(nullptr, 0.0, 0.0, dim3(g), dim3(256), 0, s, t, n, stats4);
 }
 
 void launch_change_map(float* lp10, int N, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff, int use_cutoff,
                        float* stats4, int* status, hipStream_t s) {
     if (B <= 0 || N <= 0 || N0 <= 0) throw Error(FC_ERR_INVALID, "change map: empty input");
-    hipLaunchKernelGGL(change_init_kernel, dim3(1), dim3(64), 0, s, stats4, status);
-    ProfScope ps("fc::change_map_kernel", 0.0, 4.0 * B * (3.0 * N + 3.0 * N0), s);
+    launch_kernel<change_init_kernel>(nullptr, 0.0, 0.0, dim3(1), dim3(64), 0, s, stats4, status);
+    ProfScope ps("fc::change_map_kernel", 0.0, 4.0 * B * (3.0 * N + 3.0 * N0), s);      // one scope over the two statistics passes and the map
     const long n1 = (long)B * N, n0 = (long)B * N0;
-    hipLaunchKernelGGL(inf_stats_kernel, dim3((unsigned)std::min<long>((n1 + 255) / 256, 1024)), dim3(256), 0, s, lp10, n1, stats4);
-    hipLaunchKernelGGL(inf_stats_kernel, dim3((unsigned)std::min<long>((n0 + 255) / 256, 1024)), dim3(256), 0, s, lp00, n0, stats4 + 2);
-    hipLaunchKernelGGL(change_map_kernel, dim3(B), dim3(256), 0, s, lp10, N, lp00, N0, out, stats4, stats4 + 2, multiple, hard_cutoff, use_cutoff,
-                       status);
-    FC_HIP(hipGetLastError());
+    launch_kernel<inf_stats_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)std::min<long>((n1 + 255) / 256, 1024)), dim3(256), 0, s, lp10, n1, stats4);
+    launch_kernel<inf_stats_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)std::min<long>((n0 + 255) / 256, 1024)), dim3(256), 0, s, lp00, n0, stats4 + 2);
+    launch_kernel<change_map_kernel>(nullptr, 0.0, 0.0, dim3(B), dim3(256), 0, s, lp10, N, lp00, N0, out, stats4, stats4 + 2, multiple, hard_cutoff, use_cutoff, status);
 }
 
 void launch_change_map_ragged(float* lp10, const int64_t* offsets, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff,
                               int use_cutoff, float* stats4, int* status, hipStream_t s) {
     if (B <= 0 || N0 <= 0) throw Error(FC_ERR_INVALID, "ragged change map: empty input");
-    hipLaunchKernelGGL(change_init_kernel, dim3(1), dim3(64), 0, s, stats4, status);
-    ProfScope ps("fc::change_map_ragged_kernel", 0.0, 0.0, s);                 // the row count is offsets[B], on the device
+    launch_kernel<change_init_kernel>(nullptr, 0.0, 0.0, dim3(1), dim3(64), 0, s, stats4, status);
+    ProfScope ps("fc::change_map_ragged_kernel", 0.0, 0.0, s);                 // the row count is offsets[B], on the device; one scope over all three launches
     const long n0 = (long)B * N0;
-    hipLaunchKernelGGL(inf_stats_devn_kernel, dim3(1024), dim3(256), 0, s, lp10, offsets + B, stats4);
-    hipLaunchKernelGGL(inf_stats_kernel, dim3((unsigned)std::min<long>((n0 + 255) / 256, 1024)), dim3(256), 0, s, lp00, n0, stats4 + 2);
-    hipLaunchKernelGGL(change_map_ragged_kernel, dim3(B), dim3(256), 0, s, lp10, offsets, lp00, N0, out, stats4, stats4 + 2, multiple, hard_cutoff,
-                       use_cutoff, status);
-    FC_HIP(hipGetLastError());
+    launch_kernel<inf_stats_devn_kernel>(nullptr, 0.0, 0.0, dim3(1024), dim3(256), 0, s, lp10, offsets + B, stats4);
+    launch_kernel<inf_stats_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)std::min<long>((n0 + 255) / 256, 1024)), dim3(256), 0, s, lp00, n0, stats4 + 2);
+    launch_kernel<change_map_ragged_kernel>(nullptr, 0.0, 0.0, dim3(B), dim3(256), 0, s, lp10, offsets, lp00, N0, out, stats4, stats4 + 2, multiple, hard_cutoff, use_cutoff,
+                                            status);
 }
 
 }  // namespace fc

@@ -577,14 +577,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 static void launch_attn_bwd16(const AttnBwdParams& p, int B, int* ovf, hipStream_t s) {
     const double fl = 2.0 * B * (double)p.N * p.M * 64;
-    {
-        ProfScope ps("fc::attn_bwd16_dq_kernel", 4.0 * fl, 0.0, s);
-        hipLaunchKernelGGL(attn_bwd16_dq_kernel, dim3((p.N + 127) / 128, B), dim3(256), 0, s, p, ovf);
-        FC_HIP(hipGetLastError());
-    }
-    ProfScope ps("fc::attn_bwd16_dkv_kernel", 4.0 * fl, 0.0, s);
-    hipLaunchKernelGGL(attn_bwd16_dkv_kernel, dim3((p.M + 127) / 128, B), dim3(256), 0, s, p, ovf);
-    FC_HIP(hipGetLastError());
+    launch_kernel<attn_bwd16_dq_kernel>("fc::attn_bwd16_dq_kernel", 4.0 * fl, 0.0, dim3((p.N + 127) / 128, B), dim3(256), 0, s, p, ovf);
+    launch_kernel<attn_bwd16_dkv_kernel>("fc::attn_bwd16_dkv_kernel", 4.0 * fl, 0.0, dim3((p.M + 127) / 128, B), dim3(256), 0, s, p, ovf);
 }
 
 template <int DH>

@@ -18,6 +18,7 @@
 #include <string>
 
 #include "common.h"
+#include "launch.h"
 
 namespace fc {
 
@@ -223,11 +224,9 @@ int fc_train_edge_stats_f32(const float* P, int32_t ldp, const float* Q, int32_t
     if (!stats || !ws || ws_bytes < fc_train_edge_ws_bytes(rows, C) || ((uintptr_t)ws & 7)) throw Error(FC_ERR_WORKSPACE, "fc_train_edge_stats_f32: workspace too small (fc_train_edge_ws_bytes)");
     hipStream_t s = (hipStream_t)stream;
     const int S = edge_chunks(rows), chunk = (rows + S - 1) / S, ld = round_up(C, 64);
-    ProfScope ps("fc::edge_stats_kernel", 0.0, (double)rows * k * C * 4.0, s);
-    hipLaunchKernelGGL(edge_stats_kernel, dim3((C + 63) / 64, S), dim3(256), 0, s, e, chunk, (double*)ws, ld);
-    FC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(edge_stats_reduce_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const double*)ws, S, ld, stats, C, (double)rows * k, eps);
-    FC_HIP(hipGetLastError());
+    ProfScope ps("fc::edge_stats_kernel", 0.0, (double)rows * k * C * 4.0, s);      // one scope over the partial sums and their reduction
+    launch_kernel<edge_stats_kernel>(nullptr, 0.0, 0.0, dim3((C + 63) / 64, S), dim3(256), 0, s, e, chunk, (double*)ws, ld);
+    launch_kernel<edge_stats_reduce_kernel>(nullptr, 0.0, 0.0, dim3((C + 255) / 256), dim3(256), 0, s, (const double*)ws, S, ld, stats, C, (double)rows * k, eps);
     FC_API_END
 }
 
@@ -236,10 +235,8 @@ int fc_train_edge_fwd_f32(const float* P, int32_t ldp, const float* Q, int32_t l
     FC_API_BEGIN
     const EdgeParams e = edge_params(P, ldp, Q, ldq, idx, rows, k, C, "fc_train_edge_fwd_f32");
     if (!stats || !gamma || !beta || !out || !arg || ldo < C) throw Error(FC_ERR_INVALID, "fc_train_edge_fwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::edge_fwd_kernel", 0.0, (double)rows * k * C * 4.0, s);
-    hipLaunchKernelGGL(edge_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, e, stats, gamma, beta, out, ldo, arg, slope);
-    FC_HIP(hipGetLastError());
+    launch_kernel<edge_fwd_kernel>("fc::edge_fwd_kernel", 0.0, (double)rows * k * C * 4.0, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, e, stats, gamma, beta, out, ldo, arg,
+                                   slope);
     FC_API_END
 }
 
@@ -250,10 +247,8 @@ int fc_train_edge_bwd_prep_f32(const float* P, int32_t ldp, const float* Q, int3
     FC_API_BEGIN
     const EdgeParams e = edge_params(P, ldp, Q, ldq, idx, rows, k, C, "fc_train_edge_bwd_prep_f32");
     if (!stats || !gamma || !beta || !arg || !g || !t1 || !t2 || ldg < C || ldt < C || rows_pad < rows) throw Error(FC_ERR_INVALID, "fc_train_edge_bwd_prep_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::edge_bwd_prep_kernel", 0.0, (double)rows * C * 16.0, s);
-    hipLaunchKernelGGL(edge_bwd_prep_kernel, dim3((rows_pad + 3) / 4), dim3(256), 0, s, e, stats, gamma, beta, arg, g, ldg, t1, t2, ldt, rows_pad, slope);
-    FC_HIP(hipGetLastError());
+    launch_kernel<edge_bwd_prep_kernel>("fc::edge_bwd_prep_kernel", 0.0, (double)rows * C * 16.0, dim3((rows_pad + 3) / 4), dim3(256), 0, (hipStream_t)stream, e, stats, gamma, beta,
+                                        arg, g, ldg, t1, t2, ldt, rows_pad, slope);
     FC_API_END
 }
 
@@ -265,11 +260,8 @@ int fc_train_edge_bwd_scatter_f32(const float* P, int32_t ldp, const float* Q, i
     const EdgeParams e = edge_params(P, ldp, Q, ldq, idx, rows, k, C, "fc_train_edge_bwd_scatter_f32");
     if (!stats || !gamma || !arg || !t1 || !dbeta || !dgamma || (!dP && !dQ) || ldt < C || (dP && lddp < C) || (dQ && lddq < C))
         throw Error(FC_ERR_INVALID, "fc_train_edge_bwd_scatter_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::edge_bwd_scatter_kernel", 0.0, (double)rows * k * C * 8.0, s);
-    hipLaunchKernelGGL(edge_bwd_scatter_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, e, stats, gamma, arg, t1, ldt, dbeta, dgamma,
-                       (float)(1.0 / ((double)rows * k)), dP, lddp, dQ, lddq);
-    FC_HIP(hipGetLastError());
+    launch_kernel<edge_bwd_scatter_kernel>("fc::edge_bwd_scatter_kernel", 0.0, (double)rows * k * C * 8.0, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, e, stats, gamma, arg,
+                                           t1, ldt, dbeta, dgamma, (float)(1.0 / ((double)rows * k)), dP, lddp, dQ, lddq);
     FC_API_END
 }
 
@@ -277,20 +269,16 @@ int fc_train_edge_bwd_scatter_f32(const float* P, int32_t ldp, const float* Q, i
 int fc_train_pool_fwd_f32(const float* t, int32_t ldt, int32_t width, int32_t B, int32_t M, float* out, int32_t ldo, int32_t* arg, void* stream) {
     FC_API_BEGIN
     if (!t || !out || !arg || width < 1 || B < 1 || M < 1 || ldt < width || ldo < 2 * width) throw Error(FC_ERR_INVALID, "fc_train_pool_fwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::pool_train_fwd_kernel", 0.0, (double)B * M * width * 4.0, s);
-    hipLaunchKernelGGL(pool_train_fwd_kernel, dim3((width + 63) / 64, B), dim3(256), 0, s, t, ldt, width, M, out, ldo, (int*)arg);
-    FC_HIP(hipGetLastError());
+    launch_kernel<pool_train_fwd_kernel>("fc::pool_train_fwd_kernel", 0.0, (double)B * M * width * 4.0, dim3((width + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, t, ldt, width, M,
+                                         out, ldo, (int*)arg);
     FC_API_END
 }
 int fc_train_pool_bwd_f32(const float* g, int32_t ldg, const int32_t* arg, int32_t width, int32_t B, int32_t M, float* dt, int32_t lddt, void* stream) {
     FC_API_BEGIN
     if (!g || !arg || !dt || width < 1 || B < 1 || M < 1 || ldg < 2 * width || lddt < width) throw Error(FC_ERR_INVALID, "fc_train_pool_bwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
     const size_t total = (size_t)B * M * width;
-    ProfScope ps("fc::pool_train_bwd_kernel", 0.0, (double)total * 4.0, s);
-    hipLaunchKernelGGL(pool_train_bwd_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, g, ldg, (const int*)arg, width, M, B, dt, lddt);
-    FC_HIP(hipGetLastError());
+    launch_kernel<pool_train_bwd_kernel>("fc::pool_train_bwd_kernel", 0.0, (double)total * 4.0, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0,
+                                         (hipStream_t)stream, g, ldg, (const int*)arg, width, M, B, dt, lddt);
     FC_API_END
 }
 
@@ -303,11 +291,8 @@ int fc_train_edge_bwd_gather_f32(const float* P, int32_t ldp, const float* Q, in
     const EdgeParams e = edge_params(P, ldp, Q, ldq, idx, rows, k, C, "fc_train_edge_bwd_gather_f32");
     if (!idx || !stats || !gamma || !arg || !t1 || !dbeta || !dgamma || !order || !offsets || !dP || ldt < C || lddp < C)
         throw Error(FC_ERR_INVALID, "fc_train_edge_bwd_gather_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::edge_bwd_gather_kernel", 0.0, (double)rows * k * C * 8.0, s);
-    hipLaunchKernelGGL(edge_bwd_gather_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, e, stats, gamma, arg, t1, ldt, dbeta, dgamma,
-                       (float)(1.0 / ((double)rows * k)), order, offsets, dP, lddp);
-    FC_HIP(hipGetLastError());
+    launch_kernel<edge_bwd_gather_kernel>("fc::edge_bwd_gather_kernel", 0.0, (double)rows * k * C * 8.0, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, e, stats, gamma, arg,
+                                          t1, ldt, dbeta, dgamma, (float)(1.0 / ((double)rows * k)), order, offsets, dP, lddp);
     FC_API_END
 }
 

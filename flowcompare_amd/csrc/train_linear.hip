@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "activations.h"
+#include "launch.h"
 #include "train_linear.h"
 
 namespace fc {
@@ -200,12 +201,9 @@ int fc_train_linear_pack_f32(const float* W, const float* bias, int32_t N, const
     FC_API_BEGIN
     const TrainLinearLayout L = train_layout(N, seg_widths, nseg);
     if (!W || !pack || pack_bytes < L.bytes || ((uintptr_t)pack & 255)) throw Error(FC_ERR_INVALID, "fc_train_linear_pack_f32: bad argument (pack must be 256-byte aligned, fc_train_linear_pack_bytes long)");
-    hipStream_t s = (hipStream_t)stream;
     size_t n = std::max((size_t)L.n_alloc * L.K_pad, (size_t)L.k_alloc * L.N_pad);
     if (L.wide) n = std::max(n, std::max((size_t)L.n256 * L.K_pad, (size_t)L.k256 * L.N_pad));
-    ProfScope ps("fc::train_pack_kernel", 0.0, (double)n * 16.0, s);
-    hipLaunchKernelGGL(train_pack_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, W, bias, L, (char*)pack, (int*)ovf);
-    FC_HIP(hipGetLastError());
+    launch_kernel<train_pack_kernel>("fc::train_pack_kernel", 0.0, (double)n * 16.0, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, W, bias, L, (char*)pack, (int*)ovf);
     FC_API_END
 }
 
@@ -249,10 +247,7 @@ int fc_train_act_fwd_f32(const float* u, float* y, int32_t rows_pad, int32_t ld,
     FC_API_BEGIN
     if (!u || !y || rows_pad < 1 || ld < 4 || ld % 4 != 0 || (((uintptr_t)u | (uintptr_t)y) & 15)) throw Error(FC_ERR_INVALID, "fc_train_act_fwd_f32: bad argument");
     const size_t n4 = (size_t)rows_pad * ld / 4;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::act_fwd_kernel", 0.0, (double)n4 * 32.0, s);
-    hipLaunchKernelGGL(act_fwd_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, s, (const float4*)u, (float4*)y, n4, act);
-    FC_HIP(hipGetLastError());
+    launch_kernel<act_fwd_kernel>("fc::act_fwd_kernel", 0.0, (double)n4 * 32.0, dim3(grid_for(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)u, (float4*)y, n4, act);
     FC_API_END
 }
 
@@ -261,10 +256,8 @@ int fc_train_act_bwd_f32(const float* dy, const float* u, float* du, int32_t row
     if (!dy || !u || !du || rows_pad < 1 || rows < 0 || rows > rows_pad || ld < 4 || ld % 4 != 0 || (((uintptr_t)u | (uintptr_t)dy | (uintptr_t)du) & 15))
         throw Error(FC_ERR_INVALID, "fc_train_act_bwd_f32: bad argument");
     const size_t n4 = (size_t)rows_pad * ld / 4, v4 = (size_t)rows * ld / 4;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::act_bwd_kernel", 0.0, (double)n4 * 48.0, s);
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, s, (const float4*)dy, (const float4*)u, (float4*)du, n4, v4, act);
-    FC_HIP(hipGetLastError());
+    launch_kernel<act_bwd_kernel>("fc::act_bwd_kernel", 0.0, (double)n4 * 48.0, dim3(grid_for(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)dy, (const float4*)u,
+                                  (float4*)du, n4, v4, act);
     FC_API_END
 }
 

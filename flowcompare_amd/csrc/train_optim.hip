@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "launch.h"
 
 namespace fc {
 
@@ -94,11 +95,9 @@ int fc_train_sqnorm_f32(const float* g, int64_t n, double* out, int32_t slot, vo
     if (!g || !out || n < 1 || slot < 0 || !ws || ws_bytes < fc_train_sqnorm_ws_bytes(n) || ((uintptr_t)ws & 7)) throw Error(FC_ERR_INVALID, "fc_train_sqnorm_f32: bad argument / workspace");
     hipStream_t s = (hipStream_t)stream;
     const int nparts = (int)((n + OPT_CHUNK - 1) / OPT_CHUNK);
-    ProfScope ps("fc::sqnorm_kernel", 0.0, (double)n * 4.0, s);
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(nparts), dim3(256), 0, s, g, (long)n, (double*)ws);
-    FC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sqnorm_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nparts, out, slot);
-    FC_HIP(hipGetLastError());
+    ProfScope ps("fc::sqnorm_kernel", 0.0, (double)n * 4.0, s);      // one scope over the partial sums and their reduction
+    launch_kernel<sqnorm_kernel>(nullptr, 0.0, 0.0, dim3(nparts), dim3(256), 0, s, g, (long)n, (double*)ws);
+    launch_kernel<sqnorm_reduce_kernel>(nullptr, 0.0, 0.0, dim3(1), dim3(256), 0, s, (const double*)ws, nparts, out, slot);
     FC_API_END
 }
 /* One Adam step (torch.optim.Adam semantics, amsgrad = False) for the T parameter tensors of one bucket: params [T] device array of
@@ -110,10 +109,7 @@ int fc_train_adam_f32(float* const* params, const int64_t* offsets, const int32_
     if (!params || !offsets || !chunk_tensor || !chunk_off || n_chunks < 1 || !g || !m || !v || step < 1) throw Error(FC_ERR_INVALID, "fc_train_adam_f32: bad argument");
     AdamArgs a{params, (const long*)offsets, chunk_tensor, (const long*)chunk_off, g, m, v, coef, lr, beta1, beta2, eps, weight_decay,
                (float)(1.0 - std::pow((double)beta1, (double)step)), (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step))};
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::adam_kernel", 0.0, (double)n_chunks * OPT_CHUNK * 28.0, s);
-    hipLaunchKernelGGL(adam_kernel, dim3(n_chunks), dim3(256), 0, s, a);
-    FC_HIP(hipGetLastError());
+    launch_kernel<adam_kernel>("fc::adam_kernel", 0.0, (double)n_chunks * OPT_CHUNK * 28.0, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, a);
     FC_API_END
 }
 

@@ -14,6 +14,7 @@
 #include <string>
 
 #include "common.h"
+#include "launch.h"
 
 namespace fc {
 __device__ __forceinline__ float sqd3(float ax, float ay, float az, float bx, float by, float bz) {
@@ -229,10 +230,8 @@ int fc_train_paconv_group_f32(const float* xyz, const float* feat, int32_t ldf, 
 int fc_train_softmax_fwd_f32(const float* x, int32_t ldx, int32_t width, int32_t rows, float* y, int32_t ldy, void* stream) {
     FC_API_BEGIN
     if (!x || !y || width < 1 || width > 32 || rows < 1 || ldx < width || ldy < width) throw Error(FC_ERR_INVALID, "fc_train_softmax_fwd_f32: bad argument (width <= 32)");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::softmax_fwd_kernel", 0.0, (double)rows * width * 8.0, s);
-    hipLaunchKernelGGL(softmax_fwd_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, x, ldx, width, rows, y, ldy);
-    FC_HIP(hipGetLastError());
+    launch_kernel<softmax_fwd_kernel>("fc::softmax_fwd_kernel", 0.0, (double)rows * width * 8.0, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, ldx, width, rows, y,
+                                      ldy);
     FC_API_END
 }
 int fc_train_softmax_bwd_f32(const float* y, int32_t ldy, const float* dy, int32_t lddy, int32_t width, int32_t rows, int32_t rows_pad, float* dx,
@@ -240,10 +239,8 @@ int fc_train_softmax_bwd_f32(const float* y, int32_t ldy, const float* dy, int32
     FC_API_BEGIN
     if (!y || !dy || !dx || width < 1 || width > 32 || rows < 1 || rows_pad < rows || ldy < width || lddy < width || lddx < width)
         throw Error(FC_ERR_INVALID, "fc_train_softmax_bwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::softmax_bwd_kernel", 0.0, (double)rows * width * 12.0, s);
-    hipLaunchKernelGGL(softmax_bwd_kernel, dim3((rows_pad + 255) / 256), dim3(256), 0, s, y, ldy, dy, lddy, width, rows, rows_pad, dx, lddx);
-    FC_HIP(hipGetLastError());
+    launch_kernel<softmax_bwd_kernel>("fc::softmax_bwd_kernel", 0.0, (double)rows * width * 12.0, dim3((rows_pad + 255) / 256), dim3(256), 0, (hipStream_t)stream, y, ldy, dy, lddy,
+                                      width, rows, rows_pad, dx, lddx);
     FC_API_END
 }
 /* out [rows_pad, ldo] (pad rows / columns zeroed) = sum_m S[e, m] G[e, m Cout + o] */
@@ -252,10 +249,8 @@ int fc_train_assign_fwd_f32(const float* G, int32_t ldg, const float* S, int32_t
     FC_API_BEGIN
     if (!G || !S || !out || m < 1 || Cout < 1 || rows < 1 || rows_pad < rows || ldg < m * Cout || lds < m || ldo < Cout)
         throw Error(FC_ERR_INVALID, "fc_train_assign_fwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::assign_fwd_kernel", 2.0 * rows * m * Cout, (double)rows * (m * Cout + Cout + m) * 4.0, s);
-    hipLaunchKernelGGL(assign_fwd_kernel, dim3((rows_pad + 3) / 4), dim3(256), 0, s, G, ldg, S, lds, m, Cout, rows, rows_pad, out, ldo);
-    FC_HIP(hipGetLastError());
+    launch_kernel<assign_fwd_kernel>("fc::assign_fwd_kernel", 2.0 * rows * m * Cout, (double)rows * (m * Cout + Cout + m) * 4.0, dim3((rows_pad + 3) / 4), dim3(256), 0,
+                                     (hipStream_t)stream, G, ldg, S, lds, m, Cout, rows, rows_pad, out, ldo);
     FC_API_END
 }
 int fc_train_assign_bwd_f32(const float* G, int32_t ldg, const float* S, int32_t lds, const float* dout, int32_t lddo, int32_t m, int32_t Cout, int32_t rows,
@@ -263,29 +258,23 @@ int fc_train_assign_bwd_f32(const float* G, int32_t ldg, const float* S, int32_t
     FC_API_BEGIN
     if (!G || !S || !dout || !dG || !dS || m < 1 || Cout < 1 || rows < 1 || rows_pad < rows || ldg < m * Cout || lds < m || lddo < Cout || lddg < m * Cout || ldds < m)
         throw Error(FC_ERR_INVALID, "fc_train_assign_bwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::assign_bwd_kernel", 4.0 * rows * m * Cout, (double)rows * (2.0 * m * Cout + Cout + 2.0 * m) * 4.0, s);
-    hipLaunchKernelGGL(assign_bwd_kernel, dim3((rows_pad + 3) / 4), dim3(256), 0, s, G, ldg, S, lds, dout, lddo, m, Cout, rows, rows_pad, dG, lddg, dS, ldds);
-    FC_HIP(hipGetLastError());
+    launch_kernel<assign_bwd_kernel>("fc::assign_bwd_kernel", 4.0 * rows * m * Cout, (double)rows * (2.0 * m * Cout + Cout + 2.0 * m) * 4.0, dim3((rows_pad + 3) / 4), dim3(256), 0,
+                                     (hipStream_t)stream, G, ldg, S, lds, dout, lddo, m, Cout, rows, rows_pad, dG, lddg, dS, ldds);
     FC_API_END
 }
 /* E [groups*K, ldE] = [x_e - x_centre | x_e | 0] for groups of K consecutive rows of x [groups*K, ldx] (centre = first row of the group) */
 int fc_train_centerdiff_fwd_f32(const float* x, int32_t ldx, int32_t C, int32_t K, int32_t groups, float* E, int32_t ldE, void* stream) {
     FC_API_BEGIN
     if (!x || !E || C < 1 || K < 1 || groups < 1 || ldx < C || ldE < 2 * C) throw Error(FC_ERR_INVALID, "fc_train_centerdiff_fwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::centerdiff_fwd_kernel", 0.0, (double)groups * K * (C + ldE) * 4.0, s);
-    hipLaunchKernelGGL(centerdiff_fwd_kernel, dim3((groups + 3) / 4), dim3(256), 0, s, x, ldx, C, K, groups, E, ldE);
-    FC_HIP(hipGetLastError());
+    launch_kernel<centerdiff_fwd_kernel>("fc::centerdiff_fwd_kernel", 0.0, (double)groups * K * (C + ldE) * 4.0, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, ldx, C, K,
+                                         groups, E, ldE);
     FC_API_END
 }
 int fc_train_centerdiff_bwd_f32(const float* dE, int32_t ldE, int32_t C, int32_t K, int32_t groups, float* dx, int32_t lddx, void* stream) {
     FC_API_BEGIN
     if (!dE || !dx || C < 1 || K < 1 || groups < 1 || lddx < C || ldE < 2 * C) throw Error(FC_ERR_INVALID, "fc_train_centerdiff_bwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::centerdiff_bwd_kernel", 0.0, (double)groups * K * (3.0 * C + lddx) * 4.0, s);
-    hipLaunchKernelGGL(centerdiff_bwd_kernel, dim3((groups + 3) / 4), dim3(256), 0, s, dE, ldE, C, K, groups, dx, lddx);
-    FC_HIP(hipGetLastError());
+    launch_kernel<centerdiff_bwd_kernel>("fc::centerdiff_bwd_kernel", 0.0, (double)groups * K * (3.0 * C + lddx) * 4.0, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, dE,
+                                         ldE, C, K, groups, dx, lddx);
     FC_API_END
 }
 /* dsrc [n_src_pad, lds] (everything beyond [n_src, C) zeroed): dsrc[p, c] = sum over t in [offsets[p], offsets[p+1]) of
@@ -296,21 +285,17 @@ int fc_train_rows_gather_bwd_f32(const float* dout, int32_t ldo, int32_t col0, i
     FC_API_BEGIN
     if (!dout || !order || !offsets || !dsrc || col0 < 0 || C < 1 || div < 1 || n_src < 1 || n_src_pad < n_src || ldo < col0 + C || lds < C)
         throw Error(FC_ERR_INVALID, "fc_train_rows_gather_bwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::rows_gather_bwd_kernel", 0.0, (double)n_src * C * 8.0, s);
-    hipLaunchKernelGGL(rows_gather_bwd_kernel, dim3((n_src_pad + 3) / 4), dim3(256), 0, s, dout, ldo, col0, C, order, offsets, wts, div, n_src, n_src_pad, dsrc, lds);
-    FC_HIP(hipGetLastError());
+    launch_kernel<rows_gather_bwd_kernel>("fc::rows_gather_bwd_kernel", 0.0, (double)n_src * C * 8.0, dim3((n_src_pad + 3) / 4), dim3(256), 0, (hipStream_t)stream, dout, ldo, col0, C,
+                                          order, offsets, wts, div, n_src, n_src_pad, dsrc, lds);
     FC_API_END
 }
 /* idx [B*nu, 3] = GLOBAL rows (b * mk + i) of the 3 nearest known points, w [B*nu, 3] = normalised inverse-distance weights. xyz pitch 4. */
 int fc_train_three_nn_f32(const float* uxyz, const float* kxyz, int32_t B, int32_t nu, int32_t mk, int32_t* idx, float* w, void* stream) {
     FC_API_BEGIN
     if (!uxyz || !kxyz || !idx || !w || B < 1 || nu < 1 || mk < 1) throw Error(FC_ERR_INVALID, "fc_train_three_nn_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
     const int total = B * nu;
-    ProfScope ps("fc::three_nn_kernel", 8.0 * total * (double)mk, 24.0 * total, s);
-    hipLaunchKernelGGL(three_nn_kernel, dim3((total + 3) / 4), dim3(256), 0, s, uxyz, 4, kxyz, 4, nu, mk, total, idx, w);
-    FC_HIP(hipGetLastError());
+    launch_kernel<three_nn_kernel>("fc::three_nn_kernel", 8.0 * total * (double)mk, 24.0 * total, dim3((total + 3) / 4), dim3(256), 0, (hipStream_t)stream, uxyz, 4, kxyz, 4, nu, mk,
+                                   total, idx, w);
     FC_API_END
 }
 /* out [rows_pad, ldo] (pads zeroed) = (w0 Fk[idx0] + w1 Fk[idx1]) + w2 Fk[idx2] on the first C columns */
@@ -318,10 +303,8 @@ int fc_train_interp_fwd_f32(const float* Fk, int32_t ldfk, int32_t C, const int3
                             int32_t ldo, void* stream) {
     FC_API_BEGIN
     if (!Fk || !idx || !w || !out || C < 1 || rows < 1 || rows_pad < rows || ldfk < C || ldo < C) throw Error(FC_ERR_INVALID, "fc_train_interp_fwd_f32: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("fc::interp_fwd_kernel", 0.0, (double)rows * C * 16.0, s);
-    hipLaunchKernelGGL(interp_fwd_kernel, dim3((rows_pad + 3) / 4), dim3(256), 0, s, Fk, ldfk, C, idx, w, rows, rows_pad, out, ldo);
-    FC_HIP(hipGetLastError());
+    launch_kernel<interp_fwd_kernel>("fc::interp_fwd_kernel", 0.0, (double)rows * C * 16.0, dim3((rows_pad + 3) / 4), dim3(256), 0, (hipStream_t)stream, Fk, ldfk, C, idx, w, rows,
+                                     rows_pad, out, ldo);
     FC_API_END
 }
 

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "activations.h"
+#include "launch.h"
 #include "train_linear.h"
 
 namespace fc {
@@ -326,11 +327,9 @@ static int colsum_chunks(int rows) { return std::max(1, std::min(256, rows / 128
 // out[c] (=|+=) sum over rows [0, rows) of a[row][c] for c < cols; ws: colsum_chunks(rows) partial rows of round_up(cols, 32) floats
 static void launch_colsum(const float* a, int lda, int cols, int rows, float* out, int accumulate, float* ws, hipStream_t s) {
     const int S = colsum_chunks(rows), chunk = (rows + S - 1) / S, ld = round_up(cols, 32);
-    ProfScope ps("fc::colsum_kernel", 0.0, (double)rows * cols * 4.0, s);
-    hipLaunchKernelGGL(colsum_kernel, dim3((cols + 255) / 256, S), dim3(256), 0, s, a, lda, cols, rows, chunk, ws, ld);
-    FC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(colsum_reduce_kernel, dim3((cols + 255) / 256), dim3(256), 0, s, (const float*)ws, S, ld, out, cols, accumulate);
-    FC_HIP(hipGetLastError());
+    ProfScope ps("fc::colsum_kernel", 0.0, (double)rows * cols * 4.0, s);      // one scope over the partial sums and their reduction
+    launch_kernel<colsum_kernel>(nullptr, 0.0, 0.0, dim3((cols + 255) / 256, S), dim3(256), 0, s, a, lda, cols, rows, chunk, ws, ld);
+    launch_kernel<colsum_reduce_kernel>(nullptr, 0.0, 0.0, dim3((cols + 255) / 256), dim3(256), 0, s, (const float*)ws, S, ld, out, cols, accumulate);
 }
 
 struct WgradPlan { int S, chunk, n128, k128max; size_t part_floats, colsum_floats, bytes; };
@@ -380,21 +379,15 @@ int fc_train_linear_wgrad_f32(int32_t N, const int32_t* seg_widths, int32_t nseg
             check_panel(x[i], ldx[i], L.seg_pad[i], "x");
             const int k128 = round_up(L.seg_pad[i], 128), tiles_k = k128 / 128, tiles_n = w.n128 / 128;
             if (ovf && g_knobs.train_wgrad16) {                   // (knob 11)
-                ProfScope ps("fc::wgrad16_kernel", 2.0 * rows * (double)L.N * L.seg[i], 0.0, s);
-                hipLaunchKernelGGL(wgrad16_kernel, dim3(tiles_n * tiles_k, w.S), dim3(256), 0, s, du, ldu, L.N_pad, x[i], ldx[i], L.seg_pad[i], rows,
-                                   w.chunk, tiles_k, part, w.n128, k128, (db && i == 0) ? cpart : nullptr, w.n128, (int*)ovf);
-                FC_HIP(hipGetLastError());
+                launch_kernel<wgrad16_kernel>("fc::wgrad16_kernel", 2.0 * rows * (double)L.N * L.seg[i], 0.0, dim3(tiles_n * tiles_k, w.S), dim3(256), 0, s, du, ldu, L.N_pad, x[i],
+                                              ldx[i], L.seg_pad[i], rows, w.chunk, tiles_k, part, w.n128, k128, (db && i == 0) ? cpart : nullptr, w.n128, (int*)ovf);
             } else {
-                ProfScope ps("fc::wgrad_kernel", 2.0 * rows * (double)L.N * L.seg[i], 0.0, s);
-                hipLaunchKernelGGL(wgrad_kernel, dim3(tiles_n * tiles_k, w.S), dim3(256), 0, s, du, ldu, L.N_pad, x[i], ldx[i], L.seg_pad[i], rows,
-                                   w.chunk, tiles_k, part, w.n128, k128, (db && i == 0) ? cpart : nullptr, w.n128);
-                FC_HIP(hipGetLastError());
+                launch_kernel<wgrad_kernel>("fc::wgrad_kernel", 2.0 * rows * (double)L.N * L.seg[i], 0.0, dim3(tiles_n * tiles_k, w.S), dim3(256), 0, s, du, ldu, L.N_pad, x[i], ldx[i],
+                                            L.seg_pad[i], rows, w.chunk, tiles_k, part, w.n128, k128, (db && i == 0) ? cpart : nullptr, w.n128);
             }
             const size_t total = (size_t)L.N * L.seg[i];
-            ProfScope ps("fc::wgrad_reduce_kernel", 0.0, (double)total * 4.0 * (w.S + 1), s);
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(total + L.N, 256)), dim3(256), 0, s, part, w.S, w.n128, k128, dW, L.N, L.K, k_off,
-                               L.seg[i], accumulate, cpart, w.n128, (db && i == 0) ? db : nullptr);
-            FC_HIP(hipGetLastError());
+            launch_kernel<wgrad_reduce_kernel>("fc::wgrad_reduce_kernel", 0.0, (double)total * 4.0 * (w.S + 1), dim3(grid_for(total + L.N, 256)), dim3(256), 0, s, part, w.S, w.n128,
+                                               k128, dW, L.N, L.K, k_off, L.seg[i], accumulate, cpart, w.n128, (db && i == 0) ? db : nullptr);
             k_off += L.seg[i];
         }
     }

@@ -1,6 +1,7 @@
 """Training path, first slice: the residual MLP of models/nets.py:19-30 as torch.autograd Functions whose
 forward AND backward are HIP kernels behind the C ABI (include/fcflow.h, fc_train_*; kernels in csrc/train_linear.hip, train_wgrad.hip + the GEMM of the
-inference path).  torch is plumbing: it owns the tensors, the stream and the autograd graph between the primitives; there is no
+inference path; the later slices in train_attention.hip, train_spline.hip, train_rows.hip, train_expm.hip + expm_wide.hip, train_edge.hip,
+train_paconv.hip and train_optim.hip).  torch is plumbing: it owns the tensors, the stream and the autograd graph between the primitives; there is no
 PyTorch arithmetic on activations here and no CPU fallback.
 
 Activations travel as PANELS: contiguous fp32 [rows_pad, width_pad], rows padded to 256 and widths to 32 with zero pad columns

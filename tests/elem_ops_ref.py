@@ -1,5 +1,5 @@
-"""Plain differentiable torch references of the flow's per-point training closures (csrc/train_elem.hip: affine coupling, the augmenter's
-Gaussian draw, the Slice log-density, the base density, ExponentialCoupling at d2 <= 16) and of the stand-alone activation passes
+"""Plain differentiable torch references of the flow's per-point training closures (csrc/train_rows.hip: affine coupling, the augmenter's
+Gaussian draw, the Slice log-density, the base density; csrc/train_expm.hip: ExponentialCoupling at d2 <= 16) and of the stand-alone activation passes
 (csrc/train_linear.hip), the inputs of their operator tests and the narrow ExponentialCoupling gate.  Everything works on dense [rows, c] tensors
 in whatever dtype it is given: fp64 is the reference, the same function in eager fp32 on the CPU is the yardstick
 (tests/test_gpu_train_elem_ops.py, with embed_ops_ref.gate).  Written from the formulae in the kernel headers;

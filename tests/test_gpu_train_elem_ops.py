@@ -1,5 +1,5 @@
-"""The flow's element training operators one by one (csrc/train_elem.hip through train_ops.AffineFn / GaussDrawFn / NormalLogProbFn /
-BaseDensityFn / ExpmCouplingFn and the C entries fc_train_expm_fwd_f32 / fc_train_expm_bwd_f32; csrc/train_wgrad.hip and train_linear.hip through
+"""The flow's element training operators one by one (csrc/train_rows.hip through train_ops.AffineFn / GaussDrawFn / NormalLogProbFn /
+BaseDensityFn, csrc/train_expm.hip through ExpmCouplingFn and the C entries fc_train_expm_fwd_f32 / fc_train_expm_bwd_f32; csrc/train_wgrad.hip and train_linear.hip through
 fc_train_colsum_f32, fc_train_act_fwd_f32 and fc_train_act_bwd_f32): forward and backward element-wise against the plain fp64 references
 of tests/elem_ops_ref.py (pinned to the oracle by test_oracle_elem_ops.py).
 
@@ -11,7 +11,7 @@ either side (asserted on the CPU).  The narrow ExponentialCoupling kernels: y2, 
 Outputs and gradients come from dirtied allocations (`_dirt`, which also checks that the allocator hands the dirt back): every pad column
 of a valid row and every pad row must be exactly 0.
 
-Kernel -> test:
+Kernel -> test (affine .. base: train_rows.hip; expm: train_expm.hip, arithmetic in expm_narrow.h; colsum: train_wgrad.hip; act: train_linear.hip):
   affine_train_fwd_kernel, affine_train_bwd_kernel   test_affine_matches_fp64 (exp and sigmoid; d scale and d shift apart)
   gauss_train_fwd_kernel, gauss_train_bwd_kernel     test_gauss_draw_matches_fp64 (clamp 0, 10, 0.5; odd eps pitch)
   normlp_train_fwd_kernel, normlp_train_bwd_kernel   test_normal_log_prob_matches_fp64 (clamp 0, 10, 0.5; v in a wider panel)

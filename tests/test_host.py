@@ -214,6 +214,18 @@ def test_debug_table_equals_the_definitions():
     assert abi.DEBUG_ENTRIES["fc_debug_name"][0] == "str"
 
 
+def test_every_kernel_launch_goes_through_launch_h():
+    """csrc/launch.h's launch_kernel is the one launch sequence (profile scope, launch, launch check): the raw launch macro and the
+    chevron syntax appear in no other source file.  The element training operators live in train_spline.hip, train_rows.hip and
+    train_expm.hip; the file they were split from is gone."""
+    csrc = os.path.join(ROOT, "flowcompare_amd", "csrc")
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".cpp", ".hip")))
+    raw = {f: len(re.findall(r"hipLaunchKernelGGL|<<<", open(os.path.join(csrc, f)).read())) for f in sources}
+    assert {f: n for f, n in raw.items() if n} == {"launch.h": 1}
+    assert "train_elem.hip" not in sources
+    assert {"train_spline.hip", "train_rows.hip", "train_expm.hip", "expm_narrow.h"} <= set(sources)
+
+
 def test_lib_binds_every_table_entry():
     """engine.lib() gives every table entry the library exports its argtypes and restype; FC_* status entries raise by themselves, value
     entries and the fc_debug_* entries hand back what the C function returned."""

@@ -1,6 +1,6 @@
 """Pins the fp64 references of the flow's element training operators (tests/elem_ops_ref.py) to the oracle, checks on the CPU that the
 inputs committed for the GPU tests (tests/test_gpu_train_elem_ops.py) decide every clamp and keep every matrix norm on its side of the
-narrow ExponentialCoupling kernel's bound, and measures the yardstick of that kernel's gate."""
+narrow ExponentialCoupling kernel's bound (csrc/train_expm.hip), and measures the yardstick of that kernel's gate."""
 import math
 
 import pytest

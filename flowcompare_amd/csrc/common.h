@@ -13,6 +13,7 @@
 #include "../../include/fcflow.h"
 #include "../../include/fcflow_attention_mass.h"
 #include "../../include/fcflow_context_counts.h"
+#include "../../include/fcflow_sparse_stage.h"
 #include "knobs.h"
 
 namespace fc {

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "launch.h"
 #include "fps_dist.h"
+#include "block_reduce.h"
 
 #include <algorithm>
 
@@ -197,6 +198,22 @@ __device__ __forceinline__ void fps_ragged_body(const float* __restrict__ cloud,
     }
 }
 
+// One voxel's sampling on the residency path its size asks for, the choice fps_ragged_kernel makes; false when no path holds the voxel
+// (refused by the host beforehand).  fps_ragged_kernel keeps its own three lines: routed through this helper hipcc gives it 32 VGPRs, not 30.
+__device__ __forceinline__ bool fps_ragged_voxel(const float* __restrict__ cloud, int ld, int C, int P, const int32_t* __restrict__ vr, int n, int m,
+                                                 int64_t* __restrict__ out, float* sm, int lds_floats, float* __restrict__ dist_scratch, int64_t off, float* red_v,
+                                                 int* red_i, int* s_last) {
+    if ((int64_t)n * (C + 1) <= lds_floats)
+        fps_ragged_body<true>(cloud, ld, C, P, vr, n, m, out, sm, sm + n, red_v, red_i, s_last);
+    else if (n <= min(lds_floats, kFpsLdsDist))
+        fps_ragged_body<false>(cloud, ld, C, P, vr, n, m, out, sm, nullptr, red_v, red_i, s_last);
+    else if (dist_scratch)
+        fps_ragged_body<false>(cloud, ld, C, P, vr, n, m, out, dist_scratch + off, nullptr, red_v, red_i, s_last);
+    else
+        return false;
+    return true;
+}
+
 __global__ __launch_bounds__(1024) void fps_ragged_kernel(const float* __restrict__ cloud, int ld, int C, int P, const int64_t* __restrict__ offsets,
                                                           const int32_t* __restrict__ rows, const int32_t* __restrict__ voxel_ids,
                                                           int64_t* __restrict__ idx, int m, int lds_floats, float* __restrict__ dist_scratch) {
@@ -219,19 +236,104 @@ __global__ __launch_bounds__(1024) void fps_ragged_kernel(const float* __restric
         fps_ragged_body<false>(cloud, ld, C, P, vr, n, m, out, dist_scratch + off, nullptr, red_v, red_i, &s_last);
 }
 
+// The same with a sample count per voxel: a listed voxel with n rows takes m_v = min(n, m) picks -- fps_ragged_voxel
+// with m_v in place of m, so idx[v, :m_v] is what the kernel above gives for m_v samples -- and the workgroup itself writes the literal -1 into
+// idx[v, m_v:] and m_v into sample_counts[v]: the outputs need no initialisation.  A voxel without rows (or one no residency path holds)
+// writes count 0 and a row of -1.
+__global__ __launch_bounds__(1024) void fps_ragged_counts_kernel(const float* __restrict__ cloud, int ld, int C, int P, const int64_t* __restrict__ offsets,
+                                                                 const int32_t* __restrict__ rows, const int32_t* __restrict__ voxel_ids,
+                                                                 int64_t* __restrict__ idx, int32_t* __restrict__ sample_counts, int m, int lds_floats,
+                                                                 float* __restrict__ dist_scratch) {
+    extern __shared__ float sm[];
+    __shared__ float red_v[16];
+    __shared__ int red_i[16];
+    __shared__ int s_last;
+    const int v = voxel_ids ? voxel_ids[blockIdx.x] : (int)blockIdx.x;
+    const int64_t off = offsets[v];
+    const int64_t n64 = offsets[v + 1] - off;
+    int64_t* out = idx + (size_t)blockIdx.x * m;
+    int m_v = n64 < 1 || n64 > 0x7fffffff ? 0 : (int)min(n64, (int64_t)m);      // uniform over the workgroup
+    if (m_v > 0 && !fps_ragged_voxel(cloud, ld, C, P, rows + off, (int)n64, m_v, out, sm, lds_floats, dist_scratch, off, red_v, red_i, &s_last))
+        m_v = 0;
+    for (int j = m_v + (int)threadIdx.x; j < m; j += 1024) out[j] = -1;
+    if (threadIdx.x == 0) sample_counts[blockIdx.x] = m_v;
+}
+
+// sample_counts null: fps_ragged_kernel (every listed voxel has at least m rows); otherwise fps_ragged_counts_kernel, where m may exceed max_rows
+// (every listed voxel is sparse).
 void launch_fps_ragged(const float* cloud, int ld, int C, long P, const int64_t* offsets, const int32_t* rows, const int32_t* voxel_ids, int n_voxels,
-                       int max_rows, int m, int64_t* idx, float* dist_scratch, hipStream_t s) {
+                       int max_rows, int m, int64_t* idx, int32_t* sample_counts, float* dist_scratch, hipStream_t s) {
     if (n_voxels <= 0 || m <= 0) return;
     if (!cloud || !offsets || !rows || !idx) throw Error(FC_ERR_INVALID, "ragged fps: null pointer");
     if (C < 1 || C > 8 || ld < C) throw Error(FC_ERR_UNSUPPORTED, "fps: 1..8 feature columns supported");
     if (P < 1 || P > 0x7fffffffL) throw Error(FC_ERR_INVALID, "ragged fps: bad cloud size");
-    if (m > max_rows) throw Error(FC_ERR_INVALID, "fps: more samples than points");
+    if (max_rows < 0) throw Error(FC_ERR_INVALID, "ragged fps: bad max_rows");
+    if (!sample_counts && m > max_rows) throw Error(FC_ERR_INVALID, "fps: more samples than points");
     if (max_rows > kFpsLdsDist && !dist_scratch)
         throw Error(FC_ERR_WORKSPACE, "ragged fps: voxels above 24576 rows need a float scratch as long as the row list");
     const long want = (long)max_rows * (C + 1);
     const int lds_floats = want <= kFpsLdsFloats ? (int)want : kFpsLdsFloats;          // >= min(max_rows, 24576) either way
-    launch_kernel<fps_ragged_kernel, kFpsLdsFloats * 4>("fc::fps_ragged_kernel", 0.0, 4.0 * n_voxels * ((double)max_rows * (C + 1) + 2.0 * m), dim3(n_voxels), dim3(1024),
-                                                        (size_t)lds_floats * sizeof(float), s, cloud, ld, C, (int)P, offsets, rows, voxel_ids, idx, m, lds_floats, dist_scratch);
+    const double bytes = 4.0 * n_voxels * ((double)max_rows * (C + 1) + 2.0 * m);
+    if (!sample_counts)
+        launch_kernel<fps_ragged_kernel, kFpsLdsFloats * 4>("fc::fps_ragged_kernel", 0.0, bytes, dim3(n_voxels), dim3(1024), (size_t)lds_floats * sizeof(float), s, cloud, ld, C,
+                                                            (int)P, offsets, rows, voxel_ids, idx, m, lds_floats, dist_scratch);
+    else
+        launch_kernel<fps_ragged_counts_kernel, kFpsLdsFloats * 4>("fc::fps_ragged_counts_kernel", 0.0, bytes, dim3(n_voxels), dim3(1024), (size_t)lds_floats * sizeof(float), s,
+                                                                   cloud, ld, C, (int)P, offsets, rows, voxel_ids, idx, sample_counts, m, lds_floats, dist_scratch);
+}
+
+// ---------------------------------------------------------------- gather + joint normalisation with a context count per pair
+// One workgroup per pair k: its context cloud is the c = clamp(counts_0[k], 1, M) rows of cloud_0 named by index_0[k, :c], its target cloud the
+// N rows of cloud_1 named by index_1[k] (the lists the ragged FPS kernels write; -1 behind c is never read).  The rows are read straight through
+// the lists -- no gathered intermediate -- and normalised with co_unit_sphere_kernel's operations in that kernel's order (staging.hip: strided
+// sums over the joint index, block_sum / block_max of block_reduce.h, subtract then divide), so the result is bit for bit what that kernel gives
+// for the pair (cloud_0[index_0[k, :c]], cloud_1[index_1[k]]).  Rows c .. M-1 of out_0[k] are written as 0.0f: the outputs need no initialisation.
+__global__ __launch_bounds__(1024) void stage_pairs_counts_kernel(const float* __restrict__ cloud_0, int P0, const float* __restrict__ cloud_1, int P1, int ld,
+                                                                  const int64_t* __restrict__ index_0, const int64_t* __restrict__ index_1,
+                                                                  const int32_t* __restrict__ counts_0, int M, int N, float* __restrict__ o0,
+                                                                  float* __restrict__ o1, float* __restrict__ inverse) {
+    __shared__ float red[16];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n0 = min(max(counts_0[b], 1), M), n = n0 + N;
+    const int64_t* i0 = index_0 + (size_t)b * M;
+    const int64_t* i1 = index_1 + (size_t)b * N;
+    auto row = [&](int k) {                                    // clamped: a bad list cannot read outside the clouds
+        return k < n0 ? cloud_0 + (size_t)min(max(i0[k], (int64_t)0), (int64_t)P0 - 1) * ld
+                      : cloud_1 + (size_t)min(max(i1[k - n0], (int64_t)0), (int64_t)P1 - 1) * ld;
+    };
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int k = tid; k < n; k += 1024) {
+        const float* r = row(k);
+        sx += r[0]; sy += r[1]; sz += r[2];
+    }
+    const float mx = block_sum(sx, red) / (float)n, my = block_sum(sy, red) / (float)n, mz = block_sum(sz, red) / (float)n;
+    float far2 = 0.f;
+    for (int k = tid; k < n; k += 1024) {
+        const float* r = row(k);
+        const float x = r[0] - mx, y = r[1] - my, z = r[2] - mz;
+        far2 = fmaxf(far2, sqrtf((x * x + y * y) + z * z));
+    }
+    const float far = block_max(far2, red);
+    float* w0 = o0 + (size_t)b * M * ld;
+    for (int k = tid; k < n; k += 1024) {
+        const float* r = row(k);
+        float* w = k < n0 ? w0 + (size_t)k * ld : o1 + ((size_t)b * N + (k - n0)) * ld;
+        w[0] = (r[0] - mx) / far; w[1] = (r[1] - my) / far; w[2] = (r[2] - mz) / far;
+        for (int col = 3; col < ld; ++col) w[col] = r[col];
+    }
+    for (int e = n0 * ld + tid; e < M * ld; e += 1024) w0[e] = 0.0f;
+    if (tid == 0) { inverse[4 * b] = far; inverse[4 * b + 1] = mx; inverse[4 * b + 2] = my; inverse[4 * b + 3] = mz; }
+}
+
+void launch_stage_pairs_counts(const float* cloud_0, long P0, const float* cloud_1, long P1, int ld, const int64_t* index_0, const int64_t* index_1,
+                               const int32_t* counts_0, int n_pairs, int M, int N, float* out_0, float* out_1, float* inverse, hipStream_t s) {
+    if (n_pairs <= 0) return;
+    if (!cloud_0 || !cloud_1 || !index_0 || !index_1 || !counts_0 || !out_0 || !out_1 || !inverse) throw Error(FC_ERR_INVALID, "stage pairs: null pointer");
+    if (ld < 3 || ld > 8) throw Error(FC_ERR_UNSUPPORTED, "stage pairs: 3..8 columns supported (xyz first)");
+    if (P0 < 1 || P0 > 0x7fffffffL || P1 < 1 || P1 > 0x7fffffffL) throw Error(FC_ERR_INVALID, "stage pairs: bad cloud size");
+    if (M < 1 || N < 0 || (long)M * ld > 0x7fffffffL || (long)M + N > 0x7fffffffL) throw Error(FC_ERR_INVALID, "stage pairs: bad sample counts");
+    launch_kernel<stage_pairs_counts_kernel>("fc::stage_pairs_counts_kernel", 0.0, 4.0 * n_pairs * ((double)(M + N) * (2.0 * ld + 2.0)), dim3(n_pairs), dim3(1024), 0, s,
+                                             cloud_0, (int)P0, cloud_1, (int)P1, ld, index_0, index_1, counts_0, M, N, out_0, out_1, inverse);
 }
 
 // ---------------------------------------------------------------- dense blocks: ALL members of the staged voxels
@@ -310,7 +412,27 @@ int fc_stage_fps_ragged_f32(const float* cloud, int32_t ld, int32_t C, int64_t P
                             int32_t n_voxels, int32_t max_rows, int32_t m, int64_t* idx, float* dist_scratch, void* stream) {
     FC_API_BEGIN
     if (n_voxels < 0 || m < 1) throw fc::Error(FC_ERR_INVALID, "fc_stage_fps_ragged_f32: bad argument");
-    fc::launch_fps_ragged(cloud, ld, C, (long)P, offsets, rows, voxel_ids, n_voxels, max_rows, m, idx, dist_scratch, (hipStream_t)stream);
+    fc::launch_fps_ragged(cloud, ld, C, (long)P, offsets, rows, voxel_ids, n_voxels, max_rows, m, idx, nullptr, dist_scratch, (hipStream_t)stream);
+    FC_API_END
+}
+
+/* include/fcflow_sparse_stage.h */
+int fc_stage_fps_ragged_counts_f32(const float* cloud, int32_t ld, int32_t C, int64_t P, const int64_t* offsets, const int32_t* rows,
+                                   const int32_t* voxel_ids, int32_t n_voxels, int32_t max_rows, int32_t m, int64_t* idx, int32_t* sample_counts,
+                                   float* dist_scratch, void* stream) {
+    FC_API_BEGIN
+    if (n_voxels < 0 || m < 1 || !sample_counts) throw fc::Error(FC_ERR_INVALID, "fc_stage_fps_ragged_counts_f32: bad argument");
+    fc::launch_fps_ragged(cloud, ld, C, (long)P, offsets, rows, voxel_ids, n_voxels, max_rows, m, idx, sample_counts, dist_scratch, (hipStream_t)stream);
+    FC_API_END
+}
+
+int fc_stage_pairs_counts_f32(const float* cloud_0, int64_t P0, const float* cloud_1, int64_t P1, int32_t ld, const int64_t* index_0,
+                              const int64_t* index_1, const int32_t* counts_0, int32_t n_pairs, int32_t M, int32_t N, float* out_0, float* out_1,
+                              float* inverse, void* stream) {
+    FC_API_BEGIN
+    if (n_pairs < 0) throw fc::Error(FC_ERR_INVALID, "fc_stage_pairs_counts_f32: bad argument");
+    fc::launch_stage_pairs_counts(cloud_0, (long)P0, cloud_1, (long)P1, ld, index_0, index_1, counts_0, n_pairs, M, N, out_0, out_1, inverse,
+                                  (hipStream_t)stream);
     FC_API_END
 }
 

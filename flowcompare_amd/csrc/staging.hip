@@ -6,6 +6,7 @@
 #include "common.h"
 #include "launch.h"
 #include "fps_dist.h"
+#include "block_reduce.h"
 
 #include <cfloat>
 
@@ -75,29 +76,6 @@ void launch_fps_nd(const float* pts, int ld, int C, int64_t* idx, int B, int n, 
         launch_kernel<fps_nd_kernel<false>, 0>("fc::fps_nd_kernel", 0.0, bytes, dim3(B), dim3(1024), 0, s, pts, ld, C, idx, n, m, dist_scratch);
     }
 }
-
-// ---------------------------------------------------------------- block reductions (fixed order: reproducible run to run)
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-    return t;
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = fmaxf(t, red[w]);
-    return t;
-}
-__device__ __forceinline__ float block_min(float v, float* red) { return -block_max(-v, red); }
 
 // ---------------------------------------------------------------- joint unit-sphere normalisation (utils.py:259-280)
 // joint = cat(points_0, points_1): xyz -= mean(xyz); xyz /= max |xyz|; other columns pass through.  One workgroup per pair.

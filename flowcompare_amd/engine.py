@@ -24,7 +24,8 @@ EXPM = {"torch": 0, "original": 1}
 OP_ACTS = {"none": 0, "gelu": 1, "relu": 2, "elu": 3, "lrelu": 4}      # `act` of op_linear / op_mlp_hidden (FC_ACT_*)
 
 EXPORTS = list(abi.ENTRIES)          # every entry point include/fcflow.h declares
-EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES) + list(abi.COUNTS_ENTRIES)      # ... and those of the headers behind it (include/fcflow_attention_mass.h, fcflow_context_counts.h)
+# ... and those of the headers behind it (include/fcflow_attention_mass.h, fcflow_context_counts.h, fcflow_sparse_stage.h)
+EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES) + list(abi.COUNTS_ENTRIES) + list(abi.SPARSE_STAGE_ENTRIES)
 
 
 class FcTensor(ctypes.Structure):
@@ -525,6 +526,34 @@ def stage_fps_ragged(cloud, offsets, rows, m, max_rows, voxel_ids=None):
         lib().fc_stage_fps_ragged_f32(_ptr(cloud), cloud.shape[1], cloud.shape[1], cloud.shape[0], _ptr(offsets), _ptr(rows),
                                       _ptr(voxel_ids), n_vox, int(max_rows), int(m), _ptr(idx), _ptr(scratch), _stream())
     return idx
+
+
+def stage_fps_ragged_counts(cloud, offsets, rows, m, max_rows, voxel_ids=None):
+    """(idx [K', m] int64, sample_counts [K'] int32): listed voxel v with n_v rows takes m_v = min(n_v, m) FPS picks; idx[v, :m_v] are cloud row
+    numbers, idx[v, m_v:] is -1, sample_counts[v] = m_v (fc_stage_fps_ragged_counts_f32, include/fcflow_sparse_stage.h).  Arguments as
+    stage_fps_ragged; m may exceed max_rows."""
+    n_vox = offsets.numel() - 1 if voxel_ids is None else voxel_ids.numel()
+    idx = torch.empty(n_vox, m, dtype=torch.int64, device=cloud.device)
+    sample_counts = torch.empty(n_vox, dtype=torch.int32, device=cloud.device)
+    scratch = torch.empty(rows.numel(), dtype=torch.float32, device=cloud.device) if max_rows > 24576 else None
+    with torch.cuda.device(cloud.device):
+        lib().fc_stage_fps_ragged_counts_f32(_ptr(cloud), cloud.shape[1], cloud.shape[1], cloud.shape[0], _ptr(offsets), _ptr(rows), _ptr(voxel_ids),
+                                             n_vox, int(max_rows), int(m), _ptr(idx), _ptr(sample_counts), _ptr(scratch), _stream())
+    return idx, sample_counts
+
+
+def stage_pairs_counts(cloud_0, cloud_1, index_0, index_1, counts_0):
+    """cloud_0 [P0, C], cloud_1 [P1, C] contiguous fp32, index_0 [K', M] / index_1 [K', N] int64, counts_0 [K'] int32 -> (out_0 [K', M, C], out_1
+    [K', N, C], inverse [K', 4]): pair k = (cloud_0[index_0[k, :counts_0[k]]], cloud_1[index_1[k]]) normalised as stage_co_unit_sphere does,
+    rows of out_0[k] behind its count exact zeros (fc_stage_pairs_counts_f32, include/fcflow_sparse_stage.h)."""
+    (K1, M), N, C = index_0.shape, index_1.shape[1], cloud_0.shape[1]
+    o0 = torch.empty(K1, M, C, dtype=torch.float32, device=cloud_0.device)
+    o1 = torch.empty(K1, N, C, dtype=torch.float32, device=cloud_0.device)
+    inv = torch.empty(K1, 4, dtype=torch.float32, device=cloud_0.device)
+    with torch.cuda.device(cloud_0.device):
+        lib().fc_stage_pairs_counts_f32(_ptr(cloud_0), cloud_0.shape[0], _ptr(cloud_1), cloud_1.shape[0], C, _ptr(index_0), _ptr(index_1),
+                                        _ptr(counts_0), K1, M, N, _ptr(o0), _ptr(o1), _ptr(inv), _stream())
+    return o0, o1, inv
 
 
 def stage_dense_blocks(cloud, offsets, rows, inverse, block_offsets, n_blocks, block, voxel_ids=None):

@@ -294,6 +294,17 @@ def attention_mass(batch, models_dict, config, layers=("aug",), weights=None, ep
                                               return_log_prob=return_log_prob, context_counts=context_counts)
 
 
+def _scene_min_context(what, min_context, models_dict, config):
+    """min_context of the scene-level functions, checked before anything is staged: staging._min_context's rule, and eval mode, since every
+    inner_loop call will carry `context_counts`."""
+    from . import staging
+    min_context = staging._min_context(what, min_context, config["n_samples_context"])
+    if min_context is not None and (models_dict["flow"].training or models_dict["input_embedder"].training):
+        raise RuntimeError(f"{what}: min_context is eval-mode only (it stages per-voxel context_counts, which the training path does not take): "
+                           "initialize_flow(mode='test') or .eval() on the flow and the embedder")
+    return min_context
+
+
 def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None):
     """Log-probs of ALL members of the staged voxels against their voxel's staged context: st = the SceneStage (context st.extract_0,
     st.extra_context), dense = staging.stage_dense(...) of the same voxels.  In eval mode a target point's log-likelihood depends on
@@ -302,7 +313,9 @@ def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None
     is one flow.log_prob with the blocks' voxels' embeddings / extra context gathered by index_select and expanded over the block as
     inner_loop does.  eps: None draws per batch as inner_loop does; otherwise one tensor [total, width_i] per noise site of the flow
     (flow.noise_shapes) in CSR row order -- pad slots get zeros.  Returns flat [total] log-probs in CSR order (dense.offsets /
-    dense.rows); pad slots are dropped.  Eval mode, under torch.no_grad(); the batch is taken as given under config['data_parallel']."""
+    dense.rows); pad slots are dropped.  Eval mode, under torch.no_grad(); the batch is taken as given under config['data_parallel'].
+    A SceneStage staged with min_context (st.context_counts set) is honoured: every chunk of voxels is embedded through
+    _embed_batch's equal-count grouping, and every flow.log_prob gets its blocks' counts, gathered like the embeddings."""
     if not (torch.is_tensor(st.extract_0) and st.extract_0.is_cuda and torch.is_tensor(dense.blocks) and dense.blocks.is_cuda):
         raise RuntimeError("dense_log_prob: expects a SceneStage and a DenseStage on the GPU (flowcompare_amd has no CPU fallback)")
     flow, embedder = models_dict["flow"], models_dict["input_embedder"]
@@ -322,8 +335,12 @@ def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None
             raise RuntimeError(f"dense_log_prob: eps must be one GPU tensor [{total}, width] per noise site, widths {widths}")
         csr_pos = (torch.cumsum(member, 0) - 1).clamp_(min=0)                     # CSR position of every slot (pads: any valid row, zeroed below)
     out = torch.empty(n_blocks, block, dtype=torch.float32, device=dense.blocks.device)
+    counts = getattr(st, "context_counts", None)
     with torch.no_grad():
-        if n_blocks:
+        if n_blocks and counts is not None:
+            emb = torch.cat([_embed_batch((st.extract_0[a:a + blocks_per_batch], st.extract_1[a:a + blocks_per_batch], None), models_dict, config,
+                                          counts[a:a + blocks_per_batch], "dense_log_prob")[1] for a in range(0, K1, blocks_per_batch)])
+        elif n_blocks:
             emb = torch.cat([embedder(st.extract_0[a:a + blocks_per_batch, :, :Din]) for a in range(0, K1, blocks_per_batch)])
         for a in range(0, n_blocks, blocks_per_batch):
             b = min(a + blocks_per_batch, n_blocks)
@@ -338,12 +355,16 @@ def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None
             if eps is not None:
                 sl = slice(a * block, b * block)
                 noise = [torch.where(member[sl, None], e.index_select(0, csr_pos[sl]), e.new_zeros(())).reshape(b - a, block, -1) for e in eps]
-            out[a:b] = flow.log_prob(dense.blocks[a:b, :, :Din], context=context, extra_context=extra, eps=noise)
+            if counts is None:
+                out[a:b] = flow.log_prob(dense.blocks[a:b, :, :Din], context=context, extra_context=extra, eps=noise)
+            else:
+                out[a:b] = flow.log_prob(dense.blocks[a:b, :, :Din], context=context, extra_context=extra, eps=noise,
+                                         context_counts=counts.index_select(0, voxel))
     return out.reshape(-1)[member]
 
 
 def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=None, multiple=5.4, hard_cutoff=None, voxels_per_batch=16,
-                 final_voxel_size=None, context_voxel_size=None, dense=False, block=None):
+                 final_voxel_size=None, context_voxel_size=None, dense=False, block=None, min_context=None):
     """test_flow.py:151-166 for a whole scene, one direction: the change of cloud_1 [P1, C] given cloud_0 [P0, C] at the voxel centres
     `centers` [K, 3].  Sample counts are config['sample_size'] / config['n_samples_context'] as the reference's loader takes them
     (test_flow.py:141-143); the box sizes default to the config's 'final_voxel_size' / 'context_voxel_size'.  Evaluated are the centres
@@ -360,7 +381,13 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
     voxels_per_batch blocks per flow call), and ONE log_prob_to_change_ragged call covers the scene: min / max scaling over all of a
     voxel's members, threshold from its sampled (0 | 0) row.  Unlike the sampled mode, whose clamp_infs acts per chunk, the dense mode's
     clamp_infs acts over the whole scene's tensor.  Every point inside an evaluated voxel comes back finite (the larger value where boxes
-    share a face), points of voxels that fail the validity mask stay NaN, and the returned SceneStage carries the DenseStage as `.dense`."""
+    share a face), points of voxels that fail the validity mask stay NaN, and the returned SceneStage carries the DenseStage as `.dense`.
+
+    min_context (an integer in [1, n_samples_context], eval mode) also evaluates voxels whose context box holds fewer
+    than n_samples_context points: the validity mask becomes (c0_ctx >= min_context) & (c1_fin >= N) & (c0_fin >= N), both stagings are made
+    with stage_scene's min_context (they share the context boxes, so the counts), and every inner_loop / dense_log_prob call passes its
+    voxels' counts as `context_counts`; the returned SceneStage carries them as `.context_counts`.  The embedder then runs once per DISTINCT
+    count of a chunk (_embed_batch), and its own minimum applies (DGCNN: n_neighbors points, PAConv: 256)."""
     from . import change as change_ops
     from . import staging
     fin = config.get("final_voxel_size") if final_voxel_size is None else final_voxel_size
@@ -370,13 +397,15 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
     if config.get("using_extra_context") and ground_height is None:
         raise RuntimeError("scene_change: this config uses the extra z-value context and needs ground_height")
     N, M = config["sample_size"], config["n_samples_context"]
+    min_context = _scene_min_context("scene_change", min_context, models_dict, config)
     c0_ctx, c1_fin, c0_fin = (staging.voxel_counts(cloud_0, centers, ctx), staging.voxel_counts(cloud_1, centers, fin),
                               staging.voxel_counts(cloud_0, centers, fin))
-    both = torch.nonzero((c0_ctx >= M) & (c1_fin >= N) & (c0_fin >= N)).flatten()
+    both = torch.nonzero((c0_ctx >= (M if min_context is None else min_context)) & (c1_fin >= N) & (c0_fin >= N)).flatten()
     sel = centers[both].contiguous()
-    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height)
-    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height)
+    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height, min_context=min_context)
+    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height, min_context=min_context)
     assert st10.voxel.numel() == st00.voxel.numel() == both.numel()
+    counts = st10.context_counts                                  # None without min_context; st00's are the same (same context boxes)
     out = torch.full((cloud_1.shape[0],), float("nan"), dtype=torch.float32, device=cloud_1.device)
     if dense:
         st10.dense = staging.stage_dense(cloud_1, st10, fin, sel, N if block is None else block)
@@ -387,7 +416,8 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
                 for a in range(0, both.numel(), voxels_per_batch):
                     sl = slice(a, a + voxels_per_batch)
                     extra = st10.extra_context[sl] if config.get("using_extra_context") else None
-                    lp_0_0.append(inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config)[1])
+                    lp_0_0.append(inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config,
+                                             context_counts=None if counts is None else counts[sl])[1])
             change = change_ops.log_prob_to_change_ragged(lp_1_0, st10.dense.offsets, torch.cat(lp_0_0), multiple, hard_cutoff)
             out.scatter_reduce_(0, st10.dense.rows, change, "amax", include_self=False)
         st10.voxel, st10.count_0, st10.count_1 = both, c0_ctx, c1_fin
@@ -397,8 +427,9 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
         for a in range(0, both.numel(), voxels_per_batch):
             sl = slice(a, a + voxels_per_batch)
             extra = st10.extra_context[sl] if config.get("using_extra_context") else None
-            _, lp_1_0, _ = inner_loop((st10.extract_0[sl], st10.extract_1[sl], extra), models_dict, config)
-            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config)
+            cnt = None if counts is None else counts[sl]
+            _, lp_1_0, _ = inner_loop((st10.extract_0[sl], st10.extract_1[sl], extra), models_dict, config, context_counts=cnt)
+            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config, context_counts=cnt)
             chunks.append(change_ops.log_prob_to_change(lp_1_0, lp_0_0, multiple, hard_cutoff))
     if chunks:
         out.scatter_reduce_(0, st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1), "amax", include_self=False)
@@ -407,7 +438,7 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
 
 
 def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, layers=("aug",), ground_height=None, multiple=5.4, hard_cutoff=None,
-                              voxels_per_batch=16, weight="change"):
+                              voxels_per_batch=16, weight="change", min_context=None):
     """Which points of the OLD scan the change map relied on: the sampled mode of scene_change (same validity rule, stagings, sample
     counts, chunks of `voxels_per_batch` voxels, log_prob_to_change per chunk) plus, per chunk, attention_mass on the (1 | 0) batch with
     weights = that chunk's change (weight="change") or ones (weight="uniform").  Per chunk ONE set of augmenter / CIF noise is drawn from
@@ -416,7 +447,9 @@ def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, la
     none, and is another sample of the same quantity otherwise.)  layers as in attention_mass ("all" included).
     Returns (mass_0 [len(layers), P0], change_1 [P1], the (1 | 0) SceneStage): mass_0[i, r] = layer i's mass on row r of cloud_0, scattered
     through st10.index_0 -- NaN where no evaluated voxel sampled the row as context, the larger value where two voxels share it (the
-    rule scene_change applies to shared points; deterministic); change_1 as scene_change returns it."""
+    rule scene_change applies to shared points; deterministic); change_1 as scene_change returns it.
+    min_context as in scene_change: every pass of a chunk gets the chunk's counts, and mass is scattered only through index_0 >= 0 -- the pad
+    slots of a sparse voxel hold exact zeros and reach no row of cloud_0."""
     from . import change as change_ops
     from . import staging
     if weight not in ("change", "uniform"):
@@ -431,13 +464,15 @@ def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, la
         layers = flow.attention_layers() if layers == "all" else (layers,)
     layers = list(layers)
     N, M = config["sample_size"], config["n_samples_context"]
+    min_context = _scene_min_context("scene_context_attribution", min_context, models_dict, config)
     c0_ctx, c1_fin, c0_fin = (staging.voxel_counts(cloud_0, centers, ctx), staging.voxel_counts(cloud_1, centers, fin),
                               staging.voxel_counts(cloud_0, centers, fin))
-    both = torch.nonzero((c0_ctx >= M) & (c1_fin >= N) & (c0_fin >= N)).flatten()
+    both = torch.nonzero((c0_ctx >= (M if min_context is None else min_context)) & (c1_fin >= N) & (c0_fin >= N)).flatten()
     sel = centers[both].contiguous()
-    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height)
-    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height)
+    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height, min_context=min_context)
+    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height, min_context=min_context)
     assert st10.voxel.numel() == st00.voxel.numel() == both.numel()
+    counts = st10.context_counts
     change_1 = torch.full((cloud_1.shape[0],), float("nan"), dtype=torch.float32, device=cloud_1.device)
     mass_0 = torch.full((len(layers), cloud_0.shape[0]), float("nan"), dtype=torch.float32, device=cloud_0.device)
     chunks, masses = [], []
@@ -447,16 +482,20 @@ def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, la
             extra = st10.extra_context[sl] if config.get("using_extra_context") else None
             batch_10 = (st10.extract_0[sl], st10.extract_1[sl], extra)
             eps = [torch.randn(s, device=cloud_1.device, dtype=torch.float32) for s in flow.noise_shapes(st10.extract_1[sl].shape[0], N)]
-            _, lp_1_0, _ = inner_loop(batch_10, models_dict, config, eps=eps)
-            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config, eps=eps)
+            cnt = None if counts is None else counts[sl]
+            _, lp_1_0, _ = inner_loop(batch_10, models_dict, config, eps=eps, context_counts=cnt)
+            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config, eps=eps, context_counts=cnt)
             change = change_ops.log_prob_to_change(lp_1_0, lp_0_0, multiple, hard_cutoff)
             chunks.append(change)
             masses.append(torch.stack(attention_mass(batch_10, models_dict, config, layers=layers, weights=change if weight == "change" else None,
-                                                     eps=eps)))
+                                                     eps=eps, context_counts=cnt)))
     if chunks:
         change_1.scatter_reduce_(0, st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1), "amax", include_self=False)
-        rows = st10.index_0.reshape(1, -1).expand(len(layers), -1)
-        mass_0.scatter_reduce_(1, rows, torch.cat(masses, dim=1).reshape(len(layers), -1), "amax", include_self=False)
+        rows, vals = st10.index_0.reshape(-1), torch.cat(masses, dim=1).reshape(len(layers), -1)
+        if counts is not None:                                    # pad slots of sparse voxels: index -1, mass 0.0 -- they name no row
+            real = torch.nonzero(rows >= 0).flatten()
+            rows, vals = rows.index_select(0, real), vals.index_select(1, real)
+        mass_0.scatter_reduce_(1, rows.reshape(1, -1).expand(len(layers), -1), vals, "amax", include_self=False)
     st10.voxel, st10.count_0, st10.count_1 = both, c0_ctx, c1_fin
     return mass_0, change_1, st10
 

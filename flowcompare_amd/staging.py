@@ -6,6 +6,7 @@ the package is not in this image, so its published algorithm is restated: start 
 columns, first maximum wins).  `unit_sphere` / `co_unit_sphere` mirror utils.py.  All arithmetic runs in the HIP library.
 """
 import math
+import numbers
 
 import torch
 
@@ -62,7 +63,9 @@ def stage_pair(voxel_0_large, voxel_1_small, n_samples_context, n_samples):
 class SceneStage:
     """What `stage_scene` returns: the staged voxel pairs of a scene, K' valid voxels out of K centres.
     extract_0 [K', M, C], extract_1 [K', N, C], extra_context [K', 1] or None, inverse {'furthest_distance' [K'], 'mean' [K', 3]},
-    index_0 [K', M] / index_1 [K', N] (rows of cloud_0 / cloud_1), voxel [K'] (which centres), count_0 / count_1 [K] int32."""
+    index_0 [K', M] / index_1 [K', N] (rows of cloud_0 / cloud_1), voxel [K'] (which centres), count_0 / count_1 [K] int32,
+    context_counts [K'] int32 (stage_scene's min_context: the context samples of every staged voxel, what inner_loop's `context_counts` takes;
+    extract_0[k, count:] is exact zeros and index_0[k, count:] is -1) or None."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -142,6 +145,43 @@ def _fps_ragged(cloud, offsets, rows32, m, voxel_ids=None):
     return engine.stage_fps_ragged(cloud, offsets, rows32, m, hi, None if voxel_ids is None else voxel_ids.to(torch.int32).contiguous())
 
 
+def _fps_ragged_counts(cloud, offsets, rows32, m, voxel_ids=None):
+    """(idx [K', m], sample_counts [K'] int32): voxel v takes min(n_v, m) picks, -1 behind them (engine.stage_fps_ragged_counts).  One
+    read-back, the largest voxel, where _fps_ragged reads the smallest and the largest."""
+    n = offsets[1:] - offsets[:-1]
+    if voxel_ids is not None:
+        n = n[voxel_ids.long()]
+    if n.numel() == 0:
+        return torch.zeros(0, m, dtype=torch.int64, device=cloud.device), torch.zeros(0, dtype=torch.int32, device=cloud.device)
+    if m < 1:
+        raise RuntimeError(f"fps_ragged_counts: {m} samples asked")
+    return engine.stage_fps_ragged_counts(cloud, offsets, rows32, m, int(n.max()), None if voxel_ids is None else voxel_ids.to(torch.int32).contiguous())
+
+
+def _check_rows(name, cloud, offsets, rows):
+    _scene_input(name, cloud)
+    if not (offsets.is_cuda and rows.is_cuda and offsets.dtype == torch.int64 and rows.dtype in (torch.int64, torch.int32)):
+        raise RuntimeError(f"{name}: offsets (int64) and rows must be GPU tensors (flowcompare_amd has no CPU fallback)")
+    if not 1 <= cloud.shape[1] <= 8:
+        raise RuntimeError(f"{name}: 1..8 feature columns supported")
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= cloud.shape[0]) or int(offsets[-1]) != rows.numel():
+        raise RuntimeError(f"{name}: rows / offsets do not describe rows of this cloud")
+
+
+def fps_ragged_counts(cloud, offsets, rows, m, voxel_ids=None):
+    """fps_ragged for voxels that may hold fewer than m rows -> (idx [K', m] int64, sample_counts [K'] int32): voxel v with n_v rows takes
+    m_v = min(n_v, m) picks; idx[v, :m_v] are the picks of `fps(cloud[rows of voxel v], random_start=False)` with m_v samples, index for
+    index, idx[v, m_v:] is -1 and sample_counts[v] = m_v (0 for a voxel without rows).  voxel_ids [K'] (optional): which voxels of the CSR
+    list, in that order, repeats allowed; None = all of them."""
+    _check_rows("fps_ragged_counts", cloud, offsets, rows)
+    if voxel_ids is not None:
+        if not (torch.is_tensor(voxel_ids) and voxel_ids.is_cuda and voxel_ids.dim() == 1 and voxel_ids.dtype in (torch.int64, torch.int32)):
+            raise RuntimeError("fps_ragged_counts: voxel_ids must be a 1-d integer GPU tensor")
+        if voxel_ids.numel() and (int(voxel_ids.min()) < 0 or int(voxel_ids.max()) >= offsets.numel() - 1):
+            raise RuntimeError("fps_ragged_counts: voxel_ids name voxels outside the list")
+    return _fps_ragged_counts(cloud, offsets.contiguous(), rows.to(torch.int32).contiguous(), int(m), voxel_ids)
+
+
 def fps_ragged(cloud, offsets, rows, m):
     """Farthest point subsampling of every voxel of a CSR list (voxel_rows) in one launch -> [K, m] int64 rows of `cloud`: the first m
     picks of `fps(cloud[rows of voxel k], random_start=False)`, index for index.  Raises if a voxel has fewer than m rows."""
@@ -155,12 +195,29 @@ def fps_ragged(cloud, offsets, rows, m):
     return _fps_ragged(cloud, offsets.contiguous(), rows.to(torch.int32).contiguous(), int(m))
 
 
-def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size, n_samples, n_samples_context, ground_height=None):
+def _min_context(name, min_context, M):
+    """min_context of stage_scene / scene_change: None, or a plain integer in [1, n_samples_context]."""
+    if min_context is None:
+        return None
+    if isinstance(min_context, bool) or torch.is_tensor(min_context) or not isinstance(min_context, numbers.Integral):
+        raise RuntimeError(f"{name}: min_context must be None or an integer, got {type(min_context).__name__}")
+    if not 1 <= min_context <= M:
+        raise RuntimeError(f"{name}: min_context must lie in [1, n_samples_context = {M}], got {int(min_context)}")
+    return int(min_context)
+
+
+def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size, n_samples, n_samples_context, ground_height=None, min_context=None):
     """The loader's test-mode item (ams_voxel_loader.py:291-307, 338, 349-350) for every centre of a scene at once: target =
     get_voxel(cloud_1, c, final) -> first n_samples FPS picks, context = get_voxel(cloud_0, c, context) -> first n_samples_context
     picks, co_unit_sphere(context, target).  A voxel is valid when count_0 >= n_samples_context and count_1 >= n_samples (:240);
     invalid voxels are skipped, never padded; staged voxels keep ascending centre order.  Returns a SceneStage; with no valid voxel
-    its tensors are empty and nothing is launched beyond the counts.  stage_scene(cloud_0, cloud_0, ...) is the "self" pair."""
+    its tensors are empty and nothing is launched beyond the counts.  stage_scene(cloud_0, cloud_0, ...) is the "self" pair.
+
+    min_context (an integer in [1, n_samples_context]) keeps voxels with sparse context: a voxel is valid when count_0 >=
+    min_context and count_1 >= n_samples, and valid voxel k gets min(count_0[k], n_samples_context) context samples -- its rows are bit for bit
+    stage_pair(cloud_0[members], cloud_1[members], that count, n_samples); extract_0[k, count:] is exact zeros, index_0[k, count:] is -1, and
+    SceneStage.context_counts [K'] int32 holds the counts: st.batch() plus context_counts=st.context_counts is what inner_loop takes.  The
+    target side is unchanged.  With None nothing changes and context_counts is None."""
     _cloud_and_centers("stage_scene", cloud_0, centers)
     _cloud_and_centers("stage_scene", cloud_1, centers)
     if cloud_0.shape[1] != cloud_1.shape[1] or cloud_0.device != cloud_1.device:
@@ -168,32 +225,40 @@ def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size,
     M, N, C, dev = int(n_samples_context), int(n_samples), cloud_0.shape[1], cloud_0.device
     if M < 1 or N < 1:
         raise RuntimeError("stage_scene: sample counts must be positive")
+    min_context = _min_context("stage_scene", min_context, M)
     count_0, ws_0 = _count("stage_scene", cloud_0, centers, context_voxel_size)
     count_1, ws_1 = _count("stage_scene", cloud_1, centers, final_voxel_size)
-    voxel = torch.nonzero((count_0 >= M) & (count_1 >= N)).flatten()
+    voxel = torch.nonzero((count_0 >= (M if min_context is None else min_context)) & (count_1 >= N)).flatten()
     K1 = voxel.numel()
     if K1 == 0:
         f, i = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
         return SceneStage(extract_0=torch.zeros(0, M, C, **f), extract_1=torch.zeros(0, N, C, **f),
                           extra_context=None if ground_height is None else torch.zeros(0, 1, **f),
                           inverse={'furthest_distance': torch.zeros(0, **f), 'mean': torch.zeros(0, 3, **f)},
-                          index_0=torch.zeros(0, M, **i), index_1=torch.zeros(0, N, **i), voxel=voxel, count_0=count_0, count_1=count_1)
+                          index_0=torch.zeros(0, M, **i), index_1=torch.zeros(0, N, **i), voxel=voxel, count_0=count_0, count_1=count_1,
+                          context_counts=None if min_context is None else torch.zeros(0, dtype=torch.int32, device=dev))
 
-    def picks(cloud, size, counts, ws, m):
+    def picks(cloud, size, counts, ws, m, ragged=_fps_ragged):
         offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=dev)
         torch.cumsum(counts, 0, out=offsets[1:])
         rows = engine.stage_voxel_select(cloud, centers, _dims(size), offsets, int(offsets[-1]), ws)
-        return _fps_ragged(cloud, offsets, rows, m, voxel)
+        return ragged(cloud, offsets, rows, m, voxel)
 
-    index_0 = picks(cloud_0, context_voxel_size, count_0, ws_0, M)
-    index_1 = picks(cloud_1, final_voxel_size, count_1, ws_1, N)
-    e0 = cloud_0.index_select(0, index_0.reshape(-1)).reshape(K1, M, C)
-    e1 = cloud_1.index_select(0, index_1.reshape(-1)).reshape(K1, N, C)
-    o0, o1, inv = engine.stage_co_unit_sphere(e0, e1)
+    if min_context is None:
+        context_counts = None
+        index_0 = picks(cloud_0, context_voxel_size, count_0, ws_0, M)
+        index_1 = picks(cloud_1, final_voxel_size, count_1, ws_1, N)
+        e0 = cloud_0.index_select(0, index_0.reshape(-1)).reshape(K1, M, C)
+        e1 = cloud_1.index_select(0, index_1.reshape(-1)).reshape(K1, N, C)
+        o0, o1, inv = engine.stage_co_unit_sphere(e0, e1)
+    else:                                                              # index_0 holds -1 behind a sparse voxel's count: the pair kernel reads through the lists
+        index_0, context_counts = picks(cloud_0, context_voxel_size, count_0, ws_0, M, _fps_ragged_counts)
+        index_1 = picks(cloud_1, final_voxel_size, count_1, ws_1, N)
+        o0, o1, inv = engine.stage_pairs_counts(cloud_0, cloud_1, index_0, index_1, context_counts)
     inverse = {'furthest_distance': inv[:, 0].contiguous(), 'mean': inv[:, 1:4].contiguous()}
     extra = None if ground_height is None else (inverse['mean'][:, 2] - ground_height).unsqueeze(-1)
     return SceneStage(extract_0=o0, extract_1=o1, extra_context=extra, inverse=inverse, index_0=index_0, index_1=index_1, voxel=voxel,
-                      count_0=count_0, count_1=count_1)
+                      count_0=count_0, count_1=count_1, context_counts=context_counts)
 
 
 # ---------------------------------------------------------------- every member of the staged voxels (csrc/scene_stage.hip)

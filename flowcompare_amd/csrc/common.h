@@ -395,6 +395,7 @@ void launch_expm_wide(const float* params, int ldp, const float* x2, int ldx, co
                       int ldj_mode, int rows, int d2, int inverse, int* status, float* info, hipStream_t s);
 void launch_spline_flat(const float* x, const float* params, float* y, float* lad, int64_t n, int K, int inverse, hipStream_t s);
 void launch_knn(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm = nullptr);
+void knn_check_shape(int ldf, int C, int M, int k);   // throws what launch_knn would for this shape, before anything is launched
 void launch_gather_max(const float* uv, int lduv, int c_out, const int32_t* idx, int k, float* out, int ldo, int out_col0,
                        int B, int M, int m_stride_rows, hipStream_t s);
 void launch_pool_max_mean(const float* t, int ldt, int width, float* out, int ldo, int B, int M, int m_stride_rows, hipStream_t s);

@@ -194,8 +194,8 @@ __device__ __forceinline__ void knn_insert(float& sv, int& si, float v, int ci) 
 constexpr int KM_TC = 64;       // candidates per LDS block
 
 template <int CP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void knn_mfma_kernel(const float* __restrict__ f, int ldf, int C, int32_t* __restrict__ idx_out, int M, int m_stride,
-                                                       int k, const int32_t* __restrict__ warm) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void knn_mfma_kernel(const float* __restrict__ f, int ldf, int C, int32_t* idx_out, int M, int m_stride,
+                                                       int k, const int32_t* warm) {
     extern __shared__ float smem[];
     constexpr int LDC = CP + 4, H = CP / 2, NLD = (KM_TC * CP / 4 + 255) / 256;
     float* s_qxx = smem + 2 * KM_TC * LDC;                        // [4 waves][32]
@@ -274,8 +274,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 cmax = fmaxf(cmax, cx);
             }
             // |2 x.y computed two ways| differs by at most ~2 C eps |x| |y| <= C eps (|x|^2 + |y|^2); 2^-21 = 4 eps covers the two subtractions as well
-            tau0 = tmin - (float)CP * 4.76837158e-7f * (nrm + cmax + fabsf(tmin));
-            if (bad || !(tau0 == tau0)) tau0 = -INFINITY;
+            const float margin = (float)CP * 4.76837158e-7f * (nrm + cmax + fabsf(tmin));
+            tau0 = tmin - margin;
+            // The bound above is a RELATIVE one: it holds while no product or partial sum leaves the normal range.  Where it does (norms
+            // below ~2^-40: a term that rounds in the subnormal range is off by up to 2^-150, 2 CP + 2 of them by < 2^-141) or where the
+            // margin is plain zero (query and warm neighbours all zero: every candidate ties at pd = 0 and `pd > tau0` would turn all of
+            // them away), tau0 would not lie strictly below the k-th best as the stream computes it.  A margin of at least 2^-100 is normal
+            // itself and covers 2^-141 many times over; anything smaller gives no bound: tau0 = -inf, the plain stream.
+            if (bad || !(margin >= 7.88860905e-31f) || !(tau0 < tmin)) tau0 = -INFINITY;
         }
         if (lh == 0) s_tau[wave * 32 + li] = tau0;
     }
@@ -393,35 +399,43 @@ static void launch_knn_mfma(const float* f, int ldf, int C, int32_t* idx, int B,
                                                  f, ldf, C, idx, M, m_stride_rows, k, warm);
 }
 
+// the padded feature width of the matrix-core kernel where a search of this shape takes it, 0 where it takes the lane-per-candidate kernel
+static int knn_mfma_width(int ldf, int C, int M) {
+    if (!g_knobs.knn_mfma) return 0;                                // (knob 24)
+    const int Cp8 = C <= 8 ? 8 : (C <= 16 ? 16 : (C <= 32 ? 32 : (C <= 64 ? 64 : (C <= 128 ? 128 : 0))));
+    // (wider features or a pitch that does not cover the padded row: the lane-per-candidate kernel; so do small scenes -- a workgroup of the MFMA
+    // kernel owns 128 queries for ALL M candidates, which takes as long with two scenes in the batch as with sixteen, so the choice depends on
+    // M alone (a scene's neighbour sets, near-ties included, must not depend on the batch it sits in); at M = 1024 the 16-query
+    // workgroups of the lane-per-candidate kernel finish a C1 batch in 0.37 ms against 2.7)
+    return Cp8 && ldf >= Cp8 && (g_knobs.knn_mfma == 2 || M >= 2048) ? Cp8 : 0;
+}
+static size_t knn_lane_lds(int Cp) { return ((size_t)(64 + 16) * (Cp + 4) + 16 + 16 * KNN_CAP) * sizeof(float) + 16 * KNN_CAP * sizeof(int32_t); }
+
+// every refusal of launch_knn that the shape alone decides (an operator entry asks before it launches anything of its own)
+void knn_check_shape(int ldf, int C, int M, int k) {
+    if (k > 64 || k < 1) throw Error(FC_ERR_UNSUPPORTED, "knn: k must be in [1, 64]");
+    if (M < k) throw Error(FC_ERR_INVALID, "knn: fewer points than neighbours (torch.topk would raise as well)");
+    if (!knn_mfma_width(ldf, C, M) && knn_lane_lds(round_up(C, 4)) > 160 * 1024)
+        throw Error(FC_ERR_UNSUPPORTED, "knn: feature dimension too large for the LDS tile");
+}
+
 // warm: k neighbours per query of the same cloud from another feature space (may alias idx: a workgroup reads its own queries' sets before it
 // writes them), or null; used by the matrix-core kernel only -- the result is the exact top-k set either way
 void launch_knn(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm) {
     if (!g_knobs.knn_warm) warm = nullptr;                          // (knob 32)
-    if (k > 64 || k < 1) throw Error(FC_ERR_UNSUPPORTED, "knn: k must be in [1, 64]");
-    if (M < k) throw Error(FC_ERR_INVALID, "knn: fewer points than neighbours (torch.topk would raise as well)");
+    knn_check_shape(ldf, C, M, k);
     const int Cp = round_up(C, 4);
     if (ldf < Cp || ldf % 4 != 0 || ((uintptr_t)f & 15)) throw Error(FC_ERR_INVALID, "knn: feature pitch must cover round_up(C,4) and be 16-byte aligned");
-    if (g_knobs.knn_mfma) {                                         // (knob 24)
-        const int Cp8 = C <= 8 ? 8 : (C <= 16 ? 16 : (C <= 32 ? 32 : (C <= 64 ? 64 : (C <= 128 ? 128 : 0))));
-        // (wider features or a pitch that does not cover the padded row: the kernel below; so do small scenes -- a workgroup of the MFMA kernel
-        // owns 128 queries for ALL M candidates, which takes as long with two scenes in the batch as with sixteen, so the choice depends on
-        // M alone (a scene's neighbour sets, near-ties included, must not depend on the batch it sits in); at M = 1024 the 16-query
-        // workgroups of the kernel below finish a C1 batch in 0.37 ms against 2.7)
-        if (Cp8 && ldf >= Cp8 && (g_knobs.knn_mfma == 2 || M >= 2048)) {
-            switch (Cp8) {
-                case 8: launch_knn_mfma<8>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm); break;
-                case 16: launch_knn_mfma<16>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm); break;
-                case 32: launch_knn_mfma<32>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm); break;
-                case 64: launch_knn_mfma<64>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm); break;
-                default: launch_knn_mfma<128>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm); break;
-            }
-            return;
-        }
+    switch (knn_mfma_width(ldf, C, M)) {
+        case 0: break;
+        case 8: return launch_knn_mfma<8>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm);
+        case 16: return launch_knn_mfma<16>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm);
+        case 32: return launch_knn_mfma<32>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm);
+        case 64: return launch_knn_mfma<64>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm);
+        default: return launch_knn_mfma<128>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm);
     }
-    const size_t lds = ((size_t)(64 + 16) * (Cp + 4) + 16 + 16 * KNN_CAP) * sizeof(float) + 16 * KNN_CAP * sizeof(int32_t);
-    if (lds > 160 * 1024) throw Error(FC_ERR_UNSUPPORTED, "knn: feature dimension too large for the LDS tile");
     launch_kernel<knn_kernel, 160 * 1024>("fc::knn_kernel(float const*, int, int, int*, int, int, int)", 2.0 * B * (double)M * M * C, 4.0 * B * (double)M * (C + k),
-                                          dim3((M + 15) / 16, B), dim3(256), lds, s, f, ldf, Cp, idx, M, m_stride_rows, k);
+                                          dim3((M + 15) / 16, B), dim3(256), knn_lane_lds(Cp), s, f, ldf, Cp, idx, M, m_stride_rows, k);
 }
 
 }  // namespace fc

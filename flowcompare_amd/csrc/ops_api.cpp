@@ -488,6 +488,7 @@ int fc_op_knn_f32(const float* f, int32_t* idx, int32_t B, int32_t M, int32_t C,
     if (!f || !idx || B < 1 || M < 1 || C < 1) throw Error(FC_ERR_INVALID, "fc_op_knn_f32: bad argument");
     hipStream_t s = (hipStream_t)stream;
     const int cp = round_up(C, 32);
+    knn_check_shape(cp, C, M, k);
     TmpBuf fp((size_t)B * M * cp * 4);
     launch_pack_rows(f, C, C, fp.f(), cp, 0, cp, B * M, s);
     launch_knn(fp.f(), cp, C, idx, B, M, M, k, s);
@@ -502,6 +503,7 @@ int fc_op_knn_warm_f32(const float* f, const int32_t* idx_warm, int32_t* idx, in
     if (!f || !idx || !idx_warm || B < 1 || M < 1 || C < 1) throw Error(FC_ERR_INVALID, "fc_op_knn_warm_f32: bad argument");
     hipStream_t s = (hipStream_t)stream;
     const int cp = round_up(C, 32);
+    knn_check_shape(cp, C, M, k);
     TmpBuf fp((size_t)B * M * cp * 4);
     launch_pack_rows(f, C, C, fp.f(), cp, 0, cp, B * M, s);
     launch_knn(fp.f(), cp, C, idx, B, M, M, k, s, idx_warm);

@@ -737,20 +737,24 @@ def op_attention_mass(q, k, scale, weights=None):
     return out
 
 
-def op_knn(f, k, warm=None):
+def op_knn(f, k, warm=None, in_place=False):
     """k nearest neighbours in feature space [B, M, C] -> int32 [B, M, k] (unordered sets); `warm`: neighbour sets [B, M, k] of the same cloud from
-    another feature space to start the search from (the result is the exact top-k either way)."""
+    another feature space to start the search from (the result is the exact top-k either way).  in_place: the result overwrites the warm
+    sets' own buffer, as between the levels of the DGCNN engine (a copy of `warm`; the caller's tensor stays as it is)."""
     f = _dev_f32(f)
     B, M, C = f.shape
-    idx = torch.empty(B, M, k, dtype=torch.int32, device=f.device)
+    if in_place and warm is None:
+        raise RuntimeError("op_knn: in_place needs warm sets")
     with torch.cuda.device(f.device):
         if warm is None:
+            idx = torch.empty(B, M, k, dtype=torch.int32, device=f.device)
             lib().fc_op_knn_f32(_ptr(f), _ptr(idx), B, M, C, k, _stream())
         else:
-            warm = warm.to(device=f.device, dtype=torch.int32).contiguous()
             if tuple(warm.shape) != (B, M, k):
                 raise RuntimeError(f"op_knn: warm sets have shape {tuple(warm.shape)}, expected {(B, M, k)}")
-            lib().fc_op_knn_warm_f32(_ptr(f), _ptr(warm), _ptr(idx), B, M, C, k, _stream())
+            warm = warm.to(device=f.device, dtype=torch.int32).contiguous()
+            idx = warm.clone() if in_place else torch.empty(B, M, k, dtype=torch.int32, device=f.device)
+            lib().fc_op_knn_warm_f32(_ptr(f), _ptr(idx if in_place else warm), _ptr(idx), B, M, C, k, _stream())
     return idx
 
 

@@ -286,7 +286,14 @@ int fc_op_attention_weights_f32(const float* q, const float* k, float* out, cons
                                 int32_t B, int32_t N, int32_t M, int32_t D, float scale, void* stream);
 
 /* k nearest neighbours in feature space, reference ranking -|xi|^2 + 2 xi.xj - |xj|^2 (self included)
- * (models/pytorch_gcn.py:13-20).  f [B,M,C] channels-last -> idx [B,M,k] int32 (unordered set). */
+ * (models/pytorch_gcn.py:13-20).  f [B,M,C] channels-last -> idx [B,M,k] int32 (unordered set).
+ * Ties: among candidates of equal ranking value (as computed in fp32) the one of LOWEST index wins, in both kernels and with or without
+ * a warm start, so a set is a function of the scene's features alone, not of the batch it sits in or of idx_warm (which of the two
+ * kernels runs, and with it the rounding of near-ties, depends on M and C only).
+ * Fewer than k candidates of finite ranking value (NaN / infinite features): the set holds those there are, and every open slot
+ * holds the query's own index -- always an index inside the scene, possibly repeated.
+ * Refused with nothing launched: k outside [1, 64] (FC_ERR_UNSUPPORTED), M < k (FC_ERR_INVALID), C beyond the kernels' tiles
+ * (FC_ERR_UNSUPPORTED; C <= 456 always fits). */
 int fc_op_knn_f32(const float* f, int32_t* idx, int32_t B, int32_t M, int32_t C, int32_t k, void* stream);
 /* The same search started from given neighbour sets idx_warm [B,M,k] (may equal idx): what the DGCNN embedder does between its four
  * levels, which search one cloud in successive feature spaces (models/pytorch_gcn.py:43-60).  Any k distinct candidates bound the k-th

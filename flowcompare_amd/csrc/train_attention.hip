@@ -303,6 +303,29 @@ __device__ __forceinline__ void stage_store(const StageRegs& g, char* dst, int t
     asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v[4]), "v"(v[5]));
     asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v[6]), "v"(v[7]));
 }
+// The same for a dO tile, times the exact power of two c (below) on the way into the limbs
+__device__ __forceinline__ void stage_store_scaled(const StageRegs& g, float c, char* dst, int tid, float& amax) {
+    const StageRegs s{{g.a.x * c, g.a.y * c, g.a.z * c, g.a.w * c}, {g.b.x * c, g.b.y * c, g.b.z * c, g.b.w * c}};
+    stage_store(s, dst, tid, amax);
+}
+// Upstream-gradient normalisation.  Everything behind dO is linear in it (D, dP, dS, dq, dk, dv), and a training step's dO is ~1e-5 and
+// below: split at the fixed scale, dS = P (dP - D) scale then has its hi limb in fp16's subnormals and few bits in lo'.  So dO is multiplied
+// where it is loaded by an exact power of two c with 1 <= c max |dO| < 2 (products by a power of two are exact), and dq / dk / dv by 1 / c
+// where they are stored: the limbs see the magnitudes of a unit-scale gradient at every scale of dO.  The dq kernel takes c per query row
+// (its own 64 values); the dk/dv kernel contracts over the queries and takes one c per scene, from a pass of its own over the scene's dO.
+// The D vector between the two launches is stored unscaled.  c = 1 for an all-zero or non-finite maximum; clamped to 2^+-126.
+__device__ __forceinline__ float grad_norm_factor(float amax) {
+    unsigned e = (__float_as_uint(amax) >> 23) & 0xffu;
+    if (amax == 0.f || e == 255u) return 1.f;
+    e = e < 1u ? 1u : e > 253u ? 253u : e;
+    return __uint_as_float((254u - e) << 23);
+}
+__device__ __forceinline__ float pow2_inverse(float c) { return __uint_as_float(0x7F000000u - __float_as_uint(c)); }
+// range flag of the values handed to split8 behind the inputs (dS); amax as in stage_store
+__device__ __forceinline__ void amax16(const float (&v)[16], float& amax) {
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v[r]), "v"(v[r + 1]));
+}
 #define FC_TR16(PTR_) __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16*)(PTR_))
 #define FC_TR16x2(PTR_) __builtin_bit_cast(f16x8, __builtin_shufflevector(FC_TR16(PTR_), FC_TR16((PTR_) + 8 * A16_PITCH), 0, 1, 2, 3, 4, 5, 6, 7))
 #define FC_MMA3(MAIN_, CROSS_, AH_, AL_, BH_, BL_)                                   \
@@ -310,7 +333,7 @@ __device__ __forceinline__ void stage_store(const StageRegs& g, char* dst, int t
     CROSS_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH_, BL_, CROSS_, 0, 0, 0);      \
     CROSS_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL_, BH_, CROSS_, 0, 0, 0);
 
-// (two waves per SIMD: 247 registers, no scratch -- left to itself hipcc takes 276 and one wave per SIMD: 569 -> 388 us per C2 launch)
+// (two waves per SIMD: 248 registers with the per-query factor, no scratch -- left to itself hipcc takes 276 and one wave per SIMD: 569 -> 388 us per C2 launch)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd16_dq_kernel(AttnBwdParams p, int* __restrict__ ovf) {
     constexpr int DH = 64;
     constexpr int ST = 32 * A16_PITCH;                                // one stage; two per operand
@@ -325,7 +348,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const float* vb = p.v + (size_t)b * p.M * p.ldv;
     // this lane's query row as B operands: step ds covers head dims 16 ds + 8 h .. + 7
     f16x8 Qh[4], Ql[4], Gh[4], Gl[4];
-    float dsum = 0.f, amax = 0.f;
+    float dsum = 0.f, amax = 0.f, gmax = 0.f;
+    float graw[4][8];
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            graw[ds][i] = qok ? p.dout[grow * p.lddo + 16 * ds + 8 * h + i] : 0.f;
+            gmax = fmaxf(gmax, fabsf(graw[ds][i]));
+        }
+    gmax = fmaxf(gmax, __shfl_xor(gmax, 32, 64));
+    const float gc = grad_norm_factor(gmax);                          // this query's power of two: dO, D, dP, dS and dQ below are times gc
 #pragma unroll
     for (int ds = 0; ds < 4; ++ds) {
         float qv[8], gv[8];
@@ -333,7 +366,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int i = 0; i < 8; ++i) {
             const int d = 16 * ds + 8 * h + i;
             qv[i] = qok ? p.q[grow * p.ldq + d] : 0.f;
-            gv[i] = qok ? p.dout[grow * p.lddo + d] : 0.f;
+            gv[i] = graw[ds][i] * gc;
             dsum += gv[i] * (qok ? p.o[grow * p.ldo + d] : 0.f);
             amax = fmaxf(amax, fmaxf(fabsf(qv[i]), fabsf(gv[i])));
         }
@@ -377,7 +410,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     const float lse = p.have_lse ? p.lse[grow] : (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;      // natural log-sum-exp
     const float lse2 = lse * 1.4426950408889634f;
-    if (qok && h == 0) { if (!p.have_lse) p.lse[grow] = lse; p.dvec[grow] = dsum; }
+    if (qok && h == 0) { if (!p.have_lse) p.lse[grow] = lse; p.dvec[grow] = dsum * pow2_inverse(gc); }
     // ---- pass B: dQ^T[d][query] += K^T dS^T
     floatx16 qm[2], qc[2];
 #pragma unroll
@@ -419,6 +452,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const float pr = kok ? __builtin_amdgcn_exp2f((sm[r] + sc[r] * (1.0f / 2048.0f)) * sl2 - lse2) : 0.f;
             dsv[r] = pr * ((pm[r] + pc[r] * (1.0f / 2048.0f)) - dsum) * p.scale;          // dS^T[key][query]
         }
+        amax16(dsv, amax);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             f16x8 sh, sl;
@@ -431,12 +465,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
     }
-    if (amax >= 65504.0f || amax != amax) atomicOr(ovf, 1);
+    const float ginv = pow2_inverse(gc);
+    bool nan = false;                                                  // (v_max3 returns the other operand for a NaN: NaNs are caught where they end up)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            qm[i][r] = (qm[i][r] + qc[i][r] * (1.0f / 2048.0f)) * ginv;
+            nan |= qm[i][r] != qm[i][r];
+        }
+    if (amax >= 65504.0f || amax != amax || nan) atomicOr(ovf, 1);
     if (qok)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) p.dq[grow * p.lddq + i * 32 + acc_row(r, h)] = qm[i][r] + qc[i][r] * (1.0f / 2048.0f);
+            for (int r = 0; r < 16; ++r) p.dq[grow * p.lddq + i * 32 + acc_row(r, h)] = qm[i][r];
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd16_dkv_kernel(AttnBwdParams p, int* __restrict__ ovf) {
@@ -445,11 +488,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __shared__ __attribute__((aligned(16))) char sG[2 * ST];
     __shared__ float sLse[2][32];
     __shared__ float sD[2][32];
+    __shared__ float sMax[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
     const int b = blockIdx.y;
     const int krow = blockIdx.x * 128 + wave * 32 + li;
     const bool kok = krow < p.M;
     const size_t gk = (size_t)b * p.M + (kok ? krow : 0);
+    const int ntiles = (p.N + 31) / 32;
+    const size_t q0 = (size_t)b * p.N;
+    const float* const qsrc = p.q + q0 * p.ldq;
+    const float* const gsrc = p.dout + q0 * p.lddo;
+    // the scene's power of two (grad_norm_factor): one pass over the scene's dO rows, which the tile loop below reads again (out of L2);
+    // every workgroup of a scene derives the same value, whatever the batch around it
+    float gmax = 0.f;
+#pragma unroll 4
+    for (int t = 0; t < ntiles; ++t) {
+        const StageRegs g = stage_load(gsrc, p.lddo, t * 32, p.N, tid);
+        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(gmax) : "v"(g.a.x), "v"(g.a.y));
+        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(gmax) : "v"(g.a.z), "v"(g.a.w));
+        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(gmax) : "v"(g.b.x), "v"(g.b.y));
+        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(gmax) : "v"(g.b.z), "v"(g.b.w));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o, 64));
+    if (lane == 0) sMax[wave] = gmax;
+    __syncthreads();
+    gmax = fmaxf(fmaxf(sMax[0], sMax[1]), fmaxf(sMax[2], sMax[3]));
+    const float gc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(grad_norm_factor(gmax))));
     f16x8 Kh[4], Kl[4], Vh[4], Vl[4];
     float amax = 0.f;
 #pragma unroll
@@ -470,26 +535,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { km[i][r] = 0.f; kc[i][r] = 0.f; vm[i][r] = 0.f; vc[i][r] = 0.f; }
-    const int ntiles = (p.N + 31) / 32;
     const float sl2 = p.scale * 1.4426950408889634f;
-    const size_t q0 = (size_t)b * p.N;
     const int a_off = li * A16_PITCH + 16 * h;
     const int tr_off = (4 * h + ((lane & 15) >> 2)) * A16_PITCH + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
-    const float* const qsrc = p.q + q0 * p.ldq;
-    const float* const gsrc = p.dout + q0 * p.lddo;
     StageRegs rq, rg;
     float r_lse = INFINITY, r_d = 0.f;
     auto vec_load = [&](int t) {                                       // per-query log-sum-exp (log2 domain) and D of tile t, lanes 0..31 of wave 0
         if (tid < 32) {
             const int qi = t * 32 + tid;
             r_lse = qi < p.N ? p.lse[q0 + qi] * 1.4426950408889634f : INFINITY;          // exp2(s - inf) = 0: queries past the end contribute nothing
-            r_d = qi < p.N ? p.dvec[q0 + qi] : 0.f;
+            r_d = qi < p.N ? p.dvec[q0 + qi] * gc : 0.f;                                  // D at the scene's scale, as dO below
         }
     };
     auto vec_store = [&](int st) { if (tid < 32) { sLse[st][tid] = r_lse; sD[st][tid] = r_d; } };
     if (ntiles > 0) {
         stage_store(stage_load(qsrc, p.ldq, 0, p.N, tid), sQ, tid, amax);
-        stage_store(stage_load(gsrc, p.lddo, 0, p.N, tid), sG, tid, amax);
+        stage_store_scaled(stage_load(gsrc, p.lddo, 0, p.N, tid), gc, sG, tid, amax);
         vec_load(0); vec_store(0);
     }
     if (ntiles > 1) { rq = stage_load(qsrc, p.ldq, 32, p.N, tid); rg = stage_load(gsrc, p.lddo, 32, p.N, tid); vec_load(1); }
@@ -499,10 +560,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const char* const cQ = sQ + cur * ST;
         const char* const cG = sG + cur * ST;
         // The next tile's limbs first (the co-resident wave's products cover the conversion), then S, then dP: one pair of score accumulators
-        // live at a time and the staging registers empty from here to the next request -- 256 registers hold the rest (two waves per SIMD)
+        // live at a time and the staging registers empty from here to the next request -- 256 registers hold the rest (two waves per SIMD;
+        // hipcc's resource-usage remark also reports 120 bytes of scratch per lane, 128 before the scene factor, which is a scalar)
         if (t + 1 < ntiles) {
             stage_store(rq, sQ + (cur ^ 1) * ST, tid, amax);
-            stage_store(rg, sG + (cur ^ 1) * ST, tid, amax);
+            stage_store_scaled(rg, gc, sG + (cur ^ 1) * ST, tid, amax);
             vec_store(cur ^ 1);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -532,6 +594,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 dsv[r] = pv[r] * ((pm[r] + pc[r] * (1.0f / 2048.0f)) - sD[cur][acc_row(r, h)]) * p.scale;
+            amax16(dsv, amax);
         }
         // dV from P, then dK from dS (each accumulator still receives j = 0 before j = 1): fewer operands live at once than with both interleaved
         __builtin_amdgcn_sched_barrier(0);
@@ -561,14 +624,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __builtin_amdgcn_sched_barrier(0);
         if (t + 2 < ntiles) { rq = stage_load(qsrc, p.ldq, (t + 2) * 32, p.N, tid); rg = stage_load(gsrc, p.lddo, (t + 2) * 32, p.N, tid); vec_load(t + 2); }
     }
-    if (amax >= 65504.0f || amax != amax) atomicOr(ovf, 1);
+    const float ginv = pow2_inverse(gc);
+    bool nan = false;                                                  // as in the dq kernel
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            km[i][r] = (km[i][r] + kc[i][r] * (1.0f / 2048.0f)) * ginv;
+            vm[i][r] = (vm[i][r] + vc[i][r] * (1.0f / 2048.0f)) * ginv;
+            nan |= km[i][r] != km[i][r] || vm[i][r] != vm[i][r];
+        }
+    if (amax >= 65504.0f || amax != amax || nan) atomicOr(ovf, 1);
     if (kok)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                p.dk[gk * p.lddk + i * 32 + acc_row(r, h)] = km[i][r] + kc[i][r] * (1.0f / 2048.0f);
-                p.dv[gk * p.lddv + i * 32 + acc_row(r, h)] = vm[i][r] + vc[i][r] * (1.0f / 2048.0f);
+                p.dk[gk * p.lddk + i * 32 + acc_row(r, h)] = km[i][r];
+                p.dv[gk * p.lddv + i * 32 + acc_row(r, h)] = vm[i][r];
             }
 }
 #undef FC_MMA3

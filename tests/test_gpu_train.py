@@ -594,7 +594,7 @@ def test_flow_backward_with_extra_context_matches_oracle_autograd():
     assert errs["loss"] < 2e-4 and errs["dx"] < 2e-4 and errs["dctx"] < 2e-4 and worst < 2e-4
 
 
-def test_deep_stack_gradients_are_as_close_to_fp64_as_eager_fp32():
+def test_deep_stack_gradients_are_as_close_to_fp64_as_eager_fp32(monkeypatch):
     """Module-initialised weights make a deep stack ill-conditioned (the forward already differs by O(1e-3) nats between fp32 and fp64
     at 8 layers, tests/test_gpu_fullsize.py): the whole-gradient distance of the HIP training path from fp64 autograd through the
     pinned oracle must be no worse than that of the same oracle in fp32 (eager PyTorch, the arithmetic the reference trains in)."""
@@ -610,10 +610,25 @@ def test_deep_stack_gradients_are_as_close_to_fp64_as_eager_fp32():
     ctx = torch.randn(B, Mc, 64, generator=g) * 0.5
     eps = [torch.randn(B, N, 294, generator=g)]
     md["flow"].zero_grad()
+    # the magnitude of the upstream gradient that a real step hands the operators (printed only: test_gpu_train_grad_scale.py relates its
+    # exponents to these): max |dout| per call of the attention backward and of the Linear backward, in the order autograd runs them
+    seen = {"attention": [], "linear": []}
+
+    def recorded(fn, key):
+        def backward(ctx_, dy, *rest):
+            seen[key].append(dy.detach().abs().max().item())
+            return fn(ctx_, dy, *rest)
+        return staticmethod(backward)
+    monkeypatch.setattr(T.AttentionFn, "backward", recorded(T.AttentionFn.backward, "attention"))
+    monkeypatch.setattr(T.LinearActFn, "backward", recorded(T.LinearActFn.backward, "linear"))
     with T.step_guard(device=DEV) as guard:
         lp = TF.flow_log_prob(md["flow"], x.to(DEV), ctx.to(DEV), None, [e.to(DEV) for e in eps])
         (-lp.mean()).backward()
         assert not guard.overflowed()
+    for key, vals in seen.items():
+        if vals:
+            print(f"8 layers at real widths: max |dout| at the {key} backward: first call {vals[0]:.2e}, {len(vals)} calls, "
+                  f"smallest {min(vals):.2e}, largest {max(vals):.2e}")
     c = dict(cfg)
 
     def oracle(dtype):

@@ -14,6 +14,7 @@
 #include "../../include/fcflow_attention_mass.h"
 #include "../../include/fcflow_context_counts.h"
 #include "../../include/fcflow_sparse_stage.h"
+#include "../../include/fcflow_embed_counts.h"
 #include "knobs.h"
 
 namespace fc {
@@ -399,6 +400,18 @@ void knn_check_shape(int ldf, int C, int M, int k);   // throws what launch_knn 
 void launch_gather_max(const float* uv, int lduv, int c_out, const int32_t* idx, int k, float* out, int ldo, int out_col0,
                        int B, int M, int m_stride_rows, hipStream_t s);
 void launch_pool_max_mean(const float* t, int ldt, int width, float* out, int ldo, int B, int M, int m_stride_rows, hipStream_t s);
+// Per-scene point counts of the DGCNN embedder (fcflow_embed_counts.h): counts is a device array [B]; lo / hi are host bounds the caller vouches
+// for, k <= lo <= hi <= M.  Every kernel reads M_b = clamp(counts[b], lo, hi) (device.h: scene_count) and treats scene b as its first M_b rows;
+// buffers keep their [B][M] row strides.  The *_counts launches below are the namesakes above with M_b in the roles of the point count.
+struct SceneCounts { const int32_t* counts; int lo, hi; };
+void launch_knn_counts(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm, const SceneCounts& cnt);
+void knn_check_counts(int ldf, int C, int M, int k, const SceneCounts& cnt);   // throws what launch_knn_counts would, before anything is launched
+// rows >= M_b: no index is read, the output columns get the literal 0.0f (they feed the next level's GEMM)
+void launch_gather_max_counts(const float* uv, int lduv, int c_out, const int32_t* idx, int k, float* out, int ldo, int out_col0, int B, int M, int m_stride_rows,
+                              const SceneCounts& cnt, hipStream_t s);
+void launch_pool_max_mean_counts(const float* t, int ldt, int width, float* out, int ldo, int B, int M, int m_stride_rows, const SceneCounts& cnt, hipStream_t s);
+// rows >= M_b of a dense [B][M][width] fp32 tensor := 0.0f, any width and alignment (the per-point output of a counted embed call)
+void launch_zero_tail_rows(float* out, int width, int B, int M, const SceneCounts& cnt, hipStream_t s);
 
 // ---------------------------------------------------------------- host-side weight table
 struct HostTensor { const float* data; std::vector<int64_t> shape; int64_t numel() const; };

@@ -61,6 +61,14 @@ __device__ __forceinline__ int attn_scene_keys(const int* m_counts, int b, int M
     return c < 1 ? 1 : (c < M ? c : M);
 }
 
+// The points of scene b in a counted embedder launch (fcflow_embed_counts.h): the same scalar load, clamped into the bounds [lo, hi] the
+// host vouches for and has chosen its kernels and grids by -- a device array that disagrees with them can reach neither a row past hi nor
+// a kernel that was not launched.
+__device__ __forceinline__ int scene_count(const int* m_counts, int b, int lo, int hi) {
+    const int c = __builtin_amdgcn_readfirstlane(m_counts[b]);
+    return c < lo ? lo : (c < hi ? c : hi);
+}
+
 // ---------------------------------------------------------------- sum over a workgroup of up to 256 threads (the row kernels of training)
 // deterministic: xor tree inside each wave, then waves in order.  red: blockDim.x / 64 floats of LDS; every thread gets the sum.
 __device__ __forceinline__ float block_sum_256(float v, float* red) {

@@ -85,22 +85,31 @@ static DgWs plan_dg(const fc_dgcnn& e, int B, int M, void* ws, size_t bytes, boo
     return w;
 }
 
-static void dgcnn_forward(fc_dgcnn& e, const float* pts, float* out, int B, int M, void* ws, size_t bytes, hipStream_t s) {
-    if (!pts || !out || B < 1 || M < 1) throw Error(FC_ERR_INVALID, "fc_dgcnn_embed_f32: bad argument");
-    if (M < e.k) throw Error(FC_ERR_INVALID, "fewer context points than n_neighbors (torch.topk raises in the reference)");
+// cnt: null for the uniform call.  With per-scene counts (fcflow_embed_counts.h) scene b is embedded as its first M_b rows: the three places
+// where a row depends on its scene -- the k-NN search, the gather-max behind it, the global pool -- take the count, everything else is
+// row-wise GEMM on the padded batch, whose pad rows are kept at exact zeros going in (w.pts, the cat panel) and coming out ([B, M, E]).
+static void dgcnn_forward(fc_dgcnn& e, const char* who, const float* pts, const SceneCounts* cnt, float* out, int B, int M, void* ws, size_t bytes, hipStream_t s) {
+    if (!pts || !out || B < 1 || M < 1) throw Error(FC_ERR_INVALID, std::string(who) + ": bad argument");
+    if (cnt && !cnt->counts) throw Error(FC_ERR_INVALID, std::string(who) + ": null counts (the call without counts is fc_dgcnn_embed_f32)");
+    if ((cnt ? cnt->lo : M) < e.k) throw Error(FC_ERR_INVALID, "fewer context points than n_neighbors (torch.topk raises in the reference)");
+    if (cnt && (cnt->lo > cnt->hi || cnt->hi > M)) throw Error(FC_ERR_INVALID, std::string(who) + ": counts must satisfy n_neighbors <= count_min <= count_max <= M");
     DgWs w = plan_dg(e, B, M, ws, bytes, false, nullptr);
     launch_fill(w.pts, 0.f, (size_t)w.P_pad * 32, s);
     launch_pack_rows(pts, e.c_in, e.c_in, w.pts, 32, 0, 32, w.P, s);
+    if (cnt) launch_zero_pad_rows(w.pts, 32, cnt->counts, B, M, s);      // (a NaN or 1e30 in the caller's pad rows reaches neither the range flag nor a GEMM)
     if (w.P_pad > w.P) launch_fill(w.cat + (size_t)w.P * 512, 0.f, (size_t)(w.P_pad - w.P) * 512, s);
     for (int l = 0; l < 4; ++l) {
         const float* f = l == 0 ? w.pts : w.cat + e.lvl_col[l - 1];
         const int ldf = l == 0 ? 32 : 512;
-        launch_knn(f, ldf, e.lvl_cin[l], w.idx, B, M, M, e.k, s, l > 0 ? w.idx : nullptr);      // (levels 1-3: warm start from the previous level's sets, in place)
+        // (levels 1-3: warm start from the previous level's sets, in place)
+        if (cnt) launch_knn_counts(f, ldf, e.lvl_cin[l], w.idx, B, M, M, e.k, s, l > 0 ? w.idx : nullptr, *cnt);
+        else launch_knn(f, ldf, e.lvl_cin[l], w.idx, B, M, M, e.k, s, l > 0 ? w.idx : nullptr);
         GemmEpi g{};
         g.C = w.uv; g.ldc = 512;
         ASeg a{f, ldf};
         launch_gemm(e.level[l], &a, w.P_pad, g, EPI_LINEAR, s);
-        launch_gather_max(w.uv, 512, e.lvl_cout[l], w.idx, e.k, w.cat, 512, e.lvl_col[l], B, M, M, s);
+        if (cnt) launch_gather_max_counts(w.uv, 512, e.lvl_cout[l], w.idx, e.k, w.cat, 512, e.lvl_col[l], B, M, M, *cnt, s);
+        else launch_gather_max(w.uv, 512, e.lvl_cout[l], w.idx, e.k, w.cat, 512, e.lvl_col[l], B, M, M, s);
     }
     {
         GemmEpi g{};
@@ -112,11 +121,13 @@ static void dgcnn_forward(fc_dgcnn& e, const float* pts, float* out, int B, int 
     int rows = w.P, rows_pad = w.P_pad;
     if (e.global_pool) {
         launch_fill(w.pool, 0.f, (size_t)w.R_pad * 1024, s);
-        launch_pool_max_mean(w.t5, 512, 512, w.pool, 1024, B, M, M, s);
+        if (cnt) launch_pool_max_mean_counts(w.t5, 512, 512, w.pool, 1024, B, M, M, *cnt, s);
+        else launch_pool_max_mean(w.t5, 512, 512, w.pool, 1024, B, M, M, s);
         in = {w.pool, 1024};
         rows = B; rows_pad = w.R_pad;
     }
     run_head_mlp(e.head, in, w.h, w.otmp, out, rows, rows_pad, 0, s);       // (the out_layer launch of this engine sets no rows_valid)
+    if (cnt && !e.global_pool) launch_zero_tail_rows(out, e.head.E, B, M, *cnt, s);   // (the head ran on the pad rows too: [B, M, E] gets 0.0f there)
 }
 
 const char* get_last_error();
@@ -149,7 +160,17 @@ int fc_dgcnn_workspace_bytes(const fc_dgcnn* emb, int32_t B, int32_t M, size_t* 
 int fc_dgcnn_embed_f32(fc_dgcnn* emb, const float* pts, float* out, int32_t B, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
     FC_API_BEGIN
     fc::embed_guarded(emb, workspace, "fc_dgcnn_embed_f32", (hipStream_t)stream, [=] {
-        fc::dgcnn_forward(*emb, pts, out, B, M, workspace, workspace_bytes, (hipStream_t)stream);
+        fc::dgcnn_forward(*emb, "fc_dgcnn_embed_f32", pts, nullptr, out, B, M, workspace, workspace_bytes, (hipStream_t)stream);
+    });
+    FC_API_END
+}
+/* declared in fcflow_embed_counts.h */
+int fc_dgcnn_embed_counts_f32(fc_dgcnn* emb, const float* pts, const int32_t* counts, int32_t count_min, int32_t count_max, float* out, int32_t B, int32_t M,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    FC_API_BEGIN
+    const fc::SceneCounts cnt{counts, count_min, count_max};
+    fc::embed_guarded(emb, workspace, "fc_dgcnn_embed_counts_f32", (hipStream_t)stream, [=] {
+        fc::dgcnn_forward(*emb, "fc_dgcnn_embed_counts_f32", pts, &cnt, out, B, M, workspace, workspace_bytes, (hipStream_t)stream);
     });
     FC_API_END
 }

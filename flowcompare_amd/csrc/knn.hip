@@ -15,6 +15,7 @@
 #include "common.h"
 #include "device.h"
 #include "launch.h"
+#include <climits>
 #include <cstdio>
 
 namespace fc {
@@ -59,103 +60,27 @@ __device__ __forceinline__ float prune_set(float* vals, int32_t* idxs, int cnt, 
 constexpr int KNN_Q = 4;        // queries per wave
 constexpr int KNN_CAP = 128;    // set capacity per query
 
+// knn_kernel and knn_counts_kernel are the same statements, csrc/knn_lane_body.h, included in both.  In them M is the scene's points in every
+// role the key count has (tiles, clamps, masks, the store's guard), m_rows the rows per scene of idx_out, [B][m_rows][k], and m_stride the
+// rows per scene of f; the uniform kernel has M for both.  (Why an include and not a function: knn_lane_body.h.)
 __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ f, int ldf, int Cp, int32_t* __restrict__ idx_out, int M,
                                                   int m_stride, int k) {
-    extern __shared__ float smem[];
-    const int LDC = Cp + 4;
-    float* s_cand = smem;                                   // [64][LDC]
-    float* s_qry = s_cand + 64 * LDC;                       // [16][LDC]
-    float* s_qxx = s_qry + 16 * LDC;                        // [16]
-    float* s_vals = s_qxx + 16;                             // [16][CAP]
-    int32_t* s_idx = reinterpret_cast<int32_t*>(s_vals + 16 * KNN_CAP);
+    const int m_rows = M;
+#include "knn_lane_body.h"
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.y, q_base = blockIdx.x * 16;
-    const float* fb = f + (size_t)b * m_stride * ldf;
-    const int f4r = Cp / 4;
-
-    // ---- stage the 16 query rows, then |xq|^2 with the SAME fma order used for candidates
-    for (int e = tid; e < 16 * f4r; e += 256) {
-        const int r = e / f4r, c4 = (e - r * f4r) * 4;
-        int qi = q_base + r;
-        qi = qi < M ? qi : M - 1;
-        *reinterpret_cast<float4*>(s_qry + r * LDC + c4) = *reinterpret_cast<const float4*>(fb + (size_t)qi * ldf + c4);
-    }
-    __syncthreads();
-    if (tid < 16) {
-        float xx = 0.f;
-        for (int c = 0; c < Cp; ++c) { const float v = s_qry[tid * LDC + c]; xx = fmaf(v, v, xx); }
-        s_qxx[tid] = xx;
-    }
-    float tau[KNN_Q];
-    int cnt[KNN_Q];
-#pragma unroll
-    for (int qq = 0; qq < KNN_Q; ++qq) { tau[qq] = -INFINITY; cnt[qq] = 0; }
-    __syncthreads();
-    float qxx[KNN_Q];
-#pragma unroll
-    for (int qq = 0; qq < KNN_Q; ++qq) qxx[qq] = s_qxx[wave * KNN_Q + qq];
-
-    const int ntiles = (M + 63) / 64;
-    for (int t = 0; t < ntiles; ++t) {
-        for (int e = tid; e < 64 * f4r; e += 256) {
-            const int r = e / f4r, c4 = (e - r * f4r) * 4;
-            int ci = t * 64 + r;
-            ci = ci < M ? ci : M - 1;
-            *reinterpret_cast<float4*>(s_cand + r * LDC + c4) = *reinterpret_cast<const float4*>(fb + (size_t)ci * ldf + c4);
-        }
-        __syncthreads();
-        // ---- lane = candidate: dot with the wave's 4 queries + own squared norm
-        float dot[KNN_Q] = {0.f, 0.f, 0.f, 0.f};
-        float cxx = 0.f;
-        const float* cr = s_cand + lane * LDC;
-        const float* qr = s_qry + wave * KNN_Q * LDC;
-        for (int c4 = 0; c4 < Cp; c4 += 4) {
-            const float4 cv = *reinterpret_cast<const float4*>(cr + c4);
-            cxx = fmaf(cv.x, cv.x, cxx); cxx = fmaf(cv.y, cv.y, cxx); cxx = fmaf(cv.z, cv.z, cxx); cxx = fmaf(cv.w, cv.w, cxx);
-#pragma unroll
-            for (int qq = 0; qq < KNN_Q; ++qq) {
-                const float4 qv = *reinterpret_cast<const float4*>(qr + qq * LDC + c4);
-                float d = dot[qq];
-                d = fmaf(qv.x, cv.x, d); d = fmaf(qv.y, cv.y, d); d = fmaf(qv.z, cv.z, d); d = fmaf(qv.w, cv.w, d);
-                dot[qq] = d;
-            }
-        }
-        const int cand = t * 64 + lane;
-        const bool cvalid = cand < M;
-#pragma unroll
-        for (int qq = 0; qq < KNN_Q; ++qq) {
-            // pairwise_distance = -xx - inner - xx^T with inner = -2 x^T x   (pytorch_gcn.py:14-16)
-            const float pd = (-cxx + 2.0f * dot[qq]) - qxx[qq];
-            const bool hit = cvalid && pd > tau[qq];
-            const unsigned long long mask = __ballot(hit);
-            if (mask) {
-                float* vals = s_vals + (wave * KNN_Q + qq) * KNN_CAP;
-                int32_t* idxs = s_idx + (wave * KNN_Q + qq) * KNN_CAP;
-                if (hit) {
-                    const int pos = cnt[qq] + popc64(mask & ((1ull << lane) - 1ull));
-                    vals[pos] = pd;
-                    idxs[pos] = cand;
-                }
-                cnt[qq] += popc64(mask);
-                if (cnt[qq] > 64) {
-                    tau[qq] = prune_set(vals, idxs, cnt[qq], k, lane);
-                    cnt[qq] = k;
-                }
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int qq = 0; qq < KNN_Q; ++qq) {
-        float* vals = s_vals + (wave * KNN_Q + qq) * KNN_CAP;
-        int32_t* idxs = s_idx + (wave * KNN_Q + qq) * KNN_CAP;
-        if (cnt[qq] > k) { prune_set(vals, idxs, cnt[qq], k, lane); cnt[qq] = k; }
-        const int qi = q_base + wave * KNN_Q + qq;
-        // fewer than k finite candidates (NaN / -inf features, e.g. in a pass whose fp16 range flag is already up and whose results
-        // will be discarded): the open slots get the query itself, never an uninitialised index (the gathers downstream trust them)
-        if (qi < M && lane < k) idx_out[((size_t)b * M + qi) * k + lane] = lane < cnt[qq] ? idxs[lane] : qi;
-    }
+// Per-scene point counts (fcflow_embed_counts.h): scene b is searched as if it had been passed alone with its first M_b rows, M_b =
+// scene_count(m_counts, b, count_min, count_max); idx_out keeps its [B][M][k] shape and rows >= M_b of it are written by nobody.  The grid
+// covers count_max queries: a workgroup whose first query is past its scene's end leaves before any LDS write or barrier, and so does every
+// workgroup of a scene that the other kernel owns (M_b >= mfma_from, the count from which a scene alone takes the matrix-core kernel).
+__global__ __launch_bounds__(256) void knn_counts_kernel(const float* __restrict__ f, int ldf, int Cp, int32_t* __restrict__ idx_out, int M,
+                                                         int m_stride, int k, const int32_t* __restrict__ m_counts, int count_min, int count_max,
+                                                         int mfma_from) {
+    const int Mb = scene_count(m_counts, blockIdx.y, count_min, count_max);
+    if (Mb >= mfma_from || (int)blockIdx.x * 16 >= Mb) return;
+    const int m_rows = M;
+    M = Mb;
+#include "knn_lane_body.h"
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -193,222 +118,57 @@ __device__ __forceinline__ void knn_insert(float& sv, int& si, float v, int ci) 
 
 constexpr int KM_TC = 64;       // candidates per LDS block
 
+// (knn_mfma_kernel and knn_mfma_counts_kernel: the statements of csrc/knn_mfma_body.h, included in both; M, m_rows and m_stride as in the
+// lane kernels, and `warm` is [B][m_rows][k] like idx_out)
 template <int CP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void knn_mfma_kernel(const float* __restrict__ f, int ldf, int C, int32_t* idx_out, int M, int m_stride,
                                                        int k, const int32_t* warm) {
-    extern __shared__ float smem[];
-    constexpr int LDC = CP + 4, H = CP / 2, NLD = (KM_TC * CP / 4 + 255) / 256;
-    float* s_qxx = smem + 2 * KM_TC * LDC;                        // [4 waves][32]
-    float* s_tau = s_qxx + 128;                                   // [4 waves][32]: warm-start thresholds
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
-    const int b = blockIdx.y, q0 = blockIdx.x * 128 + wave * 32;
-    const float* fb = f + (size_t)b * m_stride * ldf;
-
-    // ---- this wave's 32 queries as the A operand: lane (i, kh) holds features kh * H + 0 .. H - 1 of query i
-    float aq[H];
-    {
-        int qi = q0 + li;
-        qi = qi < M ? qi : M - 1;
-        const float* src = fb + (size_t)qi * ldf + lh * H;
-        float nrm = 0.f;
-#pragma unroll
-        for (int u = 0; u < H; u += 4) {
-            float4 v = *reinterpret_cast<const float4*>(src + u);
-            if (CP != C) {                                        // columns C .. CP - 1 are padding, whatever the memory holds
-                const int c0 = lh * H + u;
-                v.x = c0 < C ? v.x : 0.f; v.y = c0 + 1 < C ? v.y : 0.f; v.z = c0 + 2 < C ? v.z : 0.f; v.w = c0 + 3 < C ? v.w : 0.f;
-            }
-            aq[u] = v.x; aq[u + 1] = v.y; aq[u + 2] = v.z; aq[u + 3] = v.w;
-            nrm = fmaf(v.x, v.x, nrm); nrm = fmaf(v.y, v.y, nrm); nrm = fmaf(v.z, v.z, nrm); nrm = fmaf(v.w, v.w, nrm);
-        }
-        nrm += __shfl_xor(nrm, 32);
-        if (lh == 0) s_qxx[wave * 32 + li] = nrm;
-        // ---- warm start (round 4): `warm` holds k neighbours of every query from the PREVIOUS DGCNN level (models/pytorch_gcn.py:43-60: the four
-        // edge convolutions search the same cloud in successive feature spaces).  Any k distinct candidates bound the k-th best from below, so
-        // the stream starts with tau0 = min_j pd(query, warm_j) instead of -inf and the ~k ln(M / k) insertions that only serve to raise the
-        // threshold never happen (the previous level's neighbours are mostly near in this level's space too).  The selection stays EXACT:
-        // tau0 is lowered by a bound on the rounding difference between this scalar fmaf chain and the MFMA's sums, every candidate above it
-        // goes through the same sorted insertion in the same order, and tau only ever rises.  A set that holds an index twice (e.g. through the
-        // "open slots get the query itself" rule below), an index outside the cloud or a non-finite value gives no bound: tau0 = -inf, the
-        // plain stream.  Distinctness is checked for real (a wave looks at its 32 sets one after the other, entry j on lane j, against the
-        // entries 1 .. k / 2 places further round the set: every unordered pair once).
-        float tau0 = -INFINITY;
-        if (warm) {
-            unsigned dup_mask = 0;                                     // bit q: the set of this wave's query q repeats an index
-            for (int q = 0; q < 32; ++q) {
-                int qq = q0 + q;
-                qq = qq < M ? qq : M - 1;
-                const int mine = lane < k ? warm[((size_t)b * M + qq) * k + lane] : -1 - lane;
-                bool dup = false;
-                for (int d = 1; d <= k / 2; ++d) {
-                    int o = lane + d;
-                    o = o >= k ? o - k : o;
-                    dup |= lane < k && __shfl(mine, o, 64) == mine;
-                }
-                dup_mask |= __ballot(dup) ? (1u << q) : 0u;
-            }
-            const int32_t* wl = warm + ((size_t)b * M + qi) * k;
-            float tmin = INFINITY, cmax = 0.f;
-            bool bad = ((dup_mask >> li) & 1u) != 0;
-            for (int j = 0; j < k; ++j) {
-                int ci = wl[j];
-                bad |= ci < 0 || ci >= M;
-                ci = ci < 0 ? 0 : (ci >= M ? M - 1 : ci);
-                const float* row = fb + (size_t)ci * ldf + lh * H;
-                float dot = 0.f, cx = 0.f;
-#pragma unroll
-                for (int u = 0; u < H; u += 4) {
-                    float4 v = *reinterpret_cast<const float4*>(row + u);
-                    if (CP != C) {
-                        const int c0 = lh * H + u;
-                        v.x = c0 < C ? v.x : 0.f; v.y = c0 + 1 < C ? v.y : 0.f; v.z = c0 + 2 < C ? v.z : 0.f; v.w = c0 + 3 < C ? v.w : 0.f;
-                    }
-                    dot = fmaf(aq[u], v.x, dot); dot = fmaf(aq[u + 1], v.y, dot); dot = fmaf(aq[u + 2], v.z, dot); dot = fmaf(aq[u + 3], v.w, dot);
-                    cx = fmaf(v.x, v.x, cx); cx = fmaf(v.y, v.y, cx); cx = fmaf(v.z, v.z, cx); cx = fmaf(v.w, v.w, cx);
-                }
-                dot += __shfl_xor(dot, 32);
-                cx += __shfl_xor(cx, 32);
-                const float pd = fmaf(2.0f, dot, -cx) - nrm;
-                bad |= !(pd == pd);
-                tmin = fminf(tmin, pd);
-                cmax = fmaxf(cmax, cx);
-            }
-            // |2 x.y computed two ways| differs by at most ~2 C eps |x| |y| <= C eps (|x|^2 + |y|^2); 2^-21 = 4 eps covers the two subtractions as well
-            const float margin = (float)CP * 4.76837158e-7f * (nrm + cmax + fabsf(tmin));
-            tau0 = tmin - margin;
-            // The bound above is a RELATIVE one: it holds while no product or partial sum leaves the normal range.  Where it does (norms
-            // below ~2^-40: a term that rounds in the subnormal range is off by up to 2^-150, 2 CP + 2 of them by < 2^-141) or where the
-            // margin is plain zero (query and warm neighbours all zero: every candidate ties at pd = 0 and `pd > tau0` would turn all of
-            // them away), tau0 would not lie strictly below the k-th best as the stream computes it.  A margin of at least 2^-100 is normal
-            // itself and covers 2^-141 many times over; anything smaller gives no bound: tau0 = -inf, the plain stream.
-            if (bad || !(margin >= 7.88860905e-31f) || !(tau0 < tmin)) tau0 = -INFINITY;
-        }
-        if (lh == 0) s_tau[wave * 32 + li] = tau0;
-    }
-    // ---- block loader: thread e covers float4 e of the 64 x CP block (register-staged, written to the other buffer after the block's products)
-    // in two parts (one per 32-candidate tile of the block in flight), so that only half of a block's float4s are live at a time
-    constexpr int NPART = NLD >= 2 ? 2 : 1, NPP = NLD / NPART;
-    float4 stg[NPP];
-    auto gload = [&](int blk, int part) {
-#pragma unroll
-        for (int i = 0; i < NPP; ++i) {
-            const int e = tid + 256 * (part * NPP + i);
-            if (NLD * 256 == KM_TC * CP / 4 || e < KM_TC * CP / 4) {
-                const int r = e / (CP / 4), c4 = (e - r * (CP / 4)) * 4;
-                int ci = blk * KM_TC + r;
-                ci = ci < M ? ci : M - 1;
-                float4 v = *reinterpret_cast<const float4*>(fb + (size_t)ci * ldf + c4);
-                if (CP != C) { v.x = c4 < C ? v.x : 0.f; v.y = c4 + 1 < C ? v.y : 0.f; v.z = c4 + 2 < C ? v.z : 0.f; v.w = c4 + 3 < C ? v.w : 0.f; }
-                stg[i] = v;
-            }
-        }
-    };
-    auto lstore = [&](float* dst, int part) {
-#pragma unroll
-        for (int i = 0; i < NPP; ++i) {
-            const int e = tid + 256 * (part * NPP + i);
-            if (NLD * 256 == KM_TC * CP / 4 || e < KM_TC * CP / 4) {
-                const int r = e / (CP / 4), c4 = (e - r * (CP / 4)) * 4;
-                *reinterpret_cast<float4*>(dst + r * LDC + c4) = stg[i];
-            }
-        }
-    };
-    float qxx[16], tau[16];
-    float setv[16][2];
-    int seti[16][2];
-#pragma unroll
-    for (int part = 0; part < NPART; ++part) { gload(0, part); lstore(smem, part); }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        qxx[r] = s_qxx[wave * 32 + 8 * (r >> 2) + 4 * lh + (r & 3)];
-        tau[r] = s_tau[wave * 32 + 8 * (r >> 2) + 4 * lh + (r & 3)];
-        setv[r][0] = setv[r][1] = -INFINITY;
-        seti[r][0] = seti[r][1] = 0;
-    }
-
-    const int nblk = (M + KM_TC - 1) / KM_TC;
-    for (int blk = 0; blk < nblk; ++blk) {
-        const float* cur = smem + (blk & 1) * (KM_TC * LDC);
-        float* nxt = smem + ((blk + 1) & 1) * (KM_TC * LDC);
-        const bool more = blk + 1 < nblk;
-#pragma unroll 1
-        for (int t = 0; t < KM_TC / 32; ++t) {
-            const int cbase = blk * KM_TC + t * 32;
-            if (more && t < NPART) gload(blk + 1, t);            // (the next block is complete: cbase < M for both of this block's tiles)
-            if (cbase >= M) break;
-            const float* brow = cur + (t * 32 + li) * LDC + lh * H;
-            floatx16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            float cxx = 0.f;
-#pragma unroll
-            for (int u = 0; u < H; u += 4) {
-                const float4 bv = *reinterpret_cast<const float4*>(brow + u);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[u], bv.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[u + 1], bv.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[u + 2], bv.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[u + 3], bv.w, acc, 0, 0, 0);
-                cxx = fmaf(bv.x, bv.x, cxx); cxx = fmaf(bv.y, bv.y, cxx); cxx = fmaf(bv.z, bv.z, cxx); cxx = fmaf(bv.w, bv.w, cxx);
-            }
-            cxx += __shfl_xor(cxx, 32);
-            if (cbase + li >= M) cxx = INFINITY;                  // candidates past the end: pd = -inf, never a hit
-            // tau is refreshed once per register, behind its hits: a value below the true k-th best lands behind lane k - 1, where it is
-            // ignored.  (Measured: inserting the hits of four lists side by side -- two registers x two half-waves, dummies of -inf for lists
-            // without a pending hit -- is no faster, 5.4 vs 5.2 ms per C2 forward: the second wave of the SIMD already fills the gaps of
-            // one insertion's dependent chain, so the dummy work costs what the interleaving gains.)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pd = fmaf(2.0f, acc[r], -cxx) - qxx[r];
-                unsigned long long mask = __ballot(pd > tau[r]);
-                if (mask) {                                       // (wave-uniform)
-                    do {
-                        const int bpos = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                        const float v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pd), bpos));
-                        const int ci = cbase + (bpos & 31);
-                        if (bpos < 32) knn_insert(setv[r][0], seti[r][0], v, ci);
-                        else knn_insert(setv[r][1], seti[r][1], v, ci);
-                    } while (mask);
-                    const float t0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, setv[r][0]), k - 1));
-                    const float t1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, setv[r][1]), k - 1));
-                    tau[r] = fmaxf(tau[r], lh ? t1 : t0);        // (never below the warm-start threshold; without one the list's k-th entry only rises anyway)
-                }
-            }
-            if (more && t < NPART) lstore(nxt, t);
-        }
-        __syncthreads();
-    }
-    // ---- entry e of query (r, half) sits on lane e.  Fewer than k finite candidates (NaN / -inf features in a pass whose range flag is
-    // already up): the open slots get the query itself, never an uninitialised index (the gathers downstream trust them)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int qi = q0 + 8 * (r >> 2) + 4 * h + (r & 3);
-            if (qi < M && lane < k) idx_out[((size_t)b * M + qi) * k + lane] = setv[r][h] > -INFINITY ? seti[r][h] : qi;
-        }
+    const int m_rows = M;
+#include "knn_mfma_body.h"
 }
 
+// (with per-scene counts, as knn_counts_kernel: the scenes below mfma_from belong to that kernel, and a workgroup's first query is blockIdx.x * 128)
 template <int CP>
-static void launch_knn_mfma(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void knn_mfma_counts_kernel(const float* __restrict__ f, int ldf, int C, int32_t* idx_out, int M,
+                                                       int m_stride, int k, const int32_t* warm, const int32_t* __restrict__ m_counts, int count_min, int count_max, int mfma_from) {
+    const int Mb = scene_count(m_counts, blockIdx.y, count_min, count_max);
+    if (Mb < mfma_from || (int)blockIdx.x * 128 >= Mb) return;
+    const int m_rows = M;
+    M = Mb;
+#include "knn_mfma_body.h"
+}
+
+// cnt: null for the uniform launch, or the per-scene counts of a counted one (grid over cnt->hi queries; mfma_from as in the kernels)
+template <int CP>
+static void launch_knn_mfma(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm,
+                            const SceneCounts* cnt = nullptr, int mfma_from = 0) {
     constexpr size_t lds = (2 * (size_t)KM_TC * (CP + 4) + 256) * sizeof(float);
-    char name[112];
+    char name[160];
+    if (cnt) {
+        snprintf(name, sizeof name, "void fc::knn_mfma_counts_kernel<%d>(float const*, int, int, int*, int, int, int, int const*, int const*, int, int, int)", CP);
+        launch_kernel<knn_mfma_counts_kernel<CP>, (int)lds>(name, 2.0 * B * (double)cnt->hi * cnt->hi * C, 4.0 * B * (double)cnt->hi * (C + k), dim3((cnt->hi + 127) / 128, B),
+                                                            dim3(256), lds, s, f, ldf, C, idx, M, m_stride_rows, k, warm, cnt->counts, cnt->lo, cnt->hi, mfma_from);
+        return;
+    }
     snprintf(name, sizeof name, "void fc::knn_mfma_kernel<%d>(float const*, int, int, int*, int, int, int, int const*)", CP);
     launch_kernel<knn_mfma_kernel<CP>, (int)lds>(name, 2.0 * B * (double)M * M * C, 4.0 * B * (double)M * (C + k), dim3((M + 127) / 128, B), dim3(256), lds, s,
                                                  f, ldf, C, idx, M, m_stride_rows, k, warm);
 }
 
-// the padded feature width of the matrix-core kernel where a search of this shape takes it, 0 where it takes the lane-per-candidate kernel
-static int knn_mfma_width(int ldf, int C, int M) {
+// The kernel choice in two parts.  The shape part: the padded feature width of the matrix-core kernel where it takes features of this shape,
+// 0 where it does not (wider features, a pitch that does not cover the padded row, knob 24 = 0) ...
+static int knn_mfma_shape(int ldf, int C) {
     if (!g_knobs.knn_mfma) return 0;                                // (knob 24)
     const int Cp8 = C <= 8 ? 8 : (C <= 16 ? 16 : (C <= 32 ? 32 : (C <= 64 ? 64 : (C <= 128 ? 128 : 0))));
-    // (wider features or a pitch that does not cover the padded row: the lane-per-candidate kernel; so do small scenes -- a workgroup of the MFMA
-    // kernel owns 128 queries for ALL M candidates, which takes as long with two scenes in the batch as with sixteen, so the choice depends on
-    // M alone (a scene's neighbour sets, near-ties included, must not depend on the batch it sits in); at M = 1024 the 16-query
-    // workgroups of the lane-per-candidate kernel finish a C1 batch in 0.37 ms against 2.7)
-    return Cp8 && ldf >= Cp8 && (g_knobs.knn_mfma == 2 || M >= 2048) ? Cp8 : 0;
+    return Cp8 && ldf >= Cp8 ? Cp8 : 0;
 }
+// ... and the count from which a scene of such a shape takes it.  Small scenes take the lane-per-candidate kernel -- a workgroup of the MFMA
+// kernel owns 128 queries for ALL M candidates, which takes as long with two scenes in the batch as with sixteen, so the choice depends on
+// M alone (a scene's neighbour sets, near-ties included, must not depend on the batch it sits in); at M = 1024 the 16-query
+// workgroups of the lane-per-candidate kernel finish a C1 batch in 0.37 ms against 2.7.  A counted search asks per scene (launch_knn_counts).
+static int knn_mfma_from() { return g_knobs.knn_mfma == 2 ? 1 : 2048; }
+// the padded feature width of the matrix-core kernel where a search of this shape takes it, 0 where it takes the lane-per-candidate kernel
+static int knn_mfma_width(int ldf, int C, int M) { return M >= knn_mfma_from() ? knn_mfma_shape(ldf, C) : 0; }
 static size_t knn_lane_lds(int Cp) { return ((size_t)(64 + 16) * (Cp + 4) + 16 + 16 * KNN_CAP) * sizeof(float) + 16 * KNN_CAP * sizeof(int32_t); }
 
 // every refusal of launch_knn that the shape alone decides (an operator entry asks before it launches anything of its own)
@@ -436,6 +196,40 @@ void launch_knn(const float* f, int ldf, int C, int32_t* idx, int B, int M, int 
     }
     launch_kernel<knn_kernel, 160 * 1024>("fc::knn_kernel(float const*, int, int, int*, int, int, int)", 2.0 * B * (double)M * M * C, 4.0 * B * (double)M * (C + k),
                                           dim3((M + 15) / 16, B), dim3(256), knn_lane_lds(Cp), s, f, ldf, Cp, idx, M, m_stride_rows, k);
+}
+
+// ---- per-scene counts (fcflow_embed_counts.h): scene b is searched over its first clamp(counts[b], lo, hi) rows, by the kernel it takes alone.
+// the refusals of launch_knn_counts that shape and bounds decide: k <= lo <= hi <= M, and the lane kernel's LDS tile where a scene can take it
+void knn_check_counts(int ldf, int C, int M, int k, const SceneCounts& cnt) {
+    if (k > 64 || k < 1) throw Error(FC_ERR_UNSUPPORTED, "knn: k must be in [1, 64]");
+    if (!cnt.counts) throw Error(FC_ERR_INVALID, "knn: null counts (the search without counts is launch_knn)");
+    if (cnt.lo < k) throw Error(FC_ERR_INVALID, "knn: count_min: fewer points than neighbours (torch.topk would raise as well)");
+    if (cnt.lo > cnt.hi || cnt.hi > M) throw Error(FC_ERR_INVALID, "knn: counts must satisfy k <= count_min <= count_max <= M");
+    const int from = knn_mfma_shape(ldf, C) ? knn_mfma_from() : INT_MAX;
+    if (cnt.lo < from && knn_lane_lds(round_up(C, 4)) > 160 * 1024) throw Error(FC_ERR_UNSUPPORTED, "knn: feature dimension too large for the LDS tile");
+}
+
+// idx (and warm) stay [B][M][k]; rows >= a scene's count are not written.  The lane kernel is launched iff some scene can lie below the
+// threshold, the matrix-core kernel iff some scene can lie at or above it: a batch on both sides costs two launches, each scene's workgroups
+// leave the launch that is not theirs at once, and every scene gets exactly the sets it gets alone.
+void launch_knn_counts(const float* f, int ldf, int C, int32_t* idx, int B, int M, int m_stride_rows, int k, hipStream_t s, const int32_t* warm, const SceneCounts& cnt) {
+    if (!g_knobs.knn_warm) warm = nullptr;                          // (knob 32)
+    knn_check_counts(ldf, C, M, k, cnt);
+    const int Cp = round_up(C, 4);
+    if (ldf < Cp || ldf % 4 != 0 || ((uintptr_t)f & 15)) throw Error(FC_ERR_INVALID, "knn: feature pitch must cover round_up(C,4) and be 16-byte aligned");
+    const int width = knn_mfma_shape(ldf, C), from = width ? knn_mfma_from() : INT_MAX;
+    if (cnt.lo < from)
+        launch_kernel<knn_counts_kernel, 160 * 1024>("fc::knn_counts_kernel(float const*, int, int, int*, int, int, int, int const*, int, int, int)",
+                                                     2.0 * B * (double)cnt.hi * cnt.hi * C, 4.0 * B * (double)cnt.hi * (C + k), dim3((cnt.hi + 15) / 16, B), dim3(256),
+                                                     knn_lane_lds(Cp), s, f, ldf, Cp, idx, M, m_stride_rows, k, cnt.counts, cnt.lo, cnt.hi, from);
+    if (cnt.hi < from) return;
+    switch (width) {
+        case 8: return launch_knn_mfma<8>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm, &cnt, from);
+        case 16: return launch_knn_mfma<16>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm, &cnt, from);
+        case 32: return launch_knn_mfma<32>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm, &cnt, from);
+        case 64: return launch_knn_mfma<64>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm, &cnt, from);
+        default: return launch_knn_mfma<128>(f, ldf, C, idx, B, M, m_stride_rows, k, s, warm, &cnt, from);
+    }
 }
 
 }  // namespace fc

@@ -276,12 +276,16 @@ void launch_expm_coupling(const float* params, int ldp, float* xbuf, int ldx, in
 // out[p, c] = LeakyReLU_0.2( max_j u[idx[p, j], c] + v[p, c] ), uv rows = [u (c_out) | v (c_out)].
 // Equals conv(cat(nbr - x, x)) -> BN -> LeakyReLU -> max_k of models/pytorch_gcn.py:23-47,85-99 because the 1x1 conv is
 // linear (W1 nbr + (W2 - W1) x), eval BN is a per-channel affine map folded into u and v, and LeakyReLU is monotone.
-__global__ void gather_max_kernel(const float* __restrict__ uv, int lduv, int c_out, const int32_t* __restrict__ idx, int k,
-                                  float* out, int ldo, int out_col0, int M, int m_stride, int total) {
-    const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (p >= total) return;
-    const int b = p / M, i = p - b * M;
+// The body is shared with the counted kernel (fcflow_embed_counts.h): CNT = with per-scene counts, Mb = the points of row p's scene; the uniform
+// kernel's instantiation has no pad-row test at all.
+template <bool CNT>
+__device__ __forceinline__ void gather_max_row(const float* __restrict__ uv, int lduv, int c_out, const int32_t* __restrict__ idx, int k, float* out, int ldo, int out_col0,
+                                               int M, int m_stride, int b, int i, int Mb, int lane) {
     const size_t base = (size_t)b * m_stride;
+    if (CNT && i >= Mb) {                               // a pad row: no index is read, and the next level's GEMM finds zeros, not stale workspace bytes
+        for (int c = lane; c < c_out; c += 64) out[(base + i) * ldo + out_col0 + c] = 0.0f;
+        return;
+    }
     const int32_t* ip = idx + ((size_t)b * M + i) * k;
     for (int c = lane; c < c_out; c += 64) {
         float mx = -INFINITY;
@@ -290,15 +294,37 @@ __global__ void gather_max_kernel(const float* __restrict__ uv, int lduv, int c_
         out[(base + i) * ldo + out_col0 + c] = t > 0.f ? t : 0.2f * t;
     }
 }
+__global__ void gather_max_kernel(const float* __restrict__ uv, int lduv, int c_out, const int32_t* __restrict__ idx, int k,
+                                  float* out, int ldo, int out_col0, int M, int m_stride, int total) {
+    const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (p >= total) return;
+    const int b = p / M, i = p - b * M;
+    gather_max_row<false>(uv, lduv, c_out, idx, k, out, ldo, out_col0, M, m_stride, b, i, M, lane);
+}
+__global__ void gather_max_counts_kernel(const float* __restrict__ uv, int lduv, int c_out, const int32_t* __restrict__ idx, int k,
+                                         float* out, int ldo, int out_col0, int M, int m_stride, int total, const int32_t* __restrict__ m_counts, int count_min,
+                                         int count_max) {
+    const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (p >= total) return;
+    const int b = p / M, i = p - b * M;                 // (one wave per row: b is wave-uniform)
+    gather_max_row<true>(uv, lduv, c_out, idx, k, out, ldo, out_col0, M, m_stride, b, i, scene_count(m_counts, b, count_min, count_max), lane);
+}
 void launch_gather_max(const float* uv, int lduv, int c_out, const int32_t* idx, int k, float* out, int ldo, int out_col0, int B, int M,
                        int m_stride_rows, hipStream_t s) {
     const int total = B * M;
     launch_kernel<gather_max_kernel>("fc::gather_max_kernel", 0.0, 4.0 * total * ((double)k * c_out + 2.0 * c_out + k), dim3((total + 3) / 4), dim3(256), 0, s, uv, lduv, c_out, idx, k,
                                      out, ldo, out_col0, M, m_stride_rows, total);
 }
+void launch_gather_max_counts(const float* uv, int lduv, int c_out, const int32_t* idx, int k, float* out, int ldo, int out_col0, int B, int M, int m_stride_rows,
+                              const SceneCounts& cnt, hipStream_t s) {
+    const int total = B * M;
+    launch_kernel<gather_max_counts_kernel>("fc::gather_max_counts_kernel", 0.0, 4.0 * total * ((double)k * c_out + 2.0 * c_out + k), dim3((total + 3) / 4), dim3(256), 0, s, uv, lduv,
+                                            c_out, idx, k, out, ldo, out_col0, M, m_stride_rows, total, cnt.counts, cnt.lo, cnt.hi);
+}
 
 // global embedder pooling: out[b] = [max_i t[b,i,:] | mean_i t[b,i,:]]  (models/pytorch_gcn.py:178-182)
-__global__ void pool_max_mean_kernel(const float* __restrict__ t, int ldt, int width, float* out, int ldo, int M, int m_stride) {
+// (M: the rows pooled; the counted kernel passes its scene's count: the same partial sums in the same order as for the scene alone)
+__device__ __forceinline__ void pool_max_mean_scene(const float* __restrict__ t, int ldt, int width, float* out, int ldo, int M, int m_stride) {
     const int b = blockIdx.y, c = blockIdx.x * 64 + (threadIdx.x & 63), part = threadIdx.x >> 6;   // 4 row-partitions per block
     __shared__ float smx[4][64], ssum[4][64];
     float mx = -INFINITY, sum = 0.f;
@@ -317,8 +343,34 @@ __global__ void pool_max_mean_kernel(const float* __restrict__ t, int ldt, int w
         out[(size_t)b * ldo + width + c] = ((ssum[0][l] + ssum[1][l]) + (ssum[2][l] + ssum[3][l])) / (float)M;
     }
 }
+__global__ void pool_max_mean_kernel(const float* __restrict__ t, int ldt, int width, float* out, int ldo, int M, int m_stride) {
+    pool_max_mean_scene(t, ldt, width, out, ldo, M, m_stride);
+}
+__global__ void pool_max_mean_counts_kernel(const float* __restrict__ t, int ldt, int width, float* out, int ldo, int m_stride, const int32_t* __restrict__ m_counts,
+                                            int count_min, int count_max) {
+    pool_max_mean_scene(t, ldt, width, out, ldo, scene_count(m_counts, blockIdx.y, count_min, count_max), m_stride);
+}
 void launch_pool_max_mean(const float* t, int ldt, int width, float* out, int ldo, int B, int M, int m_stride_rows, hipStream_t s) {
     launch_kernel<pool_max_mean_kernel>(nullptr, 0.0, 0.0, dim3((width + 63) / 64, B), dim3(256), 0, s, t, ldt, width, out, ldo, M, m_stride_rows);
+}
+void launch_pool_max_mean_counts(const float* t, int ldt, int width, float* out, int ldo, int B, int M, int m_stride_rows, const SceneCounts& cnt, hipStream_t s) {
+    (void)M;
+    launch_kernel<pool_max_mean_counts_kernel>(nullptr, 0.0, 0.0, dim3((width + 63) / 64, B), dim3(256), 0, s, t, ldt, width, out, ldo, m_stride_rows, cnt.counts, cnt.lo, cnt.hi);
+}
+
+// rows >= the scene's count of a dense [B][M][width] tensor := 0.0f (the per-point output of a counted embed call: callers allocate it
+// uninitialised and its width need not be a multiple of 4, so the 16-byte stores of zero_pad_rows_kernel do not fit).  blockIdx.y = scene.
+__global__ __launch_bounds__(256) void zero_tail_rows_kernel(float* __restrict__ out, int width, int M, const int32_t* __restrict__ m_counts, int count_min, int count_max) {
+    const int b = blockIdx.y;
+    const int Mb = scene_count(m_counts, b, count_min, count_max);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x + (long)Mb * width;       // element inside the scene, starting at its first pad row
+    if (i < (long)M * width) out[(size_t)b * M * width + i] = 0.0f;
+}
+void launch_zero_tail_rows(float* out, int width, int B, int M, const SceneCounts& cnt, hipStream_t s) {
+    const long n = (long)(M - cnt.lo) * width;                                    // the most pad a scene can have
+    if (B <= 0 || n <= 0) return;
+    launch_kernel<zero_tail_rows_kernel>("fc::zero_tail_rows_kernel", 0.0, 4.0 * (double)n * B, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, s, out, width, M, cnt.counts,
+                                         cnt.lo, cnt.hi);
 }
 
 }  // namespace fc

@@ -511,6 +511,24 @@ int fc_op_knn_warm_f32(const float* f, const int32_t* idx_warm, int32_t* idx, in
     FC_API_END
 }
 
+// the search with per-scene point counts (fcflow_embed_counts.h): idx_warm null = cold; rows >= a scene's count of idx are left as they are
+int fc_op_knn_counts_f32(const float* f, const int32_t* idx_warm, const int32_t* counts, int32_t count_min, int32_t count_max, int32_t* idx, int32_t B, int32_t M,
+                         int32_t C, int32_t k, void* stream) {
+    FC_API_BEGIN
+    using namespace fc;
+    if (!f || !idx || B < 1 || M < 1 || C < 1) throw Error(FC_ERR_INVALID, "fc_op_knn_counts_f32: bad argument");
+    if (!counts) throw Error(FC_ERR_INVALID, "fc_op_knn_counts_f32: null counts (the search without counts is fc_op_knn_f32)");
+    hipStream_t s = (hipStream_t)stream;
+    const int cp = round_up(C, 32);
+    const SceneCounts cnt{counts, count_min, count_max};
+    knn_check_counts(cp, C, M, k, cnt);
+    TmpBuf fp((size_t)B * M * cp * 4);
+    launch_pack_rows(f, C, C, fp.f(), cp, 0, cp, B * M, s);
+    launch_knn_counts(fp.f(), cp, C, idx, B, M, M, k, s, idx_warm, cnt);
+    FC_HIP(hipStreamSynchronize(s));
+    FC_API_END
+}
+
 int fc_op_fps_f32(const float* xyz, int32_t* idx, int32_t B, int32_t n, int32_t m, void* stream) {
     FC_API_BEGIN
     if (!xyz || !idx || B < 1 || n < 1 || m < 0) throw fc::Error(FC_ERR_INVALID, "fc_op_fps_f32: bad argument");

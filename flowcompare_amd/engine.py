@@ -24,8 +24,8 @@ EXPM = {"torch": 0, "original": 1}
 OP_ACTS = {"none": 0, "gelu": 1, "relu": 2, "elu": 3, "lrelu": 4}      # `act` of op_linear / op_mlp_hidden (FC_ACT_*)
 
 EXPORTS = list(abi.ENTRIES)          # every entry point include/fcflow.h declares
-# ... and those of the headers behind it (include/fcflow_attention_mass.h, fcflow_context_counts.h, fcflow_sparse_stage.h)
-EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES) + list(abi.COUNTS_ENTRIES) + list(abi.SPARSE_STAGE_ENTRIES)
+# ... and those of the headers behind it (include/fcflow_attention_mass.h, fcflow_context_counts.h, fcflow_sparse_stage.h, fcflow_embed_counts.h)
+EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES) + list(abi.COUNTS_ENTRIES) + list(abi.SPARSE_STAGE_ENTRIES) + list(abi.EMBED_COUNTS_ENTRIES)
 
 
 class FcTensor(ctypes.Structure):
@@ -209,8 +209,13 @@ def _context_counts(counts, B, M, device, name="context_counts"):
     """Per-scene context point counts of the *_counts_* entry points -> int32 device tensor [B], or None.  The kernels clamp a count into
     [1, M] and the library cannot check a device array without a synchronisation, so everything is checked here, before the library or an
     embedder is called: an integer tensor of shape [B] on the HIP device, every value in [1, M].  The one read-back of the call is here."""
-    if counts is None:
-        return None
+    return None if counts is None else _context_counts_range(counts, B, M, device, name)[0]
+
+
+def _context_counts_range(counts, B, M, device, name="context_counts", count_range=None):
+    """_context_counts for a caller that also needs the smallest and the largest count: -> (int32 device tensor [B], min, max).  count_range:
+    (min, max) from a caller that has read the counts back already (model_initialization._check_context_counts): the values are not read
+    again, type, device and shape are still checked."""
     if not torch.is_tensor(counts):
         raise RuntimeError(f"{name} must be None or an integer tensor of shape [B], got {type(counts).__name__}")
     if counts.is_floating_point() or counts.is_complex() or counts.dtype == torch.bool:
@@ -219,10 +224,13 @@ def _context_counts(counts, B, M, device, name="context_counts"):
         raise RuntimeError(f"{name} must live on a HIP device (there is no CPU path), got a tensor on {counts.device}")
     if tuple(counts.shape) != (B,):
         raise RuntimeError(f"{name} must have shape [B] with B = {B} (one count per scene), got {tuple(counts.shape)}")
-    lo, hi = (int(v) for v in torch.stack((counts.min(), counts.max())).tolist())
-    if lo < 1 or hi > M:
+    if count_range is not None:
+        lo, hi = int(count_range[0]), int(count_range[1])
+    else:
+        lo, hi = (int(v) for v in torch.stack((counts.min(), counts.max())).tolist())
+    if lo < 1 or hi > M or lo > hi:
         raise RuntimeError(f"{name} out of range: count {lo if lo < 1 else hi} is not in [1, {M}] (the padded context has {M} rows per scene)")
-    return counts.detach().to(device=device, dtype=torch.int32).contiguous()
+    return counts.detach().to(device=device, dtype=torch.int32).contiguous(), lo, hi
 
 
 class _Workspace:
@@ -424,26 +432,44 @@ class FlowHandle(_Handle):
 class _EmbedderHandle(_Handle):
     """A context embedder's engine: embed(pts [B,M,C]) -> [B,M,out_dim], or [B,out_dim] for a global one."""
     is_global = False
+    counts_entry = None     # the embed entry with per-scene point counts, where the engine has one (DgcnnHandle)
 
     def __init__(self, abi_prefix, state_dict, version, device, *head):
         super().__init__("embedder", abi_prefix, version, device)
         self._create(state_dict, *head)
         self.out_dim = self._entry("out_dim")(self._h)
 
-    def embed(self, pts):
-        pts = _dev_f32(pts)
+    def embed(self, pts, counts=None, count_range=None, out=None):
+        """counts (integer GPU tensor [B], values in [1, M]; _context_counts checks it): scene b is pts[b, :counts[b]] and gets the bytes it gets
+        when embedded alone; rows >= counts[b] of a per-point result are exact zeros, whatever pts holds there (include/fcflow_embed_counts.h).
+        count_range: (min, max) of counts where the caller has read them back already -- without it they are read back here, once.
+        out: a float32 tensor of the result's shape to write into (every element is written)."""
+        if counts is not None and self.counts_entry is None:
+            raise RuntimeError(f"{type(self).__name__}.embed: this embedder has no path with per-scene point counts (only the DGCNN engine has one): "
+                               "embed clouds of different sizes in groups of equal count")
         B, M = pts.shape[0], pts.shape[1]
+        cnt = None
+        if counts is not None:
+            cnt, lo, hi = _context_counts_range(counts, B, M, self.device, "counts", count_range)
+        pts = _dev_f32(pts)
         with torch.cuda.device(self.device):
             ws = self._ws.query(self._entry("workspace_bytes"), self._h, B, M, device=self.device)
             shape = (B, self.out_dim) if self.is_global else (B, M, self.out_dim)
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-            self._entry("embed_f32")(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
-            _keep_if_deferred(pts, out, ws)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+                raise RuntimeError(f"embed: out must be a contiguous float32 GPU tensor of shape {shape}")
+            if cnt is None:
+                self._entry("embed_f32")(self._h, _ptr(pts), _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
+            else:
+                self._entry(self.counts_entry)(self._h, _ptr(pts), _ptr(cnt), lo, hi, _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
+            _keep_if_deferred(pts, cnt, out, ws)
         return out
 
 
 class DgcnnHandle(_EmbedderHandle):
     """fc_dgcnn wrapper: replaces models.DGCNNembedder / DGCNNembedderGlobal forward (reference models/pytorch_gcn.py:81-188)."""
+    counts_entry = "embed_counts_f32"
 
     def __init__(self, n_neighbors, is_global, state_dict, version, device):
         self.is_global = bool(is_global)
@@ -737,14 +763,31 @@ def op_attention_mass(q, k, scale, weights=None):
     return out
 
 
-def op_knn(f, k, warm=None, in_place=False):
+def op_knn(f, k, warm=None, in_place=False, counts=None):
     """k nearest neighbours in feature space [B, M, C] -> int32 [B, M, k] (unordered sets); `warm`: neighbour sets [B, M, k] of the same cloud from
     another feature space to start the search from (the result is the exact top-k either way).  in_place: the result overwrites the warm
-    sets' own buffer, as between the levels of the DGCNN engine (a copy of `warm`; the caller's tensor stays as it is)."""
-    f = _dev_f32(f)
+    sets' own buffer, as between the levels of the DGCNN engine (a copy of `warm`; the caller's tensor stays as it is).
+    counts (integer GPU tensor [B], values in [1, M]): scene b is searched over f[b, :counts[b]] alone (fc_op_knn_counts_f32); rows >= counts[b]
+    of the result hold -1, the value the buffer is handed in with: the library writes nothing there."""
     B, M, C = f.shape
+    if counts is not None:
+        counts = _context_counts_range(counts, B, M, f.device, "counts")
+    f = _dev_f32(f)
     if in_place and warm is None:
         raise RuntimeError("op_knn: in_place needs warm sets")
+    if counts is not None:
+        cnt, lo, hi = counts
+        with torch.cuda.device(f.device):
+            idx = torch.full((B, M, k), -1, dtype=torch.int32, device=f.device)
+            if warm is not None:
+                if tuple(warm.shape) != (B, M, k):
+                    raise RuntimeError(f"op_knn: warm sets have shape {tuple(warm.shape)}, expected {(B, M, k)}")
+                warm = warm.to(device=f.device, dtype=torch.int32).contiguous()
+                if in_place:                                                        # (the scenes' own rows of the warm sets, -1 behind them)
+                    real = torch.arange(M, device=f.device)[None, :] < cnt[:, None]
+                    idx = torch.where(real[:, :, None], warm, idx)
+            lib().fc_op_knn_counts_f32(_ptr(f), _ptr(None if warm is None else (idx if in_place else warm)), _ptr(cnt), lo, hi, _ptr(idx), B, M, C, k, _stream())
+        return idx
     with torch.cuda.device(f.device):
         if warm is None:
             idx = torch.empty(B, M, k, dtype=torch.int32, device=f.device)

@@ -206,11 +206,12 @@ def _embed_batch(batch, models_dict, config, context_counts=None, what="inner_lo
     input_dim, the extra context repeated over config['sample_size'] points (einops.repeat 'b c -> b n c' in the reference), extract_0
     embedded and a global embedding repeated over the target points.
     context_counts ([B] integer GPU tensor): scene b's context cloud is extract_0[b, :count_b], the rows behind it are padding.  In eval mode
-    an embedder row depends on its own scene only, so the scenes are embedded in groups of equal count on the unpadded clouds -- groups in
-    ascending order of count, scene order kept inside a group -- with the embedder as it is (its own limits apply: DGCNN needs count >=
-    n_neighbors, PAConv count >= 256) and written into a zero-initialised [B, M, E]: a scene's embedding is bit for bit what the embedder
-    gives for that scene in a uniform batch of its group.  The cost is one embedder call per DISTINCT count; the flow, more than 95 % of
-    a step, still runs once on the padded batch."""
+    an embedder row depends on its own scene only.  A count-aware embedder (the DGCNN modules, `count_aware` True) takes the padded batch
+    and the counts in ONE call (its forward's context_counts): scene b gets the bytes it gets alone, pad rows of the
+    embedding are exact zeros.  Any other embedder (PAConv, or count_aware = False) embeds the scenes in groups of equal count on the
+    unpadded clouds -- groups in ascending order of count, scene order kept inside a group -- with the embedder as it is (PAConv needs
+    count >= 256) and written into a zero-initialised [B, M, E]: one embedder call per DISTINCT count.  DGCNN needs count >= n_neighbors
+    either way.  The flow, more than 95 % of a step, runs once on the padded batch."""
     extract_0, extract_1, extra_context = batch
     Din = config["input_dim"]
     if context_counts is not None:
@@ -219,6 +220,9 @@ def _embed_batch(batch, models_dict, config, context_counts=None, what="inner_lo
     if extra_context is not None:
         extra_context = extra_context[:, None, :].expand(-1, config["sample_size"], -1)
     if context_counts is not None:
+        embedder = models_dict["input_embedder"]
+        if getattr(embedder, "count_aware", False):
+            return extract_1, embedder(extract_0, context_counts=context_counts, count_range=(min(counts), max(counts))), extra_context
         emb = None
         for c in sorted(set(counts)):
             idx = torch.tensor([b for b, cb in enumerate(counts) if cb == c], dtype=torch.long, device=extract_0.device)
@@ -236,7 +240,8 @@ def _embed_batch(batch, models_dict, config, context_counts=None, what="inner_lo
 def inner_loop(batch, models_dict, config, eps=None, context_counts=None):
     """model_initialization.py:206-228.  `eps` (optional) pins the augmenter noise.
     context_counts (optional, eval mode): an integer GPU tensor [B] -- scene b's context is extract_0[b, :count_b] (pad_context_batch builds
-    such a batch from clouds of different sizes); embedded per group of equal count (_embed_batch), one flow call on the padded batch."""
+    such a batch from clouds of different sizes); a DGCNN embedder takes the padded batch and the counts in one call, any other one is called
+    per group of equal count (_embed_batch); one flow call on the padded batch."""
     if context_counts is not None:
         extract_1, emb, extra_context = _embed_batch(batch, models_dict, config, context_counts, "inner_loop")
         with torch.no_grad():
@@ -315,7 +320,7 @@ def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None
     (flow.noise_shapes) in CSR row order -- pad slots get zeros.  Returns flat [total] log-probs in CSR order (dense.offsets /
     dense.rows); pad slots are dropped.  Eval mode, under torch.no_grad(); the batch is taken as given under config['data_parallel'].
     A SceneStage staged with min_context (st.context_counts set) is honoured: every chunk of voxels is embedded through
-    _embed_batch's equal-count grouping, and every flow.log_prob gets its blocks' counts, gathered like the embeddings."""
+    _embed_batch with its counts (a DGCNN embedder: one call per chunk), and every flow.log_prob gets its blocks' counts, gathered like the embeddings."""
     if not (torch.is_tensor(st.extract_0) and st.extract_0.is_cuda and torch.is_tensor(dense.blocks) and dense.blocks.is_cuda):
         raise RuntimeError("dense_log_prob: expects a SceneStage and a DenseStage on the GPU (flowcompare_amd has no CPU fallback)")
     flow, embedder = models_dict["flow"], models_dict["input_embedder"]
@@ -386,8 +391,8 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
     min_context (an integer in [1, n_samples_context], eval mode) also evaluates voxels whose context box holds fewer
     than n_samples_context points: the validity mask becomes (c0_ctx >= min_context) & (c1_fin >= N) & (c0_fin >= N), both stagings are made
     with stage_scene's min_context (they share the context boxes, so the counts), and every inner_loop / dense_log_prob call passes its
-    voxels' counts as `context_counts`; the returned SceneStage carries them as `.context_counts`.  The embedder then runs once per DISTINCT
-    count of a chunk (_embed_batch), and its own minimum applies (DGCNN: n_neighbors points, PAConv: 256)."""
+    voxels' counts as `context_counts`; the returned SceneStage carries them as `.context_counts`.  A DGCNN embedder then runs once per chunk, any
+    other one once per DISTINCT count of a chunk (_embed_batch), and its own minimum applies (DGCNN: n_neighbors points, PAConv: 256)."""
     from . import change as change_ops
     from . import staging
     fin = config.get("final_voxel_size") if final_voxel_size is None else final_voxel_size

@@ -445,9 +445,22 @@ class _DGCNNBase(nn.Module):
         return _repacked(self, lambda key: _engine.DgcnnHandle(self.n_neighbors, self.is_global, self.state_dict(), key,
                                                                next(self.parameters()).device))
 
-    def forward(self, x):
+    # Whether callers with a padded batch and per-scene point counts (model_initialization._embed_batch) hand both to ONE forward call
+    # (forward's context_counts); False restores the grouping by equal count, one uniform call per distinct count.
+    count_aware = True
+
+    def forward(self, x, context_counts=None, count_range=None):
         """x [B,M,6] -> [B,M,E] (per-point) or [B,E] (global).  In train() mode: the differentiable HIP path with BatchNorm batch
-        statistics (train_embed.py); in eval() mode the fused inference engine (running statistics)."""
+        statistics (train_embed.py); in eval() mode the fused inference engine (running statistics).
+        context_counts (eval mode only; integer GPU tensor [B], values in [n_neighbors, M]): scene b is x[b, :count_b] and gets bit for bit
+        the embedding it gets when passed alone; rows >= count_b of a per-point result are exact zeros, whatever x holds there
+        (fc_dgcnn_embed_counts_f32).  count_range: (min, max) of the counts from a caller that has read them back already.  No autograd."""
+        if context_counts is not None:
+            if self.training:
+                raise RuntimeError("DGCNN forward: context_counts is eval-mode only (the training path has no per-scene context point counts): "
+                                   "initialize_flow(mode='test') or .eval() on the flow and the embedder")
+            with torch.no_grad():
+                return self._engine().embed(x, counts=context_counts, count_range=count_range)
         if self.training:                                  # (also under no_grad: train-mode BatchNorm normalises with batch statistics)
             from . import train_embed
             return train_embed.dgcnn_embed(self, x)

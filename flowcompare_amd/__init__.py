@@ -6,7 +6,7 @@ the HIP library is missing.
 """
 from .config import config_loader, named_config  # noqa: F401
 from .model_initialization import initialize_flow, inner_loop, make_sample, save_flow, load_flow, attention_weights, scene_change, dense_log_prob  # noqa: F401
-from .model_initialization import attention_mass, scene_context_attribution, pad_context_batch  # noqa: F401
+from .model_initialization import attention_mass, scene_context_attribution, pad_context_batch, pad_target_batch  # noqa: F401
 
 __all__ = ["config_loader", "named_config", "initialize_flow", "inner_loop", "make_sample", "save_flow", "load_flow", "attention_weights", "scene_change", "dense_log_prob",
-           "attention_mass", "scene_context_attribution", "pad_context_batch"]
+           "attention_mass", "scene_context_attribution", "pad_context_batch", "pad_target_batch"]

@@ -15,6 +15,7 @@
 #include "../../include/fcflow_context_counts.h"
 #include "../../include/fcflow_sparse_stage.h"
 #include "../../include/fcflow_embed_counts.h"
+#include "../../include/fcflow_sparse_target.h"
 #include "knobs.h"
 
 namespace fc {
@@ -331,6 +332,11 @@ void launch_change_map(float* lp10, int N, float* lp00, int N0, float* out, int 
                        float* stats4, int* status, hipStream_t s);
 void launch_change_map_ragged(float* lp10, const int64_t* offsets, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff,
                               int use_cutoff, float* stats4, int* status, hipStream_t s);
+// a length per row on both sides: counts_0 null = every baseline row holds N0 values
+void launch_change_map_counts(float* lp10, int N, const int32_t* counts_1, float* lp00, int N0, const int32_t* counts_0, float* out, int B, float multiple,
+                              float hard_cutoff, int use_cutoff, float* stats4, int* status, hipStream_t s);
+void launch_change_map_ragged_counts(float* lp10, const int64_t* offsets, float* lp00, int N0, const int32_t* counts_0, float* out, int B, float multiple,
+                                     float hard_cutoff, int use_cutoff, float* stats4, int* status, hipStream_t s);
 // ---- attention (attention.hip / attention_weights.hip): one call = a query, a key/value source and a problem
 // un-normalised q of the LayerNorm -> q fold: the attention kernel finishes it (rstd from the per-row sums of squares, bias) on load
 struct AttnLnq { const float* sumsq; int slots; size_t pitch; float inv_width; const float* bias; };

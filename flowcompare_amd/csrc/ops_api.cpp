@@ -598,6 +598,36 @@ int fc_change_map_ragged_f32(float* lp10, const int64_t* offsets, float* lp00, i
     FC_API_END
 }
 
+/* include/fcflow_sparse_target.h */
+int fc_change_map_counts_f32(float* lp10, int32_t N, const int32_t* counts_1, float* lp00, int32_t N0, const int32_t* counts_0, float* out, int32_t B,
+                             float multiple, float hard_cutoff, int32_t use_cutoff, int32_t* invalid, void* stream) {
+    FC_API_BEGIN
+    if (!lp10 || !counts_1 || !lp00 || !out || !invalid) throw fc::Error(FC_ERR_INVALID, "fc_change_map_counts_f32: null pointer");
+    fc::TmpBuf tmp(4 * sizeof(float) + sizeof(int));
+    int* status = (int*)(tmp.f() + 4);
+    fc::launch_change_map_counts(lp10, N, counts_1, lp00, N0, counts_0, out, B, multiple, hard_cutoff, use_cutoff, tmp.f(), status, (hipStream_t)stream);
+    int h = 0;
+    FC_HIP(hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    FC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    *invalid = h & 5;                                            /* bit 0: a result is not finite; bit 2: a baseline row shorter than 2 */
+    FC_API_END
+}
+
+int fc_change_map_ragged_counts_f32(float* lp10, const int64_t* offsets, float* lp00, int32_t N0, const int32_t* counts_0, float* out, int32_t B,
+                                    float multiple, float hard_cutoff, int32_t use_cutoff, int32_t* invalid, void* stream) {
+    FC_API_BEGIN
+    if (!lp10 || !offsets || !lp00 || !out || !invalid) throw fc::Error(FC_ERR_INVALID, "fc_change_map_ragged_counts_f32: null pointer");
+    fc::TmpBuf tmp(4 * sizeof(float) + sizeof(int));
+    int* status = (int*)(tmp.f() + 4);
+    fc::launch_change_map_ragged_counts(lp10, offsets, lp00, N0, counts_0, out, B, multiple, hard_cutoff, use_cutoff, tmp.f(), status, (hipStream_t)stream);
+    int h = 0;
+    FC_HIP(hipMemcpyAsync(&h, status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    FC_HIP(hipStreamSynchronize((hipStream_t)stream));
+    if (h & 2) throw fc::Error(FC_ERR_INVALID, "fc_change_map_ragged_counts_f32: offsets are not an ascending prefix sum of row counts below 2^31");
+    *invalid = h & 5;
+    FC_API_END
+}
+
 int fc_op_expm_action_f32(const float* params, int32_t ldp, const float* x2, int32_t ldx, const float* scal4, float* y2, int32_t ldy, float* ldj,
                           float* info, int32_t rows, int32_t d2, int32_t inverse, void* stream) {
     FC_API_BEGIN

@@ -288,13 +288,19 @@ void launch_fps_ragged(const float* cloud, int ld, int C, long P, const int64_t*
 // the lists -- no gathered intermediate -- and normalised with co_unit_sphere_kernel's operations in that kernel's order (staging.hip: strided
 // sums over the joint index, block_sum / block_max of block_reduce.h, subtract then divide), so the result is bit for bit what that kernel gives
 // for the pair (cloud_0[index_0[k, :c]], cloud_1[index_1[k]]).  Rows c .. M-1 of out_0[k] are written as 0.0f: the outputs need no initialisation.
-__global__ __launch_bounds__(1024) void stage_pairs_counts_kernel(const float* __restrict__ cloud_0, int P0, const float* __restrict__ cloud_1, int P1, int ld,
-                                                                  const int64_t* __restrict__ index_0, const int64_t* __restrict__ index_1,
-                                                                  const int32_t* __restrict__ counts_0, int M, int N, float* __restrict__ o0,
-                                                                  float* __restrict__ o1, float* __restrict__ inverse) {
-    __shared__ float red[16];
+// stage_pair_body is one pair.  TARGET_COUNTS = false is the entry above as it was (counts_1 unused, every one of the N target rows real);
+// TARGET_COUNTS = true gives the target its own count n = clamp(counts_1[k], 1, N) -- the -1 behind it in index_1[k] is
+// never read, rows n .. N-1 of out_1[k] are written as 0.0f -- and lets counts_0 be null (every context row real).  The flag is a template
+// parameter, so the first instantiation holds the statements it always held, in their order.
+template <bool TARGET_COUNTS>
+__device__ __forceinline__ void stage_pair_body(const float* __restrict__ cloud_0, int P0, const float* __restrict__ cloud_1, int P1, int ld,
+                                                const int64_t* __restrict__ index_0, const int64_t* __restrict__ index_1,
+                                                const int32_t* __restrict__ counts_0, const int32_t* __restrict__ counts_1, int M, int N,
+                                                float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ inverse, float* red) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int n0 = min(max(counts_0[b], 1), M), n = n0 + N;
+    const int n0 = TARGET_COUNTS && !counts_0 ? M : min(max(counts_0[b], 1), M);
+    const int n1 = TARGET_COUNTS ? min(max(counts_1[b], 1), N) : N;
+    const int n = n0 + n1;
     const int64_t* i0 = index_0 + (size_t)b * M;
     const int64_t* i1 = index_1 + (size_t)b * N;
     auto row = [&](int k) {                                    // clamped: a bad list cannot read outside the clouds
@@ -315,25 +321,53 @@ __global__ __launch_bounds__(1024) void stage_pairs_counts_kernel(const float* _
     }
     const float far = block_max(far2, red);
     float* w0 = o0 + (size_t)b * M * ld;
+    float* w1 = o1 + (size_t)b * N * ld;
     for (int k = tid; k < n; k += 1024) {
         const float* r = row(k);
-        float* w = k < n0 ? w0 + (size_t)k * ld : o1 + ((size_t)b * N + (k - n0)) * ld;
+        float* w = k < n0 ? w0 + (size_t)k * ld : w1 + (size_t)(k - n0) * ld;
         w[0] = (r[0] - mx) / far; w[1] = (r[1] - my) / far; w[2] = (r[2] - mz) / far;
         for (int col = 3; col < ld; ++col) w[col] = r[col];
     }
     for (int e = n0 * ld + tid; e < M * ld; e += 1024) w0[e] = 0.0f;
+    if (TARGET_COUNTS)
+        for (int e = n1 * ld + tid; e < N * ld; e += 1024) w1[e] = 0.0f;
     if (tid == 0) { inverse[4 * b] = far; inverse[4 * b + 1] = mx; inverse[4 * b + 2] = my; inverse[4 * b + 3] = mz; }
 }
 
+__global__ __launch_bounds__(1024) void stage_pairs_counts_kernel(const float* __restrict__ cloud_0, int P0, const float* __restrict__ cloud_1, int P1, int ld,
+                                                                  const int64_t* __restrict__ index_0, const int64_t* __restrict__ index_1,
+                                                                  const int32_t* __restrict__ counts_0, int M, int N, float* __restrict__ o0,
+                                                                  float* __restrict__ o1, float* __restrict__ inverse) {
+    __shared__ float red[16];
+    stage_pair_body<false>(cloud_0, P0, cloud_1, P1, ld, index_0, index_1, counts_0, nullptr, M, N, o0, o1, inverse, red);
+}
+
+// A count on both sides: pair k = (cloud_0[index_0[k, :c_k]], cloud_1[index_1[k, :n_k]]), counts_0 null = every c_k is M.
+__global__ __launch_bounds__(1024) void stage_pairs_counts2_kernel(const float* __restrict__ cloud_0, int P0, const float* __restrict__ cloud_1, int P1, int ld,
+                                                                   const int64_t* __restrict__ index_0, const int64_t* __restrict__ index_1,
+                                                                   const int32_t* __restrict__ counts_0, const int32_t* __restrict__ counts_1, int M, int N,
+                                                                   float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ inverse) {
+    __shared__ float red[16];
+    stage_pair_body<true>(cloud_0, P0, cloud_1, P1, ld, index_0, index_1, counts_0, counts_1, M, N, o0, o1, inverse, red);
+}
+
+// counts_1 null: stage_pairs_counts_kernel (counts_0 required, N >= 0); otherwise stage_pairs_counts2_kernel (counts_0 may be null, N >= 1).
 void launch_stage_pairs_counts(const float* cloud_0, long P0, const float* cloud_1, long P1, int ld, const int64_t* index_0, const int64_t* index_1,
-                               const int32_t* counts_0, int n_pairs, int M, int N, float* out_0, float* out_1, float* inverse, hipStream_t s) {
+                               const int32_t* counts_0, const int32_t* counts_1, int n_pairs, int M, int N, float* out_0, float* out_1, float* inverse,
+                               hipStream_t s) {
     if (n_pairs <= 0) return;
-    if (!cloud_0 || !cloud_1 || !index_0 || !index_1 || !counts_0 || !out_0 || !out_1 || !inverse) throw Error(FC_ERR_INVALID, "stage pairs: null pointer");
+    if (!cloud_0 || !cloud_1 || !index_0 || !index_1 || (!counts_0 && !counts_1) || !out_0 || !out_1 || !inverse) throw Error(FC_ERR_INVALID, "stage pairs: null pointer");
     if (ld < 3 || ld > 8) throw Error(FC_ERR_UNSUPPORTED, "stage pairs: 3..8 columns supported (xyz first)");
     if (P0 < 1 || P0 > 0x7fffffffL || P1 < 1 || P1 > 0x7fffffffL) throw Error(FC_ERR_INVALID, "stage pairs: bad cloud size");
-    if (M < 1 || N < 0 || (long)M * ld > 0x7fffffffL || (long)M + N > 0x7fffffffL) throw Error(FC_ERR_INVALID, "stage pairs: bad sample counts");
-    launch_kernel<stage_pairs_counts_kernel>("fc::stage_pairs_counts_kernel", 0.0, 4.0 * n_pairs * ((double)(M + N) * (2.0 * ld + 2.0)), dim3(n_pairs), dim3(1024), 0, s,
-                                             cloud_0, (int)P0, cloud_1, (int)P1, ld, index_0, index_1, counts_0, M, N, out_0, out_1, inverse);
+    if (M < 1 || N < (counts_1 ? 1 : 0) || (long)M * ld > 0x7fffffffL || (long)N * ld > 0x7fffffffL || (long)M + N > 0x7fffffffL)
+        throw Error(FC_ERR_INVALID, "stage pairs: bad sample counts");
+    const double bytes = 4.0 * n_pairs * ((double)(M + N) * (2.0 * ld + 2.0));
+    if (!counts_1)
+        launch_kernel<stage_pairs_counts_kernel>("fc::stage_pairs_counts_kernel", 0.0, bytes, dim3(n_pairs), dim3(1024), 0, s,
+                                                 cloud_0, (int)P0, cloud_1, (int)P1, ld, index_0, index_1, counts_0, M, N, out_0, out_1, inverse);
+    else
+        launch_kernel<stage_pairs_counts2_kernel>("fc::stage_pairs_counts2_kernel", 0.0, bytes, dim3(n_pairs), dim3(1024), 0, s,
+                                                  cloud_0, (int)P0, cloud_1, (int)P1, ld, index_0, index_1, counts_0, counts_1, M, N, out_0, out_1, inverse);
 }
 
 // ---------------------------------------------------------------- dense blocks: ALL members of the staged voxels
@@ -431,7 +465,20 @@ int fc_stage_pairs_counts_f32(const float* cloud_0, int64_t P0, const float* clo
                               float* inverse, void* stream) {
     FC_API_BEGIN
     if (n_pairs < 0) throw fc::Error(FC_ERR_INVALID, "fc_stage_pairs_counts_f32: bad argument");
-    fc::launch_stage_pairs_counts(cloud_0, (long)P0, cloud_1, (long)P1, ld, index_0, index_1, counts_0, n_pairs, M, N, out_0, out_1, inverse,
+    if (n_pairs > 0 && !counts_0) throw fc::Error(FC_ERR_INVALID, "stage pairs: null pointer");
+    fc::launch_stage_pairs_counts(cloud_0, (long)P0, cloud_1, (long)P1, ld, index_0, index_1, counts_0, nullptr, n_pairs, M, N, out_0, out_1, inverse,
+                                  (hipStream_t)stream);
+    FC_API_END
+}
+
+/* include/fcflow_sparse_target.h */
+int fc_stage_pairs_counts2_f32(const float* cloud_0, int64_t P0, const float* cloud_1, int64_t P1, int32_t ld, const int64_t* index_0,
+                               const int64_t* index_1, const int32_t* counts_0, const int32_t* counts_1, int32_t n_pairs, int32_t M, int32_t N,
+                               float* out_0, float* out_1, float* inverse, void* stream) {
+    FC_API_BEGIN
+    if (n_pairs < 0) throw fc::Error(FC_ERR_INVALID, "fc_stage_pairs_counts2_f32: bad argument");
+    if (n_pairs > 0 && !counts_1) throw fc::Error(FC_ERR_INVALID, "stage pairs: null pointer");
+    fc::launch_stage_pairs_counts(cloud_0, (long)P0, cloud_1, (long)P1, ld, index_0, index_1, counts_0, counts_1, n_pairs, M, N, out_0, out_1, inverse,
                                   (hipStream_t)stream);
     FC_API_END
 }

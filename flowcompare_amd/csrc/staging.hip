@@ -221,6 +221,69 @@ __global__ __launch_bounds__(256) void inf_stats_devn_kernel(const float* __rest
     if (__syncthreads_or(inf) && threadIdx.x == 0) stats[1] = 1.0f;
 }
 
+// ---- a length per row on both sides.  Row b of a padded [B, ld] tensor holds n_b = clamp(counts[b], 1, ld) real
+// values; the slots behind them are padding that is neither read nor written.  status bit 4: a baseline row with fewer than the two values
+// the unbiased std divides by (no hard cutoff).
+__device__ __forceinline__ int row_count(const int32_t* __restrict__ counts, int b, int ld) { return counts ? min(max(counts[b], 1), ld) : ld; }
+
+// inf_stats_kernel over the real slots only: a pad slot is neither seen as an inf nor feeds the minimum.  Workgroups stride over the rows.
+__global__ __launch_bounds__(256) void inf_stats_counts_kernel(const float* __restrict__ t, int ld, const int32_t* __restrict__ counts, int B,
+                                                               float* __restrict__ stats) {
+    __shared__ float red[4];
+    float mn = INFINITY;
+    bool inf = false;
+    for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        const float* r = t + (size_t)b * ld;
+        const int n = row_count(counts, b, ld);
+        for (int k = threadIdx.x; k < n; k += 256) {
+            const float v = r[k];
+            if (isinf(v)) inf = true; else mn = fminf(mn, v);
+        }
+    }
+    const float bm = block_min(mn, red);
+    if (threadIdx.x == 0 && bm < INFINITY) atomic_min_float(stats, bm);
+    if (__syncthreads_or(inf) && threadIdx.x == 0) stats[1] = 1.0f;
+}
+
+// false (and status bit 4, nothing read or written) when the baseline row cannot give a threshold
+__device__ __forceinline__ bool baseline_ok(int n0, int use_cutoff, int* __restrict__ status) {
+    if (use_cutoff || n0 >= 2) return true;
+    if (threadIdx.x == 0) atomicOr(status, 4);
+    return false;
+}
+
+// Padded layout: scene b runs change_map_rows on its first n1_b values of lp10 [B, N] and its first n0_b of lp00 [B, N0]; slots >= n1_b of
+// out[b] are NaN (not evaluated, as in the scene maps).
+__global__ __launch_bounds__(256) void change_map_counts_kernel(float* __restrict__ lp10, int N, const int32_t* __restrict__ counts_1, float* __restrict__ lp00,
+                                                                int N0, const int32_t* __restrict__ counts_0, float* __restrict__ out,
+                                                                const float* __restrict__ st10, const float* __restrict__ st00, float multiple,
+                                                                float hard_cutoff, int use_cutoff, int* __restrict__ status) {
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const int n1 = row_count(counts_1, b, N), n0 = row_count(counts_0, b, N0);
+    float* o = out + (size_t)b * N;
+    const bool ok = baseline_ok(n0, use_cutoff, status);             // uniform over the workgroup
+    for (int k = (ok ? n1 : 0) + threadIdx.x; k < N; k += 256) o[k] = NAN;
+    if (ok) change_map_rows(lp10 + (size_t)b * N, n1, lp00 + (size_t)b * N0, n0, o, st10, st00, multiple, hard_cutoff, use_cutoff, status, red);
+}
+
+// change_map_ragged_kernel with a baseline length per voxel
+__global__ __launch_bounds__(256) void change_map_ragged_counts_kernel(float* __restrict__ lp10, const int64_t* __restrict__ offsets, float* __restrict__ lp00,
+                                                                       int N0, const int32_t* __restrict__ counts_0, float* __restrict__ out,
+                                                                       const float* __restrict__ st10, const float* __restrict__ st00, float multiple,
+                                                                       float hard_cutoff, int use_cutoff, int* __restrict__ status) {
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const int64_t off = offsets[b], n = offsets[b + 1] - off;
+    if (n < 0 || n > 0x7fffffff) { if (threadIdx.x == 0) atomicOr(status, 2); return; }        // not a prefix sum; uniform over the workgroup
+    const int n0 = row_count(counts_0, b, N0);
+    if (n > 0 && !baseline_ok(n0, use_cutoff, status)) {             // a voxel without rows contributes nothing: its baseline is not asked for
+        for (int64_t k = threadIdx.x; k < n; k += 256) out[off + k] = NAN;
+        return;
+    }
+    change_map_rows(lp10 + off, (int)n, lp00 + (size_t)b * N0, n0, out + off, st10, st00, multiple, hard_cutoff, use_cutoff, status, red);
+}
+
 __global__ __launch_bounds__(256) void clamp_infs_kernel(float* __restrict__ t, long n, const float* __restrict__ stats) {
     if (stats[1] == 0.f) return;
     const float m = stats[0];
@@ -258,6 +321,29 @@ void launch_change_map_ragged(float* lp10, const int64_t* offsets, float* lp00, 
     launch_kernel<inf_stats_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)std::min<long>((n0 + 255) / 256, 1024)), dim3(256), 0, s, lp00, n0, stats4 + 2);
     launch_kernel<change_map_ragged_kernel>(nullptr, 0.0, 0.0, dim3(B), dim3(256), 0, s, lp10, offsets, lp00, N0, out, stats4, stats4 + 2, multiple, hard_cutoff, use_cutoff,
                                             status);
+}
+
+void launch_change_map_counts(float* lp10, int N, const int32_t* counts_1, float* lp00, int N0, const int32_t* counts_0, float* out, int B, float multiple,
+                              float hard_cutoff, int use_cutoff, float* stats4, int* status, hipStream_t s) {
+    if (B <= 0 || N <= 0 || N0 <= 0) throw Error(FC_ERR_INVALID, "change map: empty input");
+    launch_kernel<change_init_kernel>(nullptr, 0.0, 0.0, dim3(1), dim3(64), 0, s, stats4, status);
+    ProfScope ps("fc::change_map_counts_kernel", 0.0, 4.0 * B * (3.0 * N + 3.0 * N0), s);     // the padded size: the counts stay on the device
+    const unsigned g = (unsigned)std::min(B, 1024);
+    launch_kernel<inf_stats_counts_kernel>(nullptr, 0.0, 0.0, dim3(g), dim3(256), 0, s, lp10, N, counts_1, B, stats4);
+    launch_kernel<inf_stats_counts_kernel>(nullptr, 0.0, 0.0, dim3(g), dim3(256), 0, s, lp00, N0, counts_0, B, stats4 + 2);
+    launch_kernel<change_map_counts_kernel>(nullptr, 0.0, 0.0, dim3(B), dim3(256), 0, s, lp10, N, counts_1, lp00, N0, counts_0, out, stats4, stats4 + 2, multiple,
+                                            hard_cutoff, use_cutoff, status);
+}
+
+void launch_change_map_ragged_counts(float* lp10, const int64_t* offsets, float* lp00, int N0, const int32_t* counts_0, float* out, int B, float multiple,
+                                     float hard_cutoff, int use_cutoff, float* stats4, int* status, hipStream_t s) {
+    if (B <= 0 || N0 <= 0) throw Error(FC_ERR_INVALID, "ragged change map: empty input");
+    launch_kernel<change_init_kernel>(nullptr, 0.0, 0.0, dim3(1), dim3(64), 0, s, stats4, status);
+    ProfScope ps("fc::change_map_ragged_counts_kernel", 0.0, 0.0, s);
+    launch_kernel<inf_stats_devn_kernel>(nullptr, 0.0, 0.0, dim3(1024), dim3(256), 0, s, lp10, offsets + B, stats4);
+    launch_kernel<inf_stats_counts_kernel>(nullptr, 0.0, 0.0, dim3((unsigned)std::min(B, 1024)), dim3(256), 0, s, lp00, N0, counts_0, B, stats4 + 2);
+    launch_kernel<change_map_ragged_counts_kernel>(nullptr, 0.0, 0.0, dim3(B), dim3(256), 0, s, lp10, offsets, lp00, N0, counts_0, out, stats4, stats4 + 2, multiple,
+                                                   hard_cutoff, use_cutoff, status);
 }
 
 }  // namespace fc

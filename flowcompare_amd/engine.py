@@ -24,8 +24,10 @@ EXPM = {"torch": 0, "original": 1}
 OP_ACTS = {"none": 0, "gelu": 1, "relu": 2, "elu": 3, "lrelu": 4}      # `act` of op_linear / op_mlp_hidden (FC_ACT_*)
 
 EXPORTS = list(abi.ENTRIES)          # every entry point include/fcflow.h declares
-# ... and those of the headers behind it (include/fcflow_attention_mass.h, fcflow_context_counts.h, fcflow_sparse_stage.h, fcflow_embed_counts.h)
-EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES) + list(abi.COUNTS_ENTRIES) + list(abi.SPARSE_STAGE_ENTRIES) + list(abi.EMBED_COUNTS_ENTRIES)
+# ... and those of the headers behind it (include/fcflow_attention_mass.h, fcflow_context_counts.h, fcflow_sparse_stage.h, fcflow_embed_counts.h,
+# fcflow_sparse_target.h)
+EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES) + list(abi.COUNTS_ENTRIES) + list(abi.SPARSE_STAGE_ENTRIES) + list(abi.EMBED_COUNTS_ENTRIES) + \
+    list(abi.SPARSE_TARGET_ENTRIES)
 
 
 class FcTensor(ctypes.Structure):
@@ -212,7 +214,7 @@ def _context_counts(counts, B, M, device, name="context_counts"):
     return None if counts is None else _context_counts_range(counts, B, M, device, name)[0]
 
 
-def _context_counts_range(counts, B, M, device, name="context_counts", count_range=None):
+def _context_counts_range(counts, B, M, device, name="context_counts", count_range=None, side="context"):
     """_context_counts for a caller that also needs the smallest and the largest count: -> (int32 device tensor [B], min, max).  count_range:
     (min, max) from a caller that has read the counts back already (model_initialization._check_context_counts): the values are not read
     again, type, device and shape are still checked."""
@@ -229,7 +231,7 @@ def _context_counts_range(counts, B, M, device, name="context_counts", count_ran
     else:
         lo, hi = (int(v) for v in torch.stack((counts.min(), counts.max())).tolist())
     if lo < 1 or hi > M or lo > hi:
-        raise RuntimeError(f"{name} out of range: count {lo if lo < 1 else hi} is not in [1, {M}] (the padded context has {M} rows per scene)")
+        raise RuntimeError(f"{name} out of range: count {lo if lo < 1 else hi} is not in [1, {M}] (the padded {side} has {M} rows per scene)")
     return counts.detach().to(device=device, dtype=torch.int32).contiguous(), lo, hi
 
 
@@ -582,6 +584,28 @@ def stage_pairs_counts(cloud_0, cloud_1, index_0, index_1, counts_0):
     return o0, o1, inv
 
 
+def stage_pairs_counts2(cloud_0, cloud_1, index_0, index_1, counts_0, counts_1):
+    """stage_pairs_counts with a count on both sides (fc_stage_pairs_counts2_f32, include/fcflow_sparse_target.h): pair k =
+    (cloud_0[index_0[k, :counts_0[k]]], cloud_1[index_1[k, :counts_1[k]]]), counts_0 [K'] int32 or None (every context row real), counts_1 [K']
+    int32; rows of out_0[k] / out_1[k] behind their counts are exact zeros."""
+    for t, dt, nd in ((cloud_0, torch.float32, 2), (cloud_1, torch.float32, 2), (index_0, torch.int64, 2), (index_1, torch.int64, 2),
+                      (counts_1, torch.int32, 1)) + (() if counts_0 is None else ((counts_0, torch.int32, 1),)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == nd):
+            raise RuntimeError("stage_pairs_counts2: expects contiguous GPU tensors: float32 clouds [P, C], int64 lists [K', M] / [K', N], int32 counts [K'] "
+                               "(flowcompare_amd has no CPU fallback)")
+    (K1, M), N, C = index_0.shape, index_1.shape[1], cloud_0.shape[1]
+    if index_1.shape[0] != K1 or counts_1.numel() != K1 or (counts_0 is not None and counts_0.numel() != K1) or cloud_1.shape[1] != C:
+        raise RuntimeError(f"stage_pairs_counts2: lists of shape {tuple(index_0.shape)} / {tuple(index_1.shape)}, {counts_1.numel()} target counts and "
+                           f"clouds of {C} / {cloud_1.shape[1]} columns do not pair up")
+    o0 = torch.empty(K1, M, C, dtype=torch.float32, device=cloud_0.device)
+    o1 = torch.empty(K1, N, C, dtype=torch.float32, device=cloud_0.device)
+    inv = torch.empty(K1, 4, dtype=torch.float32, device=cloud_0.device)
+    with torch.cuda.device(cloud_0.device):
+        lib().fc_stage_pairs_counts2_f32(_ptr(cloud_0), cloud_0.shape[0], _ptr(cloud_1), cloud_1.shape[0], C, _ptr(index_0), _ptr(index_1),
+                                         _ptr(counts_0), _ptr(counts_1), K1, M, N, _ptr(o0), _ptr(o1), _ptr(inv), _stream())
+    return o0, o1, inv
+
+
 def stage_dense_blocks(cloud, offsets, rows, inverse, block_offsets, n_blocks, block, voxel_ids=None):
     """(blocks [n_blocks, block, C] fp32, index [n_blocks, block] int64, block_voxel [n_blocks] int32): all members of the listed voxels of
     a CSR list (offsets int64, rows int32) in blocks, normalised with inverse [n_voxels, 4] (fc_stage_dense_blocks_f32).  block_offsets
@@ -623,9 +647,58 @@ def change_map(lp10, lp00, multiple, hard_cutoff=None):
     return out, bool(bad.value)
 
 
-def change_map_ragged(lp10, offsets, lp00, multiple, hard_cutoff=None):
+def _row_counts(name, what, counts, B, device):
+    if not (torch.is_tensor(counts) and counts.is_cuda and counts.device == device and counts.dtype == torch.int32 and counts.is_contiguous()
+            and tuple(counts.shape) == (B,)):
+        raise RuntimeError(f"{name}: {what} must be a contiguous int32 GPU tensor [B] with B = {B}, one length per row")
+
+
+def _short_baseline(name, counts_0, N0, hard_cutoff, has_rows=None):
+    """Without hard_cutoff a baseline row needs two values: raises, naming the first scene whose row is shorter (of those with rows, for the ragged
+    form, where a voxel without rows contributes nothing).  Called BEFORE the launch, so that a refused call leaves the caller's tensors as they
+    were; status bit 4 of the kernels is the same rule on the device."""
+    if hard_cutoff is not None:
+        return
+    if counts_0 is None:
+        if N0 < 2:
+            raise RuntimeError(f"{name}: the baseline rows hold 1 value: without hard_cutoff the unbiased std of the baseline row needs two")
+        return
+    short = counts_0 < 2 if has_rows is None else (counts_0 < 2) & has_rows
+    where = torch.nonzero(short).flatten()[:1].tolist()              # the one read-back of the check
+    if where:
+        b = where[0]
+        raise RuntimeError(f"{name}: scene {b} has a baseline of {max(int(counts_0[b]), 1)} value(s): without hard_cutoff the threshold is mean - multiple * std "
+                       "of the baseline row, and the unbiased std needs two")
+
+
+def change_map_counts(lp10, counts_1, lp00, counts_0, multiple, hard_cutoff=None):
+    """fc_change_map_counts_f32 (include/fcflow_sparse_target.h): lp10 [B, N] with counts_1 [B] int32, lp00 [B, N0] with counts_0 [B] int32 or None
+    (all of N0), contiguous device tensors; real slots are clamped in place, pad slots are neither read nor written.  Returns (out [B, N] with NaN
+    behind every count, invalid flag); a baseline row of fewer than 2 values without hard_cutoff raises, naming the scene."""
+    for t in (lp10, lp00):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2):
+            raise RuntimeError("change_map_counts: expects contiguous float32 [B, N] tensors on the GPU (flowcompare_amd has no CPU fallback)")
+    B, N = lp10.shape
+    if lp00.shape[0] != B or B < 1 or N < 1 or lp00.shape[1] < 1:
+        raise RuntimeError("change_map_counts: batch sizes differ or a tensor is empty")
+    _row_counts("change_map_counts", "counts_1", counts_1, B, lp10.device)
+    if counts_0 is not None:
+        _row_counts("change_map_counts", "counts_0", counts_0, B, lp10.device)
+    _short_baseline("change_map_counts", counts_0, lp00.shape[1], hard_cutoff)
+    out = torch.empty_like(lp10)
+    bad = ctypes.c_int32(0)
+    with torch.cuda.device(lp10.device):
+        lib().fc_change_map_counts_f32(_ptr(lp10), N, _ptr(counts_1), _ptr(lp00), lp00.shape[1], _ptr(counts_0), _ptr(out), B, multiple,
+                                       0.0 if hard_cutoff is None else hard_cutoff, 0 if hard_cutoff is None else 1, ctypes.byref(bad), _stream())
+    if bad.value & 4:                                      # (not reached: refused above)
+        raise RuntimeError("change_map_counts: a baseline row holds fewer than two values")
+    return out, bool(bad.value & 1)
+
+
+def change_map_ragged(lp10, offsets, lp00, multiple, hard_cutoff=None, counts_0=None):
     """fc_change_map_ragged_f32: lp10 flat [offsets[-1]], offsets [B + 1] int64, lp00 [B, N0], contiguous device tensors (clamped in place);
-    returns (out flat, invalid flag)."""
+    returns (out flat, invalid flag).  counts_0 ([B] int32 on the device; fc_change_map_ragged_counts_f32): voxel k's baseline is lp00[k, :counts_0[k]],
+    the slots behind it are neither read nor written; a baseline of fewer than 2 values without hard_cutoff raises, naming the voxel."""
     for t, dt, nd in ((lp10, torch.float32, 1), (lp00, torch.float32, 2), (offsets, torch.int64, 1)):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == nd):
             raise RuntimeError("change_map_ragged: expects contiguous float32 lp10 [total] / lp00 [B, N0] and int64 offsets [B + 1] on the GPU "
@@ -633,12 +706,23 @@ def change_map_ragged(lp10, offsets, lp00, multiple, hard_cutoff=None):
     B = lp00.shape[0]
     if offsets.numel() != B + 1:
         raise RuntimeError("change_map_ragged: offsets must have one entry more than lp00 has rows")
+    if counts_0 is not None:
+        _row_counts("change_map_ragged", "counts_0", counts_0, B, lp10.device)
     if B < 1 or not bool((offsets[0] == 0) & (offsets[-1] == lp10.numel()) & (offsets[1:] >= offsets[:-1]).all()):
         raise RuntimeError("change_map_ragged: offsets must ascend from 0 to the length of lp10, one voxel at least")
     out = torch.empty_like(lp10)
     if lp10.numel() == 0:                                  # no voxel has a row: nothing to scale
         return out, False
     bad = ctypes.c_int32(0)
+    if counts_0 is not None:
+        _short_baseline("change_map_ragged", counts_0, lp00.shape[1], hard_cutoff, has_rows=offsets[1:] > offsets[:-1])
+        with torch.cuda.device(lp10.device):
+            lib().fc_change_map_ragged_counts_f32(_ptr(lp10), _ptr(offsets), _ptr(lp00), lp00.shape[1], _ptr(counts_0), _ptr(out), B, multiple,
+                                                  0.0 if hard_cutoff is None else hard_cutoff, 0 if hard_cutoff is None else 1, ctypes.byref(bad),
+                                                  _stream())
+        if bad.value & 4:                                  # (not reached: refused above)
+            raise RuntimeError("change_map_ragged: a baseline row holds fewer than two values")
+        return out, bool(bad.value & 1)
     with torch.cuda.device(lp10.device):
         lib().fc_change_map_ragged_f32(_ptr(lp10), _ptr(offsets), _ptr(lp00), lp00.shape[1], _ptr(out), B, multiple,
                                        0.0 if hard_cutoff is None else hard_cutoff, 0 if hard_cutoff is None else 1, ctypes.byref(bad), _stream())

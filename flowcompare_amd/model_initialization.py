@@ -181,6 +181,43 @@ def pad_context_batch(clouds):
     return extract_0, counts
 
 
+def pad_target_batch(clouds):
+    """Target clouds of different sizes -> the padded batch the `target_counts` argument of inner_loop takes: clouds = a list of [N_b, C] GPU
+    tensors (at least one point each, one C), returns (extract_1 [B, max N_b, C] fp32 with zeros behind every cloud, counts [B] int32 on the same
+    device).  inner_loop((extract_0, extract_1, extra), ..., target_counts=counts) then scores the points of clouds[b] in scene b."""
+    clouds = list(clouds)
+    if not clouds:
+        raise RuntimeError("pad_target_batch: no clouds given")
+    for i, c in enumerate(clouds):
+        if not (torch.is_tensor(c) and c.is_cuda):
+            raise RuntimeError(f"pad_target_batch: cloud {i} must be a tensor on a HIP device (there is no CPU path)")
+        if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] != clouds[0].shape[1] or c.device != clouds[0].device:
+            raise RuntimeError(f"pad_target_batch: cloud {i} has shape {tuple(c.shape)} on {c.device}: every cloud must be [N_b, C] with N_b >= 1, "
+                               f"C = {clouds[0].shape[1] if clouds[0].dim() == 2 else '?'} and on {clouds[0].device}")
+    counts = torch.tensor([c.shape[0] for c in clouds], dtype=torch.int32, device=clouds[0].device)
+    extract_1 = torch.zeros(len(clouds), max(c.shape[0] for c in clouds), clouds[0].shape[1], dtype=torch.float32, device=clouds[0].device)
+    for b, c in enumerate(clouds):
+        extract_1[b, :c.shape[0]] = c
+    return extract_1, counts
+
+
+def _check_target_counts(what, target_counts, batch, models_dict):
+    """What `target_counts` cannot be combined with, and the tensor itself, before an embedder or the library runs.  Returns the counts as an
+    int32 device tensor [B]."""
+    from . import engine as _engine
+    flow, embedder = models_dict["flow"], models_dict["input_embedder"]
+    if flow.training or embedder.training:
+        raise RuntimeError(f"{what}: target_counts is eval-mode only (train-mode statistics couple the rows of a batch, pad rows included): "
+                           "initialize_flow(mode='test') or .eval() on the flow and the embedder")
+    if models_dict.get("sharded"):
+        raise RuntimeError(f"{what}: target_counts is not supported with a sharded models_dict (config['data_parallel']): the scene split does not "
+                           "carry the counts -- give every rank its own scenes and counts through an unsharded models_dict")
+    extract_1 = batch[1]
+    if not (torch.is_tensor(extract_1) and extract_1.is_cuda):
+        raise RuntimeError("flowcompare_amd: tensors must live on a HIP device (there is no CPU path)")
+    return _engine._context_counts_range(target_counts, extract_1.shape[0], extract_1.shape[1], extract_1.device, "target_counts", side="target")[0]
+
+
 def _check_context_counts(what, context_counts, batch, models_dict, config):
     """What `context_counts` cannot be combined with, and the tensor itself (engine._context_counts), before an embedder or the library runs.
     Returns the counts as a Python list."""
@@ -237,11 +274,27 @@ def _embed_batch(batch, models_dict, config, context_counts=None, what="inner_lo
     return extract_1, emb, extra_context
 
 
-def inner_loop(batch, models_dict, config, eps=None, context_counts=None):
+def inner_loop(batch, models_dict, config, eps=None, context_counts=None, target_counts=None):
     """model_initialization.py:206-228.  `eps` (optional) pins the augmenter noise.
     context_counts (optional, eval mode): an integer GPU tensor [B] -- scene b's context is extract_0[b, :count_b] (pad_context_batch builds
     such a batch from clouds of different sizes); a DGCNN embedder takes the padded batch and the counts in one call, any other one is called
-    per group of equal count (_embed_batch); one flow call on the padded batch."""
+    per group of equal count (_embed_batch); one flow call on the padded batch.
+    target_counts (optional, eval mode, not with a sharded models_dict): an integer GPU tensor [B] with 1 <= n_b <= N --
+    scene b's target is extract_1[b, :n_b] (pad_target_batch builds such a batch).  In eval mode a target point's log-prob depends on that point,
+    its context and its own noise only, so the flow runs once on the padded batch: rows >= n_b of extract_1 are replaced by zeros first (whatever
+    the caller's pad rows hold, it does not reach the flow or its range flag), log_prob[b, n_b:] comes back NaN (not evaluated), and loss / bpd are
+    taken over the real slots only.  Goes with context_counts or without."""
+    if target_counts is not None:
+        counts_1 = _check_target_counts("inner_loop", target_counts, batch, models_dict)
+        extract_0, extract_1, extra = batch
+        real = torch.arange(extract_1.shape[1], device=extract_1.device)[None, :] < counts_1[:, None]
+        with torch.no_grad():
+            padded = (extract_0, torch.where(real[:, :, None], extract_1, extract_1.new_zeros(())), extra)
+            _, log_prob, _ = inner_loop(padded, models_dict, config, eps=eps, context_counts=context_counts)
+            loss = -log_prob[real].mean()
+            bpd = loss * math.log2(math.exp(1)) / config["input_dim"]
+            log_prob = torch.where(real, log_prob, log_prob.new_full((), float("nan")))
+        return loss, log_prob, bpd
     if context_counts is not None:
         extract_1, emb, extra_context = _embed_batch(batch, models_dict, config, context_counts, "inner_loop")
         with torch.no_grad():
@@ -310,6 +363,21 @@ def _scene_min_context(what, min_context, models_dict, config):
     return min_context
 
 
+def _scene_min_target(what, min_target, models_dict, config):
+    """min_target of the scene-level functions, checked before anything is staged: an integer in [2, sample_size], and eval mode, since every
+    inner_loop call will carry `target_counts`."""
+    from . import staging
+    min_target = staging._min_target(what, min_target, config["sample_size"], 2,
+                                     " (a voxel's threshold is mean - multiple * std of its (0 | 0) baseline, and the unbiased std needs two values)")
+    if min_target is not None and (models_dict["flow"].training or models_dict["input_embedder"].training):
+        raise RuntimeError(f"{what}: min_target is eval-mode only (it stages per-voxel target_counts, which the training path does not take): "
+                           "initialize_flow(mode='test') or .eval() on the flow and the embedder")
+    if min_target is not None and models_dict.get("sharded"):
+        raise RuntimeError(f"{what}: min_target is not supported with a sharded models_dict (config['data_parallel']): the scene split does not "
+                           "carry the counts")
+    return min_target
+
+
 def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None):
     """Log-probs of ALL members of the staged voxels against their voxel's staged context: st = the SceneStage (context st.extract_0,
     st.extra_context), dense = staging.stage_dense(...) of the same voxels.  In eval mode a target point's log-likelihood depends on
@@ -369,7 +437,7 @@ def dense_log_prob(st, dense, models_dict, config, blocks_per_batch=16, eps=None
 
 
 def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=None, multiple=5.4, hard_cutoff=None, voxels_per_batch=16,
-                 final_voxel_size=None, context_voxel_size=None, dense=False, block=None, min_context=None):
+                 final_voxel_size=None, context_voxel_size=None, dense=False, block=None, min_context=None, min_target=None):
     """test_flow.py:151-166 for a whole scene, one direction: the change of cloud_1 [P1, C] given cloud_0 [P0, C] at the voxel centres
     `centers` [K, 3].  Sample counts are config['sample_size'] / config['n_samples_context'] as the reference's loader takes them
     (test_flow.py:141-143); the box sizes default to the config's 'final_voxel_size' / 'context_voxel_size'.  Evaluated are the centres
@@ -392,7 +460,15 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
     than n_samples_context points: the validity mask becomes (c0_ctx >= min_context) & (c1_fin >= N) & (c0_fin >= N), both stagings are made
     with stage_scene's min_context (they share the context boxes, so the counts), and every inner_loop / dense_log_prob call passes its
     voxels' counts as `context_counts`; the returned SceneStage carries them as `.context_counts`.  A DGCNN embedder then runs once per chunk, any
-    other one once per DISTINCT count of a chunk (_embed_batch), and its own minimum applies (DGCNN: n_neighbors points, PAConv: 256)."""
+    other one once per DISTINCT count of a chunk (_embed_batch), and its own minimum applies (DGCNN: n_neighbors points, PAConv: 256).
+
+    min_target (an integer in [2, sample_size], eval mode) also evaluates voxels whose FINAL boxes hold fewer than
+    sample_size points -- where something was removed, appeared in a nearly empty place, or the scene ends: the validity mask becomes
+    (context rule) & (c1_fin >= min_target) & (c0_fin >= min_target), both stagings are made with stage_scene's min_target and carry their own
+    `target_counts` (the (1 | 0) target is cloud 1, the (0 | 0) target cloud 0).  Sampled mode: every inner_loop gets its staging's counts as
+    `target_counts`, log_prob_to_change_counts acts per chunk on the real slots, and the change is scattered through index_1 >= 0 only.  Dense mode:
+    a sparse voxel's members are all picked, so its single block is its sample; log_prob_to_change_ragged takes the (0 | 0) counts as base_counts.
+    2 is the lowest value because a voxel's threshold needs the unbiased std of its baseline.  Goes with min_context or without."""
     from . import change as change_ops
     from . import staging
     fin = config.get("final_voxel_size") if final_voxel_size is None else final_voxel_size
@@ -403,14 +479,17 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
         raise RuntimeError("scene_change: this config uses the extra z-value context and needs ground_height")
     N, M = config["sample_size"], config["n_samples_context"]
     min_context = _scene_min_context("scene_change", min_context, models_dict, config)
+    min_target = _scene_min_target("scene_change", min_target, models_dict, config)
     c0_ctx, c1_fin, c0_fin = (staging.voxel_counts(cloud_0, centers, ctx), staging.voxel_counts(cloud_1, centers, fin),
                               staging.voxel_counts(cloud_0, centers, fin))
-    both = torch.nonzero((c0_ctx >= (M if min_context is None else min_context)) & (c1_fin >= N) & (c0_fin >= N)).flatten()
+    n_min = N if min_target is None else min_target
+    both = torch.nonzero((c0_ctx >= (M if min_context is None else min_context)) & (c1_fin >= n_min) & (c0_fin >= n_min)).flatten()
     sel = centers[both].contiguous()
-    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height, min_context=min_context)
-    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height, min_context=min_context)
+    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height, min_context=min_context, min_target=min_target)
+    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height, min_context=min_context, min_target=min_target)
     assert st10.voxel.numel() == st00.voxel.numel() == both.numel()
     counts = st10.context_counts                                  # None without min_context; st00's are the same (same context boxes)
+    t10, t00 = st10.target_counts, st00.target_counts             # None without min_target; each staging has its own (different target clouds)
     out = torch.full((cloud_1.shape[0],), float("nan"), dtype=torch.float32, device=cloud_1.device)
     if dense:
         st10.dense = staging.stage_dense(cloud_1, st10, fin, sel, N if block is None else block)
@@ -422,8 +501,9 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
                     sl = slice(a, a + voxels_per_batch)
                     extra = st10.extra_context[sl] if config.get("using_extra_context") else None
                     lp_0_0.append(inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config,
-                                             context_counts=None if counts is None else counts[sl])[1])
-            change = change_ops.log_prob_to_change_ragged(lp_1_0, st10.dense.offsets, torch.cat(lp_0_0), multiple, hard_cutoff)
+                                             context_counts=None if counts is None else counts[sl],
+                                             target_counts=None if t00 is None else t00[sl])[1])
+            change = change_ops.log_prob_to_change_ragged(lp_1_0, st10.dense.offsets, torch.cat(lp_0_0), multiple, hard_cutoff, base_counts=t00)
             out.scatter_reduce_(0, st10.dense.rows, change, "amax", include_self=False)
         st10.voxel, st10.count_0, st10.count_1 = both, c0_ctx, c1_fin
         return out, st10
@@ -433,17 +513,23 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
             sl = slice(a, a + voxels_per_batch)
             extra = st10.extra_context[sl] if config.get("using_extra_context") else None
             cnt = None if counts is None else counts[sl]
-            _, lp_1_0, _ = inner_loop((st10.extract_0[sl], st10.extract_1[sl], extra), models_dict, config, context_counts=cnt)
-            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config, context_counts=cnt)
-            chunks.append(change_ops.log_prob_to_change(lp_1_0, lp_0_0, multiple, hard_cutoff))
+            n10, n00 = (None, None) if min_target is None else (t10[sl], t00[sl])
+            _, lp_1_0, _ = inner_loop((st10.extract_0[sl], st10.extract_1[sl], extra), models_dict, config, context_counts=cnt, target_counts=n10)
+            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config, context_counts=cnt, target_counts=n00)
+            chunks.append(change_ops.log_prob_to_change(lp_1_0, lp_0_0, multiple, hard_cutoff) if min_target is None else
+                          change_ops.log_prob_to_change_counts(lp_1_0, n10, lp_0_0, n00, multiple, hard_cutoff))
     if chunks:
-        out.scatter_reduce_(0, st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1), "amax", include_self=False)
+        rows, vals = st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1)
+        if min_target is not None:                                # pad slots of sparse voxels: index -1, change NaN -- they name no row
+            real = torch.nonzero(rows >= 0).flatten()
+            rows, vals = rows.index_select(0, real), vals.index_select(0, real)
+        out.scatter_reduce_(0, rows, vals, "amax", include_self=False)
     st10.voxel, st10.count_0, st10.count_1 = both, c0_ctx, c1_fin
     return out, st10
 
 
 def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, layers=("aug",), ground_height=None, multiple=5.4, hard_cutoff=None,
-                              voxels_per_batch=16, weight="change", min_context=None):
+                              voxels_per_batch=16, weight="change", min_context=None, min_target=None):
     """Which points of the OLD scan the change map relied on: the sampled mode of scene_change (same validity rule, stagings, sample
     counts, chunks of `voxels_per_batch` voxels, log_prob_to_change per chunk) plus, per chunk, attention_mass on the (1 | 0) batch with
     weights = that chunk's change (weight="change") or ones (weight="uniform").  Per chunk ONE set of augmenter / CIF noise is drawn from
@@ -454,7 +540,9 @@ def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, la
     through st10.index_0 -- NaN where no evaluated voxel sampled the row as context, the larger value where two voxels share it (the
     rule scene_change applies to shared points; deterministic); change_1 as scene_change returns it.
     min_context as in scene_change: every pass of a chunk gets the chunk's counts, and mass is scattered only through index_0 >= 0 -- the pad
-    slots of a sparse voxel hold exact zeros and reach no row of cloud_0."""
+    slots of a sparse voxel hold exact zeros and reach no row of cloud_0.
+    min_target as in scene_change's sampled mode: target pad slots get weight 0 in attention_mass -- weight="change": the change with its NaN pads
+    replaced by 0, weight="uniform": the 0/1 mask of real slots -- and the change is scattered through index_1 >= 0 only."""
     from . import change as change_ops
     from . import staging
     if weight not in ("change", "uniform"):
@@ -470,14 +558,17 @@ def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, la
     layers = list(layers)
     N, M = config["sample_size"], config["n_samples_context"]
     min_context = _scene_min_context("scene_context_attribution", min_context, models_dict, config)
+    min_target = _scene_min_target("scene_context_attribution", min_target, models_dict, config)
     c0_ctx, c1_fin, c0_fin = (staging.voxel_counts(cloud_0, centers, ctx), staging.voxel_counts(cloud_1, centers, fin),
                               staging.voxel_counts(cloud_0, centers, fin))
-    both = torch.nonzero((c0_ctx >= (M if min_context is None else min_context)) & (c1_fin >= N) & (c0_fin >= N)).flatten()
+    n_min = N if min_target is None else min_target
+    both = torch.nonzero((c0_ctx >= (M if min_context is None else min_context)) & (c1_fin >= n_min) & (c0_fin >= n_min)).flatten()
     sel = centers[both].contiguous()
-    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height, min_context=min_context)
-    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height, min_context=min_context)
+    st10 = staging.stage_scene(cloud_0, cloud_1, sel, fin, ctx, N, M, ground_height, min_context=min_context, min_target=min_target)
+    st00 = staging.stage_scene(cloud_0, cloud_0, sel, fin, ctx, N, M, ground_height, min_context=min_context, min_target=min_target)
     assert st10.voxel.numel() == st00.voxel.numel() == both.numel()
     counts = st10.context_counts
+    t10, t00 = st10.target_counts, st00.target_counts
     change_1 = torch.full((cloud_1.shape[0],), float("nan"), dtype=torch.float32, device=cloud_1.device)
     mass_0 = torch.full((len(layers), cloud_0.shape[0]), float("nan"), dtype=torch.float32, device=cloud_0.device)
     chunks, masses = [], []
@@ -488,14 +579,23 @@ def scene_context_attribution(cloud_0, cloud_1, models_dict, config, centers, la
             batch_10 = (st10.extract_0[sl], st10.extract_1[sl], extra)
             eps = [torch.randn(s, device=cloud_1.device, dtype=torch.float32) for s in flow.noise_shapes(st10.extract_1[sl].shape[0], N)]
             cnt = None if counts is None else counts[sl]
-            _, lp_1_0, _ = inner_loop(batch_10, models_dict, config, eps=eps, context_counts=cnt)
-            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config, eps=eps, context_counts=cnt)
-            change = change_ops.log_prob_to_change(lp_1_0, lp_0_0, multiple, hard_cutoff)
+            n10, n00 = (None, None) if min_target is None else (t10[sl], t00[sl])
+            _, lp_1_0, _ = inner_loop(batch_10, models_dict, config, eps=eps, context_counts=cnt, target_counts=n10)
+            _, lp_0_0, _ = inner_loop((st00.extract_0[sl], st00.extract_1[sl], extra), models_dict, config, eps=eps, context_counts=cnt, target_counts=n00)
+            if min_target is None:
+                change = change_ops.log_prob_to_change(lp_1_0, lp_0_0, multiple, hard_cutoff)
+                w = change if weight == "change" else None
+            else:                                                 # weight 0 on the target pad slots, whose change is NaN
+                change = change_ops.log_prob_to_change_counts(lp_1_0, n10, lp_0_0, n00, multiple, hard_cutoff)
+                w = change.nan_to_num(nan=0.0) if weight == "change" else (st10.index_1[sl] >= 0).to(torch.float32)
             chunks.append(change)
-            masses.append(torch.stack(attention_mass(batch_10, models_dict, config, layers=layers, weights=change if weight == "change" else None,
-                                                     eps=eps, context_counts=cnt)))
+            masses.append(torch.stack(attention_mass(batch_10, models_dict, config, layers=layers, weights=w, eps=eps, context_counts=cnt)))
     if chunks:
-        change_1.scatter_reduce_(0, st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1), "amax", include_self=False)
+        rows_1, vals_1 = st10.index_1.reshape(-1), torch.cat(chunks).reshape(-1)
+        if min_target is not None:                                # target pad slots: index -1, change NaN -- they name no row
+            real_1 = torch.nonzero(rows_1 >= 0).flatten()
+            rows_1, vals_1 = rows_1.index_select(0, real_1), vals_1.index_select(0, real_1)
+        change_1.scatter_reduce_(0, rows_1, vals_1, "amax", include_self=False)
         rows, vals = st10.index_0.reshape(-1), torch.cat(masses, dim=1).reshape(len(layers), -1)
         if counts is not None:                                    # pad slots of sparse voxels: index -1, mass 0.0 -- they name no row
             real = torch.nonzero(rows >= 0).flatten()

@@ -65,7 +65,8 @@ class SceneStage:
     extract_0 [K', M, C], extract_1 [K', N, C], extra_context [K', 1] or None, inverse {'furthest_distance' [K'], 'mean' [K', 3]},
     index_0 [K', M] / index_1 [K', N] (rows of cloud_0 / cloud_1), voxel [K'] (which centres), count_0 / count_1 [K] int32,
     context_counts [K'] int32 (stage_scene's min_context: the context samples of every staged voxel, what inner_loop's `context_counts` takes;
-    extract_0[k, count:] is exact zeros and index_0[k, count:] is -1) or None."""
+    extract_0[k, count:] is exact zeros and index_0[k, count:] is -1) or None, target_counts [K'] int32 (stage_scene's min_target: the same for
+    extract_1 / index_1, what inner_loop's `target_counts` takes) or None."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -206,7 +207,19 @@ def _min_context(name, min_context, M):
     return int(min_context)
 
 
-def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size, n_samples, n_samples_context, ground_height=None, min_context=None):
+def _min_target(name, min_target, N, lowest=1, why=""):
+    """min_target of stage_scene / scene_change: None, or a plain integer in [lowest, n_samples]."""
+    if min_target is None:
+        return None
+    if isinstance(min_target, bool) or torch.is_tensor(min_target) or not isinstance(min_target, numbers.Integral):
+        raise RuntimeError(f"{name}: min_target must be None or an integer, got {type(min_target).__name__}")
+    if not lowest <= min_target <= N:
+        raise RuntimeError(f"{name}: min_target must lie in [{lowest}, n_samples = {N}], got {int(min_target)}{why}")
+    return int(min_target)
+
+
+def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size, n_samples, n_samples_context, ground_height=None, min_context=None,
+                min_target=None):
     """The loader's test-mode item (ams_voxel_loader.py:291-307, 338, 349-350) for every centre of a scene at once: target =
     get_voxel(cloud_1, c, final) -> first n_samples FPS picks, context = get_voxel(cloud_0, c, context) -> first n_samples_context
     picks, co_unit_sphere(context, target).  A voxel is valid when count_0 >= n_samples_context and count_1 >= n_samples (:240);
@@ -217,7 +230,12 @@ def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size,
     min_context and count_1 >= n_samples, and valid voxel k gets min(count_0[k], n_samples_context) context samples -- its rows are bit for bit
     stage_pair(cloud_0[members], cloud_1[members], that count, n_samples); extract_0[k, count:] is exact zeros, index_0[k, count:] is -1, and
     SceneStage.context_counts [K'] int32 holds the counts: st.batch() plus context_counts=st.context_counts is what inner_loop takes.  The
-    target side is unchanged.  With None nothing changes and context_counts is None."""
+    target side is untouched by min_context (min_target, below, gives it a count of its own).  With None nothing changes and context_counts is None.
+
+    min_target (an integer in [1, n_samples]) does the same for the target: a voxel is valid when count_1 >= min_target (the
+    context rule is whatever min_context makes it), valid voxel k gets n_k = min(count_1[k], n_samples) target samples, extract_1[k, n_k:] is exact
+    zeros, index_1[k, n_k:] is -1, SceneStage.target_counts [K'] int32 holds the n_k, and the pair is bit for bit stage_pair on the truncated
+    clouds.  min_target = n_samples gives the tensors of None (plus the counts); with None target_counts is None."""
     _cloud_and_centers("stage_scene", cloud_0, centers)
     _cloud_and_centers("stage_scene", cloud_1, centers)
     if cloud_0.shape[1] != cloud_1.shape[1] or cloud_0.device != cloud_1.device:
@@ -226,9 +244,10 @@ def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size,
     if M < 1 or N < 1:
         raise RuntimeError("stage_scene: sample counts must be positive")
     min_context = _min_context("stage_scene", min_context, M)
+    min_target = _min_target("stage_scene", min_target, N)
     count_0, ws_0 = _count("stage_scene", cloud_0, centers, context_voxel_size)
     count_1, ws_1 = _count("stage_scene", cloud_1, centers, final_voxel_size)
-    voxel = torch.nonzero((count_0 >= (M if min_context is None else min_context)) & (count_1 >= N)).flatten()
+    voxel = torch.nonzero((count_0 >= (M if min_context is None else min_context)) & (count_1 >= (N if min_target is None else min_target))).flatten()
     K1 = voxel.numel()
     if K1 == 0:
         f, i = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
@@ -236,7 +255,8 @@ def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size,
                           extra_context=None if ground_height is None else torch.zeros(0, 1, **f),
                           inverse={'furthest_distance': torch.zeros(0, **f), 'mean': torch.zeros(0, 3, **f)},
                           index_0=torch.zeros(0, M, **i), index_1=torch.zeros(0, N, **i), voxel=voxel, count_0=count_0, count_1=count_1,
-                          context_counts=None if min_context is None else torch.zeros(0, dtype=torch.int32, device=dev))
+                          context_counts=None if min_context is None else torch.zeros(0, dtype=torch.int32, device=dev),
+                          target_counts=None if min_target is None else torch.zeros(0, dtype=torch.int32, device=dev))
 
     def picks(cloud, size, counts, ws, m, ragged=_fps_ragged):
         offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=dev)
@@ -244,7 +264,13 @@ def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size,
         rows = engine.stage_voxel_select(cloud, centers, _dims(size), offsets, int(offsets[-1]), ws)
         return ragged(cloud, offsets, rows, m, voxel)
 
-    if min_context is None:
+    target_counts = None
+    if min_target is not None:                                         # a count on both sides; counts_0 None = every context row real
+        index_0, context_counts = picks(cloud_0, context_voxel_size, count_0, ws_0, M, _fps_ragged_counts) if min_context is not None else \
+            (picks(cloud_0, context_voxel_size, count_0, ws_0, M), None)
+        index_1, target_counts = picks(cloud_1, final_voxel_size, count_1, ws_1, N, _fps_ragged_counts)
+        o0, o1, inv = engine.stage_pairs_counts2(cloud_0, cloud_1, index_0, index_1, context_counts, target_counts)
+    elif min_context is None:
         context_counts = None
         index_0 = picks(cloud_0, context_voxel_size, count_0, ws_0, M)
         index_1 = picks(cloud_1, final_voxel_size, count_1, ws_1, N)
@@ -258,7 +284,7 @@ def stage_scene(cloud_0, cloud_1, centers, final_voxel_size, context_voxel_size,
     inverse = {'furthest_distance': inv[:, 0].contiguous(), 'mean': inv[:, 1:4].contiguous()}
     extra = None if ground_height is None else (inverse['mean'][:, 2] - ground_height).unsqueeze(-1)
     return SceneStage(extract_0=o0, extract_1=o1, extra_context=extra, inverse=inverse, index_0=index_0, index_1=index_1, voxel=voxel,
-                      count_0=count_0, count_1=count_1, context_counts=context_counts)
+                      count_0=count_0, count_1=count_1, context_counts=context_counts, target_counts=target_counts)
 
 
 # ---------------------------------------------------------------- every member of the staged voxels (csrc/scene_stage.hip)

@@ -5,7 +5,8 @@ without a declaration in the header.  tests/test_host.py compares both tables wi
 declared in headers of their own behind fcflow.h (include/fcflow_attention_mass.h; tests/test_attention_mass_host.py), COUNTS_ENTRIES
 those of include/fcflow_context_counts.h (tests/test_context_counts_host.py), SPARSE_STAGE_ENTRIES those of include/fcflow_sparse_stage.h
 (tests/test_sparse_stage_host.py), EMBED_COUNTS_ENTRIES those of include/fcflow_embed_counts.h (tests/test_embed_counts_host.py), SPARSE_TARGET_ENTRIES those of
-include/fcflow_sparse_target.h (tests/test_sparse_target_host.py).
+include/fcflow_sparse_target.h (tests/test_sparse_target_host.py), PACONV_COUNTS_ENTRIES those of include/fcflow_paconv_counts.h
+(tests/test_paconv_counts_host.py).
 
 Parameter kinds:  P  any pointer (handles, struct pointers, const char*, the stream)     i  int32_t / int     l  int64_t
                   f  float     z  size_t
@@ -158,6 +159,13 @@ SPARSE_TARGET_ENTRIES = {
     "fc_change_map_ragged_counts_f32":       ("status", "PPPiPPiffiPP"),
 }
 
+# The PAConv embedder with per-scene point counts: include/fcflow_paconv_counts.h, in that header's order (tests/test_paconv_counts_host.py compares).
+PACONV_COUNTS_ENTRIES = {
+    "fc_paconv_embed_counts_f32":            ("status", "PPPiiPiiPzP"),
+    "fc_op_fps_counts_f32":                  ("status", "PPiiPiiiP"),
+    "fc_op_paconv_knn_counts_f32":           ("status", "PPPPPiiiiP"),
+}
+
 # Diagnostics and test hooks: they hand back their raw code and never raise (a caller compares fc_debug_set(...) with 0).
 DEBUG_ENTRIES = {
     "fc_debug_set":                          ("int", "ii"),
@@ -181,7 +189,8 @@ def bind(L, status_errcheck):
     """Sets argtypes and restype of every table entry the loaded library has; a status entry of ENTRIES also gets `status_errcheck`.
     A symbol the library lacks is skipped (an FCFLOW_LIB build of this ABI version that predates an entry still loads) and fails
     with AttributeError at the call."""
-    for table in (ENTRIES, EXTRA_ENTRIES, COUNTS_ENTRIES, SPARSE_STAGE_ENTRIES, EMBED_COUNTS_ENTRIES, SPARSE_TARGET_ENTRIES, DEBUG_ENTRIES):
+    for table in (ENTRIES, EXTRA_ENTRIES, COUNTS_ENTRIES, SPARSE_STAGE_ENTRIES, EMBED_COUNTS_ENTRIES, SPARSE_TARGET_ENTRIES, PACONV_COUNTS_ENTRIES,
+                  DEBUG_ENTRIES):
         for name, (ret, params) in table.items():
             fn = getattr(L, name, None)
             if fn is None:

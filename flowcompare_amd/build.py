@@ -46,7 +46,7 @@ def _newer(a, deps):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(HERE, "..", "include", h) for h in ("fcflow.h", "fcflow_attention_mass.h", "fcflow_context_counts.h", "fcflow_sparse_stage.h", "fcflow_embed_counts.h", "fcflow_sparse_target.h")]
+    headers += [os.path.join(HERE, "..", "include", h) for h in ("fcflow.h", "fcflow_attention_mass.h", "fcflow_context_counts.h", "fcflow_sparse_stage.h", "fcflow_embed_counts.h", "fcflow_sparse_target.h", "fcflow_paconv_counts.h")]
     jobs = []
     objs = []
     for src in _sources():

@@ -16,6 +16,7 @@
 #include "../../include/fcflow_sparse_stage.h"
 #include "../../include/fcflow_embed_counts.h"
 #include "../../include/fcflow_sparse_target.h"
+#include "../../include/fcflow_paconv_counts.h"
 #include "knobs.h"
 
 namespace fc {
@@ -326,6 +327,21 @@ void launch_score_reduce(const float* G, int ldg, const float* scores, const flo
                          int dst_col0, int mode, int total_queries, hipStream_t s);
 void launch_three_nn_interp(const float* uxyz, int ldu, const float* kxyz, int ldk, const float* Fk, int ldfk, int C2, const float* Fu, int ldfu, int C1,
                             float* X, int ldX, int B, int nu, int mk, hipStream_t s);
+// Per-scene sizes of one level of a counted PAConv launch (fcflow_paconv_counts.h): scene b uses the first
+// clamp(counts[b], lo, hi) >> shift rows of its block (device.h: level_count); blocks keep the uniform row strides.  counts null = the uniform launch.
+struct LevelCounts { const int32_t* counts = nullptr; int lo = 0, hi = 0, shift = 0; };
+// the namesakes above with per-scene sizes: cn the points of a scene at the launch's source level (n_b), cm its queries (m_b); n and m stay the
+// strides and the largest sizes.  A pad query / point reads no index and writes literal zeros into everything it owns; fps writes -1 into idx[b, m_b:].
+void launch_fps_counts(const float* xyz, int ld, int32_t* idx, int B, int n, int m, float* scratch, const LevelCounts& cn, hipStream_t s);
+void launch_gather_xyz_counts(const float* src, int ld, const int32_t* idx, float* dst, int B, int n, int m, const LevelCounts& cm, hipStream_t s);
+void launch_knn_xyz_counts(const float* xyz, int ld, const float* qxyz, int32_t* out, int B, int n, int m, int k, const LevelCounts& cn, const LevelCounts& cm,
+                           hipStream_t s);
+void launch_paconv_group_counts(const float* xyz, int ldxyz, const float* feat, int ldf, int C, const float* qxyz, const int32_t* nidx, float* E, int ldE,
+                                float* gdiff, int B, int n, int m, int K, const LevelCounts& cm, hipStream_t s);
+void launch_score_reduce_counts(const float* G, int ldg, const float* scores, const float* bn_s, const float* bn_t, int Cout, int K, float* dst, int ldd,
+                                int dst_col0, int mode, int B, int m, const LevelCounts& cm, hipStream_t s);
+void launch_three_nn_interp_counts(const float* uxyz, int ldu, const float* kxyz, int ldk, const float* Fk, int ldfk, int C2, const float* Fu, int ldfu, int C1,
+                                   float* X, int ldX, int B, int nu, int mk, const LevelCounts& cu, const LevelCounts& ck, hipStream_t s);
 void launch_co_unit_sphere(const float* p0, int n0, const float* p1, int n1, int ld, float* o0, float* o1, float* inverse, int B, hipStream_t s);
 void launch_clamp_infs(float* t, long n, float* stats4, int* status, hipStream_t s);
 void launch_change_map(float* lp10, int N, float* lp00, int N0, float* out, int B, float multiple, float hard_cutoff, int use_cutoff,

@@ -69,6 +69,16 @@ __device__ __forceinline__ int scene_count(const int* m_counts, int b, int lo, i
     return c < lo ? lo : (c < hi ? c : hi);
 }
 
+// The rows scene b uses at one level of a counted PAConv launch (common.h: LevelCounts): its clamped count, divided by 4 once per level.
+template <class LC>
+__device__ __forceinline__ int level_count(const LC& c, int b) { return scene_count(c.counts, b, c.lo, c.hi) >> c.shift; }
+// the same where b differs between the lanes of a wave (one thread per row): a vector load, no SGPR pin
+template <class LC>
+__device__ __forceinline__ int level_count_lane(const LC& c, int b) {
+    const int v = c.counts[b];
+    return (v < c.lo ? c.lo : (v < c.hi ? v : c.hi)) >> c.shift;
+}
+
 // ---------------------------------------------------------------- sum over a workgroup of up to 256 threads (the row kernels of training)
 // deterministic: xor tree inside each wave, then waves in order.  red: blockDim.x / 64 floats of LDS; every thread gets the sum.
 __device__ __forceinline__ float block_sum_256(float v, float* red) {

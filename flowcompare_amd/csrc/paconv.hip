@@ -10,7 +10,10 @@
 //   score_reduce_kernel   util/paconv_util.py:52-56 (assign_score) + BN + ReLU + either the next layer's cat(.) or the max over K
 //   three_nn_interp_kernel .../interpolation/interpolation_cuda_kernel.cu:134-195 + PointNet2FPModule.forward
 //                         (model/pointnet2/pointnet2_paconv_modules.py:224-236): 3-NN, inverse-distance weights, interpolation, skip concat
+#include <algorithm>
+
 #include "common.h"
+#include "device.h"
 #include "launch.h"
 
 namespace fc {
@@ -35,15 +38,32 @@ __device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx,
 // takes 226).  (value, bit-reversed id) is a total order, so any reduction order finds that winner.
 // BIG (more than 8192 points per scene: the LDS image would not fit): coordinates are read from the input rows and the running
 // min-distance lives in a caller-provided global scratch [B][n]; both stay L2-resident over the m sweeps (same arithmetic, same ties).
-template <bool BIG>
-__global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ xyz, int ld, int32_t* __restrict__ idx, int n, int m, int T,
-                                                   float* __restrict__ scratch) {
+// CNT (fcflow_paconv_counts.h): scene b samples m_b = n_b >> 2 of its first n_b = level_count(cn, b) rows with the T = opt_n_threads(n_b) it uses
+// alone (the tie rule depends on T); sn / sm_ are then the strides of xyz and idx (the launch's largest sizes, which also choose BIG), and
+// idx[b, m_b:] is written as -1.  The uniform instantiations (CNT false: n = sn, m = sm_) keep their statements.
+__host__ __device__ static inline int opt_n_threads(int n) {
+    int p = 0;
+    while ((2 << p) <= n) ++p;
+    int t = 1 << p;
+    return t > 1024 ? 1024 : (t < 1 ? 1 : t);
+}
+template <bool BIG, bool CNT>
+__global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ xyz, int ld, int32_t* __restrict__ idx, int sn, int sm_, int T,
+                                                   float* __restrict__ scratch, LevelCounts cn) {
     extern __shared__ float sm[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* src = xyz + (size_t)b * n * ld;
+    int n = sn, m = sm_;
+    if constexpr (CNT) {
+        n = level_count(cn, b);
+        m = n >> 2;
+        T = opt_n_threads(n);
+        for (int j = m + tid; j < sm_; j += 1024) idx[(size_t)b * sm_ + j] = -1;
+        if (m < 1) return;                                  // (block-uniform; never taken through the entries: the engine's counts >= 256 and fc_op_fps_counts_f32's count_min >= 4 give m >= 1)
+    }
+    const float* src = xyz + (size_t)b * sn * ld;
     const float* sx = BIG ? src : sm;                       // [n][3] (pitch 3 in LDS, ld in global)
     const int pitch = BIG ? ld : 3;
-    float* st = BIG ? scratch + (size_t)b * n : sm + 3 * n; // [n]
+    float* st = BIG ? scratch + (size_t)b * sn : sm + 3 * n; // [n]
     __shared__ float red_v[16];
     __shared__ int red_i[16];
     __shared__ int red_t[16];
@@ -52,7 +72,7 @@ __global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ xyz
         if (!BIG) { sm[3 * k] = src[(size_t)k * ld]; sm[3 * k + 1] = src[(size_t)k * ld + 1]; sm[3 * k + 2] = src[(size_t)k * ld + 2]; }
         st[k] = 1e10f;
     }
-    if (tid == 0) { idx[(size_t)b * m] = 0; s_old = 0; }
+    if (tid == 0) { idx[(size_t)b * sm_] = 0; s_old = 0; }
     __syncthreads();
     for (int j = 1; j < m; ++j) {
         const int old = s_old;
@@ -87,16 +107,10 @@ __global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ xyz
                 const unsigned ow = (unsigned)__shfl_xor((int)w2, off, 64);
                 if (ov > v || (ov == v && ow < w2)) { v = ov; i = oi; w2 = ow; }
             }
-            if (lane == 0) { s_old = i; idx[(size_t)b * m + j] = i; }
+            if (lane == 0) { s_old = i; idx[(size_t)b * sm_ + j] = i; }
         }
         __syncthreads();
     }
-}
-static int opt_n_threads_host(int n) {
-    int p = 0;
-    while ((2 << p) <= n) ++p;
-    int t = 1 << p;
-    return t > 1024 ? 1024 : (t < 1 ? 1 : t);
 }
 size_t fps_scratch_floats(int B, int n) { return n > 8192 ? (size_t)B * n : 0; }
 void launch_fps(const float* xyz, int ld, int32_t* idx, int B, int n, int m, float* scratch, hipStream_t s) {
@@ -105,18 +119,39 @@ void launch_fps(const float* xyz, int ld, int32_t* idx, int B, int n, int m, flo
     const double bytes = 4.0 * B * (3.0 * n + m);
     if (n > 8192) {
         if (!scratch) throw Error(FC_ERR_WORKSPACE, "furthest point sampling: more than 8192 points per scene need the [B][n] min-distance scratch (fps_scratch_floats)");
-        launch_kernel<fps_kernel<true>, 0>("fc::fps_kernel", 0.0, bytes, dim3(B), dim3(1024), 0, s, xyz, ld, idx, n, m, opt_n_threads_host(n), scratch);
+        launch_kernel<fps_kernel<true, false>, 0>("fc::fps_kernel", 0.0, bytes, dim3(B), dim3(1024), 0, s, xyz, ld, idx, n, m, opt_n_threads(n), scratch, LevelCounts{});
     } else {
-        launch_kernel<fps_kernel<false>, 8192 * 16>("fc::fps_kernel", 0.0, bytes, dim3(B), dim3(1024), (size_t)n * 4 * sizeof(float), s, xyz, ld, idx, n, m,
-                                                    opt_n_threads_host(n), (float*)nullptr);
+        launch_kernel<fps_kernel<false, false>, 8192 * 16>("fc::fps_kernel", 0.0, bytes, dim3(B), dim3(1024), (size_t)n * 4 * sizeof(float), s, xyz, ld, idx, n, m,
+                                                           opt_n_threads(n), (float*)nullptr, LevelCounts{});
+    }
+}
+// n, m = n >> 2: the strides and the largest level size of the launch; every scene's own sizes are read on the device
+void launch_fps_counts(const float* xyz, int ld, int32_t* idx, int B, int n, int m, float* scratch, const LevelCounts& cn, hipStream_t s) {
+    if (m <= 0) return;
+    if (m != n >> 2) throw Error(FC_ERR_INVALID, "furthest point sampling with counts: m must be n >> 2");
+    const double bytes = 4.0 * B * (3.0 * n + m);
+    if (n > 8192) {
+        if (!scratch) throw Error(FC_ERR_WORKSPACE, "furthest point sampling: more than 8192 points per scene need the [B][n] min-distance scratch (fps_scratch_floats)");
+        launch_kernel<fps_kernel<true, true>, 0>("fc::fps_kernel", 0.0, bytes, dim3(B), dim3(1024), 0, s, xyz, ld, idx, n, m, 0, scratch, cn);
+    } else {
+        launch_kernel<fps_kernel<false, true>, 8192 * 16>("fc::fps_kernel", 0.0, bytes, dim3(B), dim3(1024), (size_t)n * 4 * sizeof(float), s, xyz, ld, idx, n, m, 0,
+                                                          (float*)nullptr, cn);
     }
 }
 
-// dst[b, j, 0:3] = src[b, idx[b, j], 0:3] ; dst pitch 4 (last component 0)
-__global__ void gather_xyz_kernel(const float* __restrict__ src, int ld, const int32_t* __restrict__ idx, float* dst, int n, int m, int total) {
+// dst[b, j, 0:3] = src[b, idx[b, j], 0:3] ; dst pitch 4 (last component 0).  CNT: rows j >= m_b = level_count(cm, b) read no index and get zeros.
+template <bool CNT>
+__global__ void gather_xyz_kernel(const float* __restrict__ src, int ld, const int32_t* __restrict__ idx, float* dst, int n, int m, int total, LevelCounts cm) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
     const int b = t / m;
+    if constexpr (CNT) {
+        if (t - b * m >= level_count_lane(cm, b)) {        // (one thread per row: a wave may straddle two scenes)
+            float* d = dst + (size_t)t * 4;
+            d[0] = 0.f; d[1] = 0.f; d[2] = 0.f; d[3] = 0.f;
+            return;
+        }
+    }
     const float* p = src + ((size_t)b * n + idx[t]) * ld;
     float* d = dst + (size_t)t * 4;
     d[0] = p[0]; d[1] = p[1]; d[2] = p[2]; d[3] = 0.f;
@@ -124,7 +159,12 @@ __global__ void gather_xyz_kernel(const float* __restrict__ src, int ld, const i
 void launch_gather_xyz(const float* src, int ld, const int32_t* idx, float* dst, int B, int n, int m, hipStream_t s) {
     const int total = B * m;
     if (total <= 0) return;
-    launch_kernel<gather_xyz_kernel>(nullptr, 0.0, 0.0, dim3((total + 255) / 256), dim3(256), 0, s, src, ld, idx, dst, n, m, total);
+    launch_kernel<gather_xyz_kernel<false>>(nullptr, 0.0, 0.0, dim3((total + 255) / 256), dim3(256), 0, s, src, ld, idx, dst, n, m, total, LevelCounts{});
+}
+void launch_gather_xyz_counts(const float* src, int ld, const int32_t* idx, float* dst, int B, int n, int m, const LevelCounts& cm, hipStream_t s) {
+    const int total = B * m;
+    if (total <= 0) return;
+    launch_kernel<gather_xyz_kernel<true>>(nullptr, 0.0, 0.0, dim3((total + 255) / 256), dim3(256), 0, s, src, ld, idx, dst, n, m, total, cm);
 }
 
 // ---------------------------------------------------------------- k nearest neighbours in xyz, ascending distance
@@ -137,13 +177,24 @@ void launch_gather_xyz(const float* src, int ld, const int32_t* idx, float* dst,
 // eviction is the heap's choice too -- neither is an index order.  The wave therefore extracts one candidate more than k, and when any two
 // neighbouring distances among those k + 1 are equal its lane 0 re-runs the query through the kernel's own heap, literally (LDS arrays):
 // same set, same order as the reference on every input.  Clouds without exact ties never take that path.
-template <int LK>   // per-lane list length
+// CNT (fcflow_paconv_counts.h): scene b's candidates are its first n_b = level_count(cn, b) rows and its queries its first m_b = level_count(cm, b);
+// sn and m stay the strides.  A pad query reads nothing and writes k zeros.  LK is chosen by the launch's largest n_b: whenever a scene alone would
+// run a shorter list, that list already holds all of a lane's candidates, so every sufficient LK extracts the same sequence.
+template <int LK, bool CNT>   // per-lane list length
 __global__ __launch_bounds__(256) void knn_xyz_kernel(const float* __restrict__ xyz, int ld, const float* __restrict__ qxyz, int32_t* __restrict__ out,
-                                                      int n, int m, int k, int total) {
+                                                      int sn, int m, int k, int total, LevelCounts cn, LevelCounts cm) {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= total) return;
     const int b = q / m;
-    const float* src = xyz + (size_t)b * n * ld;
+    int n = sn;
+    if constexpr (CNT) {
+        n = level_count(cn, b);
+        if (q - b * m >= level_count(cm, b)) {              // (wave-uniform)
+            if (lane < k) out[(size_t)q * k + lane] = 0;
+            return;
+        }
+    }
+    const float* src = xyz + (size_t)b * sn * ld;
     const float qx = qxyz[(size_t)q * 4], qy = qxyz[(size_t)q * 4 + 1], qz = qxyz[(size_t)q * 4 + 2];
     float bd[LK];
     int bi[LK];
@@ -222,21 +273,43 @@ void launch_knn_xyz(const float* xyz, int ld, const float* qxyz, int32_t* out, i
     // a lane sees ceil(n/64) candidates; its list must be able to hold all of them or k of them, whichever is smaller
     const int need = (n + 63) / 64 < k ? (n + 63) / 64 : k;
     ProfScope ps("fc::knn_xyz_kernel", 8.0 * total * (double)n, 4.0 * total * k, s);      // one scope, whichever list length runs
-    if (need <= 8) launch_kernel<knn_xyz_kernel<8>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
-    else if (need <= 16) launch_kernel<knn_xyz_kernel<16>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
-    else launch_kernel<knn_xyz_kernel<32>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total);
+    const LevelCounts no{};
+    if (need <= 8) launch_kernel<knn_xyz_kernel<8, false>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total, no, no);
+    else if (need <= 16) launch_kernel<knn_xyz_kernel<16, false>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total, no, no);
+    else launch_kernel<knn_xyz_kernel<32, false>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total, no, no);
+}
+void launch_knn_xyz_counts(const float* xyz, int ld, const float* qxyz, int32_t* out, int B, int n, int m, int k, const LevelCounts& cn, const LevelCounts& cm,
+                           hipStream_t s) {
+    const int total = B * m;
+    if (total <= 0) return;
+    if (k > 32) throw Error(FC_ERR_UNSUPPORTED, "xyz k-NN: nsample > 32");
+    const int nmax = std::min(n, cn.hi >> cn.shift);                                      // the largest n_b the clamp lets through
+    const int need = (nmax + 63) / 64 < k ? (nmax + 63) / 64 : k;
+    ProfScope ps("fc::knn_xyz_kernel", 8.0 * total * (double)nmax, 4.0 * total * k, s);
+    if (need <= 8) launch_kernel<knn_xyz_kernel<8, true>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total, cn, cm);
+    else if (need <= 16) launch_kernel<knn_xyz_kernel<16, true>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total, cn, cm);
+    else launch_kernel<knn_xyz_kernel<32, true>>(nullptr, 0.0, 0.0, dim3((total + 3) / 4), dim3(256), 0, s, xyz, ld, qxyz, out, n, m, k, total, cn, cm);
 }
 
 // ---------------------------------------------------------------- grouping + first PAConv layer input
 // Per query q (one wave) and neighbour e: f_e = [xyz_src[idx_e] - new_xyz[q] (3) | F_src[idx_e] (C)]  (QueryAndGroup, use_xyz)
 //   E[q*K + e] = [f_e - f_0 (C+3) | f_e (C+3) | 0-pad]   (PAConv kernel_input 'neighbor': the centre is neighbour 0)
 //   gdiff[q*K + e] = xyz_src[idx_e] - xyz_src[idx_0]      (ScoreNet input, score_input 'identity')
+// CNT: a pad query (row >= m_b = level_count(cm, b) of its scene) reads no index and writes zeros into its K rows of E and of gdiff.
+template <bool CNT>
 __global__ __launch_bounds__(256) void paconv_group_kernel(const float* __restrict__ xyz, int ldxyz, const float* __restrict__ feat, int ldf, int C,
                                                            const float* __restrict__ qxyz, const int32_t* __restrict__ nidx, float* E, int ldE,
-                                                           float* gdiff, int n, int m, int K, int total) {
+                                                           float* gdiff, int n, int m, int K, int total, LevelCounts cm) {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= total) return;
     const int b = q / m;
+    if constexpr (CNT) {
+        if (q - b * m >= level_count(cm, b)) {              // (wave-uniform)
+            for (int t = lane; t < K * ldE; t += 64) E[(size_t)q * K * ldE + t] = 0.f;
+            for (int t = lane; t < K * 4; t += 64) gdiff[(size_t)q * K * 4 + t] = 0.f;
+            return;
+        }
+    }
     const size_t base = (size_t)b * n;
     const int32_t* ip = nidx + (size_t)q * K;
     const int i0 = ip[0];
@@ -270,8 +343,15 @@ void launch_paconv_group(const float* xyz, int ldxyz, const float* feat, int ldf
                          float* gdiff, int B, int n, int m, int K, hipStream_t s) {
     const int total = B * m;
     if (total <= 0) return;
-    launch_kernel<paconv_group_kernel>("fc::paconv_group_kernel", 0.0, 4.0 * total * K * (ldE + 4.0 + C), dim3((total + 3) / 4), dim3(256), 0, s, xyz, ldxyz, feat, ldf, C, qxyz, nidx,
-                                       E, ldE, gdiff, n, m, K, total);
+    launch_kernel<paconv_group_kernel<false>>("fc::paconv_group_kernel", 0.0, 4.0 * total * K * (ldE + 4.0 + C), dim3((total + 3) / 4), dim3(256), 0, s, xyz, ldxyz, feat, ldf, C, qxyz, nidx,
+                                              E, ldE, gdiff, n, m, K, total, LevelCounts{});
+}
+void launch_paconv_group_counts(const float* xyz, int ldxyz, const float* feat, int ldf, int C, const float* qxyz, const int32_t* nidx, float* E, int ldE,
+                                float* gdiff, int B, int n, int m, int K, const LevelCounts& cm, hipStream_t s) {
+    const int total = B * m;
+    if (total <= 0) return;
+    launch_kernel<paconv_group_kernel<true>>("fc::paconv_group_kernel", 0.0, 4.0 * total * K * (ldE + 4.0 + C), dim3((total + 3) / 4), dim3(256), 0, s, xyz, ldxyz, feat, ldf, C, qxyz, nidx,
+                                             E, ldE, gdiff, n, m, K, total, cm);
 }
 
 // ---------------------------------------------------------------- ScoreNet: one thread per edge
@@ -313,11 +393,21 @@ void launch_scorenet(const float* gdiff, const float* w, float* scores, int edge
 // ---------------------------------------------------------------- score-weighted kernel assembly + BN + ReLU
 // O[e, o] = ReLU( bn_s[o] * sum_m score[e, m] * G[e, m*Cout + o] + bn_t[o] )        (assign_score + BN2d + ReLU)
 //   mode 0: next layer input  E[e] = [O_e - O_0 | O_e | 0-pad]      mode 1: pooled[q, o] = max_e O[e, o]
+// CNT: a pad query (row >= m_b = level_count(cm, b) of its scene's m) writes zeros: its K rows of the next E, pad columns included, or its pooled row.
+template <bool CNT>
 __global__ __launch_bounds__(256) void score_reduce_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ scores,
                                                            const float* __restrict__ bn_s, const float* __restrict__ bn_t, int Cout, int K,
-                                                           float* dst, int ldd, int dst_col0, int mode, int total) {
+                                                           float* dst, int ldd, int dst_col0, int mode, int total, int m, LevelCounts cm) {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= total) return;
+    if constexpr (CNT) {
+        const int b = q / m;
+        if (q - b * m >= level_count(cm, b)) {              // (wave-uniform)
+            if (mode == 0) for (int t = lane; t < K * ldd; t += 64) dst[(size_t)q * K * ldd + t] = 0.f;
+            else for (int o = lane; o < Cout; o += 64) dst[(size_t)q * ldd + dst_col0 + o] = 0.f;
+            return;
+        }
+    }
     const float* sq = scores + (size_t)q * K * 8;
     for (int o = lane; o < Cout; o += 64) {
         const float bs = bn_s[o], bt = bn_t[o];
@@ -349,22 +439,40 @@ __global__ __launch_bounds__(256) void score_reduce_kernel(const float* __restri
 void launch_score_reduce(const float* G, int ldg, const float* scores, const float* bn_s, const float* bn_t, int Cout, int K, float* dst, int ldd,
                          int dst_col0, int mode, int total_queries, hipStream_t s) {
     if (total_queries <= 0) return;
-    launch_kernel<score_reduce_kernel>("fc::score_reduce_kernel", 0.0, 4.0 * total_queries * K * (8.0 * Cout + 8.0 + (mode == 0 ? 2.0 * Cout : 0.0)), dim3((total_queries + 3) / 4),
-                                       dim3(256), 0, s, G, ldg, scores, bn_s, bn_t, Cout, K, dst, ldd, dst_col0, mode, total_queries);
+    launch_kernel<score_reduce_kernel<false>>("fc::score_reduce_kernel", 0.0, 4.0 * total_queries * K * (8.0 * Cout + 8.0 + (mode == 0 ? 2.0 * Cout : 0.0)), dim3((total_queries + 3) / 4),
+                                              dim3(256), 0, s, G, ldg, scores, bn_s, bn_t, Cout, K, dst, ldd, dst_col0, mode, total_queries, 0, LevelCounts{});
+}
+void launch_score_reduce_counts(const float* G, int ldg, const float* scores, const float* bn_s, const float* bn_t, int Cout, int K, float* dst, int ldd,
+                                int dst_col0, int mode, int B, int m, const LevelCounts& cm, hipStream_t s) {
+    const int total_queries = B * m;
+    if (total_queries <= 0) return;
+    launch_kernel<score_reduce_kernel<true>>("fc::score_reduce_kernel", 0.0, 4.0 * total_queries * K * (8.0 * Cout + 8.0 + (mode == 0 ? 2.0 * Cout : 0.0)), dim3((total_queries + 3) / 4),
+                                             dim3(256), 0, s, G, ldg, scores, bn_s, bn_t, Cout, K, dst, ldd, dst_col0, mode, total_queries, m, cm);
 }
 
 // ---------------------------------------------------------------- feature propagation front end
 // Per unknown point (one wave): the 3 nearest known points (strict '<' updates: the earliest index wins ties; bests kept as the
 // float distance like the CUDA kernel's double copies of float values), weights (1/(sqrt(d2)+1e-8)) normalised, then
 //   X[p] = [ sum_i w_i Fk[idx_i, 0:C2] | Fu[p, 0:C1] | 0-pad ]
+// CNT: scene b has nu_b = level_count(cu, b) unknown and mk_b = level_count(ck, b) known points (smk stays the stride of the known level); a pad
+// point (row >= nu_b) reads nothing and writes its whole row of X as zeros.  Fewer than 3 known points follows mk_b.
+template <bool CNT>
 __global__ __launch_bounds__(256) void three_nn_interp_kernel(const float* __restrict__ uxyz, int ldu, const float* __restrict__ kxyz, int ldk,
                                                               const float* __restrict__ Fk, int ldfk, int C2, const float* __restrict__ Fu, int ldfu,
-                                                              int C1, float* X, int ldX, int nu, int mk, int total) {
+                                                              int C1, float* X, int ldX, int nu, int smk, int total, LevelCounts cu, LevelCounts ck) {
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (p >= total) return;
     const int b = p / nu;
+    int mk = smk;
+    if constexpr (CNT) {
+        mk = level_count(ck, b);
+        if (p - b * nu >= level_count(cu, b)) {             // (wave-uniform)
+            for (int c = lane; c < ldX; c += 64) X[(size_t)p * ldX + c] = 0.f;
+            return;
+        }
+    }
     const float ux = uxyz[(size_t)p * ldu], uy = uxyz[(size_t)p * ldu + 1], uz = uxyz[(size_t)p * ldu + 2];
-    const float* ks = kxyz + (size_t)b * mk * ldk;
+    const float* ks = kxyz + (size_t)b * smk * ldk;
     float d0 = INFINITY, d1 = INFINITY, d2 = INFINITY;
     int i0 = 0x7fffffff, i1 = 0x7fffffff, i2 = 0x7fffffff;
     for (int c = lane; c < mk; c += 64) {
@@ -394,9 +502,9 @@ __global__ __launch_bounds__(256) void three_nn_interp_kernel(const float* __res
     for (int r = 0; r < 3; ++r) { w[r] = 1.0f / (sqrtf(bd[r]) + 1e-8f); ws += w[r]; }
 #pragma unroll
     for (int r = 0; r < 3; ++r) w[r] = w[r] / ws;
-    const float* f0 = Fk + ((size_t)b * mk + bi[0]) * ldfk;
-    const float* f1 = Fk + ((size_t)b * mk + bi[1]) * ldfk;
-    const float* f2 = Fk + ((size_t)b * mk + bi[2]) * ldfk;
+    const float* f0 = Fk + ((size_t)b * smk + bi[0]) * ldfk;
+    const float* f1 = Fk + ((size_t)b * smk + bi[1]) * ldfk;
+    const float* f2 = Fk + ((size_t)b * smk + bi[2]) * ldfk;
     float* x = X + (size_t)p * ldX;
     for (int c = lane; c < C2; c += 64) x[c] = (w[0] * f0[c] + w[1] * f1[c]) + w[2] * f2[c];
     for (int c = lane; c < C1; c += 64) x[C2 + c] = Fu[(size_t)p * ldfu + c];
@@ -407,8 +515,17 @@ void launch_three_nn_interp(const float* uxyz, int ldu, const float* kxyz, int l
     const int total = B * nu;
     if (total <= 0) return;
     if (mk < 1) throw Error(FC_ERR_INVALID, "feature propagation: no known points");
-    launch_kernel<three_nn_interp_kernel>("fc::three_nn_interp_kernel", 8.0 * total * (double)mk, 4.0 * total * (ldX + 3.0 * C2 + C1), dim3((total + 3) / 4), dim3(256), 0, s, uxyz, ldu,
-                                          kxyz, ldk, Fk, ldfk, C2, Fu, ldfu, C1, X, ldX, nu, mk, total);
+    const LevelCounts no{};
+    launch_kernel<three_nn_interp_kernel<false>>("fc::three_nn_interp_kernel", 8.0 * total * (double)mk, 4.0 * total * (ldX + 3.0 * C2 + C1), dim3((total + 3) / 4), dim3(256), 0, s, uxyz, ldu,
+                                                 kxyz, ldk, Fk, ldfk, C2, Fu, ldfu, C1, X, ldX, nu, mk, total, no, no);
+}
+void launch_three_nn_interp_counts(const float* uxyz, int ldu, const float* kxyz, int ldk, const float* Fk, int ldfk, int C2, const float* Fu, int ldfu, int C1,
+                                   float* X, int ldX, int B, int nu, int mk, const LevelCounts& cu, const LevelCounts& ck, hipStream_t s) {
+    const int total = B * nu;
+    if (total <= 0) return;
+    if (mk < 1 || ck.lo >> ck.shift < 1) throw Error(FC_ERR_INVALID, "feature propagation: no known points");
+    launch_kernel<three_nn_interp_kernel<true>>("fc::three_nn_interp_kernel", 8.0 * total * (double)mk, 4.0 * total * (ldX + 3.0 * C2 + C1), dim3((total + 3) / 4), dim3(256), 0, s, uxyz, ldu,
+                                                kxyz, ldk, Fk, ldfk, C2, Fu, ldfu, C1, X, ldX, nu, mk, total, cu, ck);
 }
 
 }  // namespace fc

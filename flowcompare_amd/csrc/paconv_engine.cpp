@@ -156,28 +156,46 @@ static PaWs plan_pa(const fc_paconv& e, int B, int M, void* ws, size_t bytes, bo
     return w;
 }
 
-static void paconv_forward(fc_paconv& e, const float* pts, float* out, int B, int M, void* ws, size_t bytes, hipStream_t s) {
-    if (!pts || !out || B < 1) throw Error(FC_ERR_INVALID, "fc_paconv_embed_f32: bad argument");
-    if (M < 256) throw Error(FC_ERR_INVALID, "PAConv embedder needs at least 256 context points (four 4x farthest-point down-samplings)");
+// cnt: null for the uniform call.  With per-scene counts (fcflow_paconv_counts.h) scene b is embedded as its first count_b
+// rows: level l of scene b stays at b * n[l] and uses its first count_b >> 2l rows.  The five kernels through which a row depends on its scene --
+// FPS, the xyz gather, the 32-NN, the grouping, the 3-NN interpolation -- and score_reduce take the counts; ScoreNet, the GEMMs and the head run on
+// the padded row count, whose pad rows are written as exact zeros wherever they enter a GEMM and in the output [B, M, E].
+static void paconv_forward(fc_paconv& e, const char* who, const float* pts, const SceneCounts* cnt, float* out, int B, int M, void* ws, size_t bytes, hipStream_t s) {
+    if (!pts || !out || B < 1) throw Error(FC_ERR_INVALID, std::string(who) + ": bad argument");
+    if (cnt && !cnt->counts) throw Error(FC_ERR_INVALID, std::string(who) + ": null counts (the call without counts is fc_paconv_embed_f32)");
+    if ((cnt ? std::min(cnt->lo, M) : M) < 256) throw Error(FC_ERR_INVALID, "PAConv embedder needs at least 256 context points (four 4x farthest-point down-samplings)");
+    if (cnt && (cnt->lo > cnt->hi || cnt->hi > M)) throw Error(FC_ERR_INVALID, std::string(who) + ": counts must satisfy 256 <= count_min <= count_max <= M");
     constexpr int K = fc_paconv::K;
     PaWs w = plan_pa(e, B, M, ws, bytes, false, nullptr);
     const int ldp = 3 + e.c_feat;
+    auto lvl = [&](int l) { return LevelCounts{cnt->counts, cnt->lo, cnt->hi, 2 * l}; };      // the scene's rows at level l: count_b >> 2l
     // level 0: xyz (pitch 4) and raw features (pitch 32)
     launch_fill(w.xyz[0], 0.f, (size_t)round_up(B * M, ROW_PAD) * 4, s);
     launch_pack_rows(pts, ldp, 3, w.xyz[0], 4, 0, 4, B * M, s);
     launch_fill(w.feat[0], 0.f, (size_t)round_up(B * M, ROW_PAD) * w.ldf[0], s);
     if (e.c_feat > 0) launch_pack_rows(pts + 3, ldp, e.c_feat, w.feat[0], w.ldf[0], 0, e.c_feat, B * M, s);
+    if (cnt) {                                             // (a NaN or 1e30 in the caller's pad rows stays out of every panel)
+        launch_zero_pad_rows(w.xyz[0], 4, cnt->counts, B, M, s);
+        launch_zero_pad_rows(w.feat[0], w.ldf[0], cnt->counts, B, M, s);
+    }
     int cprev = e.c_feat;
     // ---- set abstraction
     for (int l = 0; l < 4; ++l) {
         const int n = w.n[l], m = w.n[l + 1], edges = B * m * K, edges_pad = round_up(std::max(edges, 1), ROW_PAD);
-        launch_fps(w.xyz[l], 4, w.fidx, B, n, m, w.fps_tmp, s);
-        launch_gather_xyz(w.xyz[l], 4, w.fidx, w.xyz[l + 1], B, n, m, s);
-        launch_knn_xyz(w.xyz[l], 4, w.xyz[l + 1], w.nidx, B, n, m, K, s);
         float* Ein = w.Ea;
         float* Eout = w.Eb;
         const int ldE0 = e.sa[l][0].bank.K_pad;
-        launch_paconv_group(w.xyz[l], 4, w.feat[l], w.ldf[l], cprev, w.xyz[l + 1], w.nidx, Ein, ldE0, w.gdiff, B, n, m, K, s);
+        if (cnt) {
+            launch_fps_counts(w.xyz[l], 4, w.fidx, B, n, m, w.fps_tmp, lvl(l), s);
+            launch_gather_xyz_counts(w.xyz[l], 4, w.fidx, w.xyz[l + 1], B, n, m, lvl(l + 1), s);
+            launch_knn_xyz_counts(w.xyz[l], 4, w.xyz[l + 1], w.nidx, B, n, m, K, lvl(l), lvl(l + 1), s);
+            launch_paconv_group_counts(w.xyz[l], 4, w.feat[l], w.ldf[l], cprev, w.xyz[l + 1], w.nidx, Ein, ldE0, w.gdiff, B, n, m, K, lvl(l + 1), s);
+        } else {
+            launch_fps(w.xyz[l], 4, w.fidx, B, n, m, w.fps_tmp, s);
+            launch_gather_xyz(w.xyz[l], 4, w.fidx, w.xyz[l + 1], B, n, m, s);
+            launch_knn_xyz(w.xyz[l], 4, w.xyz[l + 1], w.nidx, B, n, m, K, s);
+            launch_paconv_group(w.xyz[l], 4, w.feat[l], w.ldf[l], cprev, w.xyz[l + 1], w.nidx, Ein, ldE0, w.gdiff, B, n, m, K, s);
+        }
         for (size_t j = 0; j < e.sa[l].size(); ++j) {
             const PaLayer& L = e.sa[l][j];
             launch_scorenet(w.gdiff, L.score_w, w.scores, edges, s);
@@ -187,11 +205,13 @@ static void paconv_forward(fc_paconv& e, const float* pts, float* out, int B, in
             launch_gemm(L.bank, &a, edges_pad, g, EPI_LINEAR, s);
             const bool last = j + 1 == e.sa[l].size();
             if (!last) {
-                launch_score_reduce(w.G, 8 * L.cout, w.scores, L.bn_s, L.bn_t, L.cout, K, Eout, e.sa[l][j + 1].bank.K_pad, 0, 0, B * m, s);
+                if (cnt) launch_score_reduce_counts(w.G, 8 * L.cout, w.scores, L.bn_s, L.bn_t, L.cout, K, Eout, e.sa[l][j + 1].bank.K_pad, 0, 0, B, m, lvl(l + 1), s);
+                else launch_score_reduce(w.G, 8 * L.cout, w.scores, L.bn_s, L.bn_t, L.cout, K, Eout, e.sa[l][j + 1].bank.K_pad, 0, 0, B * m, s);
                 std::swap(Ein, Eout);
             } else {
                 launch_fill(w.feat[l + 1], 0.f, (size_t)round_up(std::max(B * m, 1), ROW_PAD) * w.ldf[l + 1], s);
-                launch_score_reduce(w.G, 8 * L.cout, w.scores, L.bn_s, L.bn_t, L.cout, K, w.feat[l + 1], w.ldf[l + 1], 0, 1, B * m, s);
+                if (cnt) launch_score_reduce_counts(w.G, 8 * L.cout, w.scores, L.bn_s, L.bn_t, L.cout, K, w.feat[l + 1], w.ldf[l + 1], 0, 1, B, m, lvl(l + 1), s);
+                else launch_score_reduce(w.G, 8 * L.cout, w.scores, L.bn_s, L.bn_t, L.cout, K, w.feat[l + 1], w.ldf[l + 1], 0, 1, B * m, s);
             }
         }
         cprev = e.sa_out[l];
@@ -202,7 +222,8 @@ static void paconv_forward(fc_paconv& e, const float* pts, float* out, int B, in
         const int nu = w.n[i], mk = w.n[i + 1], rows = B * nu, rows_pad = round_up(std::max(rows, 1), ROW_PAD);
         const int c_skip = i == 0 ? e.c_feat : e.sa_out[i - 1];
         const int ldX = e.fp[i][0].lin.K_pad;
-        launch_three_nn_interp(w.xyz[i], 4, w.xyz[i + 1], 4, w.feat[i + 1], w.ldf[i + 1], c_known, w.feat[i], w.ldf[i], c_skip, w.X, ldX, B, nu, mk, s);
+        if (cnt) launch_three_nn_interp_counts(w.xyz[i], 4, w.xyz[i + 1], 4, w.feat[i + 1], w.ldf[i + 1], c_known, w.feat[i], w.ldf[i], c_skip, w.X, ldX, B, nu, mk, lvl(i), lvl(i + 1), s);
+        else launch_three_nn_interp(w.xyz[i], 4, w.xyz[i + 1], 4, w.feat[i + 1], w.ldf[i + 1], c_known, w.feat[i], w.ldf[i], c_skip, w.X, ldX, B, nu, mk, s);
         const float* cur = w.X;
         int ldcur = ldX;
         for (size_t j = 0; j < e.fp[i].size(); ++j) {
@@ -222,6 +243,7 @@ static void paconv_forward(fc_paconv& e, const float* pts, float* out, int B, in
     }
     // ---- head MLP on level 0
     run_head_mlp(e.head, {w.feat[0], w.ldf[0]}, w.h, w.otmp, out, B * M, w.P_pad, B * M, s);
+    if (cnt) launch_zero_tail_rows(out, e.head.E, B, M, *cnt, s);        // (the head ran on the pad rows too: [B, M, E] gets 0.0f there)
 }
 
 }  // namespace fc
@@ -250,8 +272,41 @@ int fc_paconv_workspace_bytes(const fc_paconv* emb, int32_t B, int32_t M, size_t
 int fc_paconv_embed_f32(fc_paconv* emb, const float* pts, float* out, int32_t B, int32_t M, void* workspace, size_t workspace_bytes, void* stream) {
     FC_API_BEGIN
     fc::embed_guarded(emb, workspace, "fc_paconv_embed_f32", (hipStream_t)stream, [=] {
-        fc::paconv_forward(*emb, pts, out, B, M, workspace, workspace_bytes, (hipStream_t)stream);
+        fc::paconv_forward(*emb, "fc_paconv_embed_f32", pts, nullptr, out, B, M, workspace, workspace_bytes, (hipStream_t)stream);
     });
+    FC_API_END
+}
+/* declared in fcflow_paconv_counts.h */
+int fc_paconv_embed_counts_f32(fc_paconv* emb, const float* pts, const int32_t* counts, int32_t count_min, int32_t count_max, float* out, int32_t B, int32_t M,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    FC_API_BEGIN
+    const fc::SceneCounts cnt{counts, count_min, count_max};
+    fc::embed_guarded(emb, workspace, "fc_paconv_embed_counts_f32", (hipStream_t)stream, [=] {
+        fc::paconv_forward(*emb, "fc_paconv_embed_counts_f32", pts, &cnt, out, B, M, workspace, workspace_bytes, (hipStream_t)stream);
+    });
+    FC_API_END
+}
+/* the engine's counted FPS launch on its own: xyz [B, n, 3], idx [B, m] with m = n >> 2 */
+int fc_op_fps_counts_f32(const float* xyz, const int32_t* counts, int32_t count_min, int32_t count_max, int32_t* idx, int32_t B, int32_t n, int32_t m, void* stream) {
+    FC_API_BEGIN
+    if (!xyz || !counts || !idx) throw fc::Error(FC_ERR_INVALID, "fc_op_fps_counts_f32: null pointer");
+    if (B < 1 || n < 4 || m != n >> 2) throw fc::Error(FC_ERR_INVALID, "fc_op_fps_counts_f32: bad argument (m must be n >> 2, n >= 4)");
+    if (count_min < 4 || count_min > count_max || count_max > n) throw fc::Error(FC_ERR_INVALID, "fc_op_fps_counts_f32: counts must satisfy 4 <= count_min <= count_max <= n");
+    float* scratch = nullptr;
+    const size_t nf = fc::fps_scratch_floats(B, n);
+    if (nf) FC_HIP(hipMallocAsync((void**)&scratch, nf * sizeof(float), (hipStream_t)stream));
+    try { fc::launch_fps_counts(xyz, 3, idx, B, n, m, scratch, fc::LevelCounts{counts, count_min, count_max, 0}, (hipStream_t)stream); }
+    catch (...) { if (scratch) (void)hipFreeAsync(scratch, (hipStream_t)stream); throw; }
+    if (scratch) FC_HIP(hipFreeAsync(scratch, (hipStream_t)stream));
+    FC_API_END
+}
+/* the engine's counted 32-NN launch on its own: xyz [B, n, 4], qxyz [B, m, 4], out [B, m, k]; counts_n in [1, n], counts_m in [0, m] (clamped) */
+int fc_op_paconv_knn_counts_f32(const float* xyz, const float* qxyz, const int32_t* counts_n, const int32_t* counts_m, int32_t* out, int32_t B, int32_t n, int32_t m,
+                                int32_t k, void* stream) {
+    FC_API_BEGIN
+    if (!xyz || !qxyz || !counts_n || !counts_m || !out) throw fc::Error(FC_ERR_INVALID, "fc_op_paconv_knn_counts_f32: null pointer");
+    if (B < 1 || n < 1 || m < 1 || k < 1) throw fc::Error(FC_ERR_INVALID, "fc_op_paconv_knn_counts_f32: bad argument");
+    fc::launch_knn_xyz_counts(xyz, 4, qxyz, out, B, n, m, k, fc::LevelCounts{counts_n, 1, n, 0}, fc::LevelCounts{counts_m, 0, m, 0}, (hipStream_t)stream);
     FC_API_END
 }
 

@@ -27,7 +27,7 @@ EXPORTS = list(abi.ENTRIES)          # every entry point include/fcflow.h declar
 # ... and those of the headers behind it (include/fcflow_attention_mass.h, fcflow_context_counts.h, fcflow_sparse_stage.h, fcflow_embed_counts.h,
 # fcflow_sparse_target.h)
 EXTRA_EXPORTS = list(abi.EXTRA_ENTRIES) + list(abi.COUNTS_ENTRIES) + list(abi.SPARSE_STAGE_ENTRIES) + list(abi.EMBED_COUNTS_ENTRIES) + \
-    list(abi.SPARSE_TARGET_ENTRIES)
+    list(abi.SPARSE_TARGET_ENTRIES) + list(abi.PACONV_COUNTS_ENTRIES)
 
 
 class FcTensor(ctypes.Structure):
@@ -448,7 +448,7 @@ class _EmbedderHandle(_Handle):
         out: a float32 tensor of the result's shape to write into (every element is written)."""
         if counts is not None and self.counts_entry is None:
             raise RuntimeError(f"{type(self).__name__}.embed: this embedder has no path with per-scene point counts (only the DGCNN engine has one): "
-                               "embed clouds of different sizes in groups of equal count")
+                               "embed clouds of different sizes in groups of equal count, or see PaconvHandle.embed_counts")
         B, M = pts.shape[0], pts.shape[1]
         cnt = None
         if counts is not None:
@@ -484,6 +484,28 @@ class PaconvHandle(_EmbedderHandle):
     def __init__(self, state_dict, version, device):
         super().__init__("fc_paconv", state_dict, version, device)
 
+    def embed_counts(self, pts, counts, count_range=None, out=None):
+        """The padded batch pts [B, M, C] and counts (integer GPU tensor [B], values in [256, M]) in ONE engine call
+        (fc_paconv_embed_counts_f32, include/fcflow_paconv_counts.h): scene b is pts[b, :counts[b]] and gets the bytes it gets when embedded
+        alone; rows >= counts[b] of the result [B, M, out_dim] are exact zeros, whatever pts holds there.  count_range and out as in embed.
+        Opt-in beside embed, whose counts= keeps refusing (counts_entry stays None): PointNet2SSGSeg.forward(context_counts=) comes here."""
+        B, M = pts.shape[0], pts.shape[1]
+        cnt, lo, hi = _context_counts_range(counts, B, M, self.device, "counts", count_range)
+        if lo < 256:
+            raise RuntimeError(f"PaconvHandle.embed_counts: count {lo} is below 256: the PAConv embedder needs at least 256 context points of every "
+                               "scene (four 4x farthest-point down-samplings)")
+        pts = _dev_f32(pts)
+        with torch.cuda.device(self.device):
+            ws = self._ws.query(self._entry("workspace_bytes"), self._h, B, M, device=self.device)
+            shape = (B, M, self.out_dim)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+                raise RuntimeError(f"embed_counts: out must be a contiguous float32 GPU tensor of shape {shape}")
+            self._entry("embed_counts_f32")(self._h, _ptr(pts), _ptr(cnt), lo, hi, _ptr(out), B, M, _ptr(ws), ws.numel(), _stream())
+            _keep_if_deferred(pts, cnt, out, ws)
+        return out
+
 
 # ---------------------------------------------------------------- single operators (unit-level parity tests)
 def op_fps(xyz, m):
@@ -493,6 +515,35 @@ def op_fps(xyz, m):
     with torch.cuda.device(xyz.device):
         lib().fc_op_fps_f32(_ptr(xyz), _ptr(idx), B, n, m, _stream())
     return idx
+
+
+def op_fps_counts(xyz, counts):
+    """op_fps with per-scene point counts, as the PAConv engine launches it (fc_op_fps_counts_f32): xyz [B, n, 3], counts integer GPU tensor [B]
+    with values in [4, n] -> int32 [B, n >> 2]; idx[b, :counts[b] >> 2] are op_fps's picks on xyz[b:b+1, :counts[b]], -1 behind them."""
+    B, n, _ = xyz.shape
+    cnt, lo, hi = _context_counts_range(counts, B, n, xyz.device, "counts")
+    xyz = _dev_f32(xyz)
+    idx = torch.empty(B, n >> 2, dtype=torch.int32, device=xyz.device)
+    with torch.cuda.device(xyz.device):
+        lib().fc_op_fps_counts_f32(_ptr(xyz), _ptr(cnt), lo, hi, _ptr(idx), B, n, n >> 2, _stream())
+    return idx
+
+
+def op_paconv_knn_counts(xyz, qxyz, counts_n, counts_m, k):
+    """The PAConv grouper's xyz k-NN with per-scene sizes (fc_op_paconv_knn_counts_f32): xyz [B, n, 4], qxyz [B, m, 4] (pitch 4), counts_n /
+    counts_m integer GPU tensors [B] in [1, n] / [1, m] -> int32 [B, m, k]; out[b, :counts_m[b]] is fc_op_paconv_knn_f32 on the scene alone,
+    rows behind it are zeros."""
+    B, n, _ = xyz.shape
+    m = qxyz.shape[1]
+    cn = _context_counts_range(counts_n, B, n, xyz.device, "counts_n")[0]
+    cm = _context_counts_range(counts_m, B, m, xyz.device, "counts_m")[0]
+    xyz, qxyz = _dev_f32(xyz), _dev_f32(qxyz)
+    if xyz.shape[2] != 4 or tuple(qxyz.shape) != (B, m, 4):
+        raise RuntimeError("op_paconv_knn_counts: xyz [B, n, 4] and qxyz [B, m, 4] (pitch 4)")
+    out = torch.empty(B, m, k, dtype=torch.int32, device=xyz.device)
+    with torch.cuda.device(xyz.device):
+        lib().fc_op_paconv_knn_counts_f32(_ptr(xyz), _ptr(qxyz), _ptr(cn), _ptr(cm), _ptr(out), B, n, m, k, _stream())
+    return out
 
 
 def stage_fps(pts, m, n_coord=None):

@@ -245,10 +245,11 @@ def _embed_batch(batch, models_dict, config, context_counts=None, what="inner_lo
     context_counts ([B] integer GPU tensor): scene b's context cloud is extract_0[b, :count_b], the rows behind it are padding.  In eval mode
     an embedder row depends on its own scene only.  A count-aware embedder (the DGCNN modules, `count_aware` True) takes the padded batch
     and the counts in ONE call (its forward's context_counts): scene b gets the bytes it gets alone, pad rows of the
-    embedding are exact zeros.  Any other embedder (PAConv, or count_aware = False) embeds the scenes in groups of equal count on the
-    unpadded clouds -- groups in ascending order of count, scene order kept inside a group -- with the embedder as it is (PAConv needs
-    count >= 256) and written into a zero-initialised [B, M, E]: one embedder call per DISTINCT count.  DGCNN needs count >= n_neighbors
-    either way.  The flow, more than 95 % of a step, runs once on the padded batch."""
+    embedding are exact zeros.  The PAConv module has the same path but is not count-aware by default: it is once
+    `embedder.count_aware = True` is set on the instance.  Any other embedder (PAConv as shipped, or count_aware = False) embeds the scenes
+    in groups of equal count on the unpadded clouds -- groups in ascending order of count, scene order kept inside a group -- with the
+    embedder as it is and written into a zero-initialised [B, M, E]: one embedder call per DISTINCT count.  DGCNN needs
+    count >= n_neighbors and PAConv count >= 256 either way.  The flow, more than 95 % of a step, runs once on the padded batch."""
     extract_0, extract_1, extra_context = batch
     Din = config["input_dim"]
     if context_counts is not None:
@@ -277,8 +278,8 @@ def _embed_batch(batch, models_dict, config, context_counts=None, what="inner_lo
 def inner_loop(batch, models_dict, config, eps=None, context_counts=None, target_counts=None):
     """model_initialization.py:206-228.  `eps` (optional) pins the augmenter noise.
     context_counts (optional, eval mode): an integer GPU tensor [B] -- scene b's context is extract_0[b, :count_b] (pad_context_batch builds
-    such a batch from clouds of different sizes); a DGCNN embedder takes the padded batch and the counts in one call, any other one is called
-    per group of equal count (_embed_batch); one flow call on the padded batch.
+    such a batch from clouds of different sizes); a count-aware embedder (DGCNN; PAConv with `count_aware = True` on the instance) takes the
+    padded batch and the counts in one call, any other one is called per group of equal count (_embed_batch); one flow call on the padded batch.
     target_counts (optional, eval mode, not with a sharded models_dict): an integer GPU tensor [B] with 1 <= n_b <= N --
     scene b's target is extract_1[b, :n_b] (pad_target_batch builds such a batch).  In eval mode a target point's log-prob depends on that point,
     its context and its own noise only, so the flow runs once on the padded batch: rows >= n_b of extract_1 are replaced by zeros first (whatever
@@ -459,8 +460,9 @@ def scene_change(cloud_0, cloud_1, models_dict, config, centers, ground_height=N
     min_context (an integer in [1, n_samples_context], eval mode) also evaluates voxels whose context box holds fewer
     than n_samples_context points: the validity mask becomes (c0_ctx >= min_context) & (c1_fin >= N) & (c0_fin >= N), both stagings are made
     with stage_scene's min_context (they share the context boxes, so the counts), and every inner_loop / dense_log_prob call passes its
-    voxels' counts as `context_counts`; the returned SceneStage carries them as `.context_counts`.  A DGCNN embedder then runs once per chunk, any
-    other one once per DISTINCT count of a chunk (_embed_batch), and its own minimum applies (DGCNN: n_neighbors points, PAConv: 256).
+    voxels' counts as `context_counts`; the returned SceneStage carries them as `.context_counts`.  A count-aware embedder (DGCNN; PAConv with
+    `count_aware = True` on the instance) then runs once per chunk, any other one once per DISTINCT count of a chunk (_embed_batch), and its own
+    minimum applies (DGCNN: n_neighbors points, PAConv: 256).
 
     min_target (an integer in [2, sample_size], eval mode) also evaluates voxels whose FINAL boxes hold fewer than
     sample_size points -- where something was removed, appeared in a nearly empty place, or the scene ends: the validity mask becomes

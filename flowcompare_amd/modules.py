@@ -573,9 +573,22 @@ class PointNet2SSGSeg(nn.Module):
             raise RuntimeError("flowcompare_amd: the HIP PAConv embedder implements eval-mode BatchNorm only; call .eval()")
         return _repacked(self, lambda key: _engine.PaconvHandle(self.state_dict(), key, next(self.parameters()).device))
 
-    def forward(self, pointcloud):
+    # count_aware: not set on the class, which model_initialization._embed_batch reads as False -- a padded batch with per-scene point counts is
+    # embedded in groups of equal count.  `embedder.count_aware = True` on an instance opts in to ONE engine call per batch (forward's
+    # context_counts).
+
+    def forward(self, pointcloud, context_counts=None, count_range=None):
         """pointcloud [B,M,3+c] (xyz first) -> [B,M,k].  In train() mode: the differentiable HIP path with BatchNorm batch statistics
-        (train_paconv.py); in eval() mode the fused inference engine (running statistics)."""
+        (train_paconv.py); in eval() mode the fused inference engine (running statistics).
+        context_counts (eval mode only; integer GPU tensor [B], values in [256, M]): scene b is pointcloud[b, :count_b] and gets bit for bit the
+        embedding it gets when passed alone; rows >= count_b of the result are exact zeros, whatever pointcloud holds there
+        (fc_paconv_embed_counts_f32).  count_range: (min, max) of the counts from a caller that has read them back already.  No autograd."""
+        if context_counts is not None:
+            if self.training:
+                raise RuntimeError("PAConv forward: context_counts is eval-mode only (the training path has no per-scene context point counts): "
+                                   "initialize_flow(mode='test') or .eval() on the flow and the embedder")
+            with torch.no_grad():
+                return self._engine().embed_counts(pointcloud, context_counts, count_range=count_range)
         if self.training:
             from . import train_paconv
             return train_paconv.paconv_embed(self, pointcloud)
